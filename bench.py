@@ -12,6 +12,13 @@ copies, the network scores them, 512 scores stay on the device.  With N GPUs eve
 own 128 images (weak scaling; N=8 is BASELINE configs[3], 1024 images) and ONE RCCL all-gather of
 the per-mask scores closes the step.  Inputs (images, label map, mask-vectors, weights) are
 resident in HBM before the timed region.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the line can
+carry -- the per-kernel profile step and `roofline`, the CPU baseline and the parity of the engine's
+scores against it (`cpu_baseline`, `parity`, `score_max_abs_delta`, `argmax_agree`) -- is measured
+only under --full; a plain run reports those fields as null.  --dump-outputs DIR writes what the last
+timed step computed (DIR/scores.npy, DIR/preds.npy; float32) for output-for-output comparison of two
+builds: the inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -30,6 +37,8 @@ sys.path.insert(0, ROOT)
 PEAK_F16_MFMA_TFLOPS = 2500.0   # MI355X dense fp16/bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
 F16X3_CEILING_TFLOPS = PEAK_F16_MFMA_TFLOPS / 3.0   # three MFMA products per algorithmic product
 PEAK_F32_MFMA_TFLOPS = 157.3    # exact-f32 MFMA (v_mfma_f32_16x16x4_f32), same guide: the pipe the reference's own arithmetic type would run on
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20240601     # --dump-outputs: the fixed sample of an output too large to write whole
 
 
 def parse(argv=None):
@@ -49,14 +58,23 @@ def parse(argv=None):
     ap.add_argument("--stem", choices=("table", "conv"), default=None,
                     help="how the masks are staged (MaskedForwardEngine(stem=...)): 'table' = the stem by superposition (the engine's default on the "
                          "ImageNet ResNets), 'conv' = K0 + the MFMA stem conv + max pool (rounds 1-3)")
-    ap.add_argument("--cpu-masks", type=int, default=16, help="masks of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-masks", type=int, default=16, help="masks of the CPU baseline sample (--full only; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: one profiled step after the timed region (`roofline`) "
+                         "and, at one rank, the CPU baseline and the engine-vs-CPU parity on its sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; %d MB at most in all, "
+                         "a fixed seeded sample of larger outputs)" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and run the all-gather even with one rank (rehearsal of the N>1 path)")
     ap.add_argument("--stub-step", action="store_true",
                     help="TEST HOOK, not a measurement: no GPU and no engine -- gloo on the CPU and a step that fills the rank's block of "
                          "scores with a function of the flat (image, mask) index; exercises the launcher, the rendezvous, the barrier / "
                          "max-over-ranks timing and the all-gather, and prints a line whose `data` says \"stub\" (tests/test_bench_launcher.py)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def pmc_traffic(arch, batch):
@@ -174,6 +192,23 @@ def cpu_baseline(arch, n_masks, eng=None):
                                                   "sample": "16 of the 64 masks"},
                                    "eight_threads": {"value": c1_8, "threads": min(8, all_threads), "seconds": dt_8, "gflops": c1_8 * gf18}}}
     return base, parity
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: 1-D tensor or array} -> DIR/<name>.npy in float32.  Outputs that together exceed DUMP_MAX_BYTES are cut to
+    the same fixed, seeded sample of positions (all of the same length), whose flat indices go to DIR/sample_index.npy (float64)."""
+    import numpy as np
+    arrays = {k: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v).reshape(-1).astype(np.float32) for k, v in arrays.items()}
+    n = max(a.size for a in arrays.values())
+    keep = (DUMP_MAX_BYTES - 4096) // (4 * len(arrays) + 8)        # 4 kB for the .npy headers
+    os.makedirs(dirname, exist_ok=True)
+    if n > keep:
+        assert all(a.size == n for a in arrays.values()), "a sampled dump needs outputs of one length"
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        np.save(os.path.join(dirname, "sample_index.npy"), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def _free_port():
@@ -300,6 +335,8 @@ def stub_main(args, rank, world):
     dt, _ms, out = timed_steps(step, fence, args.steps, args.warmup, use_dist, torch.device("cpu"), record_events=False)
     want = (torch.sin(torch.arange(total, dtype=torch.float64) * 0.37) * 0.5 + 0.5).to(torch.float32)
     assert out.numel() == total and bool((out == want).all()), "stub: gathered scores differ from the single-process values"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": out})
     if rank == 0:
         print(json.dumps({"metric": "masked-forward-passes/sec (stub)", "value": total * args.steps / dt, "unit": "masked-forward-passes/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -390,11 +427,16 @@ def main(argv=None):
     # HIP events on the launch stream brackets it for the GPU-side time
     dt, gpu_ms_timed, out = timed_steps(step, fence, args.steps, args.warmup, use_dist, dev)
     assert out.numel() == total and bool(torch.isfinite(out).all())
-    # per-kernel durations: ONE more step of the same work after the timed region, every launch bracketed by HIP events
+    if args.dump_outputs:
+        # what a caller of the step receives: the (gathered) scores and the argmax of every (image, mask), before anything else runs
+        all_preds = shard.all_gather_blocks(preds.view(-1).to(torch.float32), total) if use_dist else preds.view(-1)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"scores": out, "preds": all_preds})
+    # --full: per-kernel durations: ONE more step of the same work after the timed region, every launch bracketed by HIP events
     # on its stream (engine profile pool)
     prof = {"ms": {}, "launches": {}}
     batches_profiled = forwards_profiled = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         step_imgs = n_img
         rows = step_imgs * n_mask
         eng.profile(True)
@@ -418,10 +460,10 @@ def main(argv=None):
         bound["lib_stamp_matches_tree"] = bound["lib_stamp"] == g._source_hash(g.lib_sources(), g.HIPCC_FLAGS)
         if not bound["product_library"]:
             cfg_name = "custom (probe library)"
-        conv_ms, conv_n = prof["ms"]["conv"], prof["launches"]["conv"]
+        conv_ms, conv_n = prof["ms"].get("conv", 0.0), prof["launches"].get("conv", 0)
         flops_per_batch = eng.flops_per_forward * batch
         roofline = None
-        traffic_per_batch, traffic_source = pmc_traffic(args.arch, batch)
+        traffic_per_batch, traffic_source = pmc_traffic(args.arch, batch) if args.full else (None, None)
         if conv_n:
             # dominant kernel = conv_f16x3_kernel (all conv/fc launches).  achieved = algorithmic FLOPs
             # of the launches / their summed HIP-event durations; MFMA-issued FLOPs are 3x algorithmic.
@@ -467,11 +509,12 @@ def main(argv=None):
                        "lib_stamp_matches_tree": bound["lib_stamp_matches_tree"], "product_library": bound["product_library"],
                        "parallelism": "mask-batch shard x%d + one all_gather of scores" % world},
             "tflops_algorithmic": value * eng.flops_per_forward / 1e12,
+            "full": args.full,
             "roofline": roofline,
         }
-        # CPU baseline on rank 0 at N=1 only (bounded sample) -- and the metric's second half on the same masks: the engine's
+        # --full: CPU baseline on rank 0 at N=1 only (bounded sample) -- and the metric's second half on the same masks: the engine's
         # scores against the reference-style CPU loop
-        base, parity = cpu_baseline(args.arch, args.cpu_masks, eng) if (world == 1 and args.cpu_masks > 0) else (None, None)
+        base, parity = cpu_baseline(args.arch, args.cpu_masks, eng) if (args.full and world == 1 and args.cpu_masks > 0) else (None, None)
         line["cpu_baseline"] = base
         line["score_max_abs_delta"] = parity["score_max_abs_delta"] if parity else None
         line["argmax_agree"] = parity["argmax_agree"] if parity else None

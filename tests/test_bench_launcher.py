@@ -78,3 +78,48 @@ def test_world_size_mismatch_is_an_error():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub-step"], env=_env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"),
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_steps_gathered_scores(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned to its caller, as DIR/scores.npy in float32 (here the stub's gathered scores of
+    2 ranks); --full is accepted and changes nothing in the stub's line."""
+    import numpy as np
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--stub-step", "--images", "3", "--masks", "7", "--steps", "3", "--warmup", "0",
+                        "--full", "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _json_lines(r.stdout)[0]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0
+    got = np.load(d / "scores.npy")
+    want = (np.sin(np.arange(2 * 3 * 7, dtype=np.float64) * 0.37) * 0.5 + 0.5).astype(np.float32)
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+    assert sorted(p.name for p in d.iterdir()) == ["scores.npy"]
+
+
+def test_steps_below_one_is_an_error():
+    r = subprocess.run([sys.executable, BENCH, "--stub-step", "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_of_a_large_output_is_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """Outputs above DUMP_MAX_BYTES in all are cut to one seeded sample of positions, the same for every array and every run."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 10)
+    n = 100000
+    scores, preds = np.arange(n, dtype=np.float32) * 0.5, (np.arange(n) % 1000).astype(np.int32)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"scores": scores, "preds": preds})
+    total = sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir())
+    assert total <= 64 << 10
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    s, p = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "preds.npy")
+    assert s.dtype == p.dtype == np.float32 and len(s) == len(p) == len(idx)
+    assert np.array_equal(s, scores[idx.astype(np.int64)]) and np.array_equal(p, preds[idx.astype(np.int64)])
+    for f in ("sample_index.npy", "scores.npy", "preds.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), {"scores": scores[:100], "preds": preds[:100]})
+    assert sorted(p.name for p in small.iterdir()) == ["preds.npy", "scores.npy"]
+    assert np.array_equal(np.load(small / "preds.npy"), preds[:100].astype(np.float32))

@@ -12,7 +12,7 @@ python tools/layer_profile.py resnet101 $B 3 > $O/${R}_layers_resnet101_b$B.txt 
 MPX_FUSION_MASK=1 python tools/layer_profile.py resnet101 $B 3 > $O/${R}_layers_resnet101_b${B}_no_block_tails.txt 2>&1
 python tools/layer_profile.py resnet18 $B 3 > $O/${R}_layers_resnet18_b$B.txt 2>&1
 echo "layers done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --images 32 --steps 1 --warmup 1 --cpu-masks 0 > $O/${R}_bench_images32.json 2> $O/rocprof_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --full --images 32 --steps 1 --warmup 1 --cpu-masks 0 > $O/${R}_bench_images32.json 2> $O/rocprof_stats.err
 cp $(find $O/stats -name "*kernel_stats.csv" | sed -n 1p) $O/${R}_rocprofv3_kernel_stats_bench_images32_steps1.csv
 echo "stats done"
 for A in resnet101 resnet18; do
@@ -28,12 +28,12 @@ cp $O/${R}_pmc_traffic_b$B.json $O/${R}_pmc_traffic_resnet18_b$B.json profiles/ 
 # power and clock next to the bench (one sample per second while it runs)
 ( while true; do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "sclk|mclk|Power \(W\)" | tr '\n' ';'; echo; sleep 1; done ) > $O/${R}_rocm_smi_during_bench.txt &
 SMI=$!
-python bench.py > $O/${R}_bench_n1.json 2> $O/bench.err
+python bench.py --full > $O/${R}_bench_n1.json 2> $O/bench.err
 kill $SMI
 cat $O/${R}_bench_n1.json
-python bench.py --arch resnet18 --images 32 --masks 256 --steps 8 --warmup 2 --cpu-masks 0 > $O/${R}_bench_cfg2_resnet18.json 2> $O/bench18.err
+python bench.py --full --arch resnet18 --images 32 --masks 256 --steps 8 --warmup 2 --cpu-masks 0 > $O/${R}_bench_cfg2_resnet18.json 2> $O/bench18.err
 cat $O/${R}_bench_cfg2_resnet18.json
-python bench.py --force-dist --images 16 --steps 1 --warmup 1 --cpu-masks 0 > $O/${R}_force_dist_rehearsal.txt 2>&1
+python bench.py --full --force-dist --images 16 --steps 1 --warmup 1 --cpu-masks 0 > $O/${R}_force_dist_rehearsal.txt 2>&1
 tail -2 $O/${R}_force_dist_rehearsal.txt
 python tools/latency_bench.py resnet101 10 2>&1 | grep -v amdgpu.ids > $O/${R}_latency_cfg5.txt
 cat $O/${R}_latency_cfg5.txt

@@ -114,8 +114,8 @@ int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has wei
  *  12 = the patch kernel (6) as ONE persistent workgroup per CU: weight ring and patch buffers run on across tiles, register
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
  * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default.  (Ids 3, 5, 8 and 11 of
- * earlier rounds -- kernels that were measured and never became a default -- exist only in probe builds,
- * tools/probes/build_experimental.sh.)  A non-default tile on a layer of a block tail makes mpx_forward run that block layer by
+ * earlier rounds -- kernels that were measured and never became a default -- were removed; commit e4ccec8 is the last that has
+ * them.)  A non-default tile on a layer of a block tail makes mpx_forward run that block layer by
  * layer (mpx_bottleneck_tail). */
 int mpx_set_conv_tile(mpx_engine* h, int i, int tile);
 int mpx_get_conv_tile(const mpx_engine* h, int i);

@@ -10,13 +10,6 @@
 #include "mpx_convw.h"
 #include "mpx_btail.h"
 #include "mpx_stemtab.h"
-#ifdef MPX_EXPERIMENTAL
-// Kernels that were measured in the network and did not become any layer class's default: tile ids 3 and 5 (other
-// shapes of the generic kernel), 8 (persistent kernel with a register epilogue) and 11 (pixel-stationary expanding 1x1 kernel).
-// They live under tools/probes/experimental/ and are compiled into probe builds only (tools/probes/build_experimental.sh).
-#include "../../tools/probes/experimental/mpx_convp.h"
-#include "../../tools/probes/experimental/mpx_convs.h"
-#endif
 
 #include <algorithm>
 #include <cmath>
@@ -27,7 +20,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 using namespace mpx;
@@ -519,161 +511,51 @@ struct ProfScope {
     }
 };
 
-// tile id (mpx_set_conv_tile) of a shape of the generic kernel
-template <class Cfg>
-constexpr int tile_id_of() {
-    return std::is_same<Cfg, ConvTile0>::value ? 0 : std::is_same<Cfg, ConvTile1>::value ? 1 : std::is_same<Cfg, ConvTile2>::value ? 2 :
-           std::is_same<Cfg, ConvTile4>::value ? 4 : std::is_same<Cfg, ConvTile7>::value ? 7 : 31;       // 31: a probe build's shape
-}
+// ---- conv dispatch ----------------------------------------------------------------------------------------------------------------
+// A layer's conv kernel is a tile id (mpx_set_conv_tile).  kTiles below holds one row per product id; a launcher is handed the id whose
+// bit of mpx_last_conv_kernels it sets when its own kernel runs, and falls back to other rows by id.
 
-template <class Cfg, bool DUAL = false>
-int launch_conv_tile(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = (p.cout + Cfg::TC - 1) / Cfg::TC;     // weights are padded to cout_pad >= n_tiles_c * TC rows
-    if (p.n_tiles_c * Cfg::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const int n_tiles_p = (p.M + Cfg::TP - 1) / Cfg::TP;
-    const long long nblocks = (long long)n_tiles_p * p.n_tiles_c;
-    if (nblocks <= 0 || nblocks > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    if (DUAL && (((p.k1 >> 5) - Cfg::NSX) < 0 || (((p.k1 >> 5) - Cfg::NSX) & 1)))
-        return fail(h, MPX_E_INTERNAL, "dual conv: k1/32 - ring depth must be even and >= 0");
-    hipLaunchKernelGGL((conv_f16x3_kernel<Cfg, DUAL>), dim3((unsigned)nblocks), dim3(Cfg::NT), Cfg::LDS, st, p);
+typedef int (*LaunchFn)(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st);
+int launch_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st);
+
+// a kernel of tile `id` was launched: the launch error, else bit `id` of mpx_last_conv_kernels
+int launched(mpx_engine* h, int id) {
     MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << tile_id_of<Cfg>();
+    h->last_kernels |= 1u << id;
     return 0;
 }
 
-#ifdef MPX_EXPERIMENTAL
-// Persistent kernel (mpx_convp.h, tile id 8 = the 128x128 4-wave tile): a fixed grid of
-// MINB-per-CU workgroups walks all tiles.
-template <class Cfg, bool DUAL = false>
-int launch_convp_tile(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = (p.cout + Cfg::TC - 1) / Cfg::TC;
-    if (p.n_tiles_c * Cfg::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const int n_tiles_p = (p.M + Cfg::TP - 1) / Cfg::TP;
-    const long long n_tiles = (long long)n_tiles_p * p.n_tiles_c;
-    if (n_tiles <= 0 || n_tiles > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    if (DUAL && (((p.k1 >> 5) - Cfg::NSX) < 0 || (((p.k1 >> 5) - Cfg::NSX) & 1)))
-        return fail(h, MPX_E_INTERNAL, "dual conv: k1/32 - ring depth must be even and >= 0");
-    p.n_tiles = (int)n_tiles;
-    const int wg_per_cu = (160 * 1024) / Cfg::RING < Cfg::MINB * 256 / Cfg::NT ? (160 * 1024) / Cfg::RING : Cfg::MINB * 256 / Cfg::NT;
-    const long long resident = (long long)h->num_cus * (wg_per_cu > 0 ? wg_per_cu : 1);     // a multiple of 8 (256 CUs)
-    const unsigned grid = (unsigned)(n_tiles < resident ? n_tiles : resident);
-    hipLaunchKernelGGL((convp_f16x3_kernel<Cfg, DUAL>), dim3(grid), dim3(Cfg::NT), Cfg::RING, st, p);
-    MPX_HIP(h, hipGetLastError());
+// p.n_tiles_c and the number of TC x TP tiles of a launch (`tiles`), which must fit the packed weight rows and a 32-bit grid
+int conv_tiles(mpx_engine* h, ConvParams& p, int cout_pad, int TC, int TP, long long& tiles) {
+    p.n_tiles_c = (p.cout + TC - 1) / TC;     // weights are padded to cout_pad >= n_tiles_c * TC rows
+    if (p.n_tiles_c * TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
+    tiles = ((long long)p.M + TP - 1) / TP * p.n_tiles_c;
+    if (tiles <= 0 || tiles > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
     return 0;
 }
 
-#endif
+// Grid of a persistent kernel: one workgroup per CU, a multiple of 8 (XCD classes) and of n_tiles_c (a workgroup keeps its cout tile);
+// 0 when the tiles do not fill one such unit.  Each launcher keeps its own threshold under which smaller tiles win.
+long long persistent_grid(const mpx_engine* h, const ConvParams& p, long long tiles) {
+    const int c = p.n_tiles_c, unit = 8 > c ? (8 % c == 0 ? 8 : 8 * c) : (c % 8 == 0 ? c : 8 * c);
+    return std::min<long long>(h->num_cus, tiles) / unit * unit;
+}
 
+// Eligibility predicates judge a layer's descriptor (default_tile sees nothing else; eligible() below adds what only the layer knows).
 // 256x256 tile (mpx_conv256.h, tile id 9): 1x1 stride-1 layers whose cout is a multiple of 256 and whose K is a multiple of 64
-bool conv256_eligible(const ConvLayer& L) {
-    return !L.is_fc && !L.is_stem && L.d.ksize == 1 && L.d.stride == 1 && L.d.pad == 0 && L.cout_store % 256 == 0 &&
-           L.cin_pad % 64 == 0 && L.cin_pad == L.d.cin;
+bool conv256_eligible(const mpx_conv_desc& d) {
+    return d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.cout % 256 == 0 && d.cin % 64 == 0;
 }
 
-// persistent expanding-1x1 kernel (mpx_convx.h, tile id 10): as tile 9 plus K >= 128; a launch with fewer tiles than one grid
-// unit (8 or n_tiles_c workgroups) runs on the 128x128 kernel instead
-bool convx_eligible(const ConvLayer& L) { return conv256_eligible(L) && L.cin_pad >= 128; }
-
-int launch_convx(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = p.cout / ConvX::TC;
-    if (p.n_tiles_c * ConvX::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const long long n_tiles_p = ((long long)p.M + ConvX::TP - 1) / ConvX::TP;
-    const long long total = n_tiles_p * p.n_tiles_c;
-    if (total <= 0 || total > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    // one workgroup per CU; the grid must be a multiple of 8 (XCD classes) and of n_tiles_c (a workgroup keeps its cout tile)
-    long long grid = h->num_cus;
-    if (total < grid) grid = total;
-    const int unit = 8 > p.n_tiles_c ? (8 % p.n_tiles_c == 0 ? 8 : 8 * p.n_tiles_c) : (p.n_tiles_c % 8 == 0 ? p.n_tiles_c : 8 * p.n_tiles_c);
-    grid = grid / unit * unit;
-    // less than one round of tiles (small batches: one image's window table, a BO round): the persistent walk would serialise the
-    // tiles that do not fill a grid unit, and half-empty CUs gain more from tiles a quarter of the size -- the 128x128 kernel, which
-    // sums in the same order (bit-identical).  tools/layer_profile.py, conv ms per forward: batch 29 8.24 -> 3.92, 118 10.28 -> 6.78,
-    // 211 13.50 -> 11.62 with this rule on the three persistent kernels
-    if (grid <= 0 || total < h->num_cus) return launch_conv_tile<ConvTile7>(h, p, cout_pad, st);
-    hipLaunchKernelGGL(convx_f16x3_kernel, dim3((unsigned)grid), dim3(ConvX::NT), ConvX::LDS, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 10;
-    return 0;
-}
+// persistent expanding-1x1 kernel (mpx_convx.h, tile id 10): as tile 9 plus K >= 128
+bool convx_eligible(const mpx_conv_desc& d) { return conv256_eligible(d) && d.cin >= 128; }
 
 // weights-in-registers expanding-1x1 kernel (mpx_convw.h, tile id 14): tile 10's layers with K = 256 exactly (a wave keeps the
-// 64 x 256 x (hi + lo) weights of its channels in 256 VGPRs); under one round of tiles the 128x128 kernel, as launch_convx
-bool convw_eligible(const ConvLayer& L) { return conv256_eligible(L) && L.cin_pad == ConvW::K; }
+// 64 x 256 x (hi + lo) weights of its channels in 256 VGPRs)
+bool convw_eligible(const mpx_conv_desc& d) { return conv256_eligible(d) && d.cin == ConvW::K; }
 
-int launch_convw(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    if (p.ktot != ConvW::K) return fail(h, MPX_E_INTERNAL, "convw: K = %d (the kernel holds K = %d in registers)", p.ktot, ConvW::K);
-    // The kernel serves what every layer it is the default for asks of it and what the parity tests cover: the residual add + ReLU of a block's
-    // last conv.  A call through mpx_conv_bn_act WITHOUT a residual or (no such layer exists in the networks) without ReLU takes tile 10's
-    // kernel, which sums in the same order: only <K, RELU = true> is instantiated (ADVICE r5: the <false> and null-residual paths had no test).
-    if (!p.relu || !p.r_hi) return launch_convx(h, p, cout_pad, st);
-    p.n_tiles_c = p.cout / ConvW::TC;
-    if (p.n_tiles_c * ConvW::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const long long n_tiles_p = ((long long)p.M + ConvW::TP - 1) / ConvW::TP;
-    const long long total = n_tiles_p * p.n_tiles_c;
-    if (total <= 0 || total > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    long long grid = h->num_cus;
-    if (total < grid) grid = total;
-    const int unit = 8 > p.n_tiles_c ? (8 % p.n_tiles_c == 0 ? 8 : 8 * p.n_tiles_c) : (p.n_tiles_c % 8 == 0 ? p.n_tiles_c : 8 * p.n_tiles_c);
-    grid = grid / unit * unit;
-    if (grid <= 0 || total < 2LL * h->num_cus) return launch_conv_tile<ConvTile7>(h, p, cout_pad, st);
-    // (the kernel is a template over K; K = 128 -- 128 -> 512 on 28 x 28 maps -- was built and measured in round 5: parity green, bit-equal to tile 10, and a
-    // tie with it, 7.26 against 7.19 ms for the four layers: two stages of the epilogue slice per MFMA gap do not hide any more.  Only K = 256 is instantiated.)
-    hipLaunchKernelGGL((convw_f16x3_kernel<ConvW::K, true>), dim3((unsigned)grid), dim3(ConvW::NT), ConvW::LDS, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 14;
-    return 0;
-}
-
-#ifdef MPX_EXPERIMENTAL
-// X-stationary expanding-1x1 kernel (mpx_convs.h, tile id 11): 1x1 stride-1 layers with cout % 256 == 0 and K = 128 or 256
-bool convs_eligible(const ConvLayer& L) { return conv256_eligible(L) && (L.cin_pad == 128 || L.cin_pad == 256); }
-
-int launch_convs(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = p.cout / ConvS::TC;
-    if (p.n_tiles_c * ConvS::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const long long n_pt = ((long long)p.M + ConvS::TP - 1) / ConvS::TP;
-    if (n_pt <= 0 || n_pt > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    const long long grid = n_pt < h->num_cus ? n_pt : h->num_cus;         // one persistent workgroup per CU
-    hipLaunchKernelGGL(convs_f16x3_kernel, dim3((unsigned)grid), dim3(ConvS::NT), ConvS::LDS, st, p);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
-}
-
-#endif
-
-int launch_conv256(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = p.cout / Conv256::TC;
-    if (p.n_tiles_c * Conv256::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const int n_tiles_p = (p.M + Conv256::TP - 1) / Conv256::TP;
-    const long long nblocks = (long long)n_tiles_p * p.n_tiles_c;
-    if (nblocks <= 0 || nblocks > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    hipLaunchKernelGGL(conv256_f16x3_kernel, dim3((unsigned)nblocks), dim3(Conv256::NT), Conv256::LDS, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 9;
-    return 0;
-}
-
-// persistent 256x256 kernel (mpx_conv256p.h, tile id 13): tile 9's layers without a residual operand; a launch with fewer tiles than
-// one grid unit (8 or n_tiles_c workgroups) runs on the 256x256 kernel itself (same bits)
-bool conv256p_eligible(const ConvLayer& L) { return conv256_eligible(L) && !L.d.residual; }
-
-int launch_conv256p(mpx_engine* h, ConvParams& p, int cout_pad, hipStream_t st) {
-    p.n_tiles_c = p.cout / Conv256P::TC;
-    if (p.n_tiles_c * Conv256P::TC > cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    const long long n_tiles_p = ((long long)p.M + Conv256P::TP - 1) / Conv256P::TP;
-    const long long total = n_tiles_p * p.n_tiles_c;
-    if (total <= 0 || total > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    long long grid = h->num_cus;
-    if (total < grid) grid = total;
-    const int unit = 8 > p.n_tiles_c ? (8 % p.n_tiles_c == 0 ? 8 : 8 * p.n_tiles_c) : (p.n_tiles_c % 8 == 0 ? p.n_tiles_c : 8 * p.n_tiles_c);
-    grid = grid / unit * unit;
-    if (p.r_hi) return launch_conv256(h, p, cout_pad, st);
-    if (grid <= 0 || total < h->num_cus) return launch_conv_tile<ConvTile2>(h, p, cout_pad, st);      // under one round: smaller tiles (launch_convx)
-    hipLaunchKernelGGL(conv256p_f16x3_kernel, dim3((unsigned)grid), dim3(Conv256P::NT), Conv256P::LDS, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 13;
-    return 0;
-}
+// persistent 256x256 kernel (mpx_conv256p.h, tile id 13): tile 9's layers without a residual operand
+bool conv256p_eligible(const mpx_conv_desc& d) { return conv256_eligible(d) && !d.residual; }
 
 // Rows of the largest input patch any TP-pixel tile of an HxH map needs (mpx_conv3p.h), rounded up to 16.
 int patch_rows_needed(int H, int TP) {
@@ -701,23 +583,8 @@ bool patch_eligible(const mpx_conv_desc& d) {
     return d.cout <= 64 ? patch_fits<PatchTile1>(d) : (patch_fits<PatchTile0>(d) || patch_fits<PatchTile2>(d));
 }
 
-template <class PC>
-int launch_conv_patch(mpx_engine* h, ConvParams& p, const mpx_conv_desc& d, hipStream_t st) {
-    p.n_tiles_c = (p.cout + PC::TC - 1) / PC::TC;
-    if (p.n_tiles_c * PC::TC > d.cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    p.patch_rows = patch_rows_needed(d.hin, PC::TP);
-    const int lds = PC::lds_bytes(p.patch_rows);
-    const int n_tiles_p = (p.M + PC::TP - 1) / PC::TP;
-    const long long nblocks = (long long)n_tiles_p * p.n_tiles_c;
-    if (nblocks <= 0 || nblocks > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    hipLaunchKernelGGL(conv3x3p_f16x3_kernel<PC>, dim3((unsigned)nblocks), dim3(PC::NT), lds, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 6;
-    return 0;
-}
-
 // persistent patch kernel (mpx_conv3pp.h, tile id 12): the patch kernel's layers with cout >= 128 and no residual whose LDS image leaves 1 KB for the
-// cout tile's scale / shift vectors; a launch with fewer tiles than one grid unit runs on the patch kernel itself (same bits)
+// cout tile's scale / shift vectors
 template <class PC>
 bool patchp_fits(const mpx_conv_desc& d) {
     return d.cout >= 128 && !d.residual && patch_fits<PC>(d) && PatchPersistent<PC>::lds_bytes(patch_rows_needed(d.hin, PC::TP)) <= kLdsLimit;
@@ -725,27 +592,179 @@ bool patchp_fits(const mpx_conv_desc& d) {
 
 bool patchp_eligible(const mpx_conv_desc& d) { return patchp_fits<PatchTile0>(d) || patchp_fits<PatchTile2>(d); }
 
+// The generic kernel (mpx_conv.h) on tile Cfg.  With DUAL, a launch whose params carry a K-concatenated second operand (p.k1 > 0,
+// launch_conv_fused) runs the dual-operand instantiation.
+template <class Cfg, bool DUAL = false>
+int launch_conv_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, Cfg::TC, Cfg::TP, tiles)) return rc;
+    if constexpr (DUAL) {
+        if (p.k1) {
+            if (((p.k1 >> 5) - Cfg::NSX) < 0 || (((p.k1 >> 5) - Cfg::NSX) & 1))
+                return fail(h, MPX_E_INTERNAL, "dual conv: k1/32 - ring depth must be even and >= 0");
+            hipLaunchKernelGGL((conv_f16x3_kernel<Cfg, true>), dim3((unsigned)tiles), dim3(Cfg::NT), Cfg::LDS, st, p);
+            return launched(h, id);
+        }
+    }
+    hipLaunchKernelGGL((conv_f16x3_kernel<Cfg>), dim3((unsigned)tiles), dim3(Cfg::NT), Cfg::LDS, st, p);
+    return launched(h, id);
+}
+
+int launch_conv256(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, Conv256::TC, Conv256::TP, tiles)) return rc;
+    hipLaunchKernelGGL(conv256_f16x3_kernel, dim3((unsigned)tiles), dim3(Conv256::NT), Conv256::LDS, st, p);
+    return launched(h, id);
+}
+
+// a residual operand runs on the 256x256 kernel itself, under one round of tiles the 128x128 kernel (same bits, as launch_convx)
+int launch_conv256p(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (p.r_hi) return launch_tile(h, 9, L, p, st);
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, Conv256P::TC, Conv256P::TP, tiles)) return rc;
+    const long long grid = persistent_grid(h, p, tiles);
+    if (grid <= 0 || tiles < h->num_cus) return launch_tile(h, 2, L, p, st);
+    hipLaunchKernelGGL(conv256p_f16x3_kernel, dim3((unsigned)grid), dim3(Conv256P::NT), Conv256P::LDS, st, p);
+    return launched(h, id);
+}
+
+int launch_convx(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, ConvX::TC, ConvX::TP, tiles)) return rc;
+    const long long grid = persistent_grid(h, p, tiles);
+    // less than one round of tiles (small batches: one image's window table, a BO round): the persistent walk would serialise the
+    // tiles that do not fill a grid unit, and half-empty CUs gain more from tiles a quarter of the size -- the 128x128 kernel, which
+    // sums in the same order (bit-identical).  tools/layer_profile.py, conv ms per forward: batch 29 8.24 -> 3.92, 118 10.28 -> 6.78,
+    // 211 13.50 -> 11.62 with this rule on the three persistent kernels
+    if (grid <= 0 || tiles < h->num_cus) return launch_tile(h, 7, L, p, st);
+    hipLaunchKernelGGL(convx_f16x3_kernel, dim3((unsigned)grid), dim3(ConvX::NT), ConvX::LDS, st, p);
+    return launched(h, id);
+}
+
+// under two rounds of tiles the 128x128 kernel, as launch_convx
+int launch_convw(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (p.ktot != ConvW::K) return fail(h, MPX_E_INTERNAL, "convw: K = %d (the kernel holds K = %d in registers)", p.ktot, ConvW::K);
+    // The kernel serves what every layer it is the default for asks of it and what the parity tests cover: the residual add + ReLU of a block's
+    // last conv.  A call through mpx_conv_bn_act WITHOUT a residual or (no such layer exists in the networks) without ReLU takes tile 10's
+    // kernel, which sums in the same order: only <K, RELU = true> is instantiated (ADVICE r5: the <false> and null-residual paths had no test).
+    if (!p.relu || !p.r_hi) return launch_tile(h, 10, L, p, st);
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, ConvW::TC, ConvW::TP, tiles)) return rc;
+    const long long grid = persistent_grid(h, p, tiles);
+    if (grid <= 0 || tiles < 2LL * h->num_cus) return launch_tile(h, 7, L, p, st);
+    // (the kernel is a template over K; K = 128 -- 128 -> 512 on 28 x 28 maps -- was built and measured in round 5: parity green, bit-equal to tile 10, and a
+    // tie with it, 7.26 against 7.19 ms for the four layers: two stages of the epilogue slice per MFMA gap do not hide any more.  Only K = 256 is instantiated.)
+    hipLaunchKernelGGL((convw_f16x3_kernel<ConvW::K, true>), dim3((unsigned)grid), dim3(ConvW::NT), ConvW::LDS, st, p);
+    return launched(h, id);
+}
+
 template <class PC>
-int launch_conv_patchp(mpx_engine* h, ConvParams& p, const mpx_conv_desc& d, hipStream_t st) {
-    p.n_tiles_c = (p.cout + PC::TC - 1) / PC::TC;
-    if (p.n_tiles_c * PC::TC > d.cout_pad) return fail(h, MPX_E_ARG, "conv tile exceeds the packed weight rows");
-    p.patch_rows = patch_rows_needed(d.hin, PC::TP);
-    const int lds = PatchPersistent<PC>::lds_bytes(p.patch_rows);
-    const long long n_tiles_p = ((long long)p.M + PC::TP - 1) / PC::TP;
-    const long long total = n_tiles_p * p.n_tiles_c;
-    if (total <= 0 || total > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
-    // one workgroup per CU; the grid is a multiple of 8 (XCD classes) and of n_tiles_c (a workgroup keeps its cout tile)
-    long long grid = h->num_cus;
-    if (total < grid) grid = total;
-    const int unit = 8 > p.n_tiles_c ? (8 % p.n_tiles_c == 0 ? 8 : 8 * p.n_tiles_c) : (p.n_tiles_c % 8 == 0 ? p.n_tiles_c : 8 * p.n_tiles_c);
-    grid = grid / unit * unit;
+int launch_conv_patch(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, PC::TC, PC::TP, tiles)) return rc;
+    p.patch_rows = patch_rows_needed(L.d.hin, PC::TP);
+    hipLaunchKernelGGL(conv3x3p_f16x3_kernel<PC>, dim3((unsigned)tiles), dim3(PC::NT), PC::lds_bytes(p.patch_rows), st, p);
+    return launched(h, id);
+}
+
+// under one round of tiles, with a residual operand or past 2^23 padded pixels the patch kernel of the same tile (tile 6, same bits)
+template <class PC>
+int launch_conv_patchp(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, PC::TC, PC::TP, tiles)) return rc;
+    const long long grid = persistent_grid(h, p, tiles);
     // (the kernel divides pixel and padded-pixel indices with a float reciprocal: exact below 2^23)
-    const long long padded = (long long)(p.M / (d.hin * d.hin) + 2) * (d.hin + 2) * (d.hin + 2);
-    if (grid <= 0 || total < h->num_cus || p.r_hi || padded >= (1 << 23)) return launch_conv_patch<PC>(h, p, d, st);     // under one round: a workgroup per tile
-    hipLaunchKernelGGL(conv3x3pp_f16x3_kernel<PC>, dim3((unsigned)grid), dim3(PC::NT), lds, st, p);
-    MPX_HIP(h, hipGetLastError());
-    h->last_kernels |= 1u << 12;
-    return 0;
+    const int H = L.d.hin;
+    const long long padded = (long long)(p.M / (H * H) + 2) * (H + 2) * (H + 2);
+    if (grid <= 0 || tiles < h->num_cus || p.r_hi || padded >= (1 << 23)) return launch_conv_patch<PC>(h, 6, L, p, st);
+    p.patch_rows = patch_rows_needed(H, PC::TP);
+    hipLaunchKernelGGL(conv3x3pp_f16x3_kernel<PC>, dim3((unsigned)grid), dim3(PC::NT), PatchPersistent<PC>::lds_bytes(p.patch_rows), st, p);
+    return launched(h, id);
+}
+
+int launch_patch(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (L.d.cout <= 64) return launch_conv_patch<PatchTile1>(h, id, L, p, st);
+    return patch_fits<PatchTile0>(L.d) ? launch_conv_patch<PatchTile0>(h, id, L, p, st) : launch_conv_patch<PatchTile2>(h, id, L, p, st);
+}
+
+int launch_patchp(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    return patchp_fits<PatchTile0>(L.d) ? launch_conv_patchp<PatchTile0>(h, id, L, p, st) : launch_conv_patchp<PatchTile2>(h, id, L, p, st);
+}
+
+struct TileRow {
+    int id;
+    LaunchFn launch;
+    bool (*eligible)(const mpx_conv_desc&);     // nullptr: every layer
+    const char* refusal;                        // why mpx_set_conv_tile refuses a layer that is not eligible
+    int dual;       // the tile whose DUAL kernel (launch_conv_tile<Cfg, true>) runs the layer fused with its downsample conv; -1: none
+    bool split;     // the images behind the last whole round of tiles go to tile 2 (launch_conv)
+};
+
+// The product tile ids: every id default_tile hands out (include/mpx.h, mpx_set_conv_tile).
+const TileRow kTiles[] = {
+    {0, launch_conv_tile<ConvTile0>, nullptr, nullptr, -1, false},
+    {1, launch_conv_tile<ConvTile1>, nullptr, nullptr, -1, false},
+    {2, launch_conv_tile<ConvTile2, true>, nullptr, nullptr, 2, false},
+    {4, launch_conv_tile<ConvTile4>, nullptr, nullptr, -1, false},
+    {6, launch_patch, patch_eligible, "the patch kernel needs a 3x3 stride-1 layer whose input patch fits the LDS", -1, false},
+    {7, launch_conv_tile<ConvTile7, true>, nullptr, nullptr, 7, false},
+    {9, launch_conv256, conv256_eligible, "the 256x256 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin % 64 == 0", -1, true},
+    {10, launch_convx, convx_eligible,
+     "the persistent expanding-1x1 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin % 64 == 0, cin >= 128", 7, false},
+    {12, launch_patchp, patchp_eligible,
+     "the persistent patch kernel needs a 3x3 stride-1 layer with cout >= 128 and no residual operand whose input patch fits the LDS", -1, false},
+    {13, launch_conv256p, conv256p_eligible,
+     "the persistent 256x256 kernel runs 1x1 stride-1 layers with cout % 256 == 0, cin % 64 == 0 and no residual operand", -1, true},
+    {14, launch_convw, convw_eligible,
+     "the weights-in-registers expanding-1x1 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin = 256", 7, false},
+};
+
+// Dynamic LDS ceiling of every conv kernel (mpx_create): the kernels of kTiles with their DUAL forms, the stem + pool kernel, the block
+// tails; the patch kernels size their LDS per layer.
+struct KernelLds {
+    const void* kernel;
+    int bytes;
+};
+const KernelLds kKernelLds[] = {
+    {(const void*)conv_f16x3_kernel<ConvTile0>, ConvTile0::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile1>, ConvTile1::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile1, false, true>, ConvTile1::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile2>, ConvTile2::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile7>, ConvTile7::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile2, true>, ConvTile2::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile7, true>, ConvTile7::LDS},
+    {(const void*)conv256_f16x3_kernel, Conv256::LDS},
+    {(const void*)convx_f16x3_kernel, ConvX::LDS},
+    {(const void*)convw_f16x3_kernel<ConvW::K, true>, ConvW::LDS},
+    {(const void*)conv256p_f16x3_kernel, Conv256P::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile4>, ConvTile4::LDS},
+    {(const void*)btail_f16x3_kernel<BtResC64>, BtResC64::LDS},
+    {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
+    {(const void*)btail_f16x3_kernel<BtDualC64>, BtDualC64::LDS},
+    {(const void*)btail_f16x3_kernel<BtHeadC64>, BtHeadC64::LDS},
+    {(const void*)conv3x3p_f16x3_kernel<PatchTile0>, kLdsLimit},
+    {(const void*)conv3x3p_f16x3_kernel<PatchTile1>, kLdsLimit},
+    {(const void*)conv3x3p_f16x3_kernel<PatchTile2>, kLdsLimit},
+    {(const void*)conv3x3pp_f16x3_kernel<PatchTile0>, kLdsLimit},
+    {(const void*)conv3x3pp_f16x3_kernel<PatchTile2>, kLdsLimit},
+};
+
+const TileRow* find_tile(int id) {
+    for (const TileRow& r : kTiles)
+        if (r.id == id) return &r;
+    return nullptr;
+}
+
+// Layer L may run row r's kernel.  The predicates see the descriptor, whose cin is the channels per input pixel except in the small
+// networks' planes, padded to 32 (cin_pad); the stem and the fc read planes of their own.
+bool eligible(const TileRow& r, const ConvLayer& L) {
+    return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && r.eligible(L.d));
+}
+
+int launch_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    const TileRow* r = find_tile(id);
+    if (!r) return fail(h, MPX_E_INTERNAL, "conv: no kernel for tile id %d", id);
+    return r->launch(h, id, L, p, st);
 }
 
 // Default variant per layer, from tools/tile_sweep.sh and in-network tools/layer_profile.py runs on MI355X at
@@ -770,10 +789,10 @@ int default_tile(const mpx_conv_desc& d) {
     // ... and with K = 256 exactly (256 -> 1024, a fifth of ResNet-101's conv time) the kernel that keeps the weights of a wave in its
     // 256 AGPRs and only pixels in the LDS (mpx_convw.h): in the network at batch 2340, A/B in one call, 24.3 -> 21.3 ms for the 23 layers
 #ifndef MPX_PROBE_NO_CONVW               // A/B builds only (tools/ab_lib.sh)
-    if (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.cout > d.cin && d.cout % 256 == 0 && d.cin == ConvW::K && d.hout >= 14) return 14;
+    if (convw_eligible(d) && d.cout > d.cin && d.hout >= 14) return 14;
 #endif
     // (round 4: on 7x7 maps too -- 512 -> 2048 x3 3.53 -> 3.38 ms per batch in the network, A/B in one call; round 2 had measured a tie)
-    if (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.cout > d.cin && d.cout % 256 == 0 && d.cin % 64 == 0 && d.cin >= 128) return 10;
+    if (convx_eligible(d) && d.cout > d.cin) return 10;
     if (d.stride == 1 && d.cout > d.cin) return 7;
     // reducing / square 1x1 stride-1 layers with cout % 256 == 0: the 256x256 tile (mpx_conv256.h) halves the operand bytes
     // per MAC and runs +10..18 % (1024->256: 365 vs 322 TFLOP/s, 1024->512: 411 vs 346); expanding layers lose on it (one
@@ -782,53 +801,23 @@ int default_tile(const mpx_conv_desc& d) {
     // them in the torchvision ResNets): in the network at batch 2340, A/B in one call, 1024->256 13.73 -> 13.12 ms, 512->256 1.47 -> 1.32,
     // 1024->512 1.18 -> 1.11, 2048->512 1.11 -> 1.10 per batch
 #ifdef MPX_PROBE_NO_PERSISTENT_256      // A/B builds only (tools/ab_lib.sh)
-    if (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.cout % 256 == 0 && d.cin % 64 == 0) return 9;
+    if (conv256_eligible(d)) return 9;
 #endif
-    if (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.cout % 256 == 0 && d.cin % 64 == 0) return d.residual ? 9 : 13;
+    if (conv256_eligible(d)) return conv256p_eligible(d) ? 13 : 9;
     return 2;
 }
 
-// one launch of layer L's conv with the given kernel variant
-int dispatch_conv(mpx_engine* h, const ConvLayer& L, ConvParams& p, int tile, hipStream_t st) {
-    if (tile == 12)
-        return patchp_fits<PatchTile0>(L.d) ? launch_conv_patchp<PatchTile0>(h, p, L.d, st) : launch_conv_patchp<PatchTile2>(h, p, L.d, st);
-    if (tile == 6) {
-        if (L.d.cout <= 64) return launch_conv_patch<PatchTile1>(h, p, L.d, st);
-        return patch_fits<PatchTile0>(L.d) ? launch_conv_patch<PatchTile0>(h, p, L.d, st) : launch_conv_patch<PatchTile2>(h, p, L.d, st);
-    }
-    switch (tile) {
-        case 10: return launch_convx(h, p, L.d.cout_pad, st);
-        case 14: return launch_convw(h, p, L.d.cout_pad, st);
-        case 9: return launch_conv256(h, p, L.d.cout_pad, st);
-        case 13: return launch_conv256p(h, p, L.d.cout_pad, st);
-        case 0: return launch_conv_tile<ConvTile0>(h, p, L.d.cout_pad, st);
-        case 1: return launch_conv_tile<ConvTile1>(h, p, L.d.cout_pad, st);
-        case 2: return launch_conv_tile<ConvTile2>(h, p, L.d.cout_pad, st);
-        case 7: return launch_conv_tile<ConvTile7>(h, p, L.d.cout_pad, st);
-        case 4: return launch_conv_tile<ConvTile4>(h, p, L.d.cout_pad, st);
-#ifdef MPX_EXPERIMENTAL
-        case 11: return launch_convs(h, p, L.d.cout_pad, st);
-        case 8: return launch_convp_tile<ConvTile2>(h, p, L.d.cout_pad, st);
-        case 3: return launch_conv_tile<ConvTile3>(h, p, L.d.cout_pad, st);
-        case 5: return launch_conv_tile<ConvTile5>(h, p, L.d.cout_pad, st);
-#endif
-        default: return fail(h, MPX_E_INTERNAL, "conv: no kernel for tile id %d", tile);
-    }
-}
-
-int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, const half_t* r_hi,
-                const half_t* r_lo, half_t* y_hi, half_t* y_lo, float* y_f32, int B, hipStream_t st) {
-    const ConvLayer& L = h->convs[i];
-    if (!L.loaded) return fail(h, MPX_E_STATE, "layer %d (%s) has no weights", i, L.d.name);
-    ConvParams p;
+// The ConvParams of layer L over B images: its packed weights, the input planes in_* (the ImageNet stem: the engine's padded NHWC4 staging,
+// where a (ky) tap is one 64-B run of 8 pixels x 4 channels, no bounds to check), the output planes y_*.  The output pixels must fit
+// 32-bit indices; the callers check the extent of the input planes their kernel indexes.
+int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const half_t* in_lo, half_t* y_hi, half_t* y_lo, int B, ConvParams& p) {
     std::memset(&p, 0, sizeof p);
     p.w_hi = L.w_hi; p.w_lo = L.w_lo; p.scale = L.scale; p.shift = L.shift;
-    p.r_hi = r_hi; p.r_lo = r_lo; p.y_hi = y_hi; p.y_lo = y_lo; p.y_f32 = y_f32;
+    p.y_hi = y_hi; p.y_lo = y_lo;
     p.cout = L.cout_store;
     p.relu = L.d.relu;
     p.ktot = L.d.k_packed;
     if (L.is_stem) {
-        // padded NHWC4 staging: a (ky) tap is one 64-B run of 8 pixels x 4 channels, no bounds to check
         p.x_hi = h->in_hi; p.x_lo = h->in_lo;
         p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
         p.kh = kStemK; p.kw = 1; p.stride = 2; p.pad = 0; p.k_per_tap = 32;
@@ -839,12 +828,22 @@ int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, 
     }
     p.ho = L.d.hout; p.wo = L.d.hout;
     const long long M = (long long)B * p.ho * p.wo;
-    if (M > 0x7fffffffLL || (long long)B * p.hin * p.win > 0x7fffffffLL)
-        return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
+    if (M > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
     p.M = (int)M;
 #ifdef MPX_DIAG
     p.stamps = h->stamps;
 #endif
+    return 0;
+}
+
+int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, const half_t* r_hi,
+                const half_t* r_lo, half_t* y_hi, half_t* y_lo, float* y_f32, int B, hipStream_t st) {
+    const ConvLayer& L = h->convs[i];
+    if (!L.loaded) return fail(h, MPX_E_STATE, "layer %d (%s) has no weights", i, L.d.name);
+    ConvParams p;
+    if (int rc = conv_params(h, L, in_hi, in_lo, y_hi, y_lo, B, p)) return rc;
+    if ((long long)B * p.hin * p.win > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
+    p.r_hi = r_hi; p.r_lo = r_lo; p.y_f32 = y_f32;
     ProfScope ps(h, st, OP_CONV, i);
     h->last_kernels = 0;
     // The 256x256 kernel keeps ONE workgroup per CU, so a launch runs in "rounds" of num_cus tiles and a small remainder would
@@ -854,27 +853,26 @@ int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, 
     // scores wherever a mask sits in the batch): 1024->256 12.9 -> 12.3 ms, 2048->512 1.15 -> 1.01 ms per batch.  (The same
     // split of the 3x3 patch kernel's and tile 0's last round was measured and gains nothing: their remainder lives as long
     // as one of their tiles whatever its tile size)
-    int big_tc = 0, big_tp = 0;
-    if (L.tile == 9 || L.tile == 13) { big_tc = Conv256::TC; big_tp = Conv256::TP; }
-    if (big_tc && !L.is_stem) {
-        const long long tiles_c = (p.cout + big_tc - 1) / big_tc, tiles_p = (M + big_tp - 1) / big_tp;
+    const TileRow* row = find_tile(L.tile);
+    if (row && row->split && !L.is_stem) {
+        const long long M = p.M, tiles_c = (p.cout + Conv256::TC - 1) / Conv256::TC, tiles_p = (M + Conv256::TP - 1) / Conv256::TP;
         const long long total = tiles_p * tiles_c, rounds = total / h->num_cus, rest = total - rounds * h->num_cus;
         const long long howo = (long long)p.ho * p.wo;
-        const long long n_a = rounds * h->num_cus / tiles_c * big_tp / howo;           // images that fill the whole rounds
+        const long long n_a = rounds * h->num_cus / tiles_c * Conv256::TP / howo;      // images that fill the whole rounds
         if (rounds >= 1 && rest > 0 && 2 * rest <= h->num_cus && n_a >= 1 && n_a < B) {
             ConvParams q = p;
             p.M = (int)(n_a * howo);
-            int rc = dispatch_conv(h, L, p, L.tile, st);
+            int rc = launch_tile(h, L.tile, L, p, st);
             if (rc) return rc;
             const size_t xo = (size_t)n_a * p.hin * p.win * p.pix_stride, yo = (size_t)n_a * howo * p.cout;
             q.M = (int)(M - n_a * howo);
             q.x_hi += xo; q.x_lo += xo;
             q.y_hi += yo; q.y_lo += yo;
             if (q.r_hi) { q.r_hi += yo; q.r_lo += yo; }
-            return dispatch_conv(h, L, q, 2, st);
+            return launch_tile(h, 2, L, q, st);
         }
     }
-    return dispatch_conv(h, L, p, L.tile, st);
+    return launch_tile(h, L.tile, L, p, st);
 }
 
 // A block's last 1x1 conv with its downsample branch K-concatenated: out = relu(s * (W3' . t2 + Wds' . x) + shift)
@@ -885,30 +883,15 @@ int launch_conv_fused(mpx_engine* h, int i, const half_t* in_hi, const half_t* i
     if (!L.fuse_main || !L.fused_loaded) return fail(h, MPX_E_STATE, "layer %d (%s) has no fused weights", i, L.d.name);
     const ConvLayer& D = h->convs[L.fuse_partner];
     ConvParams p;
-    std::memset(&p, 0, sizeof p);
+    if (int rc = conv_params(h, L, in_hi, in_lo, y_hi, y_lo, B, p)) return rc;
+    if ((long long)B * D.d.hin * D.d.hin > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
     p.w_hi = L.fw_hi; p.w_lo = L.fw_lo; p.scale = L.fscale; p.shift = L.fshift;
-    p.y_hi = y_hi; p.y_lo = y_lo;
-    p.cout = L.d.cout; p.relu = 1;
     p.k1 = L.d.cin; p.ktot = L.d.cin + D.d.cin;
-    p.x_hi = in_hi; p.x_lo = in_lo;
-    p.hin = L.d.hin; p.win = L.d.hin; p.pix_stride = L.d.cin;
-    p.kh = 1; p.kw = 1; p.stride = 1; p.pad = 0; p.k_per_tap = L.d.cin;
     p.x2_hi = x2_hi; p.x2_lo = x2_lo;
     p.hin2 = D.d.hin; p.win2 = D.d.hin; p.pix_stride2 = D.d.cin; p.stride2 = D.d.stride;
-    p.ho = L.d.hout; p.wo = L.d.hout;
-    const long long M = (long long)B * p.ho * p.wo;
-    if (M > 0x7fffffffLL || (long long)B * p.hin2 * p.win2 > 0x7fffffffLL)
-        return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
-    p.M = (int)M;
-#ifdef MPX_DIAG
-    p.stamps = h->stamps;
-#endif
     ProfScope ps(h, st, OP_CONV, i);
-    if (L.tile == 2) return launch_conv_tile<ConvTile2, true>(h, p, L.d.cout_pad, st);
-#ifdef MPX_EXPERIMENTAL
-    if (L.tile == 8) return launch_convp_tile<ConvTile2, true>(h, p, L.d.cout_pad, st);
-#endif
-    return launch_conv_tile<ConvTile7, true>(h, p, L.d.cout_pad, st);       // (tiles 7, 10 and 14: the persistent kernels have no dual-operand form)
+    const TileRow* row = find_tile(L.tile);
+    return launch_tile(h, row && row->dual >= 0 ? row->dual : 7, L, p, st);     // (mpx_conv_dual_bn_act on any other tile: tile 7's)
 }
 
 // The ImageNet stem (7x7 stride-2 conv + BN + ReLU) with its 3x3 stride-2 pad-1 max pool in ONE launch (mpx_conv.h, POOL): writes the
@@ -924,21 +907,8 @@ int launch_stem_pool(mpx_engine* h, half_t* y_hi, half_t* y_lo, int B, hipStream
     if (!stem_pool_eligible(h)) return fail(h, MPX_E_STATE, "stem + max pool: this architecture has no 7x7 stem with a max pool");
     if (!L.loaded) return fail(h, MPX_E_STATE, "layer 0 (%s) has no weights", L.d.name);
     ConvParams p;
-    std::memset(&p, 0, sizeof p);
-    p.w_hi = L.w_hi; p.w_lo = L.w_lo; p.scale = L.scale; p.shift = L.shift;
-    p.y_hi = y_hi; p.y_lo = y_lo;
-    p.cout = L.cout_store; p.relu = L.d.relu; p.ktot = L.d.k_packed;
-    p.x_hi = h->in_hi; p.x_lo = h->in_lo;
-    p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
-    p.kh = kStemK; p.kw = 1; p.stride = 2; p.pad = 0; p.k_per_tap = 32;
-    p.ho = L.d.hout; p.wo = L.d.hout;
-    const long long M = (long long)B * p.ho * p.wo;
-    if (M > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
-    p.M = (int)M;
+    if (int rc = conv_params(h, L, nullptr, nullptr, y_hi, y_lo, B, p)) return rc;
     p.n_tiles_c = 1;
-#ifdef MPX_DIAG
-    p.stamps = h->stamps;
-#endif
     const long long nblocks = (long long)B * (p.ho / 2 / POOL_PY) * (p.wo / 2 / POOL_PX);
     if (nblocks > 0x7fffffffLL) return fail(h, MPX_E_ARG, "conv grid out of range");
     ProfScope ps(h, st, OP_CONV, 0);
@@ -1248,60 +1218,8 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     e = hipMemset(h->arena, 0, scratch_bytes + 2 * in_plane);
     if (e == hipSuccess) e = hipMemset(h->pool_hi, 0, 2 * pool_plane);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile0>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile0::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile1>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile1::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile1::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile2>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile2::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile7>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile7::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile2::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile7::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv256_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Conv256::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)convx_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ConvX::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)convw_f16x3_kernel<ConvW::K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvW::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv256p_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Conv256P::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile4>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile4::LDS);
-#ifdef MPX_EXPERIMENTAL
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile3>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile3::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_f16x3_kernel<ConvTile5>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile5::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)convp_f16x3_kernel<ConvTile2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile2::RING);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)convp_f16x3_kernel<ConvTile2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile2::RING);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)convs_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ConvS::LDS);
-#endif
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)btail_f16x3_kernel<BtResC64>, hipFuncAttributeMaxDynamicSharedMemorySize, BtResC64::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)btail_f16x3_kernel<BtResC128>, hipFuncAttributeMaxDynamicSharedMemorySize, BtResC128::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)btail_f16x3_kernel<BtDualC64>, hipFuncAttributeMaxDynamicSharedMemorySize, BtDualC64::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)btail_f16x3_kernel<BtHeadC64>, hipFuncAttributeMaxDynamicSharedMemorySize, BtHeadC64::LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3p_f16x3_kernel<PatchTile0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3p_f16x3_kernel<PatchTile1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3p_f16x3_kernel<PatchTile2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3pp_f16x3_kernel<PatchTile0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv3x3pp_f16x3_kernel<PatchTile2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+    for (const KernelLds& k : kKernelLds)
+        if (e == hipSuccess) e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
     if (e != hipSuccess) { (void)hipFree(h->arena); delete h; return (int)e; }
     *out = h;
     return 0;
@@ -1397,28 +1315,13 @@ int mpx_set_conv_tile(mpx_engine* h, int i, int tile) {
     if (i < 0 || i >= (int)h->convs.size()) return fail(h, MPX_E_ARG, "set_conv_tile: bad layer index");
     ConvLayer& L = h->convs[i];
     if (tile < 0) tile = default_tile(L.d);
-    // product ids = what default_tile can return: 0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14
-    bool known = tile == 0 || tile == 1 || tile == 2 || tile == 4 || tile == 6 || tile == 7 || tile == 9 || tile == 10 || tile == 12 || tile == 13 || tile == 14;
-#ifdef MPX_EXPERIMENTAL
-    known = known || tile == 3 || tile == 5 || tile == 8 || tile == 11;
-    if (tile == 11 && !convs_eligible(L))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the pixel-stationary expanding-1x1 kernel (11) runs 1x1 stride-1 layers with cout %% 256 == 0 and cin = 256 (%s is not one)", L.d.name);
-    if (tile == 8 && (L.is_fc || L.is_stem || L.d.cout < 128))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the persistent kernel (8) runs conv layers with cout >= 128 (%s is not one)", L.d.name);
-#endif
-    if (!known) return fail(h, MPX_E_ARG, "set_conv_tile: unknown tile %d (product ids: 0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)", tile);
-    if (tile == 13 && !conv256p_eligible(L))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the persistent 256x256 kernel (13) runs 1x1 stride-1 layers with cout %% 256 == 0, cin %% 64 == 0 and no residual operand (%s is not one)", L.d.name);
-    if (tile == 12 && !patchp_eligible(L.d))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the persistent patch kernel (12) needs a 3x3 stride-1 layer with cout >= 128 and no residual operand whose input patch fits the LDS (%s is not one)", L.d.name);
-    if (tile == 14 && !convw_eligible(L))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the weights-in-registers expanding-1x1 kernel (14) runs 1x1 stride-1 layers with cout %% 256 == 0 and cin = 256 (%s is not one)", L.d.name);
-    if (tile == 10 && !convx_eligible(L))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the persistent expanding-1x1 kernel (10) runs 1x1 stride-1 layers with cout %% 256 == 0 and cin %% 64 == 0, cin >= 128 (%s is not one)", L.d.name);
-    if (tile == 9 && !conv256_eligible(L))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the 256x256 kernel (9) runs 1x1 stride-1 layers with cout %% 256 == 0 and cin %% 64 == 0 (%s is not one)", L.d.name);
-    if (tile == 6 && !patch_eligible(L.d))
-        return fail(h, MPX_E_ARG, "set_conv_tile: the patch kernel (6) needs a 3x3 stride-1 layer whose input patch fits the LDS (%s does not)", L.d.name);
+    const TileRow* r = find_tile(tile);
+    if (!r) {
+        std::string ids;
+        for (const TileRow& k : kTiles) ids += (ids.empty() ? "" : ", ") + std::to_string(k.id);
+        return fail(h, MPX_E_ARG, "set_conv_tile: unknown tile %d (product ids: %s)", tile, ids.c_str());
+    }
+    if (!eligible(*r, L)) return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: %s (%s is not one)", tile, r->refusal, L.d.name);
     L.tile = tile;
     return 0;
 }
@@ -1719,7 +1622,8 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 if (h->fuse_ds && h->convs[o.conv].fuse_partner >= 0) {
                     const ConvLayer& CL = h->convs[o.conv];
                     const ConvLayer& MAIN = CL.fuse_main ? CL : h->convs[CL.fuse_partner];
-                    if (MAIN.fused_loaded && (MAIN.tile == 2 || MAIN.tile == 7 || MAIN.tile == 8 || MAIN.tile == 10 || MAIN.tile == 11 || MAIN.tile == 14)) {      // (8, 11: experimental builds)
+                    const TileRow* r = find_tile(MAIN.tile);
+                    if (MAIN.fused_loaded && r && r->dual >= 0) {
                         if (!CL.fuse_main) break;       // the downsample conv runs inside its main conv's launch
                         rc = launch_conv_fused(h, o.conv, hi(o.in), lo(o.in), hi(o.in2), lo(o.in2), hi(o.out), lo(o.out), B, as_stream(stream));
                         break;

@@ -207,7 +207,7 @@ def test_conv_every_tile_variant(eng101, name, tile):
 
 def test_conv_tile_ids_are_the_default_kernels(eng101):
     """The documented tile ids are exactly what default_tile hands out; the ids of kernels that never became a default (3, 5, 8, 11:
-    probe builds only) and anything else are refused."""
+    removed) and anything else are refused."""
     i = _layer_index(eng101, "layer3.5.conv3")
     for tile in (3, 5, 8, 11, 15):
         assert eng101._lib.mpx_set_conv_tile(eng101._h, i, tile) == -1

@@ -28,11 +28,7 @@ def build_diag(extra_flags=()):
     written at build time (mtimes mean nothing once the tree has been copied to the GPU box, __graft_entry__._stale)."""
     import __graft_entry__ as g
     flags = g.HIPCC_FLAGS + ["-DMPX_DIAG"] + list(extra_flags)
-    srcs = g.lib_sources()
-    if "-DMPX_EXPERIMENTAL" in extra_flags:
-        import glob
-        srcs = srcs + sorted(glob.glob(os.path.join(HERE, "experimental", "*.h")))
-    want = g._source_hash(srcs, flags)
+    want = g._source_hash(g.lib_sources(), flags)
     stamp = DIAG + ".sha256"
     if os.path.exists(DIAG) and os.path.exists(stamp) and open(stamp).read().strip() == want:
         return

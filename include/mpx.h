@@ -43,16 +43,26 @@ enum {
  * (SURVEY.md 8 f4), whose trained checkpoints ship with it:
  *   MPX_ARCH_MNIST_NET            Classification_Net, 28x28x1 -> 10 (generate_gp_training_data_mnist.py:86-105)
  *   MPX_ARCH_CIFAR_RESNET + depth ResNetCifar(depth = 6n+2), 32x32x3 -> 10 (models/resnet.py:77-146; the checkpoint is depth 56)
+ * -- or one of torchvision's VGG networks, which the reference's `-a` also selects (its README lists them next to the ResNets):
+ *   MPX_ARCH_VGG + depth          vgg11 / vgg13 / vgg16 / vgg19 (torchvision cfgs A / B / D / E), depth 11, 13, 16 or 19
+ *   MPX_ARCH_VGG_BN + depth       the same with BatchNorm2d after every conv (vgg11_bn ... vgg19_bn)
+ * A VGG engine is a plain chain: 3x3 conv (+ bias, + BN) + ReLU layers with 2x2 stride-2 max pools (mpx_maxpool2x2s2), then the classifier
+ * as three more entries of the conv list (classifier.0 = a 7x7 valid conv over the [B][7][7][512] map, K = 25088; classifier.3 = 1x1
+ * 4096 -> 4096; classifier.6 = the logit layer).  AdaptiveAvgPool2d((7, 7)) is the identity at 224 input and Dropout is the identity in
+ * eval, so neither is an op.  It stages through mpx_mask_apply_normalize only: it has no 7x7 stem, so the stem-table and stem + pool
+ * entry points return MPX_E_STATE.  Its first layer (3 -> 64, 3x3 pad 1) reads the padded NHWC4 staging as the ResNet stem does.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
 #define MPX_ARCH_MNIST_NET 1
 #define MPX_ARCH_CIFAR_RESNET 2000
+#define MPX_ARCH_VGG 3000
+#define MPX_ARCH_VGG_BN 3100
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
-    char name[48];       /* torchvision state_dict prefix of the conv ("layer3.4.conv2", "fc") */
-    char bn_name[48];    /* prefix of its BatchNorm ("layer3.4.bn2"); "" for fc */
+    char name[48];       /* torchvision state_dict prefix of the conv ("layer3.4.conv2", "fc", "features.7", "classifier.0") */
+    char bn_name[48];    /* prefix of its BatchNorm ("layer3.4.bn2", "features.8"); "" for a layer without one (fc, plain VGG) */
     int32_t cin, cout, ksize, stride, pad;
     int32_t hin, hout;   /* square spatial sizes at 224x224 input */
     int32_t relu;        /* ReLU in the epilogue */
@@ -73,12 +83,13 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets and the VGG networks, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
 /* ---- topology / weights ------------------------------------------------------------------
- * Layer i in [0, mpx_num_convs): every conv in forward order, then "fc" as the last entry. */
+ * Layer i in [0, mpx_num_convs): every conv in forward order; the last entry is the logit layer, whatever its name ("fc", "fc1",
+ * "classifier.6"). */
 int mpx_num_convs(const mpx_engine* h);
 int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
 
@@ -127,7 +138,8 @@ int mpx_last_conv_kernels(const mpx_engine* h);
 
 /* Host-only packer (no GPU needed; what mpx_set_conv_weights runs before the upload).
  * Produces the fp16 planes w_hi/w_lo of cout_pad x k_packed elements (k order = (ky,kx,ci), ci fastest;
- * for the 7x7 stem k = ky*32 + px*4 + c over the NHWC4 padded input) in PIECE-major order: element (row, k) of a plane is at
+ * for a layer that reads the NHWC4 padded input -- cin == 3 and k_packed == ksize * 32: the ImageNet ResNets' 7x7 stem, the VGG first
+ * layer -- k = ky*32 + px*4 + c, one run of 8 pixels x 4 channels per kernel row, zero weights on px >= ksize and c == 3) in PIECE-major order: element (row, k) of a plane is at
  *   ((((row/16) * (k_packed/32) + k/32) * 16 + row%16) * 4 + ((k/8)%4 ^ (((row%16)/8) * 2))) * 8 + k%8
  * -- [cout_pad/16][k_packed/32][16 rows][four 16-byte chunks, XOR-swizzled by the row], so that each 1-KiB LDS-DMA piece of
  * the conv kernels is one contiguous run of 8 cache lines already in the order of its LDS image (cout_pad % 16 == 0,
@@ -249,6 +261,12 @@ int mpx_bottleneck_tail_info(const mpx_engine* h, int k, int* conv2, int* conv3,
 int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                      void* out_lo, int B, int hin, int c, void* stream);
 
+/* ---- K3 of the VGG networks: maxpool 2x2 s2 (nn.MaxPool2d(2, 2)), NHWC split planes [B][hin][hin][c] -> [B][hin/2][hin/2][c].
+ * replaces: every "M" of torchvision's VGG cfgs inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * Bit-exact: each output (hi, lo) is the pair of the input element with the largest hi + lo.  hin even, c a multiple of 8. */
+int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
+                     void* out_lo, int B, int hin, int c, void* stream);
+
 /* ---- K1 + K3 in one launch: the ImageNet stem and its max pool -------------------------------------------
  * replaces: `x = self.conv1(x); x = self.bn1(x); x = self.relu(x); x = self.maxpool(x)` (torchvision resnet.py, reached through
  *           model(masked_img_tensor), generate_gp_training_data_imagenet.py:246): the 7x7 stride-2 conv + BN + ReLU of layer 0 reads
@@ -288,7 +306,7 @@ int mpx_heatmap_accumulate(mpx_engine* h, const int32_t* seg, const uint8_t* ono
                            const int32_t* label, int M, int S, float* heat, void* stream);
 
 /* ---- introspection for tests / benchmarks --------------------------------------------------- */
-/* DEV pointers of the input staging planes: fp16 [max_batch][230][230][4] (padded NHWC4) for the ImageNet ResNets, [max_batch][H][W][32] for
+/* DEV pointers of the input staging planes: fp16 [max_batch][230][230][4] (padded NHWC4) for the ImageNet ResNets and VGG, [max_batch][H][W][32] for
  * the small networks.  A pure getter: the record of how each slot was staged is not touched, so a diagnostic call between
  * mpx_stem_table_apply and mpx_forward changes nothing. */
 int mpx_input_planes(const mpx_engine* h, void** hi, void** lo);
@@ -297,7 +315,7 @@ int mpx_input_planes(const mpx_engine* h, void** hi, void** lo);
  * mpx_stem_table_apply (which marks the slots it writes as its own again).  MPX_E_ARG outside [0, max_batch). */
 int mpx_mark_input_staged(mpx_engine* h, int slot0, int M);
 /* DEV pointers of the pooled stem output planes: fp16 [max_batch][56][56][64], written by the stem + max pool launch of mpx_forward or by
- * mpx_stem_table_apply (NULL for the small networks, which have no such stem). */
+ * mpx_stem_table_apply (NULL for the small networks and VGG, which have no such stem). */
 int mpx_stem_planes(const mpx_engine* h, void** hi, void** lo);
 /* When enabled, every kernel launch of mpx_forward / mpx_mask_apply_normalize is bracketed by
  * HIP events on the launch stream (bounded pool; launches beyond it are not recorded). */

@@ -30,9 +30,10 @@ constexpr int kActBufs = 4;
 constexpr int kStemK = 7;
 constexpr int kProfilePairs = 4096;
 constexpr size_t kActElemsPerImage = 112 * 112 * 64;   // ImageNet: largest activation (stem output, = 56*56*256)
+constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel maps of the first stage
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
-enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5 };
+enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -96,6 +97,8 @@ struct mpx_engine {
     // the reference's two small networks (28x28x1 / 32x32x3, staging [B][H][W][32] read by a generic 3x3 conv, 10 classes)
     int img = MPX_IMG, in_ch = 3, ncls = MPX_NUM_CLASSES, logit_pitch = MPX_NUM_CLASSES;
     bool small = false;
+    bool vgg = false;               // torchvision VGG: a plain chain, two activation buffers, no 7x7 stem
+    int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
     bool bottleneck = false;
@@ -187,10 +190,12 @@ int default_tile(const mpx_conv_desc& d);
 
 // torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
 int build_topology_small(mpx_engine* h);
+int build_topology_vgg(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
         return build_topology_small(h);
+    if (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) return build_topology_vgg(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -482,6 +487,84 @@ int build_topology_small(mpx_engine* h) {
     }
     add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0);
     h->act_elems_per_image = act;
+    return 0;
+}
+
+// torchvision VGG (vgg.py: make_layers over cfgs "A" / "B" / "D" / "E", then the classifier), depth 11 / 13 / 16 / 19, with or without
+// BatchNorm.  Names follow torchvision's module indices: a conv at features.i, its BatchNorm (the _bn variants) at features.(i+1), the ReLU
+// after them, one index per "M" (MaxPool2d(2, 2)).  Every conv has a bias.  The classifier runs as three more layers of the conv list:
+// classifier.0 = Linear(25088, 4096) as a 7x7 valid conv over the [B][7][7][512] map (torch.flatten of NCHW is channel-major, so the
+// [4096][25088] weight viewed as [4096][512][7][7] is its OIHW weight), classifier.3 = Linear(4096, 4096) as a 1x1 conv, classifier.6 =
+// Linear(4096, 1000), the logit layer.  AdaptiveAvgPool2d((7, 7)) on a 7x7 map and Dropout in eval are identities.  A plain chain: the
+// op list ping-pongs between two activation buffers.
+int build_topology_vgg(mpx_engine* h) {
+    const bool bn = h->arch > MPX_ARCH_VGG_BN;
+    const int depth = h->arch - (bn ? MPX_ARCH_VGG_BN : MPX_ARCH_VGG);
+    constexpr int M = 0;                                    // "M" of the cfgs
+    static const int cfg_a[] = {64, M, 128, M, 256, 256, M, 512, 512, M, 512, 512, M};
+    static const int cfg_b[] = {64, 64, M, 128, 128, M, 256, 256, M, 512, 512, M, 512, 512, M};
+    static const int cfg_d[] = {64, 64, M, 128, 128, M, 256, 256, 256, M, 512, 512, 512, M, 512, 512, 512, M};
+    static const int cfg_e[] = {64, 64, M, 128, 128, M, 256, 256, 256, 256, M, 512, 512, 512, 512, M, 512, 512, 512, 512, M};
+    const int* cfg = nullptr;
+    int n = 0;
+    switch (depth) {
+        case 11: cfg = cfg_a; n = (int)(sizeof cfg_a / sizeof *cfg_a); break;
+        case 13: cfg = cfg_b; n = (int)(sizeof cfg_b / sizeof *cfg_b); break;
+        case 16: cfg = cfg_d; n = (int)(sizeof cfg_d / sizeof *cfg_d); break;
+        case 19: cfg = cfg_e; n = (int)(sizeof cfg_e / sizeof *cfg_e); break;
+        default: return MPX_E_ARG;
+    }
+    h->vgg = true;
+    h->n_act_bufs = 2;
+    h->act_elems_per_image = kVggActElemsPerImage;
+    auto add_conv = [&](const std::string& name, const std::string& bn_name, int cin, int cout, int k, int pad, int hin, int relu, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn_name);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = 1; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = hin + 2 * pad - k + 1;
+        L.d.relu = relu;
+        L.has_bias = true;
+        L.is_fc = fc;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row
+        L.cin_pad = cin;
+        L.cout_store = cout;
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * cin;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto add_op = [&](int kind, int conv, int in, int out, int hin, int c) {
+        h->ops.push_back(Op{kind, conv, in, out, BUF_NONE, hin, c, BUF_NONE});
+    };
+    int X = BUF_INPUT, cin = 3, hcur = MPX_IMG, idx = 0;
+    for (int j = 0; j < n; ++j) {
+        const int O = X == 0 ? 1 : 0;
+        if (cfg[j] == M) {
+            add_op(OP_MAXPOOL2, -1, X, O, hcur, cin);
+            hcur /= 2;
+            idx += 1;
+        } else {
+            const int c = add_conv("features." + std::to_string(idx), bn ? "features." + std::to_string(idx + 1) : "", cin, cfg[j], 3, 1, hcur, 1, false);
+            add_op(OP_CONV, c, X, O, 0, 0);
+            cin = cfg[j];
+            idx += bn ? 3 : 2;
+        }
+        X = O;
+    }
+    // hcur = 7, cin = 512
+    int O = X == 0 ? 1 : 0;
+    int c = add_conv("classifier.0", "", cin, 4096, hcur, 0, hcur, 1, false);
+    add_op(OP_CONV, c, X, O, 0, 0);
+    X = O; O = X == 0 ? 1 : 0;
+    c = add_conv("classifier.3", "", 4096, 4096, 1, 0, 1, 1, false);
+    add_op(OP_CONV, c, X, O, 0, 0);
+    X = O;
+    c = add_conv("classifier.6", "", 4096, MPX_NUM_CLASSES, 1, 0, 1, 0, true);
+    add_op(OP_CONV, c, X, BUF_NONE, 0, 0);
+    add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, 0, 0);
     return 0;
 }
 
@@ -818,9 +901,13 @@ int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const ha
     p.relu = L.d.relu;
     p.ktot = L.d.k_packed;
     if (L.is_stem) {
+        // a K step is one kernel row: a run of 8 pixels x 4 channels starting at the window's left edge in the staging, whose
+        // 3-pixel border already holds the padding (the 7x7 stem's pad 3: origin shift 0; the VGG 3x3 pad-1 layer: -2).  A run that
+        // passes a row's end reads the next row of the same image (row 2y + 3 + ky <= 229 for the stem, y + 2 + ky <= 227 for VGG),
+        // and meets the zero weights of px >= ksize.
         p.x_hi = h->in_hi; p.x_lo = h->in_lo;
         p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
-        p.kh = kStemK; p.kw = 1; p.stride = 2; p.pad = 0; p.k_per_tap = 32;
+        p.kh = L.d.ksize; p.kw = 1; p.stride = L.d.stride; p.pad = L.d.pad - (MPX_IMG_PAD - MPX_IMG) / 2; p.k_per_tap = 32;
     } else {
         p.x_hi = in_hi; p.x_lo = in_lo;
         p.hin = L.d.hin; p.win = L.d.hin; p.pix_stride = L.cin_pad;
@@ -1070,11 +1157,15 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
                           uint16_t* w_lo, float* scale, float* shift) {
     if (!d || !w || !w_hi || !w_lo || !scale || !shift) return MPX_E_ARG;
     const int cin = d->cin, cout = d->cout, k = d->ksize, K = d->k_packed;
-    const bool stem = (cin == 3 && k == kStemK);
     if (k <= 0 || cin <= 0 || cout <= 0 || cout > d->cout_pad || d->cout_pad % 16 != 0) return MPX_E_ARG;
+    // row-run layout (the layers that read the padded NHWC4 staging: the 7x7 stem, K = 224, and the VGG 3x3 first layer, K = 96): one
+    // 32-wide K step per kernel row, 8 pixels x 4 channels.  (The CIFAR ResNet's 3-channel conv1 reads [H][W][32] planes: K = 288.)  Odd
+    // k in [3, 7] only: no descriptor the generic layout accepts (k = 1, 2, 4, 8 with K = k * 32) changes meaning.
+    const bool stem = (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7);
+    if (cin == 3 && k == kStemK && !stem) return MPX_E_ARG;
     // K = k*k*cin_pad: the input planes may carry more channels per pixel than the layer reads (small nets pad to 32)
     const int cin_pad = stem ? 0 : K / (k * k);
-    if (stem ? (K != kStemK * 32) : (K != k * k * cin_pad || cin_pad < cin || K % 32 != 0)) return MPX_E_ARG;
+    if (!stem && (K != k * k * cin_pad || cin_pad < cin || K % 32 != 0)) return MPX_E_ARG;
     std::memset(w_hi, 0, (size_t)d->cout_pad * K * 2);
     std::memset(w_lo, 0, (size_t)d->cout_pad * K * 2);
     for (int co = 0; co < d->cout_pad; ++co) {
@@ -1168,7 +1259,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     // only ever stages through K0, stem = "conv", never pays for it)
     const size_t stemtab_bytes = 2 * stem_plane + stem_w_bytes;
     h->tab_sizes[0] = tab_int_bytes; h->tab_sizes[1] = tab_lab_bytes; h->tab_sizes[2] = tab_vec_bytes; h->tab_sizes[3] = tab_bits_bytes;
-    const size_t total = scratch_bytes + 2 * in_plane + 2 * kActBufs * act_plane + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes;
+    const size_t total = scratch_bytes + 2 * in_plane + 2 * (size_t)h->n_act_bufs * act_plane + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes;
     e = hipMalloc((void**)&h->arena, total);
     if (e != hipSuccess) { delete h; return (int)e; }
     h->arena_bytes = total;
@@ -1177,7 +1268,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     h->seg_scratch = (float*)take(scratch_bytes);
     h->in_hi = (half_t*)take(in_plane);
     h->in_lo = (half_t*)take(in_plane);
-    for (int b = 0; b < kActBufs; ++b) {
+    for (int b = 0; b < h->n_act_bufs; ++b) {
         h->act_hi[b] = (half_t*)take(act_plane);
         h->act_lo[b] = (half_t*)take(act_plane);
     }
@@ -1373,7 +1464,7 @@ int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const flo
 int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg, int S,
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg ? " (VGG stages through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -1538,6 +1629,22 @@ int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     return 0;
 }
 
+int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin,
+                     int c, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
+        return fail(h, MPX_E_ARG, "maxpool2x2s2: bad arguments (hin even, c multiple of 8)");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1);
+    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (c / 8);
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
+    hipLaunchKernelGGL(maxpool2x2s2_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
+                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
                        int c, void* stream) {
     if (!h) return MPX_E_ARG;
@@ -1638,6 +1745,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 if (skip_pool) { skip_pool = false; break; }
                 rc = mpx_maxpool3x3s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream);
                 break;
+            case OP_MAXPOOL2: rc = mpx_maxpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
             case OP_AVGPOOL: rc = mpx_global_avgpool(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
             case OP_HEAD: rc = mpx_head_softmax_gather(h, logits, label, score, pred, B, stream); break;
             case OP_AVGPAD: rc = mpx_avgpool2_pad(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c >> 16, o.c & 0xffff, stream); break;

@@ -140,6 +140,51 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const half_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// K3 of the VGG family: maxpool 2x2 stride 2 (nn.MaxPool2d(2, 2), no padding) on split planes.  One thread = 8 channels of one
+// output pixel; the output pair is the (hi, lo) pair of the input element with the largest hi + lo (the first one on a tie), so the
+// merged output equals F.max_pool2d of the merged planes bit for bit.  Offsets are 64-bit: one plane of a 224x224x64 map passes
+// 2^31 elements from 669 images on.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void maxpool2x2s2_kernel(const half_t* __restrict__ in_hi,
+                                                            const half_t* __restrict__ in_lo,
+                                                            half_t* __restrict__ out_hi,
+                                                            half_t* __restrict__ out_lo, int B, int hin,
+                                                            int c) {
+    const int ho = hin / 2;
+    const int cg = c / 8;
+    const size_t total = (size_t)B * ho * ho * cg;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t g = t % cg;
+        const size_t pix = t / cg;                      // output pixel: (n * ho + oy) * ho + ox
+        const size_t ox = pix % ho;
+        const size_t ny = pix / ho;                     // n * ho + oy: input row 2 * ny of the image-stacked map
+        const size_t i00 = ((2 * ny) * hin + 2 * ox) * c + g * 8;
+        const size_t at[4] = {i00, i00 + c, i00 + (size_t)hin * c, i00 + (size_t)hin * c + c};
+        h8 bh = *(const h8*)(in_hi + at[0]);
+        h8 bl = *(const h8*)(in_lo + at[0]);
+        float best[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) best[j] = (float)bh[j] + (float)bl[j];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+            const h8 vh = *(const h8*)(in_hi + at[q]);
+            const h8 vl = *(const h8*)(in_lo + at[q]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (float)vh[j] + (float)vl[j];
+                const bool take = v > best[j];
+                best[j] = take ? v : best[j];
+                bh[j] = take ? vh[j] : bh[j];
+                bl[j] = take ? vl[j] : bl[j];
+            }
+        }
+        const size_t o = pix * c + g * 8;
+        *(h8*)(out_hi + o) = bh;
+        *(h8*)(out_lo + o) = bl;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // K4a: global average pool [B][hw][c] -> [B][c] (one thread = 8 channels of one image)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void global_avgpool_kernel(const half_t* __restrict__ in_hi,

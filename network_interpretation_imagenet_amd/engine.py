@@ -24,6 +24,8 @@ BN_EPS = 1e-5   # torchvision BatchNorm2d default
 ARCH_IDS = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "resnet101": 101, "resnet152": 152,
             # the reference's two small networks (include/mpx.h MPX_ARCH_*)
             "mnist_net": 1, "cifar_resnet20": 2020, "cifar_resnet56": 2056, "cifar_resnet110": 2110}
+# torchvision's VGG networks (include/mpx.h MPX_ARCH_VGG / MPX_ARCH_VGG_BN + depth), which the reference's `-a` selects as well
+ARCH_IDS.update({"vgg%d%s" % (d, bn): (3100 if bn else 3000) + d for d in (11, 13, 16, 19) for bn in ("", "_bn")})
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -95,15 +97,24 @@ def rank_segments(segments):
 class MaskedForwardEngine:
     """One engine per process per GPU (one RCCL rank).  `arch` is the reference's `-a/--arch`."""
 
-    def __init__(self, arch="resnet101", max_batch=512, device=None, stem=None):
-        """stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
+    def __init__(self, arch="resnet101", max_batch=None, device=None, stem=None):
+        """max_batch: slots of the workspace (masked images per forward); None = 512 for the ResNets and the small networks.  A VGG
+        engine has no default: a VGG slot holds 26.5 MB (two 224x224x64 split-fp16 activation planes and the input staging, 1.8x a
+        ResNet slot), so its caller sizes it -- MaskedForwardEngine("vgg16") raises ValueError, MaskedForwardEngine("vgg16",
+        max_batch=512) is the size INTEGRATION.md 1 suggests.
+        stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
         least `stem_table_min_rows` (256) rows -- decided per image, however the rows are packed into calls and batches --, K0 + the MFMA
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets and VGGs and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+        if max_batch is None:
+            if arch.startswith("vgg"):
+                raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
+                                 "(max_batch=512: 14 GB, INTEGRATION.md 1)" % arch)
+            max_batch = 512
         if not torch.cuda.is_available():
             raise MpxError("no MI355X visible: the scorer has no CPU path")
         self._lib = _lib.load()
@@ -134,9 +145,14 @@ class MaskedForwardEngine:
         self.stem_table_min_rows = 256
         if stem not in (None, "table", "conv"):
             raise ValueError("stem must be 'table' or 'conv', got %r" % (stem,))
-        if self.small and stem == "table":
+        if not self.has_stem_table and stem == "table":
             raise ValueError("%s has no 7x7 stem: stem='table' is the ImageNet ResNets' path" % arch)
-        self.stem = "conv" if self.small else (stem or "table")
+        self.stem = (stem or "table") if self.has_stem_table else "conv"
+
+    @property
+    def has_stem_table(self):
+        """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith("vgg")
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -152,7 +168,7 @@ class MaskedForwardEngine:
             return self.stem_for_rows(rows)
         if stem not in ("table", "conv"):
             raise ValueError("stem must be None, 'table' or 'conv', got %r" % (stem,))
-        if stem == "table" and self.small:
+        if stem == "table" and not self.has_stem_table:
             raise ValueError("%s has no 7x7 stem: stem='table' is the ImageNet ResNets' path" % self.arch)
         return stem
 
@@ -182,8 +198,8 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
-        torch.load(local_path, weights_only=True).  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
+        """`sd`: torchvision ResNet / VGG state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy)."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
@@ -205,8 +221,10 @@ class MaskedForwardEngine:
             name, bn = d.name.decode(), d.bn_name.decode()
             if only is not None and name not in only:
                 continue
-            wshape = (d.cout, d.cin) if (d.ksize == 1 and sd[name + ".weight"].dim() == 2) else (d.cout, d.cin, d.ksize, d.ksize)
-            w = get(name + ".weight", wshape)
+            w4 = (d.cout, d.cin, d.ksize, d.ksize)
+            wshape = (d.cout, d.cin * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
+            # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7], channel-major as torch.flatten of NCHW
+            w = get(name + ".weight", wshape).reshape(w4).contiguous()
             if not bn:          # no BatchNorm: fc, or the MNIST net's conv6 -- the layer's own bias goes in as `beta`
                 b = get(name + ".bias", (d.cout,))
                 args = (_ptr(w), None, None, _ptr(b), None, None)
@@ -323,7 +341,7 @@ class MaskedForwardEngine:
     def stem_planes(self, n=None):
         """Zero-copy fp16 views (hi, lo) [n,56,56,64] of the engine-owned pooled stem output planes (ImageNet ResNets).  For tests."""
         n = self.max_batch if n is None else int(n)
-        if self.small or not 0 < n <= self.max_batch:
+        if not self.has_stem_table or not 0 < n <= self.max_batch:
             raise ValueError("stem_planes: an ImageNet ResNet engine and n in [1, max_batch=%d]" % self.max_batch)
         hi, lo = C.c_void_p(), C.c_void_p()
         _lib.check(self._h, self._lib.mpx_stem_planes(self._h, C.byref(hi), C.byref(lo)), "mpx_stem_planes")

@@ -12,6 +12,11 @@ the class probability would be vacuous:
           running_mean ~ N(0,0.05), running_var ~ U(0.8,1.25)
   fc      N(0, FC_GAIN/sqrt(C)), bias ~ N(0,0.1)
 
+The VGG networks (torchvision cfgs A / B / D / E, plain and _bn) get the same conv / BN draws plus the conv biases torchvision's
+VGG has, N(0, 0.01); classifier.0 / .3 are He-initialised like the convs, classifier.6 as the ResNets' fc.  Without BatchNorm the
+He draws alone keep the trunk's RMS within 0.8 .. 1.3 on the `blobs` images (max |x| ~ 11, far below fp16's 65504) and the softmax
+peak between 0.08 and 0.95 (tests/test_vgg_cpu.py asserts bounds on both).
+
 Images are u8 HWC; `blobs` gives smooth low-frequency content (felzenszwalb-friendly),
 `noise` uniform random bytes (content does not affect timing).
 """
@@ -29,6 +34,22 @@ ARCH_DEPTHS = {
 }
 FC_GAIN = 2.5
 
+# torchvision vgg.py cfgs ("M" = MaxPool2d(2, 2))
+VGG_CFGS = {
+    11: (64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M"),
+    13: (64, 64, "M", 128, 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M"),
+    16: (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"),
+    19: (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"),
+}
+
+
+def vgg_arch(arch):
+    """'vgg16_bn' -> (16, True); None for any other name."""
+    if not arch.startswith("vgg"):
+        return None
+    d, _, bn = arch[3:].partition("_")
+    return (int(d), bn == "bn") if d.isdigit() and int(d) in VGG_CFGS and bn in ("", "bn") else None
+
 
 def _bn(sd, prefix, c, g, last=0.0):
     gamma = torch.empty(c).uniform_(0.9, 1.1, generator=g)
@@ -45,8 +66,39 @@ def _conv(sd, name, cin, cout, k, g):
     sd[name + ".weight"] = torch.randn(cout, cin, k, k, generator=g) * std
 
 
+def make_vgg_state_dict(arch, seed=7):
+    """OrderedDict with the torchvision VGG key set and shapes (models.vgg16_bn().state_dict(): features.i.weight / .bias, the
+    BatchNorm's weight / bias / running_mean / running_var / num_batches_tracked at features.(i+1), classifier.{0,3,6}.weight / .bias)."""
+    depth, bn = vgg_arch(arch)
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    cin, idx = 3, 0
+    for v in VGG_CFGS[depth]:
+        if v == "M":
+            idx += 1
+            continue
+        name = "features.%d" % idx
+        _conv(sd, name, cin, v, 3, g)
+        sd[name + ".bias"] = torch.randn(v, generator=g) * 0.01
+        if bn:
+            _bn(sd, "features.%d" % (idx + 1), v, g)
+            sd["features.%d.num_batches_tracked" % (idx + 1)] = torch.tensor(0, dtype=torch.int64)
+        idx += 3 if bn else 2
+        cin = v
+    feat = cin * 7 * 7
+    sd["classifier.0.weight"] = torch.randn(4096, feat, generator=g) * (2.0 / feat) ** 0.5
+    sd["classifier.0.bias"] = torch.randn(4096, generator=g) * 0.01
+    sd["classifier.3.weight"] = torch.randn(4096, 4096, generator=g) * (2.0 / 4096) ** 0.5
+    sd["classifier.3.bias"] = torch.randn(4096, generator=g) * 0.01
+    sd["classifier.6.weight"] = torch.randn(1000, 4096, generator=g) * (FC_GAIN / 4096 ** 0.5)
+    sd["classifier.6.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
-    """OrderedDict of f32 CPU tensors with the torchvision ResNet key set."""
+    """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict) key set."""
+    if vgg_arch(arch):
+        return make_vgg_state_dict(arch, seed)
     kind, depths = ARCH_DEPTHS[arch]
     exp = 1 if kind == "basic" else 4
     g = torch.Generator().manual_seed(seed)

@@ -51,6 +51,15 @@ enum {
  * 4096 -> 4096; classifier.6 = the logit layer).  AdaptiveAvgPool2d((7, 7)) is the identity at 224 input and Dropout is the identity in
  * eval, so neither is an op.  It stages through mpx_mask_apply_normalize only: it has no 7x7 stem, so the stem-table and stem + pool
  * entry points return MPX_E_STATE.  Its first layer (3 -> 64, 3x3 pad 1) reads the padded NHWC4 staging as the ResNet stem does.
+ * -- or torchvision's AlexNet, the third family the reference's README names for `-a`:
+ *   MPX_ARCH_ALEXNET              alexnet (any other id in [4000, 4100) is MPX_E_ARG)
+ * An AlexNet engine is a plain chain too: features.0 (3 -> 64, 11x11 stride 4 pad 2, 224 -> 55), features.3 (64 -> 192, 5x5 pad 2, 27x27),
+ * features.6 / .8 / .10 (192 -> 384 -> 256 -> 256, 3x3 pad 1, 13x13), each with bias + ReLU, three 3x3 stride-2 max pools WITHOUT padding
+ * (mpx_maxpool3x3s2p0: 55 -> 27 -> 13 -> 6), then classifier.1 = a 6x6 valid conv over the [B][6][6][256] map (K = 9216), classifier.4 =
+ * 1x1 4096 -> 4096, classifier.6 = the logit layer.  AdaptiveAvgPool2d((6, 6)) is the identity at 224 input.  Two activation buffers of
+ * 55 * 55 * 64 elements per image (2.4 MB per slot with the staging).  Like VGG it stages through mpx_mask_apply_normalize only and the
+ * stem-table and stem + pool entry points return MPX_E_STATE.  features.0 reads the padded NHWC4 staging, one run of 16 pixels x 4
+ * channels (two K steps) per kernel row: k_packed = 11 * 64 = 704.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -58,6 +67,7 @@ enum {
 #define MPX_ARCH_CIFAR_RESNET 2000
 #define MPX_ARCH_VGG 3000
 #define MPX_ARCH_VGG_BN 3100
+#define MPX_ARCH_ALEXNET 4000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -83,7 +93,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets and the VGG networks, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks and AlexNet, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -139,7 +149,8 @@ int mpx_last_conv_kernels(const mpx_engine* h);
 /* Host-only packer (no GPU needed; what mpx_set_conv_weights runs before the upload).
  * Produces the fp16 planes w_hi/w_lo of cout_pad x k_packed elements (k order = (ky,kx,ci), ci fastest;
  * for a layer that reads the NHWC4 padded input -- cin == 3 and k_packed == ksize * 32: the ImageNet ResNets' 7x7 stem, the VGG first
- * layer -- k = ky*32 + px*4 + c, one run of 8 pixels x 4 channels per kernel row, zero weights on px >= ksize and c == 3) in PIECE-major order: element (row, k) of a plane is at
+ * layer -- k = ky*32 + px*4 + c, one run of 8 pixels x 4 channels per kernel row, zero weights on px >= ksize and c == 3; for AlexNet's
+ * 11x11 first layer -- cin == 3, ksize == 11 and k_packed == 704 -- k = ky*64 + px*4 + c, one run of 16 pixels per kernel row) in PIECE-major order: element (row, k) of a plane is at
  *   ((((row/16) * (k_packed/32) + k/32) * 16 + row%16) * 4 + ((k/8)%4 ^ (((row%16)/8) * 2))) * 8 + k%8
  * -- [cout_pad/16][k_packed/32][16 rows][four 16-byte chunks, XOR-swizzled by the row], so that each 1-KiB LDS-DMA piece of
  * the conv kernels is one contiguous run of 8 cache lines already in the order of its LDS image (cout_pad % 16 == 0,
@@ -267,6 +278,15 @@ int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
 int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                      void* out_lo, int B, int hin, int c, void* stream);
 
+/* ---- K3 of AlexNet: maxpool 3x3 s2 without padding (nn.MaxPool2d(3, 2)), NHWC split planes [B][hin][hin][c] -> [B][ho][ho][c] with
+ * ho = (hin - 3) / 2 + 1: every window lies inside the map.
+ * replaces: the three MaxPool2d(kernel_size=3, stride=2) of torchvision's AlexNet inside model(masked_img_tensor)
+ *           (generate_gp_training_data_imagenet.py:246).
+ * Bit-exact for any sign: each output (hi, lo) is the pair of the window's element with the largest hi + lo, the first in row-major
+ * order on a tie.  MPX_E_ARG for hin < 3, an even hin (floor mode is not part of the contract) and c not a multiple of 8. */
+int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
+                       void* out_lo, int B, int hin, int c, void* stream);
+
 /* ---- K1 + K3 in one launch: the ImageNet stem and its max pool -------------------------------------------
  * replaces: `x = self.conv1(x); x = self.bn1(x); x = self.relu(x); x = self.maxpool(x)` (torchvision resnet.py, reached through
  *           model(masked_img_tensor), generate_gp_training_data_imagenet.py:246): the 7x7 stride-2 conv + BN + ReLU of layer 0 reads
@@ -306,7 +326,7 @@ int mpx_heatmap_accumulate(mpx_engine* h, const int32_t* seg, const uint8_t* ono
                            const int32_t* label, int M, int S, float* heat, void* stream);
 
 /* ---- introspection for tests / benchmarks --------------------------------------------------- */
-/* DEV pointers of the input staging planes: fp16 [max_batch][230][230][4] (padded NHWC4) for the ImageNet ResNets and VGG, [max_batch][H][W][32] for
+/* DEV pointers of the input staging planes: fp16 [max_batch][230][230][4] (padded NHWC4) for the ImageNet ResNets, VGG and AlexNet, [max_batch][H][W][32] for
  * the small networks.  A pure getter: the record of how each slot was staged is not touched, so a diagnostic call between
  * mpx_stem_table_apply and mpx_forward changes nothing. */
 int mpx_input_planes(const mpx_engine* h, void** hi, void** lo);
@@ -315,7 +335,7 @@ int mpx_input_planes(const mpx_engine* h, void** hi, void** lo);
  * mpx_stem_table_apply (which marks the slots it writes as its own again).  MPX_E_ARG outside [0, max_batch). */
 int mpx_mark_input_staged(mpx_engine* h, int slot0, int M);
 /* DEV pointers of the pooled stem output planes: fp16 [max_batch][56][56][64], written by the stem + max pool launch of mpx_forward or by
- * mpx_stem_table_apply (NULL for the small networks and VGG, which have no such stem). */
+ * mpx_stem_table_apply (NULL for the small networks, VGG and AlexNet, which have no such stem). */
 int mpx_stem_planes(const mpx_engine* h, void** hi, void** lo);
 /* When enabled, every kernel launch of mpx_forward / mpx_mask_apply_normalize is bracketed by
  * HIP events on the launch stream (bounded pool; launches beyond it are not recorded). */

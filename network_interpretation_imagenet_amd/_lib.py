@@ -65,6 +65,7 @@ SIGNATURES = {
     "mpx_stem_conv_maxpool": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mpx_maxpool3x3s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_maxpool2x2s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_maxpool3x3s2p0": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_global_avgpool": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_head_softmax_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mpx_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -31,9 +31,10 @@ constexpr int kStemK = 7;
 constexpr int kProfilePairs = 4096;
 constexpr size_t kActElemsPerImage = 112 * 112 * 64;   // ImageNet: largest activation (stem output, = 56*56*256)
 constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel maps of the first stage
+constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output of features.0
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
-enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6 };
+enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -98,6 +99,7 @@ struct mpx_engine {
     int img = MPX_IMG, in_ch = 3, ncls = MPX_NUM_CLASSES, logit_pitch = MPX_NUM_CLASSES;
     bool small = false;
     bool vgg = false;               // torchvision VGG: a plain chain, two activation buffers, no 7x7 stem
+    bool alexnet = false;           // torchvision AlexNet: as VGG a plain chain over two activation buffers, staged through K0 only
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -191,11 +193,13 @@ int default_tile(const mpx_conv_desc& d);
 // torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
 int build_topology_small(mpx_engine* h);
 int build_topology_vgg(mpx_engine* h);
+int build_topology_alexnet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
         return build_topology_small(h);
     if (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) return build_topology_vgg(h);
+    if (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) return build_topology_alexnet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -568,6 +572,62 @@ int build_topology_vgg(mpx_engine* h) {
     return 0;
 }
 
+// torchvision AlexNet (alexnet.py): features = conv 11x11/4 pad 2 (3 -> 64), ReLU, MaxPool2d(3, 2), conv 5x5 pad 2 (64 -> 192), ReLU,
+// MaxPool2d(3, 2), conv 3x3 pad 1 (192 -> 384), ReLU, conv 3x3 pad 1 (384 -> 256), ReLU, conv 3x3 pad 1 (256 -> 256), ReLU, MaxPool2d(3, 2);
+// maps 224 -> 55 -> 27 -> 27 -> 13 -> 13 -> 13 -> 13 -> 6.  No BatchNorm, every layer has a bias.  The classifier runs as three more
+// layers of the conv list, as VGG's: classifier.1 = Linear(9216, 4096) as a 6x6 valid conv over the [B][6][6][256] map (the [4096][9216]
+// weight viewed as [4096][256][6][6] is its OIHW weight), classifier.4 = Linear(4096, 4096) as a 1x1 conv, classifier.6 = the logit layer.
+// AdaptiveAvgPool2d((6, 6)) on a 6x6 map and Dropout in eval are identities.  The op list ping-pongs between two activation buffers.
+int build_topology_alexnet(mpx_engine* h) {
+    if (h->arch != MPX_ARCH_ALEXNET) return MPX_E_ARG;
+    h->alexnet = true;
+    h->n_act_bufs = 2;
+    h->act_elems_per_image = kAlexActElemsPerImage;
+    auto add_conv = [&](const char* name, int cin, int cout, int k, int stride, int pad, int hin, int relu, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = relu;
+        L.has_bias = true;
+        L.is_fc = fc;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 16-pixel x 4-channel run (two K steps) per kernel row
+        L.cin_pad = cin;
+        L.cout_store = cout;
+        L.d.k_packed = L.is_stem ? k * 64 : k * k * cin;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    int X = BUF_INPUT, hcur = MPX_IMG, ccur = 3;
+    auto conv = [&](const char* name, int cout, int k, int stride, int pad, int relu = 1, bool fc = false) {
+        const int O = fc ? BUF_NONE : (X == 0 ? 1 : 0);
+        const int c = add_conv(name, ccur, cout, k, stride, pad, hcur, relu, fc);
+        h->ops.push_back(Op{OP_CONV, c, X, O, BUF_NONE, 0, 0, BUF_NONE});
+        hcur = h->convs[c].d.hout; ccur = cout; X = O;
+    };
+    auto pool = [&]() {
+        const int O = X == 0 ? 1 : 0;
+        h->ops.push_back(Op{OP_MAXPOOL3P0, -1, X, O, BUF_NONE, hcur, ccur, BUF_NONE});
+        hcur = (hcur - 3) / 2 + 1; X = O;
+    };
+    conv("features.0", 64, 11, 4, 2);       // 224 -> 55
+    pool();                                 // 55 -> 27
+    conv("features.3", 192, 5, 1, 2);
+    pool();                                 // 27 -> 13
+    conv("features.6", 384, 3, 1, 1);
+    conv("features.8", 256, 3, 1, 1);
+    conv("features.10", 256, 3, 1, 1);
+    pool();                                 // 13 -> 6
+    conv("classifier.1", 4096, hcur, 1, 0); // 6x6 valid conv: K = 9216
+    conv("classifier.4", 4096, 1, 1, 0);
+    conv("classifier.6", MPX_NUM_CLASSES, 1, 1, 0, 0, true);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -861,10 +921,20 @@ int default_tile(const mpx_conv_desc& d) {
     // ... as one persistent workgroup per CU (mpx_conv3pp.h) where the layer has no residual operand: in the network (batch 2340,
     // A/B in one call) 128->128 on 28x28 3.89 -> 3.67 ms, 256->256 on 14x14 24.65 -> 24.49 ms per batch; 7x7 maps lose 1 % (2.29 -> 2.32)
 #ifndef MPX_PROBE_NO_PERSISTENT_PATCH   // A/B builds only (tools/ab_lib.sh)
-    if (patchp_eligible(d) && d.hout >= 14) return 12;
+    // ... and on AlexNet's 13x13 maps (the only maps between 7 and 14 in any network here) where the cout tiles are a power of two, so that
+    // the persistent grid fills every CU: in the network at batch 2340, on two boxes, 384->256 1.344 -> 1.285 / 1.404 -> 1.383 ms, 256->256
+    // 0.931 -> 0.873 / 0.978 -> 0.945.  192->384 is three cout tiles, a grid of 240 of the 256 CUs: 1.118 -> 1.084 on one box, 1.158 -> 1.184
+    // on the other, so it keeps tile 6.  (Under three rounds of tiles the persistent form loses: 4-7 % at batch 512, 0-3 % at 1024.)
+    if (patchp_eligible(d) && (d.hout >= 14 || (d.hout == 13 && ((d.cout / 128) & (d.cout / 128 - 1)) == 0))) return 12;
 #endif
     if (patch_eligible(d)) return 6;                      // 3x3 stride 1 on 28x28 / 14x14 / 7x7 maps: -10..18 % against tile 0
     if (d.ksize == 3) return 0;
+    // AlexNet's two layers with kernel sizes no other network here has (tools/layer_profile.py alexnet B with MPX_TILE_SWEEP=1, in the
+    // network).  5x5 64->192: three 64-row cout tiles instead of two 128-row ones a quarter of whose MFMA rows are padding -- tile 7 -> 1
+    // 2.915 -> 2.703 ms at batch 2340, 1.280 -> 1.188 at 1024, 0.662 -> 0.622 at 512.  classifier.1 (6x6 valid conv, K = 9216): long K, so the
+    // four waves per SIMD of tile 7 cover nothing -- tile 7 -> 2 0.551 -> 0.544 ms at 2340, 0.268 -> 0.263 at 1024, a tie at 512
+    if (d.ksize == 5 && d.cout % 128 != 0 && d.cout % 64 == 0) return 1;
+    if (d.ksize == 6) return 2;
     // expanding 1x1 layers (short K, long epilogue): four waves per SIMD cover the epilogue better, -2..4 % in the
     // network; the reducing ones (long K) gain nothing from it
     // ... and on 28x28 / 14x14 maps with K >= 128 the persistent pipelined kernel (mpx_convx.h) is 2-4 % faster still in the
@@ -904,10 +974,11 @@ int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const ha
         // a K step is one kernel row: a run of 8 pixels x 4 channels starting at the window's left edge in the staging, whose
         // 3-pixel border already holds the padding (the 7x7 stem's pad 3: origin shift 0; the VGG 3x3 pad-1 layer: -2).  A run that
         // passes a row's end reads the next row of the same image (row 2y + 3 + ky <= 229 for the stem, y + 2 + ky <= 227 for VGG),
-        // and meets the zero weights of px >= ksize.
+        // and meets the zero weights of px >= ksize.  AlexNet's 11-wide row is two K steps, a run of 16 pixels (k_per_tap = 64; the
+        // kernel walks c0 = 0, 32 within a tap): origin shift -1, columns 4x + 1 .. 4x + 16 <= 232, rows 4y + 1 + ky <= 227.
         p.x_hi = h->in_hi; p.x_lo = h->in_lo;
         p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
-        p.kh = L.d.ksize; p.kw = 1; p.stride = L.d.stride; p.pad = L.d.pad - (MPX_IMG_PAD - MPX_IMG) / 2; p.k_per_tap = 32;
+        p.kh = L.d.ksize; p.kw = 1; p.stride = L.d.stride; p.pad = L.d.pad - (MPX_IMG_PAD - MPX_IMG) / 2; p.k_per_tap = L.d.k_packed / L.d.ksize;
     } else {
         p.x_hi = in_hi; p.x_lo = in_lo;
         p.hin = L.d.hin; p.win = L.d.hin; p.pix_stride = L.cin_pad;
@@ -1161,7 +1232,10 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
     // row-run layout (the layers that read the padded NHWC4 staging: the 7x7 stem, K = 224, and the VGG 3x3 first layer, K = 96): one
     // 32-wide K step per kernel row, 8 pixels x 4 channels.  (The CIFAR ResNet's 3-channel conv1 reads [H][W][32] planes: K = 288.)  Odd
     // k in [3, 7] only: no descriptor the generic layout accepts (k = 1, 2, 4, 8 with K = k * 32) changes meaning.
-    const bool stem = (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7);
+    // AlexNet's 11x11 first layer is the two-run form: 16 pixels x 4 channels = two K steps per kernel row, K = 11 * 64 = 704 (a
+    // descriptor the generic layout refuses: 704 is not 121 * cin_pad).
+    const int run = (cin == 3 && k == 11 && K == 11 * 64) ? 64 : 32;
+    const bool stem = run == 64 || (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7);
     if (cin == 3 && k == kStemK && !stem) return MPX_E_ARG;
     // K = k*k*cin_pad: the input planes may carry more channels per pixel than the layer reads (small nets pad to 32)
     const int cin_pad = stem ? 0 : K / (k * k);
@@ -1193,7 +1267,7 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
         if (stem) {
             for (int ky = 0; ky < k; ++ky)
                 for (int px = 0; px < k; ++px)
-                    for (int c = 0; c < 3; ++c) put(ky * 32 + px * 4 + c, wc[((size_t)c * k + ky) * k + px]);
+                    for (int c = 0; c < 3; ++c) put(ky * run + px * 4 + c, wc[((size_t)c * k + ky) * k + px]);
         } else {
             for (int ky = 0; ky < k; ++ky)
                 for (int kx = 0; kx < k; ++kx)
@@ -1464,7 +1538,7 @@ int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const flo
 int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg, int S,
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg ? " (VGG stages through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet ? " (VGG and AlexNet stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -1645,6 +1719,23 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     return 0;
 }
 
+int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin,
+                       int c, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin < 3 || !(hin & 1) || c <= 0 || (c & 7))
+        return fail(h, MPX_E_ARG, "maxpool3x3s2p0: bad arguments (hin odd and >= 3, c multiple of 8)");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1);
+    const int ho = (hin - 3) / 2 + 1;
+    const size_t total = (size_t)B * ho * ho * (c / 8);
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
+    hipLaunchKernelGGL(maxpool3x3s2p0_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
+                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
                        int c, void* stream) {
     if (!h) return MPX_E_ARG;
@@ -1746,6 +1837,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 rc = mpx_maxpool3x3s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream);
                 break;
             case OP_MAXPOOL2: rc = mpx_maxpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
+            case OP_MAXPOOL3P0: rc = mpx_maxpool3x3s2p0(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
             case OP_AVGPOOL: rc = mpx_global_avgpool(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
             case OP_HEAD: rc = mpx_head_softmax_gather(h, logits, label, score, pred, B, stream); break;
             case OP_AVGPAD: rc = mpx_avgpool2_pad(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c >> 16, o.c & 0xffff, stream); break;

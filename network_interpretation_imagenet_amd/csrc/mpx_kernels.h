@@ -184,6 +184,51 @@ __global__ __launch_bounds__(256) void maxpool2x2s2_kernel(const half_t* __restr
     }
 }
 
+// 3x3 stride-2 max pool WITHOUT padding (AlexNet's MaxPool2d(3, 2)) on split-fp16 NHWC planes: ho = (hin - 3) / 2 + 1 with hin odd, so
+// every window lies inside the map.  One thread = 8 channels of an output pixel (16-byte loads and stores, 64-bit offsets, grid-stride).
+// As the 2x2 kernel it copies the (hi, lo) PAIR of the window's largest hi + lo (the sum of two fp16 is exact in fp32), the first in
+// row-major window order on a tie, so the merged output is max_pool2d of the merged input bit for bit, for any sign.
+__global__ __launch_bounds__(256) void maxpool3x3s2p0_kernel(const half_t* __restrict__ in_hi,
+                                                              const half_t* __restrict__ in_lo,
+                                                              half_t* __restrict__ out_hi,
+                                                              half_t* __restrict__ out_lo, int B, int hin,
+                                                              int c) {
+    const int ho = (hin - 3) / 2 + 1;
+    const int cg = c / 8;
+    const size_t total = (size_t)B * ho * ho * cg;
+    const size_t row = (size_t)hin * c;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t g = t % cg;
+        const size_t pix = t / cg;                      // output pixel: (n * ho + oy) * ho + ox
+        const size_t ox = pix % ho;
+        const size_t ny = pix / ho;
+        const size_t n = ny / ho, oy = ny - n * ho;
+        const size_t i00 = ((n * hin + 2 * oy) * hin + 2 * ox) * c + g * 8;     // rows 2oy .. 2oy + 2 <= hin - 1, columns likewise
+        h8 bh = *(const h8*)(in_hi + i00);
+        h8 bl = *(const h8*)(in_lo + i00);
+        float best[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) best[j] = (float)bh[j] + (float)bl[j];
+#pragma unroll
+        for (int q = 1; q < 9; ++q) {
+            const size_t at = i00 + (q / 3) * row + (size_t)(q % 3) * c;
+            const h8 vh = *(const h8*)(in_hi + at);
+            const h8 vl = *(const h8*)(in_lo + at);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (float)vh[j] + (float)vl[j];
+                const bool take = v > best[j];
+                best[j] = take ? v : best[j];
+                bh[j] = take ? vh[j] : bh[j];
+                bl[j] = take ? vl[j] : bl[j];
+            }
+        }
+        const size_t o = pix * c + g * 8;
+        *(h8*)(out_hi + o) = bh;
+        *(h8*)(out_lo + o) = bl;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // K4a: global average pool [B][hw][c] -> [B][c] (one thread = 8 channels of one image)
 // ------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ ARCH_IDS = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "resnet101": 101, "r
             "mnist_net": 1, "cifar_resnet20": 2020, "cifar_resnet56": 2056, "cifar_resnet110": 2110}
 # torchvision's VGG networks (include/mpx.h MPX_ARCH_VGG / MPX_ARCH_VGG_BN + depth), which the reference's `-a` selects as well
 ARCH_IDS.update({"vgg%d%s" % (d, bn): (3100 if bn else 3000) + d for d in (11, 13, 16, 19) for bn in ("", "_bn")})
+ARCH_IDS["alexnet"] = 4000      # torchvision's AlexNet (MPX_ARCH_ALEXNET), the third family the reference's README names
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -101,7 +102,7 @@ class MaskedForwardEngine:
         """max_batch: slots of the workspace (masked images per forward); None = 512 for the ResNets and the small networks.  A VGG
         engine has no default: a VGG slot holds 26.5 MB (two 224x224x64 split-fp16 activation planes and the input staging, 1.8x a
         ResNet slot), so its caller sizes it -- MaskedForwardEngine("vgg16") raises ValueError, MaskedForwardEngine("vgg16",
-        max_batch=512) is the size INTEGRATION.md 1 suggests.
+        max_batch=512) is the size INTEGRATION.md 1 suggests.  An AlexNet slot holds 2.4 MB and keeps the default of 512.
         stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
@@ -109,7 +110,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets and VGGs and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs and AlexNet and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if max_batch is None:
             if arch.startswith("vgg"):
                 raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
@@ -151,8 +152,8 @@ class MaskedForwardEngine:
 
     @property
     def has_stem_table(self):
-        """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith("vgg")
+        """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -198,7 +199,7 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet / VGG state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy)."""
@@ -223,7 +224,7 @@ class MaskedForwardEngine:
                 continue
             w4 = (d.cout, d.cin, d.ksize, d.ksize)
             wshape = (d.cout, d.cin * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
-            # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7], channel-major as torch.flatten of NCHW
+            # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7] (AlexNet's classifier.1 [4096, 256 * 6 * 6]), channel-major as torch.flatten of NCHW
             w = get(name + ".weight", wshape).reshape(w4).contiguous()
             if not bn:          # no BatchNorm: fc, or the MNIST net's conv6 -- the layer's own bias goes in as `beta`
                 b = get(name + ".bias", (d.cout,))

@@ -17,6 +17,9 @@ VGG has, N(0, 0.01); classifier.0 / .3 are He-initialised like the convs, classi
 He draws alone keep the trunk's RMS within 0.8 .. 1.3 on the `blobs` images (max |x| ~ 11, far below fp16's 65504) and the softmax
 peak between 0.08 and 0.95 (tests/test_vgg_cpu.py asserts bounds on both).
 
+AlexNet (make_alexnet_state_dict) gets He draws for its five convs and classifier.1 / .4, biases N(0, 0.01) and classifier.6 as the
+ResNets' fc: post-ReLU RMS 0.95 .. 2.2, max |x| ~ 13, softmax peak ~ 0.45 on the `blobs` images (tests/test_alexnet_cpu.py).
+
 Images are u8 HWC; `blobs` gives smooth low-frequency content (felzenszwalb-friendly),
 `noise` uniform random bytes (content does not affect timing).
 """
@@ -95,10 +98,35 @@ def make_vgg_state_dict(arch, seed=7):
     return sd
 
 
+# torchvision alexnet.py: (module index, cin, cout, kernel) of the five convs of `features`
+ALEXNET_CONVS = ((0, 3, 64, 11), (3, 64, 192, 5), (6, 192, 384, 3), (8, 384, 256, 3), (10, 256, 256, 3))
+
+
+def make_alexnet_state_dict(seed=7):
+    """OrderedDict with torchvision's AlexNet key set and shapes (models.alexnet().state_dict(): features.{0,3,6,8,10}.weight / .bias,
+    classifier.{1,4,6}.weight / .bias; classifier.1 is Linear(256 * 6 * 6, 4096))."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    for idx, cin, cout, k in ALEXNET_CONVS:
+        name = "features.%d" % idx
+        _conv(sd, name, cin, cout, k, g)
+        sd[name + ".bias"] = torch.randn(cout, generator=g) * 0.01
+    feat = 256 * 6 * 6
+    sd["classifier.1.weight"] = torch.randn(4096, feat, generator=g) * (2.0 / feat) ** 0.5
+    sd["classifier.1.bias"] = torch.randn(4096, generator=g) * 0.01
+    sd["classifier.4.weight"] = torch.randn(4096, 4096, generator=g) * (2.0 / 4096) ** 0.5
+    sd["classifier.4.bias"] = torch.randn(4096, generator=g) * 0.01
+    sd["classifier.6.weight"] = torch.randn(1000, 4096, generator=g) * (FC_GAIN / 4096 ** 0.5)
+    sd["classifier.6.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
-    """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict) key set."""
+    """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict) key set."""
     if vgg_arch(arch):
         return make_vgg_state_dict(arch, seed)
+    if arch == "alexnet":
+        return make_alexnet_state_dict(seed)
     kind, depths = ARCH_DEPTHS[arch]
     exp = 1 if kind == "basic" else 4
     g = torch.Generator().manual_seed(seed)

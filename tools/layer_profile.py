@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Per-layer conv timing (HIP events inside the engine) for one forward batch.
-usage: python tools/layer_profile.py [arch] [batch] [reps]"""
+usage: python tools/layer_profile.py [arch] [batch] [reps]
+       MPX_PER_LAYER=1 ...    one row per conv with its tile
+       MPX_TILE_SWEEP=1 ...   after the table: one row per conv with the in-network time of EVERY tile mpx_set_conv_tile accepts for it, two
+                              repeats each (the spread between them is what a default may lose by)"""
 import os
 import sys
 
@@ -119,3 +122,27 @@ print("layer1 (+ layer2.0.conv1): %.3f ms/batch" % layer1)
 allfl = eng.flops_per_forward * batch
 print("conv total %.3f ms/batch -> %.1f TFLOP/s algorithmic; other kinds ms/batch: %s" % (
     tot, allfl / tot / 1e9, {k: round(v / reps, 3) for k, v in prof["ms"].items()}))
+
+if os.environ.get("MPX_TILE_SWEEP"):     # tool-only: every eligible tile of every layer, in the network, one layer changed at a time
+    def layer_ms(li):
+        eng.profile(True)
+        for _ in range(reps):
+            stage()
+            eng.forward(batch, labels)
+        eng.profile(False)
+        return eng.collect_profile()["per_conv_ms"][li] / reps
+
+    print("-- every eligible tile, ms per batch in the network (two repeats); * = default --")
+    for li, d in enumerate(eng.layers):
+        default = eng.conv_tile(li)
+        cells = []
+        for t in (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14):
+            try:
+                eng.set_conv_tile(li, t)
+            except MpxError:
+                continue
+            stage()
+            eng.forward(batch, labels)          # warm this kernel
+            cells.append("%s%d: %.3f %.3f" % ("*" if t == default else "", t, layer_ms(li), layer_ms(li)))
+        eng.set_conv_tile(li, -1)
+        print("%-14s %5d->%-5d k%-2d s%d out%-3d  %s" % (d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hout, " | ".join(cells)))

@@ -60,6 +60,21 @@ enum {
  * 55 * 55 * 64 elements per image (2.4 MB per slot with the staging).  Like VGG it stages through mpx_mask_apply_normalize only and the
  * stem-table and stem + pool entry points return MPX_E_STATE.  features.0 reads the padded NHWC4 staging, one run of 16 pixels x 4
  * channels (two K steps) per kernel row: k_packed = 11 * 64 = 704.
+ * -- or one of torchvision's DenseNets with growth rate 32, the last classic family the reference's `-a` reaches (it also carries one of its
+ * own: models/densenet.py):
+ *   MPX_ARCH_DENSENET + depth     densenet121 / densenet169 / densenet201 (block sizes (6, 12, 24, 16) / (6, 12, 32, 32) / (6, 12, 48, 32));
+ *                                 any other id in [5000, 6000) is MPX_E_ARG (densenet161 -- growth rate 48, 96 initial features -- included)
+ * A DenseNet engine runs the ResNet stem shape (features.conv0 3 -> 64 7x7 stride 2 + norm0 + ReLU + MaxPool(3, 2, 1): the fused stem + pool
+ * launch), then four dense blocks.  A dense layer is norm1 -> ReLU -> conv1 (1x1, C -> 128) -> norm2 -> ReLU -> conv2 (3x3 pad 1, 128 -> 32),
+ * its 32 channels concatenated behind its C input channels.  BatchNorm + ReLU sit BEFORE conv1, and every later layer normalises the same
+ * concatenation with statistics of its own, so they cannot ride in a producer's epilogue: the engine keeps the block's concatenation raw
+ * ([B][H][W][C_block], channel-strided) and runs mpx_concat_bn_relu once per dense layer -- it appends conv2's output to the concatenation and
+ * writes relu(bn(.)) of the first C channels as the dense operand of the next conv1 / transition conv / the head.  norm2 + ReLU are conv1's
+ * epilogue; conv2 has neither BatchNorm nor ReLU nor bias.  A transition is norm -> ReLU -> conv (1x1, C -> C / 2, no bias) ->
+ * mpx_avgpool2x2s2; the head is norm5 -> ReLU -> mpx_global_avgpool -> classifier (Linear(C_final, 1000), the logit layer).  The
+ * stand-alone BatchNorms (every norm1, each transition's norm, norm5) belong to no conv: mpx_num_norms / mpx_norm_info / mpx_load_norm.
+ * Four ResNet-sized activation buffers (14.5 MB per slot with the staging and the pooled stem planes).  It stages through
+ * mpx_mask_apply_normalize only: the stem-table entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -68,6 +83,7 @@ enum {
 #define MPX_ARCH_VGG 3000
 #define MPX_ARCH_VGG_BN 3100
 #define MPX_ARCH_ALEXNET 4000
+#define MPX_ARCH_DENSENET 5000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -93,7 +109,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks and AlexNet, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet and the DenseNets, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -111,7 +127,23 @@ int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
  * uploads synchronously. */
 int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv_bias, const float* gamma,
                          const float* beta, const float* mean, const float* var, float eps);
-int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has weights */
+int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has weights (and every stand-alone BatchNorm its vectors) */
+
+/* ---- stand-alone BatchNorms (DenseNet) -------------------------------------------------------
+ * Norm k in [0, mpx_num_norms): the BatchNorm2d modules that precede their conv, in forward order ("features.denseblock1.denselayer1.norm1",
+ * ..., "features.transition1.norm", ..., "features.norm5"); 0 norms on every other architecture.  mpx_load_norm takes the HOST f32[channels]
+ * tensors of torchvision's state_dict (<name>.weight / .bias / .running_mean / .running_var) and uploads, synchronously, the fp32 vectors
+ * scale = gamma / sqrt(var + eps), shift = beta - mean * scale (computed in double, rounded once).  mpx_norm_params returns their DEV
+ * pointers (f32[channels] each; what mpx_forward hands to mpx_concat_bn_relu). */
+typedef struct mpx_norm_desc {
+    char name[64];       /* torchvision state_dict prefix of the BatchNorm */
+    int32_t channels;    /* C: the channels of the concatenation it normalises */
+    int32_t hw;          /* side of the square map it runs on at 224x224 input */
+} mpx_norm_desc;
+int mpx_num_norms(const mpx_engine* h);
+int mpx_norm_info(const mpx_engine* h, int k, mpx_norm_desc* out);
+int mpx_load_norm(mpx_engine* h, int k, const float* gamma, const float* beta, const float* mean, const float* var, float eps);
+int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float** shift);
 
 /* Kernel variant of layer i (tuning / test hook; results are identical up to fp32 summation order).  The ids are exactly the
  * kernels some layer class runs by default:
@@ -134,7 +166,8 @@ int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has wei
  *       eligible for 9 without a residual operand: their default; bit-identical to 9);
  *  12 = the patch kernel (6) as ONE persistent workgroup per CU: weight ring and patch buffers run on across tiles, register
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
- * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default.  (Ids 3, 5, 8 and 11 of
+ * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default (a DenseNet's conv2, 3x3 128 -> 32,
+ * defaults to 6, its topology's own choice: the cout <= 64 rule above was judged on 64 -> 64 layers and would give it 1).  (Ids 3, 5, 8 and 11 of
  * earlier rounds -- kernels that were measured and never became a default -- were removed; commit e4ccec8 is the last that has
  * them.)  A non-default tile on a layer of a block tail makes mpx_forward run that block layer by
  * layer (mpx_bottleneck_tail). */
@@ -287,6 +320,31 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
 int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                        void* out_lo, int B, int hin, int c, void* stream);
 
+/* ---- DenseNet: concat-append + BatchNorm + ReLU on split planes ---------------------------------------------
+ * replaces: `torch.cat(features, 1)` of a dense block (torchvision densenet.py _DenseBlock.forward / _DenseLayer.bn_function) for ONE new
+ *           feature and the `relu(norm(.))` that the next consumer applies to the concatenation -- the next layer's norm1 + relu1, a
+ *           transition's norm + relu, or features.norm5 + F.relu -- inside model(masked_img_tensor)
+ *           (generate_gp_training_data_imagenet.py:246).
+ * fresh_hi|lo: DEV planes [npix][fresh_stride] whose first g channels are the new feature (NULL, NULL with g = 0: nothing to append).
+ * raw_hi|lo:   DEV planes [npix][c_total], the block's raw concatenation; channels [c_old, c_old + g) receive the fresh (hi, lo) pairs bit
+ *              for bit, no other element is written.
+ * out_hi|lo:   DEV planes [npix][c_norm], dense: split(relu(scale[c] * (hi + lo) + shift[c])) of channels [0, c_norm) of the concatenation
+ *              as it is after the append, in fp32 (hi + lo is exact; one multiply, one add, the re-split).  NULL, NULL with c_norm = 0 and
+ *              scale = shift = NULL: append only.  scale / shift: DEV f32[c_norm] (mpx_norm_params).
+ * With both, c_norm == c_old + g (the fresh channels are read once, from fresh_*); without fresh, c_norm <= c_total.  ONE launch either
+ * way.  Every channel count and stride is a multiple of 8 and every pointer 16-byte aligned (16-byte accesses), npix > 0; else MPX_E_ARG.
+ * The three plane pairs must not overlap.  Offsets are 64-bit. */
+int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo, int g, int fresh_stride, void* raw_hi, void* raw_lo,
+                       int c_total, int c_old, const float* scale, const float* shift, void* out_hi, void* out_lo, int c_norm,
+                       long long npix, void* stream);
+
+/* ---- DenseNet transitions: average pool 2x2 s2 (nn.AvgPool2d(2, 2)), NHWC split planes [B][hin][hin][c] -> [B][hin/2][hin/2][c].
+ * replaces: `pool` of torchvision's _Transition inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * Each output is split(0.25 * (((x00 + x01) + x10) + x11)) of the merged taps in fp32.  MPX_E_ARG for hin odd or <= 0 and c not a
+ * positive multiple of 8. */
+int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
+                     void* stream);
+
 /* ---- K1 + K3 in one launch: the ImageNet stem and its max pool -------------------------------------------
  * replaces: `x = self.conv1(x); x = self.bn1(x); x = self.relu(x); x = self.maxpool(x)` (torchvision resnet.py, reached through
  *           model(masked_img_tensor), generate_gp_training_data_imagenet.py:246): the 7x7 stride-2 conv + BN + ReLU of layer 0 reads
@@ -345,6 +403,10 @@ int mpx_profile_enable(mpx_engine* h, int on);
  * 3 = head (K4b).  per_conv_ms (HOST f64[mpx_num_convs], may be NULL) gets the per-layer split. */
 int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4],
                         double* per_conv_ms);
+/* The same with the split of kind 2 that a DenseNet engine adds: per_norm_ms (HOST f64[mpx_num_norms], may be NULL) gets the
+ * mpx_concat_bn_relu launch of every stand-alone BatchNorm, avgpool2_ms (HOST f64[1], may be NULL) the transitions' average pools. */
+int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                           double* per_norm_ms, double* avgpool2_ms);
 /* Algorithmic FLOPs (2*MAC, convs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 

@@ -31,6 +31,10 @@ class ConvDesc(C.Structure):
                 ("k_packed", C.c_int32), ("cout_pad", C.c_int32)]
 
 
+class NormDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 64), ("channels", C.c_int32), ("hw", C.c_int32)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -76,6 +80,15 @@ SIGNATURES = {
     "mpx_profile_enable": (_i, [_vp, _i]),
     "mpx_profile_collect": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "mpx_flops_per_forward": (C.c_double, [_vp]),
+    # DenseNet: the stand-alone BatchNorms, concat-append + BN + ReLU, the transitions' average pool
+    "mpx_num_norms": (_i, [_vp]),
+    "mpx_norm_info": (_i, [_vp, _i, C.POINTER(NormDesc)]),
+    "mpx_load_norm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f]),
+    "mpx_norm_params": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "mpx_concat_bn_relu": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, C.c_longlong, _vp]),
+    "mpx_avgpool2x2s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_profile_collect_ex": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)]),
 }
 
 _lib = None

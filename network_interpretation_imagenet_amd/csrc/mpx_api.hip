@@ -34,7 +34,8 @@ constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel m
 constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output of features.0
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
-enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7 };
+enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -50,6 +51,7 @@ struct ConvLayer {
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
     int cout_store = 0;     // channels per pixel of the output planes (row pitch and store bound)
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
+    int tile_default = -1;  // the layer's default where the topology sets one of its own (DenseNet's conv2); -1: default_tile(d)
     // downsample fusion (bottleneck blocks): the block's last 1x1 conv ("main") and its downsample 1x1 conv ("ds")
     // run as ONE launch over the K-concatenation [W3 * s3/s | Wds * sds/s] (build_fused)
     int fuse_partner = -1;  // main -> ds layer index, ds -> main layer index
@@ -71,6 +73,16 @@ struct Op {
     int in2;        // fused main conv: buffer of the block input (the downsample branch's operand), else BUF_NONE
     int z = BUF_NONE;   // OP_BTAIL: buffer of the next block's conv1 output; `conv` = index into mpx_engine::tails,
                         // in = t1, res = block input / identity, out = block output
+    int g = 0, ctot = 0;    // OP_CATNORM (DenseNet): `conv` = index into mpx_engine::norms, in = the fresh g channels, res = the block's raw
+                            // concatenation (ctot channels per pixel), out = the normalised first c channels, hin = the map's side
+};
+
+// A BatchNorm that precedes its conv (DenseNet: every norm1, each transition's norm, norm5): fp32 scale / shift vectors of its own.
+struct NormLayer {
+    mpx_norm_desc d;
+    float* scale = nullptr;
+    float* shift = nullptr;
+    bool loaded = false;
 };
 
 // A 64-channel bottleneck block whose tail runs as ONE launch (mpx_btail.h): conv2 -> conv3 (+ identity or K-concatenated
@@ -87,6 +99,7 @@ struct ProfRec {
     hipEvent_t t0, t1;
     int kind;
     int conv;
+    int sub;        // kind 2 on a DenseNet engine: -1 = any pool, -2 = a transition's average pool, k >= 0 = the launch of norm k
 };
 
 }  // namespace
@@ -100,6 +113,8 @@ struct mpx_engine {
     bool small = false;
     bool vgg = false;               // torchvision VGG: a plain chain, two activation buffers, no 7x7 stem
     bool alexnet = false;           // torchvision AlexNet: as VGG a plain chain over two activation buffers, staged through K0 only
+    bool densenet = false;          // torchvision DenseNet (growth rate 32): the ResNet stem shape, dense blocks over a raw concatenation
+    std::vector<NormLayer> norms;   // its stand-alone BatchNorms in forward order
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -189,17 +204,20 @@ void set_name(char* dst, const std::string& s) {
 }
 
 int default_tile(const mpx_conv_desc& d);
+bool patch_eligible(const mpx_conv_desc& d);
 
 // torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
 int build_topology_small(mpx_engine* h);
 int build_topology_vgg(mpx_engine* h);
 int build_topology_alexnet(mpx_engine* h);
+int build_topology_densenet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
         return build_topology_small(h);
     if (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) return build_topology_vgg(h);
     if (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) return build_topology_alexnet(h);
+    if (h->arch >= MPX_ARCH_DENSENET && h->arch < MPX_ARCH_DENSENET + 1000) return build_topology_densenet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -628,6 +646,101 @@ int build_topology_alexnet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision DenseNet (densenet.py; growth rate 32, bn_size 4, 64 initial features): features.conv0 (3 -> 64, 7x7 stride 2 pad 3) + norm0
+// + ReLU + MaxPool2d(3, 2, 1) -- the ResNet stem shape, so the fused stem + pool launch serves it --, four dense blocks with a transition
+// behind the first three, norm5 + ReLU, global average pool, classifier.  No conv has a bias.
+//   dense layer j of block b on C = C_in + 32 (j - 1) channels: norm1(C) -> ReLU -> conv1 1x1 C -> 128 -> norm2 -> ReLU -> conv2 3x3 pad 1
+//       128 -> 32, output concatenated behind the C input channels.  norm2 + ReLU are conv1's epilogue; conv2 has no epilogue at all.
+//   transition b: norm(C) -> ReLU -> conv 1x1 C -> C / 2 -> AvgPool2d(2, 2), in torchvision's order (the conv at full resolution).
+// Buffers: R = 0 the block's RAW concatenation [B][H][W][C_block], N = 1 its normalised first C channels (dense), T1 = 2 conv1's /
+// the transition conv's output, T2 = 3 conv2's / the average pool's output.  One OP_CATNORM per consumer of the concatenation appends
+// the fresh channels (the block input: the pooled stem / the pooled transition; then every conv2 output) to R and writes the consumer's
+// relu(bn(.)) into N.
+int build_topology_densenet(mpx_engine* h) {
+    int blocks[4];
+    switch (h->arch - MPX_ARCH_DENSENET) {
+        case 121: blocks[0] = 6; blocks[1] = 12; blocks[2] = 24; blocks[3] = 16; break;
+        case 169: blocks[0] = 6; blocks[1] = 12; blocks[2] = 32; blocks[3] = 32; break;
+        case 201: blocks[0] = 6; blocks[1] = 12; blocks[2] = 48; blocks[3] = 32; break;
+        default: return MPX_E_ARG;      // (densenet161: growth rate 48 from 96 features, C = 96 + 48 k is not a multiple of the 32-wide K step)
+    }
+    constexpr int G = 32, MID = 128, R = 0, N = 1, T1 = 2, T2 = 3;
+    h->densenet = true;
+    h->act_elems_per_image = kActElemsPerImage;
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = relu;
+        L.is_fc = fc;
+        L.is_stem = (cin == 3);
+        L.cin_pad = cin;
+        L.cout_store = cout;
+        L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * cin;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        // conv2 (3x3, 128 -> 32) runs the patch kernel.  default_tile's rule for cout <= 64 is the 64-row tile 1, judged on the ResNets'
+        // 64 -> 64 layers (where the patch kernel lost 10 %) and left as it is; here half of those rows are padding either way, and the
+        // patch kernel stages the 128-channel input once per 32-channel chunk instead of once per tap.  DenseNet-121 in the network, the
+        // 58 conv2 layers, ms per batch 2340 / 512: tile 1 56.1 / 13.8, tiles 0, 2, 4, 7 47.8 .. 48.7 / 11.0 .. 12.4, tile 6 30.2 / 7.5 --
+        // faster on every map (56x56 30.3 -> 16.6, 28x28 16.4 -> 8.4, 14x14 8.2 -> 4.3, 7x7 1.18 -> 0.90).  A default of THIS
+        // topology's layers (tile_default), not a rule of default_tile: no other network's layer can change tile.
+        if (k == 3 && cout == G && patch_eligible(L.d)) L.tile = L.tile_default = 6;
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
+    auto catnorm = [&](const std::string& name, int fresh, int g, int c, int ctot, int hw) {
+        NormLayer nl;
+        std::memset(&nl.d, 0, sizeof nl.d);
+        std::snprintf(nl.d.name, sizeof nl.d.name, "%s", name.c_str());
+        nl.d.channels = c;
+        nl.d.hw = hw;
+        h->norms.push_back(nl);
+        Op o{OP_CATNORM, (int)h->norms.size() - 1, fresh, N, R, hw, c, BUF_NONE};
+        o.g = g; o.ctot = ctot;
+        h->ops.push_back(o);
+    };
+    int c = add_conv("features.conv0", "features.norm0", 3, 64, 7, 2, 3, 224, 1, false);
+    conv_op(c, BUF_INPUT, 0);
+    h->ops.push_back(Op{OP_MAXPOOL, -1, 0, BUF_STEM, BUF_NONE, 112, 64, BUF_NONE});
+    int X = BUF_STEM, cin = 64, hcur = 56;
+    for (int b = 0; b < 4; ++b) {
+        const int ctot = cin + G * blocks[b];
+        if ((size_t)hcur * hcur * ctot > kActElemsPerImage) return MPX_E_INTERNAL;
+        const std::string bp = "features.denseblock" + std::to_string(b + 1) + ".denselayer";
+        catnorm(bp + "1.norm1", X, cin, cin, ctot, hcur);          // the block input becomes the head of the concatenation
+        for (int j = 1; j <= blocks[b]; ++j) {
+            const std::string p = bp + std::to_string(j) + ".";
+            c = add_conv(p + "conv1", p + "norm2", cin, MID, 1, 1, 0, hcur, 1, false);
+            conv_op(c, N, T1);
+            c = add_conv(p + "conv2", "", MID, G, 3, 1, 1, hcur, 0, false);
+            conv_op(c, T1, T2);
+            cin += G;
+            const std::string next = j < blocks[b] ? bp + std::to_string(j + 1) + ".norm1"
+                                                   : (b < 3 ? "features.transition" + std::to_string(b + 1) + ".norm" : std::string("features.norm5"));
+            catnorm(next, T2, G, cin, ctot, hcur);
+        }
+        if (b < 3) {
+            c = add_conv("features.transition" + std::to_string(b + 1) + ".conv", "", cin, cin / 2, 1, 1, 0, hcur, 0, false);
+            conv_op(c, N, T1);
+            cin /= 2;
+            h->ops.push_back(Op{OP_AVGPOOL2, -1, T1, T2, BUF_NONE, hcur, cin, BUF_NONE});
+            hcur /= 2;
+            X = T2;
+        }
+    }
+    h->feat = cin;
+    h->ops.push_back(Op{OP_AVGPOOL, -1, N, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
+    c = add_conv("classifier", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, true);
+    conv_op(c, BUF_POOL, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -640,11 +753,12 @@ struct ProfScope {
     mpx_engine* h;
     hipStream_t st;
     ProfRec* rec = nullptr;
-    ProfScope(mpx_engine* h_, hipStream_t st_, int kind, int conv) : h(h_), st(st_) {
+    ProfScope(mpx_engine* h_, hipStream_t st_, int kind, int conv, int sub = -1) : h(h_), st(st_) {
         if (h->prof_on && h->prof_used < (int)h->prof_pool.size()) {
             rec = &h->prof_pool[h->prof_used++];
             rec->kind = kind;
             rec->conv = conv;
+            rec->sub = sub;
             h->prof_stream = st;
             (void)hipEventRecord(rec->t0, st);
         }
@@ -1218,6 +1332,17 @@ int build_fused(mpx_engine* h, int main) {
     return 0;
 }
 
+// one concat_bn_relu_kernel launch; `norm` = the engine's norm it runs for (profile record), -1 from the stand-alone entry
+int launch_catnorm(mpx_engine* h, const CatNormParams& p, int norm, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, norm);
+    const unsigned long long units = (unsigned long long)p.npix * (unsigned)((p.c_end - p.c_begin) / 8);
+    // Guideline 13 of the HIP guide for HBM-bound kernels: about 8 workgroups per CU, striding over the rest
+    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
+    hipLaunchKernelGGL(concat_bn_relu_kernel, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1318,13 +1443,15 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
             wbytes += 2 * round_up((size_t)L.d.cout_pad * (L.d.cin + h->convs[L.fuse_partner].d.cin) * 2, 256) + 2 * round_up((size_t)L.d.cout_pad * 4, 256);
     }
     for (const TailBlock& tb : h->tails) wbytes += 2 * round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
+    for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
     const size_t scratch_bytes = 4096 * sizeof(float);
     // the stem by superposition (ImageNet ResNets): pooled stem planes, fp32 stem weights + BatchNorm vectors, one image's table (worst case:
     // 49 entries per conv output pixel), the bit planes of one staging call
     const bool stemtab = stem_pool_eligible(h);
     const int tab_nmb = (max_batch + 31) / 32 + 1;
     const size_t stem_plane = stemtab ? round_up((size_t)max_batch * ST_POOLED * ST_POOLED * ST_C * 2, 256) : 0;
-    const size_t stem_w_bytes = stemtab ? round_up((size_t)ST_TAPS * 3 * ST_C * 4, 256) + 2 * 256 : 0;
+    const bool stemw = stemtab && !h->densenet;     // a DenseNet engine runs the fused stem + pool launch but keeps no stem table
+    const size_t stem_w_bytes = stemw ? round_up((size_t)ST_TAPS * 3 * ST_C * 4, 256) + 2 * 256 : 0;
     const size_t tab_int_bytes = stemtab ? round_up((size_t)(ST_NPIX + 1) * 4, 256) : 0;
     const size_t tab_lab_bytes = stemtab ? round_up((size_t)ST_MAX_ENTRIES * 4, 256) : 0;
     const size_t tab_vec_bytes = stemtab ? round_up((size_t)ST_MAX_ENTRIES * ST_C * 4, 256) : 0;
@@ -1353,6 +1480,8 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     if (stemtab) {
         h->stem_hi = (half_t*)take(stem_plane);
         h->stem_lo = (half_t*)take(stem_plane);
+    }
+    if (stemw) {
         h->stem_w32 = (float*)take(stem_w_bytes - 512);
         h->stem_s32 = (float*)take(256);
         h->stem_t32 = (float*)take(256);
@@ -1377,6 +1506,11 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
         const size_t pb = round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
         tb.w3p_hi = (half_t*)take(pb);
         tb.w3p_lo = (half_t*)take(pb);
+    }
+    for (NormLayer& nl : h->norms) {
+        const size_t nb = round_up((size_t)nl.d.channels * 4, 256);
+        nl.scale = (float*)take(nb);
+        nl.shift = (float*)take(nb);
     }
     // the never-written borders (ImageNet) / padding channels (small nets) of the input staging must be zero, and so must
     // the pooled planes' padding channels
@@ -1479,7 +1613,7 @@ int mpx_set_conv_tile(mpx_engine* h, int i, int tile) {
     if (!h) return MPX_E_ARG;
     if (i < 0 || i >= (int)h->convs.size()) return fail(h, MPX_E_ARG, "set_conv_tile: bad layer index");
     ConvLayer& L = h->convs[i];
-    if (tile < 0) tile = default_tile(L.d);
+    if (tile < 0) tile = L.tile_default >= 0 ? L.tile_default : default_tile(L.d);
     const TileRow* r = find_tile(tile);
     if (!r) {
         std::string ids;
@@ -1500,7 +1634,43 @@ int mpx_weights_complete(const mpx_engine* h) {
     if (!h) return MPX_E_ARG;
     for (const ConvLayer& L : h->convs)
         if (!L.loaded) return 0;
+    for (const NormLayer& nl : h->norms)
+        if (!nl.loaded) return 0;
     return 1;
+}
+
+int mpx_num_norms(const mpx_engine* h) { return h ? (int)h->norms.size() : MPX_E_ARG; }
+
+int mpx_norm_info(const mpx_engine* h, int k, mpx_norm_desc* out) {
+    if (!h || !out || k < 0 || k >= (int)h->norms.size()) return MPX_E_ARG;
+    *out = h->norms[k].d;
+    return 0;
+}
+
+int mpx_load_norm(mpx_engine* h, int k, const float* gamma, const float* beta, const float* mean, const float* var, float eps) {
+    if (!h) return MPX_E_ARG;
+    if (k < 0 || k >= (int)h->norms.size()) return fail(h, MPX_E_ARG, "load_norm: bad norm index %d (this engine has %d)", k, (int)h->norms.size());
+    NormLayer& nl = h->norms[k];
+    if (!gamma || !beta || !mean || !var) return fail(h, MPX_E_ARG, "load_norm: BatchNorm tensors missing for %s", nl.d.name);
+    const int n = nl.d.channels;
+    std::vector<float> sc(n), sh(n);
+    for (int c = 0; c < n; ++c) {
+        const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)eps);
+        sc[c] = (float)s;
+        sh[c] = (float)((double)beta[c] - (double)mean[c] * s);
+    }
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(nl.scale, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(nl.shift, sh.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    nl.loaded = true;
+    return 0;
+}
+
+int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float** shift) {
+    if (!h || !scale || !shift || k < 0 || k >= (int)h->norms.size()) return MPX_E_ARG;
+    *scale = h->norms[k].scale;
+    *shift = h->norms[k].shift;
+    return 0;
 }
 
 int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg,
@@ -1538,6 +1708,7 @@ int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const flo
 int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg, int S,
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
+    if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
     if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet ? " (VGG and AlexNet stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
@@ -1583,6 +1754,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
 
 int mpx_stem_table_apply(mpx_engine* h, const uint8_t* onoff, int M, int S, int slot0, void* stream) {
     if (!h) return MPX_E_ARG;
+    if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_apply: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
     if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_apply: this architecture has no 7x7 stem with a max pool");
     if (!onoff || M <= 0) return fail(h, MPX_E_ARG, "stem_table_apply: null mask rows or empty M");
     if (h->tab_S < 0) return fail(h, MPX_E_STATE, "stem_table_apply: no table in place (mpx_stem_table_build first; loading layer 0 again discards it)");
@@ -1751,6 +1923,52 @@ int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void
     return 0;
 }
 
+int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo, int g, int fresh_stride, void* raw_hi, void* raw_lo,
+                       int c_total, int c_old, const float* scale, const float* shift, void* out_hi, void* out_lo, int c_norm,
+                       long long npix, void* stream) {
+    if (!h) return MPX_E_ARG;
+    const bool fresh = fresh_hi != nullptr, norm = out_hi != nullptr;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!raw_hi || !raw_lo || (fresh_hi == nullptr) != (fresh_lo == nullptr) || (out_hi == nullptr) != (out_lo == nullptr) || (!fresh && !norm))
+        return fail(h, MPX_E_ARG, "concat_bn_relu: raw planes and at least one of fresh / out planes, planes in pairs");
+    if (npix <= 0 || c_total <= 0 || (c_total & 7) || c_old < 0 || (c_old & 7))
+        return fail(h, MPX_E_ARG, "concat_bn_relu: npix > 0, c_total a positive multiple of 8, c_old a multiple of 8");
+    if (fresh ? (g <= 0 || (g & 7) || fresh_stride < g || (fresh_stride & 7) || (long long)c_old + g > c_total) : (g != 0))
+        return fail(h, MPX_E_ARG, "concat_bn_relu: g a positive multiple of 8 with c_old + g <= c_total and fresh_stride >= g a multiple of 8 (g = 0 without fresh planes)");
+    if (norm ? (!scale || !shift || c_norm <= 0 || (c_norm & 7) || (fresh ? c_norm != c_old + g : c_norm > c_total)) : (c_norm != 0 || scale || shift))
+        return fail(h, MPX_E_ARG, "concat_bn_relu: c_norm = c_old + g with fresh planes, a positive multiple of 8 <= c_total without; scale / shift with out planes only");
+    if (misaligned(fresh_hi) || misaligned(fresh_lo) || misaligned(raw_hi) || misaligned(raw_lo) || misaligned(out_hi) || misaligned(out_lo) ||
+        misaligned(scale) || misaligned(shift))
+        return fail(h, MPX_E_ARG, "concat_bn_relu: every pointer must be 16-byte aligned");
+    CatNormParams p;
+    std::memset(&p, 0, sizeof p);
+    p.f_hi = (const half_t*)fresh_hi; p.f_lo = (const half_t*)fresh_lo;
+    p.r_hi = (half_t*)raw_hi; p.r_lo = (half_t*)raw_lo;
+    p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.scale = scale; p.shift = shift;
+    p.npix = npix; p.f_stride = fresh_stride; p.c_total = c_total; p.c_old = c_old;
+    p.c_begin = norm ? 0 : c_old;
+    p.c_end = norm ? c_norm : c_old + g;
+    MPX_SET_DEVICE(h);
+    return launch_catnorm(h, p, -1, as_stream(stream));
+}
+
+int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
+                     void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
+        return fail(h, MPX_E_ARG, "avgpool2x2s2: bad arguments (hin even and > 0, c a positive multiple of 8)");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1, -2);
+    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (c / 8);
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->num_cus * 8);
+    hipLaunchKernelGGL(avgpool2x2s2_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
+                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 int mpx_head_softmax_gather(mpx_engine* h, const float* logits, const int32_t* label, float* score, int32_t* pred,
                             int B, void* stream) {
     if (!h) return MPX_E_ARG;
@@ -1841,6 +2059,20 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_AVGPOOL: rc = mpx_global_avgpool(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
             case OP_HEAD: rc = mpx_head_softmax_gather(h, logits, label, score, pred, B, stream); break;
             case OP_AVGPAD: rc = mpx_avgpool2_pad(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c >> 16, o.c & 0xffff, stream); break;
+            case OP_AVGPOOL2: rc = mpx_avgpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
+            case OP_CATNORM: {
+                // append the fresh g channels (o.in, dense) to the block's raw concatenation (o.res) and write relu(bn(.)) of its
+                // first o.c channels into o.out, in one launch
+                const NormLayer& nl = h->norms[o.conv];
+                CatNormParams p;
+                std::memset(&p, 0, sizeof p);
+                p.f_hi = hi(o.in); p.f_lo = lo(o.in); p.r_hi = hi(o.res); p.r_lo = lo(o.res); p.y_hi = hi(o.out); p.y_lo = lo(o.out);
+                p.scale = nl.scale; p.shift = nl.shift;
+                p.npix = (long long)B * o.hin * o.hin;
+                p.f_stride = o.g; p.c_total = o.ctot; p.c_old = o.c - o.g; p.c_begin = 0; p.c_end = o.c;
+                rc = launch_catnorm(h, p, o.conv, as_stream(stream));
+                break;
+            }
         }
         if (rc) return rc;
     }
@@ -1970,6 +2202,11 @@ int mpx_profile_enable(mpx_engine* h, int on) {
 }
 
 int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms) {
+    return mpx_profile_collect_ex(h, ms_by_kind, launches_by_kind, per_conv_ms, nullptr, nullptr);
+}
+
+int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                           double* per_norm_ms, double* avgpool2_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -1981,6 +2218,8 @@ int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_
         ms_by_kind[r.kind] += ms;
         launches_by_kind[r.kind] += 1;
         if (per_conv_ms && r.kind == OP_CONV && r.conv >= 0) per_conv_ms[r.conv] += ms;
+        if (per_norm_ms && r.kind == 2 && r.sub >= 0 && r.sub < (int)h->norms.size()) per_norm_ms[r.sub] += ms;
+        if (avgpool2_ms && r.kind == 2 && r.sub == -2) *avgpool2_ms += ms;
     }
     h->prof_used = 0;
     return 0;

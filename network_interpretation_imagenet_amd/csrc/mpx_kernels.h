@@ -475,4 +475,119 @@ __global__ __launch_bounds__(256) void heatmap_gather_kernel(const int32_t* __re
     if ((unsigned)s < (unsigned)S) heat[p] += per_segment[s];
 }
 
+// ------------------------------------------------------------------------------------------
+// DenseNet: concat-append + BatchNorm + ReLU (torchvision densenet.py: `torch.cat(features, 1)` followed by the NEXT layer's
+// norm1 + relu1, a transition's norm + relu, or norm5 + relu).  A dense block keeps its running concatenation RAW (every consumer
+// normalises it with statistics of its own) in planes r_* [P][c_total]; a layer's fresh channels arrive dense in f_* [P][f_stride].
+// One launch walks channels [c_begin, c_end) of every pixel in units of 8 channels (16 bytes per plane per lane):
+//   c <  c_old : the (hi, lo) pair is read from r_*;
+//   c >= c_old : it is read from f_* (channel c - c_old) and copied into r_* bit for bit -- the append;
+//   and, when y_* is given, split(relu(scale[c] * (hi + lo) + shift[c])) goes to the dense operand y_* [P][c_end] of the next conv
+//   (fp32: hi + lo is exact, one multiply and one add rounded separately, then the re-split).
+// f_* == NULL: normalise only (every channel from r_*); y_* == NULL: append only (c_begin = c_old).  Consecutive lanes take consecutive
+// 16-byte units of a pixel, so every load and store of a wave is one contiguous run; the grid is capped (host: 8 blocks per CU) and
+// strides over the rest, advancing (pixel, unit) by a fixed step without a division; offsets are 64-bit.
+// ------------------------------------------------------------------------------------------
+struct CatNormParams {
+    const half_t* f_hi;
+    const half_t* f_lo;
+    half_t* r_hi;
+    half_t* r_lo;
+    half_t* y_hi;
+    half_t* y_lo;
+    const float* scale;
+    const float* shift;
+    long long npix;
+    int f_stride, c_total, c_old, c_begin, c_end;
+};
+
+__global__ __launch_bounds__(256) void concat_bn_relu_kernel(const CatNormParams p) {
+    const unsigned cg = (unsigned)(p.c_end - p.c_begin) >> 3;       // units per pixel
+    const unsigned step = gridDim.x * 256u;                         // <= 2^20 units: 32-bit divisions, once
+    const unsigned u0 = blockIdx.x * 256u + threadIdx.x;
+    const unsigned dpix = step / cg, dk = step % cg;
+    long long pix = u0 / cg;
+    unsigned k = u0 % cg;
+    const bool fresh = p.f_hi != nullptr, norm = p.y_hi != nullptr;
+    while (pix < p.npix) {
+        const int c = p.c_begin + (int)(k << 3);
+        const size_t at_r = (size_t)pix * p.c_total + c;
+        // one load per plane whatever the source (a wave that straddles c_old does not run two load paths one after the other); only
+        // the store of the append is predicated
+        const bool from_f = fresh && c >= p.c_old;
+        const size_t at_f = from_f ? (size_t)pix * p.f_stride + (c - p.c_old) : 0;
+        const h8 vh = *(const h8*)(from_f ? p.f_hi + at_f : p.r_hi + at_r);
+        const h8 vl = *(const h8*)(from_f ? p.f_lo + at_f : p.r_lo + at_r);
+        if (from_f) {
+            *(h8*)(p.r_hi + at_r) = vh;
+            *(h8*)(p.r_lo + at_r) = vl;
+        }
+        if (norm) {
+            const f4 s0 = *(const f4*)(p.scale + c), s1 = *(const f4*)(p.scale + c + 4);
+            const f4 t0 = *(const f4*)(p.shift + c), t1 = *(const f4*)(p.shift + c + 4);
+            h8 oh, ol;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x = (float)vh[j] + (float)vl[j];
+                const float s = j < 4 ? s0[j & 3] : s1[j & 3], t = j < 4 ? t0[j & 3] : t1[j & 3];
+                const float v = fmaxf(__fadd_rn(__fmul_rn(s, x), t), 0.f);
+                half_t hi, lo;
+                split_f32(v, hi, lo);
+                oh[j] = hi;
+                ol[j] = lo;
+            }
+            const size_t at_y = (size_t)pix * p.c_end + c;
+            *(h8*)(p.y_hi + at_y) = oh;
+            *(h8*)(p.y_lo + at_y) = ol;
+        }
+        pix += dpix;
+        k += dk;
+        if (k >= cg) { k -= cg; ++pix; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// DenseNet transitions: AvgPool2d(2, 2) on split planes [B][hin][hin][c] -> [B][hin/2][hin/2][c].  One thread = 8 channels of an
+// output pixel: the four taps are merged (hi + lo, exact in fp32), summed in row-major order in fp32, multiplied by 0.25 (exact)
+// and re-split.  16-byte loads and stores, 64-bit offsets, grid-stride.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void avgpool2x2s2_kernel(const half_t* __restrict__ in_hi, const half_t* __restrict__ in_lo,
+                                                           half_t* __restrict__ out_hi, half_t* __restrict__ out_lo, int B,
+                                                           int hin, int c) {
+    const int ho = hin / 2;
+    const int cg = c / 8;
+    const size_t total = (size_t)B * ho * ho * cg;
+    const size_t row = (size_t)hin * c;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t g = t % cg;
+        const size_t pix = t / cg;                      // output pixel: (n * ho + oy) * ho + ox
+        const size_t ox = pix % ho;
+        const size_t ny = pix / ho;                     // n * ho + oy: input row 2 * ny of the image-stacked map
+        const size_t i00 = ((2 * ny) * hin + 2 * ox) * c + g * 8;
+        const size_t at[4] = {i00, i00 + c, i00 + row, i00 + row + c};
+        float acc[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const h8 vh = *(const h8*)(in_hi + at[q]);
+            const h8 vl = *(const h8*)(in_lo + at[q]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = (float)vh[j] + (float)vl[j];
+                acc[j] = q == 0 ? v : __fadd_rn(acc[j], v);
+            }
+        }
+        h8 oh, ol;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            half_t hi, lo;
+            split_f32(acc[j] * 0.25f, hi, lo);
+            oh[j] = hi;
+            ol[j] = lo;
+        }
+        const size_t o = pix * c + g * 8;
+        *(h8*)(out_hi + o) = oh;
+        *(h8*)(out_lo + o) = ol;
+    }
+}
+
 }  // namespace mpx

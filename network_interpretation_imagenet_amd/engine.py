@@ -27,6 +27,8 @@ ARCH_IDS = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "resnet101": 101, "r
 # torchvision's VGG networks (include/mpx.h MPX_ARCH_VGG / MPX_ARCH_VGG_BN + depth), which the reference's `-a` selects as well
 ARCH_IDS.update({"vgg%d%s" % (d, bn): (3100 if bn else 3000) + d for d in (11, 13, 16, 19) for bn in ("", "_bn")})
 ARCH_IDS["alexnet"] = 4000      # torchvision's AlexNet (MPX_ARCH_ALEXNET), the third family the reference's README names
+# torchvision's DenseNets with growth rate 32 (MPX_ARCH_DENSENET + depth); densenet161 (growth rate 48) is not served
+ARCH_IDS.update({"densenet%d" % d: 5000 + d for d in (121, 169, 201)})
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -102,7 +104,9 @@ class MaskedForwardEngine:
         """max_batch: slots of the workspace (masked images per forward); None = 512 for the ResNets and the small networks.  A VGG
         engine has no default: a VGG slot holds 26.5 MB (two 224x224x64 split-fp16 activation planes and the input staging, 1.8x a
         ResNet slot), so its caller sizes it -- MaskedForwardEngine("vgg16") raises ValueError, MaskedForwardEngine("vgg16",
-        max_batch=512) is the size INTEGRATION.md 1 suggests.  An AlexNet slot holds 2.4 MB and keeps the default of 512.
+        max_batch=512) is the size INTEGRATION.md 1 suggests.  An AlexNet slot holds 2.4 MB and keeps the default of 512.  A DenseNet slot
+        holds 14.5 MB -- four 56x56x256 split-fp16 activation buffers (the block's raw concatenation, its normalised copy, conv1's and
+        conv2's outputs: 12.8 MB), the input staging and the pooled stem planes, exactly a ResNet slot -- and keeps the default of 512.
         stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
@@ -110,7 +114,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs and AlexNet and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet and DenseNets and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if max_batch is None:
             if arch.startswith("vgg"):
                 raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
@@ -132,6 +136,11 @@ class MaskedForwardEngine:
             d = _lib.ConvDesc()
             _lib.check(h, self._lib.mpx_conv_info(h, i, C.byref(d)), "mpx_conv_info")
             self.layers.append(d)
+        self.norms = []         # the BatchNorms that precede their conv (DenseNet: every norm1, the transitions' norm, norm5)
+        for k in range(self._lib.mpx_num_norms(h)):
+            nd = _lib.NormDesc()
+            _lib.check(h, self._lib.mpx_norm_info(h, k, C.byref(nd)), "mpx_norm_info")
+            self.norms.append(nd)
         self.flops_per_forward = float(self._lib.mpx_flops_per_forward(h))
         self.num_cus = int(self._lib.mpx_num_cus(h))        # what the persistent kernels' grids are sized from (whole_round_batch)
         self._mean, self._std = _f3(MEAN), _f3(STD)
@@ -152,8 +161,9 @@ class MaskedForwardEngine:
 
     @property
     def has_stem_table(self):
-        """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet"))
+        """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
+        which keeps no table) and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -199,7 +209,7 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy)."""
@@ -226,7 +236,10 @@ class MaskedForwardEngine:
             wshape = (d.cout, d.cin * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
             # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7] (AlexNet's classifier.1 [4096, 256 * 6 * 6]), channel-major as torch.flatten of NCHW
             w = get(name + ".weight", wshape).reshape(w4).contiguous()
-            if not bn:          # no BatchNorm: fc, or the MNIST net's conv6 -- the layer's own bias goes in as `beta`
+            if not bn and self.norms and i != len(self.layers) - 1:
+                # DenseNet's conv2 / transition convs: no BatchNorm behind them, no ReLU and no bias (scale = 2^-e, shift = 0)
+                args = (_ptr(w), None, None, None, None, None)
+            elif not bn:        # no BatchNorm: fc, or the MNIST net's conv6 -- the layer's own bias goes in as `beta`
                 b = get(name + ".bias", (d.cout,))
                 args = (_ptr(w), None, None, _ptr(b), None, None)
             else:
@@ -238,6 +251,11 @@ class MaskedForwardEngine:
                 args = (_ptr(w), _ptr(cb), _ptr(g), _ptr(b), _ptr(m), _ptr(v))
             _lib.check(self._h, self._lib.mpx_set_conv_weights(self._h, i, *args, float(eps)),
                        "mpx_set_conv_weights(%s)" % name)
+        if only is None:        # the stand-alone BatchNorms belong to no conv: a full load brings them all
+            for k, nd in enumerate(self.norms):
+                name = nd.name.decode()
+                t = [get("%s.%s" % (name, key), (nd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
+                _lib.check(self._h, self._lib.mpx_load_norm(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_norm(%s)" % name)
         return self
 
     # ---- kernels ----
@@ -676,11 +694,15 @@ class MaskedForwardEngine:
         _lib.check(self._h, self._lib.mpx_profile_enable(self._h, 1 if on else 0), "mpx_profile_enable")
 
     def collect_profile(self):
-        """{'ms': {kind: ms}, 'launches': {kind: n}, 'per_conv_ms': [...]} accumulated since the last call."""
+        """{'ms': {kind: ms}, 'launches': {kind: n}, 'per_conv_ms': [...], 'per_norm_ms': [...], 'avgpool2_ms': ms} accumulated since the
+        last call.  per_norm_ms (one entry per stand-alone BatchNorm: its concat-append + BN + ReLU launch) and avgpool2_ms (the
+        transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
-        _lib.check(self._h, self._lib.mpx_profile_collect(self._h, ms, n, per), "mpx_profile_collect")
+        per_norm = (C.c_double * max(1, len(self.norms)))()
+        avg2 = (C.c_double * 1)()
+        _lib.check(self._h, self._lib.mpx_profile_collect_ex(self._h, ms, n, per, per_norm, avg2), "mpx_profile_collect_ex")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
-                "per_conv_ms": list(per)}
+                "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0])}

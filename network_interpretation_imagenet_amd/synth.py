@@ -20,6 +20,13 @@ peak between 0.08 and 0.95 (tests/test_vgg_cpu.py asserts bounds on both).
 AlexNet (make_alexnet_state_dict) gets He draws for its five convs and classifier.1 / .4, biases N(0, 0.01) and classifier.6 as the
 ResNets' fc: post-ReLU RMS 0.95 .. 2.2, max |x| ~ 13, softmax peak ~ 0.45 on the `blobs` images (tests/test_alexnet_cpu.py).
 
+The DenseNets (make_densenet_state_dict; growth rate 32) get the same He draws for every conv and the same BatchNorm draws for
+norm0 / norm1 / norm2 / the transitions' norm / norm5.  A dense layer's output is a raw He conv of a ReLU of a He conv of a ReLU of the
+concatenation, so its second moment is about the concatenation's mean second moment: the trunk neither grows nor dies through 58-98 dense
+layers (post-ReLU RMS within 0.2 .. 3 on the `blobs` images; each transition's average pool takes some off).  The pooled features are smaller
+than a ResNet's, so the classifier gets DENSENET_FC_GAIN instead of FC_GAIN: softmax peak between 0.05 and 0.85
+(tests/test_densenet_cpu.py asserts the bounds).
+
 Images are u8 HWC; `blobs` gives smooth low-frequency content (felzenszwalb-friendly),
 `noise` uniform random bytes (content does not affect timing).
 """
@@ -121,12 +128,55 @@ def make_alexnet_state_dict(seed=7):
     return sd
 
 
+# torchvision densenet.py: block sizes of the networks with growth rate 32, bn_size 4 and 64 initial features
+DENSENET_BLOCKS = {"densenet121": (6, 12, 24, 16), "densenet169": (6, 12, 32, 32), "densenet201": (6, 12, 48, 32)}
+DENSENET_GROWTH, DENSENET_MID, DENSENET_INIT = 32, 128, 64
+DENSENET_FC_GAIN = 4.0
+
+
+def make_densenet_state_dict(arch, seed=7):
+    """OrderedDict with torchvision's DenseNet key set, order and shapes (models.densenet121().state_dict(): features.conv0.weight,
+    features.norm0.*, features.denseblock{b}.denselayer{j}.{norm1.*, conv1.weight, norm2.*, conv2.weight}, features.transition{b}.{norm.*,
+    conv.weight}, features.norm5.*, classifier.weight / .bias; every BatchNorm with its num_batches_tracked; no conv has a bias)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def bn(prefix, c):
+        _bn(sd, prefix, c, g)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    _conv(sd, "features.conv0", 3, DENSENET_INIT, 7, g)
+    bn("features.norm0", DENSENET_INIT)
+    c = DENSENET_INIT
+    blocks = DENSENET_BLOCKS[arch]
+    for b, n in enumerate(blocks):
+        for j in range(n):
+            p = "features.denseblock%d.denselayer%d." % (b + 1, j + 1)
+            bn(p + "norm1", c)
+            _conv(sd, p + "conv1", c, DENSENET_MID, 1, g)
+            bn(p + "norm2", DENSENET_MID)
+            _conv(sd, p + "conv2", DENSENET_MID, DENSENET_GROWTH, 3, g)
+            c += DENSENET_GROWTH
+        if b + 1 < len(blocks):
+            p = "features.transition%d." % (b + 1)
+            bn(p + "norm", c)
+            _conv(sd, p + "conv", c, c // 2, 1, g)
+            c //= 2
+    bn("features.norm5", c)
+    sd["classifier.weight"] = torch.randn(1000, c, generator=g) * (DENSENET_FC_GAIN / c ** 0.5)
+    sd["classifier.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
-    """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict) key set."""
+    """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
+    DenseNet: make_densenet_state_dict) key set."""
     if vgg_arch(arch):
         return make_vgg_state_dict(arch, seed)
     if arch == "alexnet":
         return make_alexnet_state_dict(seed)
+    if arch in DENSENET_BLOCKS:
+        return make_densenet_state_dict(arch, seed)
     kind, depths = ARCH_DEPTHS[arch]
     exp = 1 if kind == "basic" else 4
     g = torch.Generator().manual_seed(seed)

@@ -1,0 +1,254 @@
+"""DenseNet without a GPU: the synthetic state_dict with torchvision's keys in torchvision's order, the parameter and MAC counts of the
+three networks, the fp64 / fp32 CPU restatement (tests/densenet_ref.py) against an independent nn.Module build, the statistics of the
+synthetic network on exactly the rows the GPU test scores, the C-ABI surface and what conv2 relies on in the packer."""
+import ctypes as C
+import os
+import re
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import densenet_ref
+from network_interpretation_imagenet_amd import _lib, engine, synth
+from oracle import scorer
+
+ARCHS = ("densenet121", "densenet169", "densenet201")
+BLOCKS = {"densenet121": (6, 12, 24, 16), "densenet169": (6, 12, 32, 32), "densenet201": (6, 12, 48, 32)}
+PARAMS = {"densenet121": 7978856, "densenet169": 14149480, "densenet201": 20013928}       # torchvision's parameter counts
+MACS = {"densenet121": 2834161664, "densenet169": 3359843328, "densenet201": 4291365888}  # convs + classifier, torchvision's order
+C_FINAL = {"densenet121": 1024, "densenet169": 1664, "densenet201": 1920}
+NEW_SYMBOLS = ("mpx_num_norms", "mpx_norm_info", "mpx_load_norm", "mpx_norm_params", "mpx_concat_bn_relu", "mpx_avgpool2x2s2",
+               "mpx_profile_collect_ex")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bn_keys(prefix, c):
+    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
+            (prefix + ".num_batches_tracked", ())]
+
+
+def _expected_keys(arch):
+    """models.<arch>().state_dict(): key -> shape, in module order, written out from the block tuple."""
+    out = [("features.conv0.weight", (64, 3, 7, 7))] + _bn_keys("features.norm0", 64)
+    c = 64
+    for b, n in enumerate(BLOCKS[arch], 1):
+        for j in range(1, n + 1):
+            p = "features.denseblock%d.denselayer%d." % (b, j)
+            out += _bn_keys(p + "norm1", c) + [(p + "conv1.weight", (128, c, 1, 1))] + _bn_keys(p + "norm2", 128) + [(p + "conv2.weight", (32, 128, 3, 3))]
+            c += 32
+        if b < 4:
+            p = "features.transition%d." % b
+            out += _bn_keys(p + "norm", c) + [(p + "conv.weight", (c // 2, c, 1, 1))]
+            c //= 2
+    return out + _bn_keys("features.norm5", c) + [("classifier.weight", (1000, c)), ("classifier.bias", (1000,))]
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_synth_densenet_state_dict_has_torchvisions_keys_order_and_shapes(arch):
+    sd = synth.make_state_dict(arch)
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _expected_keys(arch)
+    assert all(v.dtype == (torch.int64 if k.endswith("num_batches_tracked") else torch.float32) for k, v in sd.items())
+    params = sum(v.numel() for k, v in sd.items() if k.endswith((".weight", ".bias")))     # nn.Parameters: no running statistics
+    assert params == PARAMS[arch]
+    assert sd["classifier.weight"].shape[1] == C_FINAL[arch]
+    assert not any(k.endswith("conv0.bias") or re.search(r"conv\d?\.bias$", k) for k in sd)       # no conv has a bias
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_macs_per_forward_are_the_known_answers(arch):
+    """Counted here from the block tuple alone, then compared with the restatement's topology (which the GPU test compares with the
+    engine's conv list and mpx_flops_per_forward = 2 x this).  The engine runs torchvision's order -- a transition's conv at full
+    resolution, then the pool -- so this is also the figure it performs."""
+    macs = 112 * 112 * 64 * 3 * 49
+    c, h = 64, 56
+    for b, n in enumerate(BLOCKS[arch]):
+        for _ in range(n):
+            macs += h * h * (c * 128 + 128 * 32 * 9)
+            c += 32
+        if b < 3:
+            macs += h * h * c * (c // 2)
+            c //= 2
+            h //= 2
+    macs += c * 1000
+    assert macs == MACS[arch]
+    assert densenet_ref.macs(arch) == MACS[arch]
+    convs, norms = densenet_ref.topology(arch)
+    assert len(convs) == 2 * sum(BLOCKS[arch]) + 5 and len(norms) == sum(BLOCKS[arch]) + 4
+    assert convs[-1][1] == c == C_FINAL[arch] and norms[-1] == ("features.norm5", c, 7)
+
+
+def test_densenet_arch_ids_are_unique_and_161_is_not_served():
+    assert [engine.ARCH_IDS[a] for a in ARCHS] == [5121, 5169, 5201]
+    ids = list(engine.ARCH_IDS.values())
+    assert len(ids) == len(set(ids))
+    assert "densenet161" not in engine.ARCH_IDS
+    with pytest.raises(ValueError, match="AlexNet"):
+        engine.MaskedForwardEngine("densenet161")
+
+
+def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
+    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
+        header = fh.read()
+    assert "#define MPX_ARCH_DENSENET 5000" in header
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint %s\(" % name, header), name
+        assert name in _lib.SIGNATURES, name
+        assert getattr(mpx_lib, name) is not None
+    # every entry refuses a null engine before it touches a device
+    assert mpx_lib.mpx_num_norms(None) == -1
+    assert mpx_lib.mpx_concat_bn_relu(None, None, None, 0, 0, None, None, 0, 0, None, None, None, None, 0, 0, None) == -1
+    assert mpx_lib.mpx_avgpool2x2s2(None, None, None, None, None, 1, 56, 64, None) == -1
+    assert mpx_lib.mpx_load_norm(None, 0, None, None, None, None, 1e-5) == -1
+
+
+@pytest.mark.parametrize("arch_id", [5000, 5100, 5161, 5122, 5999])
+def test_unknown_densenet_id_is_refused(mpx_lib, arch_id):
+    """mpx_create rejects the id before it touches a device (densenet161 among them: growth rate 48)."""
+    h = C.c_void_p()
+    assert mpx_lib.mpx_create(arch_id, 4, 0, C.byref(h)) == -1 and not h.value
+
+
+# ------------------------------------------------------------------------------------------------
+# the restatement against an independent nn.Module build
+# ------------------------------------------------------------------------------------------------
+class _DenseLayer(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.norm1 = nn.BatchNorm2d(c)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.conv1 = nn.Conv2d(c, 128, kernel_size=1, stride=1, bias=False)
+        self.norm2 = nn.BatchNorm2d(128)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(128, 32, kernel_size=3, stride=1, padding=1, bias=False)
+
+    def forward(self, feats):
+        x = torch.cat(feats, 1)
+        return self.conv2(self.relu2(self.norm2(self.conv1(self.relu1(self.norm1(x))))))
+
+
+class _DenseBlock(nn.ModuleDict):
+    def __init__(self, n, c):
+        super().__init__()
+        for j in range(n):
+            self.add_module("denselayer%d" % (j + 1), _DenseLayer(c + 32 * j))
+
+    def forward(self, x):
+        feats = [x]
+        for _name, layer in self.items():
+            feats.append(layer(feats))
+        return torch.cat(feats, 1)
+
+
+class _DenseNet(nn.Module):
+    """torchvision's module tree (same names, so load_state_dict(strict=True) is the check of the key set), written independently of
+    densenet_ref: a list of features per block and torch.cat per layer, as torchvision does."""
+
+    def __init__(self, blocks):
+        super().__init__()
+        feats = OrderedDict([("conv0", nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)), ("norm0", nn.BatchNorm2d(64)),
+                             ("relu0", nn.ReLU(inplace=True)), ("pool0", nn.MaxPool2d(kernel_size=3, stride=2, padding=1))])
+        c = 64
+        for b, n in enumerate(blocks):
+            feats["denseblock%d" % (b + 1)] = _DenseBlock(n, c)
+            c += 32 * n
+            if b != len(blocks) - 1:
+                feats["transition%d" % (b + 1)] = nn.Sequential(OrderedDict([
+                    ("norm", nn.BatchNorm2d(c)), ("relu", nn.ReLU(inplace=True)), ("conv", nn.Conv2d(c, c // 2, kernel_size=1, stride=1, bias=False)),
+                    ("pool", nn.AvgPool2d(kernel_size=2, stride=2))]))
+                c //= 2
+        feats["norm5"] = nn.BatchNorm2d(c)
+        self.features = nn.Sequential(feats)
+        self.classifier = nn.Linear(c, 1000)
+
+    def forward(self, x):
+        out = F.relu(self.features(x), inplace=True)
+        return self.classifier(torch.flatten(F.adaptive_avg_pool2d(out, (1, 1)), 1))
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_restatement_matches_an_nn_module_build(arch, dtype):
+    sd = synth.make_state_dict(arch)
+    model = _DenseNet(BLOCKS[arch])
+    model.load_state_dict(sd, strict=True)
+    model.to(dtype).eval()
+    x = scorer.to_tensor_normalize(synth.make_images(2)[1])[None].to(dtype)
+    with torch.no_grad():
+        want = model(x)
+        got = densenet_ref.forward(densenet_ref.cast(sd, dtype), arch, x)
+    assert tuple(got.shape) == (1, 1000)
+    scale = want.abs().max().item()
+    err = (got - want).abs().max().item()
+    print("%s %s: max |d| %.3e of logit scale %.2f" % (arch, dtype, err, scale))
+    assert scale > 1.0 and err <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_synthetic_densenet_statistics_on_the_rows_the_gpu_test_scores(arch, golden_dir):
+    """Activations O(1) through every dense layer (fp16 hi saturates at 65504), the unmasked softmax peaked but unsaturated, and on EVERY
+    mask row of densenet_ref.E2E_CASES an fp64 top-two logit margin >= 1e-3: the GPU test then compares the argmax of every row."""
+    sd = synth.make_state_dict(arch)
+    sd64 = densenet_ref.cast(sd, torch.float64)
+    for kind, m, seed in densenet_ref.E2E_CASES:
+        img, seg = densenet_ref.e2e_inputs(golden_dir, kind)
+        x = scorer.to_tensor_normalize(img)
+        trace = []
+        with torch.no_grad():
+            logits = densenet_ref.forward(sd64, arch, x[None].double(), trace)
+        assert len(trace) == 2 * sum(BLOCKS[arch]) + 4
+        rms = [t.pow(2).mean().sqrt().item() for t in trace]
+        assert min(rms) > 0.2 and max(rms) < 3.0, (min(rms), max(rms))
+        assert max(t.abs().max().item() for t in trace) < 65504 / 1000
+        p = F.softmax(logits, 1)[0]
+        print("%s %s: post-ReLU rms %.3f .. %.3f, top softmax %.4f, %d classes over 1e-3" % (arch, kind, min(rms), max(rms), p.max().item(), int((p > 1e-3).sum())))
+        assert 0.05 <= p.max().item() <= 0.85
+        assert int((p > 1e-3).sum()) >= 3
+        label = int(p.argmax())
+        onoff = synth.random_onoff(m, len(np.unique(seg)), seed=seed)
+        s64, logits64 = densenet_ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
+        top2 = np.sort(logits64, axis=1)[:, -2:]
+        gap = top2[:, 1] - top2[:, 0]
+        print("%s %s: %d rows, scores %.4f .. %.4f, smallest fp64 top-two margin %.4f" % (arch, kind, m, s64.min(), s64.max(), gap.min()))
+        assert gap.min() >= 1e-3
+        assert s64.max() - s64.min() > 0.01                   # the masks move the score
+
+
+# ------------------------------------------------------------------------------------------------
+# what conv2 relies on in the packer
+# ------------------------------------------------------------------------------------------------
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def test_pack_a_bias_free_bn_free_3x3_128_to_32_layer(mpx_lib):
+    """gamma = beta = conv_bias = NULL: scale = 2^-e exactly (e = the exponent that brings the row's max |w| into [512, 1024)) and
+    shift = 0 exactly -- conv2 of a dense layer has no epilogue of its own."""
+    rng = np.random.default_rng(6)
+    w = (rng.standard_normal((32, 128, 3, 3)) * (2.0 / 1152) ** 0.5).astype(np.float32)
+    d = _lib.ConvDesc()
+    d.cin, d.cout, d.ksize, d.stride, d.pad = 128, 32, 3, 1, 1
+    d.k_packed = K = 9 * 128
+    d.cout_pad = 128
+    hi = np.zeros((128, K), dtype=np.uint16)
+    lo = np.zeros_like(hi)
+    sc = np.full(128, np.nan, dtype=np.float32)
+    sh = np.full(128, np.nan, dtype=np.float32)
+    assert mpx_lib.mpx_pack_conv_weights(C.byref(d), _p(w), None, None, None, None, None, 1e-5, _p(hi), _p(lo), _p(sc), _p(sh)) == 0
+    mx = np.abs(w.reshape(32, -1)).max(1).astype(np.float64)
+    e = 10 - (np.floor(np.log2(mx)).astype(int) + 1)           # frexp: mx = f * 2^ex with f in [0.5, 1)
+    assert ((mx * 2.0 ** e >= 512) & (mx * 2.0 ** e < 1024)).all()
+    assert np.array_equal(sc[:32], (2.0 ** -e).astype(np.float32))
+    assert (sh == 0).all() and (sc[32:] == 0).all()
+    # the planes hold w * 2^e as hi + lo, (ky, kx, ci) order with ci fastest; padding rows are zero
+    row = np.arange(128)[:, None]
+    k = np.arange(K)[None, :]
+    r = row % 16
+    at = ((((row // 16) * (K // 32) + k // 32) * 16 + r) * 4 + (((k // 8) % 4) ^ ((r // 8) * 2))) * 8 + k % 8
+    planes = hi.ravel()[at].view(np.float16).astype(np.float64) + lo.ravel()[at].view(np.float16).astype(np.float64)
+    want = w.transpose(0, 2, 3, 1).reshape(32, K).astype(np.float64) * (2.0 ** e)[:, None]
+    np.testing.assert_allclose(planes[:32], want, rtol=0, atol=1024 * 2.0 ** -21)
+    assert (planes[32:] == 0).all()

@@ -109,6 +109,27 @@ print("-- grouped by shape --")
 for key, (n, ms, fl) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     print("%5d->%-5d k%d s%d out%-4d x%-3d %8.3f ms %5.1f%% %8.1f TFLOP/s%s" % (key[0], key[1], key[2], key[3], key[4], n, ms, 100 * ms / tot, fl / max(ms, 1e-9) / 1e9,
                                                                              "   (runs inside its block's conv3 launch)" if ms == 0 else ""))
+if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + ReLU once per consumer of a block's concatenation, the transitions' pools
+    print("-- concat-append + BN + ReLU (mpx_concat_bn_relu: one launch per stand-alone BatchNorm), grouped by map; bytes = split-fp16 read + written --")
+    by_map = {}
+    tot_norm = tot_bytes = 0.0
+    for nd, ms in zip(eng.norms, prof["per_norm_ms"]):
+        ms /= reps
+        fresh = nd.channels if nd.name.endswith(b".denselayer1.norm1") else 32      # a block's first launch appends the whole block input
+        nbytes = batch * nd.hw * nd.hw * 4.0 * (2 * nd.channels + fresh)        # read C, write C normalised, write the appended channels
+        a = by_map.setdefault(nd.hw, [0, 0.0, 0.0, nd.channels, nd.channels])
+        a[0] += 1
+        a[1] += ms
+        a[2] += nbytes
+        a[3], a[4] = min(a[3], nd.channels), max(a[4], nd.channels)
+        tot_norm += ms
+        tot_bytes += nbytes
+        if os.environ.get("MPX_PER_LAYER"):
+            print("%-44s C %5d %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (nd.name.decode(), nd.channels, nd.hw, nd.hw, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    for hw, (n, ms, nbytes, c0, c1) in sorted(by_map.items(), reverse=True):
+        print("%3dx%-3d C %4d..%-4d x%-3d %8.3f ms %9.1f MB %7.2f TB/s" % (hw, hw, c0, c1, n, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
+          % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
 tails = eng.bottleneck_tails()
 if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_MASK", "3") == "3":
     names = [d.name.decode() for d in eng.layers]

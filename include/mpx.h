@@ -163,7 +163,10 @@ int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float
  *       whole pixel tiles (1x1 stride-1 layers with cout % 256 == 0 and cin = 256: the default of 256 -> 1024 on 14x14 maps;
  *       bit-identical to 7 and 10);
  *  13 = the 256x256 kernel (9) as ONE persistent workgroup per CU: the two-stage ring runs on across tiles, register epilogue (layers
- *       eligible for 9 without a residual operand: their default; bit-identical to 9);
+ *       eligible for 9 without a residual operand: their default; bit-identical to 9).  Its DUAL form runs the conv3 + downsample launch
+ *       of a Bottleneck stage (mpx_conv_dual_bn_act) whose main layer sits on tile 9, 10, 13 or 14 -- 1x1 stride 1, cout % 256 == 0, both
+ *       K segments multiples of 64 -- from one round of tiles on, and reports bit 13; under one round, and with the main layer on any other
+ *       tile (7 and 2 force their own dual kernels), tile 7's or tile 2's dual kernel runs (bit-identical);
  *  12 = the patch kernel (6) as ONE persistent workgroup per CU: weight ring and patch buffers run on across tiles, register
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
  * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default (a DenseNet's conv2, 3x3 128 -> 32,
@@ -173,7 +176,7 @@ int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float
  * layer (mpx_bottleneck_tail). */
 int mpx_set_conv_tile(mpx_engine* h, int i, int tile);
 int mpx_get_conv_tile(const mpx_engine* h, int i);
-/* Test hook: which kernels the LAST mpx_conv_bn_act call launched, as a bit mask over the tile ids above (bit t = the kernel of tile
+/* Test hook: which kernels the LAST mpx_conv_bn_act or mpx_conv_dual_bn_act call launched, as a bit mask over the tile ids above (bit t = the kernel of tile
  * t ran).  A layer's tile is a request: a launch under one round of tiles of a persistent kernel (10, 12, 13; 14: under two rounds) runs on the small-tile
  * kernel that sums in the same order (7, 6, 2; 14: 7), a residual operand sends 13 to 9, and the 256x256 kernels hand the images behind the
  * last whole round to tile 2 -- so a test that means to cover a persistent walk asserts that it ran. */

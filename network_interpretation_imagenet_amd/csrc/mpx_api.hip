@@ -881,8 +881,30 @@ int launch_conv256p(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hi
     if (int rc = conv_tiles(h, p, L.d.cout_pad, Conv256P::TC, Conv256P::TP, tiles)) return rc;
     const long long grid = persistent_grid(h, p, tiles);
     if (grid <= 0 || tiles < h->num_cus) return launch_tile(h, 2, L, p, st);
-    hipLaunchKernelGGL(conv256p_f16x3_kernel, dim3((unsigned)grid), dim3(Conv256P::NT), Conv256P::LDS, st, p);
+    hipLaunchKernelGGL(conv256p_f16x3_kernel<false>, dim3((unsigned)grid), dim3(Conv256P::NT), Conv256P::LDS, st, p);
     return launched(h, id);
+}
+
+// The DUAL form of the persistent 256x256 kernel: a fused launch (launch_conv_fused) whose main conv is a 1x1 stride-1 layer with
+// cout % 256 == 0 and whose two K segments are whole step pairs.  The launch has no residual operand (the identity is inside K), which is
+// what kept these layers off tile 13.
+bool conv256p_dual_eligible(const ConvLayer& L, const ConvLayer& D) {
+    return !L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && D.cin_pad == D.d.cin && conv256_eligible(L.d) && D.d.ksize == 1 && D.d.pad == 0 &&
+           D.d.cin % 64 == 0;
+}
+
+// 1: the kernel ran (bit 13); 0: the launch has less than one round of tiles and stays with tile 7's dual kernel (BO rounds, small
+// batches: the rule and its reason are launch_convx's); < 0: error
+int launch_conv256p_dual(mpx_engine* h, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (p.k1 <= 0 || p.k1 % 64 != 0 || (p.ktot - p.k1) <= 0 || (p.ktot - p.k1) % 64 != 0 || p.r_hi)
+        return fail(h, MPX_E_INTERNAL, "dual 256x256 conv: k1 = %d and k2 = %d must be multiples of 64, without a residual operand", p.k1, p.ktot - p.k1);
+    long long tiles;
+    if (int rc = conv_tiles(h, p, L.d.cout_pad, Conv256P::TC, Conv256P::TP, tiles)) return rc;
+    const long long grid = persistent_grid(h, p, tiles);
+    if (grid <= 0 || tiles < h->num_cus) return 0;
+    hipLaunchKernelGGL(conv256p_f16x3_kernel<true>, dim3((unsigned)grid), dim3(Conv256P::NT), Conv256P::LDS, st, p);
+    if (int rc = launched(h, 13)) return rc;
+    return 1;
 }
 
 int launch_convx(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
@@ -993,7 +1015,8 @@ const KernelLds kKernelLds[] = {
     {(const void*)conv256_f16x3_kernel, Conv256::LDS},
     {(const void*)convx_f16x3_kernel, ConvX::LDS},
     {(const void*)convw_f16x3_kernel<ConvW::K, true>, ConvW::LDS},
-    {(const void*)conv256p_f16x3_kernel, Conv256P::LDS},
+    {(const void*)conv256p_f16x3_kernel<false>, Conv256P::LDS},
+    {(const void*)conv256p_f16x3_kernel<true>, Conv256P::LDS},
     {(const void*)conv_f16x3_kernel<ConvTile4>, ConvTile4::LDS},
     {(const void*)btail_f16x3_kernel<BtResC64>, BtResC64::LDS},
     {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
@@ -1162,7 +1185,24 @@ int launch_conv_fused(mpx_engine* h, int i, const half_t* in_hi, const half_t* i
     p.x2_hi = x2_hi; p.x2_lo = x2_lo;
     p.hin2 = D.d.hin; p.win2 = D.d.hin; p.pix_stride2 = D.d.cin; p.stride2 = D.d.stride;
     ProfScope ps(h, st, OP_CONV, i);
+    h->last_kernels = 0;
     const TileRow* row = find_tile(L.tile);
+    // Bottleneck stages' first conv3 + downsample (the main layer on one of the 256-row tiles 9, 10, 13, 14, whose rows send a fused launch to
+    // tile 7): the DUAL form of the persistent 256x256 kernel (mpx_conv256p.h), reported as tile 13.  In the network at batch 2340, parent
+    // build and this one alternating twice in one call (tile 7's dual kernel -> this one, ms per batch): layer2.0 (K = 128 + 256, 28x28)
+    // 2.549 / 2.535 -> 2.107 / 2.089, layer3.0 (256 + 512, 14x14) 2.120 / 2.116 -> 1.758 / 1.743, layer4.0 (512 + 1024, 7x7) 1.869 / 1.879 ->
+    // 1.593 / 1.583: every stage gains 15-17 %, so eligibility is the whole rule.  A last round that is not whole ends the persistent
+    // walk raggedly: splitting it off to tile 2's dual kernel (as launch_conv does for the plain 256x256 tile) was measured and loses or
+    // ties -- batch 2048, ragged / split, two runs each: layer3.0 (24.5 rounds) 1.512 1.505 / 1.532 1.541 ms, layer4.0 (12.25 rounds) 1.397
+    // 1.380 / 1.375 1.382 -- and was not kept (profiles/dual256p_ab.txt).
+    // mpx_set_conv_tile(i, 7) or (i, 2) on the main layer still forces the generic dual kernels; BasicBlock fusions (3x3 main conv) are
+    // not eligible and keep them too.
+#ifndef MPX_PROBE_NO_DUAL256P            // A/B builds only (tools/ab_lib.sh)
+    if ((L.tile == 9 || L.tile == 10 || L.tile == 13 || L.tile == 14) && conv256p_dual_eligible(L, D)) {
+        const int rc = launch_conv256p_dual(h, L, p, st);
+        if (rc != 0) return rc < 0 ? rc : 0;
+    }
+#endif
     return launch_tile(h, row && row->dual >= 0 ? row->dual : 7, L, p, st);     // (mpx_conv_dual_bn_act on any other tile: tile 7's)
 }
 

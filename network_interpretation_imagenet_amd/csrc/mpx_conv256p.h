@@ -12,6 +12,13 @@
 //   * the K step is mpx_conv256.h's quadrant snake, unchanged.
 // Layers without a residual operand only (every layer the 256x256 tile is a default for: the reducing 1x1 convs).  Same summation order
 // and epilogue arithmetic as mpx_conv256.h: results are bit-identical to tile 9.
+//
+// DUAL: a stage's first conv3 with its downsample branch K-concatenated (mpx_conv.h, ConvParams::k1 / x2_*; launch_conv_fused) -- the
+// launch has no residual operand, the identity is inside K.  Only the pixel side of the DMA differs: the stages of K steps [0, k1/32)
+// read rows of x_* with pitch k1, the later ones gather the block input x2_* as a 1x1 stride-`stride2` conv.  ONE descriptor pair and ONE
+// pair of per-lane row offsets serve both operands: they are rebuilt where the fill position switches operand (twice per tile, a few
+// dozen VALU against 12 .. 48 steps of 96 MFMAs), always for the tile being FILLED, which runs up to two stages ahead of the tile
+// being computed.  Weights, K loop, fragment reads and epilogue are the plain form's: bit-identical to tile 7's dual kernel.
 #pragma once
 #include "mpx_conv256.h"
 
@@ -25,6 +32,7 @@ struct Conv256P {
     static constexpr int EPI_STORES = 32;               // 2 cout groups x 4 pixel fragments x 2 half-fragments x hi/lo
 };
 
+template <bool DUAL = false>
 __global__ __launch_bounds__(512, 2) void conv256p_f16x3_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -35,6 +43,8 @@ __global__ __launch_bounds__(512, 2) void conv256p_f16x3_kernel(const ConvParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const int K = p.ktot, nk = K >> 5;                  // nk even (K % 64 == 0, host)
+    const int K1 = DUAL ? p.k1 : K;                     // row pitch of x_*; DUAL: K steps [0, k1s) read x_*, [k1s, nk) read x2_*
+    const int k1s = K1 >> 5;
     constexpr unsigned OOB = 0x80000000u;
 
     // ---- the tiles of this workgroup: logical ids v0, v0 + G, ... (cout tile fastest, so it is the same for all of them) ----
@@ -55,21 +65,55 @@ __global__ __launch_bounds__(512, 2) void conv256p_f16x3_kernel(const ConvParams
         w_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w_hi + (size_t)n0 * K), 0, wrec, 0x00020000);
         w_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w_lo + (size_t)n0 * K), 0, wrec, 0x00020000);
     }
+    int roff0, roff1;                            // this lane's two rows of the operand being filled (DUAL: rebuilt at every operand switch)
     auto set_x_desc = [&](int ti) {
         const int m0 = (mt0 + ti * mt_step) * C::TP;
-        const long long rem = ((long long)p.M - m0) * K * 2;               // rows >= M are out of range: zeros
+        const long long rem = ((long long)p.M - m0) * K1 * 2;              // rows >= M are out of range: zeros
         const int rec = rem > 0x7fffffffLL ? 0x7fffffff : (rem < 0 ? 0 : (int)rem);
-        x_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x_hi + (size_t)m0 * K), 0, rec, 0x00020000);
-        x_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x_lo + (size_t)m0 * K), 0, rec, 0x00020000);
+        x_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x_hi + (size_t)m0 * K1), 0, rec, 0x00020000);
+        x_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x_lo + (size_t)m0 * K1), 0, rec, 0x00020000);
+        if (DUAL) {
+            int l_ = lane;                       // opaque copy: the offsets are recomputed here, not kept in registers across the tile
+            asm volatile("" : "+v"(l_));
+            const int pr = l_ >> 2;
+            roff0 = ((wave * 32 + pr) * K1) * 2 + ((l_ & 3) ^ (((pr >> 3) & 1) << 1)) * 16;
+            roff1 = roff0 + 16 * K1 * 2;
+        }
+    };
+    // DUAL, second operand: output pixel m = (n, oy, ox) reads the block input's pixel (n, oy * stride2, ox * stride2).  The descriptors
+    // start at the first image of the tile (32-bit offsets: a tile spans a few images, the planes of a batch can pass 2^31 bytes); the
+    // gather is not contiguous, so rows m >= M carry the out-of-range bit themselves (as x2_off0 in mpx_conv.h)
+    auto set_x2_desc = [&](int ti) {
+        int l_ = lane;
+        asm volatile("" : "+v"(l_));
+        const int m0 = (mt0 + ti * mt_step) * C::TP;
+        const unsigned howo = (unsigned)(p.ho * p.wo);
+        const int n_first = (int)((unsigned)m0 / howo);
+        const int img2 = p.hin2 * p.win2 * p.pix_stride2;
+        const long long rem = ((long long)(p.M / (int)howo) - n_first) * img2 * 2;
+        const int rec = rem > 0x7fffffffLL ? 0x7fffffff : (rem < 0 ? 0 : (int)rem);
+        x_hi = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2_hi + (size_t)n_first * img2), 0, rec, 0x00020000);
+        x_lo = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2_lo + (size_t)n_first * img2), 0, rec, 0x00020000);
+        auto row_off = [&](int m) {
+            const unsigned n = (unsigned)m / howo, r = (unsigned)m - n * howo;
+            const unsigned oy = r / (unsigned)p.wo, ox = r - oy * (unsigned)p.wo;
+            const int off = ((((int)n - n_first) * p.hin2 + (int)oy * p.stride2) * p.win2 + (int)ox * p.stride2) * p.pix_stride2 * 2;
+            return (off + ((l_ & 3) ^ (((l_ >> 5) & 1) << 1)) * 16) | ((p.M - 1 - m) & (int)OOB);
+        };
+        const int m = m0 + wave * 32 + (l_ >> 2);
+        roff0 = row_off(m);
+        roff1 = row_off(m + 16);
     };
     set_x_desc(0);
-    const int roff0 = ((wave * 32 + prow) * K) * 2 + src_q;
-    const int roff1 = roff0 + 16 * K * 2;
+    if (!DUAL) {
+        roff0 = ((wave * 32 + prow) * K) * 2 + src_q;
+        roff1 = roff0 + 16 * K * 2;
+    }
     const int w_lane = lane * 16;
     int f_tile = 0, f_ks = 0, f_dead = 0;        // the next stage to issue: tile index, K step; dead behind the last tile
     auto dma_piece = [&](int slot, int which) {  // which = 0..7: W_hi p0, W_lo p0, W_hi p1, W_lo p1, X_hi p0, X_lo p0, X_hi p1, X_lo p1
         char* sb = smem + slot * C::STAGE;
-        const int soff = f_ks * 64;
+        const int soff = (DUAL && f_ks >= k1s ? f_ks - k1s : f_ks) * 64;
         const int pc = (which >> 1) & 1;
         const int voff = (pc ? roff1 : roff0) | f_dead;
         const int d = (wave * 2 + pc) * 1024;
@@ -84,6 +128,7 @@ __global__ __launch_bounds__(512, 2) void conv256p_f16x3_kernel(const ConvParams
     };
     auto next_fill = [&]() {                     // advance (f_tile, f_ks) after a stage has been issued
         f_ks += 1;
+        if (DUAL && f_ks == k1s) set_x2_desc(f_tile);    // (behind the last tile too: harmless, every piece there is dead)
         if (f_ks == nk) {
             f_ks = 0;
             f_tile += 1;

@@ -2,6 +2,8 @@
 """Per-layer conv timing (HIP events inside the engine) for one forward batch.
 usage: python tools/layer_profile.py [arch] [batch] [reps]
        MPX_PER_LAYER=1 ...    one row per conv with its tile
+A conv + downsample conv that run as ONE launch (K-concatenated) are booked on the main conv; they get rows of their own, with both convs'
+FLOPs, under the grouped table (the grouped rows count the main conv's FLOPs only).
        MPX_TILE_SWEEP=1 ...   after the table: one row per conv with the in-network time of EVERY tile mpx_set_conv_tile accepts for it, two
                               repeats each (the spread between them is what a default may lose by)"""
 import os
@@ -93,10 +95,25 @@ eng.profile(False)
 prof = eng.collect_profile()
 tot = 0.0
 groups = {}
+# a downsample conv without a time of its own ran inside its block's last conv (K-concatenated, one launch): main conv index -> its index
+names = [d.name.decode() for d in eng.layers]
+fused = {}
+for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
+    if names[li].endswith(".downsample.0") and ms == 0:
+        block = names[li][:-len("downsample.0")]
+        mains = [k for k, n in enumerate(names) if n in (block + "conv3", block + "conv2")]
+        if mains and prof["per_conv_ms"][mains[-1]] > 0:
+            fused[mains[-1]] = li
+
+
+def conv_flops(d):
+    return 2.0 * batch * d.hout * d.hout * d.cout * d.cin * d.ksize * d.ksize
+
+
 print("%-26s %5s %5s %2s %2s %4s %9s %9s %8s" % ("layer", "cin", "cout", "k", "s", "hout", "ms", "GFLOP", "TFLOP/s"))
 for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
     ms /= reps
-    fl = 2.0 * batch * d.hout * d.hout * d.cout * d.cin * d.ksize * d.ksize
+    fl = conv_flops(d)
     key = (d.cin, d.cout, d.ksize, d.stride, d.hout)
     a = groups.setdefault(key, [0, 0.0, 0.0])
     a[0] += 1
@@ -104,11 +121,21 @@ for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
     a[2] += fl
     tot += ms
     if os.environ.get("MPX_PER_LAYER"):     # tool-only: one row per conv (a fused launch is booked on its main conv)
-        print("%-26s %5d %5d %2d %2d %4d %9.3f %9.1f %8.1f   tile %d" % (d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hout, ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9, eng.conv_tile(li)))
+        if li in fused:     # the launch's own work: both K segments
+            fl += conv_flops(eng.layers[fused[li]])
+        print("%-26s %5d %5d %2d %2d %4d %9.3f %9.1f %8.1f   tile %d%s" % (d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hout, ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9, eng.conv_tile(li),
+                                                                          ("   + %s in the same launch (K = %d + %d)" % (names[fused[li]], d.cin * d.ksize * d.ksize, eng.layers[fused[li]].cin)) if li in fused else ""))
 print("-- grouped by shape --")
 for key, (n, ms, fl) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     print("%5d->%-5d k%d s%d out%-4d x%-3d %8.3f ms %5.1f%% %8.1f TFLOP/s%s" % (key[0], key[1], key[2], key[3], key[4], n, ms, 100 * ms / tot, fl / max(ms, 1e-9) / 1e9,
                                                                              "   (runs inside its block's conv3 launch)" if ms == 0 else ""))
+if fused:       # the grouped rows above book these launches under their main conv's shape, with the main conv's FLOPs only
+    print("-- conv + downsample conv in one launch (K-concatenated), rows of their own; GFLOP = both convs --")
+    for li, lj in sorted(fused.items()):
+        d, ms = eng.layers[li], prof["per_conv_ms"][li] / reps
+        fl = conv_flops(d) + conv_flops(eng.layers[lj])
+        print("%-16s + %-24s K %4d + %-4d out%-3d %8.3f ms %5.1f%% %9.1f GFLOP %8.1f TFLOP/s" % (
+            names[li], names[lj], d.cin * d.ksize * d.ksize, eng.layers[lj].cin, d.hout, ms, 100 * ms / tot, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + ReLU once per consumer of a block's concatenation, the transitions' pools
     print("-- concat-append + BN + ReLU (mpx_concat_bn_relu: one launch per stand-alone BatchNorm), grouped by map; bytes = split-fp16 read + written --")
     by_map = {}

@@ -75,6 +75,22 @@ enum {
  * stand-alone BatchNorms (every norm1, each transition's norm, norm5) belong to no conv: mpx_num_norms / mpx_norm_info / mpx_load_norm.
  * Four ResNet-sized activation buffers (14.5 MB per slot with the staging and the pooled stem planes).  It stages through
  * mpx_mask_apply_normalize only: the stem-table entry points return MPX_E_STATE.
+ * -- or torchvision's MobileNetV2 (width 1.0), the first mobile network of `models.__dict__[arch]` the engine serves:
+ *   MPX_ARCH_MOBILENET + 2        mobilenet_v2; every other id in [6000, 7000) is MPX_E_ARG
+ * A MobileNetV2 engine runs features.0 (3 -> 32, 3x3 stride 2 pad 1, reading the padded NHWC4 staging: k_packed = 96) + BN + ReLU6, 17
+ * inverted-residual blocks (t, c, n, s) = (1,16,1,1) (6,24,2,2) (6,32,3,2) (6,64,4,2) (6,96,3,1) (6,160,3,2) (6,320,1,1) -- 1x1 expand + BN +
+ * ReLU6 (absent when t = 1), depthwise 3x3 + BN + ReLU6 (mpx_dwconv3x3_bn_relu6), 1x1 project + BN without activation, plus the block input
+ * when stride is 1 and cin == cout (the residual operand of the project conv; no ReLU behind the add) --, features.18 (320 -> 1280, 1x1) + BN +
+ * ReLU6, mpx_global_avgpool_clamp6 and classifier.1 (Linear(1280, 1000), the logit layer).  The 1x1 and stem convs are entries of the conv
+ * list; the 17 depthwise layers are a list of their own: mpx_num_dwconvs / mpx_dwconv_info / mpx_load_dwconv.
+ * THE CLAMP BELONGS TO THE CONSUMER.  The MFMA conv kernels' epilogues know ReLU only, and relu6(x) = min(relu(x), 6): a conv that torchvision
+ * follows with ReLU6 (relu = 1 in its descriptor: the stem, every expand conv, features.18) stores the ReLU output, and whoever reads it takes
+ * min(x, 6) as it loads -- a depthwise layer (clamp_in = 1) or the clamped global pool.  mpx_conv_bn_act on such a layer therefore returns
+ * relu(bn(conv(x))), NOT relu6(.); mpx_conv_desc keeps its layout.  The depthwise kernel applies its own full ReLU6.
+ * Channel counts 16, 24 and 144 are stored with a pitch of 32, 32 and 160 (k_packed = ksize^2 * pitch of the input, zero weight columns, zero
+ * scale and shift on the padded rows: padded channels are exact zeros wherever they are read); such layers run the generic tiles only.
+ * Three activation buffers of 112 * 112 * 96 elements per image (features.2's expanded map, 1.5 x a ResNet buffer): 15.3 MB per slot with
+ * the staging.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -84,6 +100,7 @@ enum {
 #define MPX_ARCH_VGG_BN 3100
 #define MPX_ARCH_ALEXNET 4000
 #define MPX_ARCH_DENSENET 5000
+#define MPX_ARCH_MOBILENET 6000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -109,7 +126,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet and the DenseNets, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets and MobileNetV2, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -144,6 +161,27 @@ int mpx_num_norms(const mpx_engine* h);
 int mpx_norm_info(const mpx_engine* h, int k, mpx_norm_desc* out);
 int mpx_load_norm(mpx_engine* h, int k, const float* gamma, const float* beta, const float* mean, const float* var, float eps);
 int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float** shift);
+
+/* ---- depthwise layers (MobileNetV2) ------------------------------------------------------------
+ * Depthwise layer k in [0, mpx_num_dwconvs): the 3x3 depthwise convs in forward order ("features.1.conv.0.0", "features.2.conv.1.0", ...);
+ * 0 on every other architecture.  mpx_load_dwconv takes the HOST f32 tensors of torchvision's state_dict -- w = <name>.weight
+ * [channels][1][3][3], gamma / beta / mean / var = <bn_name>.weight / .bias / .running_mean / .running_var [channels] -- and uploads,
+ * synchronously, the fp32 tap-major weights [9][pitch] (tap = ky * 3 + kx) and the vectors scale = gamma / sqrt(var + eps), shift = beta -
+ * mean * scale [pitch] (computed in double, rounded once, as mpx_load_norm), zeros on channels [channels, pitch).  mpx_dwconv_params returns
+ * their DEV pointers (what mpx_forward hands to the kernel).  mpx_weights_complete and mpx_forward count the depthwise layers. */
+typedef struct mpx_dwconv_desc {
+    char name[48];       /* torchvision state_dict prefix of the depthwise conv */
+    char bn_name[48];    /* prefix of its BatchNorm */
+    int32_t channels;    /* C: groups = in channels = out channels */
+    int32_t pitch;       /* channels per pixel of its input and output planes (C rounded up to a multiple of 32) */
+    int32_t stride;      /* 1 or 2; pad is 1, so hout = (hin - 1) / stride + 1 */
+    int32_t hin;         /* side of the square input map at 224x224 input */
+    int32_t clamp_in;    /* 1: the input is the ReLU output of an MFMA conv that torchvision follows with ReLU6; min(x, 6) is taken on load */
+} mpx_dwconv_desc;
+int mpx_num_dwconvs(const mpx_engine* h);
+int mpx_dwconv_info(const mpx_engine* h, int k, mpx_dwconv_desc* out);
+int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps);
+int mpx_dwconv_params(const mpx_engine* h, int k, const float** w, const float** scale, const float** shift);
 
 /* Kernel variant of layer i (tuning / test hook; results are identical up to fp32 summation order).  The ids are exactly the
  * kernels some layer class runs by default:
@@ -348,6 +386,25 @@ int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo
 int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
                      void* stream);
 
+/* ---- MobileNetV2: depthwise 3x3 conv (pad 1, stride 1 or 2) + BatchNorm + ReLU6 on split planes ----------------------------------
+ * replaces: one `Conv2dNormActivation(hidden, hidden, stride=stride, groups=hidden, activation_layer=nn.ReLU6)` of torchvision's
+ *           InvertedResidual inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * in_hi|lo:  DEV planes [B][hin][hin][pitch]; out_hi|lo: DEV planes [B][ho][ho][pitch], ho = (hin - 1) / stride + 1, every channel of the
+ *            pitch written.  w: DEV f32[9][pitch], tap-major (tap = ky * 3 + kx); scale / shift: DEV f32[pitch] (mpx_dwconv_params).
+ * Per output element, in fp32: x = hi + lo (exact), min(x, 6) when clamp_in != 0; acc = 0, then acc = fma(w[tap], x[tap], acc) over the taps
+ * in row-major order (ky, then kx), taps outside the map left out; fl(fl(scale * acc) + shift); min(max(., 0), 6); the re-split.
+ * pitch a positive multiple of 8, stride 1 or 2, every pointer 16-byte aligned, else MPX_E_ARG.  The planes must not overlap.  Offsets are
+ * 64-bit.  ONE launch. */
+int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
+                           void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, int clamp_in, void* stream);
+
+/* ---- MobileNetV2: K4a with the ReLU6 clamp of its producer: global average pool of min(x, 6), [B][hw][c] -> [B][c].
+ * replaces: the ReLU6 of features.18 and `nn.functional.adaptive_avg_pool2d(x, (1, 1))` of torchvision's MobileNetV2 inside
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  Sums in pixel order in fp32, divides by hw, re-splits;
+ *           mpx_global_avgpool is unchanged.  c a multiple of 8. */
+int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
+                              int c, void* stream);
+
 /* ---- K1 + K3 in one launch: the ImageNet stem and its max pool -------------------------------------------
  * replaces: `x = self.conv1(x); x = self.bn1(x); x = self.relu(x); x = self.maxpool(x)` (torchvision resnet.py, reached through
  *           model(masked_img_tensor), generate_gp_training_data_imagenet.py:246): the 7x7 stride-2 conv + BN + ReLU of layer 0 reads
@@ -410,7 +467,11 @@ int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_
  * mpx_concat_bn_relu launch of every stand-alone BatchNorm, avgpool2_ms (HOST f64[1], may be NULL) the transitions' average pools. */
 int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms);
-/* Algorithmic FLOPs (2*MAC, convs + fc) of one masked forward. */
+/* The same with MobileNetV2's split of kind 2: per_dw_ms (HOST f64[mpx_num_dwconvs], may be NULL) gets the launch of every depthwise
+ * layer. */
+int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                           double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms);
+/* Algorithmic FLOPs (2*MAC, convs + depthwise convs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 
 #ifdef __cplusplus

@@ -35,6 +35,11 @@ class NormDesc(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("channels", C.c_int32), ("hw", C.c_int32)]
 
 
+class DwConvDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 48), ("bn_name", C.c_char * 48), ("channels", C.c_int32), ("pitch", C.c_int32),
+                ("stride", C.c_int32), ("hin", C.c_int32), ("clamp_in", C.c_int32)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -89,6 +94,15 @@ SIGNATURES = {
     "mpx_avgpool2x2s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_ex": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double)]),
+    # MobileNetV2: the depthwise layers, the depthwise 3x3 + BN + ReLU6 kernel, the clamped global pool
+    "mpx_num_dwconvs": (_i, [_vp]),
+    "mpx_dwconv_info": (_i, [_vp, _i, C.POINTER(DwConvDesc)]),
+    "mpx_load_dwconv": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f]),
+    "mpx_dwconv_params": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mpx_dwconv3x3_bn_relu6": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mpx_global_avgpool_clamp6": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_profile_collect_dw": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
 #include "mpx_convw.h"
 #include "mpx_btail.h"
 #include "mpx_stemtab.h"
+#include "mpx_dw.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,10 +33,11 @@ constexpr int kProfilePairs = 4096;
 constexpr size_t kActElemsPerImage = 112 * 112 * 64;   // ImageNet: largest activation (stem output, = 56*56*256)
 constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel maps of the first stage
 constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output of features.0
+constexpr size_t kMobileActElemsPerImage = 112 * 112 * 96;   // MobileNetV2: features.2's expanded map, 1.5 x kActElemsPerImage
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
-              OP_CATNORM = 8, OP_AVGPOOL2 = 9 };
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -95,11 +97,23 @@ struct TailBlock {
     bool ready = false;
 };
 
+// A depthwise 3x3 conv + BatchNorm + ReLU6 (MobileNetV2; mpx_dw.h): fp32 tap-major weights [9][pitch] and BatchNorm vectors of its own.
+struct DwLayer {
+    mpx_dwconv_desc d;
+    float* w = nullptr;
+    float* scale = nullptr;
+    float* shift = nullptr;
+    bool loaded = false;
+};
+
+constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
+
 struct ProfRec {
     hipEvent_t t0, t1;
     int kind;
     int conv;
-    int sub;        // kind 2 on a DenseNet engine: -1 = any pool, -2 = a transition's average pool, k >= 0 = the launch of norm k
+    int sub;        // kind 2: -1 = any pool, -2 = a DenseNet transition's average pool, k >= 0 = the launch of DenseNet norm k,
+                    // kProfSubDw - k = MobileNetV2's depthwise layer k
 };
 
 }  // namespace
@@ -115,6 +129,8 @@ struct mpx_engine {
     bool alexnet = false;           // torchvision AlexNet: as VGG a plain chain over two activation buffers, staged through K0 only
     bool densenet = false;          // torchvision DenseNet (growth rate 32): the ResNet stem shape, dense blocks over a raw concatenation
     std::vector<NormLayer> norms;   // its stand-alone BatchNorms in forward order
+    bool mobilenet = false;         // torchvision MobileNetV2: inverted residuals over three activation buffers, staged through K0 only
+    std::vector<DwLayer> dws;       // its depthwise layers in forward order
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -211,6 +227,7 @@ int build_topology_small(mpx_engine* h);
 int build_topology_vgg(mpx_engine* h);
 int build_topology_alexnet(mpx_engine* h);
 int build_topology_densenet(mpx_engine* h);
+int build_topology_mobilenet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -218,6 +235,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) return build_topology_vgg(h);
     if (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) return build_topology_alexnet(h);
     if (h->arch >= MPX_ARCH_DENSENET && h->arch < MPX_ARCH_DENSENET + 1000) return build_topology_densenet(h);
+    if (h->arch >= MPX_ARCH_MOBILENET && h->arch < MPX_ARCH_MOBILENET + 1000) return build_topology_mobilenet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -737,6 +755,95 @@ int build_topology_densenet(mpx_engine* h) {
     h->ops.push_back(Op{OP_AVGPOOL, -1, N, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
     c = add_conv("classifier", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, true);
     conv_op(c, BUF_POOL, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
+// torchvision MobileNetV2 (mobilenetv2.py, width 1.0): features.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN + ReLU6, 17 inverted-residual blocks
+// (t, c, n, s) = (1,16,1,1) (6,24,2,2) (6,32,3,2) (6,64,4,2) (6,96,3,1) (6,160,3,2) (6,320,1,1), features.18 = conv 320 -> 1280 1x1 + BN +
+// ReLU6, global average pool, classifier.1 = Linear(1280, 1000).  A block is 1x1 expand + BN + ReLU6 (absent when t = 1), depthwise 3x3 +
+// BN + ReLU6, 1x1 project + BN without activation; with stride 1 and cin == cout the block input is added, no ReLU behind the add.  No
+// conv has a bias.
+// ReLU6: the MFMA convs run their ReLU epilogue and the consumer clamps at 6 as it loads (mpx_dw.h) -- every such conv is read by a
+// depthwise layer (clamp_in) or by the clamped global pool (OP_AVGPOOL6).
+// Channels: 16, 24 and 144 are stored with a pitch of 32, 32 and 160 (cin_pad / cout_store as the small networks: zero weight columns,
+// zero scale and shift on the padded rows, so padded channels are exact zeros wherever they are read -- the next conv, the depthwise
+// layer, the residual add).  Those layers are eligible for the generic tiles only (eligible()); every generic tile runs a one-step K
+// loop (K = 32: the 1x1 layers on 16, 24 or 32 channels) as it is -- its prologue stages dead steps past the end of K and the last-step
+// branch runs the one fragment set -- so no tile is refused and K is not padded.
+// Buffers: three of 112 * 112 * 96 elements per image (features.2's expanded map): X the block input, T1 the expanded map and then --
+// dead after the depthwise layer -- the block output, T2 the depthwise output.
+int build_topology_mobilenet(mpx_engine* h) {
+    if (h->arch != MPX_ARCH_MOBILENET + 2) return MPX_E_ARG;
+    h->mobilenet = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kMobileActElemsPerImage;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu,
+                        int residual, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = relu; L.d.residual = residual;
+        L.is_fc = fc;
+        L.has_bias = fc;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
+        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
+        L.cout_store = fc ? cout : pitch_of(cout);
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
+    auto add_dw = [&](const std::string& name, const std::string& bn, int c, int stride, int hin, int in, int out) {
+        DwLayer D;
+        std::memset(&D.d, 0, sizeof D.d);
+        set_name(D.d.name, name);
+        set_name(D.d.bn_name, bn);
+        D.d.channels = c; D.d.pitch = pitch_of(c); D.d.stride = stride; D.d.hin = hin;
+        D.d.clamp_in = 1;                   // every depthwise layer of this network reads an MFMA conv that torchvision follows with ReLU6
+        h->dws.push_back(D);
+        h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, in, out, BUF_NONE, hin, D.d.pitch, BUF_NONE});
+    };
+    int c = add_conv("features.0.0", "features.0.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
+    conv_op(c, BUF_INPUT, 0, BUF_NONE);
+    int X = 0, cin = 32, hcur = 112, idx = 1;
+    static const int cfg[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
+    for (const auto& row : cfg) {
+        for (int b = 0; b < row[2]; ++b, ++idx) {
+            const int t = row[0], cout = row[1], stride = b == 0 ? row[3] : 1, hidden = cin * t;
+            const bool use_res = stride == 1 && cin == cout;
+            const std::string p = "features." + std::to_string(idx) + ".conv.";
+            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
+            if ((size_t)hcur * hcur * pitch_of(hidden) > kMobileActElemsPerImage) return MPX_E_INTERNAL;
+            const int hout = (hcur - 1) / stride + 1;
+            if (t == 1) {
+                add_dw(p + "0.0", p + "0.1", hidden, stride, hcur, X, T2);
+                c = add_conv(p + "1", p + "2", hidden, cout, 1, 1, 0, hout, 0, use_res, false);
+            } else {
+                c = add_conv(p + "0.0", p + "0.1", cin, hidden, 1, 1, 0, hcur, 1, 0, false);
+                conv_op(c, X, T1, BUF_NONE);
+                add_dw(p + "1.0", p + "1.1", hidden, stride, hcur, T1, T2);
+                c = add_conv(p + "2", p + "3", hidden, cout, 1, 1, 0, hout, 0, use_res, false);
+            }
+            conv_op(c, T2, T1, use_res ? X : BUF_NONE);
+            X = T1;
+            cin = cout;
+            hcur = hout;
+        }
+    }
+    const int T = (X + 1) % 3;
+    c = add_conv("features.18.0", "features.18.1", cin, 1280, 1, 1, 0, hcur, 1, 0, false);
+    conv_op(c, X, T, BUF_NONE);
+    h->feat = 1280;
+    h->ops.push_back(Op{OP_AVGPOOL6, -1, T, BUF_POOL, BUF_NONE, hcur, 1280, BUF_NONE});
+    c = add_conv("classifier.1", "", 1280, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
+    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
     h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
     return 0;
 }
@@ -1383,6 +1490,17 @@ int launch_catnorm(mpx_engine* h, const CatNormParams& p, int norm, hipStream_t 
     return 0;
 }
 
+// one dwconv3x3_bn_relu6_kernel launch; `dw` = the engine's depthwise layer it runs for (profile record), -1 from the stand-alone entry
+int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+    const unsigned long long units = (unsigned long long)p.npix * (unsigned)(p.pitch / 8);
+    // as launch_catnorm: about 8 workgroups per CU, striding over the rest
+    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
+    hipLaunchKernelGGL(dwconv3x3_bn_relu6_kernel, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1484,6 +1602,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     }
     for (const TailBlock& tb : h->tails) wbytes += 2 * round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
     for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
+    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)9 * D.d.pitch * 4, 256) + 2 * round_up((size_t)D.d.pitch * 4, 256);
     const size_t scratch_bytes = 4096 * sizeof(float);
     // the stem by superposition (ImageNet ResNets): pooled stem planes, fp32 stem weights + BatchNorm vectors, one image's table (worst case:
     // 49 entries per conv output pixel), the bit planes of one staging call
@@ -1551,6 +1670,11 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
         const size_t nb = round_up((size_t)nl.d.channels * 4, 256);
         nl.scale = (float*)take(nb);
         nl.shift = (float*)take(nb);
+    }
+    for (DwLayer& D : h->dws) {
+        D.w = (float*)take(round_up((size_t)9 * D.d.pitch * 4, 256));
+        D.scale = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
+        D.shift = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
     }
     // the never-written borders (ImageNet) / padding channels (small nets) of the input staging must be zero, and so must
     // the pooled planes' padding channels
@@ -1676,6 +1800,8 @@ int mpx_weights_complete(const mpx_engine* h) {
         if (!L.loaded) return 0;
     for (const NormLayer& nl : h->norms)
         if (!nl.loaded) return 0;
+    for (const DwLayer& D : h->dws)
+        if (!D.loaded) return 0;
     return 1;
 }
 
@@ -1749,7 +1875,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet ? " (VGG and AlexNet stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet ? " (VGG, AlexNet and MobileNetV2 stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -1993,6 +2119,78 @@ int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo
     return launch_catnorm(h, p, -1, as_stream(stream));
 }
 
+int mpx_num_dwconvs(const mpx_engine* h) { return h ? (int)h->dws.size() : MPX_E_ARG; }
+
+int mpx_dwconv_info(const mpx_engine* h, int k, mpx_dwconv_desc* out) {
+    if (!h || !out || k < 0 || k >= (int)h->dws.size()) return MPX_E_ARG;
+    *out = h->dws[k].d;
+    return 0;
+}
+
+int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps) {
+    if (!h) return MPX_E_ARG;
+    if (k < 0 || k >= (int)h->dws.size()) return fail(h, MPX_E_ARG, "load_dwconv: bad depthwise index %d (this engine has %d)", k, (int)h->dws.size());
+    DwLayer& D = h->dws[k];
+    if (!w || !gamma || !beta || !mean || !var) return fail(h, MPX_E_ARG, "load_dwconv: weight or BatchNorm tensors missing for %s", D.d.name);
+    const int n = D.d.channels, pitch = D.d.pitch;
+    std::vector<float> wt((size_t)9 * pitch, 0.f), sc(pitch, 0.f), sh(pitch, 0.f);     // zeros on the padded channels
+    for (int c = 0; c < n; ++c) {
+        for (int t = 0; t < 9; ++t) wt[(size_t)t * pitch + c] = w[(size_t)c * 9 + t];
+        const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)eps);
+        sc[c] = (float)s;
+        sh[c] = (float)((double)beta[c] - (double)mean[c] * s);
+    }
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(D.w, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(D.scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(D.shift, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+    D.loaded = true;
+    return 0;
+}
+
+int mpx_dwconv_params(const mpx_engine* h, int k, const float** w, const float** scale, const float** shift) {
+    if (!h || !w || !scale || !shift || k < 0 || k >= (int)h->dws.size()) return MPX_E_ARG;
+    *w = h->dws[k].w;
+    *scale = h->dws[k].scale;
+    *shift = h->dws[k].shift;
+    return 0;
+}
+
+int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
+                           void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, int clamp_in, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo)
+        return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: null pointer");
+    if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (stride != 1 && stride != 2))
+        return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: B > 0, hin > 0, pitch a positive multiple of 8, stride 1 or 2");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: every pointer must be 16-byte aligned");
+    DwParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.w = w; p.scale = scale; p.shift = shift;
+    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.stride = stride; p.clamp_in = clamp_in != 0;
+    p.npix = (long long)B * p.ho * p.ho;
+    MPX_SET_DEVICE(h);
+    return launch_dwconv(h, p, -1, as_stream(stream));
+}
+
+int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
+                              int c, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
+        return fail(h, MPX_E_ARG, "global_avgpool_clamp6: bad arguments (c multiple of 8)");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1);
+    const int total = B * (c / 8);
+    hipLaunchKernelGGL(global_avgpool_clamp6_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi,
+                       (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
                      void* stream) {
     if (!h) return MPX_E_ARG;
@@ -2100,6 +2298,18 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_HEAD: rc = mpx_head_softmax_gather(h, logits, label, score, pred, B, stream); break;
             case OP_AVGPAD: rc = mpx_avgpool2_pad(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c >> 16, o.c & 0xffff, stream); break;
             case OP_AVGPOOL2: rc = mpx_avgpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
+            case OP_AVGPOOL6: rc = mpx_global_avgpool_clamp6(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
+            case OP_DWCONV: {
+                const DwLayer& D = h->dws[o.conv];
+                DwParams p;
+                std::memset(&p, 0, sizeof p);
+                p.x_hi = hi(o.in); p.x_lo = lo(o.in); p.y_hi = hi(o.out); p.y_lo = lo(o.out);
+                p.w = D.w; p.scale = D.scale; p.shift = D.shift;
+                p.hin = D.d.hin; p.ho = (D.d.hin - 1) / D.d.stride + 1; p.pitch = D.d.pitch; p.stride = D.d.stride; p.clamp_in = D.d.clamp_in;
+                p.npix = (long long)B * p.ho * p.ho;
+                rc = launch_dwconv(h, p, o.conv, as_stream(stream));
+                break;
+            }
             case OP_CATNORM: {
                 // append the fresh g channels (o.in, dense) to the block's raw concatenation (o.res) and write relu(bn(.)) of its
                 // first o.c channels into o.out, in one launch
@@ -2247,6 +2457,11 @@ int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_
 
 int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms) {
+    return mpx_profile_collect_dw(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, nullptr);
+}
+
+int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                           double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -2260,6 +2475,7 @@ int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launch
         if (per_conv_ms && r.kind == OP_CONV && r.conv >= 0) per_conv_ms[r.conv] += ms;
         if (per_norm_ms && r.kind == 2 && r.sub >= 0 && r.sub < (int)h->norms.size()) per_norm_ms[r.sub] += ms;
         if (avgpool2_ms && r.kind == 2 && r.sub == -2) *avgpool2_ms += ms;
+        if (per_dw_ms && r.kind == 2 && r.sub <= kProfSubDw && kProfSubDw - r.sub < (int)h->dws.size()) per_dw_ms[kProfSubDw - r.sub] += ms;
     }
     h->prof_used = 0;
     return 0;
@@ -2279,6 +2495,10 @@ double mpx_flops_per_forward(const mpx_engine* h) {
     double macs = 0.0;
     for (const ConvLayer& L : h->convs)
         macs += (double)L.d.hout * L.d.hout * L.d.cout * L.d.cin * L.d.ksize * L.d.ksize;
+    for (const DwLayer& D : h->dws) {
+        const int ho = (D.d.hin - 1) / D.d.stride + 1;
+        macs += (double)ho * ho * D.d.channels * 9;
+    }
     return 2.0 * macs;
 }
 

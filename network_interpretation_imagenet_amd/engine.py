@@ -29,6 +29,7 @@ ARCH_IDS.update({"vgg%d%s" % (d, bn): (3100 if bn else 3000) + d for d in (11, 1
 ARCH_IDS["alexnet"] = 4000      # torchvision's AlexNet (MPX_ARCH_ALEXNET), the third family the reference's README names
 # torchvision's DenseNets with growth rate 32 (MPX_ARCH_DENSENET + depth); densenet161 (growth rate 48) is not served
 ARCH_IDS.update({"densenet%d" % d: 5000 + d for d in (121, 169, 201)})
+ARCH_IDS["mobilenet_v2"] = 6002   # torchvision's MobileNetV2, width 1.0 (MPX_ARCH_MOBILENET + 2)
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -107,6 +108,8 @@ class MaskedForwardEngine:
         max_batch=512) is the size INTEGRATION.md 1 suggests.  An AlexNet slot holds 2.4 MB and keeps the default of 512.  A DenseNet slot
         holds 14.5 MB -- four 56x56x256 split-fp16 activation buffers (the block's raw concatenation, its normalised copy, conv1's and
         conv2's outputs: 12.8 MB), the input staging and the pooled stem planes, exactly a ResNet slot -- and keeps the default of 512.
+        A MobileNetV2 slot holds 15.3 MB -- three 112x112x96 split-fp16 activation buffers (features.2's expanded map, 1.5x a ResNet
+        buffer: 14.5 MB) and the input staging -- and keeps the default of 512 (7.8 GB).
         stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
@@ -114,7 +117,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet and DenseNets and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets and MobileNetV2 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if max_batch is None:
             if arch.startswith("vgg"):
                 raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
@@ -141,6 +144,11 @@ class MaskedForwardEngine:
             nd = _lib.NormDesc()
             _lib.check(h, self._lib.mpx_norm_info(h, k, C.byref(nd)), "mpx_norm_info")
             self.norms.append(nd)
+        self.dwconvs = []       # the depthwise 3x3 layers (MobileNetV2), a list of their own next to the conv list
+        for k in range(self._lib.mpx_num_dwconvs(h)):
+            dd = _lib.DwConvDesc()
+            _lib.check(h, self._lib.mpx_dwconv_info(h, k, C.byref(dd)), "mpx_dwconv_info")
+            self.dwconvs.append(dd)
         self.flops_per_forward = float(self._lib.mpx_flops_per_forward(h))
         self.num_cus = int(self._lib.mpx_num_cus(h))        # what the persistent kernels' grids are sized from (whole_round_batch)
         self._mean, self._std = _f3(MEAN), _f3(STD)
@@ -162,8 +170,8 @@ class MaskedForwardEngine:
     @property
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
-        which keeps no table) and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet"))
+        which keeps no table), MobileNetV2 and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -209,14 +217,15 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
-        layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy)."""
+        layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's depthwise layers load with the
+        convs, and `only` takes their names ("features.2.conv.1.0") too."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         if only is not None:
             only = set(only)
-            unknown = only - {d.name.decode() for d in self.layers}
+            unknown = only - {d.name.decode() for d in self.layers} - {d.name.decode() for d in self.dwconvs}
             if unknown:
                 raise KeyError("no such conv layers: %s" % sorted(unknown))
 
@@ -251,6 +260,13 @@ class MaskedForwardEngine:
                 args = (_ptr(w), _ptr(cb), _ptr(g), _ptr(b), _ptr(m), _ptr(v))
             _lib.check(self._h, self._lib.mpx_set_conv_weights(self._h, i, *args, float(eps)),
                        "mpx_set_conv_weights(%s)" % name)
+        for k, dd in enumerate(self.dwconvs):
+            name, bn = dd.name.decode(), dd.bn_name.decode()
+            if only is not None and name not in only:
+                continue
+            t = [get(name + ".weight", (dd.channels, 1, 3, 3))]
+            t += [get("%s.%s" % (bn, key), (dd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
+            _lib.check(self._h, self._lib.mpx_load_dwconv(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_dwconv(%s)" % name)
         if only is None:        # the stand-alone BatchNorms belong to no conv: a full load brings them all
             for k, nd in enumerate(self.norms):
                 name = nd.name.decode()
@@ -696,13 +712,16 @@ class MaskedForwardEngine:
     def collect_profile(self):
         """{'ms': {kind: ms}, 'launches': {kind: n}, 'per_conv_ms': [...], 'per_norm_ms': [...], 'avgpool2_ms': ms} accumulated since the
         last call.  per_norm_ms (one entry per stand-alone BatchNorm: its concat-append + BN + ReLU launch) and avgpool2_ms (the
-        transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture."""
+        transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture.  'per_dw_ms'
+        (one entry per depthwise layer) is the same split on a MobileNetV2 engine."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
         per_norm = (C.c_double * max(1, len(self.norms)))()
         avg2 = (C.c_double * 1)()
-        _lib.check(self._h, self._lib.mpx_profile_collect_ex(self._h, ms, n, per, per_norm, avg2), "mpx_profile_collect_ex")
+        per_dw = (C.c_double * max(1, len(self.dwconvs)))()
+        _lib.check(self._h, self._lib.mpx_profile_collect_dw(self._h, ms, n, per, per_norm, avg2, per_dw), "mpx_profile_collect_dw")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
-                "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0])}
+                "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
+                "per_dw_ms": list(per_dw)[:len(self.dwconvs)]}

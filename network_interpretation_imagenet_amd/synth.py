@@ -27,6 +27,9 @@ layers (post-ReLU RMS within 0.2 .. 3 on the `blobs` images; each transition's a
 than a ResNet's, so the classifier gets DENSENET_FC_GAIN instead of FC_GAIN: softmax peak between 0.05 and 0.85
 (tests/test_densenet_cpu.py asserts the bounds).
 
+MobileNetV2 (make_mobilenetv2_state_dict) scales the BatchNorms that ReLU6 follows up so that ReLU6 really clips, and the project
+BatchNorms down by the same factor (its docstring has the draws).
+
 Images are u8 HWC; `blobs` gives smooth low-frequency content (felzenszwalb-friendly),
 `noise` uniform random bytes (content does not affect timing).
 """
@@ -168,9 +171,64 @@ def make_densenet_state_dict(arch, seed=7):
     return sd
 
 
+# torchvision mobilenetv2.py, width 1.0: (expand ratio t, output channels c, blocks n, stride of the first block s)
+MOBILENETV2_CFG = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))
+MOBILENETV2_ACT_GAIN = 2.0      # gamma factor of every BatchNorm that ReLU6 follows
+MOBILENETV2_RES_GAIN = 0.35     # gamma factor of the project BatchNorm of a block with a residual connection
+MOBILENETV2_FC_GAIN = 2.0
+
+
+def make_mobilenetv2_state_dict(seed=7):
+    """OrderedDict with torchvision's MobileNetV2 key set, order and shapes (models.mobilenet_v2().state_dict(): features.0.{0.weight, 1.*},
+    features.1.conv.{0.0.weight, 0.1.*, 1.weight, 2.*}, features.k.conv.{0.0.weight, 0.1.*, 1.0.weight, 1.1.*, 2.weight, 3.*} for k = 2..17,
+    features.18.{0.weight, 1.*}, classifier.1.weight / .bias; every BatchNorm with its num_batches_tracked; no conv has a bias).
+    Draws: convs that ReLU6 follows are He-initialised (1x1 and stem N(0, sqrt(2 / (k*k*cin))), depthwise N(0, sqrt(2 / 9))) and their
+    BatchNorm's gamma is U(0.9, 1.1) x MOBILENETV2_ACT_GAIN, so that pre-activations have a standard deviation of 2 to 3 and ReLU6 clips
+    their upper tail; a project conv (linear: no activation behind it) is N(0, sqrt(1 / cin)) with gamma x 1 / MOBILENETV2_ACT_GAIN, which
+    hands the next block a trunk of the same scale, x MOBILENETV2_RES_GAIN more where the block adds its input, so that the trunk neither
+    grows nor dies through the 10 residual adds (tests/test_mobilenet_cpu.py asserts the bounds)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def bn(prefix, c, factor):
+        _bn(sd, prefix, c, g, last=factor)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    def conv(name, cin, cout, k, gain, groups=1):
+        std = (gain / (k * k * cin // groups)) ** 0.5
+        sd[name + ".weight"] = torch.randn(cout, cin // groups, k, k, generator=g) * std
+
+    conv("features.0.0", 3, 32, 3, 2.0)
+    bn("features.0.1", 32, MOBILENETV2_ACT_GAIN)
+    cin, idx = 32, 1
+    for t, c, n, s in MOBILENETV2_CFG:
+        for b in range(n):
+            stride = s if b == 0 else 1
+            hidden = cin * t
+            p = "features.%d.conv." % idx
+            j = 0
+            if t != 1:
+                conv(p + "0.0", cin, hidden, 1, 2.0)
+                bn(p + "0.1", hidden, MOBILENETV2_ACT_GAIN)
+                j = 1
+            conv(p + "%d.0" % j, hidden, hidden, 3, 2.0, groups=hidden)
+            bn(p + "%d.1" % j, hidden, MOBILENETV2_ACT_GAIN)
+            conv(p + "%d" % (j + 1), hidden, c, 1, 1.0)
+            bn(p + "%d" % (j + 2), c, (MOBILENETV2_RES_GAIN if (stride == 1 and cin == c) else 1.0) / MOBILENETV2_ACT_GAIN)
+            cin = c
+            idx += 1
+    conv("features.18.0", cin, 1280, 1, 2.0)
+    bn("features.18.1", 1280, MOBILENETV2_ACT_GAIN)
+    sd["classifier.1.weight"] = torch.randn(1000, 1280, generator=g) * (MOBILENETV2_FC_GAIN / 1280 ** 0.5)
+    sd["classifier.1.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
-    DenseNet: make_densenet_state_dict) key set."""
+    DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict) key set."""
+    if arch == "mobilenet_v2":
+        return make_mobilenetv2_state_dict(seed)
     if vgg_arch(arch):
         return make_vgg_state_dict(arch, seed)
     if arch == "alexnet":

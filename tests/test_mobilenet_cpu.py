@@ -1,0 +1,276 @@
+"""MobileNetV2 without a GPU: the synthetic state_dict with torchvision's keys in torchvision's order, the parameter and MAC counts, the
+fp64 / fp32 CPU restatement (tests/mobilenet_ref.py) against an independent nn.Module build, the statistics of the synthetic network on
+exactly the rows the GPU test scores (ReLU6 really clips there), the C-ABI surface and the packing of a channel-padded layer."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import mobilenet_ref
+from network_interpretation_imagenet_amd import _lib, engine, synth
+from oracle import scorer
+
+ARCH = "mobilenet_v2"
+CFG = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))
+PARAMS = 3504872            # torchvision's parameter count
+MACS = 300774272            # convs + depthwise convs + classifier
+NEW_SYMBOLS = ("mpx_num_dwconvs", "mpx_dwconv_info", "mpx_load_dwconv", "mpx_dwconv_params", "mpx_dwconv3x3_bn_relu6",
+               "mpx_global_avgpool_clamp6", "mpx_profile_collect_dw")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bn_keys(prefix, c):
+    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
+            (prefix + ".num_batches_tracked", ())]
+
+
+def _expected_keys():
+    """models.mobilenet_v2().state_dict(): key -> shape, in module order, written out from the (t, c, n, s) table."""
+    out = [("features.0.0.weight", (32, 3, 3, 3))] + _bn_keys("features.0.1", 32)
+    cin, k = 32, 1
+    for t, c, n, _s in CFG:
+        for _b in range(n):
+            hidden = cin * t
+            p = "features.%d.conv." % k
+            j = 0
+            if t != 1:
+                out += [(p + "0.0.weight", (hidden, cin, 1, 1))] + _bn_keys(p + "0.1", hidden)
+                j = 1
+            out += [(p + "%d.0.weight" % j, (hidden, 1, 3, 3))] + _bn_keys(p + "%d.1" % j, hidden)
+            out += [(p + "%d.weight" % (j + 1), (c, hidden, 1, 1))] + _bn_keys(p + "%d" % (j + 2), c)
+            cin, k = c, k + 1
+    out += [("features.18.0.weight", (1280, 320, 1, 1))] + _bn_keys("features.18.1", 1280)
+    return out + [("classifier.1.weight", (1000, 1280)), ("classifier.1.bias", (1000,))]
+
+
+def test_synth_mobilenet_state_dict_has_torchvisions_keys_order_and_shapes():
+    sd = synth.make_state_dict(ARCH)
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _expected_keys()
+    assert list(sd) == list(synth.make_mobilenetv2_state_dict())
+    assert all(v.dtype == (torch.int64 if k.endswith("num_batches_tracked") else torch.float32) for k, v in sd.items())
+    params = sum(v.numel() for k, v in sd.items() if k.endswith((".weight", ".bias")))     # nn.Parameters: no running statistics
+    assert params == PARAMS == mobilenet_ref.PARAMS
+    assert not any(re.search(r"\.\d\.bias$", k) and sd[k[:-4] + "weight"].dim() == 4 for k in sd)        # no conv has a bias
+
+
+def test_macs_and_layer_counts_are_the_known_answers():
+    """Counted here from the (t, c, n, s) table alone, then compared with the restatement's topology (which the GPU test compares with
+    the engine's lists and mpx_flops_per_forward = 2 x this)."""
+    macs = 112 * 112 * 32 * 3 * 9
+    cin, h = 32, 112
+    n_conv, n_dw = 1, 0
+    for t, c, n, s in CFG:
+        for b in range(n):
+            stride = s if b == 0 else 1
+            hidden = cin * t
+            ho = (h - 1) // stride + 1
+            if t != 1:
+                macs += h * h * cin * hidden
+                n_conv += 1
+            macs += ho * ho * hidden * 9 + ho * ho * hidden * c
+            n_conv += 1
+            n_dw += 1
+            cin, h = c, ho
+    macs += h * h * cin * 1280 + 1280 * 1000
+    n_conv += 1
+    assert (cin, h) == (320, 7)
+    assert macs == MACS == mobilenet_ref.MACS == mobilenet_ref.macs()
+    convs, dws = mobilenet_ref.topology()
+    assert n_conv + n_dw == 52 and (n_conv, n_dw) == (35, 17)           # 52 convs and depthwise layers, plus the classifier
+    assert len(convs) == n_conv + 1 and len(dws) == n_dw and convs[-1][0] == "classifier.1"
+    assert sorted({c for _n, _b, c, _s, _h in dws if c % 32}) == [144]
+    assert sorted({c[3] for c in convs if c[3] % 32 and c[0] != "classifier.1"}) == [16, 24, 144]
+    assert max(c[3] * c[8] * c[8] for c in convs) == 96 * 112 * 112 == 1204224                 # the largest activation: features.2's expanded map
+    # every conv that ReLU6 follows is read by a depthwise layer or by the global pool: the clamp has a consumer to live in
+    names = [c[0] for c in convs]
+    for name, _bn, _cin, _cout, _k, _s, _p, _hin, _hout, relu, _res in convs:
+        if relu:
+            follower = name[:-3] + "1.0" if name.endswith(".conv.0.0") else None
+            assert name == "features.18.0" or (name == "features.0.0" and dws[0][0] == "features.1.conv.0.0") or follower in [d[0] for d in dws], name
+    assert len(names) == len(set(names))
+
+
+def test_mobilenet_arch_id_is_unique():
+    assert engine.ARCH_IDS[ARCH] == 6002
+    ids = list(engine.ARCH_IDS.values())
+    assert len(ids) == len(set(ids))
+    assert "mobilenet_v3_small" not in engine.ARCH_IDS and "mobilenet_v3_large" not in engine.ARCH_IDS
+    with pytest.raises(ValueError, match="AlexNet"):
+        engine.MaskedForwardEngine("mobilenet_v3_small")
+
+
+def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
+    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
+        header = fh.read()
+    assert "#define MPX_ARCH_MOBILENET 6000" in header
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint %s\(" % name, header), name
+        assert name in _lib.SIGNATURES, name
+        assert getattr(mpx_lib, name) is not None
+    # every entry refuses a null engine before it touches a device
+    dd = _lib.DwConvDesc()
+    p = C.c_void_p()
+    assert mpx_lib.mpx_num_dwconvs(None) == -1
+    assert mpx_lib.mpx_dwconv_info(None, 0, C.byref(dd)) == -1
+    assert mpx_lib.mpx_load_dwconv(None, 0, None, None, None, None, None, 1e-5) == -1
+    assert mpx_lib.mpx_dwconv_params(None, 0, C.byref(p), C.byref(p), C.byref(p)) == -1
+    assert mpx_lib.mpx_dwconv3x3_bn_relu6(None, None, None, None, None, None, None, None, 1, 7, 32, 1, 1, None) == -1
+    assert mpx_lib.mpx_global_avgpool_clamp6(None, None, None, None, None, 1, 49, 1280, None) == -1
+    assert mpx_lib.mpx_profile_collect_dw(None, None, None, None, None, None, None) == -1
+    # the descriptor: name, BatchNorm name, channels, pitch, stride, hin, clamp_in
+    assert [f[0] for f in _lib.DwConvDesc._fields_] == ["name", "bn_name", "channels", "pitch", "stride", "hin", "clamp_in"]
+    assert C.sizeof(_lib.DwConvDesc) == 48 + 48 + 5 * 4
+
+
+@pytest.mark.parametrize("arch_id", [6000, 6001, 6003, 6999])
+def test_unknown_mobilenet_id_is_refused(mpx_lib, arch_id):
+    """mpx_create rejects the id before it touches a device."""
+    h = C.c_void_p()
+    assert mpx_lib.mpx_create(arch_id, 4, 0, C.byref(h)) == -1 and not h.value
+
+
+# ------------------------------------------------------------------------------------------------
+# the restatement against an independent nn.Module build
+# ------------------------------------------------------------------------------------------------
+def _cna(cin, cout, k=3, stride=1, groups=1):
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout), nn.ReLU6(inplace=True))
+
+
+class _InvertedResidual(nn.Module):
+    def __init__(self, inp, oup, stride, expand_ratio):
+        super().__init__()
+        hidden = int(round(inp * expand_ratio))
+        self.use_res_connect = stride == 1 and inp == oup
+        layers = []
+        if expand_ratio != 1:
+            layers.append(_cna(inp, hidden, k=1))
+        layers += [_cna(hidden, hidden, stride=stride, groups=hidden), nn.Conv2d(hidden, oup, 1, 1, 0, bias=False), nn.BatchNorm2d(oup)]
+        self.conv = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.conv(x) if self.use_res_connect else self.conv(x)
+
+
+class _MobileNetV2(nn.Module):
+    """torchvision's module tree (same names, so load_state_dict(strict=True) is the check of the key set), written independently of
+    mobilenet_ref: nn.Sequential modules with nn.ReLU6, as torchvision builds it."""
+
+    def __init__(self):
+        super().__init__()
+        feats = [_cna(3, 32, stride=2)]
+        inp = 32
+        for t, c, n, s in CFG:
+            for i in range(n):
+                feats.append(_InvertedResidual(inp, c, s if i == 0 else 1, t))
+                inp = c
+        feats.append(_cna(inp, 1280, k=1))
+        self.features = nn.Sequential(*feats)
+        self.classifier = nn.Sequential(nn.Dropout(p=0.2), nn.Linear(1280, 1000))
+
+    def forward(self, x):
+        x = self.features(x)
+        return self.classifier(torch.flatten(F.adaptive_avg_pool2d(x, (1, 1)), 1))
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_restatement_matches_an_nn_module_build(dtype):
+    sd = synth.make_state_dict(ARCH)
+    model = _MobileNetV2()
+    model.load_state_dict(sd, strict=True)
+    model.to(dtype).eval()
+    g = torch.Generator().manual_seed(2)
+    x = torch.cat([scorer.to_tensor_normalize(synth.make_images(2)[1])[None], torch.randn(1, 3, 224, 224, generator=g)]).to(dtype)
+    with torch.no_grad():
+        want = model(x)
+        got = mobilenet_ref.forward(mobilenet_ref.cast(sd, dtype), x)
+    assert tuple(got.shape) == (2, 1000)
+    scale = want.abs().max().item()
+    err = (got - want).abs().max().item()
+    print("%s %s: max |d| %.3e of logit scale %.2f" % (ARCH, dtype, err, scale))
+    assert scale > 1.0 and err <= 1e-5 * scale
+
+
+def test_synthetic_mobilenet_statistics_on_the_rows_the_gpu_test_scores(golden_dir):
+    """The trunk neither grows nor dies through the 17 blocks, ReLU6 clips on every activation map, the unmasked softmax is peaked but
+    unsaturated, the fp64 scores with ReLU in place of ReLU6 are different numbers on the end-to-end rows, and on EVERY mask row of
+    mobilenet_ref.E2E_CASES the fp64 top-two logit margin is >= 1e-3: the GPU test then compares the argmax of every row, none excluded."""
+    sd = synth.make_state_dict(ARCH)
+    sd64 = mobilenet_ref.cast(sd, torch.float64)
+    for kind, m, seed in mobilenet_ref.E2E_CASES:
+        img, seg = mobilenet_ref.e2e_inputs(golden_dir, kind)
+        x = scorer.to_tensor_normalize(img)
+        trace = []
+        with torch.no_grad():
+            logits = mobilenet_ref.forward(sd64, x[None].double(), trace)
+        assert len(trace) == 1 + 16 * 3 + 2 + 1               # the stem, (expand, depthwise, block) x 16, features.1's two, features.18
+        trunk = [t.pow(2).mean().sqrt().item() for name, t in trace if name.count(".") == 1 and name not in ("features.0", "features.18")]
+        acts = [(name, t) for name, t in trace if ".conv." in name or name in ("features.0", "features.18")]
+        assert len(trunk) == 17 and len(acts) == 35
+        assert min(trunk) > 0.4 and max(trunk) < 2.5, (min(trunk), max(trunk))
+        clipped = [(t >= 6.0).double().mean().item() for _name, t in acts]
+        assert all(t.max().item() == 6.0 for _name, t in acts) and min(clipped) > 1e-3       # ReLU6 clips on every map it follows
+        p = F.softmax(logits, 1)[0]
+        print("%s %s: trunk rms %.3f .. %.3f, clipped share %.4f .. %.4f, top softmax %.4f, %d classes over 1e-3"
+              % (ARCH, kind, min(trunk), max(trunk), min(clipped), max(clipped), p.max().item(), int((p > 1e-3).sum())))
+        assert 0.05 <= p.max().item() <= 0.95
+        assert int((p > 1e-3).sum()) >= 3
+        label = int(p.argmax())
+        onoff = synth.random_onoff(m, len(np.unique(seg)), seed=seed)
+        s64, logits64 = mobilenet_ref.score_masks_fp64(sd, x, seg, onoff, label)
+        s_relu, _l = mobilenet_ref.score_masks_fp64(sd, x, seg, onoff, label, act6=False)
+        top2 = np.sort(logits64, axis=1)[:, -2:]
+        gap = top2[:, 1] - top2[:, 0]
+        print("%s %s: %d rows, scores %.4f .. %.4f, smallest fp64 top-two margin %.4f, |relu6 - relu| score %.4f .. %.4f"
+              % (ARCH, kind, m, s64.min(), s64.max(), gap.min(), np.abs(s64 - s_relu).min(), np.abs(s64 - s_relu).max()))
+        assert gap.min() >= 1e-3                                # every row, none excluded
+        assert np.abs(s64 - s_relu).min() > 1e-3                # ReLU6 is active on every end-to-end row
+        assert s64.max() - s64.min() > 0.01                     # the masks move the score
+
+
+# ------------------------------------------------------------------------------------------------
+# packing of a channel-padded layer
+# ------------------------------------------------------------------------------------------------
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def test_pack_a_channel_padded_1x1_layer(mpx_lib):
+    """features.3.conv.0.0: 24 -> 144 on planes with a pitch of 32, stored with a pitch of 160 (cout_pad 256).  K = 32 is ONE K step; the
+    weight columns of the 8 padded input channels are zero, and so are the weight rows, scale and shift of every row from 144 on -- the 16
+    stored padding channels among them, which the epilogue therefore writes as 0 * acc + 0 = 0."""
+    rng = np.random.default_rng(24)
+    w = (rng.standard_normal((144, 24, 1, 1)) * (2.0 / 24) ** 0.5).astype(np.float32)
+    gamma, beta, mean = (rng.standard_normal(144).astype(np.float32) for _ in range(3))
+    var = rng.uniform(0.5, 2.0, 144).astype(np.float32)
+    d = _lib.ConvDesc()
+    d.cin, d.cout, d.ksize, d.stride, d.pad = 24, 144, 1, 1, 0
+    d.k_packed = K = 32
+    d.cout_pad = 256
+    hi = np.full((256, K), 0x7e00, dtype=np.uint16)
+    lo = np.full_like(hi, 0x7e00)
+    sc = np.full(256, np.nan, dtype=np.float32)
+    sh = np.full(256, np.nan, dtype=np.float32)
+    assert mpx_lib.mpx_pack_conv_weights(C.byref(d), _p(w), None, _p(gamma), _p(beta), _p(mean), _p(var), 1e-5, _p(hi), _p(lo), _p(sc), _p(sh)) == 0
+    row = np.arange(256)[:, None]
+    k = np.arange(K)[None, :]
+    r = row % 16
+    at = ((((row // 16) * (K // 32) + k // 32) * 16 + r) * 4 + (((k // 8) % 4) ^ ((r // 8) * 2))) * 8 + k % 8
+    ph, pl = hi.ravel()[at], lo.ravel()[at]
+    assert (ph[:, 24:] == 0).all() and (pl[:, 24:] == 0).all()                  # zero weight columns on the padded input channels
+    assert (ph[144:] == 0).all() and (pl[144:] == 0).all()                      # zero rows from the layer's last channel on
+    assert (sc[144:] == 0).all() and (sh[144:] == 0).all()                      # ... with zero scale and shift
+    mx = np.abs(w.reshape(144, -1)).max(1).astype(np.float64)
+    e = 10 - (np.floor(np.log2(mx)).astype(int) + 1)
+    planes = ph.view(np.float16).astype(np.float64) + pl.view(np.float16).astype(np.float64)
+    np.testing.assert_allclose(planes[:144, :24], w.reshape(144, 24).astype(np.float64) * (2.0 ** e)[:, None], rtol=0, atol=1024 * 2.0 ** -21)
+    s = gamma.astype(np.float64) / np.sqrt(var.astype(np.float64) + 1e-5)
+    assert np.array_equal(sc[:144], (s * 2.0 ** -e).astype(np.float32))
+    assert np.array_equal(sh[:144], (beta.astype(np.float64) - mean.astype(np.float64) * s).astype(np.float32))
+    # a K the planes' pitch does not explain is refused
+    d.k_packed = 24
+    assert mpx_lib.mpx_pack_conv_weights(C.byref(d), _p(w), None, _p(gamma), _p(beta), _p(mean), _p(var), 1e-5, _p(hi), _p(lo), _p(sc), _p(sh)) == -1

@@ -157,6 +157,24 @@ if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + 
         print("%3dx%-3d C %4d..%-4d x%-3d %8.3f ms %9.1f MB %7.2f TB/s" % (hw, hw, c0, c1, n, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
     print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
           % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
+if eng.dwconvs:   # MobileNetV2: the depthwise 3x3 + BN + ReLU6 launches between the 1x1 convs; bytes = split-fp16 read (each input element once) + written
+    print("-- depthwise 3x3 + BN + ReLU6 (mpx_dwconv3x3_bn_relu6: one launch per depthwise layer); bytes = split-fp16 planes read + written, pitch channels per pixel --")
+    tot_dw = tot_bytes = 0.0
+    for dd, ms in zip(eng.dwconvs, prof["per_dw_ms"]):
+        ms /= reps
+        ho = (dd.hin - 1) // dd.stride + 1
+        nbytes = batch * 4.0 * dd.pitch * (dd.hin * dd.hin + ho * ho)
+        tot_dw += ms
+        tot_bytes += nbytes
+        print("%-22s C %4d pitch %4d s%d %3dx%-3d -> %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (
+            dd.name.decode(), dd.channels, dd.pitch, dd.stride, dd.hin, dd.hin, ho, ho, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    pool_ms = prof["ms"]["pool"] / reps - tot_dw
+    allms = sum(prof["ms"].values()) / reps
+    print("depthwise total %.3f ms/batch, %.1f MB -> %.2f TB/s; clamped global pool %.3f ms/batch; conv total %.3f ms/batch"
+          % (tot_dw, tot_bytes / 1e6, tot_bytes / max(tot_dw, 1e-9) / 1e9, pool_ms, tot))
+    print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise %.1f %%, staging (K0) %.1f %%, global pool %.1f %%, head %.1f %%"
+          % (100 * tot / allms, 100 * tot_dw / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms,
+             100 * prof["ms"]["head"] / reps / allms))
 tails = eng.bottleneck_tails()
 if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_MASK", "3") == "3":
     names = [d.name.decode() for d in eng.layers]

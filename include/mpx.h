@@ -91,6 +91,24 @@ enum {
  * scale and shift on the padded rows: padded channels are exact zeros wherever they are read); such layers run the generic tiles only.
  * Three activation buffers of 112 * 112 * 96 elements per image (features.2's expanded map, 1.5 x a ResNet buffer): 15.3 MB per slot with
  * the staging.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
+ * -- or torchvision's SqueezeNet 1.1, the small network of the model zoo (1.2 M parameters, 0.35 GMAC per forward):
+ *   MPX_ARCH_SQUEEZENET + 11      squeezenet1_1; every other id in [7000, 8000) is MPX_E_ARG (squeezenet1_0 -- a 7x7 stride-2 unpadded stem and a
+ *                                 ceil-mode pool whose last window hangs over the edge -- included)
+ * A SqueezeNet engine runs features.0 (3 -> 64, 3x3 stride 2 WITHOUT padding, 224 -> 111, reading the padded NHWC4 staging: k_packed = 96) +
+ * ReLU, eight Fire modules features.N = Fire(cin, s, e, e), (N, cin, s, e) = (3,64,16,64) (4,128,16,64) (6,128,32,128) (7,256,32,128)
+ * (9,256,48,192) (10,384,48,192) (11,384,64,256) (12,512,64,256) -- squeeze 1x1 + ReLU, then expand1x1 and expand3x3 (pad 1) on the squeeze map,
+ * each + ReLU, concatenated along the channels --, the max pools features.2 / .5 / .8 in front of Fire 3, 6 and 9 (MaxPool2d(3, 2,
+ * ceil_mode=True) on 111 -> 55 -> 27 -> 13: hin - 3 is even in all three, so ceil mode equals floor mode, every window lies inside the map and
+ * mpx_maxpool3x3s2p0 serves them), classifier.1 (512 -> 1000, 1x1) + ReLU on the 13x13 map and mpx_global_avgpool_logits.  Every conv has a
+ * bias and there is no BatchNorm (bn_name ""; the bias loads as `beta`, as on the plain VGGs).  26 entries in the conv list.
+ * THE CONCATENATION IS THE EXPAND CONVS' EPILOGUE.  expand1x1 writes channels [0, e) and expand3x3 channels [e, 2e) of the same planes
+ * [B][h][h][2e] (mpx_conv_out_slice: row pitch 2e, channel offset 0 or e); nothing joins or copies them.  Such OUTPUT-SLICE layers run the
+ * generic tiles 0, 1, 2, 4 and 7 only, take no residual operand, and mpx_conv_bn_act on one of them takes the BASE of the concatenated planes.
+ * THE LAST CONV ENTRY IS NOT THE LOGIT LAYER HERE.  classifier.1 is followed by ReLU and the average pool, so in mpx_conv_bn_act it behaves
+ * like any other layer: split planes [B][13][13][1000] out, out_f32 must be NULL; the logits are mpx_global_avgpool_logits' output.
+ * Squeeze widths 16 and 48 are stored with a pitch of 32 and 64 (zero weight columns, zero scale and shift on the padded rows: exact zeros).
+ * Three activation buffers of 111 * 111 * 64 elements per image (a module's input, its squeeze map, the concatenation): 10.3 MB per slot with
+ * the staging.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -101,6 +119,7 @@ enum {
 #define MPX_ARCH_ALEXNET 4000
 #define MPX_ARCH_DENSENET 5000
 #define MPX_ARCH_MOBILENET 6000
+#define MPX_ARCH_SQUEEZENET 7000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -126,15 +145,21 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets and MobileNetV2, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2 and SqueezeNet 1.1, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
 /* ---- topology / weights ------------------------------------------------------------------
  * Layer i in [0, mpx_num_convs): every conv in forward order; the last entry is the logit layer, whatever its name ("fc", "fc1",
- * "classifier.6"). */
+ * "classifier.6") -- except on a SqueezeNet engine, whose last entry (classifier.1) writes planes like any other layer and whose logits come
+ * out of mpx_global_avgpool_logits. */
 int mpx_num_convs(const mpx_engine* h);
 int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
+/* Where layer i writes: *pitch = channels between adjacent pixels of its output planes, *offset = its first channel within a pixel.  An
+ * ordinary layer fills whole pixel rows: its stored channel count (cout, or cout rounded up to 32 where the network pads) and 0.  A
+ * SqueezeNet expand conv writes half of its Fire module's concatenation: 2 * cout and 0 (expand1x1) or cout (expand3x3).  mpx_conv_desc keeps
+ * its layout. */
+int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
  * w = conv weight OIHW [cout][cin][k][k]; conv_bias = the conv's own bias [cout] or NULL (torchvision's ResNet convs have
@@ -296,7 +321,10 @@ int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
  * in_hi|lo, res_hi|lo, out_hi|lo: DEV fp16 NHWC planes [B][h][w][c] (layer 0 reads the engine's padded
  * NHWC4 input staging instead: pass in_hi = in_lo = NULL).  res_* may be NULL.
  * For the last entry ("fc") out_hi/out_lo are ignored and out_f32 (DEV f32[B][1000]) is written;
- * for every other layer out_f32 must be NULL. */
+ * for every other layer out_f32 must be NULL (a SqueezeNet engine has no such entry: its last conv, classifier.1, writes planes
+ * [B][13][13][1000] and out_f32 must be NULL there too).
+ * An output-slice layer (a SqueezeNet expand conv, mpx_conv_out_slice): out_hi|lo is the BASE of the concatenated planes
+ * [B][h][w][pitch]; the layer writes channels [offset, offset + cout) of every pixel and nothing else; res_* must be NULL. */
 int mpx_conv_bn_act(mpx_engine* h, int i, const void* in_hi, const void* in_lo,
                     const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
                     float* out_f32, int B, void* stream);
@@ -404,6 +432,16 @@ int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, 
  *           mpx_global_avgpool is unchanged.  c a multiple of 8. */
 int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
                               int c, void* stream);
+
+/* ---- SqueezeNet: the global average pool that ends the network, [B][hw][c] split planes -> fp32 logits [B][out_pitch].
+ * replaces: `nn.AdaptiveAvgPool2d((1, 1))` of torchvision's SqueezeNet classifier and the torch.flatten behind it inside
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  Per channel: the hw values hi + lo (exact in fp32) summed in
+ *           pixel order in fp32, then one correctly rounded division by hw; written as fp32, which is what mpx_head_softmax_gather reads.
+ *           Channels [c, out_pitch) of a row are left untouched.  mpx_global_avgpool is unchanged.
+ * MPX_E_ARG for a null pointer, B <= 0, hw <= 0, c not a positive multiple of 8, out_pitch < c or planes that are not 16-byte aligned.
+ * ONE launch. */
+int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_lo, float* out_f32, int B, int hw, int c, int out_pitch,
+                              void* stream);
 
 /* ---- K1 + K3 in one launch: the ImageNet stem and its max pool -------------------------------------------
  * replaces: `x = self.conv1(x); x = self.bn1(x); x = self.relu(x); x = self.maxpool(x)` (torchvision resnet.py, reached through

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mpx_global_avgpool_clamp6": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_dw": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # SqueezeNet 1.1: where a conv writes (the expand convs fill halves of one concatenation), the average pool that writes the logits
+    "mpx_conv_out_slice": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mpx_global_avgpool_logits": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@
 #include "mpx_btail.h"
 #include "mpx_stemtab.h"
 #include "mpx_dw.h"
+#include "mpx_fire.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,10 +35,11 @@ constexpr size_t kActElemsPerImage = 112 * 112 * 64;   // ImageNet: largest acti
 constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel maps of the first stage
 constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output of features.0
 constexpr size_t kMobileActElemsPerImage = 112 * 112 * 96;   // MobileNetV2: features.2's expanded map, 1.5 x kActElemsPerImage
+constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: the output of features.0 (the largest concatenation is 55 * 55 * 128)
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
-              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11 };
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -52,6 +54,11 @@ struct ConvLayer {
     bool has_bias = false;  // the reference module is nn.Conv2d(bias=True) (small nets): state_dict has <name>.bias
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
     int cout_store = 0;     // channels per pixel of the output planes (row pitch and store bound)
+    // output slice (a SqueezeNet expand conv: half of its Fire module's concatenation): the layer writes channels [y_offset, y_offset +
+    // cout_store) of planes whose pixels are y_pitch channels apart, on the SLICE form of the generic kernel (mpx_conv.h).  y_pitch = 0: an
+    // ordinary layer, which fills whole pixel rows of cout_store channels.
+    int y_pitch = 0;
+    int y_offset = 0;
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
     int tile_default = -1;  // the layer's default where the topology sets one of its own (DenseNet's conv2); -1: default_tile(d)
     // downsample fusion (bottleneck blocks): the block's last 1x1 conv ("main") and its downsample 1x1 conv ("ds")
@@ -131,6 +138,7 @@ struct mpx_engine {
     std::vector<NormLayer> norms;   // its stand-alone BatchNorms in forward order
     bool mobilenet = false;         // torchvision MobileNetV2: inverted residuals over three activation buffers, staged through K0 only
     std::vector<DwLayer> dws;       // its depthwise layers in forward order
+    bool squeezenet = false;        // torchvision SqueezeNet 1.1: Fire modules over three activation buffers, staged through K0 only
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -228,6 +236,7 @@ int build_topology_vgg(mpx_engine* h);
 int build_topology_alexnet(mpx_engine* h);
 int build_topology_densenet(mpx_engine* h);
 int build_topology_mobilenet(mpx_engine* h);
+int build_topology_squeezenet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -236,6 +245,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) return build_topology_alexnet(h);
     if (h->arch >= MPX_ARCH_DENSENET && h->arch < MPX_ARCH_DENSENET + 1000) return build_topology_densenet(h);
     if (h->arch >= MPX_ARCH_MOBILENET && h->arch < MPX_ARCH_MOBILENET + 1000) return build_topology_mobilenet(h);
+    if (h->arch >= MPX_ARCH_SQUEEZENET && h->arch < MPX_ARCH_SQUEEZENET + 1000) return build_topology_squeezenet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -848,6 +858,92 @@ int build_topology_mobilenet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision SqueezeNet 1.1 (squeezenet.py, version "1_1"): features.0 = conv 3 -> 64 3x3 stride 2 WITHOUT padding (224 -> 111) + ReLU, eight
+// Fire modules features.N = Fire(cin, s, e, e) for (N, cin, s, e) = (3,64,16,64) (4,128,16,64) (6,128,32,128) (7,256,32,128) (9,256,48,192)
+// (10,384,48,192) (11,384,64,256) (12,512,64,256) with a MaxPool2d(3, 2, ceil_mode=True) in front of features.3, .6 and .9, then
+// classifier.1 = conv 512 -> 1000 1x1 + ReLU on the 13x13 map and a global average pool whose output is the logits (Dropout is the identity
+// in eval).  A Fire module is squeeze 1x1 + ReLU, then expand1x1 and expand3x3 (pad 1) on the squeeze map, each + ReLU, concatenated along
+// the channels.  Every conv has a bias and there is no BatchNorm: the layers load as the plain VGG convs do (the bias as `beta`).
+// Op list, 31 launches: stem | pool 111 -> 55 | Fire 3, Fire 4 | pool 55 -> 27 | Fire 6, Fire 7 | pool 27 -> 13 | Fire 9 .. 12 | classifier.1 |
+// average pool -> logits | K4b; a Fire module is three OP_CONV.
+// The max pools: 111 - 3, 55 - 3 and 27 - 3 are even, so ceil((hin - 3) / 2) = floor((hin - 3) / 2) -- the ceil-mode output has the floor-mode
+// size and its last window ends on the last row / column of the map, none hangs over the edge.  OP_MAXPOOL3P0 (AlexNet's unpadded
+// floor-mode 3x3 stride-2 pool) therefore IS this pool; no new pool kernel.  (squeezenet1_0's 109 -> 54 -> 27 -> 13 has an odd hin - 3 at 54: not served.)
+// The concatenation: expand1x1 writes channels [0, e) and expand3x3 channels [e, 2e) of the same planes [B][h][h][2e] (y_pitch / y_offset:
+// the SLICE form of the generic kernel), so nothing is copied and no op joins them.
+// Channels: the squeeze widths 16 and 48 are stored with a pitch of 32 and 64 (cin_pad / cout_store as MobileNetV2: zero weight columns,
+// zero scale and shift on the padded rows, exact zeros in the padded channels), so K = 32 / 32 / 64 / 64 for the 1x1 expands and 288 / 288 /
+// 576 / 576 for the 3x3 ones.
+// Buffers: three of 111 * 111 * 64 elements per image: X the module input, S the squeeze map, Y the concatenation, which is the next X.
+int build_topology_squeezenet(mpx_engine* h) {
+    if (h->arch != MPX_ARCH_SQUEEZENET + 11) return MPX_E_ARG;
+    h->squeezenet = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kSqueezeActElemsPerImage;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    // slice: 0 = an ordinary layer, 1 / 2 = the first / second half of a concatenation of 2 * cout channels
+    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int pad, int hin, int slice, bool head) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = 1;
+        L.has_bias = true;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 0)
+        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
+        L.cout_store = (head || slice) ? cout : pitch_of(cout);
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        if (slice) {
+            L.y_pitch = 2 * cout;
+            L.y_offset = slice == 2 ? cout : 0;
+            // default_tile judges the descriptor alone and would hand 64 -> 256 the 256x256 or patch kernels, which know no output pitch:
+            // its rules restricted to the generic tiles (64-row tiles for cout <= 64, tile 0 for 3x3, tile 7 for the expanding 1x1 layers)
+            L.tile = L.tile_default = cout <= 64 ? (k >= 3 ? 1 : 4) : (k == 3 ? 0 : 7);
+        }
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
+    int c = add_conv("features.0", 3, 64, 3, 2, 0, MPX_IMG, 0, false);
+    conv_op(c, BUF_INPUT, 0);
+    int X = 0, cin = 64, hcur = h->convs[c].d.hout;
+    static const int fires[8][3] = {{3, 16, 64}, {4, 16, 64}, {6, 32, 128}, {7, 32, 128}, {9, 48, 192}, {10, 48, 192}, {11, 64, 256}, {12, 64, 256}};
+    for (const auto& f : fires) {
+        const int N = f[0], s = f[1], e = f[2];
+        if (N == 3 || N == 6 || N == 9) {       // features.2 / .5 / .8
+            if ((hcur - 3) % 2 != 0) return MPX_E_INTERNAL;     // ceil mode would differ from the floor-mode kernel
+            const int O = (X + 1) % 3;
+            h->ops.push_back(Op{OP_MAXPOOL3P0, -1, X, O, BUF_NONE, hcur, cin, BUF_NONE});
+            hcur = (hcur - 3) / 2 + 1;
+            X = O;
+        }
+        const int S = (X + 1) % 3, Y = (X + 2) % 3;
+        if ((size_t)hcur * hcur * 2 * e > kSqueezeActElemsPerImage || (size_t)hcur * hcur * pitch_of(s) > kSqueezeActElemsPerImage) return MPX_E_INTERNAL;
+        const std::string p = "features." + std::to_string(N) + ".";
+        c = add_conv(p + "squeeze", cin, s, 1, 1, 0, hcur, 0, false);
+        conv_op(c, X, S);
+        c = add_conv(p + "expand1x1", s, e, 1, 1, 0, hcur, 1, false);
+        conv_op(c, S, Y);
+        c = add_conv(p + "expand3x3", s, e, 3, 1, 1, hcur, 2, false);
+        conv_op(c, S, Y);
+        X = Y;
+        cin = 2 * e;
+    }
+    // classifier.1 is the last entry of the conv list but NOT the logit layer (is_fc): it writes split planes [B][13][13][1000] like any
+    // other layer, and the average pool behind it writes the fp32 logits
+    const int T = (X + 1) % 3;
+    if ((size_t)hcur * hcur * MPX_NUM_CLASSES > kSqueezeActElemsPerImage) return MPX_E_INTERNAL;
+    c = add_conv("classifier.1", cin, MPX_NUM_CLASSES, 1, 1, 0, hcur, 0, true);
+    conv_op(c, X, T);
+    h->feat = MPX_NUM_CLASSES;
+    h->ops.push_back(Op{OP_AVGLOGITS, -1, T, BUF_NONE, BUF_NONE, hcur, MPX_NUM_CLASSES, BUF_NONE});
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -962,6 +1058,12 @@ template <class Cfg, bool DUAL = false>
 int launch_conv_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
     long long tiles;
     if (int rc = conv_tiles(h, p, L.d.cout_pad, Cfg::TC, Cfg::TP, tiles)) return rc;
+    if (L.y_pitch) {        // an output slice (launch_conv has set p.y_pitch and advanced p.y_*): the SLICE form, whatever else the row offers
+        if (p.r_hi || p.y_f32 || p.k1 || p.y_pitch != L.y_pitch)
+            return fail(h, MPX_E_INTERNAL, "slice conv: %s takes no residual operand, no fp32 output and no second K segment", L.d.name);
+        hipLaunchKernelGGL((conv_f16x3_kernel<Cfg, false, false, true>), dim3((unsigned)tiles), dim3(Cfg::NT), Cfg::LDS, st, p);
+        return launched(h, id);
+    }
     if constexpr (DUAL) {
         if (p.k1) {
             if (((p.k1 >> 5) - Cfg::NSX) < 0 || (((p.k1 >> 5) - Cfg::NSX) & 1))
@@ -1125,6 +1227,11 @@ const KernelLds kKernelLds[] = {
     {(const void*)conv256p_f16x3_kernel<false>, Conv256P::LDS},
     {(const void*)conv256p_f16x3_kernel<true>, Conv256P::LDS},
     {(const void*)conv_f16x3_kernel<ConvTile4>, ConvTile4::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile0, false, false, true>, ConvTile0::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile1, false, false, true>, ConvTile1::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile2, false, false, true>, ConvTile2::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile4, false, false, true>, ConvTile4::LDS},
+    {(const void*)conv_f16x3_kernel<ConvTile7, false, false, true>, ConvTile7::LDS},
     {(const void*)btail_f16x3_kernel<BtResC64>, BtResC64::LDS},
     {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
     {(const void*)btail_f16x3_kernel<BtDualC64>, BtDualC64::LDS},
@@ -1143,9 +1250,10 @@ const TileRow* find_tile(int id) {
 }
 
 // Layer L may run row r's kernel.  The predicates see the descriptor, whose cin is the channels per input pixel except in the small
-// networks' planes, padded to 32 (cin_pad); the stem and the fc read planes of their own.
+// networks' planes, padded to 32 (cin_pad); the stem and the fc read planes of their own.  Only the generic kernel has a SLICE form, so an
+// output-slice layer (y_pitch) runs the rows without a predicate -- tiles 0, 1, 2, 4 and 7 -- and nothing else.
 bool eligible(const TileRow& r, const ConvLayer& L) {
-    return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && r.eligible(L.d));
+    return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && r.eligible(L.d));
 }
 
 int launch_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
@@ -1218,7 +1326,9 @@ int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const ha
         // a K step is one kernel row: a run of 8 pixels x 4 channels starting at the window's left edge in the staging, whose
         // 3-pixel border already holds the padding (the 7x7 stem's pad 3: origin shift 0; the VGG 3x3 pad-1 layer: -2).  A run that
         // passes a row's end reads the next row of the same image (row 2y + 3 + ky <= 229 for the stem, y + 2 + ky <= 227 for VGG),
-        // and meets the zero weights of px >= ksize.  AlexNet's 11-wide row is two K steps, a run of 16 pixels (k_per_tap = 64; the
+        // and meets the zero weights of px >= ksize.  SqueezeNet's unpadded 3x3 stride-2 stem: origin shift +3, rows 2y + 3 + ky <= 225,
+        // columns 2x + 3 .. 2x + 10 <= 230 -- the last column's run passes the row end by ONE pixel (the first of the next row, always inside
+        // the image's own 230 x 230 staging since the row is at most 225) and meets zero weights there.  AlexNet's 11-wide row is two K steps, a run of 16 pixels (k_per_tap = 64; the
         // kernel walks c0 = 0, 32 within a tap): origin shift -1, columns 4x + 1 .. 4x + 16 <= 232, rows 4y + 1 + ky <= 227.
         p.x_hi = h->in_hi; p.x_lo = h->in_lo;
         p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
@@ -1246,6 +1356,11 @@ int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, 
     if (int rc = conv_params(h, L, in_hi, in_lo, y_hi, y_lo, B, p)) return rc;
     if ((long long)B * p.hin * p.win > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
     p.r_hi = r_hi; p.r_lo = r_lo; p.y_f32 = y_f32;
+    if (L.y_pitch) {        // output slice: y_* is the base of the concatenated planes; the kernel gets it advanced to the layer's first channel
+        if (r_hi || r_lo || y_f32) return fail(h, MPX_E_ARG, "conv: %s writes a channel slice; it takes no residual operand and no fp32 output", L.d.name);
+        p.y_pitch = L.y_pitch;
+        p.y_hi += L.y_offset; p.y_lo += L.y_offset;
+    }
     ProfScope ps(h, st, OP_CONV, i);
     h->last_kernels = 0;
     // The 256x256 kernel keeps ONE workgroup per CU, so a launch runs in "rounds" of num_cus tiles and a small remainder would
@@ -1256,7 +1371,7 @@ int launch_conv(mpx_engine* h, int i, const half_t* in_hi, const half_t* in_lo, 
     // split of the 3x3 patch kernel's and tile 0's last round was measured and gains nothing: their remainder lives as long
     // as one of their tiles whatever its tile size)
     const TileRow* row = find_tile(L.tile);
-    if (row && row->split && !L.is_stem) {
+    if (row && row->split && !L.is_stem && !L.y_pitch) {     // (eligible() keeps slice layers off these rows; the split's offsets assume pitch = cout)
         const long long M = p.M, tiles_c = (p.cout + Conv256::TC - 1) / Conv256::TC, tiles_p = (M + Conv256::TP - 1) / Conv256::TP;
         const long long total = tiles_p * tiles_c, rounds = total / h->num_cus, rest = total - rounds * h->num_cus;
         const long long howo = (long long)p.ho * p.wo;
@@ -1875,7 +1990,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet ? " (VGG, AlexNet and MobileNetV2 stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet ? " (VGG, AlexNet, MobileNetV2 and SqueezeNet stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -2191,6 +2306,30 @@ int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_l
     return 0;
 }
 
+int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_lo, float* out_f32, int B, int hw, int c, int out_pitch,
+                              void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_f32 || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || out_pitch < c || (long long)B * (c / 8) > 0x7fffffffLL)
+        return fail(h, MPX_E_ARG, "global_avgpool_logits: bad arguments (c a multiple of 8, out_pitch >= c)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo) & 15) return fail(h, MPX_E_ARG, "global_avgpool_logits: the planes must be 16-byte aligned");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1);
+    const int total = B * (c / 8);
+    hipLaunchKernelGGL(global_avgpool_logits_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi,
+                       (const half_t*)in_lo, out_f32, B, hw, c, out_pitch);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset) {
+    if (!h || !pitch || !offset || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    const ConvLayer& L = h->convs[i];
+    *pitch = L.y_pitch ? L.y_pitch : L.cout_store;
+    *offset = L.y_pitch ? L.y_offset : 0;
+    return 0;
+}
+
 int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
                      void* stream) {
     if (!h) return MPX_E_ARG;
@@ -2299,6 +2438,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_AVGPAD: rc = mpx_avgpool2_pad(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c >> 16, o.c & 0xffff, stream); break;
             case OP_AVGPOOL2: rc = mpx_avgpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
             case OP_AVGPOOL6: rc = mpx_global_avgpool_clamp6(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
+            case OP_AVGLOGITS: rc = mpx_global_avgpool_logits(h, hi(o.in), lo(o.in), logits, B, o.hin * o.hin, o.c, h->logit_pitch, stream); break;
             case OP_DWCONV: {
                 const DwLayer& D = h->dws[o.conv];
                 DwParams p;

@@ -69,7 +69,8 @@ struct ConvParams {
     const half_t* x2_lo;
     int hin2, win2, pix_stride2, stride2;
     int k1;
-    int n_tiles;             // unused (read by the removed persistent kernel of tile id 8; kept: the argument layout stays)
+    int y_pitch;             // SLICE kernels only: elements between adjacent output pixels of y (a Fire concatenation's 2e); 0 and unread in every
+                             // other form (the slot of the removed persistent kernel's n_tiles: the layout of every field before it stays)
 #ifdef MPX_DIAG
     unsigned long long* stamps;   // diagnostic build only (tools/probes/conv_timeline.py): 8 u64 per workgroup
 #endif
@@ -147,7 +148,12 @@ __device__ __forceinline__ void wait_vmcnt() {
 constexpr int POOL_PY = 7, POOL_PX = 8;                                    // pooled pixels per tile: rows, columns
 constexpr int POOL_CY = 2 * POOL_PY + 1, POOL_CX = 2 * POOL_PX + 1;        // conv pixels under them
 
-template <class C, bool DUAL = false, bool POOL = false>
+// SLICE (the two expand convs of a SqueezeNet Fire module): the layer fills channels [offset, offset + cout) of planes whose pixels are
+// y_pitch channels apart -- y_hi / y_lo arrive advanced by the channel offset, phase 2 stores at pix * y_pitch + co8, and co8 < cout stays the
+// store bound, which is what keeps a 128-wide tile of a 64-channel slice out of its neighbour's half.  expand1x1 and expand3x3 thus write
+// the two halves of one buffer and the concatenation is never copied.  No residual operand and no fp32 output (the host refuses both).
+// K loop and phases 0 / 1 are the other forms'; every other instantiation compiles to what it was (the template parameter is a constant).
+template <class C, bool DUAL = false, bool POOL = false, bool SLICE = false>
 __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (buffer-resource builtins are device-only)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -456,7 +462,7 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvPa
     const int co8 = n0 + g * 8;
     const bool co_ok = co8 < p.cout;
     h8 rh[ITERS], rl[ITERS];
-    if (p.r_hi) {
+    if (!SLICE && p.r_hi) {
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int pix = m0 + it * PPI + prow2;
@@ -539,7 +545,7 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvPa
         const f4 v0 = *(const f4*)(smem + pl * RP + (((2 * g) ^ (pl & 7)) << 4));
         const f4 v1 = *(const f4*)(smem + pl * RP + (((2 * g + 1) ^ (pl & 7)) << 4));
         float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        if (p.r_hi) {
+        if (!SLICE && p.r_hi) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += (float)rh[it][j] + (float)rl[it][j];
         }
@@ -547,8 +553,8 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvPa
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
         }
-        const size_t o = (size_t)pix * p.cout + co8;
-        if (p.y_f32) {
+        const size_t o = (size_t)pix * (SLICE ? p.y_pitch : p.cout) + co8;
+        if (!SLICE && p.y_f32) {
             *(f4*)(p.y_f32 + o) = (f4){v[0], v[1], v[2], v[3]};
             *(f4*)(p.y_f32 + o + 4) = (f4){v[4], v[5], v[6], v[7]};
         } else {

@@ -30,6 +30,7 @@ ARCH_IDS["alexnet"] = 4000      # torchvision's AlexNet (MPX_ARCH_ALEXNET), the 
 # torchvision's DenseNets with growth rate 32 (MPX_ARCH_DENSENET + depth); densenet161 (growth rate 48) is not served
 ARCH_IDS.update({"densenet%d" % d: 5000 + d for d in (121, 169, 201)})
 ARCH_IDS["mobilenet_v2"] = 6002   # torchvision's MobileNetV2, width 1.0 (MPX_ARCH_MOBILENET + 2)
+ARCH_IDS["squeezenet1_1"] = 7011  # torchvision's SqueezeNet 1.1 (MPX_ARCH_SQUEEZENET + 11); squeezenet1_0 is not served
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -110,6 +111,8 @@ class MaskedForwardEngine:
         conv2's outputs: 12.8 MB), the input staging and the pooled stem planes, exactly a ResNet slot -- and keeps the default of 512.
         A MobileNetV2 slot holds 15.3 MB -- three 112x112x96 split-fp16 activation buffers (features.2's expanded map, 1.5x a ResNet
         buffer: 14.5 MB) and the input staging -- and keeps the default of 512 (7.8 GB).
+        A SqueezeNet 1.1 slot holds 10.3 MB -- three 111x111x64 split-fp16 activation buffers (a Fire module's input, its squeeze map and
+        the concatenation: 9.5 MB) and the input staging -- and keeps the default of 512 (5.3 GB).
         stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
@@ -117,7 +120,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets and MobileNetV2 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2 and SqueezeNet 1.1 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if max_batch is None:
             if arch.startswith("vgg"):
                 raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
@@ -170,8 +173,8 @@ class MaskedForwardEngine:
     @property
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
-        which keeps no table), MobileNetV2 and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet"))
+        which keeps no table), MobileNetV2, SqueezeNet 1.1 and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -217,7 +220,7 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's depthwise layers load with the

@@ -224,9 +224,47 @@ def make_mobilenetv2_state_dict(seed=7):
     return sd
 
 
+# torchvision squeezenet.py, version 1_1: (index N of features.N, input channels, squeeze planes s, expand planes e of each branch)
+SQUEEZENET_FIRES = ((3, 64, 16, 64), (4, 128, 16, 64), (6, 128, 32, 128), (7, 256, 32, 128), (9, 256, 48, 192), (10, 384, 48, 192),
+                    (11, 384, 64, 256), (12, 512, 64, 256))
+
+
+# The synthetic SqueezeNet draws from torch generator seed SQUEEZENET_SEED_OFFSET + seed.  The draws are plain He-normal, so how peaked the
+# softmax is depends on the draw: generator seeds 0 .. 79 were surveyed on the rows tests/squeezenet_ref.E2E_CASES scores (unmasked softmax
+# peak from 0.004 to 0.74), and 79 is the only one of them on which EVERY masked row -- the heavily masked felzenszwalb rows of the `blobs`
+# picture included -- has a softmax peak in [0.05, 0.95] and an fp64 top-two logit gap >= 1e-3 (peaks 0.10 .. 0.77, gaps >= 0.76; generator
+# seed 7 gives peaks down to 0.013 on those rows; 31 and 56 come to 0.044 and 0.049).  The offset puts the seed every caller uses by default
+# (make_state_dict's 7, which the test suite's cache passes on explicitly) on that draw.  tests/test_squeezenet_cpu.py asserts the condition.
+SQUEEZENET_SEED_OFFSET = 72
+
+
+def make_squeezenet_state_dict(seed=7):
+    """OrderedDict with the key set, order and shapes of torchvision's squeezenet1_1 (models.squeezenet1_1().state_dict(): features.0.weight /
+    .bias, features.N.{squeeze, expand1x1, expand3x3}.weight / .bias for the eight Fire modules, classifier.1.weight / .bias: 52 tensors, no
+    BatchNorm).  Draws: every conv He-normal N(0, sqrt(2 / (k * k * cin))) with a bias N(0, 0.05), classifier.1 included -- its ReLU and the
+    mean over the 13 x 13 map leave logits whose softmax is peaked but unsaturated at the default seed (SQUEEZENET_SEED_OFFSET above;
+    tests/test_squeezenet_cpu.py asserts the bounds)."""
+    g = torch.Generator().manual_seed(SQUEEZENET_SEED_OFFSET + seed)
+    sd = OrderedDict()
+
+    def conv(name, cin, cout, k):
+        _conv(sd, name, cin, cout, k, g)
+        sd[name + ".bias"] = torch.randn(cout, generator=g) * 0.05
+
+    conv("features.0", 3, 64, 3)
+    for n, cin, s, e in SQUEEZENET_FIRES:
+        conv("features.%d.squeeze" % n, cin, s, 1)
+        conv("features.%d.expand1x1" % n, s, e, 1)
+        conv("features.%d.expand3x3" % n, s, e, 3)
+    conv("classifier.1", 512, 1000, 1)
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
-    DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict) key set."""
+    DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict) key set."""
+    if arch == "squeezenet1_1":
+        return make_squeezenet_state_dict(seed)
     if arch == "mobilenet_v2":
         return make_mobilenetv2_state_dict(seed)
     if vgg_arch(arch):

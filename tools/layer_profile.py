@@ -175,6 +175,50 @@ if eng.dwconvs:   # MobileNetV2: the depthwise 3x3 + BN + ReLU6 launches between
     print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise %.1f %%, staging (K0) %.1f %%, global pool %.1f %%, head %.1f %%"
           % (100 * tot / allms, 100 * tot_dw / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms,
              100 * prof["ms"]["head"] / reps / allms))
+if arch.startswith("squeezenet"):     # SqueezeNet: the Fire modules' convs by their bytes (they are memory-bound), and the average pool that writes the logits
+    import ctypes as C
+    print("-- Fire modules: split-fp16 bytes read (the input map once) + written per launch; the expand convs write their half of the concatenation --")
+    tot_bytes = {"squeeze": 0.0, "expand1x1": 0.0, "expand3x3": 0.0}
+    tot_ms = dict.fromkeys(tot_bytes, 0.0)
+    for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
+        kind = d.name.decode().rsplit(".", 1)[-1]
+        if kind not in tot_bytes:
+            continue
+        ms /= reps
+        pitch, off = C.c_int(), C.c_int()
+        eng._lib.mpx_conv_out_slice(eng._h, li, C.byref(pitch), C.byref(off))
+        cin_p = -(-d.cin // 32) * 32
+        nbytes = batch * 4.0 * d.hout * d.hout * (cin_p + (d.cout if kind != "squeeze" else pitch.value))
+        tot_bytes[kind] += nbytes
+        tot_ms[kind] += ms
+        print("%-22s %4d->%-4d k%d %3dx%-3d pitch %4d offset %3d tile %d %8.3f ms %8.1f MB %6.2f TB/s %7.1f TFLOP/s" % (
+            d.name.decode(), d.cin, d.cout, d.ksize, d.hout, d.hout, pitch.value, off.value, eng.conv_tile(li), ms, nbytes / 1e6,
+            nbytes / max(ms, 1e-9) / 1e9, conv_flops(d) / max(ms, 1e-9) / 1e9))
+    for kind in tot_bytes:
+        print("%-10s total %8.3f ms/batch %9.1f MB -> %5.2f TB/s" % (kind, tot_ms[kind], tot_bytes[kind] / 1e6, tot_bytes[kind] / max(tot_ms[kind], 1e-9) / 1e9))
+    # the average pool (mpx_global_avgpool_logits) shares the profile's 'pool' kind with the three max pools: timed here as a launch of its own
+    # over planes of classifier.1's shape, through the same event pairs
+    hw, c = eng.layers[-1].hout ** 2, eng.layers[-1].cout
+    ph = torch.rand(batch, hw, c, device=dev).half()
+    pl = (torch.rand(batch, hw, c, device=dev) * 1e-3).half()
+    lg = torch.empty(batch, c, dtype=torch.float32, device=dev)
+    args = (eng._h, C.c_void_p(ph.data_ptr()), C.c_void_p(pl.data_ptr()), C.c_void_p(lg.data_ptr()), batch, hw, c, c, eng._stream())
+    eng._lib.mpx_global_avgpool_logits(*args)
+    torch.cuda.synchronize()
+    eng.profile(True)
+    for _ in range(reps):
+        eng._lib.mpx_global_avgpool_logits(*args)
+    eng.profile(False)
+    avg_ms = eng.collect_profile()["ms"]["pool"] / reps
+    nbytes = batch * 4.0 * (hw * c + c)
+    pool_ms = prof["ms"]["pool"] / reps
+    allms = sum(prof["ms"].values()) / reps
+    print("average pool -> logits (mpx_global_avgpool_logits, one launch) %3dx%-3d C %d: %8.3f ms %8.1f MB %6.2f TB/s; the four pool launches in the network %.3f ms/batch"
+          % (eng.layers[-1].hout, eng.layers[-1].hout, c, avg_ms, nbytes / 1e6, nbytes / max(avg_ms, 1e-9) / 1e9, pool_ms))
+    print("share of the forward by op class: conv (MFMA) %.1f %%, staging (K0) %.1f %%, pools %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
+          % (100 * tot / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms, 100 * prof["ms"]["head"] / reps / allms, allms,
+             sum(prof["launches"].values()) // reps - 1))
+    del ph, pl, lg
 tails = eng.bottleneck_tails()
 if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_MASK", "3") == "3":
     names = [d.name.decode() for d in eng.layers]

@@ -109,6 +109,25 @@ enum {
  * Squeeze widths 16 and 48 are stored with a pitch of 32 and 64 (zero weight columns, zero scale and shift on the padded rows: exact zeros).
  * Three activation buffers of 111 * 111 * 64 elements per image (a module's input, its squeeze map, the concatenation): 10.3 MB per slot with
  * the staging.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
+ * -- or torchvision's GoogLeNet (aux_logits off, eval mode; 6.6 M parameters, 1.5 GMAC per forward):
+ *   MPX_ARCH_GOOGLENET            googlenet; every other id in [8000, 9000) is MPX_E_ARG
+ * A GoogLeNet engine runs conv1 (3 -> 64, 7x7 stride 2 pad 3, 224 -> 112: the ResNet stem's shape, as a launch of its own), maxpool1, conv2
+ * (1x1 64 -> 64), conv3 (3x3 pad 1 64 -> 192), maxpool2, inception3a / 3b, maxpool3, inception4a .. 4e, maxpool4 (2x2 stride 2, exact:
+ * mpx_maxpool2x2s2), inception5a / 5b, mpx_global_avgpool and fc 1024 -> 1000, the logit layer and last conv entry as on a ResNet.  Every
+ * conv is BasicConv2d = Conv2d(bias=False) + BatchNorm2d(eps = 0.001) + ReLU: names "<module>.conv", bn names "<module>.bn" ("conv1.conv",
+ * "inception3a.branch2.1.conv"); the caller passes eps = 1e-3.  58 entries in the conv list: conv1, conv2, conv3, six per Inception module
+ * (branch1, branch2.0, branch2.1, branch3.0, branch3.1, branch4.1), fc.
+ * THE POOLS.  maxpool1 / 2 / 3 are MaxPool2d(3, 2, ceil_mode=True) on 112 -> 56 -> 28 -> 14: hin - 3 is odd, the last window hangs over the
+ * edge; every Inception module's branch4 starts with MaxPool2d(3, 1, 1, ceil_mode=True).  All twelve run mpx_maxpool3x3_clip.
+ * THE CONCATENATION IS THE BRANCHES' EPILOGUE, as SqueezeNet's: branch1, branch2.1, branch3.1 and branch4.1 write channels [0, c1), [c1, c1 +
+ * c3), [c1 + c3, c1 + c3 + c5) and [c1 + c3 + c5, out) of one buffer (mpx_conv_out_slice); such OUTPUT-SLICE layers run the generic tiles
+ * 0, 1, 2, 4 and 7 only and take no residual operand.
+ * Reduce widths 16, 24, 48, 112 and 144 are stored with a pitch of 32, 32, 64, 128 and 160 (exact zeros in the padded channels).
+ * inception4d's 528-channel concatenation is stored with a pitch of 544 and its branch4.1 (64 channels at offset 464) stores 80 channels, so
+ * channels 528 .. 543 are written as exact zeros by every forward; inception4e's 1x1 convs and its pool read that pitch.
+ * Three activation buffers of 112 * 112 * 64 elements per image (the stem's output): 10.5 MB per slot with the staging.  It stages through
+ * mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.  torchvision's transform_input (on in its
+ * pretrained googlenet) is NOT applied: the caller's normalisation is the network's input.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -120,6 +139,7 @@ enum {
 #define MPX_ARCH_DENSENET 5000
 #define MPX_ARCH_MOBILENET 6000
 #define MPX_ARCH_SQUEEZENET 7000
+#define MPX_ARCH_GOOGLENET 8000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -145,7 +165,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2 and SqueezeNet 1.1, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1 and GoogLeNet, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -157,8 +177,11 @@ int mpx_num_convs(const mpx_engine* h);
 int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
 /* Where layer i writes: *pitch = channels between adjacent pixels of its output planes, *offset = its first channel within a pixel.  An
  * ordinary layer fills whole pixel rows: its stored channel count (cout, or cout rounded up to 32 where the network pads) and 0.  A
- * SqueezeNet expand conv writes half of its Fire module's concatenation: 2 * cout and 0 (expand1x1) or cout (expand3x3).  mpx_conv_desc keeps
- * its layout. */
+ * SqueezeNet expand conv writes half of its Fire module's concatenation: 2 * cout and 0 (expand1x1) or cout (expand3x3).  A GoogLeNet branch's
+ * last conv writes its range of the Inception module's concatenation: the concatenation's width rounded up to 32 (544 for inception4d's 528)
+ * and 0 (branch1), c1 (branch2.1), c1 + c3 (branch3.1) or c1 + c3 + c5 (branch4.1).  In general a slice is any pitch, offset and stored
+ * width that are multiples of 8 with offset + stored width <= pitch; the stored width is cout, except where the last slice also writes the
+ * concatenation's pad channels as zeros (inception4d.branch4.1: cout 64, 80 stored).  mpx_conv_desc keeps its layout. */
 int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
@@ -323,8 +346,9 @@ int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
  * For the last entry ("fc") out_hi/out_lo are ignored and out_f32 (DEV f32[B][1000]) is written;
  * for every other layer out_f32 must be NULL (a SqueezeNet engine has no such entry: its last conv, classifier.1, writes planes
  * [B][13][13][1000] and out_f32 must be NULL there too).
- * An output-slice layer (a SqueezeNet expand conv, mpx_conv_out_slice): out_hi|lo is the BASE of the concatenated planes
- * [B][h][w][pitch]; the layer writes channels [offset, offset + cout) of every pixel and nothing else; res_* must be NULL. */
+ * An output-slice layer (a SqueezeNet expand conv, the last conv of a GoogLeNet branch; mpx_conv_out_slice): out_hi|lo is the BASE of the
+ * concatenated planes [B][h][w][pitch]; the layer writes channels [offset, offset + cout) of every pixel (inception4d.branch4.1: 16 zero
+ * channels more, up to the pitch) and nothing else; res_* must be NULL. */
 int mpx_conv_bn_act(mpx_engine* h, int i, const void* in_hi, const void* in_lo,
                     const void* res_hi, const void* res_lo, void* out_hi, void* out_lo,
                     float* out_f32, int B, void* stream);
@@ -388,6 +412,23 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
  * order on a tie.  MPX_E_ARG for hin < 3, an even hin (floor mode is not part of the contract) and c not a multiple of 8. */
 int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                        void* out_lo, int B, int hin, int c, void* stream);
+
+/* ---- GoogLeNet: 3x3 max pool with ceil-mode size, windows clipped at the map's edge --------------------------
+ * replaces: `nn.MaxPool2d(3, stride=2, ceil_mode=True)` (maxpool1 / 2 / 3) and `nn.MaxPool2d(3, stride=1, padding=1, ceil_mode=True)`
+ *           (branch4.0 of every Inception module) of torchvision's googlenet.py inside model(masked_img_tensor)
+ *           (generate_gp_training_data_imagenet.py:246).
+ * in: DEV split planes [B][hin][hin][pitch]; out: [B][ho][ho][pitch] with ho = ceil((hin + 2 * pad - 3) / stride) + 1, minus one if the
+ * last window would start at or beyond hin + pad (PyTorch's rule).  stride 1 or 2, pad 0 or 1, pitch a multiple of 8 (all of a pixel's
+ * pitch is pooled, pad channels included).  Taps outside the map are left out, never read as zero.  Bit-exact for any sign: each output
+ * (hi, lo) is the pair of a window element with the largest hi + lo, so the merged output equals F.max_pool2d(merged, 3, stride, pad, 1,
+ * ceil_mode=True).  in and out must not overlap.  MPX_E_ARG for any other stride or pad, hin + 2 * pad < 3, a pitch that is not a
+ * multiple of 8, B <= 0, a null pointer or planes that are not 16-byte aligned.  ONE launch. */
+int mpx_maxpool3x3_clip(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int stride, int pad,
+                        int pitch, void* stream);
+/* The clipped pools of a GoogLeNet engine's forward, in order (12; 0 for every other engine), and pool k's map side, stride, pad and pitch
+ * (any pointer may be NULL). */
+int mpx_num_clip_pools(const mpx_engine* h);
+int mpx_clip_pool_info(const mpx_engine* h, int k, int* hin, int* stride, int* pad, int* pitch);
 
 /* ---- DenseNet: concat-append + BatchNorm + ReLU on split planes ---------------------------------------------
  * replaces: `torch.cat(features, 1)` of a dense block (torchvision densenet.py _DenseBlock.forward / _DenseLayer.bn_function) for ONE new
@@ -509,6 +550,10 @@ int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launch
  * layer. */
 int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms);
+/* The same with GoogLeNet's split of kind 2: per_clip_pool_ms (HOST f64[mpx_num_clip_pools], may be NULL) gets every clipped max pool
+ * launch of the forward. */
+int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                             double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms);
 /* Algorithmic FLOPs (2*MAC, convs + depthwise convs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 

@@ -106,6 +106,12 @@ SIGNATURES = {
     # SqueezeNet 1.1: where a conv writes (the expand convs fill halves of one concatenation), the average pool that writes the logits
     "mpx_conv_out_slice": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mpx_global_avgpool_logits": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # GoogLeNet: the clipped-window 3x3 max pool, the pools of the forward, their launches in the profile
+    "mpx_maxpool3x3_clip": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mpx_num_clip_pools": (_i, [_vp]),
+    "mpx_clip_pool_info": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mpx_profile_collect_pool": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@
 #include "mpx_stemtab.h"
 #include "mpx_dw.h"
 #include "mpx_fire.h"
+#include "mpx_pool3c.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,7 +40,7 @@ constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: 
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
-              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12 };
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -54,9 +55,11 @@ struct ConvLayer {
     bool has_bias = false;  // the reference module is nn.Conv2d(bias=True) (small nets): state_dict has <name>.bias
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
     int cout_store = 0;     // channels per pixel of the output planes (row pitch and store bound)
-    // output slice (a SqueezeNet expand conv: half of its Fire module's concatenation): the layer writes channels [y_offset, y_offset +
-    // cout_store) of planes whose pixels are y_pitch channels apart, on the SLICE form of the generic kernel (mpx_conv.h).  y_pitch = 0: an
-    // ordinary layer, which fills whole pixel rows of cout_store channels.
+    // output slice (a SqueezeNet expand conv: half of its Fire module's concatenation; a GoogLeNet branch's last conv: one of the four ranges of
+    // its Inception module's): the layer writes channels [y_offset, y_offset + cout_store) of planes whose pixels are y_pitch channels apart, on
+    // the SLICE form of the generic kernel (mpx_conv.h).  Any (y_pitch, y_offset, cout_store) that are multiples of 8 with y_offset + cout_store
+    // <= y_pitch; cout_store may exceed cout (rows of zero weights, scale and shift: exact zeros), which is how inception4d's 528-channel
+    // concatenation gets its 16 pad channels written.  y_pitch = 0: an ordinary layer, which fills whole pixel rows of cout_store channels.
     int y_pitch = 0;
     int y_offset = 0;
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
@@ -114,13 +117,19 @@ struct DwLayer {
 };
 
 constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
+constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max pool k (mpx_engine::pools3c) kProfSubPool3c - k
+
+// A clipped-window 3x3 max pool of the op list (GoogLeNet; mpx_pool3c.h)
+struct ClipPool {
+    int hin, stride, pad, pitch;
+};
 
 struct ProfRec {
     hipEvent_t t0, t1;
     int kind;
     int conv;
     int sub;        // kind 2: -1 = any pool, -2 = a DenseNet transition's average pool, k >= 0 = the launch of DenseNet norm k,
-                    // kProfSubDw - k = MobileNetV2's depthwise layer k
+                    // kProfSubDw - k = MobileNetV2's depthwise layer k, kProfSubPool3c - k = GoogLeNet's clipped max pool k
 };
 
 }  // namespace
@@ -139,6 +148,8 @@ struct mpx_engine {
     bool mobilenet = false;         // torchvision MobileNetV2: inverted residuals over three activation buffers, staged through K0 only
     std::vector<DwLayer> dws;       // its depthwise layers in forward order
     bool squeezenet = false;        // torchvision SqueezeNet 1.1: Fire modules over three activation buffers, staged through K0 only
+    bool googlenet = false;         // torchvision GoogLeNet: Inception modules over three activation buffers, staged through K0 only
+    std::vector<ClipPool> pools3c;  // its clipped-window 3x3 max pools in forward order
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -237,6 +248,7 @@ int build_topology_alexnet(mpx_engine* h);
 int build_topology_densenet(mpx_engine* h);
 int build_topology_mobilenet(mpx_engine* h);
 int build_topology_squeezenet(mpx_engine* h);
+int build_topology_googlenet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -246,6 +258,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_DENSENET && h->arch < MPX_ARCH_DENSENET + 1000) return build_topology_densenet(h);
     if (h->arch >= MPX_ARCH_MOBILENET && h->arch < MPX_ARCH_MOBILENET + 1000) return build_topology_mobilenet(h);
     if (h->arch >= MPX_ARCH_SQUEEZENET && h->arch < MPX_ARCH_SQUEEZENET + 1000) return build_topology_squeezenet(h);
+    if (h->arch >= MPX_ARCH_GOOGLENET && h->arch < MPX_ARCH_GOOGLENET + 1000) return build_topology_googlenet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -944,6 +957,138 @@ int build_topology_squeezenet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision GoogLeNet (googlenet.py, aux_logits off, eval mode): conv1 7x7/2 pad 3 (3 -> 64, 224 -> 112: the ResNet stem's shape, run as a
+// launch of its own -- the pool behind it is not the ResNets') | maxpool1 3/2 ceil 112 -> 56 | conv2 1x1 64 -> 64 | conv3 3x3 pad 1 64 -> 192 |
+// maxpool2 3/2 ceil 56 -> 28 | inception3a, 3b | maxpool3 3/2 ceil 28 -> 14 | inception4a .. 4e | maxpool4 2x2/2 ceil 14 -> 7 (exact: the VGG
+// pool) | inception5a, 5b | global average pool | fc 1024 -> 1000.  Every conv is BasicConv2d = Conv2d(bias=False) + BatchNorm2d(eps 0.001) + ReLU.
+// Inception(in, c1, r3, c3, r5, c5, pp) concatenates branch1 (1x1 in -> c1), branch2 (1x1 in -> r3, 3x3 pad 1 r3 -> c3), branch3 (1x1 in -> r5,
+// 3x3 pad 1 r5 -> c5: torchvision's 3x3 where the paper has 5x5) and branch4 (MaxPool2d(3, 1, 1, ceil_mode=True), 1x1 in -> pp).
+// Op list, 73 launches: 57 OP_CONV (the stem, conv2, conv3, six per module, fc), 12 OP_MAXPOOL3C (mpx_pool3c.h: the three stride-2 ceil-mode
+// pools, whose last window hangs over the edge -- 112 - 3, 56 - 3 and 28 - 3 are odd --, and the nine stride-1 pad-1 pools), OP_MAXPOOL2,
+// OP_AVGPOOL, OP_HEAD.
+// THE CONCATENATION IS THE BRANCHES' EPILOGUE: branch1, branch2.1, branch3.1 and branch4.1 write channels [0, c1), [c1, c1 + c3), [c1 + c3,
+// c1 + c3 + c5) and [c1 + c3 + c5, out) of one buffer (y_pitch / y_offset: the SLICE form of the generic kernel); nothing is copied.  Every
+// offset is a multiple of 8.
+// Channels: the reduce widths 16, 24, 48, 112 and 144 are stored with pitch 32, 32, 64, 128 and 160 (zero weight columns in the 3x3 conv that
+// reads them, zero scale and shift on the padded rows: exact zeros).  inception4d's concatenation is 528 wide and feeds K = 528, not a
+// multiple of the 32-wide K step: it is stored with pitch 544, and its last slice (branch4.1, 64 channels at offset 464) stores 80 -- rows
+// 64 .. 79 of its weights, scale and shift are zero, so channels 528 .. 543 are WRITTEN as exact zeros by every forward.  inception4e's three
+// 1x1 convs on the module input (cin_pad 544), its pool (pitch 544: the max of zeros is zero) and branch4.1 behind the pool (cin_pad 544)
+// all read that pitch.
+// Buffers: three of 112 * 112 * 64 elements per image (the stem's output; conv3's 56 * 56 * 192 and every concatenation are smaller): X the
+// module input, T what one branch keeps between its two launches (the reduce map, the pooled input), Y the concatenation, the next X.
+int build_topology_googlenet(mpx_engine* h) {
+    if (h->arch != MPX_ARCH_GOOGLENET) return MPX_E_ARG;
+    h->googlenet = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kActElemsPerImage;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    // y_pitch = 0: an ordinary layer (output pitch = cout rounded up to 32); else a slice of y_pitch-wide planes that stores `store` channels
+    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int pad, int hin, int y_pitch, int y_offset, int store) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name + ".conv");
+        set_name(L.d.bn_name, name + ".bn");
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = 1;
+        L.is_stem = (cin == 3);
+        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
+        L.cout_store = y_pitch ? store : pitch_of(cout);
+        L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(std::max(cout, L.cout_store), 128);
+        L.tile = default_tile(L.d);
+        if (y_pitch) {
+            L.y_pitch = y_pitch;
+            L.y_offset = y_offset;
+            // default_tile judges the descriptor alone and may hand out kernels that know no output pitch: its rules restricted to the generic
+            // tiles, as build_topology_squeezenet (64-row tiles for cout <= 64, tile 0 for 3x3, tile 7 for the expanding 1x1 layers, tile 2 for
+            // the reducing ones)
+            L.tile = L.tile_default = cout <= 64 ? (k >= 3 ? 1 : 4) : (k == 3 ? 0 : (cout > cin ? 7 : 2));
+        }
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
+    // a clipped 3x3 max pool over planes of `pitch` channels per pixel; returns the output side
+    auto pool_op = [&](int in, int out, int hin, int stride, int pad, int pitch) {
+        h->pools3c.push_back(ClipPool{hin, stride, pad, pitch});
+        h->ops.push_back(Op{OP_MAXPOOL3C, (int)h->pools3c.size() - 1, in, out, BUF_NONE, hin, pitch, BUF_NONE});
+        return pool3c_out_side(hin, stride, pad);
+    };
+    int c = add_conv("conv1", 3, 64, 7, 2, 3, MPX_IMG, 0, 0, 0);
+    conv_op(c, BUF_INPUT, 0);
+    int hcur = pool_op(0, 1, 112, 2, 0, 64);                    // maxpool1: 112 -> 56
+    c = add_conv("conv2", 64, 64, 1, 1, 0, hcur, 0, 0, 0);
+    conv_op(c, 1, 2);
+    c = add_conv("conv3", 64, 192, 3, 1, 1, hcur, 0, 0, 0);
+    conv_op(c, 2, 0);
+    int X = 1;
+    hcur = pool_op(0, X, hcur, 2, 0, 192);                      // maxpool2: 56 -> 28
+    if (hcur != 28) return MPX_E_INTERNAL;
+    struct Mod { const char* name; int cin, c1, r3, c3, r5, c5, pp; };
+    static const Mod mods[9] = {{"inception3a", 192, 64, 96, 128, 16, 32, 32},   {"inception3b", 256, 128, 128, 192, 32, 96, 64},
+                                {"inception4a", 480, 192, 96, 208, 16, 48, 64},  {"inception4b", 512, 160, 112, 224, 24, 64, 64},
+                                {"inception4c", 512, 128, 128, 256, 24, 64, 64}, {"inception4d", 512, 112, 144, 288, 32, 64, 64},
+                                {"inception4e", 528, 256, 160, 320, 32, 128, 128}, {"inception5a", 832, 256, 160, 320, 32, 128, 128},
+                                {"inception5b", 832, 384, 192, 384, 48, 128, 128}};
+    int cin = 192;
+    for (int m = 0; m < 9; ++m) {
+        const Mod& M = mods[m];
+        if (M.cin != cin) return MPX_E_INTERNAL;
+        if (m == 2 || m == 7) {
+            const int O = (X + 1) % 3;
+            if (m == 2) {
+                hcur = pool_op(X, O, hcur, 2, 0, pitch_of(cin));    // maxpool3: 28 -> 14
+            } else {
+                h->ops.push_back(Op{OP_MAXPOOL2, -1, X, O, BUF_NONE, hcur, pitch_of(cin), BUF_NONE});   // maxpool4: 14 -> 7, every window inside the map
+                hcur /= 2;
+            }
+            X = O;
+        }
+        const int T = (X + 1) % 3, Y = (X + 2) % 3;
+        const int out = M.c1 + M.c3 + M.c5 + M.pp, P = pitch_of(out), Pin = pitch_of(cin);
+        if ((size_t)hcur * hcur * std::max(P, Pin) > kActElemsPerImage || (M.c1 | M.c3 | M.c5 | M.pp) & 7) return MPX_E_INTERNAL;
+        const std::string p = std::string(M.name) + ".";
+        c = add_conv(p + "branch1", cin, M.c1, 1, 1, 0, hcur, P, 0, M.c1);
+        conv_op(c, X, Y);
+        c = add_conv(p + "branch2.0", cin, M.r3, 1, 1, 0, hcur, 0, 0, 0);
+        conv_op(c, X, T);
+        c = add_conv(p + "branch2.1", M.r3, M.c3, 3, 1, 1, hcur, P, M.c1, M.c3);
+        conv_op(c, T, Y);
+        c = add_conv(p + "branch3.0", cin, M.r5, 1, 1, 0, hcur, 0, 0, 0);
+        conv_op(c, X, T);
+        c = add_conv(p + "branch3.1", M.r5, M.c5, 3, 1, 1, hcur, P, M.c1 + M.c3, M.c5);
+        conv_op(c, T, Y);
+        if (pool_op(X, T, hcur, 1, 1, Pin) != hcur) return MPX_E_INTERNAL;
+        // the last slice also writes the concatenation's pad channels [out, P), as zeros (inception4d: 64 -> 80)
+        c = add_conv(p + "branch4.1", cin, M.pp, 1, 1, 0, hcur, P, M.c1 + M.c3 + M.c5, M.pp + P - out);
+        conv_op(c, T, Y);
+        X = Y;
+        cin = out;
+    }
+    if (cin != 1024 || hcur != 7) return MPX_E_INTERNAL;
+    h->feat = cin;
+    h->ops.push_back(Op{OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
+    {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, "fc");
+        L.d.cin = cin; L.d.cout = MPX_NUM_CLASSES; L.d.ksize = 1; L.d.stride = 1; L.d.hin = 1; L.d.hout = 1;
+        L.is_fc = true;
+        L.has_bias = true;
+        L.cin_pad = cin;
+        L.cout_store = MPX_NUM_CLASSES;
+        L.d.k_packed = cin;
+        L.d.cout_pad = (int)round_up(MPX_NUM_CLASSES, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        conv_op((int)h->convs.size() - 1, BUF_POOL, BUF_NONE);
+    }
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -1431,7 +1576,7 @@ int launch_conv_fused(mpx_engine* h, int i, const half_t* in_hi, const half_t* i
 // The ImageNet stem (7x7 stride-2 conv + BN + ReLU) with its 3x3 stride-2 pad-1 max pool in ONE launch (mpx_conv.h, POOL): writes the
 // pooled planes [B][56][56][64]; the 112x112 conv output is never stored.  Needs the 64-row tile 1 (the stem's default).
 bool stem_pool_eligible(const mpx_engine* h) {
-    if (h->small || h->convs.empty()) return false;
+    if (h->small || h->googlenet || h->convs.empty()) return false;     // (GoogLeNet's stem has the shape, but a ceil-mode unpadded pool behind it)
     const ConvLayer& L = h->convs[0];
     return L.is_stem && L.d.cout == 64 && L.d.hout == 112 && (L.d.hout / 2) % POOL_PY == 0 && (L.d.hout / 2) % POOL_PX == 0 && L.d.relu;
 }
@@ -1612,6 +1757,27 @@ int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st) {
     // as launch_catnorm: about 8 workgroups per CU, striding over the rest
     const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
     hipLaunchKernelGGL(dwconv3x3_bn_relu6_kernel, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one maxpool3x3_clip_kernel launch over B images; `k` = the engine's clipped pool it runs for (profile record), -1 from the stand-alone entry
+int launch_pool3c(mpx_engine* h, const half_t* in_hi, const half_t* in_lo, half_t* out_hi, half_t* out_lo, int B, int hin, int stride, int pad,
+                  int pitch, int k, hipStream_t st) {
+    Pool3cParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = in_hi; p.x_lo = in_lo; p.y_hi = out_hi; p.y_lo = out_lo;
+    p.hin = hin; p.ho = pool3c_out_side(hin, stride, pad); p.pitch = pitch; p.pad = pad;
+    p.runs = (p.ho + (stride == 1 ? Pool3c<1>::W : Pool3c<2>::W) - 1) / (stride == 1 ? Pool3c<1>::W : Pool3c<2>::W);
+    p.units = (long long)B * p.ho * p.runs * (pitch / 8);
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubPool3c - k : -1);
+    // a thread keeps the 18 (stride 1) or 15 (stride 2) loads per plane of its run in flight, so two workgroups per CU already cover the
+    // latency; the grid strides over the rest
+    const unsigned grid = (unsigned)std::min<long long>((p.units + 255) / 256, (long long)h->num_cus * 2);
+    if (stride == 1)
+        hipLaunchKernelGGL(maxpool3x3_clip_kernel<1>, dim3(grid), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(maxpool3x3_clip_kernel<2>, dim3(grid), dim3(256), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -1990,7 +2156,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet ? " (VGG, AlexNet, MobileNetV2 and SqueezeNet stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet and GoogLeNet stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -2186,6 +2352,31 @@ int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void
     hipLaunchKernelGGL(maxpool3x3s2p0_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
                        (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
     MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_maxpool3x3_clip(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int stride, int pad,
+                        int pitch, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (stride != 1 && stride != 2) || (pad != 0 && pad != 1) || pitch <= 0 ||
+        (pitch & 7) || pool3c_out_side(hin, stride, pad) <= 0)
+        return fail(h, MPX_E_ARG, "maxpool3x3_clip: bad arguments (stride 1 or 2, pad 0 or 1, hin + 2 * pad >= 3, pitch a multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "maxpool3x3_clip: the planes must be 16-byte aligned");
+    MPX_SET_DEVICE(h);
+    return launch_pool3c(h, (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, stride, pad, pitch, -1,
+                         as_stream(stream));
+}
+
+int mpx_num_clip_pools(const mpx_engine* h) { return h ? (int)h->pools3c.size() : MPX_E_ARG; }
+
+int mpx_clip_pool_info(const mpx_engine* h, int k, int* hin, int* stride, int* pad, int* pitch) {
+    if (!h || k < 0 || k >= (int)h->pools3c.size()) return MPX_E_ARG;
+    const ClipPool& P = h->pools3c[k];
+    if (hin) *hin = P.hin;
+    if (stride) *stride = P.stride;
+    if (pad) *pad = P.pad;
+    if (pitch) *pitch = P.pitch;
     return 0;
 }
 
@@ -2439,6 +2630,11 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_AVGPOOL2: rc = mpx_avgpool2x2s2(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin, o.c, stream); break;
             case OP_AVGPOOL6: rc = mpx_global_avgpool_clamp6(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
             case OP_AVGLOGITS: rc = mpx_global_avgpool_logits(h, hi(o.in), lo(o.in), logits, B, o.hin * o.hin, o.c, h->logit_pitch, stream); break;
+            case OP_MAXPOOL3C: {
+                const ClipPool& P = h->pools3c[o.conv];
+                rc = launch_pool3c(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, P.hin, P.stride, P.pad, P.pitch, o.conv, as_stream(stream));
+                break;
+            }
             case OP_DWCONV: {
                 const DwLayer& D = h->dws[o.conv];
                 DwParams p;
@@ -2602,6 +2798,11 @@ int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launch
 
 int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms) {
+    return mpx_profile_collect_pool(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, nullptr);
+}
+
+int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                             double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -2616,6 +2817,8 @@ int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launch
         if (per_norm_ms && r.kind == 2 && r.sub >= 0 && r.sub < (int)h->norms.size()) per_norm_ms[r.sub] += ms;
         if (avgpool2_ms && r.kind == 2 && r.sub == -2) *avgpool2_ms += ms;
         if (per_dw_ms && r.kind == 2 && r.sub <= kProfSubDw && kProfSubDw - r.sub < (int)h->dws.size()) per_dw_ms[kProfSubDw - r.sub] += ms;
+        if (per_clip_pool_ms && r.kind == 2 && r.sub <= kProfSubPool3c && kProfSubPool3c - r.sub < (int)h->pools3c.size())
+            per_clip_pool_ms[kProfSubPool3c - r.sub] += ms;
     }
     h->prof_used = 0;
     return 0;

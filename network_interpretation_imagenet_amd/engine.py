@@ -20,6 +20,7 @@ from ._lib import MpxError, IMG, NUM_CLASSES
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 BN_EPS = 1e-5   # torchvision BatchNorm2d default
+GOOGLENET_BN_EPS = 1e-3     # torchvision googlenet.py: BasicConv2d = Conv2d(bias=False) + BatchNorm2d(eps=0.001) + ReLU
 
 ARCH_IDS = {"resnet18": 18, "resnet34": 34, "resnet50": 50, "resnet101": 101, "resnet152": 152,
             # the reference's two small networks (include/mpx.h MPX_ARCH_*)
@@ -31,6 +32,7 @@ ARCH_IDS["alexnet"] = 4000      # torchvision's AlexNet (MPX_ARCH_ALEXNET), the 
 ARCH_IDS.update({"densenet%d" % d: 5000 + d for d in (121, 169, 201)})
 ARCH_IDS["mobilenet_v2"] = 6002   # torchvision's MobileNetV2, width 1.0 (MPX_ARCH_MOBILENET + 2)
 ARCH_IDS["squeezenet1_1"] = 7011  # torchvision's SqueezeNet 1.1 (MPX_ARCH_SQUEEZENET + 11); squeezenet1_0 is not served
+ARCH_IDS["googlenet"] = 8000      # torchvision's GoogLeNet without the aux classifiers (MPX_ARCH_GOOGLENET); inception_v3 is not served
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -58,6 +60,11 @@ def whole_round_batch(limit, num_cus=None):
     if (rounds + 1) * per_round // 196 <= int(limit):       # the last tile of a batch may be partial: 2340 images are 1791.6 -> 1792 tiles
         rounds += 1
     return rounds * per_round // 196 if rounds >= 1 else int(limit)
+
+
+def default_bn_eps(arch):
+    """The epsilon of torchvision's BatchNorm layers in `arch`: BatchNorm2d's default 1e-5, except GoogLeNet's BasicConv2d (1e-3)."""
+    return GOOGLENET_BN_EPS if arch == "googlenet" else BN_EPS
 
 
 class BasePredictionWrong(Exception):
@@ -102,7 +109,7 @@ def rank_segments(segments):
 class MaskedForwardEngine:
     """One engine per process per GPU (one RCCL rank).  `arch` is the reference's `-a/--arch`."""
 
-    def __init__(self, arch="resnet101", max_batch=None, device=None, stem=None):
+    def __init__(self, arch="resnet101", max_batch=None, device=None, stem=None, transform_input=False):
         """max_batch: slots of the workspace (masked images per forward); None = 512 for the ResNets and the small networks.  A VGG
         engine has no default: a VGG slot holds 26.5 MB (two 224x224x64 split-fp16 activation planes and the input staging, 1.8x a
         ResNet slot), so its caller sizes it -- MaskedForwardEngine("vgg16") raises ValueError, MaskedForwardEngine("vgg16",
@@ -113,6 +120,11 @@ class MaskedForwardEngine:
         buffer: 14.5 MB) and the input staging -- and keeps the default of 512 (7.8 GB).
         A SqueezeNet 1.1 slot holds 10.3 MB -- three 111x111x64 split-fp16 activation buffers (a Fire module's input, its squeeze map and
         the concatenation: 9.5 MB) and the input staging -- and keeps the default of 512 (5.3 GB).
+        A GoogLeNet slot holds 10.5 MB -- three 112x112x64 split-fp16 activation buffers (the stem's output; a module's input, one branch's
+        intermediate map and the concatenation: 9.6 MB) and the input staging -- and keeps the default of 512 (5.4 GB).
+        transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
+        caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
+        True raises ValueError; False, the default, is models.googlenet() without weights.
         stem: how score_packed / score_masks / score_images stage the masks of an image on the ImageNet ResNets --
         "table" (default): the stem by superposition (mpx_stem_table_build once per image, mpx_stem_table_apply per block of mask rows:
         K0, the stem conv and its max pool for all masks of an image without materialising a masked image) for every IMAGE that brings at
@@ -120,7 +132,10 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2 and SqueezeNet 1.1 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1 and GoogLeNet and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+        if transform_input:
+            raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
+                             "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
         if max_batch is None:
             if arch.startswith("vgg"):
                 raise ValueError("%s: pass max_batch -- a VGG engine holds 26.5 MB per slot and has no default size "
@@ -173,8 +188,9 @@ class MaskedForwardEngine:
     @property
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
-        which keeps no table), MobileNetV2, SqueezeNet 1.1 and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet"))
+        which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it) and the small
+        networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -219,13 +235,17 @@ class MaskedForwardEngine:
         return int(self._lib.mpx_workspace_bytes(self._h))
 
     # ---- weights ----
-    def load_state_dict(self, sd, eps=BN_EPS, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 state_dict (key names as `models.<arch>().state_dict()`), e.g.
-        torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`) are ignored.  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
+    def load_state_dict(self, sd, eps=None, only=None):
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`, the `aux1.` / `aux2.` classifiers
+        of torchvision's GoogLeNet checkpoint) are ignored.  `eps`: the BatchNorms' epsilon; None = default_bn_eps(arch), torchvision's value
+        for the architecture (1e-5; 1e-3 for googlenet).  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's depthwise layers load with the
         convs, and `only` takes their names ("features.2.conv.1.0") too."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        if eps is None:
+            eps = default_bn_eps(self.arch)
         if only is not None:
             only = set(only)
             unknown = only - {d.name.decode() for d in self.layers} - {d.name.decode() for d in self.dwconvs}
@@ -716,15 +736,18 @@ class MaskedForwardEngine:
         """{'ms': {kind: ms}, 'launches': {kind: n}, 'per_conv_ms': [...], 'per_norm_ms': [...], 'avgpool2_ms': ms} accumulated since the
         last call.  per_norm_ms (one entry per stand-alone BatchNorm: its concat-append + BN + ReLU launch) and avgpool2_ms (the
         transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture.  'per_dw_ms'
-        (one entry per depthwise layer) is the same split on a MobileNetV2 engine."""
+        (one entry per depthwise layer) is the same split on a MobileNetV2 engine, 'per_clip_pool_ms' (one entry per clipped 3x3 max pool,
+        mpx_clip_pool_info) on a GoogLeNet engine."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
         per_norm = (C.c_double * max(1, len(self.norms)))()
         avg2 = (C.c_double * 1)()
         per_dw = (C.c_double * max(1, len(self.dwconvs)))()
-        _lib.check(self._h, self._lib.mpx_profile_collect_dw(self._h, ms, n, per, per_norm, avg2, per_dw), "mpx_profile_collect_dw")
+        n_cp = int(self._lib.mpx_num_clip_pools(self._h))
+        per_cp = (C.c_double * max(1, n_cp))()
+        _lib.check(self._h, self._lib.mpx_profile_collect_pool(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp), "mpx_profile_collect_pool")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
                 "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
-                "per_dw_ms": list(per_dw)[:len(self.dwconvs)]}
+                "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp]}

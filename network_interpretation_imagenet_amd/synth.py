@@ -260,9 +260,54 @@ def make_squeezenet_state_dict(seed=7):
     return sd
 
 
+# torchvision googlenet.py: Inception(in, ch1x1, ch3x3red, ch3x3, ch5x5red, ch5x5, pool_proj) of the nine modules
+GOOGLENET_MODULES = (("inception3a", 192, 64, 96, 128, 16, 32, 32), ("inception3b", 256, 128, 128, 192, 32, 96, 64),
+                     ("inception4a", 480, 192, 96, 208, 16, 48, 64), ("inception4b", 512, 160, 112, 224, 24, 64, 64),
+                     ("inception4c", 512, 128, 128, 256, 24, 64, 64), ("inception4d", 512, 112, 144, 288, 32, 64, 64),
+                     ("inception4e", 528, 256, 160, 320, 32, 128, 128), ("inception5a", 832, 256, 160, 320, 32, 128, 128),
+                     ("inception5b", 832, 384, 192, 384, 48, 128, 128))
+GOOGLENET_FC_GAIN = 2.5
+
+
+def make_googlenet_state_dict(seed=7):
+    """OrderedDict with the key set, order and shapes of torchvision's GoogLeNet without the aux classifiers
+    (models.googlenet(aux_logits=False).state_dict(): <m>.conv.weight and <m>.bn.{weight, bias, running_mean, running_var,
+    num_batches_tracked} for m = conv1, conv2, conv3 and inception<k>.{branch1, branch2.0, branch2.1, branch3.0, branch3.1, branch4.1} of the nine
+    modules, fc.weight / .bias: 57 x 6 + 2 = 344 tensors; no conv has a bias).  Draws: every conv He-normal, the BatchNorm draws of the
+    other networks (_bn), fc N(0, GOOGLENET_FC_GAIN / sqrt(1024)) with bias N(0, 0.1).  The engine loads these BatchNorms with eps = 1e-3.
+    How peaked the softmax is depends on the draw.  Seeds 0 .. 15 were surveyed in fp32 on the 28 rows tests/googlenet_ref.E2E_CASES scores:
+    the default seed 7 gives an unmasked peak of 0.74 / 0.89 (felzenszwalb picture / grid picture), masked rows' peaks of 0.28 .. 0.92 and
+    top-two logit gaps >= 1.7, so it needs no offset; seed 3 saturates (0.996), seeds 0, 10, 11 and 15 have rows with gaps of 0.003 .. 0.008.
+    tests/test_googlenet_cpu.py asserts the conditions in fp64 at the default seed."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def basic(name, cin, cout, k):
+        _conv(sd, name + ".conv", cin, cout, k, g)
+        _bn(sd, name + ".bn", cout, g)
+        sd[name + ".bn.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    basic("conv1", 3, 64, 7)
+    basic("conv2", 64, 64, 1)
+    basic("conv3", 64, 192, 3)
+    for name, cin, c1, r3, c3, r5, c5, pp in GOOGLENET_MODULES:
+        basic(name + ".branch1", cin, c1, 1)
+        basic(name + ".branch2.0", cin, r3, 1)
+        basic(name + ".branch2.1", r3, c3, 3)
+        basic(name + ".branch3.0", cin, r5, 1)
+        basic(name + ".branch3.1", r5, c5, 3)
+        basic(name + ".branch4.1", cin, pp, 1)
+    sd["fc.weight"] = torch.randn(1000, 1024, generator=g) * (GOOGLENET_FC_GAIN / 1024 ** 0.5)
+    sd["fc.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
-    DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict) key set."""
+    DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
+    make_googlenet_state_dict) key set."""
+    if arch == "googlenet":
+        return make_googlenet_state_dict(seed)
     if arch == "squeezenet1_1":
         return make_squeezenet_state_dict(seed)
     if arch == "mobilenet_v2":

@@ -219,6 +219,50 @@ if arch.startswith("squeezenet"):     # SqueezeNet: the Fire modules' convs by t
           % (100 * tot / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms, 100 * prof["ms"]["head"] / reps / allms, allms,
              sum(prof["launches"].values()) // reps - 1))
     del ph, pl, lg
+if arch == "googlenet":     # GoogLeNet: the clipped 3x3 max pools as launches of their own, and each module's launches side by side
+    import ctypes as C
+    print("-- clipped-window 3x3 max pools (mpx_maxpool3x3_clip: one launch each); bytes = split-fp16 planes, one read of the map + one write, pitch channels per pixel --")
+    pools = []
+    for k in range(eng._lib.mpx_num_clip_pools(eng._h)):
+        v = [C.c_int() for _ in range(4)]
+        eng._lib.mpx_clip_pool_info(eng._h, k, *[C.byref(q) for q in v])
+        pools.append(tuple(q.value for q in v))
+    mods = [n[:-len(".branch1.conv")] for n in names if n.endswith(".branch1.conv")]
+    pool_names = ["maxpool1", "maxpool2"] + [x for m in mods for x in (["maxpool3"] if m == "inception4a" else []) + [m + ".branch4.0"]]
+    tot_cp = tot_bytes = s1_ms = s1_bytes = 0.0
+    cp_ms = {}
+    for name, (hin, stride, pad, pitch), ms in zip(pool_names, pools, prof["per_clip_pool_ms"]):
+        ms /= reps
+        ho = hin if stride == 1 else -(-(hin - 3) // 2) + 1
+        nbytes = batch * 4.0 * pitch * (hin * hin + ho * ho)
+        tot_cp += ms
+        tot_bytes += nbytes
+        if stride == 1:
+            s1_ms += ms
+            s1_bytes += nbytes
+        cp_ms[name] = ms
+        print("%-24s pitch %4d s%d p%d %3dx%-3d -> %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (name, pitch, stride, pad, hin, hin, ho, ho, ms, nbytes / 1e6,
+                                                                                            nbytes / max(ms, 1e-9) / 1e9))
+    allms = sum(prof["ms"].values()) / reps
+    print("clipped pools total %.3f ms/batch, %.1f MB -> %.2f TB/s (the nine stride-1 pools %.3f ms, %.2f TB/s; the three stride-2 pools %.3f ms, %.2f TB/s)"
+          % (tot_cp, tot_bytes / 1e6, tot_bytes / max(tot_cp, 1e-9) / 1e9, s1_ms, s1_bytes / max(s1_ms, 1e-9) / 1e9, tot_cp - s1_ms,
+             (tot_bytes - s1_bytes) / max(tot_cp - s1_ms, 1e-9) / 1e9))
+    print("-- per Inception module, ms per batch: the three 1x1 convs that read the module input | the two 3x3 convs | the pool | branch4.1 --")
+    per = dict(zip(names, [ms / reps for ms in prof["per_conv_ms"]]))
+    heads = 0.0
+    for m in mods:
+        h3 = [per["%s.%s.conv" % (m, b)] for b in ("branch1", "branch2.0", "branch3.0")]
+        k3 = per[m + ".branch2.1.conv"] + per[m + ".branch3.1.conv"]
+        heads += sum(h3)
+        print("%-12s 1x1 heads %.3f + %.3f + %.3f = %.3f | 3x3 %.3f | pool %.3f | branch4.1 %.3f | module %.3f ms" % (
+            m, h3[0], h3[1], h3[2], sum(h3), k3, cp_ms[m + ".branch4.0"], per[m + ".branch4.1.conv"],
+            sum(h3) + k3 + cp_ms[m + ".branch4.0"] + per[m + ".branch4.1.conv"]))
+    other_pool = prof["ms"]["pool"] / reps - tot_cp
+    print("share of the forward by op class: conv (MFMA) %.1f %% (of which the 27 same-input 1x1 heads %.1f %% of the forward), clipped pools %.1f %%, "
+          "maxpool4 + global average pool %.1f %%, staging (K0) %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
+          % (100 * tot / allms, 100 * heads / allms, 100 * tot_cp / allms, 100 * other_pool / allms,
+             100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * prof["ms"]["head"] / reps / allms, allms,
+             sum(prof["launches"].values()) // reps - 1))
 tails = eng.bottleneck_tails()
 if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_MASK", "3") == "3":
     names = [d.name.decode() for d in eng.layers]

@@ -128,6 +128,29 @@ enum {
  * Three activation buffers of 112 * 112 * 64 elements per image (the stem's output): 10.5 MB per slot with the staging.  It stages through
  * mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.  torchvision's transform_input (on in its
  * pretrained googlenet) is NOT applied: the caller's normalisation is the network's input.
+ * -- or one of torchvision's ShuffleNetV2 networks (1.4 .. 7.4 M parameters, 0.04 .. 0.58 GMAC per forward):
+ *   MPX_ARCH_SHUFFLENET + 5 / 10 / 15 / 20   shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0; every other id in [9000, 10000) is MPX_E_ARG
+ * A ShuffleNetV2 engine runs conv1 (3 -> 24, 3x3 stride 2 pad 1, reading the padded NHWC4 staging: k_packed = 96) + BN + ReLU, the padded
+ * 3x3 stride-2 max pool (mpx_maxpool3x3s2, 112 -> 56), stage2 / stage3 / stage4 of 4 / 8 / 4 blocks on 28x28 / 14x14 / 7x7 maps, conv5 (1x1 to
+ * 1024, 2048 for x2_0) + BN + ReLU, mpx_global_avgpool and fc, the logit layer and last conv entry.  Stage widths (stage2, stage3, stage4):
+ * x0_5 48, 96, 192; x1_0 116, 232, 464; x1_5 176, 352, 704; x2_0 244, 488, 976.  With bf = half a stage's width, a block is
+ *   stride 1: x1, x2 = the halves of its input; cat(x1, branch2(x2));   stride 2 (block 0 of a stage): cat(branch1(x), branch2(x))
+ *   branch2 = 1x1 conv + BN + ReLU, depthwise 3x3 + BN WITHOUT activation, 1x1 conv + BN + ReLU;  branch1 = depthwise 3x3 stride 2 + BN, 1x1 conv + BN + ReLU
+ * followed by channel_shuffle(., 2).  38 entries in the conv list ("conv1.0", "stage2.0.branch1.2", "stage2.0.branch2.0", "stage2.0.branch2.5",
+ * "stage2.1.branch2.0", ..., "conv5.0", "fc"; bn names "conv1.1", "stageN.k.branch1.3", ...), 19 depthwise layers in the depthwise list
+ * ("stageN.0.branch1.0", "stageN.k.branch2.3"; clamp_in 0, linear: mpx_dwconv_layout, mpx_dwconv3x3_bn), 16 shuffles (mpx_num_shuffles).
+ * THE TWO-HALF LAYOUT.  A stage map of 2 bf logical channels is stored with pitch 2 hp, hp = bf rounded up to 32: logical channel l < bf at
+ * physical l, l >= bf at hp + (l - bf); physical channels [bf, hp) and [hp + bf, 2 hp) are exact zeros that every forward writes.  (bf, hp) of
+ * stage2 / 3 / 4: x0_5 (24, 32) (48, 64) (96, 96); x1_0 (58, 64) (116, 128) (232, 256); x1_5 (88, 96) (176, 192) (352, 352); x2_0 (122, 128)
+ * (244, 256) (488, 512).  A stride-1 block's branch2.0 is an INPUT-SLICE layer: it reads the second half in place (mpx_conv_in_slice: pitch
+ * 2 hp, offset hp, K = hp), and mpx_conv_bn_act on it takes the BASE of the stage planes, as an output-slice layer takes the base of the
+ * concatenation.  A stride-2 block's branch1.2 and branch2.5 are output-slice layers: they write the halves of one buffer (pitch 2 hp, offset
+ * 0 / hp, hp channels stored: the pads as zeros).  mpx_shuffle2_concat interleaves the halves into the next two-half map.  A layer that reads
+ * a whole stage map -- the next stage's branch1.0, branch1.2 and branch2.0, and conv5 -- has its weights placed at the physical channels
+ * (mpx_conv_in_slice / mpx_dwconv_layout report bf and hp; mpx_pack_conv_weights, which sees the descriptor alone, packs the dense layout).
+ * Input-slice, output-slice and padded layers run the generic tiles 0, 1, 2, 4 and 7 only.  conv1 and the pool keep 24 channels at pitch 32.
+ * Three activation buffers of 112 * 112 * 32 elements per image (conv1's output) for every width: 5.7 MB per slot with the staging.  It
+ * stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -140,6 +163,7 @@ enum {
 #define MPX_ARCH_MOBILENET 6000
 #define MPX_ARCH_SQUEEZENET 7000
 #define MPX_ARCH_GOOGLENET 8000
+#define MPX_ARCH_SHUFFLENET 9000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -165,7 +189,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1 and GoogLeNet, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet and the ShuffleNetV2s, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -183,6 +207,12 @@ int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
  * width that are multiples of 8 with offset + stored width <= pitch; the stored width is cout, except where the last slice also writes the
  * concatenation's pad channels as zeros (inception4d.branch4.1: cout 64, 80 stored).  mpx_conv_desc keeps its layout. */
 int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
+/* Where layer i reads: *pitch = channels between adjacent pixels of its input planes, *offset = its first channel within a pixel.  An
+ * ordinary layer reads whole pixel rows: k_packed / ksize^2 and 0 (4 and 0 for a layer on the NHWC4 staging).  A stride-1 ShuffleNetV2
+ * block's branch2.0 reads the second half of a two-half stage map in place: 2 hp and hp (its k_packed is hp).  *bf, *hp: non-zero when the
+ * layer reads a WHOLE two-half stage map (cin = 2 bf logical channels at pitch 2 hp): its weight column of logical channel l sits at l
+ * (l < bf) or hp + l - bf; 0, 0 for every other layer.  Any pointer may be NULL. */
+int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
  * w = conv weight OIHW [cout][cin][k][k]; conv_bias = the conv's own bias [cout] or NULL (torchvision's ResNet convs have
@@ -230,6 +260,11 @@ int mpx_num_dwconvs(const mpx_engine* h);
 int mpx_dwconv_info(const mpx_engine* h, int k, mpx_dwconv_desc* out);
 int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps);
 int mpx_dwconv_params(const mpx_engine* h, int k, const float** w, const float** scale, const float** shift);
+/* What mpx_dwconv_desc has no field for (its layout is fixed): *linear = 1 when the layer has NO activation behind its BatchNorm and no clamp
+ * on load (every depthwise layer of a ShuffleNetV2 engine: mpx_forward runs mpx_dwconv3x3_bn on it), 0 for MobileNetV2's ReLU6 layers; *bf,
+ * *hp non-zero when its planes are a whole two-half stage map (channels = 2 bf at pitch 2 hp: channel c >= bf loads to hp + c - bf).  Any
+ * pointer may be NULL. */
+int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp);
 
 /* Kernel variant of layer i (tuning / test hook; results are identical up to fp32 summation order).  The ids are exactly the
  * kernels some layer class runs by default:
@@ -346,6 +381,8 @@ int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
  * For the last entry ("fc") out_hi/out_lo are ignored and out_f32 (DEV f32[B][1000]) is written;
  * for every other layer out_f32 must be NULL (a SqueezeNet engine has no such entry: its last conv, classifier.1, writes planes
  * [B][13][13][1000] and out_f32 must be NULL there too).
+ * An input-slice layer (a stride-1 ShuffleNetV2 block's branch2.0; mpx_conv_in_slice): in_hi|lo is the BASE of the stage planes
+ * [B][h][w][pitch]; the layer reads channels [offset, offset + k_packed) of every pixel and nothing else -- the SLICE precedent, on the input side.
  * An output-slice layer (a SqueezeNet expand conv, the last conv of a GoogLeNet branch; mpx_conv_out_slice): out_hi|lo is the BASE of the
  * concatenated planes [B][h][w][pitch]; the layer writes channels [offset, offset + cout) of every pixel (inception4d.branch4.1: 16 zero
  * channels more, up to the pitch) and nothing else; res_* must be NULL. */
@@ -467,6 +504,33 @@ int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
 int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
                            void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, int clamp_in, void* stream);
 
+/* ---- ShuffleNetV2: depthwise 3x3 conv (pad 1, stride 1 or 2) + BatchNorm, NO activation, on split planes ---------------------------
+ * replaces: `nn.Conv2d(c, c, 3, stride, 1, groups=c, bias=False)` + `nn.BatchNorm2d(c)` of torchvision's shufflenetv2.py InvertedResidual
+ *           (branch1.0 / .1 and branch2.3 / .4) inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * Operands and arithmetic are mpx_dwconv3x3_bn_relu6's without its two clamps: x = hi + lo (exact); acc = fma(w[tap], x[tap], acc) over the
+ * taps inside the map in row-major order; fl(fl(scale * acc) + shift); the re-split.  Negative results and results above 6 pass through.
+ * Channels with zero weights, scale and shift (the pitch's pads, the gaps of a two-half map) come out as exact zeros for finite inputs.
+ * MPX_E_ARG for a null pointer, B <= 0, hin <= 0, a pitch that is not a positive multiple of 8, a stride other than 1 or 2 and pointers that
+ * are not 16-byte aligned.  The planes must not overlap.  Offsets are 64-bit.  ONE launch. */
+int mpx_dwconv3x3_bn(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
+                     void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, void* stream);
+
+/* ---- ShuffleNetV2: channel_shuffle(cat(a, b), 2) into the two-half layout ------------------------------------------------------
+ * replaces: `torch.cat((x1, self.branch2(x2)), dim=1)` / `torch.cat((self.branch1(x), self.branch2(x)), dim=1)` and `channel_shuffle(out, 2)`
+ *           of torchvision's shufflenetv2.py InvertedResidual.forward inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * a: DEV split planes [B][hw][hw][a_pitch], b: [B][hw][hw][b_pitch], bf real channels each (their other channels are never read); out:
+ * [B][hw][hw][2 hp].  For physical output channel q, h = q / hp and j = q % hp: j >= bf gets zero bits in both planes; else l = h * bf + j and
+ * the (hi, lo) pair is copied verbatim from (l & 1 ? b : a)[l >> 1].  Bit-exact.  a may be the first half of a two-half map (a_pitch = 2 hp)
+ * and b its second half (pointer + hp, b_pitch = 2 hp).  out must not overlap a or b.
+ * MPX_E_ARG for a null pointer, B <= 0, hw <= 0, bf odd or <= 0, hp < bf or not a multiple of 32, a pitch below bf or not a multiple of 8,
+ * and pointers that are not 16-byte aligned.  Offsets are 64-bit.  ONE launch. */
+int mpx_shuffle2_concat(mpx_engine* h, const void* a_hi, const void* a_lo, int a_pitch, const void* b_hi, const void* b_lo, int b_pitch,
+                        void* out_hi, void* out_lo, int B, int hw, int bf, int hp, void* stream);
+/* The shuffles of a ShuffleNetV2 engine's forward, in order (16; 0 for every other engine), and shuffle k's map side, bf, hp and the pitches
+ * of its two sources (any pointer may be NULL). */
+int mpx_num_shuffles(const mpx_engine* h);
+int mpx_shuffle_info(const mpx_engine* h, int k, int* hw, int* bf, int* hp, int* a_pitch, int* b_pitch);
+
 /* ---- MobileNetV2: K4a with the ReLU6 clamp of its producer: global average pool of min(x, 6), [B][hw][c] -> [B][c].
  * replaces: the ReLU6 of features.18 and `nn.functional.adaptive_avg_pool2d(x, (1, 1))` of torchvision's MobileNetV2 inside
  *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  Sums in pixel order in fp32, divides by hw, re-splits;
@@ -554,6 +618,10 @@ int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launch
  * launch of the forward. */
 int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                              double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms);
+/* The same with ShuffleNetV2's split of kind 2: per_shuffle_ms (HOST f64[mpx_num_shuffles], may be NULL) gets every channel shuffle launch
+ * of the forward. */
+int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                                double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms);
 /* Algorithmic FLOPs (2*MAC, convs + depthwise convs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 

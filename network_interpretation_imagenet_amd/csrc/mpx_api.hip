@@ -13,6 +13,7 @@
 #include "mpx_dw.h"
 #include "mpx_fire.h"
 #include "mpx_pool3c.h"
+#include "mpx_shuffle.h"
 
 #include <algorithm>
 #include <cmath>
@@ -37,10 +38,11 @@ constexpr size_t kVggActElemsPerImage = 224 * 224 * 64; // VGG: the 64-channel m
 constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output of features.0
 constexpr size_t kMobileActElemsPerImage = 112 * 112 * 96;   // MobileNetV2: features.2's expanded map, 1.5 x kActElemsPerImage
 constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: the output of features.0 (the largest concatenation is 55 * 55 * 128)
+constexpr size_t kShuffleActElemsPerImage = 112 * 112 * 32; // ShuffleNetV2: conv1's output, 24 channels at pitch 32 (= x2_0's stage2.0.branch2.0 map, 56 * 56 * 128)
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
-              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13 };
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -62,6 +64,15 @@ struct ConvLayer {
     // concatenation gets its 16 pad channels written.  y_pitch = 0: an ordinary layer, which fills whole pixel rows of cout_store channels.
     int y_pitch = 0;
     int y_offset = 0;
+    // input slice (a stride-1 ShuffleNetV2 block's branch2.0: the second half of a two-half stage map, read in place): the layer reads channels
+    // [x_offset, x_offset + cin_pad) of planes whose pixels are x_pitch channels apart -- the generic kernel's pix_stride, which it carries
+    // separately from k_per_tap.  x_pitch = 0: an ordinary layer, which reads whole pixel rows of cin_pad channels.
+    int x_pitch = 0;
+    int x_offset = 0;
+    // input in the two-half layout (mpx_shuffle.h): the layer reads a whole stage map of 2 * in_bf logical channels stored with pitch
+    // 2 * in_hp = cin_pad; the packer puts logical weight column l at l (l < in_bf) or in_hp + l - in_bf.  in_hp = 0: columns as they come.
+    int in_bf = 0;
+    int in_hp = 0;
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
     int tile_default = -1;  // the layer's default where the topology sets one of its own (DenseNet's conv2); -1: default_tile(d)
     // downsample fusion (bottleneck blocks): the block's last 1x1 conv ("main") and its downsample 1x1 conv ("ds")
@@ -110,6 +121,8 @@ struct TailBlock {
 // A depthwise 3x3 conv + BatchNorm + ReLU6 (MobileNetV2; mpx_dw.h): fp32 tap-major weights [9][pitch] and BatchNorm vectors of its own.
 struct DwLayer {
     mpx_dwconv_desc d;
+    bool linear = false;    // ShuffleNetV2: BatchNorm only, no activation and no clamp (dwconv3x3_bn_kernel, mpx_shuffle.h)
+    int in_bf = 0, in_hp = 0;   // its planes are a two-half stage map (channels = 2 * in_bf, pitch = 2 * in_hp): logical channel c loads to its physical position
     float* w = nullptr;
     float* scale = nullptr;
     float* shift = nullptr;
@@ -118,6 +131,12 @@ struct DwLayer {
 
 constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
 constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max pool k (mpx_engine::pools3c) kProfSubPool3c - k
+constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shuffle k (mpx_engine::shuffles) kProfSubShuffle - k
+
+// A channel shuffle of the op list (ShuffleNetV2; mpx_shuffle.h): a = Op::in at a_pitch, b = Op::res advanced by b_offset at b_pitch
+struct ShuffleOp {
+    int side, bf, hp, a_pitch, b_pitch, b_offset;
+};
 
 // A clipped-window 3x3 max pool of the op list (GoogLeNet; mpx_pool3c.h)
 struct ClipPool {
@@ -129,7 +148,7 @@ struct ProfRec {
     int kind;
     int conv;
     int sub;        // kind 2: -1 = any pool, -2 = a DenseNet transition's average pool, k >= 0 = the launch of DenseNet norm k,
-                    // kProfSubDw - k = MobileNetV2's depthwise layer k, kProfSubPool3c - k = GoogLeNet's clipped max pool k
+                    // kProfSubDw - k = a depthwise layer k, kProfSubPool3c - k = GoogLeNet's clipped max pool k, kProfSubShuffle - k = ShuffleNetV2's shuffle k
 };
 
 }  // namespace
@@ -150,6 +169,8 @@ struct mpx_engine {
     bool squeezenet = false;        // torchvision SqueezeNet 1.1: Fire modules over three activation buffers, staged through K0 only
     bool googlenet = false;         // torchvision GoogLeNet: Inception modules over three activation buffers, staged through K0 only
     std::vector<ClipPool> pools3c;  // its clipped-window 3x3 max pools in forward order
+    bool shufflenet = false;        // torchvision ShuffleNetV2: split / shuffle blocks over three activation buffers, staged through K0 only
+    std::vector<ShuffleOp> shuffles;    // its channel shuffles in forward order
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -249,6 +270,7 @@ int build_topology_densenet(mpx_engine* h);
 int build_topology_mobilenet(mpx_engine* h);
 int build_topology_squeezenet(mpx_engine* h);
 int build_topology_googlenet(mpx_engine* h);
+int build_topology_shufflenet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -259,6 +281,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_MOBILENET && h->arch < MPX_ARCH_MOBILENET + 1000) return build_topology_mobilenet(h);
     if (h->arch >= MPX_ARCH_SQUEEZENET && h->arch < MPX_ARCH_SQUEEZENET + 1000) return build_topology_squeezenet(h);
     if (h->arch >= MPX_ARCH_GOOGLENET && h->arch < MPX_ARCH_GOOGLENET + 1000) return build_topology_googlenet(h);
+    if (h->arch >= MPX_ARCH_SHUFFLENET && h->arch < MPX_ARCH_SHUFFLENET + 1000) return build_topology_shufflenet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -1089,6 +1112,145 @@ int build_topology_googlenet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision ShuffleNetV2 (shufflenetv2.py; x0_5 / x1_0 / x1_5 / x2_0): conv1 = Conv2d(3, 24, 3, stride 2, pad 1) + BN + ReLU (224 -> 112) |
+// MaxPool2d(3, 2, 1) (112 -> 56) | stage2, stage3, stage4 of 4, 8, 4 InvertedResidual blocks on 28x28, 14x14, 7x7 maps (block 0 of a stage has
+// stride 2) | conv5 = 1x1 conv to 1024 (2048 for x2_0) + BN + ReLU | mean over the 7x7 map | fc.  No conv has a bias.  With bf = oup / 2:
+//   stride 1: x1, x2 = x[:, :bf], x[:, bf:];  out = cat(x1, branch2(x2))
+//   stride 2: out = cat(branch1(x), branch2(x))
+//   branch2 = 1x1 conv (bf -> bf on x2; stride 2: inp -> bf on x) + BN + ReLU, depthwise 3x3 (the block's stride) + BN, 1x1 conv bf -> bf + BN + ReLU
+//   branch1 = depthwise 3x3 stride 2 (groups = inp) + BN, 1x1 conv inp -> bf + BN + ReLU
+//   then channel_shuffle(out, 2): out'[2i] = out[i], out'[2i + 1] = out[bf + i].
+// Stage maps live in the TWO-HALF layout (mpx_shuffle.h): pitch 2 hp, hp = bf rounded up to 32, the second half at hp, exact zeros on the
+// pads.  A stride-1 block's branch2.0 reads the second half IN PLACE (ConvLayer::x_pitch / x_offset: the generic kernel's pix_stride is not
+// its K per tap), the shuffle reads the first half in place; whoever reads a whole stage map -- the next stage's branch1.0 (depthwise),
+// branch1.2, branch2.0 and conv5 -- has its weights packed at the physical channel positions (in_bf / in_hp).  conv1 and the max pool keep
+// the plain layout, 24 channels at pitch 32.  The depthwise layers have no activation (DwLayer::linear: dwconv3x3_bn_kernel).
+// Op list, 76 launches: conv1 | OP_MAXPOOL | 13 stride-1 blocks of 4 (branch2.0, branch2.3, branch2.5, shuffle) | 3 stride-2 blocks of 6
+// (branch1.0, branch1.2, branch2.0, branch2.3, branch2.5, shuffle) | conv5 | OP_AVGPOOL | fc | OP_HEAD.  38 conv entries, 19 depthwise, 16 shuffles.
+// Buffers: three of 112 * 112 * 32 elements per image.  Stride 1: X the block input, T1 branch2.0's output and then branch2.5's, T2 the
+// depthwise output and then the shuffled map, the next X.  Stride 2: branch1.0 X -> T1, branch1.2 T1 -> the first half of T2 (SLICE form),
+// branch2.0 X -> T1, branch2.3 T1 -> X (dead from here on), branch2.5 X -> the second half of T2, the shuffle T2 -> T1, the next X.
+int build_topology_shufflenet(mpx_engine* h) {
+    static const int widths[4][5] = {{24, 48, 96, 192, 1024}, {24, 116, 232, 464, 1024}, {24, 176, 352, 704, 1024}, {24, 244, 488, 976, 2048}};
+    const int* w = nullptr;
+    switch (h->arch - MPX_ARCH_SHUFFLENET) {
+        case 5: w = widths[0]; break;
+        case 10: w = widths[1]; break;
+        case 15: w = widths[2]; break;
+        case 20: w = widths[3]; break;
+        default: return MPX_E_ARG;
+    }
+    h->shufflenet = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kShuffleActElemsPerImage;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    struct ConvOpt { int cin_pad, cout_store, in_bf, in_hp, x_pitch, x_offset, y_pitch, y_offset; };
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, const ConvOpt& o) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = 1;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
+        L.cin_pad = L.is_stem ? cin : o.cin_pad;
+        L.cout_store = o.cout_store;
+        L.in_bf = o.in_bf; L.in_hp = o.in_hp;
+        L.x_pitch = o.x_pitch; L.x_offset = o.x_offset;
+        L.y_pitch = o.y_pitch; L.y_offset = o.y_offset;
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(std::max(cout, L.cout_store), 128);
+        L.tile = default_tile(L.d);
+        // default_tile judges the descriptor alone; a layer that reads or writes a channel slice, or whose planes are wider than its channels,
+        // runs the generic tiles only: its rules restricted to them, as build_topology_googlenet (all such layers here are 1x1)
+        if (!L.is_stem && (L.x_pitch || L.y_pitch || L.cin_pad != cin))
+            L.tile = L.tile_default = cout <= 64 ? 4 : (cout > cin ? 7 : 2);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
+    auto add_dw = [&](const std::string& name, const std::string& bn, int c, int pitch, int in_bf, int in_hp, int stride, int hin, int in, int out) {
+        DwLayer D;
+        std::memset(&D.d, 0, sizeof D.d);
+        set_name(D.d.name, name);
+        set_name(D.d.bn_name, bn);
+        D.d.channels = c; D.d.pitch = pitch; D.d.stride = stride; D.d.hin = hin;
+        D.d.clamp_in = 0;
+        D.linear = true;
+        D.in_bf = in_bf; D.in_hp = in_hp;
+        h->dws.push_back(D);
+        h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, in, out, BUF_NONE, hin, pitch, BUF_NONE});
+    };
+    auto shuffle_op = [&](int a, int b, int out, int side, int bf, int hp, int a_pitch, int b_pitch, int b_offset) {
+        h->shuffles.push_back(ShuffleOp{side, bf, hp, a_pitch, b_pitch, b_offset});
+        h->ops.push_back(Op{OP_SHUFFLE, (int)h->shuffles.size() - 1, a, out, b, side, 2 * hp, BUF_NONE});
+    };
+    auto fits = [&](int side, int pitch) { return (size_t)side * side * pitch <= kShuffleActElemsPerImage; };
+    int c = add_conv("conv1.0", "conv1.1", 3, w[0], 3, 2, 1, MPX_IMG, ConvOpt{3, pitch_of(w[0]), 0, 0, 0, 0, 0, 0});
+    conv_op(c, BUF_INPUT, 0);
+    h->ops.push_back(Op{OP_MAXPOOL, -1, 0, 1, BUF_NONE, 112, pitch_of(w[0]), BUF_NONE});
+    int X = 1, hcur = 56;
+    int ibf = 0, ihp = 0, Pin = pitch_of(w[0]);     // layout of the current map: plain (ihp = 0) at pitch Pin, or two halves of ibf at ihp
+    static const int repeats[3] = {4, 8, 4};
+    for (int s = 0; s < 3; ++s) {
+        const int inp = w[s], oup = w[s + 1], bf = oup / 2, hp = pitch_of(bf);
+        if ((oup & 3) || (s > 0 && inp != 2 * ibf)) return MPX_E_INTERNAL;      // bf even: a shuffle unit starts on an even logical channel
+        for (int b = 0; b < repeats[s]; ++b) {
+            const std::string p = "stage" + std::to_string(s + 2) + "." + std::to_string(b) + ".";
+            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
+            if (b == 0) {
+                const int ho = (hcur - 1) / 2 + 1;
+                if (!fits(hcur, Pin) || !fits(hcur, hp) || !fits(ho, 2 * hp)) return MPX_E_INTERNAL;
+                add_dw(p + "branch1.0", p + "branch1.1", inp, Pin, ibf, ihp, 2, hcur, X, T1);
+                c = add_conv(p + "branch1.2", p + "branch1.3", inp, bf, 1, 1, 0, ho, ConvOpt{Pin, hp, ibf, ihp, 0, 0, 2 * hp, 0});
+                conv_op(c, T1, T2);
+                c = add_conv(p + "branch2.0", p + "branch2.1", inp, bf, 1, 1, 0, hcur, ConvOpt{Pin, hp, ibf, ihp, 0, 0, 0, 0});
+                conv_op(c, X, T1);
+                add_dw(p + "branch2.3", p + "branch2.4", bf, hp, 0, 0, 2, hcur, T1, X);       // X is dead: both branches have read it
+                c = add_conv(p + "branch2.5", p + "branch2.6", bf, bf, 1, 1, 0, ho, ConvOpt{hp, hp, 0, 0, 0, 0, 2 * hp, hp});
+                conv_op(c, X, T2);
+                shuffle_op(T2, T2, T1, ho, bf, hp, 2 * hp, 2 * hp, hp);
+                X = T1;
+                hcur = ho;
+                ibf = bf; ihp = hp; Pin = 2 * hp;
+            } else {
+                if (!fits(hcur, 2 * hp)) return MPX_E_INTERNAL;
+                c = add_conv(p + "branch2.0", p + "branch2.1", bf, bf, 1, 1, 0, hcur, ConvOpt{hp, hp, 0, 0, 2 * hp, hp, 0, 0});
+                conv_op(c, X, T1);
+                add_dw(p + "branch2.3", p + "branch2.4", bf, hp, 0, 0, 1, hcur, T1, T2);
+                c = add_conv(p + "branch2.5", p + "branch2.6", bf, bf, 1, 1, 0, hcur, ConvOpt{hp, hp, 0, 0, 0, 0, 0, 0});
+                conv_op(c, T2, T1);
+                shuffle_op(X, T1, T2, hcur, bf, hp, 2 * hp, hp, 0);
+                X = T2;
+            }
+        }
+    }
+    if (hcur != 7) return MPX_E_INTERNAL;
+    const int T = (X + 1) % 3;
+    c = add_conv("conv5.0", "conv5.1", w[3], w[4], 1, 1, 0, hcur, ConvOpt{Pin, w[4], ibf, ihp, 0, 0, 0, 0});
+    conv_op(c, X, T);
+    h->feat = w[4];
+    h->ops.push_back(Op{OP_AVGPOOL, -1, T, BUF_POOL, BUF_NONE, hcur, w[4], BUF_NONE});
+    {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, "fc");
+        L.d.cin = w[4]; L.d.cout = MPX_NUM_CLASSES; L.d.ksize = 1; L.d.stride = 1; L.d.hin = 1; L.d.hout = 1;
+        L.is_fc = true;
+        L.has_bias = true;
+        L.cin_pad = w[4];
+        L.cout_store = MPX_NUM_CLASSES;
+        L.d.k_packed = w[4];
+        L.d.cout_pad = (int)round_up(MPX_NUM_CLASSES, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        conv_op((int)h->convs.size() - 1, BUF_POOL, BUF_NONE);
+    }
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -1396,9 +1558,12 @@ const TileRow* find_tile(int id) {
 
 // Layer L may run row r's kernel.  The predicates see the descriptor, whose cin is the channels per input pixel except in the small
 // networks' planes, padded to 32 (cin_pad); the stem and the fc read planes of their own.  Only the generic kernel has a SLICE form, so an
-// output-slice layer (y_pitch) runs the rows without a predicate -- tiles 0, 1, 2, 4 and 7 -- and nothing else.
+// output-slice layer (y_pitch) runs the rows without a predicate -- tiles 0, 1, 2, 4 and 7 -- and nothing else.  An INPUT-slice layer (x_pitch: pixels
+// farther apart than its K per tap) does the same: the generic kernel addresses a tap through pix_stride and walks k_per_tap within it, while
+// the 256-row kernels (mpx_conv256.h, mpx_conv256p.h, mpx_convx.h, mpx_convw.h) and the patch kernels (cin = k_per_tap is their row pitch)
+// read dense pixel rows.
 bool eligible(const TileRow& r, const ConvLayer& L) {
-    return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && r.eligible(L.d));
+    return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && !L.x_pitch && r.eligible(L.d));
 }
 
 int launch_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
@@ -1479,8 +1644,12 @@ int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const ha
         p.hin = MPX_IMG_PAD; p.win = MPX_IMG_PAD; p.pix_stride = 4;
         p.kh = L.d.ksize; p.kw = 1; p.stride = L.d.stride; p.pad = L.d.pad - (MPX_IMG_PAD - MPX_IMG) / 2; p.k_per_tap = L.d.k_packed / L.d.ksize;
     } else {
-        p.x_hi = in_hi; p.x_lo = in_lo;
-        p.hin = L.d.hin; p.win = L.d.hin; p.pix_stride = L.cin_pad;
+        // an input-slice layer (x_pitch) gets the BASE of the planes it reads a channel range of, as an output-slice layer the base of y.
+        // The kernel builds its buffer descriptor from the advanced pointer with hin * win * pix_stride records per image, so the descriptor
+        // spans x_offset elements past the end of the planes: no load goes there (a pixel's offsets stay below k_per_tap = the slice's width,
+        // so the last pixel's read ENDS at the end of the planes), but the descriptor's out-of-range zeroing no longer guards that tail.
+        p.x_hi = in_hi ? in_hi + L.x_offset : in_hi; p.x_lo = in_lo ? in_lo + L.x_offset : in_lo;
+        p.hin = L.d.hin; p.win = L.d.hin; p.pix_stride = L.x_pitch ? L.x_pitch : L.cin_pad;
         p.kh = L.d.ksize; p.kw = L.d.ksize; p.stride = L.d.stride; p.pad = L.d.pad; p.k_per_tap = L.cin_pad;
     }
     p.ho = L.d.hout; p.wo = L.d.hout;
@@ -1751,12 +1920,42 @@ int launch_catnorm(mpx_engine* h, const CatNormParams& p, int norm, hipStream_t 
 }
 
 // one dwconv3x3_bn_relu6_kernel launch; `dw` = the engine's depthwise layer it runs for (profile record), -1 from the stand-alone entry
-int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st) {
+// (`linear`: ShuffleNetV2's form without activation and clamps, dwconv3x3_bn_kernel of mpx_shuffle.h)
+int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st, bool linear = false) {
     ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+    if (linear) {
+        // the run form: a unit is a run of 4 (stride 1) or 2 (stride 2) output pixels.  Grid cap, blocks per CU, measured at batch 2340 next to
+        // the one-pixel form, ms at 8 / 4 / 2: 28x28 x 64 stride 1 0.262 / 0.263 / 0.257, 14x14 x 128 0.139 / 0.144 / 0.142,
+        // 7x7 x 256 0.058 / 0.063 / 0.065; 56x56 x 64 stride 2 0.495 / 0.484 / 0.460, 28x28 x 128 0.249 / 0.250 / 0.237: 8 at stride 1, 2 at stride 2
+        const int W = p.stride == 1 ? DwRun<1>::W : DwRun<2>::W;
+        const unsigned long long units = (unsigned long long)(p.npix / p.ho) * (unsigned)((p.ho + W - 1) / W) * (unsigned)(p.pitch / 8);
+        const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (p.stride == 1 ? 8 : 2));
+        if (p.stride == 1)
+            hipLaunchKernelGGL(dwconv3x3_bn_kernel<1>, dim3(grid), dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL(dwconv3x3_bn_kernel<2>, dim3(grid), dim3(256), 0, st, p);
+        MPX_HIP(h, hipGetLastError());
+        return 0;
+    }
     const unsigned long long units = (unsigned long long)p.npix * (unsigned)(p.pitch / 8);
     // as launch_catnorm: about 8 workgroups per CU, striding over the rest
     const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
     hipLaunchKernelGGL(dwconv3x3_bn_relu6_kernel, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one shuffle2_concat_kernel launch; `k` = the engine's shuffle it runs for (profile record), -1 from the stand-alone entry.  The load width
+// follows the alignment of the sources (mpx_shuffle.h): 8-byte loads when bf % 8 == 0, 2-byte loads otherwise.
+int launch_shuffle(mpx_engine* h, const ShuffleParams& p, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubShuffle - k : -1);
+    const unsigned long long units = (unsigned long long)p.npix * (unsigned)(2 * p.hp / 8);
+    // as launch_dwconv: about 8 workgroups per CU, striding over the rest
+    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
+    if (p.bf % 8 == 0)
+        hipLaunchKernelGGL(shuffle2_concat_kernel<true>, dim3(grid), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(shuffle2_concat_kernel<false>, dim3(grid), dim3(256), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -1782,6 +1981,13 @@ int launch_pool3c(mpx_engine* h, const half_t* in_hi, const half_t* in_lo, half_
     return 0;
 }
 
+// mpx_pack_conv_weights with the input's channel layout: in_hp = 0 puts logical input channel ci in column ci of its tap; in_hp > 0 (the
+// layer reads a whole two-half stage map, mpx_shuffle.h: 2 * in_bf logical channels at pitch 2 * in_hp = cin_pad) puts ci < in_bf at ci and
+// ci >= in_bf at in_hp + ci - in_bf; the columns of the gaps stay zero.
+int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float* w, const float* conv_bias, const float* gamma,
+                      const float* beta, const float* mean, const float* var, float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale,
+                      float* shift);
+
 }  // namespace
 
 // =============================================================================================
@@ -1790,6 +1996,16 @@ extern "C" {
 int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* conv_bias, const float* gamma,
                           const float* beta, const float* mean, const float* var, float eps, uint16_t* w_hi,
                           uint16_t* w_lo, float* scale, float* shift) {
+    return pack_conv_weights(d, 0, 0, w, conv_bias, gamma, beta, mean, var, eps, w_hi, w_lo, scale, shift);
+}
+
+}  // extern "C"
+
+namespace {
+
+int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float* w, const float* conv_bias, const float* gamma,
+                      const float* beta, const float* mean, const float* var, float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale,
+                      float* shift) {
     if (!d || !w || !w_hi || !w_lo || !scale || !shift) return MPX_E_ARG;
     const int cin = d->cin, cout = d->cout, k = d->ksize, K = d->k_packed;
     if (k <= 0 || cin <= 0 || cout <= 0 || cout > d->cout_pad || d->cout_pad % 16 != 0) return MPX_E_ARG;
@@ -1804,6 +2020,7 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
     // K = k*k*cin_pad: the input planes may carry more channels per pixel than the layer reads (small nets pad to 32)
     const int cin_pad = stem ? 0 : K / (k * k);
     if (!stem && (K != k * k * cin_pad || cin_pad < cin || K % 32 != 0)) return MPX_E_ARG;
+    if (in_hp && (stem || in_bf <= 0 || in_hp < in_bf || cin != 2 * in_bf || cin_pad != 2 * in_hp)) return MPX_E_ARG;
     std::memset(w_hi, 0, (size_t)d->cout_pad * K * 2);
     std::memset(w_lo, 0, (size_t)d->cout_pad * K * 2);
     for (int co = 0; co < d->cout_pad; ++co) {
@@ -1836,7 +2053,7 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
             for (int ky = 0; ky < k; ++ky)
                 for (int kx = 0; kx < k; ++kx)
                     for (int ci = 0; ci < cin; ++ci)
-                        put((ky * k + kx) * cin_pad + ci, wc[((size_t)ci * k + ky) * k + kx]);
+                        put((ky * k + kx) * cin_pad + (in_hp && ci >= in_bf ? in_hp + ci - in_bf : ci), wc[((size_t)ci * k + ky) * k + kx]);
         }
         // y = bn(conv(x) + conv_bias) = s * acc + (beta + (conv_bias - mean) * s); without BatchNorm: y = acc + beta (+ conv_bias)
         double s = 1.0, t = 0.0;
@@ -1852,6 +2069,10 @@ int mpx_pack_conv_weights(const mpx_conv_desc* d, const float* w, const float* c
     }
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     if (!out || max_batch <= 0) return MPX_E_ARG;
@@ -2007,7 +2228,7 @@ int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv
     const size_t n = (size_t)L.d.cout_pad * L.d.k_packed;
     std::vector<uint16_t> hi(n), lo(n);
     std::vector<float> sc(L.d.cout_pad), sh(L.d.cout_pad);
-    int rc = mpx_pack_conv_weights(&L.d, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data());
+    int rc = pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data());
     if (rc) return fail(h, rc, "pack failed for %s", L.d.name);
     MPX_SET_DEVICE(h);
     MPX_HIP(h, hipMemcpy(L.w_hi, hi.data(), n * 2, hipMemcpyHostToDevice));
@@ -2156,7 +2377,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet and GoogLeNet stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet and ShuffleNetV2 stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -2441,10 +2662,11 @@ int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, co
     const int n = D.d.channels, pitch = D.d.pitch;
     std::vector<float> wt((size_t)9 * pitch, 0.f), sc(pitch, 0.f), sh(pitch, 0.f);     // zeros on the padded channels
     for (int c = 0; c < n; ++c) {
-        for (int t = 0; t < 9; ++t) wt[(size_t)t * pitch + c] = w[(size_t)c * 9 + t];
+        const int q = D.in_hp && c >= D.in_bf ? D.in_hp + c - D.in_bf : c;      // a two-half stage map: the channel's physical position
+        for (int t = 0; t < 9; ++t) wt[(size_t)t * pitch + q] = w[(size_t)c * 9 + t];
         const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)eps);
-        sc[c] = (float)s;
-        sh[c] = (float)((double)beta[c] - (double)mean[c] * s);
+        sc[q] = (float)s;
+        sh[q] = (float)((double)beta[c] - (double)mean[c] * s);
     }
     MPX_SET_DEVICE(h);
     MPX_HIP(h, hipMemcpy(D.w, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
@@ -2480,6 +2702,75 @@ int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, 
     p.npix = (long long)B * p.ho * p.ho;
     MPX_SET_DEVICE(h);
     return launch_dwconv(h, p, -1, as_stream(stream));
+}
+
+int mpx_dwconv3x3_bn(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift, void* out_hi,
+                     void* out_lo, int B, int hin, int pitch, int stride, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv3x3_bn: null pointer");
+    if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (stride != 1 && stride != 2))
+        return fail(h, MPX_E_ARG, "dwconv3x3_bn: B > 0, hin > 0, pitch a positive multiple of 8, stride 1 or 2");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "dwconv3x3_bn: every pointer must be 16-byte aligned");
+    DwParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.w = w; p.scale = scale; p.shift = shift;
+    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.stride = stride; p.clamp_in = 0;
+    p.npix = (long long)B * p.ho * p.ho;
+    MPX_SET_DEVICE(h);
+    return launch_dwconv(h, p, -1, as_stream(stream), true);
+}
+
+int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp) {
+    if (!h || k < 0 || k >= (int)h->dws.size()) return MPX_E_ARG;
+    if (linear) *linear = h->dws[k].linear ? 1 : 0;
+    if (bf) *bf = h->dws[k].in_bf;
+    if (hp) *hp = h->dws[k].in_hp;
+    return 0;
+}
+
+int mpx_shuffle2_concat(mpx_engine* h, const void* a_hi, const void* a_lo, int a_pitch, const void* b_hi, const void* b_lo, int b_pitch,
+                        void* out_hi, void* out_lo, int B, int hw, int bf, int hp, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!a_hi || !a_lo || !b_hi || !b_lo || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "shuffle2_concat: null pointer");
+    if (B <= 0 || hw <= 0 || bf <= 0 || (bf & 1) || hp < bf || (hp & 31) || a_pitch < bf || (a_pitch & 7) || b_pitch < bf || (b_pitch & 7))
+        return fail(h, MPX_E_ARG, "shuffle2_concat: B > 0, hw > 0, bf even and > 0, hp >= bf a multiple of 32, pitches >= bf and multiples of 8");
+    if (misaligned(a_hi) || misaligned(a_lo) || misaligned(b_hi) || misaligned(b_lo) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "shuffle2_concat: every pointer must be 16-byte aligned");
+    ShuffleParams p;
+    std::memset(&p, 0, sizeof p);
+    p.a_hi = (const half_t*)a_hi; p.a_lo = (const half_t*)a_lo; p.b_hi = (const half_t*)b_hi; p.b_lo = (const half_t*)b_lo;
+    p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.npix = (long long)B * hw * hw;
+    p.a_pitch = a_pitch; p.b_pitch = b_pitch; p.bf = bf; p.hp = hp;
+    MPX_SET_DEVICE(h);
+    return launch_shuffle(h, p, -1, as_stream(stream));
+}
+
+int mpx_num_shuffles(const mpx_engine* h) { return h ? (int)h->shuffles.size() : MPX_E_ARG; }
+
+int mpx_shuffle_info(const mpx_engine* h, int k, int* hw, int* bf, int* hp, int* a_pitch, int* b_pitch) {
+    if (!h || k < 0 || k >= (int)h->shuffles.size()) return MPX_E_ARG;
+    const ShuffleOp& S = h->shuffles[k];
+    if (hw) *hw = S.side;
+    if (bf) *bf = S.bf;
+    if (hp) *hp = S.hp;
+    if (a_pitch) *a_pitch = S.a_pitch;
+    if (b_pitch) *b_pitch = S.b_pitch;
+    return 0;
+}
+
+int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp) {
+    if (!h || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    const ConvLayer& L = h->convs[i];
+    if (pitch) *pitch = L.is_stem ? 4 : (L.x_pitch ? L.x_pitch : L.cin_pad);
+    if (offset) *offset = L.x_offset;
+    if (bf) *bf = L.in_bf;
+    if (hp) *hp = L.in_hp;
+    return 0;
 }
 
 int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
@@ -2643,7 +2934,18 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 p.w = D.w; p.scale = D.scale; p.shift = D.shift;
                 p.hin = D.d.hin; p.ho = (D.d.hin - 1) / D.d.stride + 1; p.pitch = D.d.pitch; p.stride = D.d.stride; p.clamp_in = D.d.clamp_in;
                 p.npix = (long long)B * p.ho * p.ho;
-                rc = launch_dwconv(h, p, o.conv, as_stream(stream));
+                rc = launch_dwconv(h, p, o.conv, as_stream(stream), D.linear);
+                break;
+            }
+            case OP_SHUFFLE: {
+                const ShuffleOp& S = h->shuffles[o.conv];
+                ShuffleParams p;
+                std::memset(&p, 0, sizeof p);
+                p.a_hi = hi(o.in); p.a_lo = lo(o.in); p.b_hi = hi(o.res) + S.b_offset; p.b_lo = lo(o.res) + S.b_offset;
+                p.y_hi = hi(o.out); p.y_lo = lo(o.out);
+                p.npix = (long long)B * S.side * S.side;
+                p.a_pitch = S.a_pitch; p.b_pitch = S.b_pitch; p.bf = S.bf; p.hp = S.hp;
+                rc = launch_shuffle(h, p, o.conv, as_stream(stream));
                 break;
             }
             case OP_CATNORM: {
@@ -2803,6 +3105,11 @@ int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launch
 
 int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                              double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms) {
+    return mpx_profile_collect_shuffle(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, nullptr);
+}
+
+int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
+                                double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -2819,6 +3126,8 @@ int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long laun
         if (per_dw_ms && r.kind == 2 && r.sub <= kProfSubDw && kProfSubDw - r.sub < (int)h->dws.size()) per_dw_ms[kProfSubDw - r.sub] += ms;
         if (per_clip_pool_ms && r.kind == 2 && r.sub <= kProfSubPool3c && kProfSubPool3c - r.sub < (int)h->pools3c.size())
             per_clip_pool_ms[kProfSubPool3c - r.sub] += ms;
+        if (per_shuffle_ms && r.kind == 2 && r.sub <= kProfSubShuffle && kProfSubShuffle - r.sub < (int)h->shuffles.size())
+            per_shuffle_ms[kProfSubShuffle - r.sub] += ms;
     }
     h->prof_used = 0;
     return 0;

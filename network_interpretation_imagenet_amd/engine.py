@@ -33,6 +33,8 @@ ARCH_IDS.update({"densenet%d" % d: 5000 + d for d in (121, 169, 201)})
 ARCH_IDS["mobilenet_v2"] = 6002   # torchvision's MobileNetV2, width 1.0 (MPX_ARCH_MOBILENET + 2)
 ARCH_IDS["squeezenet1_1"] = 7011  # torchvision's SqueezeNet 1.1 (MPX_ARCH_SQUEEZENET + 11); squeezenet1_0 is not served
 ARCH_IDS["googlenet"] = 8000      # torchvision's GoogLeNet without the aux classifiers (MPX_ARCH_GOOGLENET); inception_v3 is not served
+# torchvision's ShuffleNetV2 family (MPX_ARCH_SHUFFLENET + 10 x the width multiplier)
+ARCH_IDS.update({"shufflenet_v2_x0_5": 9005, "shufflenet_v2_x1_0": 9010, "shufflenet_v2_x1_5": 9015, "shufflenet_v2_x2_0": 9020})
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -122,6 +124,9 @@ class MaskedForwardEngine:
         the concatenation: 9.5 MB) and the input staging -- and keeps the default of 512 (5.3 GB).
         A GoogLeNet slot holds 10.5 MB -- three 112x112x64 split-fp16 activation buffers (the stem's output; a module's input, one branch's
         intermediate map and the concatenation: 9.6 MB) and the input staging -- and keeps the default of 512 (5.4 GB).
+        A ShuffleNetV2 slot holds 5.7 MB for every width -- three 112x112x32 split-fp16 activation buffers (conv1's output, 24 channels at
+        pitch 32; a block's input, its branch2 map and the shuffled output: 4.8 MB) and the input staging -- and keeps the default of 512
+        (2.9 GB).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -132,7 +137,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1 and GoogLeNet and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet and ShuffleNetV2s and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -188,9 +193,9 @@ class MaskedForwardEngine:
     @property
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
-        which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it) and the small
-        networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet"))
+        which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s
+        and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -236,13 +241,14 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=None, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet / ShuffleNetV2 state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`, the `aux1.` / `aux2.` classifiers
         of torchvision's GoogLeNet checkpoint) are ignored.  `eps`: the BatchNorms' epsilon; None = default_bn_eps(arch), torchvision's value
         for the architecture (1e-5; 1e-3 for googlenet).  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
-        layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's depthwise layers load with the
-        convs, and `only` takes their names ("features.2.conv.1.0") too."""
+        layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's and ShuffleNetV2's depthwise layers
+        load with the convs, and `only` takes their names ("features.2.conv.1.0", "stage2.0.branch1.0") too.  A ShuffleNetV2 state_dict loads
+        as saved: the engine places the columns of a layer that reads a two-half stage map itself."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         if eps is None:
             eps = default_bn_eps(self.arch)
@@ -737,7 +743,7 @@ class MaskedForwardEngine:
         last call.  per_norm_ms (one entry per stand-alone BatchNorm: its concat-append + BN + ReLU launch) and avgpool2_ms (the
         transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture.  'per_dw_ms'
         (one entry per depthwise layer) is the same split on a MobileNetV2 engine, 'per_clip_pool_ms' (one entry per clipped 3x3 max pool,
-        mpx_clip_pool_info) on a GoogLeNet engine."""
+        mpx_clip_pool_info) on a GoogLeNet engine, 'per_shuffle_ms' (one entry per channel shuffle, mpx_shuffle_info) on a ShuffleNetV2 engine."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
@@ -746,8 +752,10 @@ class MaskedForwardEngine:
         per_dw = (C.c_double * max(1, len(self.dwconvs)))()
         n_cp = int(self._lib.mpx_num_clip_pools(self._h))
         per_cp = (C.c_double * max(1, n_cp))()
-        _lib.check(self._h, self._lib.mpx_profile_collect_pool(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp), "mpx_profile_collect_pool")
+        n_sh = int(self._lib.mpx_num_shuffles(self._h))
+        per_sh = (C.c_double * max(1, n_sh))()
+        _lib.check(self._h, self._lib.mpx_profile_collect_shuffle(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh), "mpx_profile_collect_shuffle")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
                 "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
-                "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp]}
+                "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp], "per_shuffle_ms": list(per_sh)[:n_sh]}

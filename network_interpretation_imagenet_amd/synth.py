@@ -302,10 +302,73 @@ def make_googlenet_state_dict(seed=7):
     return sd
 
 
+# torchvision shufflenetv2.py: stages_out_channels (conv1, stage2, stage3, stage4, conv5); stages_repeats is (4, 8, 4) for every width
+SHUFFLENET_WIDTHS = {"shufflenet_v2_x0_5": (24, 48, 96, 192, 1024), "shufflenet_v2_x1_0": (24, 116, 232, 464, 1024),
+                     "shufflenet_v2_x1_5": (24, 176, 352, 704, 1024), "shufflenet_v2_x2_0": (24, 244, 488, 976, 2048)}
+SHUFFLENET_REPEATS = (4, 8, 4)
+# The pooled features of these narrow networks are small, so fc gets a larger gain than the ResNets' FC_GAIN.  Surveyed on the CPU in fp64 on
+# the 28 rows tests/shufflenet_ref.E2E_CASES scores, x1_0 / x0_5: gain 2.5 leaves the softmax flat (row peaks 0.006 .. 0.035 / 0.007 ..
+# 0.018), gain 5 gives 0.024 .. 0.24 / 0.025 .. 0.11, gain 8 at the default seed 7 gives 0.088 .. 0.59 / 0.071 .. 0.35 with unmasked peaks 0.64,
+# 0.72 / 0.25, 0.46 and top-two fp64 logit gaps >= 0.53 / 0.57.  Seeds 0 .. 11 at gain 8: 7 needs no offset; 4 is too flat on both widths
+# (peaks down to 0.038), 3 and 6 saturate x0_5 (0.97, 0.98), 0, 5 and 10 leave rows under 0.05 on one of the two, 9 and 11 have rows with
+# gaps of 0.008 .. 0.015.  tests/test_shufflenet_cpu.py asserts the conditions at the default seed.
+SHUFFLENET_FC_GAIN = 8.0
+
+
+def make_shufflenet_state_dict(arch, seed=7):
+    """OrderedDict with the key set, order and shapes of torchvision's shufflenet_v2_x{0_5, 1_0, 1_5, 2_0} (models.<arch>().state_dict():
+    conv1.0.weight, conv1.1.*, per block stageN.k.{branch1.0.weight, branch1.1.*, branch1.2.weight, branch1.3.* -- stride-2 blocks, k = 0,
+    only --, branch2.0.weight, branch2.1.*, branch2.3.weight, branch2.4.*, branch2.5.weight, branch2.6.*}, conv5.0.weight, conv5.1.*,
+    fc.weight / .bias: 56 convs, 56 BatchNorms with num_batches_tracked, 338 tensors; no conv has a bias).
+    Draws.  Half of every stride-1 block's channels pass through untouched and never meet a BatchNorm, so no gain may compound: a 1x1 conv
+    that ReLU follows is He-normal N(0, sqrt(2 / cin)) -- relu of a zero-mean map of variance 2 r^2 has second moment r^2, the input's --,
+    a depthwise conv (linear: nothing but its BatchNorm behind it) is N(0, sqrt(1 / 9)), which keeps the second moment as it is, and every
+    BatchNorm has the other networks' draws (gamma U(0.9, 1.1), running_var U(0.8, 1.25): a factor near 1).  Both halves of every block
+    output then carry the RMS of the block input, and the shuffle only permutes them: the map RMS neither grows nor dies over the 16 blocks
+    (tests/test_shufflenet_cpu.py asserts bounds).  fc is N(0, SHUFFLENET_FC_GAIN / sqrt(C)) with bias N(0, 0.1)."""
+    w = SHUFFLENET_WIDTHS[arch]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def bn(prefix, c):
+        _bn(sd, prefix, c, g)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    def dw(name, c):
+        sd[name + ".weight"] = torch.randn(c, 1, 3, 3, generator=g) * (1.0 / 9) ** 0.5
+
+    _conv(sd, "conv1.0", 3, w[0], 3, g)
+    bn("conv1.1", w[0])
+    inp = w[0]
+    for s, (oup, reps) in enumerate(zip(w[1:4], SHUFFLENET_REPEATS)):
+        bf = oup // 2
+        for b in range(reps):
+            p = "stage%d.%d." % (s + 2, b)
+            if b == 0:
+                dw(p + "branch1.0", inp)
+                bn(p + "branch1.1", inp)
+                _conv(sd, p + "branch1.2", inp, bf, 1, g)
+                bn(p + "branch1.3", bf)
+            _conv(sd, p + "branch2.0", inp if b == 0 else bf, bf, 1, g)
+            bn(p + "branch2.1", bf)
+            dw(p + "branch2.3", bf)
+            bn(p + "branch2.4", bf)
+            _conv(sd, p + "branch2.5", bf, bf, 1, g)
+            bn(p + "branch2.6", bf)
+        inp = oup
+    _conv(sd, "conv5.0", inp, w[4], 1, g)
+    bn("conv5.1", w[4])
+    sd["fc.weight"] = torch.randn(1000, w[4], generator=g) * (SHUFFLENET_FC_GAIN / w[4] ** 0.5)
+    sd["fc.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict) key set."""
+    if arch in SHUFFLENET_WIDTHS:
+        return make_shufflenet_state_dict(arch, seed)
     if arch == "googlenet":
         return make_googlenet_state_dict(seed)
     if arch == "squeezenet1_1":

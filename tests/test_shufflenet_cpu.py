@@ -1,0 +1,287 @@
+"""The ShuffleNetV2 family without a GPU: the four names, the synthetic state_dicts with torchvision's keys in torchvision's order, the
+parameter and MAC counts, the (bf, hp) table of the two-half layout, the engine's shuffle index map against torchvision's literal
+view / transpose shuffle, the fp64 / fp32 CPU restatement (tests/shufflenet_ref.py) against an independent nn.Module build, the statistics of
+the synthetic networks on exactly the rows the GPU test scores, and the C-ABI surface."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import shufflenet_ref as ref
+from network_interpretation_imagenet_amd import _lib, engine, synth
+from oracle import scorer
+
+ARCH_IDS = {"shufflenet_v2_x0_5": 9005, "shufflenet_v2_x1_0": 9010, "shufflenet_v2_x1_5": 9015, "shufflenet_v2_x2_0": 9020}
+WIDTHS = {"shufflenet_v2_x0_5": (24, 48, 96, 192, 1024), "shufflenet_v2_x1_0": (24, 116, 232, 464, 1024),
+          "shufflenet_v2_x1_5": (24, 176, 352, 704, 1024), "shufflenet_v2_x2_0": (24, 244, 488, 976, 2048)}
+PARAMS = {"shufflenet_v2_x0_5": 1366792, "shufflenet_v2_x1_0": 2278604, "shufflenet_v2_x1_5": 3503624, "shufflenet_v2_x2_0": 7393996}
+MACS = {"shufflenet_v2_x0_5": 40476448, "shufflenet_v2_x1_0": 144907992, "shufflenet_v2_x1_5": 295759392, "shufflenet_v2_x2_0": 583253464}
+HALVES = {"shufflenet_v2_x0_5": ((24, 32), (48, 64), (96, 96)), "shufflenet_v2_x1_0": ((58, 64), (116, 128), (232, 256)),
+          "shufflenet_v2_x1_5": ((88, 96), (176, 192), (352, 352)), "shufflenet_v2_x2_0": ((122, 128), (244, 256), (488, 512))}
+NEW_SYMBOLS = ("mpx_shuffle2_concat", "mpx_dwconv3x3_bn", "mpx_dwconv_layout", "mpx_num_shuffles", "mpx_shuffle_info", "mpx_conv_in_slice",
+               "mpx_profile_collect_shuffle")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARCHS = tuple(ARCH_IDS)
+
+
+def test_the_four_names_are_served_with_ids_of_their_own():
+    for name, arch_id in ARCH_IDS.items():
+        assert engine.ARCH_IDS[name] == arch_id
+    ids = list(engine.ARCH_IDS.values())
+    assert len(ids) == len(set(ids))
+    assert ref.ARCHS == ARCHS and set(synth.SHUFFLENET_WIDTHS) == set(ARCHS)
+    with pytest.raises(ValueError, match="ShuffleNetV2"):
+        engine.MaskedForwardEngine("shufflenet_v2_x3_0")
+
+
+def _bn_keys(prefix, c):
+    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
+            (prefix + ".num_batches_tracked", ())]
+
+
+def _expected_keys(arch):
+    """models.<arch>().state_dict(): key -> shape, in module order, written out from the width table."""
+    w = WIDTHS[arch]
+    out = [("conv1.0.weight", (w[0], 3, 3, 3))] + _bn_keys("conv1.1", w[0])
+    inp = w[0]
+    for s, reps in enumerate((4, 8, 4)):
+        oup = w[s + 1]
+        bf = oup // 2
+        for b in range(reps):
+            p = "stage%d.%d." % (s + 2, b)
+            if b == 0:
+                out += [(p + "branch1.0.weight", (inp, 1, 3, 3))] + _bn_keys(p + "branch1.1", inp)
+                out += [(p + "branch1.2.weight", (bf, inp, 1, 1))] + _bn_keys(p + "branch1.3", bf)
+            out += [(p + "branch2.0.weight", (bf, inp if b == 0 else bf, 1, 1))] + _bn_keys(p + "branch2.1", bf)
+            out += [(p + "branch2.3.weight", (bf, 1, 3, 3))] + _bn_keys(p + "branch2.4", bf)
+            out += [(p + "branch2.5.weight", (bf, bf, 1, 1))] + _bn_keys(p + "branch2.6", bf)
+        inp = oup
+    out += [("conv5.0.weight", (w[4], w[3], 1, 1))] + _bn_keys("conv5.1", w[4])
+    return out + [("fc.weight", (1000, w[4])), ("fc.bias", (1000,))]
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_synth_state_dict_has_torchvisions_keys_order_shapes_and_parameter_count(arch):
+    sd = synth.make_state_dict(arch)
+    assert len(sd) == 338
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _expected_keys(arch)
+    assert list(sd) == list(synth.make_shufflenet_state_dict(arch))
+    assert all(v.dtype == (torch.int64 if k.endswith("num_batches_tracked") else torch.float32) for k, v in sd.items())
+    assert sum(k.endswith("num_batches_tracked") for k in sd) == 56 and sum(v.dim() == 4 for v in sd.values()) == 56
+    params = sum(v.numel() for k, v in sd.items() if k.endswith((".weight", ".bias")))     # nn.Parameters: no running statistics
+    assert params == PARAMS[arch] == ref.PARAMS[arch]
+    assert [k for k in sd if k.endswith(".bias") and sd[k[:-4] + "weight"].dim() == 4] == []      # no conv has a bias
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_topology_counts_macs_and_the_two_half_table(arch):
+    """MACs counted here from the width table alone, then compared with the restatement's topology (which the GPU test compares with the
+    engine's lists and mpx_flops_per_forward = 2 x this)."""
+    w = WIDTHS[arch]
+    macs = 112 * 112 * w[0] * 3 * 9
+    inp, h = w[0], 56
+    for s, reps in enumerate((4, 8, 4)):
+        oup = w[s + 1]
+        bf = oup // 2
+        for b in range(reps):
+            if b == 0:
+                ho = (h - 1) // 2 + 1
+                macs += ho * ho * inp * 9 + ho * ho * inp * bf              # branch1: depthwise stride 2, 1x1
+                macs += h * h * inp * bf + ho * ho * bf * 9 + ho * ho * bf * bf
+                h = ho
+            else:
+                macs += h * h * bf * bf + h * h * bf * 9 + h * h * bf * bf
+        inp = oup
+    macs += 49 * inp * w[4] + w[4] * 1000
+    assert h == 7
+    assert macs == MACS[arch] == ref.MACS[arch] == ref.macs(arch)
+    convs, dws = ref.topology(arch)
+    assert len(convs) == 38 and len(dws) == 19 and convs[-1][0] == "fc" and convs[0][0] == "conv1.0"
+    assert len({c[0] for c in convs}) == 38 and len({d[0] for d in dws}) == 19
+    sd = synth.make_state_dict(arch)
+    is_dw = lambda v: v.dim() == 4 and v.shape[1] == 1 and v.shape[2] == 3
+    assert [n for n, *_ in convs] == [k[:-7] for k, v in sd.items() if (v.dim() == 4 and not is_dw(v)) or k == "fc.weight"]       # state_dict order
+    assert [n for n, *_ in dws] == [k[:-7] for k, v in sd.items() if is_dw(v)]
+    assert ref.halves(arch) == HALVES[arch] == ref.HALVES[arch]
+    for (bf, hp), oup in zip(HALVES[arch], w[1:4]):
+        assert 2 * bf == oup and bf % 2 == 0 and hp % 32 == 0 and 0 <= hp - bf < 32
+    # the largest activation of every width is 112 x 112 x 32 elements: conv1's output at pitch 32; no stage map or branch map exceeds it
+    act = 112 * 112 * 32
+    inp_pitch, h = 32, 56
+    for bf, hp in HALVES[arch]:
+        assert h * h * max(inp_pitch, hp) <= act and (h // 2) ** 2 * 2 * hp <= act
+        inp_pitch, h = 2 * hp, h // 2
+
+
+ALL_HALVES = sorted({p for v in HALVES.values() for p in v})
+
+
+@pytest.mark.parametrize("bf,hp", ALL_HALVES)
+def test_two_half_index_map_reproduces_torchvisions_shuffle(bf, hp):
+    """out = channel_shuffle(cat(a, b), 2), torchvision's literal view(B, 2, C / 2, H, W).transpose(1, 2), stored in the two-half layout, equals
+    the engine's index rule: physical channel q, h = q // hp, j = q % hp; j >= bf is zero, else l = h bf + j comes from (l & 1 ? b : a)[l >> 1].
+    This pins the RULE and the test helper shufflenet_ref.shuffle_source, not engine code: it passes without the kernel.  The kernel is held
+    to that helper bit for bit by tests/test_gpu_shufflenet.py::test_shuffle_is_bit_exact."""
+    assert len(ALL_HALVES) == 12
+    rng = np.random.default_rng(bf * 1000 + hp)
+    a = rng.standard_normal((2, bf, 3, 5)).astype(np.float32)
+    b = rng.standard_normal((2, bf, 3, 5)).astype(np.float32)
+    want = ref.channel_shuffle(torch.cat((torch.from_numpy(a), torch.from_numpy(b)), dim=1), 2).numpy()
+    assert np.array_equal(want[:, 0::2], a) and np.array_equal(want[:, 1::2], b)      # out'[2i] = out[i], out'[2i + 1] = out[bf + i]
+    # restated in numpy, not through the restatement's helper
+    q = np.arange(2 * hp)
+    h, j = q // hp, q % hp
+    l = h * bf + j
+    src = np.stack([a, b])                                  # [which][n][c][y][x]
+    got = np.where((j < bf)[None, :, None, None], src[l & 1, :, np.minimum(l >> 1, bf - 1)].transpose(1, 0, 2, 3), 0.0)
+    phys = np.where(np.arange(2 * bf) < bf, np.arange(2 * bf), hp + np.arange(2 * bf) - bf)
+    assert np.array_equal(got[:, phys], want)               # the logical channels, at their physical positions
+    pads = np.setdiff1d(q, phys)
+    assert len(pads) == 2 * (hp - bf) and (got[:, pads] == 0).all()
+    which, idx = ref.shuffle_source(bf, hp)
+    assert np.array_equal(which, np.where(j < bf, l & 1, -1)) and np.array_equal(idx[j < bf], (l >> 1)[j < bf])
+    assert np.array_equal(ref.two_half_index(bf, hp), phys)
+    # a unit of 8 output channels starts on an even logical channel, so its sources are 4 consecutive elements of a and 4 of b
+    for q0 in range(0, 2 * hp, 8):
+        if j[q0] < bf:
+            assert l[q0] % 2 == 0 and (q0 // hp) == ((q0 + 7) // hp)
+    assert ((bf // 2) % 4 == 0) == (bf % 8 == 0)            # the second half's sources are 8-byte aligned only then
+
+
+# ------------------------------------------------------------------------------------------------
+# the restatement against an independent nn.Module build
+# ------------------------------------------------------------------------------------------------
+class _InvertedResidual(nn.Module):
+    def __init__(self, inp, oup, stride):
+        super().__init__()
+        self.stride = stride
+        bf = oup // 2
+        if stride > 1:
+            self.branch1 = nn.Sequential(nn.Conv2d(inp, inp, 3, stride, 1, groups=inp, bias=False), nn.BatchNorm2d(inp),
+                                         nn.Conv2d(inp, bf, 1, 1, 0, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True))
+        else:
+            self.branch1 = nn.Sequential()
+        self.branch2 = nn.Sequential(nn.Conv2d(inp if stride > 1 else bf, bf, 1, 1, 0, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True),
+                                     nn.Conv2d(bf, bf, 3, stride, 1, groups=bf, bias=False), nn.BatchNorm2d(bf),
+                                     nn.Conv2d(bf, bf, 1, 1, 0, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        if self.stride == 1:
+            x1, x2 = x.chunk(2, dim=1)
+            out = torch.cat((x1, self.branch2(x2)), dim=1)
+        else:
+            out = torch.cat((self.branch1(x), self.branch2(x)), dim=1)
+        b, c, h, w = out.shape
+        return out.view(b, 2, c // 2, h, w).transpose(1, 2).contiguous().view(b, c, h, w)
+
+
+class _ShuffleNetV2(nn.Module):
+    """torchvision's module tree (same names, so load_state_dict(strict=True) is the check of the key set), written independently of
+    shufflenet_ref."""
+
+    def __init__(self, w):
+        super().__init__()
+        self.conv1 = nn.Sequential(nn.Conv2d(3, w[0], 3, 2, 1, bias=False), nn.BatchNorm2d(w[0]), nn.ReLU(inplace=True))
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        inp = w[0]
+        for name, reps, oup in zip(("stage2", "stage3", "stage4"), (4, 8, 4), w[1:4]):
+            seq = [_InvertedResidual(inp, oup, 2)] + [_InvertedResidual(oup, oup, 1) for _ in range(reps - 1)]
+            setattr(self, name, nn.Sequential(*seq))
+            inp = oup
+        self.conv5 = nn.Sequential(nn.Conv2d(inp, w[4], 1, 1, 0, bias=False), nn.BatchNorm2d(w[4]), nn.ReLU(inplace=True))
+        self.fc = nn.Linear(w[4], 1000)
+
+    def forward(self, x):
+        x = self.maxpool(self.conv1(x))
+        x = self.conv5(self.stage4(self.stage3(self.stage2(x))))
+        return self.fc(x.mean([2, 3]))
+
+
+@pytest.mark.parametrize("arch,dtype", [("shufflenet_v2_x1_0", torch.float64), ("shufflenet_v2_x0_5", torch.float32),
+                                        ("shufflenet_v2_x1_5", torch.float64), ("shufflenet_v2_x2_0", torch.float64)])
+def test_restatement_matches_an_nn_module_build(arch, dtype):
+    sd = synth.make_state_dict(arch)
+    model = _ShuffleNetV2(WIDTHS[arch])
+    model.load_state_dict(sd, strict=True)
+    model.to(dtype).eval()
+    x = scorer.to_tensor_normalize(synth.make_images(2)[1])[None].to(dtype)
+    with torch.no_grad():
+        want = model(x)
+        got = ref.forward(ref.cast(sd, dtype), arch, x)
+    assert tuple(got.shape) == (1, 1000)
+    scale = want.abs().max().item()
+    err = (got - want).abs().max().item()
+    print("%s %s: max |d| %.3e of logit scale %.2f" % (arch, dtype, err, scale))
+    assert scale > 1.0 and err <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("arch", ref.E2E_ARCHS)
+def test_synthetic_statistics_on_the_rows_the_gpu_test_scores(arch, golden_dir):
+    """The map RMS neither grows nor dies over the 16 blocks, the depthwise layers' linear outputs really leave [0, 6] (what separates the new
+    kernel from MobileNetV2's), and on EVERY mask row of shufflenet_ref.E2E_CASES the softmax peak lies in [0.05, 0.95] and the fp64 top-two
+    logit margin is >= 1e-3: the GPU test then compares the argmax of every row, none excluded."""
+    assert ref.E2E_ARCHS == ("shufflenet_v2_x1_0", "shufflenet_v2_x0_5")
+    sd = synth.make_state_dict(arch)
+    sd64 = ref.cast(sd, torch.float64)
+    for kind, m, seed in ref.E2E_CASES:
+        img, seg = ref.e2e_inputs(golden_dir, kind)
+        x = scorer.to_tensor_normalize(img)
+        trace = []
+        with torch.no_grad():
+            logits = ref.forward(sd64, arch, x[None].double(), trace)
+            pooled = trace[1][1]
+            t = F.relu(ref.bn(sd64, "stage2.0.branch2.1", F.conv2d(pooled, sd64["stage2.0.branch2.0.weight"])))
+            lin = ref.bn(sd64, "stage2.0.branch2.4", F.conv2d(t, sd64["stage2.0.branch2.3.weight"], None, 2, 1, 1, t.shape[1]))
+        assert lin.min().item() < -0.1 and lin.max().item() > 0.1                # no activation behind the depthwise BatchNorm
+        assert len(trace) == 2 + 16 + 1
+        rms = [t.pow(2).mean().sqrt().item() for name, t in trace if name.startswith("stage")]
+        assert len(rms) == 16 and min(rms) > 0.2 and max(rms) < 2.5, (min(rms), max(rms))
+        p = F.softmax(logits, 1)[0]
+        label = int(p.argmax())
+        assert 0.05 <= p.max().item() <= 0.95
+        onoff = synth.random_onoff(m, len(np.unique(seg)), seed=seed)
+        s64, logits64 = ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
+        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
+        top2 = np.sort(logits64, axis=1)[:, -2:]
+        gap = top2[:, 1] - top2[:, 0]
+        print("%s %s: map rms %.3f .. %.3f, unmasked peak %.4f, %d rows: peaks %.4f .. %.4f, scores %.4f .. %.4f, smallest fp64 top-two margin %.4f"
+              % (arch, kind, min(rms), max(rms), p.max().item(), m, peaks.min(), peaks.max(), s64.min(), s64.max(), gap.min()))
+        assert peaks.min() >= 0.05 and peaks.max() <= 0.95       # every row, none excluded
+        assert gap.min() >= 1e-3
+        assert s64.max() - s64.min() > 0.01                      # the masks move the score
+
+
+# ------------------------------------------------------------------------------------------------
+# the C-ABI surface
+# ------------------------------------------------------------------------------------------------
+def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
+    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
+        header = fh.read()
+    assert "#define MPX_ARCH_SHUFFLENET 9000" in header
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint %s\(" % name, header), name
+        assert name in _lib.SIGNATURES, name
+        assert getattr(mpx_lib, name) is not None
+    # every entry refuses a null engine before it touches a device
+    i = C.c_int()
+    assert mpx_lib.mpx_shuffle2_concat(None, None, None, 64, None, None, 64, None, None, 1, 7, 58, 64, None) == -1
+    assert mpx_lib.mpx_dwconv3x3_bn(None, None, None, None, None, None, None, None, 1, 7, 64, 1, None) == -1
+    assert mpx_lib.mpx_dwconv_layout(None, 0, C.byref(i), C.byref(i), C.byref(i)) == -1
+    assert mpx_lib.mpx_num_shuffles(None) == -1
+    assert mpx_lib.mpx_shuffle_info(None, 0, C.byref(i), C.byref(i), C.byref(i), C.byref(i), C.byref(i)) == -1
+    assert mpx_lib.mpx_conv_in_slice(None, 0, C.byref(i), C.byref(i), C.byref(i), C.byref(i)) == -1
+    assert mpx_lib.mpx_profile_collect_shuffle(None, None, None, None, None, None, None, None, None) == -1
+    # the depthwise descriptor keeps its layout: the linear flag has a getter of its own
+    assert C.sizeof(_lib.DwConvDesc) == 48 + 48 + 5 * 4
+
+
+@pytest.mark.parametrize("arch_id", [9000, 9001, 9004, 9006, 9011, 9025, 9999])
+def test_unknown_shufflenet_id_is_refused(mpx_lib, arch_id):
+    """mpx_create rejects the id before it touches a device."""
+    h = C.c_void_p()
+    assert mpx_lib.mpx_create(arch_id, 4, 0, C.byref(h)) == -1 and not h.value

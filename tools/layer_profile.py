@@ -157,8 +157,10 @@ if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + 
         print("%3dx%-3d C %4d..%-4d x%-3d %8.3f ms %9.1f MB %7.2f TB/s" % (hw, hw, c0, c1, n, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
     print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
           % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
-if eng.dwconvs:   # MobileNetV2: the depthwise 3x3 + BN + ReLU6 launches between the 1x1 convs; bytes = split-fp16 read (each input element once) + written
-    print("-- depthwise 3x3 + BN + ReLU6 (mpx_dwconv3x3_bn_relu6: one launch per depthwise layer); bytes = split-fp16 planes read + written, pitch channels per pixel --")
+shuffle_net = arch.startswith("shufflenet")
+if eng.dwconvs:   # MobileNetV2 / ShuffleNetV2: the depthwise 3x3 + BN (+ ReLU6) launches between the 1x1 convs; bytes = split-fp16 read (each input element once) + written
+    print("-- depthwise 3x3 + BN%s (%s: one launch per depthwise layer); bytes = split-fp16 planes read + written, pitch channels per pixel --"
+          % (("", "mpx_dwconv3x3_bn") if shuffle_net else (" + ReLU6", "mpx_dwconv3x3_bn_relu6")))
     tot_dw = tot_bytes = 0.0
     for dd, ms in zip(eng.dwconvs, prof["per_dw_ms"]):
         ms /= reps
@@ -168,13 +170,35 @@ if eng.dwconvs:   # MobileNetV2: the depthwise 3x3 + BN + ReLU6 launches between
         tot_bytes += nbytes
         print("%-22s C %4d pitch %4d s%d %3dx%-3d -> %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (
             dd.name.decode(), dd.channels, dd.pitch, dd.stride, dd.hin, dd.hin, ho, ho, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
-    pool_ms = prof["ms"]["pool"] / reps - tot_dw
+    tot_sh = 0.0
+    if shuffle_net:     # the channel shuffles: bytes = the bf real channels of a and of b read + the 2 hp channels of y written, split-fp16
+        import ctypes as C
+        print("-- channel shuffles (mpx_shuffle2_concat: one launch per block); bytes = 2 bf channels read + 2 hp written per pixel, split-fp16 --")
+        sh_bytes = 0.0
+        for k, ms in enumerate(prof["per_shuffle_ms"]):
+            ms /= reps
+            v = [C.c_int() for _ in range(5)]
+            eng._lib.mpx_shuffle_info(eng._h, k, *[C.byref(q) for q in v])
+            side, bf, hp, a_pitch, b_pitch = (q.value for q in v)
+            nbytes = batch * 4.0 * side * side * (2 * bf + 2 * hp)
+            tot_sh += ms
+            sh_bytes += nbytes
+            print("shuffle %2d  bf %3d hp %3d a_pitch %4d b_pitch %4d %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (
+                k, bf, hp, a_pitch, b_pitch, side, side, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+        print("shuffles total %.3f ms/batch, %.1f MB -> %.2f TB/s" % (tot_sh, sh_bytes / 1e6, sh_bytes / max(tot_sh, 1e-9) / 1e9))
+    pool_ms = prof["ms"]["pool"] / reps - tot_dw - tot_sh
     allms = sum(prof["ms"].values()) / reps
-    print("depthwise total %.3f ms/batch, %.1f MB -> %.2f TB/s; clamped global pool %.3f ms/batch; conv total %.3f ms/batch"
-          % (tot_dw, tot_bytes / 1e6, tot_bytes / max(tot_dw, 1e-9) / 1e9, pool_ms, tot))
-    print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise %.1f %%, staging (K0) %.1f %%, global pool %.1f %%, head %.1f %%"
-          % (100 * tot / allms, 100 * tot_dw / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms,
-             100 * prof["ms"]["head"] / reps / allms))
+    if shuffle_net:
+        print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise (%d launches) %.1f %%, shuffles (%d launches) %.1f %%, staging (K0) %.1f %%, "
+              "max pool + global pool %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
+              % (100 * tot / allms, len(eng.dwconvs), 100 * tot_dw / allms, len(prof["per_shuffle_ms"]), 100 * tot_sh / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms,
+                 100 * pool_ms / allms, 100 * prof["ms"]["head"] / reps / allms, allms, sum(prof["launches"].values()) // reps - 1))
+    print("depthwise total %.3f ms/batch, %.1f MB -> %.2f TB/s; %s %.3f ms/batch; conv total %.3f ms/batch"
+          % (tot_dw, tot_bytes / 1e6, tot_bytes / max(tot_dw, 1e-9) / 1e9, "max pool + global pool" if shuffle_net else "clamped global pool", pool_ms, tot))
+    if not shuffle_net:
+        print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise %.1f %%, staging (K0) %.1f %%, global pool %.1f %%, head %.1f %%"
+              % (100 * tot / allms, 100 * tot_dw / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms,
+                 100 * prof["ms"]["head"] / reps / allms))
 if arch.startswith("squeezenet"):     # SqueezeNet: the Fire modules' convs by their bytes (they are memory-bound), and the average pool that writes the logits
     import ctypes as C
     print("-- Fire modules: split-fp16 bytes read (the input map once) + written per launch; the expand convs write their half of the concatenation --")

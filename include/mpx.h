@@ -151,6 +151,29 @@ enum {
  * Input-slice, output-slice and padded layers run the generic tiles 0, 1, 2, 4 and 7 only.  conv1 and the pool keep 24 channels at pitch 32.
  * Three activation buffers of 112 * 112 * 32 elements per image (conv1's output) for every width: 5.7 MB per slot with the staging.  It
  * stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
+ * -- or torchvision's EfficientNet-B0 (5.3 M parameters, 0.39 GMAC per forward), the one EfficientNet whose native resolution is 224 x 224:
+ *   MPX_ARCH_EFFICIENTNET + 0     efficientnet_b0; every other id in [10000, 11000) is MPX_E_ARG
+ * An EfficientNet-B0 engine runs features.0 (3 -> 32, 3x3 stride 2 pad 1, reading the padded NHWC4 staging: k_packed = 96) + BN + SiLU, 16
+ * MBConv blocks features.S.B over seven stages (expand ratio, kernel, stride, in, out, blocks) = (1,3,1,32,16,1) (6,3,2,16,24,2)
+ * (6,5,2,24,40,2) (6,3,2,40,80,3) (6,5,1,80,112,3) (6,5,2,112,192,4) (6,3,1,192,320,1), features.8 (320 -> 1280, 1x1) + BN + SiLU,
+ * mpx_global_avgpool_silu and classifier.1 (Linear(1280, 1000), the logit layer and last conv entry).  A block with input cin and expanded
+ * width e = t * cin is 1x1 expand + BN + SiLU (absent when t = 1), depthwise k x k + BN + SiLU (mpx_dwconv_bn_act), SqueezeExcitation(e, q =
+ * max(1, cin / 4)) (mpx_se_gate, then mpx_se_scale in place), 1x1 project + BN without activation, plus the block input when stride is 1 and
+ * cin == out (the residual operand of the project conv; nothing behind the add).  34 entries in the conv list ("features.0.0",
+ * "features.1.0.block.2.0", "features.2.0.block.0.0", "features.2.0.block.3.0", ..., "features.8.0", "classifier.1"), 16 depthwise layers
+ * ("features.1.0.block.0.0", "features.2.0.block.1.0", ...; mpx_dwconv_shape reports kernel size and activations) and 16 SE layers
+ * ("features.1.0.block.1", "features.2.0.block.2", ...; mpx_num_se / mpx_se_info / mpx_load_se).  mpx_forward launches the stem, per block
+ * expand (absent in 1.0), depthwise, gate, scale, project, then features.8, the SiLU pool, classifier.1 and the head: 34 + 16 + 16 + 16 + 1 + 1.
+ * THE SiLU BELONGS TO THE CONSUMER.  The MFMA conv kernels' epilogues know ReLU only, and SiLU cannot be had from ReLU by a clamp: a conv that
+ * torchvision follows with SiLU (the stem, every expand conv, features.8) has relu = 0 in its descriptor and stores bn(conv(x)); its one
+ * consumer takes silu(x) = x / (1 + expf(-x)) as it loads -- a depthwise layer (act_in = 1) or the SiLU global pool.  mpx_conv_bn_act on such
+ * a layer therefore returns the PRE-ACTIVATION bn(conv(x)), not silu(.); mpx_conv_consumer_act says which layers these are and mpx_conv_desc
+ * keeps its layout.  The depthwise kernel applies its own SiLU in its epilogue.
+ * Channel counts 16, 24, 40, 80, 112, 144 and 240 are stored with a pitch of 32, 32, 64, 96, 128, 160 and 256 (exact zeros in the padded
+ * channels, as MobileNetV2); such layers run the generic tiles only.
+ * Three activation buffers of 112 * 112 * 96 elements per image (features.2.0's expanded map, MobileNetV2's size: 14.45 MB) plus the
+ * staging (0.85 MB) and the SE gates (f32[1152], 4.6 KB): 15.3 MB per slot.  It stages through mpx_mask_apply_normalize only: the stem-table
+ * and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -164,6 +187,7 @@ enum {
 #define MPX_ARCH_SQUEEZENET 7000
 #define MPX_ARCH_GOOGLENET 8000
 #define MPX_ARCH_SHUFFLENET 9000
+#define MPX_ARCH_EFFICIENTNET 10000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -189,7 +213,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet and the ShuffleNetV2s, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, the ShuffleNetV2s and EfficientNet-B0, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -213,6 +237,10 @@ int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
  * layer reads a WHOLE two-half stage map (cin = 2 bf logical channels at pitch 2 hp): its weight column of logical channel l sits at l
  * (l < bf) or hp + l - bf; 0, 0 for every other layer.  Any pointer may be NULL. */
 int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp);
+/* The activation torchvision puts behind layer i that the layer itself does NOT apply because its one consumer takes it on load: *act = 0
+ * none (every layer of every other network; ReLU6's clamp is reported by mpx_dwconv_desc.clamp_in), 1 SiLU (an EfficientNet-B0 engine's stem,
+ * expand convs and features.8: mpx_conv_bn_act returns bn(conv(x)) there). */
+int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
  * w = conv weight OIHW [cout][cin][k][k]; conv_bias = the conv's own bias [cout] or NULL (torchvision's ResNet convs have
@@ -222,7 +250,7 @@ int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* 
  * uploads synchronously. */
 int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv_bias, const float* gamma,
                          const float* beta, const float* mean, const float* var, float eps);
-int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has weights (and every stand-alone BatchNorm its vectors) */
+int mpx_weights_complete(const mpx_engine* h);     /* 1 when every layer has weights (and every stand-alone BatchNorm, depthwise and SE layer its vectors) */
 
 /* ---- stand-alone BatchNorms (DenseNet) -------------------------------------------------------
  * Norm k in [0, mpx_num_norms): the BatchNorm2d modules that precede their conv, in forward order ("features.denseblock1.denselayer1.norm1",
@@ -243,8 +271,8 @@ int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float
 /* ---- depthwise layers (MobileNetV2) ------------------------------------------------------------
  * Depthwise layer k in [0, mpx_num_dwconvs): the 3x3 depthwise convs in forward order ("features.1.conv.0.0", "features.2.conv.1.0", ...);
  * 0 on every other architecture.  mpx_load_dwconv takes the HOST f32 tensors of torchvision's state_dict -- w = <name>.weight
- * [channels][1][3][3], gamma / beta / mean / var = <bn_name>.weight / .bias / .running_mean / .running_var [channels] -- and uploads,
- * synchronously, the fp32 tap-major weights [9][pitch] (tap = ky * 3 + kx) and the vectors scale = gamma / sqrt(var + eps), shift = beta -
+ * [channels][1][3][3] ([channels][1][5][5] on a 5x5 layer: mpx_dwconv_shape), gamma / beta / mean / var = <bn_name>.weight / .bias / .running_mean / .running_var [channels] -- and uploads,
+ * synchronously, the fp32 tap-major weights [ksize^2][pitch] (tap = ky * ksize + kx; ksize = 3, or 5: mpx_dwconv_shape) and the vectors scale = gamma / sqrt(var + eps), shift = beta -
  * mean * scale [pitch] (computed in double, rounded once, as mpx_load_norm), zeros on channels [channels, pitch).  mpx_dwconv_params returns
  * their DEV pointers (what mpx_forward hands to the kernel).  mpx_weights_complete and mpx_forward count the depthwise layers. */
 typedef struct mpx_dwconv_desc {
@@ -265,6 +293,30 @@ int mpx_dwconv_params(const mpx_engine* h, int k, const float** w, const float**
  * *hp non-zero when its planes are a whole two-half stage map (channels = 2 bf at pitch 2 hp: channel c >= bf loads to hp + c - bf).  Any
  * pointer may be NULL. */
 int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp);
+/* More of what mpx_dwconv_desc has no field for: *ksize = 3 or 5 (5 on an EfficientNet-B0 engine's stages 3, 5 and 6: mpx_load_dwconv takes
+ * [channels][1][5][5] weights there and uploads [25][pitch], tap = ky * 5 + kx; pad is (ksize - 1) / 2), *act_in / *act_out = 1 where the
+ * layer takes SiLU on load / applies SiLU behind its BatchNorm (every depthwise layer of an EfficientNet-B0 engine, whose clamp_in is 0:
+ * mpx_forward runs mpx_dwconv_bn_act on it), 0 / 0 on every other engine.  Any pointer may be NULL. */
+int mpx_dwconv_shape(const mpx_engine* h, int k, int* ksize, int* act_in, int* act_out);
+
+/* ---- Squeeze-and-Excitation layers (EfficientNet-B0) --------------------------------------------
+ * SE layer k in [0, mpx_num_se): the SqueezeExcitation modules in forward order ("features.1.0.block.1", "features.2.0.block.2", ...); 0 on
+ * every other architecture.  mpx_load_se takes the HOST f32 tensors of torchvision's state_dict -- w1 = <name>.fc1.weight [q][channels][1][1],
+ * b1 = <name>.fc1.bias [q], w2 = <name>.fc2.weight [channels][q][1][1], b2 = <name>.fc2.bias [channels] -- and uploads, synchronously, the
+ * operands of mpx_se_gate: w1 as [q][pitch] with zero columns on channels [channels, pitch), w2 TRANSPOSED to [q][pitch] (w2[j][c] =
+ * fc2.weight[c][j]) with zeros on the pads, b1 [q], b2 [pitch] with -inf on the pads (their gates come out as exact zeros).  mpx_se_params
+ * returns their DEV pointers (what mpx_forward hands to the kernel).  mpx_weights_complete and mpx_forward count the SE layers. */
+typedef struct mpx_se_desc {
+    char name[48];       /* torchvision state_dict prefix of the SqueezeExcitation module ("features.3.1.block.2") */
+    int32_t channels;    /* e: the expanded width it gates */
+    int32_t pitch;       /* channels per pixel of the planes it reads and scales (e rounded up to a multiple of 32) */
+    int32_t q;           /* squeeze width: max(1, block input channels / 4) */
+    int32_t hw;          /* side of the square map it pools and scales at 224x224 input */
+} mpx_se_desc;
+int mpx_num_se(const mpx_engine* h);
+int mpx_se_info(const mpx_engine* h, int k, mpx_se_desc* out);
+int mpx_load_se(mpx_engine* h, int k, const float* w1, const float* b1, const float* w2, const float* b2);
+int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1, const float** w2, const float** b2);
 
 /* Kernel variant of layer i (tuning / test hook; results are identical up to fp32 summation order).  The ids are exactly the
  * kernels some layer class runs by default:
@@ -515,6 +567,44 @@ int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, 
 int mpx_dwconv3x3_bn(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
                      void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, void* stream);
 
+/* ---- EfficientNet-B0: depthwise k x k conv (k = 3 or 5, pad (k - 1) / 2, stride 1 or 2) + BatchNorm with SiLU on either side ---------------
+ * replaces: `Conv2dNormActivation(expanded, expanded, kernel_size=k, stride=stride, groups=expanded, activation_layer=nn.SiLU)` of torchvision's
+ *           efficientnet.py MBConv AND the nn.SiLU of the Conv2dNormActivation in front of it (the expand conv; the stem for block 1.0),
+ *           inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * in_hi|lo:  DEV planes [B][hin][hin][pitch]; out_hi|lo: DEV planes [B][ho][ho][pitch], ho = (hin - 1) / stride + 1, every channel of the
+ *            pitch written.  w: DEV f32[ksize^2][pitch], tap-major (tap = ky * ksize + kx); scale / shift: DEV f32[pitch] (mpx_dwconv_params).
+ * Per output element, in fp32: x = hi + lo (exact); a = act_in ? silu(x) : x with silu(x) = x / (1 + expf(-x)), the accurate expf and an IEEE
+ * division; acc = 0, then acc = fma(w[tap], a[tap], acc) over the taps inside the map in row-major order; v = fl(fl(scale * acc) + shift);
+ * act_out ? silu(v) : v; the re-split.  Channels with zero weights, scale and shift come out as exact zeros.  Act codes: 0 none, 1 SiLU.
+ * MPX_E_ARG for ksize not 3 or 5, stride not 1 or 2, an act code other than 0 / 1, a pitch that is not a positive multiple of 8, a null or
+ * misaligned (16 bytes) pointer, B <= 0 or hin <= 0.  The planes must not overlap.  Offsets are 64-bit.  ONE launch. */
+int mpx_dwconv_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
+                      void* out_hi, void* out_lo, int B, int hin, int pitch, int ksize, int stride, int act_in, int act_out, void* stream);
+
+/* ---- EfficientNet-B0: the Squeeze-and-Excitation gate, gate = sigmoid(fc2(silu(fc1(mean over the map)))) per image ----------------------
+ * replaces: `scale = self.avgpool(input); scale = self.fc1(scale); scale = self.activation(scale); scale = self.fc2(scale); return
+ *           self.scale_activation(scale)` (torchvision ops/misc.py SqueezeExcitation._scale with activation SiLU) inside
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * in_hi|lo: DEV planes [B][hw][pitch] (hw = PIXELS per image); gate: DEV f32[B][pitch].  w1: DEV f32[q][pitch]; b1: DEV f32[q]; w2: DEV
+ * f32[q][pitch], j-major (w2[j][c] multiplies s1[j] into channel c); b2: DEV f32[pitch] (mpx_se_params).  Per image, in fp32:
+ *     pooled[c] = (sum over the hw pixels of hi + lo) / hw;  s1[j] = silu(b1[j] + sum_c w1[j][c] pooled[c]), j < q;
+ *     gate[c] = 1 / (1 + expf(-(b2[c] + sum_j w2[j][c] s1[j]))).
+ * A pad channel carries zero w1 / w2 columns and b2 = -inf: its gate is 1 / (1 + inf) = 0 exactly.  One workgroup per image; every summation
+ * order is a fixed function of (hw, pitch, q) -- never of B, the grid or timing, and there are no atomics --, so an image's gate has the same
+ * bits alone and at any position of any batch.  hw >= 1, q >= 1 (no multiple of anything).  MPX_E_ARG for a null or misaligned (16 bytes)
+ * pointer, B <= 0, hw <= 0, q <= 0, a pitch that is not a positive multiple of 8, or (pitch, q) whose LDS need passes 64 KB.  ONE launch. */
+int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2,
+                float* gate, int B, int hw, int pitch, int q, void* stream);
+
+/* ---- EfficientNet-B0: the Squeeze-and-Excitation scale, out = split(fl((hi + lo) * gate[n][c])) ---------------------------------------
+ * replaces: `return scale * input` of torchvision's SqueezeExcitation.forward inside model(masked_img_tensor)
+ *           (generate_gp_training_data_imagenet.py:246).
+ * in_hi|lo, out_hi|lo: DEV planes [B][hw][pitch] (hw = pixels per image); gate: DEV f32[B][pitch].  Element-wise: one fp32 multiply of the
+ * exact hi + lo, the re-split.  out may be in (mpx_forward scales in place); any other overlap is undefined.  Same argument discipline as
+ * mpx_se_gate.  ONE launch. */
+int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
+                 void* stream);
+
 /* ---- ShuffleNetV2: channel_shuffle(cat(a, b), 2) into the two-half layout ------------------------------------------------------
  * replaces: `torch.cat((x1, self.branch2(x2)), dim=1)` / `torch.cat((self.branch1(x), self.branch2(x)), dim=1)` and `channel_shuffle(out, 2)`
  *           of torchvision's shufflenetv2.py InvertedResidual.forward inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
@@ -537,6 +627,13 @@ int mpx_shuffle_info(const mpx_engine* h, int k, int* hw, int* bf, int* hp, int*
  *           mpx_global_avgpool is unchanged.  c a multiple of 8. */
 int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
                               int c, void* stream);
+
+/* ---- EfficientNet-B0: K4a with the SiLU of its producer: global average pool of silu(x), [B][hw][c] -> [B][c].
+ * replaces: the nn.SiLU of features.8 and `self.avgpool(x)` (AdaptiveAvgPool2d(1)) of torchvision's EfficientNet inside
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  silu(hi + lo) summed in pixel order in fp32, one division
+ *           by hw, the re-split; mpx_global_avgpool is unchanged.  c a multiple of 8, planes 16-byte aligned. */
+int mpx_global_avgpool_silu(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw, int c,
+                            void* stream);
 
 /* ---- SqueezeNet: the global average pool that ends the network, [B][hw][c] split planes -> fp32 logits [B][out_pitch].
  * replaces: `nn.AdaptiveAvgPool2d((1, 1))` of torchvision's SqueezeNet classifier and the torch.flatten behind it inside
@@ -622,7 +719,12 @@ int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long laun
  * of the forward. */
 int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                                 double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms);
-/* Algorithmic FLOPs (2*MAC, convs + depthwise convs + fc) of one masked forward. */
+/* The same with EfficientNet-B0's split of kind 2: per_se_gate_ms / per_se_scale_ms (HOST f64[mpx_num_se] each, may be NULL) get the gate and
+ * the scale launch of every SE layer. */
+int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                           double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                           double* per_se_scale_ms);
+/* Algorithmic FLOPs (2*MAC, convs + depthwise convs + the SE layers' two FCs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 
 #ifdef __cplusplus

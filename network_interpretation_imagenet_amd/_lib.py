@@ -40,6 +40,10 @@ class DwConvDesc(C.Structure):
                 ("stride", C.c_int32), ("hin", C.c_int32), ("clamp_in", C.c_int32)]
 
 
+class SeDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 48), ("channels", C.c_int32), ("pitch", C.c_int32), ("q", C.c_int32), ("hw", C.c_int32)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -121,6 +125,18 @@ SIGNATURES = {
     "mpx_conv_in_slice": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mpx_profile_collect_shuffle": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # EfficientNet-B0: the depthwise k x k + BN kernel with SiLU on either side, the SE layers, their gate and scale kernels, the SiLU pool
+    "mpx_conv_consumer_act": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    "mpx_dwconv_shape": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mpx_dwconv_bn_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mpx_num_se": (_i, [_vp]),
+    "mpx_se_info": (_i, [_vp, _i, C.POINTER(SeDesc)]),
+    "mpx_load_se": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "mpx_se_params": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mpx_se_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpx_se_scale": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_global_avgpool_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_profile_collect_se": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 8),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 #include "mpx_fire.h"
 #include "mpx_pool3c.h"
 #include "mpx_shuffle.h"
+#include "mpx_mbconv.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,10 +40,12 @@ constexpr size_t kAlexActElemsPerImage = 55 * 55 * 64;  // AlexNet: the output o
 constexpr size_t kMobileActElemsPerImage = 112 * 112 * 96;   // MobileNetV2: features.2's expanded map, 1.5 x kActElemsPerImage
 constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: the output of features.0 (the largest concatenation is 55 * 55 * 128)
 constexpr size_t kShuffleActElemsPerImage = 112 * 112 * 32; // ShuffleNetV2: conv1's output, 24 channels at pitch 32 (= x2_0's stage2.0.branch2.0 map, 56 * 56 * 128)
+constexpr size_t kEffActElemsPerImage = 112 * 112 * 96;  // EfficientNet-B0: features.2.0's expanded map (= MobileNetV2's buffer)
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
-              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14 };
+              OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14,
+              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -54,6 +57,7 @@ struct ConvLayer {
     bool loaded = false;
     bool is_fc = false;
     bool is_stem = false;
+    int consumer_act = 0;   // 1: torchvision follows this conv with SiLU, which its one consumer takes on load (mpx_mbconv.h); relu is 0 then
     bool has_bias = false;  // the reference module is nn.Conv2d(bias=True) (small nets): state_dict has <name>.bias
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
     int cout_store = 0;     // channels per pixel of the output planes (row pitch and store bound)
@@ -123,15 +127,30 @@ struct DwLayer {
     mpx_dwconv_desc d;
     bool linear = false;    // ShuffleNetV2: BatchNorm only, no activation and no clamp (dwconv3x3_bn_kernel, mpx_shuffle.h)
     int in_bf = 0, in_hp = 0;   // its planes are a two-half stage map (channels = 2 * in_bf, pitch = 2 * in_hp): logical channel c loads to its physical position
+    int ksize = 3;          // 3 or 5 (EfficientNet-B0): weights [ksize * ksize][pitch]
+    bool mb = false;        // EfficientNet-B0: dwconv_bn_act_kernel (mpx_mbconv.h) with SiLU on load (act_in) and in the epilogue (act_out)
+    int act_in = 0, act_out = 0;
     float* w = nullptr;
     float* scale = nullptr;
     float* shift = nullptr;
     bool loaded = false;
 };
 
+// A Squeeze-and-Excitation layer (EfficientNet-B0; mpx_mbconv.h): fp32 fc weights and biases of its own, laid out for se_gate_kernel
+struct SeLayer {
+    mpx_se_desc d;
+    float* w1 = nullptr;    // [q][pitch]
+    float* b1 = nullptr;    // [q]
+    float* w2 = nullptr;    // [q][pitch], j-major
+    float* b2 = nullptr;    // [pitch], -inf on the pad channels
+    bool loaded = false;
+};
+
 constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
 constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max pool k (mpx_engine::pools3c) kProfSubPool3c - k
 constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shuffle k (mpx_engine::shuffles) kProfSubShuffle - k
+constexpr int kProfSubSeGate = -3000000;    // ... of EfficientNet's SE layer k (mpx_engine::ses): its gate launch kProfSubSeGate - k,
+constexpr int kProfSubSeScale = -4000000;   //     its scale launch kProfSubSeScale - k
 
 // A channel shuffle of the op list (ShuffleNetV2; mpx_shuffle.h): a = Op::in at a_pitch, b = Op::res advanced by b_offset at b_pitch
 struct ShuffleOp {
@@ -171,6 +190,10 @@ struct mpx_engine {
     std::vector<ClipPool> pools3c;  // its clipped-window 3x3 max pools in forward order
     bool shufflenet = false;        // torchvision ShuffleNetV2: split / shuffle blocks over three activation buffers, staged through K0 only
     std::vector<ShuffleOp> shuffles;    // its channel shuffles in forward order
+    bool efficientnet = false;      // torchvision EfficientNet-B0: MBConv blocks with SE over three activation buffers, staged through K0 only
+    std::vector<SeLayer> ses;       // its Squeeze-and-Excitation layers in forward order
+    float* se_gate = nullptr;       // f32[max_batch][se_pitch_max]: the gates of the SE layer in flight
+    int se_pitch_max = 0;
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -271,6 +294,7 @@ int build_topology_mobilenet(mpx_engine* h);
 int build_topology_squeezenet(mpx_engine* h);
 int build_topology_googlenet(mpx_engine* h);
 int build_topology_shufflenet(mpx_engine* h);
+int build_topology_efficientnet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -282,6 +306,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_SQUEEZENET && h->arch < MPX_ARCH_SQUEEZENET + 1000) return build_topology_squeezenet(h);
     if (h->arch >= MPX_ARCH_GOOGLENET && h->arch < MPX_ARCH_GOOGLENET + 1000) return build_topology_googlenet(h);
     if (h->arch >= MPX_ARCH_SHUFFLENET && h->arch < MPX_ARCH_SHUFFLENET + 1000) return build_topology_shufflenet(h);
+    if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     switch (h->arch) {
@@ -1251,6 +1276,104 @@ int build_topology_shufflenet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision EfficientNet-B0 (efficientnet.py, eval mode): features.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN + SiLU, 16 MBConv blocks
+// features.S.B over seven stages (t, k, s, in, out, n) = (1,3,1,32,16,1) (6,3,2,16,24,2) (6,5,2,24,40,2) (6,3,2,40,80,3) (6,5,1,80,112,3)
+// (6,5,2,112,192,4) (6,3,1,192,320,1), features.8 = conv 320 -> 1280 1x1 + BN + SiLU, global average pool, classifier.1 = Linear(1280, 1000).
+// A block with input cin and e = t * cin is `block` = 1x1 expand + BN + SiLU (absent when t = 1: every index below is one less), depthwise
+// k x k (pad (k - 1) / 2, the block's stride) + BN + SiLU, SqueezeExcitation(e, max(1, cin / 4)) -- gate = sigmoid(fc2(silu(fc1(avgpool(x))))),
+// fc1 / fc2 1x1 convs WITH bias --, 1x1 project + BN without activation; with stride 1 and cin == out the block input is added, nothing
+// behind the add.  No conv but the SE's has a bias.  StochasticDepth and Dropout are the identity in eval.  BatchNorm eps 1e-5.
+// SiLU: the MFMA convs run WITHOUT an activation (relu = 0) and the consumer takes silu(x) as it loads (ConvLayer::consumer_act; mpx_mbconv.h):
+// every such conv is read by exactly one depthwise layer (act_in) or by the SiLU global pool (OP_AVGPOOLSILU).
+// Channels 16, 24, 40, 80, 112, 144 and 240 are stored with a pitch of 32, 32, 64, 96, 128, 160 and 256 (zero weight columns, zero scale and
+// shift: exact zeros, as MobileNetV2); those layers run the generic tiles only, and default_tile's rules give every one of them a generic tile.
+// Op list, 84 launches: stem | 16 x (expand, depthwise, SE gate, SE scale in place, project) without 1.0's expand | features.8 |
+// OP_AVGPOOLSILU | classifier.1 | OP_HEAD.  34 conv entries, 16 depthwise, 16 SE layers.
+// Buffers: three of 112 * 112 * 96 elements per image (2.0's expanded map), as MobileNetV2: X the block input, T1 the expanded map and then
+// -- dead after the depthwise layer -- the block output, T2 the depthwise output, scaled in place.  The gates: f32[max_batch][1152].
+int build_topology_efficientnet(mpx_engine* h) {
+    if (h->arch != MPX_ARCH_EFFICIENTNET) return MPX_E_ARG;
+    h->efficientnet = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kEffActElemsPerImage;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int act,
+                        int residual, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = 0; L.d.residual = residual;
+        L.consumer_act = act;
+        L.is_fc = fc;
+        L.has_bias = fc;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
+        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
+        L.cout_store = fc ? cout : pitch_of(cout);
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
+    int c = add_conv("features.0.0", "features.0.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
+    conv_op(c, BUF_INPUT, 0, BUF_NONE);
+    int X = 0, cin = 32, hcur = 112;
+    static const int cfg[7][5] = {{1, 3, 1, 16, 1}, {6, 3, 2, 24, 2}, {6, 5, 2, 40, 2}, {6, 3, 2, 80, 3}, {6, 5, 1, 112, 3}, {6, 5, 2, 192, 4}, {6, 3, 1, 320, 1}};
+    for (int s = 0; s < 7; ++s) {
+        for (int b = 0; b < cfg[s][4]; ++b) {
+            const int t = cfg[s][0], k = cfg[s][1], stride = b == 0 ? cfg[s][2] : 1, cout = cfg[s][3], e = cin * t;
+            const bool use_res = stride == 1 && cin == cout;
+            const std::string p = "features." + std::to_string(s + 1) + "." + std::to_string(b) + ".block.";
+            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3, P = pitch_of(e);
+            if ((size_t)hcur * hcur * P > kEffActElemsPerImage) return MPX_E_INTERNAL;
+            const int hout = (hcur - 1) / stride + 1;
+            int j = 0, dw_in = X;
+            if (t != 1) {
+                c = add_conv(p + "0.0", p + "0.1", cin, e, 1, 1, 0, hcur, 1, 0, false);
+                conv_op(c, X, T1, BUF_NONE);
+                j = 1; dw_in = T1;
+            }
+            const std::string js = std::to_string(j), se = p + std::to_string(j + 1), pj = p + std::to_string(j + 2);
+            DwLayer D;
+            std::memset(&D.d, 0, sizeof D.d);
+            set_name(D.d.name, p + js + ".0");
+            set_name(D.d.bn_name, p + js + ".1");
+            D.d.channels = e; D.d.pitch = P; D.d.stride = stride; D.d.hin = hcur;
+            D.d.clamp_in = 0;
+            D.ksize = k; D.mb = true; D.act_in = 1; D.act_out = 1;      // every depthwise layer reads an MFMA conv that SiLU follows (1.0: the stem)
+            h->dws.push_back(D);
+            h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, dw_in, T2, BUF_NONE, hcur, P, BUF_NONE});
+            SeLayer E;
+            std::memset(&E.d, 0, sizeof E.d);
+            std::snprintf(E.d.name, sizeof E.d.name, "%s", se.c_str());
+            E.d.channels = e; E.d.pitch = P; E.d.q = std::max(1, cin / 4); E.d.hw = hout;
+            h->ses.push_back(E);
+            h->se_pitch_max = std::max(h->se_pitch_max, P);
+            h->ops.push_back(Op{OP_SEGATE, (int)h->ses.size() - 1, T2, BUF_NONE, BUF_NONE, hout, P, BUF_NONE});
+            h->ops.push_back(Op{OP_SESCALE, (int)h->ses.size() - 1, T2, T2, BUF_NONE, hout, P, BUF_NONE});
+            c = add_conv(pj + ".0", pj + ".1", e, cout, 1, 1, 0, hout, 0, use_res, false);
+            conv_op(c, T2, T1, use_res ? X : BUF_NONE);
+            X = T1;
+            cin = cout;
+            hcur = hout;
+        }
+    }
+    if (hcur != 7 || cin != 320) return MPX_E_INTERNAL;
+    const int T = (X + 1) % 3;
+    c = add_conv("features.8.0", "features.8.1", cin, 1280, 1, 1, 0, hcur, 1, 0, false);
+    conv_op(c, X, T, BUF_NONE);
+    h->feat = 1280;
+    h->ops.push_back(Op{OP_AVGPOOLSILU, -1, T, BUF_POOL, BUF_NONE, hcur, 1280, BUF_NONE});
+    c = add_conv("classifier.1", "", 1280, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
+    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -1945,6 +2068,41 @@ int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st, bool
     return 0;
 }
 
+// one dwconv_bn_act_kernel launch (mpx_mbconv.h); `dw` = the engine's depthwise layer it runs for (profile record), -1 from the
+// stand-alone entry.  Grid cap as launch_dwconv's run form: 8 blocks per CU at stride 1, 2 at stride 2, striding over the rest.
+int launch_mbdw(mpx_engine* h, const MbDwParams& p, int ksize, int stride, int dw, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+    const int W = stride == 1 ? 4 : 2;
+    const unsigned long long units = (unsigned long long)p.rows * (unsigned)((p.ho + W - 1) / W) * (unsigned)(p.pitch / 8);
+    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (stride == 1 ? 8 : 2));
+    if (ksize == 3 && stride == 1) hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 1>), dim3(grid), dim3(256), 0, st, p);
+    else if (ksize == 3) hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 2>), dim3(grid), dim3(256), 0, st, p);
+    else if (stride == 1) hipLaunchKernelGGL((dwconv_bn_act_kernel<5, 1>), dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((dwconv_bn_act_kernel<5, 2>), dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// dynamic LDS of one se_gate_kernel launch: part[S][pitch] | pooled[pitch] | s1[q]
+size_t se_gate_lds(int pitch, int q) { return ((size_t)se_gate_slices(pitch) * pitch + pitch + q) * sizeof(float); }
+
+// one se_gate_kernel launch, one workgroup per image; `k` = the engine's SE layer it runs for (profile record), -1 from the stand-alone entry
+int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubSeGate - k : -1);
+    hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)B), dim3(256), se_gate_lds(p.pitch, p.q), st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one se_scale_kernel launch; about 8 workgroups per CU, striding over the rest
+int launch_se_scale(mpx_engine* h, const SeScaleParams& p, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubSeScale - k : -1);
+    const unsigned grid = (unsigned)std::min<long long>((p.units + 255) / 256, (long long)h->num_cus * 8);
+    hipLaunchKernelGGL(se_scale_kernel, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 // one shuffle2_concat_kernel launch; `k` = the engine's shuffle it runs for (profile record), -1 from the stand-alone entry.  The load width
 // follows the alignment of the sources (mpx_shuffle.h): 8-byte loads when bf % 8 == 0, 2-byte loads otherwise.
 int launch_shuffle(mpx_engine* h, const ShuffleParams& p, int k, hipStream_t st) {
@@ -2104,7 +2262,10 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     }
     for (const TailBlock& tb : h->tails) wbytes += 2 * round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
     for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
-    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)9 * D.d.pitch * 4, 256) + 2 * round_up((size_t)D.d.pitch * 4, 256);
+    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256) + 2 * round_up((size_t)D.d.pitch * 4, 256);
+    for (const SeLayer& E : h->ses)
+        wbytes += 2 * round_up((size_t)E.d.q * E.d.pitch * 4, 256) + round_up((size_t)E.d.q * 4, 256) + round_up((size_t)E.d.pitch * 4, 256);
+    const size_t se_gate_bytes = round_up((size_t)max_batch * h->se_pitch_max * 4, 256);
     const size_t scratch_bytes = 4096 * sizeof(float);
     // the stem by superposition (ImageNet ResNets): pooled stem planes, fp32 stem weights + BatchNorm vectors, one image's table (worst case:
     // 49 entries per conv output pixel), the bit planes of one staging call
@@ -2121,7 +2282,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     // only ever stages through K0, stem = "conv", never pays for it)
     const size_t stemtab_bytes = 2 * stem_plane + stem_w_bytes;
     h->tab_sizes[0] = tab_int_bytes; h->tab_sizes[1] = tab_lab_bytes; h->tab_sizes[2] = tab_vec_bytes; h->tab_sizes[3] = tab_bits_bytes;
-    const size_t total = scratch_bytes + 2 * in_plane + 2 * (size_t)h->n_act_bufs * act_plane + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes;
+    const size_t total = scratch_bytes + 2 * in_plane + 2 * (size_t)h->n_act_bufs * act_plane + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes + se_gate_bytes;
     e = hipMalloc((void**)&h->arena, total);
     if (e != hipSuccess) { delete h; return (int)e; }
     h->arena_bytes = total;
@@ -2174,10 +2335,17 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
         nl.shift = (float*)take(nb);
     }
     for (DwLayer& D : h->dws) {
-        D.w = (float*)take(round_up((size_t)9 * D.d.pitch * 4, 256));
+        D.w = (float*)take(round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256));
         D.scale = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
         D.shift = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
     }
+    for (SeLayer& E : h->ses) {
+        E.w1 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
+        E.w2 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
+        E.b1 = (float*)take(round_up((size_t)E.d.q * 4, 256));
+        E.b2 = (float*)take(round_up((size_t)E.d.pitch * 4, 256));
+    }
+    if (se_gate_bytes) h->se_gate = (float*)take(se_gate_bytes);
     // the never-written borders (ImageNet) / padding channels (small nets) of the input staging must be zero, and so must
     // the pooled planes' padding channels
     e = hipMemset(h->arena, 0, scratch_bytes + 2 * in_plane);
@@ -2304,6 +2472,8 @@ int mpx_weights_complete(const mpx_engine* h) {
         if (!nl.loaded) return 0;
     for (const DwLayer& D : h->dws)
         if (!D.loaded) return 0;
+    for (const SeLayer& E : h->ses)
+        if (!E.loaded) return 0;
     return 1;
 }
 
@@ -2377,7 +2547,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet and ShuffleNetV2 stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2 and EfficientNet-B0 stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -2659,11 +2829,11 @@ int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, co
     if (k < 0 || k >= (int)h->dws.size()) return fail(h, MPX_E_ARG, "load_dwconv: bad depthwise index %d (this engine has %d)", k, (int)h->dws.size());
     DwLayer& D = h->dws[k];
     if (!w || !gamma || !beta || !mean || !var) return fail(h, MPX_E_ARG, "load_dwconv: weight or BatchNorm tensors missing for %s", D.d.name);
-    const int n = D.d.channels, pitch = D.d.pitch;
-    std::vector<float> wt((size_t)9 * pitch, 0.f), sc(pitch, 0.f), sh(pitch, 0.f);     // zeros on the padded channels
+    const int n = D.d.channels, pitch = D.d.pitch, taps = D.ksize * D.ksize;     // w: [channels][1][ksize][ksize]
+    std::vector<float> wt((size_t)taps * pitch, 0.f), sc(pitch, 0.f), sh(pitch, 0.f);     // zeros on the padded channels
     for (int c = 0; c < n; ++c) {
         const int q = D.in_hp && c >= D.in_bf ? D.in_hp + c - D.in_bf : c;      // a two-half stage map: the channel's physical position
-        for (int t = 0; t < 9; ++t) wt[(size_t)t * pitch + q] = w[(size_t)c * 9 + t];
+        for (int t = 0; t < taps; ++t) wt[(size_t)t * pitch + q] = w[(size_t)c * taps + t];
         const double s = (double)gamma[c] / std::sqrt((double)var[c] + (double)eps);
         sc[q] = (float)s;
         sh[q] = (float)((double)beta[c] - (double)mean[c] * s);
@@ -2728,6 +2898,133 @@ int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp)
     if (linear) *linear = h->dws[k].linear ? 1 : 0;
     if (bf) *bf = h->dws[k].in_bf;
     if (hp) *hp = h->dws[k].in_hp;
+    return 0;
+}
+
+int mpx_dwconv_shape(const mpx_engine* h, int k, int* ksize, int* act_in, int* act_out) {
+    if (!h || k < 0 || k >= (int)h->dws.size()) return MPX_E_ARG;
+    if (ksize) *ksize = h->dws[k].ksize;
+    if (act_in) *act_in = h->dws[k].act_in;
+    if (act_out) *act_out = h->dws[k].act_out;
+    return 0;
+}
+
+int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
+    if (!h || !act || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    *act = h->convs[i].consumer_act;
+    return 0;
+}
+
+int mpx_dwconv_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift, void* out_hi,
+                      void* out_lo, int B, int hin, int pitch, int ksize, int stride, int act_in, int act_out, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv_bn_act: null pointer");
+    if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (ksize != 3 && ksize != 5) || (stride != 1 && stride != 2) || (act_in != 0 && act_in != 1) ||
+        (act_out != 0 && act_out != 1))
+        return fail(h, MPX_E_ARG, "dwconv_bn_act: B > 0, hin > 0, pitch a positive multiple of 8, ksize 3 or 5, stride 1 or 2, act codes 0 (none) or 1 (SiLU)");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "dwconv_bn_act: every pointer must be 16-byte aligned");
+    MbDwParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.w = w; p.scale = scale; p.shift = shift;
+    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.act_in = act_in; p.act_out = act_out;
+    p.rows = (long long)B * p.ho;
+    MPX_SET_DEVICE(h);
+    return launch_mbdw(h, p, ksize, stride, -1, as_stream(stream));
+}
+
+int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                int B, int hw, int pitch, int q, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (!in_hi || !in_lo || !w1 || !b1 || !w2 || !b2 || !gate) return fail(h, MPX_E_ARG, "se_gate: null pointer");
+    if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7) || q <= 0) return fail(h, MPX_E_ARG, "se_gate: B > 0, hw > 0, pitch a positive multiple of 8, q > 0");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) || misaligned(gate))
+        return fail(h, MPX_E_ARG, "se_gate: every pointer must be 16-byte aligned");
+    if (se_gate_lds(pitch, q) > 64 * 1024) return fail(h, MPX_E_ARG, "se_gate: pitch %d and q %d need more than 64 KB of LDS", pitch, q);
+    SeGateParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo;
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.gate = gate;
+    p.hw = hw; p.pitch = pitch; p.q = q;
+    MPX_SET_DEVICE(h);
+    return launch_se_gate(h, p, B, -1, as_stream(stream));
+}
+
+int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
+                 void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (!in_hi || !in_lo || !gate || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "se_scale: null pointer");
+    if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7)) return fail(h, MPX_E_ARG, "se_scale: B > 0, hw > 0, pitch a positive multiple of 8");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(gate) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "se_scale: every pointer must be 16-byte aligned");
+    SeScaleParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.gate = gate; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.pitch = pitch;
+    p.per_image = (long long)hw * (pitch / 8);
+    p.units = (long long)B * p.per_image;
+    MPX_SET_DEVICE(h);
+    return launch_se_scale(h, p, -1, as_stream(stream));
+}
+
+int mpx_num_se(const mpx_engine* h) { return h ? (int)h->ses.size() : MPX_E_ARG; }
+
+int mpx_se_info(const mpx_engine* h, int k, mpx_se_desc* out) {
+    if (!h || !out || k < 0 || k >= (int)h->ses.size()) return MPX_E_ARG;
+    *out = h->ses[k].d;
+    return 0;
+}
+
+int mpx_load_se(mpx_engine* h, int k, const float* w1, const float* b1, const float* w2, const float* b2) {
+    if (!h) return MPX_E_ARG;
+    if (k < 0 || k >= (int)h->ses.size()) return fail(h, MPX_E_ARG, "load_se: bad SE index %d (this engine has %d)", k, (int)h->ses.size());
+    SeLayer& E = h->ses[k];
+    if (!w1 || !b1 || !w2 || !b2) return fail(h, MPX_E_ARG, "load_se: fc1 / fc2 weight or bias missing for %s", E.d.name);
+    const int n = E.d.channels, pitch = E.d.pitch, q = E.d.q;
+    // fc1.weight [q][n] -> [q][pitch] with zero columns on the pads; fc2.weight [n][q] -> j-major [q][pitch]; fc2.bias -> [pitch] with -inf on
+    // the pads, whose gates se_gate_kernel then writes as exact zeros
+    std::vector<float> a((size_t)q * pitch, 0.f), b((size_t)q * pitch, 0.f), c(pitch, -INFINITY);
+    for (int j = 0; j < q; ++j)
+        for (int ch = 0; ch < n; ++ch) {
+            a[(size_t)j * pitch + ch] = w1[(size_t)j * n + ch];
+            b[(size_t)j * pitch + ch] = w2[(size_t)ch * q + j];
+        }
+    for (int ch = 0; ch < n; ++ch) c[ch] = b2[ch];
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(E.w1, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(E.w2, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(E.b1, b1, (size_t)q * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(E.b2, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+    E.loaded = true;
+    return 0;
+}
+
+int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1, const float** w2, const float** b2) {
+    if (!h || !w1 || !b1 || !w2 || !b2 || k < 0 || k >= (int)h->ses.size()) return MPX_E_ARG;
+    *w1 = h->ses[k].w1;
+    *b1 = h->ses[k].b1;
+    *w2 = h->ses[k].w2;
+    *b2 = h->ses[k].b2;
+    return 0;
+}
+
+int mpx_global_avgpool_silu(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw, int c, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
+        return fail(h, MPX_E_ARG, "global_avgpool_silu: bad arguments (c multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "global_avgpool_silu: the planes must be 16-byte aligned");
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1);
+    const int total = B * (c / 8);
+    hipLaunchKernelGGL(global_avgpool_silu_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
+                       (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
+    MPX_HIP(h, hipGetLastError());
     return 0;
 }
 
@@ -2928,6 +3225,16 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             }
             case OP_DWCONV: {
                 const DwLayer& D = h->dws[o.conv];
+                if (D.mb) {
+                    MbDwParams q;
+                    std::memset(&q, 0, sizeof q);
+                    q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
+                    q.w = D.w; q.scale = D.scale; q.shift = D.shift;
+                    q.hin = D.d.hin; q.ho = (D.d.hin - 1) / D.d.stride + 1; q.pitch = D.d.pitch; q.act_in = D.act_in; q.act_out = D.act_out;
+                    q.rows = (long long)B * q.ho;
+                    rc = launch_mbdw(h, q, D.ksize, D.d.stride, o.conv, as_stream(stream));
+                    break;
+                }
                 DwParams p;
                 std::memset(&p, 0, sizeof p);
                 p.x_hi = hi(o.in); p.x_lo = lo(o.in); p.y_hi = hi(o.out); p.y_lo = lo(o.out);
@@ -2937,6 +3244,28 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 rc = launch_dwconv(h, p, o.conv, as_stream(stream), D.linear);
                 break;
             }
+            case OP_SEGATE: {
+                const SeLayer& E = h->ses[o.conv];
+                SeGateParams p;
+                std::memset(&p, 0, sizeof p);
+                p.x_hi = hi(o.in); p.x_lo = lo(o.in);
+                p.w1 = E.w1; p.b1 = E.b1; p.w2 = E.w2; p.b2 = E.b2; p.gate = h->se_gate;
+                p.hw = E.d.hw * E.d.hw; p.pitch = E.d.pitch; p.q = E.d.q;
+                rc = launch_se_gate(h, p, B, o.conv, as_stream(stream));
+                break;
+            }
+            case OP_SESCALE: {
+                const SeLayer& E = h->ses[o.conv];
+                SeScaleParams p;
+                std::memset(&p, 0, sizeof p);
+                p.x_hi = hi(o.in); p.x_lo = lo(o.in); p.gate = h->se_gate; p.y_hi = hi(o.out); p.y_lo = lo(o.out);
+                p.pitch = E.d.pitch;
+                p.per_image = (long long)E.d.hw * E.d.hw * (E.d.pitch / 8);
+                p.units = (long long)B * p.per_image;
+                rc = launch_se_scale(h, p, o.conv, as_stream(stream));
+                break;
+            }
+            case OP_AVGPOOLSILU: rc = mpx_global_avgpool_silu(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
             case OP_SHUFFLE: {
                 const ShuffleOp& S = h->shuffles[o.conv];
                 ShuffleParams p;
@@ -3110,6 +3439,13 @@ int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long laun
 
 int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                                 double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms) {
+    return mpx_profile_collect_se(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                  nullptr, nullptr);
+}
+
+int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                           double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                           double* per_se_scale_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -3128,6 +3464,10 @@ int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long l
             per_clip_pool_ms[kProfSubPool3c - r.sub] += ms;
         if (per_shuffle_ms && r.kind == 2 && r.sub <= kProfSubShuffle && kProfSubShuffle - r.sub < (int)h->shuffles.size())
             per_shuffle_ms[kProfSubShuffle - r.sub] += ms;
+        if (per_se_gate_ms && r.kind == 2 && r.sub <= kProfSubSeGate && kProfSubSeGate - r.sub < (int)h->ses.size())
+            per_se_gate_ms[kProfSubSeGate - r.sub] += ms;
+        if (per_se_scale_ms && r.kind == 2 && r.sub <= kProfSubSeScale && kProfSubSeScale - r.sub < (int)h->ses.size())
+            per_se_scale_ms[kProfSubSeScale - r.sub] += ms;
     }
     h->prof_used = 0;
     return 0;
@@ -3149,8 +3489,9 @@ double mpx_flops_per_forward(const mpx_engine* h) {
         macs += (double)L.d.hout * L.d.hout * L.d.cout * L.d.cin * L.d.ksize * L.d.ksize;
     for (const DwLayer& D : h->dws) {
         const int ho = (D.d.hin - 1) / D.d.stride + 1;
-        macs += (double)ho * ho * D.d.channels * 9;
+        macs += (double)ho * ho * D.d.channels * D.ksize * D.ksize;
     }
+    for (const SeLayer& E : h->ses) macs += 2.0 * E.d.channels * E.d.q;
     return 2.0 * macs;
 }
 

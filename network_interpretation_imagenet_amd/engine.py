@@ -35,6 +35,7 @@ ARCH_IDS["squeezenet1_1"] = 7011  # torchvision's SqueezeNet 1.1 (MPX_ARCH_SQUEE
 ARCH_IDS["googlenet"] = 8000      # torchvision's GoogLeNet without the aux classifiers (MPX_ARCH_GOOGLENET); inception_v3 is not served
 # torchvision's ShuffleNetV2 family (MPX_ARCH_SHUFFLENET + 10 x the width multiplier)
 ARCH_IDS.update({"shufflenet_v2_x0_5": 9005, "shufflenet_v2_x1_0": 9010, "shufflenet_v2_x1_5": 9015, "shufflenet_v2_x2_0": 9020})
+ARCH_IDS["efficientnet_b0"] = 10000     # torchvision's EfficientNet-B0 (MPX_ARCH_EFFICIENTNET + 0); B1 .. B7 (trained at 240 and more) are not served
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -127,6 +128,9 @@ class MaskedForwardEngine:
         A ShuffleNetV2 slot holds 5.7 MB for every width -- three 112x112x32 split-fp16 activation buffers (conv1's output, 24 channels at
         pitch 32; a block's input, its branch2 map and the shuffled output: 4.8 MB) and the input staging -- and keeps the default of 512
         (2.9 GB).
+        An EfficientNet-B0 slot holds 15.3 MB -- three 112x112x96 split-fp16 activation buffers (features.2.0's expanded map, MobileNetV2's
+        size: a block's input, its expanded map and the depthwise output the SE layer scales in place: 14.5 MB), the input staging and the
+        SE gates -- and keeps the default of 512 (7.8 GB).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -137,7 +141,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet and ShuffleNetV2s and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -172,6 +176,16 @@ class MaskedForwardEngine:
             dd = _lib.DwConvDesc()
             _lib.check(h, self._lib.mpx_dwconv_info(h, k, C.byref(dd)), "mpx_dwconv_info")
             self.dwconvs.append(dd)
+        self.dw_ksizes = []     # their kernel sizes (3; 5 on EfficientNet-B0's stages 3, 5 and 6): what mpx_dwconv_desc has no field for
+        for k in range(len(self.dwconvs)):
+            ks = C.c_int()
+            _lib.check(h, self._lib.mpx_dwconv_shape(h, k, C.byref(ks), None, None), "mpx_dwconv_shape")
+            self.dw_ksizes.append(int(ks.value))
+        self.ses = []           # the Squeeze-and-Excitation layers (EfficientNet-B0), a list of their own as well
+        for k in range(self._lib.mpx_num_se(h)):
+            sd_ = _lib.SeDesc()
+            _lib.check(h, self._lib.mpx_se_info(h, k, C.byref(sd_)), "mpx_se_info")
+            self.ses.append(sd_)
         self.flops_per_forward = float(self._lib.mpx_flops_per_forward(h))
         self.num_cus = int(self._lib.mpx_num_cus(h))        # what the persistent kernels' grids are sized from (whole_round_batch)
         self._mean, self._std = _f3(MEAN), _f3(STD)
@@ -193,9 +207,9 @@ class MaskedForwardEngine:
     @property
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
-        which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s
-        and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet"))
+        which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s,
+        EfficientNet-B0 and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -241,20 +255,22 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=None, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet / ShuffleNetV2 state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet / ShuffleNetV2 / EfficientNet-B0 state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`, the `aux1.` / `aux2.` classifiers
         of torchvision's GoogLeNet checkpoint) are ignored.  `eps`: the BatchNorms' epsilon; None = default_bn_eps(arch), torchvision's value
         for the architecture (1e-5; 1e-3 for googlenet).  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
         ("layer1.1.conv3", "fc") to (re)load instead of every layer -- the engine rebuilds whatever it derived from a reloaded
         layer (the K-concatenated conv3 | downsample planes, a block tail's permuted copy).  MobileNetV2's and ShuffleNetV2's depthwise layers
         load with the convs, and `only` takes their names ("features.2.conv.1.0", "stage2.0.branch1.0") too.  A ShuffleNetV2 state_dict loads
-        as saved: the engine places the columns of a layer that reads a two-half stage map itself."""
+        as saved: the engine places the columns of a layer that reads a two-half stage map itself.  EfficientNet-B0's depthwise and
+        Squeeze-and-Excitation layers load with the convs too (fc1 / fc2 weight and bias of every `features.S.B.block.J`), and `only` takes
+        the SE layers' names as well."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         if eps is None:
             eps = default_bn_eps(self.arch)
         if only is not None:
             only = set(only)
-            unknown = only - {d.name.decode() for d in self.layers} - {d.name.decode() for d in self.dwconvs}
+            unknown = only - {d.name.decode() for d in self.layers} - {d.name.decode() for d in self.dwconvs} - {d.name.decode() for d in self.ses}
             if unknown:
                 raise KeyError("no such conv layers: %s" % sorted(unknown))
 
@@ -293,9 +309,16 @@ class MaskedForwardEngine:
             name, bn = dd.name.decode(), dd.bn_name.decode()
             if only is not None and name not in only:
                 continue
-            t = [get(name + ".weight", (dd.channels, 1, 3, 3))]
+            t = [get(name + ".weight", (dd.channels, 1, self.dw_ksizes[k], self.dw_ksizes[k]))]
             t += [get("%s.%s" % (bn, key), (dd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
             _lib.check(self._h, self._lib.mpx_load_dwconv(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_dwconv(%s)" % name)
+        for k, se in enumerate(self.ses):
+            name = se.name.decode()
+            if only is not None and name not in only:
+                continue
+            t = [get(name + ".fc1.weight", (se.q, se.channels, 1, 1)), get(name + ".fc1.bias", (se.q,)),
+                 get(name + ".fc2.weight", (se.channels, se.q, 1, 1)), get(name + ".fc2.bias", (se.channels,))]
+            _lib.check(self._h, self._lib.mpx_load_se(self._h, k, *[_ptr(v) for v in t]), "mpx_load_se(%s)" % name)
         if only is None:        # the stand-alone BatchNorms belong to no conv: a full load brings them all
             for k, nd in enumerate(self.norms):
                 name = nd.name.decode()
@@ -743,7 +766,8 @@ class MaskedForwardEngine:
         last call.  per_norm_ms (one entry per stand-alone BatchNorm: its concat-append + BN + ReLU launch) and avgpool2_ms (the
         transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture.  'per_dw_ms'
         (one entry per depthwise layer) is the same split on a MobileNetV2 engine, 'per_clip_pool_ms' (one entry per clipped 3x3 max pool,
-        mpx_clip_pool_info) on a GoogLeNet engine, 'per_shuffle_ms' (one entry per channel shuffle, mpx_shuffle_info) on a ShuffleNetV2 engine."""
+        mpx_clip_pool_info) on a GoogLeNet engine, 'per_shuffle_ms' (one entry per channel shuffle, mpx_shuffle_info) on a ShuffleNetV2 engine,
+        'per_se_gate_ms' / 'per_se_scale_ms' (one entry per SE layer: its gate and its scale launch) on an EfficientNet-B0 engine."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
@@ -754,8 +778,11 @@ class MaskedForwardEngine:
         per_cp = (C.c_double * max(1, n_cp))()
         n_sh = int(self._lib.mpx_num_shuffles(self._h))
         per_sh = (C.c_double * max(1, n_sh))()
-        _lib.check(self._h, self._lib.mpx_profile_collect_shuffle(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh), "mpx_profile_collect_shuffle")
+        per_sg = (C.c_double * max(1, len(self.ses)))()
+        per_ss = (C.c_double * max(1, len(self.ses)))()
+        _lib.check(self._h, self._lib.mpx_profile_collect_se(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh, per_sg, per_ss), "mpx_profile_collect_se")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
                 "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
-                "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp], "per_shuffle_ms": list(per_sh)[:n_sh]}
+                "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp], "per_shuffle_ms": list(per_sh)[:n_sh],
+                "per_se_gate_ms": list(per_sg)[:len(self.ses)], "per_se_scale_ms": list(per_ss)[:len(self.ses)]}

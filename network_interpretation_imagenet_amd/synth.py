@@ -363,10 +363,88 @@ def make_shufflenet_state_dict(arch, seed=7):
     return sd
 
 
+# torchvision efficientnet.py, efficientnet_b0: (expand ratio t, kernel k, stride of the first block s, in, out, blocks n) of stages 1 .. 7
+EFFICIENTNET_B0_CFG = ((1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3), (6, 5, 1, 80, 112, 3),
+                       (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1))
+# SiLU is not homogeneous (silu(x) ~ x / 2 near 0, ~ relu(x) far from it) and no BatchNorm here renormalises (running statistics near 0 / 1), so
+# at small pre-activations a heavily masked image's trunk decays block after block against the unmasked image's, and with the common BatchNorm
+# draws the pooled features of the scored rows spread over a factor of ten: no classifier gain puts every row's softmax peak into [0.05, 0.95].
+# Two things keep the rows together.  The gains keep the pre-activations at a standard deviation of 4 to 6, where SiLU is close to
+# homogeneous, and the project gain takes the factor off again.  And a project BatchNorm's beta is N(0, EFFICIENTNET_PROJ_BETA) instead of
+# N(0, 0.05): an input-independent floor under the trunk of every block, as a trained network's biases are, which a dark (masked) image cannot
+# fall below.  Surveyed on the CPU in fp64 on the 28 rows tests/efficientnet_ref.E2E_CASES scores (felzenszwalb / grid picture): trunk RMS
+# 0.42 .. 0.73 / 0.67 .. 0.84 over the 16 blocks, pooled-feature RMS of the rows 0.52 .. 0.88 / 0.58 .. 0.91 (unmasked 1.25 / 2.03), unmasked
+# softmax peak 0.79 / 0.68, rows' peaks 0.129 .. 0.383 / 0.108 .. 0.346, top-two logit gaps >= 0.033 / 0.0086, scores 0.019 .. 0.38 / 0.0026
+# .. 0.069.  The trunk's scale goes with a high power of the project gain: 0.18 lets it decay to the floor (every row the same features),
+# 0.24 saturates the softmax.
+EFFICIENTNET_ACT_GAIN = 4.0     # gamma factor of the BatchNorm of the stem, of every expand conv and of features.8 (SiLU follows)
+EFFICIENTNET_DW_GAIN = 2.0      # ... of a depthwise layer's BatchNorm (SiLU follows; its input already has about twice the trunk's scale)
+EFFICIENTNET_PROJ_GAIN = 0.2    # gamma factor of a project BatchNorm (x EFFICIENTNET_RES_GAIN where the block adds its input)
+EFFICIENTNET_PROJ_BETA = 0.1    # standard deviation of a project BatchNorm's beta (x EFFICIENTNET_RES_GAIN where the block adds its input)
+EFFICIENTNET_RES_GAIN = 0.35
+EFFICIENTNET_SE_GAIN = 4.0      # fc2 is N(0, sqrt(EFFICIENTNET_SE_GAIN / q)): the gates spread over (0, 1) instead of sitting at 0.5
+EFFICIENTNET_FC_GAIN = 5.0
+
+
+def make_efficientnet_state_dict(seed=7):
+    """OrderedDict with the key set, order and shapes of torchvision's efficientnet_b0 (models.efficientnet_b0().state_dict(): features.0.{0.weight,
+    1.*}, per block features.S.B.block.{0.0.weight, 0.1.* -- the expand conv, absent in stage 1, whose indices are one less --, 1.0.weight, 1.1.*,
+    2.fc1.weight, 2.fc1.bias, 2.fc2.weight, 2.fc2.bias, 3.0.weight, 3.1.*}, features.8.{0.weight, 1.*}, classifier.1.weight / .bias; every
+    BatchNorm with its num_batches_tracked; only the SE layers' fc1 / fc2 have a bias): 5,288,548 parameters.
+    Draws: convs that SiLU follows are He-normal (1x1 and stem N(0, sqrt(2 / (k*k*cin))), depthwise N(0, sqrt(2 / k^2))) and their BatchNorm's
+    gamma is U(0.9, 1.1) x EFFICIENTNET_ACT_GAIN, (x EFFICIENTNET_DW_GAIN behind a depthwise conv), so that pre-activations have a standard deviation of 4 to 6
+    (the comment above the constants has the reason); an SE layer's fc1 is N(0, sqrt(2 / e)) with bias N(0, 0.1) and its fc2 N(0, sqrt(EFFICIENTNET_SE_GAIN / q)) with bias
+    N(0, 0.5), which spreads the gates over (0, 1); a project conv (linear) is N(0, sqrt(1 / e)) with gamma x EFFICIENTNET_PROJ_GAIN and
+    beta N(0, EFFICIENTNET_PROJ_BETA), both x EFFICIENTNET_RES_GAIN more where the block adds its input, so that the trunk neither grows nor dies through the 9 residual adds
+    (tests/test_efficientnet_cpu.py asserts the bounds, and that SiLU and the gates move the scores of the rows the GPU test scores)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def bn(prefix, c, factor, beta=0.0):
+        _bn(sd, prefix, c, g, last=factor)
+        if beta:
+            sd[prefix + ".bias"] = torch.randn(c, generator=g) * beta
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    def conv(name, cin, cout, k, gain, groups=1):
+        std = (gain / (k * k * cin // groups)) ** 0.5
+        sd[name + ".weight"] = torch.randn(cout, cin // groups, k, k, generator=g) * std
+
+    conv("features.0.0", 3, 32, 3, 2.0)
+    bn("features.0.1", 32, EFFICIENTNET_ACT_GAIN)
+    for s, (t, k, _st, cin, cout, n) in enumerate(EFFICIENTNET_B0_CFG):
+        for b in range(n):
+            e, q = cin * t, max(1, cin // 4)
+            p = "features.%d.%d.block." % (s + 1, b)
+            j = 0
+            if t != 1:
+                conv(p + "0.0", cin, e, 1, 2.0)
+                bn(p + "0.1", e, EFFICIENTNET_ACT_GAIN)
+                j = 1
+            conv(p + "%d.0" % j, e, e, k, 2.0, groups=e)
+            bn(p + "%d.1" % j, e, EFFICIENTNET_DW_GAIN)
+            se = p + "%d" % (j + 1)
+            sd[se + ".fc1.weight"] = torch.randn(q, e, 1, 1, generator=g) * (2.0 / e) ** 0.5
+            sd[se + ".fc1.bias"] = torch.randn(q, generator=g) * 0.1
+            sd[se + ".fc2.weight"] = torch.randn(e, q, 1, 1, generator=g) * (EFFICIENTNET_SE_GAIN / q) ** 0.5
+            sd[se + ".fc2.bias"] = torch.randn(e, generator=g) * 0.5
+            conv(p + "%d.0" % (j + 2), e, cout, 1, 1.0)
+            bn(p + "%d.1" % (j + 2), cout, EFFICIENTNET_PROJ_GAIN * (EFFICIENTNET_RES_GAIN if (b > 0) else 1.0),
+               EFFICIENTNET_PROJ_BETA * (EFFICIENTNET_RES_GAIN if (b > 0) else 1.0))
+            cin = cout
+    conv("features.8.0", 320, 1280, 1, 2.0)
+    bn("features.8.1", 1280, EFFICIENTNET_ACT_GAIN)
+    sd["classifier.1.weight"] = torch.randn(1000, 1280, generator=g) * (EFFICIENTNET_FC_GAIN / 1280 ** 0.5)
+    sd["classifier.1.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict) key set."""
+    if arch == "efficientnet_b0":
+        return make_efficientnet_state_dict(seed)
     if arch in SHUFFLENET_WIDTHS:
         return make_shufflenet_state_dict(arch, seed)
     if arch == "googlenet":

@@ -158,7 +158,44 @@ if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + 
     print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
           % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
 shuffle_net = arch.startswith("shufflenet")
-if eng.dwconvs:   # MobileNetV2 / ShuffleNetV2: the depthwise 3x3 + BN (+ ReLU6) launches between the 1x1 convs; bytes = split-fp16 read (each input element once) + written
+if eng.ses:     # EfficientNet-B0: the depthwise k x k + BN + SiLU, SE gate and SE scale launches between the 1x1 convs
+    print("-- depthwise k x k + BN with SiLU on load and in the epilogue (mpx_dwconv_bn_act); bytes = split-fp16 planes read + written, pitch channels per pixel --")
+    tot_dw = dw_bytes = tot_g = g_bytes = tot_s = s_bytes = 0.0
+    by_class = {}
+    for k, (dd, ms) in enumerate(zip(eng.dwconvs, prof["per_dw_ms"])):
+        ms /= reps
+        ho = (dd.hin - 1) // dd.stride + 1
+        nbytes = batch * 4.0 * dd.pitch * (dd.hin * dd.hin + ho * ho)
+        tot_dw += ms
+        dw_bytes += nbytes
+        a = by_class.setdefault((eng.dw_ksizes[k], dd.stride), [0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += ms
+        a[2] += nbytes
+        print("%-24s C %4d pitch %4d k%d s%d %3dx%-3d -> %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (
+            dd.name.decode(), dd.channels, dd.pitch, eng.dw_ksizes[k], dd.stride, dd.hin, dd.hin, ho, ho, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    for (ks, st), (n, ms, nbytes) in sorted(by_class.items()):
+        print("depthwise %dx%d stride %d x%-2d %9.3f ms %8.1f MB %7.2f TB/s" % (ks, ks, st, n, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    print("-- SE gate (mpx_se_gate: pool + fc1 + fc2, one workgroup per image; bytes = the map read once) and SE scale (mpx_se_scale, in place; bytes = the map read + written) --")
+    for se, gms, sms in zip(eng.ses, prof["per_se_gate_ms"], prof["per_se_scale_ms"]):
+        gms /= reps
+        sms /= reps
+        gb = batch * 4.0 * se.pitch * se.hw * se.hw
+        tot_g += gms
+        g_bytes += gb
+        tot_s += sms
+        s_bytes += 2 * gb
+        print("%-22s C %4d pitch %4d q %2d %3dx%-3d gate %8.3f ms %8.1f MB %6.2f TB/s   scale %8.3f ms %8.1f MB %6.2f TB/s" % (
+            se.name.decode(), se.channels, se.pitch, se.q, se.hw, se.hw, gms, gb / 1e6, gb / max(gms, 1e-9) / 1e9, sms, 2 * gb / 1e6, 2 * gb / max(sms, 1e-9) / 1e9))
+    pool_ms = prof["ms"]["pool"] / reps - tot_dw - tot_g - tot_s
+    allms = sum(prof["ms"].values()) / reps
+    print("depthwise total %.3f ms/batch, %.1f MB -> %.2f TB/s; SE gates %.3f ms/batch -> %.2f TB/s; SE scales %.3f ms/batch -> %.2f TB/s; SiLU global pool %.3f ms/batch; conv total %.3f ms/batch"
+          % (tot_dw, dw_bytes / 1e6, dw_bytes / max(tot_dw, 1e-9) / 1e9, tot_g, g_bytes / max(tot_g, 1e-9) / 1e9, tot_s, s_bytes / max(tot_s, 1e-9) / 1e9, pool_ms, tot))
+    print("share of the forward by op class: conv (MFMA) %.1f %%, depthwise (%d launches) %.1f %%, SE gate (%d) %.1f %%, SE scale (%d) %.1f %%, staging (K0) %.1f %%, "
+          "global pool %.1f %%, head %.1f %% of %.3f ms/batch"
+          % (100 * tot / allms, len(eng.dwconvs), 100 * tot_dw / allms, len(eng.ses), 100 * tot_g / allms, len(eng.ses), 100 * tot_s / allms,
+             100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms, 100 * prof["ms"]["head"] / reps / allms, allms))
+elif eng.dwconvs:   # MobileNetV2 / ShuffleNetV2: the depthwise 3x3 + BN (+ ReLU6) launches between the 1x1 convs; bytes = split-fp16 read (each input element once) + written
     print("-- depthwise 3x3 + BN%s (%s: one launch per depthwise layer); bytes = split-fp16 planes read + written, pitch channels per pixel --"
           % (("", "mpx_dwconv3x3_bn") if shuffle_net else (" + ReLU6", "mpx_dwconv3x3_bn_relu6")))
     tot_dw = tot_bytes = 0.0
@@ -296,7 +333,8 @@ if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_
         print("  %s%-16s + %s%s + %-16s %8.3f ms" % ((names[c2 - 1] + " + ") if ds >= 0 else "", names[c2], names[c3],
                                                       (" + " + names[ds]) if ds >= 0 else "", names[n1], prof["per_conv_ms"][c2] / reps))
 layer1 = sum(ms for d, ms in zip(eng.layers, prof["per_conv_ms"]) if d.name.startswith(b"layer1.") or d.name == b"layer2.0.conv1") / reps
-print("layer1 (+ layer2.0.conv1): %.3f ms/batch" % layer1)
+if not eng.ses:     # (a ResNet's line; an EfficientNet engine has no layer1)
+    print("layer1 (+ layer2.0.conv1): %.3f ms/batch" % layer1)
 allfl = eng.flops_per_forward * batch
 print("conv total %.3f ms/batch -> %.1f TFLOP/s algorithmic; other kinds ms/batch: %s" % (
     tot, allfl / tot / 1e9, {k: round(v / reps, 3) for k, v in prof["ms"].items()}))

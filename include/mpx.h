@@ -421,7 +421,8 @@ int mpx_mask_apply_minmax(mpx_engine* h, const float* img_f32_chw, const int32_t
                           int M, int S, int slot0, float* out_f32_nchw, void* stream);
 
 /* ---- DownsampleB (models/resnet.py:64-74): AvgPool2d(2) on the identity + zero channels; planes
- * [B][hin][hin][cin_p] -> [B][hin/2][hin/2][cout_p] (channel counts as stored: multiples of 8, cout_p >= cin_p). */
+ * [B][hin][hin][cin_p] -> [B][hin/2][hin/2][cout_p] (channel counts as stored: multiples of 8, cout_p >= cin_p).
+ * Output channels [cin_p, cout_p) are exact zeros in both planes.  MPX_E_ARG for planes that are not 16-byte aligned. */
 int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B,
                      int hin, int cin_p, int cout_p, void* stream);
 
@@ -483,13 +484,16 @@ int mpx_num_bottleneck_tails(const mpx_engine* h);
 /* layer indices of tail k: its conv2, conv3, downsample conv (-1 if none) and the following block's conv1; any pointer may be NULL */
 int mpx_bottleneck_tail_info(const mpx_engine* h, int k, int* conv2, int* conv3, int* downsample, int* next_conv1);
 
-/* ---- K3: maxpool 3x3 s2 p1 (nn.MaxPool2d inside the same forward), NHWC split planes ------ */
+/* ---- K3: maxpool 3x3 s2 p1 (nn.MaxPool2d inside the same forward), NHWC split planes ------
+ * Taps outside the map are left out (-inf padding), so the merged output equals F.max_pool2d(merged, 3, 2, 1) for any sign.
+ * hin even, c a multiple of 8.  MPX_E_ARG for planes that are not 16-byte aligned. */
 int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                      void* out_lo, int B, int hin, int c, void* stream);
 
 /* ---- K3 of the VGG networks: maxpool 2x2 s2 (nn.MaxPool2d(2, 2)), NHWC split planes [B][hin][hin][c] -> [B][hin/2][hin/2][c].
  * replaces: every "M" of torchvision's VGG cfgs inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
- * Bit-exact: each output (hi, lo) is the pair of the input element with the largest hi + lo.  hin even, c a multiple of 8. */
+ * Bit-exact: each output (hi, lo) is the pair of the input element with the largest hi + lo.  hin even, c a multiple of 8.
+ * MPX_E_ARG for planes that are not 16-byte aligned. */
 int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                      void* out_lo, int B, int hin, int c, void* stream);
 
@@ -498,7 +502,8 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
  * replaces: the three MaxPool2d(kernel_size=3, stride=2) of torchvision's AlexNet inside model(masked_img_tensor)
  *           (generate_gp_training_data_imagenet.py:246).
  * Bit-exact for any sign: each output (hi, lo) is the pair of the window's element with the largest hi + lo, the first in row-major
- * order on a tie.  MPX_E_ARG for hin < 3, an even hin (floor mode is not part of the contract) and c not a multiple of 8. */
+ * order on a tie.  MPX_E_ARG for hin < 3, an even hin (floor mode is not part of the contract), c not a multiple of 8 and planes that
+ * are not 16-byte aligned. */
 int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                        void* out_lo, int B, int hin, int c, void* stream);
 
@@ -539,8 +544,8 @@ int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo
 
 /* ---- DenseNet transitions: average pool 2x2 s2 (nn.AvgPool2d(2, 2)), NHWC split planes [B][hin][hin][c] -> [B][hin/2][hin/2][c].
  * replaces: `pool` of torchvision's _Transition inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
- * Each output is split(0.25 * (((x00 + x01) + x10) + x11)) of the merged taps in fp32.  MPX_E_ARG for hin odd or <= 0 and c not a
- * positive multiple of 8. */
+ * Each output is split(0.25 * (((x00 + x01) + x10) + x11)) of the merged taps in fp32.  MPX_E_ARG for hin odd or <= 0, c not a
+ * positive multiple of 8 and planes that are not 16-byte aligned. */
 int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int c,
                      void* stream);
 
@@ -637,8 +642,8 @@ int mpx_global_avgpool_silu(mpx_engine* h, const void* in_hi, const void* in_lo,
 
 /* ---- SqueezeNet: the global average pool that ends the network, [B][hw][c] split planes -> fp32 logits [B][out_pitch].
  * replaces: `nn.AdaptiveAvgPool2d((1, 1))` of torchvision's SqueezeNet classifier and the torch.flatten behind it inside
- *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  Per channel: the hw values hi + lo (exact in fp32) summed in
- *           pixel order in fp32, then one correctly rounded division by hw; written as fp32, which is what mpx_head_softmax_gather reads.
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).  Per channel: the hw values hi + lo summed in fp64 (exact: every
+ *           value is a multiple of 2^-24), divided by hw in fp64 and rounded to fp32; written as fp32, which is what mpx_head_softmax_gather reads.
  *           Channels [c, out_pitch) of a row are left untouched.  mpx_global_avgpool is unchanged.
  * MPX_E_ARG for a null pointer, B <= 0, hw <= 0, c not a positive multiple of 8, out_pitch < c or planes that are not 16-byte aligned.
  * ONE launch. */
@@ -655,7 +660,9 @@ int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_l
  *           with the downsample fusion. */
 int mpx_stem_conv_maxpool(mpx_engine* h, void* out_hi, void* out_lo, int B, void* stream);
 
-/* ---- K4a: global average pool [B][hw][c] -> [B][c] (nn.AvgPool2d(7) + view) ---------------- */
+/* ---- K4a: global average pool [B][hw][c] -> [B][c] (nn.AvgPool2d(7) + view) ----------------
+ * hi + lo summed in pixel order in fp32, one division by hw, the re-split.  c a multiple of 8.  MPX_E_ARG for B * (c / 8) above
+ * 2^31 - 1 and for planes that are not 16-byte aligned. */
 int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi,
                        void* out_lo, int B, int hw, int c, void* stream);
 

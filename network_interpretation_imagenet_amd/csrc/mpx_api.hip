@@ -2654,6 +2654,8 @@ int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || cin_p <= 0 || (cin_p & 7) || cout_p < cin_p || (cout_p & 7))
         return fail(h, MPX_E_ARG, "avgpool2_pad: bad arguments (hin even, channel counts multiples of 8, cout_p >= cin_p)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "avgpool2_pad: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1);
@@ -2702,6 +2704,8 @@ int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool3x3s2: bad arguments (hin even, c multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "maxpool3x3s2: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1);
@@ -2718,6 +2722,8 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool2x2s2: bad arguments (hin even, c multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "maxpool2x2s2: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1);
@@ -2734,6 +2740,8 @@ int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin < 3 || !(hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool3x3s2p0: bad arguments (hin odd and >= 3, c multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "maxpool3x3s2p0: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1);
@@ -2774,8 +2782,10 @@ int mpx_clip_pool_info(const mpx_engine* h, int k, int* hin, int* stride, int* p
 int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hw,
                        int c, void* stream) {
     if (!h) return MPX_E_ARG;
-    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7))
+    if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool: bad arguments (c multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "global_avgpool: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1);
@@ -3114,6 +3124,8 @@ int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "avgpool2x2s2: bad arguments (hin even and > 0, c a positive multiple of 8)");
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
+        return fail(h, MPX_E_ARG, "avgpool2x2s2: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
     ProfScope ps(h, st, 2, -1, -2);

@@ -550,8 +550,10 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvPa
             for (int j = 0; j < 8; ++j) v[j] += (float)rh[it][j] + (float)rl[it][j];
         }
         if (p.relu) {
+            // nn.ReLU keeps a NaN (fmaxf would return the 0): the small networks' mask convention turns a picture with every superpixel
+            // removed into 0/0, and the reference scores it NaN with argmax 0.  Every other value, -0 included, comes out as fmaxf's.
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+            for (int j = 0; j < 8; ++j) v[j] = v[j] <= 0.f ? 0.f : v[j];
         }
         const size_t o = (size_t)pix * (SLICE ? p.y_pitch : p.cout) + co8;
         if (!SLICE && p.y_f32) {

@@ -99,16 +99,17 @@ def apply_mask(x_chw, mask_u8):
     return x_chw.numpy().copy() * mask_u8
 
 
-def score_one(sd, arch, masked_chw, label):
+def score_one(sd, arch, masked_chw, label, return_logits=False):
     """One batch-1 forward + score extraction.
-    returns (class_prob_score np.float32, pred int):
+    returns (class_prob_score np.float32, pred int), and the logits f32[1000] behind them when return_logits is set:
       bayesian_active_learning_imagenet.py:189-198  softmax(logits)[0][label]
       generate_gp_training_data_imagenet.py:248      logits.max(1)[1]"""
     t = torch.from_numpy(masked_chw[None, :, :, :])
     with torch.no_grad():
         logits = resnet_ref.forward(sd, t, arch)
         prob = F.softmax(logits, dim=1)
-    return prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
+    out = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
+    return out + (logits.numpy()[0],) if return_logits else out
 
 
 def base_prediction(sd, arch, x_chw):
@@ -118,29 +119,33 @@ def base_prediction(sd, arch, x_chw):
     return int(logits.max(1, keepdim=True)[1][0, 0])
 
 
-def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label):
+def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label, return_logits=False):
     """The reference hot loop (generate_gp_training_data_imagenet.py:221-266) with the BO
     script's score (bayesian_active_learning_imagenet.py:196-198): for each mask-vector,
     build the pixel mask, multiply into the normalised image, run ONE batch-1 forward.
-    returns (score f32[M], pred i64[M]).  No PNG writes, no visualisation copies."""
+    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set.
+    No PNG writes, no visualisation copies."""
     m = onoff.shape[0]
     score = np.zeros(m, dtype=np.float32)
     pred = np.zeros(m, dtype=np.int64)
+    rows = []
     for i in range(m):
         mask = onoff_mask_u8(segments, onoff[i])
         masked = apply_mask(x_chw, mask)
-        score[i], pred[i] = score_one(sd, arch, masked, label)
-    return score, pred
+        score[i], pred[i], row = score_one(sd, arch, masked, label, return_logits=True)
+        rows.append(row)
+    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
 
 
-def score_masks_batched(sd, arch, x_chw, segments, onoff, label, dtype=torch.float32, chunk=16):
+def score_masks_batched(sd, arch, x_chw, segments, onoff, label, dtype=torch.float32, chunk=16, return_logits=False):
     """Same result as score_masks_reference_loop, forwards run `chunk` at a time (torch CPU
     kernels are batch-invariant up to accumulation order; used for fp64 yardsticks and to
-    keep CPU test time down)."""
+    keep CPU test time down).  With return_logits also the logits [M, 1000] in `dtype`."""
     sd = resnet_ref.cast_state_dict(sd, dtype)
     m = onoff.shape[0]
     score = np.zeros(m, dtype=np.float64)
     pred = np.zeros(m, dtype=np.int64)
+    rows = []
     for s in range(0, m, chunk):
         batch = np.stack([apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
                           for i in range(s, min(m, s + chunk))])
@@ -149,7 +154,8 @@ def score_masks_batched(sd, arch, x_chw, segments, onoff, label, dtype=torch.flo
             prob = F.softmax(logits, dim=1)
         score[s:s + len(batch)] = prob[:, label].double().numpy()
         pred[s:s + len(batch)] = logits.argmax(1).numpy()
-    return score, pred
+        rows.append(logits.numpy())
+    return (score, pred, np.concatenate(rows)) if return_logits else (score, pred)
 
 
 def summed_superpixel_labels(segments, onoff, correct):

@@ -151,20 +151,22 @@ def masked_batch(x_chw, segments, onoff):
     return torch.from_numpy(np.stack([apply_mask(x_chw, onoff_mask_u8(segments, row)) for row in onoff]))
 
 
-def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label):
+def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label, return_logits=False):
     """oracle.scorer.score_masks_reference_loop with the ShuffleNetV2 forward: one batch-1 fp32 forward per mask-vector.
-    returns (score f32[M], pred i64[M])."""
+    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set."""
     sd = cast(sd, torch.float32)
     m = onoff.shape[0]
     score = np.zeros(m, dtype=np.float32)
     pred = np.zeros(m, dtype=np.int64)
+    rows = []
     for i in range(m):
         masked = apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
         with torch.no_grad():
             logits = forward(sd, arch, torch.from_numpy(masked[None]))
             prob = F.softmax(logits, dim=1)
         score[i], pred[i] = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
-    return score, pred
+        rows.append(logits.numpy()[0])
+    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
 
 
 def score_masks_fp64(sd, arch, x_chw, segments, onoff, label):

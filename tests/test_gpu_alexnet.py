@@ -24,6 +24,7 @@ import torch.nn.functional as F
 import alexnet_ref
 from network_interpretation_imagenet_amd import _lib, api, shard, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -299,6 +300,8 @@ def test_first_layer_from_stage_masks(eng, dev, golden_dir, seg_kind, m):
 # end to end
 # ------------------------------------------------------------------------------------------------
 def test_alexnet_end_to_end(eng, dev, golden_dir):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: alexnet d_L 1.62e-05, engine 3.28e-05 (2.02)."""
+    lens = LogitsLens(ARCH)
     m = 64
     img, seg = _felz(golden_dir)
     sd = synth.make_state_dict(ARCH)
@@ -307,9 +310,10 @@ def test_alexnet_end_to_end(eng, dev, golden_dir):
     assert 0.05 < prob.max() < 0.99 and (prob > 1e-3).sum() >= 3          # non-degenerate softmax
     S = len(np.unique(seg))
     onoff = synth.random_onoff(m, S, seed=11)
-    _o, score, pred = eng.score_masks(img, seg, onoff, label)
-    ref_score, ref_pred = alexnet_ref.score_masks_reference_loop(sd, x, seg, onoff, label)
+    _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+    ref_score, ref_pred, ref_logits = alexnet_ref.score_masks_reference_loop(sd, x, seg, onoff, label, return_logits=True)
     s64, logits64 = alexnet_ref.score_masks_fp64(sd, x, seg, onoff, label)
+    lens.add("felz", logits, ref_logits, logits64)
     top2 = np.sort(logits64, axis=1)[:, -2:]
     gap = top2[:, 1] - top2[:, 0]
     err_engine = float(np.abs(score.astype(np.float64) - s64).max())
@@ -327,6 +331,7 @@ def test_alexnet_end_to_end(eng, dev, golden_dir):
     assert (pred == ref_pred)[clear].all()
     p_label, _ = eng.predict(img)
     assert p_label == label
+    lens.check()
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(eng, dev, golden_dir):

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 import densenet_ref
 from network_interpretation_imagenet_amd import _lib, api, shard, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -436,6 +437,9 @@ def test_avgpool2x2s2_refuses_bad_shapes(small_engines, dev):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("arch", ARCHS)
 def test_densenet_end_to_end(mpx_lib, dev, golden_dir, arch):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: densenet121 d_L 3.99e-06, engine 6.51e-06 (1.63); densenet169 d_L 4.18e-06, engine 9.63e-06 (2.30);
+    densenet201 d_L 5.42e-06, engine 9.94e-06 (1.83)."""
+    lens = LogitsLens(arch)
     sd = synth.make_state_dict(arch)
     eng = MaskedForwardEngine(arch, device=0).load_state_dict(sd)          # the default max_batch
     try:
@@ -447,9 +451,10 @@ def test_densenet_end_to_end(mpx_lib, dev, golden_dir, arch):
             assert 0.05 <= prob.max() <= 0.85
             S = len(np.unique(seg))
             onoff = synth.random_onoff(m, S, seed=seed)
-            _o, score, pred = eng.score_masks(img, seg, onoff, label)
-            ref_score, ref_pred = densenet_ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
+            _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+            ref_score, ref_pred, ref_logits = densenet_ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
             s64, logits64 = densenet_ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
+            lens.add(kind, logits, ref_logits, logits64)
             top2 = np.sort(logits64, axis=1)[:, -2:]
             gap = top2[:, 1] - top2[:, 0]
             err_engine = float(np.abs(score.astype(np.float64) - s64).max())
@@ -464,6 +469,7 @@ def test_densenet_end_to_end(mpx_lib, dev, golden_dir, arch):
             assert (pred == logits64.argmax(1)).all() and (pred == ref_pred).all()         # every row
             p_label, _ = eng.predict(img)
             assert p_label == label
+        lens.check()
     finally:
         eng.close()
 

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 import efficientnet_ref as ref
 from network_interpretation_imagenet_amd import _lib, api, shard, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -660,6 +661,8 @@ def _round_up_one_digit(v):
 
 
 def test_efficientnet_end_to_end(engine, sd, golden_dir):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: efficientnet_b0 d_L 1.58e-05, engine 2.17e-05 (1.38)."""
+    lens = LogitsLens(ARCH)
     eng = engine
     rows = []
     for kind, m, seed in ref.E2E_CASES:
@@ -669,9 +672,10 @@ def test_efficientnet_end_to_end(engine, sd, golden_dir):
         assert 0.05 <= prob.max() <= 0.95
         S = len(np.unique(seg))
         onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred = eng.score_masks(img, seg, onoff, label)
-        ref_score, ref_pred = ref.score_masks_reference_loop(sd, x, seg, onoff, label)
+        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, x, seg, onoff, label, return_logits=True)
         s64, logits64 = ref.score_masks_fp64(sd, x, seg, onoff, label)
+        lens.add(kind, logits, ref_logits, logits64)
         top2 = np.sort(logits64, axis=1)[:, -2:]
         gap = top2[:, 1] - top2[:, 0]
         err_engine = float(np.abs(score.astype(np.float64) - s64).max())
@@ -691,6 +695,7 @@ def test_efficientnet_end_to_end(engine, sd, golden_dir):
     for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
         assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
         assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
+    lens.check()
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engine, golden_dir):

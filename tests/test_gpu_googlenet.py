@@ -27,6 +27,7 @@ import torch.nn.functional as F
 import googlenet_ref
 from network_interpretation_imagenet_amd import _lib, api, shard, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError, rank_segments
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -428,6 +429,8 @@ def _round_up_one_digit(v):
 
 
 def test_googlenet_end_to_end(engine, sd, golden_dir):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: googlenet d_L 9.11e-06, engine 1.54e-05 (1.69)."""
+    lens = LogitsLens(ARCH)
     eng = engine
     rows = []
     for kind, m, seed in googlenet_ref.E2E_CASES:
@@ -437,9 +440,10 @@ def test_googlenet_end_to_end(engine, sd, golden_dir):
         assert 0.05 <= prob.max() <= 0.95
         S = len(np.unique(seg))
         onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred = eng.score_masks(img, seg, onoff, label)
-        ref_score, ref_pred = googlenet_ref.score_masks_reference_loop(sd, x, seg, onoff, label)
+        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+        ref_score, ref_pred, ref_logits = googlenet_ref.score_masks_reference_loop(sd, x, seg, onoff, label, return_logits=True)
         s64, logits64 = googlenet_ref.score_masks_fp64(sd, x, seg, onoff, label)
+        lens.add(kind, logits, ref_logits, logits64)
         top2 = np.sort(logits64, axis=1)[:, -2:]
         gap = top2[:, 1] - top2[:, 0]
         err_engine = float(np.abs(score.astype(np.float64) - s64).max())
@@ -458,6 +462,7 @@ def test_googlenet_end_to_end(engine, sd, golden_dir):
     for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
         assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
         assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
+    lens.check()
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engine, golden_dir):

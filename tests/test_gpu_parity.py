@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from network_interpretation_imagenet_amd import _lib, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -1028,19 +1029,24 @@ def test_resnet101_vs_golden(eng101, golden_dir):
 
 
 def test_resnet18_vs_live_oracle_noise_image(eng18):
-    """Same masks through the normalised-f32 entry (what the reference's val_loader yields)."""
+    """Same masks through the normalised-f32 entry (what the reference's val_loader yields).
+    Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: resnet18 d_L 5.04e-06, engine 8.47e-06 (1.68)."""
     sd = synth.make_state_dict("resnet18")
     img = synth.make_images(3, seed=77, kind="noise")[2]
     x = scorer.to_tensor_normalize(img)
     seg = synth.grid_segments()
     onoff = masks.windows_onoff(196, [0, 1, 60, 118, 196])
     label = scorer.base_prediction(sd, "resnet18", x)
-    ref, ref_pred = scorer.score_masks_reference_loop(sd, "resnet18", x, seg, onoff, label)
-    _o, s_u8, p_u8 = eng18.score_masks(img, seg, onoff, label)
+    ref, ref_pred, ref_logits = scorer.score_masks_reference_loop(sd, "resnet18", x, seg, onoff, label, return_logits=True)
+    _o, s_u8, p_u8, l_u8 = eng18.score_masks(img, seg, onoff, label, return_logits=True)
     _o, s_f32, p_f32 = eng18.score_masks(x, seg, onoff, label)
     assert np.abs(s_u8 - ref).max() <= SCORE_TOL_TIGHT and np.abs(s_f32 - ref).max() <= SCORE_TOL_TIGHT
     assert (s_u8 == s_f32).all()                                   # both entries stage identical bits
     assert (p_u8 == ref_pred).all() and (p_f32 == ref_pred).all()
+    _s64, _p64, logits64 = scorer.score_masks_batched(sd, "resnet18", x, seg, onoff, label, dtype=torch.float64, chunk=5, return_logits=True)
+    lens = LogitsLens("resnet18")
+    lens.add("noise", l_u8, ref_logits, logits64)
+    lens.check()
 
 
 @pytest.mark.parametrize("arch", ["resnet34", "resnet50", "resnet152"])
@@ -1453,6 +1459,8 @@ def test_small_network_ops(mpx_lib, dev, golden_dir):
         S = len(np.unique(seg))
         _r, score, pred, inputs = eng.score_masks_removed(g[p + "x"], seg, np.ones((1, S), dtype=np.uint8), 0, return_inputs=True)
         assert np.isnan(inputs).all()
+        # ... and the reference scores such a picture NaN with argmax 0 (nn.ReLU keeps a NaN, torch.argmax of an all-NaN row is 0)
+        assert score.shape == (1,) and np.isnan(score).all() and (pred == 0).all()
         big = MaskedForwardEngine("resnet18", max_batch=1, device=0)
         assert big._lib.mpx_mask_apply_minmax(big._h, None, None, None, 1, 1, 0, None, None) == -2      # ImageNet engines refuse it
         assert big.input_plane_shape(1) == (1, 230, 230, 4)

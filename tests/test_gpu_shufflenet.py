@@ -29,6 +29,7 @@ import torch.nn.functional as F
 import shufflenet_ref as ref
 from network_interpretation_imagenet_amd import _lib, api, shard, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -576,6 +577,8 @@ def _round_up_one_digit(v):
 
 @pytest.mark.parametrize("arch", ref.E2E_ARCHS)
 def test_end_to_end(engines, sds, golden_dir, arch):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: shufflenet_v2_x1_0 d_L 6.14e-06, engine 1.01e-05 (1.65); shufflenet_v2_x0_5 d_L 5.61e-06, engine 9.00e-06 (1.60)."""
+    lens = LogitsLens(arch)
     eng, sd = engines[arch], sds[arch]
     rows = []
     for kind, m, seed in ref.E2E_CASES:
@@ -585,9 +588,10 @@ def test_end_to_end(engines, sds, golden_dir, arch):
         assert 0.05 <= prob.max() <= 0.95
         S = len(np.unique(seg))
         onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred = eng.score_masks(img, seg, onoff, label)
-        ref_score, ref_pred = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
+        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
         s64, logits64 = ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
+        lens.add(kind, logits, ref_logits, logits64)
         top2 = np.sort(logits64, axis=1)[:, -2:]
         gap = top2[:, 1] - top2[:, 0]
         err_engine = float(np.abs(score.astype(np.float64) - s64).max())
@@ -606,6 +610,7 @@ def test_end_to_end(engines, sds, golden_dir, arch):
     for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
         assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
         assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
+    lens.check()
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engines, golden_dir):

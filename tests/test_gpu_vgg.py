@@ -17,6 +17,7 @@ import torch.nn.functional as F
 import vgg_ref
 from network_interpretation_imagenet_amd import _lib, api, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
+from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
@@ -255,6 +256,8 @@ def test_first_layer_from_stage_masks(engines, dev, golden_dir, seg_kind, m):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("arch,m", [("vgg11", 16), ("vgg16", 20), ("vgg16_bn", 20), ("vgg19_bn", 16)])
 def test_vgg_end_to_end_vs_batch1_cpu_loop(engines, dev, golden_dir, arch, m):
+    """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: vgg11 d_L 1.64e-05, engine 3.24e-05 (1.97); vgg16 d_L 1.67e-05, engine 3.83e-05 (2.30);
+    vgg16_bn d_L 1.31e-05, engine 3.00e-05 (2.30); vgg19_bn d_L 1.26e-05, engine 3.59e-05 (2.85)."""
     g = np.load(os.path.join(golden_dir, "segments_blobs.npz"))
     img = synth.make_images(2, seed=int(g["image_seed"]))[0]
     seg = g["segments"][0].astype(np.int64)
@@ -265,14 +268,18 @@ def test_vgg_end_to_end_vs_batch1_cpu_loop(engines, dev, golden_dir, arch, m):
     S = len(np.unique(seg))
     onoff = synth.random_onoff(m, S, seed=11)
     eng = _engine(engines, arch, 100 if arch in ("vgg16", "vgg16_bn") else 32)
-    _o, score, pred = eng.score_masks(img, seg, onoff, label)
-    ref_score, ref_pred = vgg_ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
+    _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
+    ref_score, ref_pred, ref_logits = vgg_ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
     err = float(np.abs(score.astype(np.float64) - ref_score).max())
     print("%s: %d masks, label %d, max|d| %.3e, scores %.4f..%.4f" % (arch, m, label, err, ref_score.min(), ref_score.max()))
     assert err <= SCORE_TOL and err <= SCORE_TOL_TIGHT
     assert (pred == ref_pred).all()
     p_label, _ = eng.predict(img)
     assert p_label == label
+    _s64, logits64 = vgg_ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
+    lens = LogitsLens(arch)
+    lens.add("felz", logits, ref_logits, logits64)
+    lens.check()
 
 
 def test_vgg16_batch_past_4gib_planes(engines, dev):

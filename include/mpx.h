@@ -456,7 +456,8 @@ int mpx_conv_bn_act(mpx_engine* h, int i, const void* in_hi, const void* in_lo,
 int mpx_conv_dual_bn_act(mpx_engine* h, int i, const void* in_hi, const void* in_lo, const void* x_hi,
                          const void* x_lo, void* out_hi, void* out_lo, int B, void* stream);
 /* mask bit 0: the downsample fusion above and the stem + max-pool fusion below; bit 1: the block tails of layer1
- * (mpx_bottleneck_tail; needs bit 0 as well).  mpx_create starts with 3; 0 = one launch per layer. */
+ * (mpx_bottleneck_tail; needs bit 0 as well); bit 2: the pointwise tails of layer2 (mpx_pointwise_tail; needs bit 0 as well).
+ * mpx_create starts with 7; 0 = one launch per layer. */
 int mpx_set_fusion(mpx_engine* h, int mask);
 
 /* ---- the tail of a 64-channel bottleneck block in ONE launch ------------------------------------------------
@@ -483,6 +484,27 @@ int mpx_bottleneck_tail(mpx_engine* h, int i, const void* t1_hi, const void* t1_
 int mpx_num_bottleneck_tails(const mpx_engine* h);
 /* layer indices of tail k: its conv2, conv3, downsample conv (-1 if none) and the following block's conv1; any pointer may be NULL */
 int mpx_bottleneck_tail_info(const mpx_engine* h, int k, int* conv2, int* conv3, int* downsample, int* next_conv1);
+
+/* ---- the pointwise tail of a 128-channel bottleneck block in ONE launch ---------------------------------------
+ * replaces: `out = self.bn3(self.conv3(out)); out += identity; out = self.relu(out)` of a plain layer2 Bottleneck (no downsample
+ *           branch) AND `out = self.relu(self.bn1(self.conv1(x)))` of the block that follows it (torchvision resnet.py, reached
+ *           through model(masked_img_tensor), generate_gp_training_data_imagenet.py:246).  Layer by layer the 512-channel trunk is
+ *           written by conv3 and read straight back by the next conv1; here the next conv1 runs on the output tile while it is on
+ *           chip, so the trunk is read once (as the identity) and written once.  Everything is pointwise: a tile is 128 consecutive
+ *           pixels of the flat [B * 28 * 28] index, and a pixel's result does not depend on where its tile starts.
+ * i = index of the block's conv3 ("layer2.N.conv3"); mpx_num_pointwise_tails / mpx_pointwise_tail_info list the pairs that have
+ * this path (ResNet-50 / 101: layer2.1 and layer2.2; ResNet-152: layer2.1 .. layer2.6).
+ * t2_*: conv3's input planes [B][28][28][128]; x_*: the block's identity planes [B][28][28][512]; out_*: block output
+ * [B][28][28][512]; next_*: the following conv1's output [B][28][28][128] (the pairs are found by their channel counts and the map
+ * side the two layers share, 28 in these networks; the kernel walks the flat pixel index).  All four plane pairs must be distinct buffers.  The launch
+ * reads the packed weight planes of its two layers as they are (a reload of either is seen by the next launch).  Same arithmetic as
+ * the layer-by-layer path up to fp32 summation order.  mpx_forward takes this path by default; a non-default tile on either layer of
+ * a pair makes it run that pair layer by layer. */
+int mpx_pointwise_tail(mpx_engine* h, int i, const void* t2_hi, const void* t2_lo, const void* x_hi, const void* x_lo,
+                       void* out_hi, void* out_lo, void* next_hi, void* next_lo, int B, void* stream);
+int mpx_num_pointwise_tails(const mpx_engine* h);
+/* layer indices of pointwise tail k: its conv3 and the following block's conv1; either pointer may be NULL */
+int mpx_pointwise_tail_info(const mpx_engine* h, int k, int* conv3, int* next_conv1);
 
 /* ---- K3: maxpool 3x3 s2 p1 (nn.MaxPool2d inside the same forward), NHWC split planes ------
  * Taps outside the map are left out (-inf padding), so the merged output equals F.max_pool2d(merged, 3, 2, 1) for any sign.

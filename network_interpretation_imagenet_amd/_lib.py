@@ -75,6 +75,9 @@ SIGNATURES = {
     "mpx_bottleneck_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mpx_num_bottleneck_tails": (_i, [_vp]),
     "mpx_bottleneck_tail_info": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "mpx_pointwise_tail": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mpx_num_pointwise_tails": (_i, [_vp]),
+    "mpx_pointwise_tail_info": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     "mpx_stem_conv_maxpool": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mpx_maxpool3x3s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_maxpool2x2s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -45,7 +45,7 @@ constexpr int kSmallCPad = 32;                         // small nets: channels a
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
               OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14,
-              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17 };
+              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17, OP_PTAIL = 18 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -100,6 +100,7 @@ struct Op {
     int in2;        // fused main conv: buffer of the block input (the downsample branch's operand), else BUF_NONE
     int z = BUF_NONE;   // OP_BTAIL: buffer of the next block's conv1 output; `conv` = index into mpx_engine::tails,
                         // in = t1, res = block input / identity, out = block output
+                        // OP_PTAIL: the same with `conv` = index into mpx_engine::ptails and in = t2
     int g = 0, ctot = 0;    // OP_CATNORM (DenseNet): `conv` = index into mpx_engine::norms, in = the fresh g channels, res = the block's raw
                             // concatenation (ctot channels per pixel), out = the normalised first c channels, hin = the map's side
 };
@@ -120,6 +121,12 @@ struct TailBlock {
     half_t* w3p_hi = nullptr;
     half_t* w3p_lo = nullptr;
     bool ready = false;
+};
+
+// A plain 128 -> 512 bottleneck block whose conv3 + identity runs with the next block's conv1 (512 -> 128) as ONE launch (mpx_btail.h,
+// the pointwise form).  It reads the packed planes of its two layers as they are: no copy to keep in step with a reload.
+struct PointTail {
+    int c3 = -1, next1 = -1;
 };
 
 // A depthwise 3x3 conv + BatchNorm + ReLU6 (MobileNetV2; mpx_dw.h): fp32 tap-major weights [9][pitch] and BatchNorm vectors of its own.
@@ -205,6 +212,11 @@ struct mpx_engine {
     std::vector<TailBlock> tails;
     int ops_bt_x = 0;               // buffer of the last block's output in ops_bt
     bool fuse_bt = true;            // mpx_forward uses ops_bt when every tail is ready (mpx_set_fusion bit 1)
+    std::vector<Op> ops_pt;         // ops_bt with layer2's pointwise tails as OP_PTAIL (empty if the arch has none)
+    std::vector<Op> ops_pt0;        // ops with them (the block tails are off or overridden by a tile)
+    std::vector<PointTail> ptails;
+    int ops_pt_x = 0, ops_pt0_x = 0;
+    bool fuse_pt = true;            // mpx_forward uses ops_pt / ops_pt0 (mpx_set_fusion bit 2; needs bit 0)
     char* arena = nullptr;
     size_t arena_bytes = 0;
     char* tab_arena = nullptr;      // the stem table of one image (CSR, heavy-pixel list, bit planes): allocated by the FIRST mpx_stem_table_build
@@ -425,10 +437,22 @@ int build_topology(mpx_engine* h) {
             return n1.cin == BT_OUT && n1.ksize == 1 && n1.stride == 1 && n1.hin == 56 && (n1.cout == 64 || n1.cout == 128) &&
                    !(blocks[k].ds >= 0 && n1.cout != 64);
         };
+        // Pointwise-tail plan (mpx_btail.h, BtPwCfg): a plain block (no downsample branch) whose conv3 is 128 -> 512 and whose successor
+        // starts with a 1x1 stride-1 conv 512 -> 128 (layer2's blocks 1 .. n-2) runs conv3 + identity and the successor's conv1 as ONE
+        // launch.  Four distinct buffers again: t2, the identity, the block output, the next t1.
+        auto ptail_ok = [&](size_t k) {
+            if (k + 1 >= blocks.size() || blocks[k].ds >= 0 || tail_ok(k)) return false;
+            const mpx_conv_desc& d3 = h->convs[blocks[k].c3].d;
+            const mpx_conv_desc& n1 = h->convs[blocks[k + 1].c1].d;
+            return d3.cin == BtPw128::MID && d3.cout == BtPw128::OUT && d3.ksize == 1 && d3.stride == 1 && d3.residual == 1 &&
+                   n1.cin == BtPw128::OUT && n1.cout == BtPw128::C1 && n1.ksize == 1 && n1.stride == 1 && n1.hin == d3.hin;
+        };
         bool any = false;
         for (size_t k = 0; k < blocks.size(); ++k) any |= tail_ok(k);
-        if (any) {
-            std::vector<Op>& out = h->ops_bt;
+        // one launch plan: layer1's block tails as OP_BTAIL (bt), layer2's pointwise tails as OP_PTAIL (pt); rec_bt / rec_pt: this plan is the
+        // one that fills h->tails / h->ptails (each list once: the other plans number their launches the same way)
+        auto plan = [&](std::vector<Op>& out, bool bt, bool pt, bool rec_bt, bool rec_pt) {
+            size_t n_bt = 0, n_pt = 0;
             out.push_back(h->ops[0]);       // stem conv, max pool
             out.push_back(h->ops[1]);
             int Xb = BUF_STEM, T1c = -100;         // T1c: buffer of a t1 that the previous tail launch has already written
@@ -440,20 +464,22 @@ int build_topology(mpx_engine* h) {
 #ifdef BT_NO_HEAD       // probe builds (tools/ab_lib.sh): layer1.0.conv1 stays a launch of its own
                 const bool whole = false;
 #else
-                const bool whole = tail_ok(k) && R.ds >= 0 && T1 < 0;
+                const bool whole = bt && tail_ok(k) && R.ds >= 0 && T1 < 0;
 #endif
                 if (T1 < 0 && !whole) {
                     T1 = pick({Xb});
                     out.push_back(Op{OP_CONV, R.c1, Xb, T1, BUF_NONE, 0, 0, BUF_NONE});
                 }
                 T1c = -100;
-                if (tail_ok(k)) {
-                    TailBlock tb;
-                    tb.c1 = R.c1; tb.c2 = R.c2; tb.c3 = R.c3; tb.ds = R.ds; tb.next1 = blocks[k + 1].c1;
-                    h->tails.push_back(tb);
+                if (bt && tail_ok(k)) {
+                    if (rec_bt) {
+                        TailBlock tb;
+                        tb.c1 = R.c1; tb.c2 = R.c2; tb.c3 = R.c3; tb.ds = R.ds; tb.next1 = blocks[k + 1].c1;
+                        h->tails.push_back(tb);
+                    }
                     if (whole) T1 = BUF_NONE;
                     const int O = pick({Xb, T1}), Z = pick({Xb, T1, O});
-                    Op o{OP_BTAIL, (int)h->tails.size() - 1, T1, O, Xb, 0, 0, BUF_NONE};
+                    Op o{OP_BTAIL, (int)n_bt++, T1, O, Xb, 0, 0, BUF_NONE};
                     o.z = Z;
                     out.push_back(o);
                     Xb = O;
@@ -462,6 +488,16 @@ int build_topology(mpx_engine* h) {
                 }
                 const int T2 = pick({Xb, T1});
                 out.push_back(Op{OP_CONV, R.c2, T1, T2, BUF_NONE, 0, 0, BUF_NONE});
+                if (pt && ptail_ok(k)) {
+                    if (rec_pt) h->ptails.push_back(PointTail{R.c3, blocks[k + 1].c1});
+                    const int O = pick({Xb, T2}), Z = pick({Xb, T2, O});
+                    Op o{OP_PTAIL, (int)n_pt++, T2, O, Xb, 0, 0, BUF_NONE};
+                    o.z = Z;
+                    out.push_back(o);
+                    Xb = O;
+                    T1c = Z;
+                    continue;
+                }
                 int res = Xb;
                 if (R.ds >= 0) {
                     const int T3 = pick({Xb, T1, T2});
@@ -471,7 +507,14 @@ int build_topology(mpx_engine* h) {
                 out.push_back(Op{OP_CONV, R.c3, T2, T1, res, 0, 0, R.ds >= 0 ? Xb : BUF_NONE});
                 Xb = T1;
             }
-            h->ops_bt_x = Xb;
+            return Xb;
+        };
+        bool any_pt = false;
+        for (size_t k = 0; k < blocks.size(); ++k) any_pt |= ptail_ok(k);
+        if (any) h->ops_bt_x = plan(h->ops_bt, true, false, true, false);
+        if (any_pt) {       // (an arch with pointwise tails and no block tails gets ops_pt0 alone: mpx_forward never picks ops_pt then)
+            h->ops_pt0_x = plan(h->ops_pt0, false, true, false, true);
+            if (any) h->ops_pt_x = plan(h->ops_pt, true, true, false, false);
         }
     }
     h->feat = cin;
@@ -480,10 +523,11 @@ int build_topology(mpx_engine* h) {
     h->convs[c].is_fc = true;
     add_op(OP_CONV, c, BUF_POOL, BUF_NONE, BUF_NONE, 0, 0);
     add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0);
-    if (!h->ops_bt.empty()) {
-        h->ops_bt.push_back(Op{OP_AVGPOOL, -1, h->ops_bt_x, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
-        h->ops_bt.push_back(h->ops[h->ops.size() - 2]);
-        h->ops_bt.push_back(h->ops[h->ops.size() - 1]);
+    for (auto lx : {std::make_pair(&h->ops_bt, h->ops_bt_x), std::make_pair(&h->ops_pt, h->ops_pt_x), std::make_pair(&h->ops_pt0, h->ops_pt0_x)}) {
+        if (lx.first->empty()) continue;
+        lx.first->push_back(Op{OP_AVGPOOL, -1, lx.second, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
+        lx.first->push_back(h->ops[h->ops.size() - 2]);
+        lx.first->push_back(h->ops[h->ops.size() - 1]);
     }
     return 0;
 }
@@ -1666,6 +1710,7 @@ const KernelLds kKernelLds[] = {
     {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
     {(const void*)btail_f16x3_kernel<BtDualC64>, BtDualC64::LDS},
     {(const void*)btail_f16x3_kernel<BtHeadC64>, BtHeadC64::LDS},
+    {(const void*)btail_f16x3_kernel<BtPw128>, BtPw128::LDS},
     {(const void*)conv3x3p_f16x3_kernel<PatchTile0>, kLdsLimit},
     {(const void*)conv3x3p_f16x3_kernel<PatchTile1>, kLdsLimit},
     {(const void*)conv3x3p_f16x3_kernel<PatchTile2>, kLdsLimit},
@@ -1983,6 +2028,43 @@ int launch_btail(mpx_engine* h, int ti, const half_t* t_hi, const half_t* t_lo, 
     else hipLaunchKernelGGL(btail_f16x3_kernel<BtResC64>, dim3(grid), dim3(256), BtResC64::LDS, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
+}
+
+// One pointwise tail (mpx_btail.h): t2 planes [M][128], x = identity planes [M][512], y = block output [M][512], z = the next block's
+// conv1 output [M][128], M = B * H * W pixels in tiles of 128.  The weights are the packed planes of the two layers themselves.
+int launch_ptail(mpx_engine* h, int ti, const half_t* t_hi, const half_t* t_lo, const half_t* x_hi, const half_t* x_lo,
+                 half_t* y_hi, half_t* y_lo, half_t* z_hi, half_t* z_lo, int B, hipStream_t st) {
+    const PointTail& pt = h->ptails[ti];
+    const ConvLayer& L3 = h->convs[pt.c3];
+    const ConvLayer& N1 = h->convs[pt.next1];
+    if (!L3.loaded || !N1.loaded) return fail(h, MPX_E_STATE, "pointwise tail %s: weights missing", L3.d.name);
+    if (L3.d.k_packed != BtPw128::MID || N1.d.k_packed != BtPw128::OUT) return fail(h, MPX_E_INTERNAL, "pointwise tail %s: packed K %d / %d", L3.d.name, L3.d.k_packed, N1.d.k_packed);
+    BtParams p;
+    std::memset(&p, 0, sizeof p);
+    p.t_hi = t_hi; p.t_lo = t_lo;
+    p.w3_hi = L3.w_hi; p.w3_lo = L3.w_lo; p.sc3 = L3.scale; p.sh3 = L3.shift;
+    p.r_hi = x_hi; p.r_lo = x_lo; p.y_hi = y_hi; p.y_lo = y_lo;
+    p.w1_hi = N1.w_hi; p.w1_lo = N1.w_lo; p.sc1 = N1.scale; p.sh1 = N1.shift;
+    p.z_hi = z_hi; p.z_lo = z_lo;
+    p.B = B; p.H = L3.d.hin; p.W = L3.d.hin;
+    const long long M = (long long)B * p.H * p.W;
+    const long long n_tiles = (M + BtPw128::TP - 1) / BtPw128::TP;
+    if (n_tiles <= 0 || M > 0x7fffffffLL) return fail(h, MPX_E_ARG, "pointwise tail: batch out of range");
+    p.n_tiles = (int)n_tiles;
+    const long long resident = 2LL * h->num_cus;                       // two 72-KB workgroups per CU
+    const unsigned grid = (unsigned)std::min<long long>(resident, n_tiles);
+    ProfScope ps(h, st, OP_CONV, pt.c3);
+    hipLaunchKernelGGL(btail_f16x3_kernel<BtPw128>, dim3(grid), dim3(256), BtPw128::LDS, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// Layers c3 and next1 of pointwise tail k run as its one launch: bit 2 of the fusion mask, and no tile override on either layer
+bool ptail_in_use(const mpx_engine* h, int k) {
+    const PointTail& pt = h->ptails[k];
+    for (int li : {pt.c3, pt.next1})
+        if (!h->convs[li].loaded || h->convs[li].tile != default_tile(h->convs[li].d)) return false;
+    return true;
 }
 
 // Fused planes of a (main, ds) pair from the host copies of both layers.  With s3 = g3/sqrt(v3+eps) and sd likewise,
@@ -3187,13 +3269,23 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
     for (const TailBlock& tb : h->tails)
         for (int li : {tb.c1, tb.c2, tb.c3, tb.next1})
             use_bt = use_bt && h->convs[li].tile == default_tile(h->convs[li].d);
-    const std::vector<Op>& ops = use_bt ? h->ops_bt : h->ops;
+    // layer2's pointwise tails likewise (bit 2); a tile override on one of a pair's two layers sends THAT pair through its two layers
+    const bool use_pt = h->fuse_pt && h->fuse_ds && !h->ptails.empty();
+    const std::vector<Op>& ops = use_pt ? (use_bt ? h->ops_pt : h->ops_pt0) : (use_bt ? h->ops_bt : h->ops);
     for (size_t oi = 0; oi < ops.size(); ++oi) {
         const Op& o = ops[oi];
         if (stem_done && ((o.kind == OP_CONV && o.conv == 0) || (o.kind == OP_MAXPOOL && o.out == BUF_STEM))) continue;
         switch (o.kind) {
             case OP_BTAIL:
                 rc = launch_btail(h, o.conv, hi(o.in), lo(o.in), hi(o.res), lo(o.res), hi(o.out), lo(o.out), hi(o.z), lo(o.z), B, as_stream(stream));
+                break;
+            case OP_PTAIL:
+                if (ptail_in_use(h, o.conv)) {
+                    rc = launch_ptail(h, o.conv, hi(o.in), lo(o.in), hi(o.res), lo(o.res), hi(o.out), lo(o.out), hi(o.z), lo(o.z), B, as_stream(stream));
+                    break;
+                }
+                rc = mpx_conv_bn_act(h, h->ptails[o.conv].c3, hi(o.in), lo(o.in), hi(o.res), lo(o.res), hi(o.out), lo(o.out), nullptr, B, stream);
+                if (!rc) rc = mpx_conv_bn_act(h, h->ptails[o.conv].next1, hi(o.out), lo(o.out), nullptr, nullptr, hi(o.z), lo(o.z), nullptr, B, stream);
                 break;
             case OP_CONV:
                 if (h->fuse_pool && o.conv == 0 && oi + 1 < ops.size() && ops[oi + 1].kind == OP_MAXPOOL && stem_pool_eligible(h) &&
@@ -3321,6 +3413,7 @@ int mpx_set_fusion(mpx_engine* h, int mask) {
     h->fuse_pool = (mask & 1) != 0;
     h->fuse_ds = (mask & 1) != 0;
     h->fuse_bt = (mask & 2) != 0;
+    h->fuse_pt = (mask & 4) != 0;
     return 0;
 }
 
@@ -3361,6 +3454,43 @@ int mpx_bottleneck_tail_info(const mpx_engine* h, int k, int* conv2, int* conv3,
     if (conv3) *conv3 = h->tails[k].c3;
     if (downsample) *downsample = h->tails[k].ds;
     if (next_conv1) *next_conv1 = h->tails[k].next1;
+    return 0;
+}
+
+int mpx_pointwise_tail(mpx_engine* h, int i, const void* t2_hi, const void* t2_lo, const void* x_hi, const void* x_lo,
+                       void* out_hi, void* out_lo, void* next_hi, void* next_lo, int B, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (B <= 0 || !t2_hi || !t2_lo || !x_hi || !x_lo || !out_hi || !out_lo || !next_hi || !next_lo)
+        return fail(h, MPX_E_ARG, "pointwise_tail: null planes or empty batch");
+    int ti = -1;
+    for (size_t k = 0; k < h->ptails.size(); ++k)
+        if (h->ptails[k].c3 == i) ti = (int)k;
+    if (ti < 0) return fail(h, MPX_E_ARG, "pointwise_tail: layer %d is not the conv3 of a block whose pointwise tail runs as one launch", i);
+    {
+        // the four plane pairs must not overlap: a workgroup reads t2 and the identity of its tiles while others write out / next
+        const PointTail& pt = h->ptails[ti];
+        const size_t px = (size_t)B * h->convs[pt.c3].d.hin * h->convs[pt.c3].d.hin * sizeof(half_t);
+        struct Range { const char* lo; size_t n; const char* what; };
+        const Range r[8] = {{(const char*)t2_hi, px * BtPw128::MID, "t2_hi"}, {(const char*)t2_lo, px * BtPw128::MID, "t2_lo"},
+                            {(const char*)x_hi, px * BtPw128::OUT, "x_hi"}, {(const char*)x_lo, px * BtPw128::OUT, "x_lo"},
+                            {(const char*)out_hi, px * BtPw128::OUT, "out_hi"}, {(const char*)out_lo, px * BtPw128::OUT, "out_lo"},
+                            {(const char*)next_hi, px * BtPw128::C1, "next_hi"}, {(const char*)next_lo, px * BtPw128::C1, "next_lo"}};
+        for (int a = 0; a < 8; ++a)
+            for (int b = a + 1; b < 8; ++b)
+                if (r[a].lo < r[b].lo + r[b].n && r[b].lo < r[a].lo + r[a].n)
+                    return fail(h, MPX_E_ARG, "pointwise_tail: planes %s and %s overlap (all plane pairs must be distinct buffers)", r[a].what, r[b].what);
+    }
+    MPX_SET_DEVICE(h);
+    return launch_ptail(h, ti, (const half_t*)t2_hi, (const half_t*)t2_lo, (const half_t*)x_hi, (const half_t*)x_lo, (half_t*)out_hi,
+                        (half_t*)out_lo, (half_t*)next_hi, (half_t*)next_lo, B, as_stream(stream));
+}
+
+int mpx_num_pointwise_tails(const mpx_engine* h) { return h ? (int)h->ptails.size() : MPX_E_ARG; }
+
+int mpx_pointwise_tail_info(const mpx_engine* h, int k, int* conv3, int* next_conv1) {
+    if (!h || k < 0 || k >= (int)h->ptails.size()) return MPX_E_ARG;
+    if (conv3) *conv3 = h->ptails[k].c3;
+    if (next_conv1) *next_conv1 = h->ptails[k].next1;
     return 0;
 }
 

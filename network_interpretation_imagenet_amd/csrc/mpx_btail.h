@@ -750,10 +750,368 @@ __global__ __launch_bounds__(256, 2) void btail_f16x3_kernel(const BtParams p) {
 #endif
 }
 
+// ---- the POINTWISE form: a block tail without conv2 -----------------------------------------------------------------------------
+//
+//     out = relu(bn3(conv3_1x1(t2)) + identity)                   128 -> 512                     (written: the next block's identity)
+//     t1' = relu(bn1'(conv1'_1x1(out)))                           512 -> 128                     the NEXT block's first conv
+//
+// layer2's plain blocks (28x28 maps): conv3 writes the 512-channel trunk and the next conv1 reads it straight back; here it is read
+// once (as the identity) and written once.  Everything is pointwise, so there is no patch, no halo and no dead lane: a tile is 128
+// consecutive pixels of the flat [B*H*W] index (wave w = pixels [32w, 32w+32) = two full 16-lane fragments) and may straddle images.
+// Every global access goes through a descriptor of the tile's own rows, so the ragged last tile (and the request for a tile behind
+// the last one) is cut off by the descriptor's range check: no exec regions, no per-lane masks.
+//
+// conv3's B operand comes from memory: 16 loads per lane fetch the wave's t2 pixels as B fragments in natural K order (as the DUAL
+// tail fetches its block input), so the packed conv3 / conv1' planes of the two layers serve as they are.  They stay in registers
+// for the tile's eight 64-channel chunks; the next tile's are requested in the first conv1' step of the LAST chunk (step JT = 60 of 64:
+// t2's last use is that chunk's fourth conv3 step, 59).  The chunk phase, the 4-stage weight ring that runs on across tiles and the counted waits are
+// those of the 3x3 form.  LDS: [scale / shift vectors 8 KB][4 wave-private 8-KB staging areas][ring 32 KB] = 72 KB, two workgroups
+// per CU.  Registers (256 per wave): t2 64 + conv1' accumulators 64 + conv3 accumulators 32 + identity lines 32 leave room for ONE
+// set of weight fragments in the conv3 steps (read behind the step's MFMAs, late_a); the conv1' steps keep the double buffer.
+template <int C1_>
+struct BtPwCfg {
+    static constexpr int C1 = C1_;
+    static constexpr int MID = 128, OUT = 512;          // conv3: MID -> OUT, conv1': OUT -> C1
+    static constexpr int TP = 128;                      // pixels of a tile
+    static constexpr int NCH = OUT / 64;                // output chunks
+    static constexpr int S3 = MID / 32;                 // conv3 steps per chunk
+    static constexpr int H1 = C1 / 64;
+    static constexpr int S1 = 2 * H1;                   // conv1' steps per chunk
+    static constexpr int SC = S3 + S1;
+    static constexpr int NSTEP = NCH * SC;
+    static constexpr int JT = NSTEP - S1;               // step behind whose stage the next tile's 4 * S3 t2 fragment loads are issued
+    static constexpr int NVEC = 2 * (OUT + C1);         // floats: sc3 sh3 sc1 sh1
+    static constexpr int OFF_STG = 8192;
+    static constexpr int OFF_RING = OFF_STG + 4 * 8192;
+    static constexpr int LDS = OFF_RING + BT_NRING * BT_STAGE;
+    static_assert(NVEC * 4 <= OFF_STG, "vectors overflow their LDS area");
+    static_assert(C1 == 128, "conv1' has 128 output channels");
+    static_assert(NSTEP % BT_NRING == 0, "ring slot of a step = step % 4 in every tile (and the fragment parity with it)");
+
+    static constexpr int mod(int j) { return ((j % NSTEP) + NSTEP) % NSTEP; }
+    static constexpr int pre(int j) {                   // loads issued right behind the stage of step j
+        j = mod(j);
+        return (j % SC == 0 ? 8 : 0) + (j == JT ? 4 * S3 : 0);             // identity lines of the chunk that starts here; t2 of the next tile
+    }
+    static constexpr int post(int j) {                  // stores at the end of step j
+        j = mod(j);
+        return (j % SC == S3 - 1 ? 8 : 0) + (j == NSTEP - 1 ? 8 * H1 : 0);  // `out` lines of the chunk; t1' lines
+    }
+    static constexpr int all(int j) { return 2 + pre(j) + post(j); }
+    static constexpr bool late_a(int j) { return mod(j) % SC < S3; }         // conv3 steps: the next step's fragments are read behind the MFMAs
+    static constexpr int wait_top(int j) { return pre(j - 3) + post(j - 3) + all(j - 2) + all(j - 1); }
+};
+
+template <class C>
+__device__ __forceinline__ void btail_pointwise_body(const BtParams& p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    constexpr int C1 = C::C1, MID = C::MID, OUT = C::OUT, TP = C::TP, NCH = C::NCH, S3 = C::S3, S1 = C::S1, SC = C::SC, H1 = C::H1, NSTEP = C::NSTEP;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lp = lane & 15, lg = lane >> 4;
+    float one = 1.0f;
+    asm volatile("" : "+s"(one));       // opaque 1.0 (bt_relu_split8)
+
+    const long long M = (long long)p.B * p.H * p.W;
+    const int G = gridDim.x;
+    const int v0 = blockIdx.x;
+    if (v0 >= p.n_tiles) return;
+    const int my_tiles = (p.n_tiles - 1 - v0) / G + 1;
+
+    char* const ring = smem + C::OFF_RING;
+    char* const stg = smem + C::OFF_STG + wave * 8192;                 // wave-private staging
+    float* const vec = (float*)smem;
+    constexpr int V_SC3 = 0, V_SH3 = OUT, V_SC1 = 2 * OUT, V_SH1 = 2 * OUT + C1;
+    for (int i = tid; i < C::NVEC; i += 256) {
+        float v;
+        if (i < V_SH3) v = p.sc3[i];
+        else if (i < V_SC1) v = p.sh3[i - V_SH3];
+        else if (i < V_SH1) v = p.sc1[i - V_SC1];
+        else v = p.sh1[i - V_SH1];
+        vec[i] = v;
+    }
+
+    // ---- weight stream: per chunk S3 stages of conv3 rows [64c, 64c+64), then S1 stages of conv1' columns [64c, 64c+64) ----------
+    const __amdgpu_buffer_rsrc_t w3h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3_hi, 0, OUT * MID * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w3l = __builtin_amdgcn_make_buffer_rsrc((void*)p.w3_lo, 0, OUT * MID * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w1h = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1_hi, 0, C1 * OUT * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t w1l = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1_lo, 0, C1 * OUT * 2, 0x00020000);
+    const int w_lane = lane * 16;
+    auto issue_stage = [&](auto js_tag, int slot) {     // this wave moves piece `wave` (16 rows) of each plane
+        constexpr int JS = decltype(js_tag)::value;
+        constexpr int cc = JS / SC, r = JS % SC;
+        char* const d = ring + slot * BT_STAGE + wave * 1024;
+        if (r < S3) {
+            const int soff = ((4 * cc + wave) * S3 + r) * 1024;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w3h, MPX_LDS_PTR(d), 16, w_lane, soff, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w3l, MPX_LDS_PTR(d + 4096), 16, w_lane, soff, 0, 0);
+        } else {
+            constexpr int r1 = r - S3, kk = r1 / H1, hb = r1 % H1;
+            const int soff = ((4 * hb + wave) * (OUT / 32) + 2 * cc + kk) * 1024;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w1h, MPX_LDS_PTR(d), 16, w_lane, soff, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w1l, MPX_LDS_PTR(d + 4096), 16, w_lane, soff, 0, 0);
+        }
+    };
+
+    // ---- addressing ------------------------------------------------------------------------------------------------------------
+    const int a_off = lp * 64 + ((lg ^ (((lane >> 3) & 1) << 1)) << 4);           // weight rows: mpx_conv.h's swizzle
+    const int sb_off = lp * 64 + ((lg ^ (((lp >> 3) & 1) << 1)) << 4);             // staging, operand layout: + (b*4 + kk*2 + plane)*1024
+    const int uq = lane & 7;           // line-layout passes: unit u = (pixel wave*32 + u*8 + lane/8 of the tile, channels 8*uq ..)
+    // per-lane offsets into the tile's rows.  The ROW part of an address stays in the vector offset, which is what the descriptor's range
+    // check sees (the ragged tile relies on it); only the position within a pixel (chunk, K step) rides in the soffset.
+    const int y_voff = (wave * 32 + (lane >> 3)) * (OUT * 2) + uq * 16;            // + u * 8 rows
+    const int z_voff = (wave * 32 + (lane >> 3)) * (C1 * 2) + uq * 16;
+    const int t_voff = (wave * 32 + lp) * (MID * 2) + lg * 16;                     // + b * 16 rows
+    // descriptor of a tile's rows of planes with `ch` channels per pixel: rows behind M (and whole tiles behind the last) are out of range
+    auto tile_rsrc = [&](const half_t* base, int t, int ch) {
+        const long long pix0 = (long long)t * TP;
+        const long long rem = M - pix0;
+        const int rows = rem < 0 ? 0 : (rem > TP ? TP : (int)rem);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(base + pix0 * ch), 0, rows * ch * 2, 0x00020000);
+    };
+
+    f4 acc1[4 * H1][2];
+    h8 t2h[S3][2], t2l[S3][2];     // conv3's B operand: [K step][pixel fragment]
+    u4 idh[4], idl[4];             // identity lines of the chunk about to be finished, one per unit
+    struct FragA { h8 hi[4], lo[4]; };
+    struct FragB { h8 hi[2], lo[2]; };
+    FragA fa[2];                   // weight fragments of the current / next step (index = step parity)
+    FragB cb[2];                   // conv1': fragments of the chunk's two K steps, from the staging area
+
+    // t2 fragments of tile t (B layout, natural K): lane (pixel lp, group lg) reads channels [32 kk + 8 lg, +8) of pixels 32 wave + 16 b + lp
+    auto issue_t2 = [&](int t) {
+        const __amdgpu_buffer_rsrc_t th = tile_rsrc(p.t_hi, t, MID);
+        const __amdgpu_buffer_rsrc_t tl = tile_rsrc(p.t_lo, t, MID);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int kk = 0; kk < S3; ++kk) {
+                t2h[kk][b] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(th, t_voff + b * 16 * MID * 2, kk * 64, 0));
+                t2l[kk][b] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(tl, t_voff + b * 16 * MID * 2, kk * 64, 0));
+            }
+    };
+    auto read_a1 = [&](int slot, FragA& f, int i) {        // fragment read i = 0..7 of a stage: hi rows 0..3, lo rows 0..3
+        const char* s = ring + slot * BT_STAGE + a_off + (i & 3) * 1024;
+        if (i < 4) f.hi[i] = *(const h8*)s;
+        else f.lo[i - 4] = *(const h8*)(s + 4096);
+    };
+
+    // prologue: stages 0 .. 3, the first tile's t2 fragments
+    issue_stage(std::integral_constant<int, 0>{}, 0);
+    issue_stage(std::integral_constant<int, 1>{}, 1);
+    issue_stage(std::integral_constant<int, 2>{}, 2);
+    issue_stage(std::integral_constant<int, 3>{}, 3);
+    issue_t2(v0);
+    __builtin_amdgcn_sched_barrier(0);
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) read_a1(0, fa[0], i);
+
+    for (int it = 0; it < my_tiles; ++it) {
+        const int t = v0 + it * G;
+        const __amdgpu_buffer_rsrc_t rh_rs = tile_rsrc(p.r_hi, t, OUT);
+        const __amdgpu_buffer_rsrc_t rl_rs = tile_rsrc(p.r_lo, t, OUT);
+        const __amdgpu_buffer_rsrc_t yh = tile_rsrc(p.y_hi, t, OUT);
+        const __amdgpu_buffer_rsrc_t yl = tile_rsrc(p.y_lo, t, OUT);
+        const __amdgpu_buffer_rsrc_t zh = tile_rsrc(p.z_hi, t, C1);
+        const __amdgpu_buffer_rsrc_t zl = tile_rsrc(p.z_lo, t, C1);
+        __builtin_amdgcn_sched_barrier(0);
+
+        // identity lines of chunk c (8 loads): unit u reads channels [64c + 8*uq, +8) of its pixel
+        auto issue_identity = [&](int c) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                idh[u] = __builtin_amdgcn_raw_buffer_load_b128(rh_rs, y_voff + u * 8 * OUT * 2, c * 128, BT_AUX_LOAD);
+                idl[u] = __builtin_amdgcn_raw_buffer_load_b128(rl_rs, y_voff + u * 8 * OUT * 2, c * 128, BT_AUX_LOAD);
+            }
+        };
+        // Step J: as the 3x3 form's.  A conv3 step (late_a) holds one set of weight fragments: the next step's are read behind its
+        // MFMAs (behind the chunk epilogue in the chunk's last conv3 step); their stage has landed by the wait at the top of step J.
+        auto step = [&](auto j_tag, f4 (*acc)[2], const h8 (&bh)[2], const h8 (&bl)[2]) {
+            constexpr int J = decltype(j_tag)::value;
+            constexpr int r = J % SC;
+            const FragA& A = fa[J & 1];
+            FragA& An = fa[(J + 1) & 1];
+            __builtin_amdgcn_sched_barrier(0);
+            wait_vmcnt<C::wait_top(J)>();
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < 24; ++i) {
+                const int a = i / 6, q = i % 6, term = q >> 1, b = q & 1;
+                if (term == 0) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi[a], bl[b], acc[a][b], 0, 0, 0);
+                else if (term == 1) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.lo[a], bh[b], acc[a][b], 0, 0, 0);
+                else acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi[a], bh[b], acc[a][b], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if ((i & 1) == 0 && i < 16 && !C::late_a(J)) {
+                    read_a1((J + 1) & 3, An, i >> 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if ((i & 1) == 0 && i >= 16 && r == S3 + H1 - 1) {
+                    // the step before conv1's second K step of this chunk: its B fragments (written by the chunk epilogue)
+                    const int k = (i - 16) >> 1, fb = k & 1, plane = k >> 1;
+                    const h8 f = *(const h8*)(stg + (fb * 4 + 2 + plane) * 1024 + sb_off);
+                    if (plane == 0) cb[1].hi[fb] = f;
+                    else cb[1].lo[fb] = f;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (i == 1) {
+                    issue_stage(std::integral_constant<int, (J + 4) % NSTEP>{}, J & 3);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (i == 5 && r == 0) {
+                    issue_identity(J / SC);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (i == 5 && J == C::JT) {
+                    issue_t2(t + G);                    // (behind the last tile: every row out of range, the loads are still counted)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (C::late_a(J) && r != S3 - 1) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) read_a1((J + 1) & 3, An, i);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+
+#pragma unroll
+        for (int a = 0; a < 4 * H1; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc1[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
+
+        // ================= NCH output chunks of 64 channels =====================================================================
+        auto chunk = [&](auto c_tag) {
+            constexpr int c = decltype(c_tag)::value;
+            constexpr int J0 = c * SC;
+            f4 acc3[4][2];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) acc3[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
+            step(std::integral_constant<int, J0>{}, acc3, t2h[0], t2l[0]);
+            step(std::integral_constant<int, J0 + 1>{}, acc3, t2h[1], t2l[1]);
+            step(std::integral_constant<int, J0 + 2>{}, acc3, t2h[2], t2l[2]);
+            step(std::integral_constant<int, J0 + 3>{}, acc3, t2h[3], t2l[3]);
+            // ---- chunk epilogue (wave-private), as the 3x3 form's ----
+            __builtin_amdgcn_sched_barrier(0);
+            // The staging addresses are worked out again in every epilogue, from a lane id the optimiser cannot see through: hoisted out
+            // of the tile loop they would be a dozen registers that this kernel does not have.
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int lp = ln & 15, lg = ln >> 4, uq = ln & 7, l8 = ln >> 3;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const f4 sc = *(const f4*)(vec + V_SC3 + c * 64 + a * 16 + 4 * lg);
+                const f4 sh = *(const f4*)(vec + V_SH3 + c * 64 + a * 16 + 4 * lg);
+#pragma unroll
+                for (int b = 0; b < 2; ++b) *(f4*)(stg + (b * 16 + lp) * 256 + (((a * 4 + lg) ^ lp) << 4)) = acc3[a][b] * sc + sh;
+            }
+            // one pixel fragment (16 slots = units 2b, 2b+1) at a time: its operand bytes replace its own fp32 bytes only
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                f4 v0[2], v1[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int slot = (2 * b + k) * 8 + l8;
+                    v0[k] = *(const f4*)(stg + slot * 256 + (((2 * uq) ^ (slot & 15)) << 4));
+                    v1[k] = *(const f4*)(stg + slot * 256 + (((2 * uq + 1) ^ (slot & 15)) << 4));
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int u = 2 * b + k;
+                    const int slot = u * 8 + l8;
+                    float v[8] = {v0[k][0], v0[k][1], v0[k][2], v0[k][3], v1[k][0], v1[k][1], v1[k][2], v1[k][3]};
+                    // + identity (hi + lo): two v_fma_mix_f32 per element (the fp16 -> fp32 conversions ride in the instruction)
+                    const h8 a8 = __builtin_bit_cast(h8, idh[u]);
+                    const h8 c8 = __builtin_bit_cast(h8, idl[u]);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf((float)c8[j], one, __builtin_fmaf((float)a8[j], one, v[j]));
+                    h8 oh, ol;
+                    bt_relu_split8(v, one, oh, ol);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, oh), yh, y_voff + u * 8 * OUT * 2, c * 128, BT_AUX_STORE);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, ol), yl, y_voff + u * 8 * OUT * 2, c * 128, BT_AUX_STORE);
+                    // operand layout for conv1': [fragment b][K step uq>>2][plane][16 slots][64 B], chunk uq&3 swizzled by the slot
+                    char* const d = stg + (b * 4 + (uq >> 2) * 2) * 1024 + (slot & 15) * 64 + (((uq & 3) ^ (((slot >> 3) & 1) << 1)) << 4);
+                    *(h8*)d = oh;
+                    *(h8*)(d + 1024) = ol;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) read_a1((J0 + S3) & 3, fa[(J0 + S3) & 1], i);
+            // B fragments of conv1's first K step of this chunk (the second one's are read during the step before it)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                cb[0].hi[b] = *(const h8*)(stg + (b * 4 + 0) * 1024 + sb_off);
+                cb[0].lo[b] = *(const h8*)(stg + (b * 4 + 1) * 1024 + sb_off);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // conv1' steps: K step kk = r1 / H1 of this chunk, 64-row block hb = r1 % H1
+            step(std::integral_constant<int, J0 + S3>{}, &acc1[0], cb[0].hi, cb[0].lo);
+            step(std::integral_constant<int, J0 + S3 + 1>{}, &acc1[4], cb[0].hi, cb[0].lo);
+            step(std::integral_constant<int, J0 + S3 + 2>{}, &acc1[0], cb[1].hi, cb[1].lo);
+            step(std::integral_constant<int, J0 + S3 + 3>{}, &acc1[4], cb[1].hi, cb[1].lo);
+        };
+        chunk(std::integral_constant<int, 0>{});
+        chunk(std::integral_constant<int, 1>{});
+        chunk(std::integral_constant<int, 2>{});
+        chunk(std::integral_constant<int, 3>{});
+        chunk(std::integral_constant<int, 4>{});
+        chunk(std::integral_constant<int, 5>{});
+        chunk(std::integral_constant<int, 6>{});
+        chunk(std::integral_constant<int, 7>{});
+
+        // ================= t1' = relu(acc1 * scale1 + shift1): 8 * H1 stores, all behind the tile's last step ====================
+        __builtin_amdgcn_sched_barrier(0);
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int lp = ln & 15, lg = ln >> 4, uq = ln & 7, l8 = ln >> 3;
+#pragma unroll
+        for (int hb = 0; hb < H1; ++hb) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const f4 sc = *(const f4*)(vec + V_SC1 + hb * 64 + a * 16 + 4 * lg);
+                const f4 sh = *(const f4*)(vec + V_SH1 + hb * 64 + a * 16 + 4 * lg);
+#pragma unroll
+                for (int b = 0; b < 2; ++b) *(f4*)(stg + (b * 16 + lp) * 256 + (((a * 4 + lg) ^ lp) << 4)) = acc1[hb * 4 + a][b] * sc + sh;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int slot = u * 8 + l8;
+                const f4 w0 = *(const f4*)(stg + slot * 256 + (((2 * uq) ^ (slot & 15)) << 4));
+                const f4 w1 = *(const f4*)(stg + slot * 256 + (((2 * uq + 1) ^ (slot & 15)) << 4));
+                const float v[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+                h8 zoh, zol;
+                bt_relu_split8(v, one, zoh, zol);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, zoh), zh, z_voff + u * 8 * C1 * 2, hb * 128, BT_AUX_STORE);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, zol), zl, z_voff + u * 8 * C1 * 2, hb * 128, BT_AUX_STORE);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    wait_vmcnt<0>();
+#endif
+}
+
 typedef BtCfg<false, 64> BtResC64;      // layer1.1 / layer1.2 tails: identity = the trunk, next conv1 256 -> 64
 typedef BtCfg<false, 128> BtResC128;    // layer1's last block: next conv1 = layer2.0.conv1, 256 -> 128
 typedef BtCfg<true, 64> BtDualC64;      // layer1.0: downsample branch K-concatenated, next conv1 256 -> 64
 typedef BtCfg<true, 64, true> BtHeadC64; // layer1.0 whole: its own conv1 runs on the patch of the block input first
+typedef BtPwCfg<128> BtPw128;           // layer2's plain blocks, pointwise: conv3 128 -> 512 + identity, next conv1 512 -> 128
+
+// The pointwise form is an explicit specialisation of the kernel template: the same kernel name, and the 3x3 form above stays the
+// primary template, word for word what it was (its instantiations compile to what they did before this form existed).
+template <>
+__global__ __launch_bounds__(256, 2) void btail_f16x3_kernel<BtPw128>(const BtParams p) {
+    btail_pointwise_body<BtPw128>(p);
+}
 
 // The wait immediates, checked against the program written out by hand for the identity tail (steps 16 .. 23: the last conv2 steps,
 // conv3 of chunk 0 with its 8 identity loads requested in step 15 and its 8 stores behind step 19, conv1' of chunk 0 with the next
@@ -763,6 +1121,13 @@ static_assert(BtResC64::wait_top(14) == 4 && BtResC64::wait_top(16) == 12 && BtR
               "conv2 -> chunk 0");
 static_assert(BtResC64::wait_top(20) == 12 && BtResC64::wait_top(21) == 20 && BtResC64::wait_top(22) == 20 && BtResC64::wait_top(23) == 12,
               "chunk pattern: conv1' steps behind the stores, the next chunk's conv3 steps behind the identity loads");
+// The pointwise form: 8 chunks of 4 + 4 steps; identity loads in a chunk's first conv3 step, its 8 stores behind the fourth; the next
+// tile's 16 t2 loads in step 60, the 16 t1' stores behind step 63.
+static_assert(BtPw128::NSTEP == 64 && BtPw128::LDS == 73728, "steps per tile, LDS of the pointwise form");
+static_assert(BtPw128::wait_top(3) == 12 && BtPw128::wait_top(4) == 12 && BtPw128::wait_top(6) == 12 && BtPw128::wait_top(7) == 4 && BtPw128::wait_top(8) == 4,
+              "chunk pattern of the pointwise form");
+static_assert(BtPw128::wait_top(63) == 20 && BtPw128::wait_top(0) == 20 && BtPw128::wait_top(1) == 28 && BtPw128::wait_top(2) == 28,
+              "tile boundary of the pointwise form");
 static_assert(BtResC64::wait_top(0) == 20 && BtDualC64::wait_top(4) == 12 && BtDualC64::wait_top(6) == 4, "tile start; block-input loads of the DUAL tail in step 2");
 
 }  // namespace mpx

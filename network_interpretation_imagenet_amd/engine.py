@@ -737,11 +737,12 @@ class MaskedForwardEngine:
 
     def set_fusion(self, on=True):
         """mpx_set_fusion.  True (default state) = every fusion: a stage's first conv3 with its downsample conv as one
-        K-concatenated launch, the ImageNet stem with its max pool, and layer1's block tails (conv2 -> conv3 + identity -> the
-        next block's conv1, mpx_bottleneck_tail).  False = one launch per layer.  An int is passed through as the mask
-        (1 = round 2's fusions without the block tails).  The stem fusion is bit-identical to the separate launches; the other
-        two change the fp32 summation order (same tolerance)."""
-        mask = (3 if on else 0) if isinstance(on, bool) else int(on)
+        K-concatenated launch, the ImageNet stem with its max pool, layer1's block tails (conv2 -> conv3 + identity -> the
+        next block's conv1, mpx_bottleneck_tail) and layer2's pointwise tails (conv3 + identity -> the next block's conv1,
+        mpx_pointwise_tail).  False = one launch per layer.  An int is passed through as the mask (1 = round 2's fusions
+        without the tails, 3 = without the pointwise tails).  The stem fusion is bit-identical to the separate launches; the
+        others change the fp32 summation order (same tolerance)."""
+        mask = (7 if on else 0) if isinstance(on, bool) else int(on)
         _lib.check(self._h, self._lib.mpx_set_fusion(self._h, mask), "mpx_set_fusion")
 
     def bottleneck_tails(self):
@@ -750,6 +751,15 @@ class MaskedForwardEngine:
         for k in range(self._lib.mpx_num_bottleneck_tails(self._h)):
             v = [C.c_int() for _ in range(4)]
             _lib.check(self._h, self._lib.mpx_bottleneck_tail_info(self._h, k, *[C.byref(x) for x in v]), "mpx_bottleneck_tail_info")
+            out.append(tuple(int(x.value) for x in v))
+        return out
+
+    def pointwise_tails(self):
+        """[(conv3, next conv1)] layer indices of the pairs that run as one pointwise-tail launch."""
+        out = []
+        for k in range(self._lib.mpx_num_pointwise_tails(self._h)):
+            v = [C.c_int() for _ in range(2)]
+            _lib.check(self._h, self._lib.mpx_pointwise_tail_info(self._h, k, *[C.byref(x) for x in v]), "mpx_pointwise_tail_info")
             out.append(tuple(int(x.value) for x in v))
         return out
 

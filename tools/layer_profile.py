@@ -25,7 +25,7 @@ dev = torch.device("cuda", 0)
 eng = MaskedForwardEngine(arch, max_batch=batch, device=0).load_state_dict(synth.make_state_dict(arch))
 if os.environ.get("MPX_NO_FUSION"):     # tool-only: run a stage's first conv3 and its downsample conv as two launches
     eng.set_fusion(False)
-if os.environ.get("MPX_FUSION_MASK"):   # tool-only: mpx_set_fusion mask (1 = round 2's plan: no block tails)
+if os.environ.get("MPX_FUSION_MASK"):   # tool-only: mpx_set_fusion mask (1 = round 2's plan: no block tails; 3 = no pointwise tails)
     eng.set_fusion(int(os.environ["MPX_FUSION_MASK"]))
 img = torch.from_numpy(synth.make_images(1, kind="noise")[0]).to(dev)
 seg = torch.from_numpy(synth.grid_segments()).to(dev)
@@ -104,6 +104,9 @@ for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
         mains = [k for k, n in enumerate(names) if n in (block + "conv3", block + "conv2")]
         if mains and prof["per_conv_ms"][mains[-1]] > 0:
             fused[mains[-1]] = li
+# a pointwise tail (conv3 + identity + the next block's conv1 in one launch) is booked on its conv3; its conv1 then has no time of its own
+ptail_of = {c3: n1 for c3, n1 in eng.pointwise_tails() if prof["per_conv_ms"][n1] == 0}
+ptail_next = {n1: c3 for c3, n1 in ptail_of.items()}
 
 
 def conv_flops(d):
@@ -123,8 +126,16 @@ for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
     if os.environ.get("MPX_PER_LAYER"):     # tool-only: one row per conv (a fused launch is booked on its main conv)
         if li in fused:     # the launch's own work: both K segments
             fl += conv_flops(eng.layers[fused[li]])
-        print("%-26s %5d %5d %2d %2d %4d %9.3f %9.1f %8.1f   tile %d%s" % (d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hout, ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9, eng.conv_tile(li),
-                                                                          ("   + %s in the same launch (K = %d + %d)" % (names[fused[li]], d.cin * d.ksize * d.ksize, eng.layers[fused[li]].cin)) if li in fused else ""))
+        if li in ptail_of and ms > 0:       # the pointwise tail's own work: conv3 and the next conv1
+            fl += conv_flops(eng.layers[ptail_of[li]])
+        note = ""
+        if li in fused:
+            note = "   + %s in the same launch (K = %d + %d)" % (names[fused[li]], d.cin * d.ksize * d.ksize, eng.layers[fused[li]].cin)
+        elif li in ptail_of and ms > 0:
+            note = "   + %s in the same launch (pointwise tail)" % names[ptail_of[li]]
+        elif li in ptail_next and ms == 0:
+            note = "   runs inside %s's launch" % names[ptail_next[li]]
+        print("%-26s %5d %5d %2d %2d %4d %9.3f %9.1f %8.1f   tile %d%s" % (d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hout, ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9, eng.conv_tile(li), note))
 print("-- grouped by shape --")
 for key, (n, ms, fl) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     print("%5d->%-5d k%d s%d out%-4d x%-3d %8.3f ms %5.1f%% %8.1f TFLOP/s%s" % (key[0], key[1], key[2], key[3], key[4], n, ms, 100 * ms / tot, fl / max(ms, 1e-9) / 1e9,
@@ -325,13 +336,20 @@ if arch == "googlenet":     # GoogLeNet: the clipped 3x3 max pools as launches o
              100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * prof["ms"]["head"] / reps / allms, allms,
              sum(prof["launches"].values()) // reps - 1))
 tails = eng.bottleneck_tails()
-if tails and not os.environ.get("MPX_NO_FUSION") and os.environ.get("MPX_FUSION_MASK", "3") == "3":
+if tails and not os.environ.get("MPX_NO_FUSION") and int(os.environ.get("MPX_FUSION_MASK", "3")) & 3 == 3:
     names = [d.name.decode() for d in eng.layers]
     print("-- block tails (one launch each: conv2 -> conv3 + identity -> next conv1; the time is booked on the conv2 row; the tail with the"
           " downsample branch runs its block's own conv1 too) --")
     for c2, c3, ds, n1 in tails:
         print("  %s%-16s + %s%s + %-16s %8.3f ms" % ((names[c2 - 1] + " + ") if ds >= 0 else "", names[c2], names[c3],
                                                       (" + " + names[ds]) if ds >= 0 else "", names[n1], prof["per_conv_ms"][c2] / reps))
+if ptail_of:
+    names = [d.name.decode() for d in eng.layers]
+    print("-- pointwise tails (one launch each: conv3 + identity -> next conv1; the time is booked on the conv3 row) --")
+    for c3, n1 in sorted(ptail_of.items()):
+        fl = conv_flops(eng.layers[c3]) + conv_flops(eng.layers[n1])
+        ms = prof["per_conv_ms"][c3] / reps
+        print("  %-16s + %-16s %8.3f ms %9.1f GFLOP %8.1f TFLOP/s" % (names[c3], names[n1], ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 layer1 = sum(ms for d, ms in zip(eng.layers, prof["per_conv_ms"]) if d.name.startswith(b"layer1.") or d.name == b"layer2.0.conv1") / reps
 if not eng.ses:     # (a ResNet's line; an EfficientNet engine has no layer1)
     print("layer1 (+ layer2.0.conv1): %.3f ms/batch" % layer1)

@@ -174,6 +174,20 @@ enum {
  * Three activation buffers of 112 * 112 * 96 elements per image (features.2.0's expanded map, MobileNetV2's size: 14.45 MB) plus the
  * staging (0.85 MB) and the SE gates (f32[1152], 4.6 KB): 15.3 MB per slot.  It stages through mpx_mask_apply_normalize only: the stem-table
  * and stem + pool entry points return MPX_E_STATE.
+ * -- or one of torchvision's two 32-group ResNeXts, the members of the ResNet family whose Bottleneck has groups = 32 (25.0 M / 88.8 M parameters,
+ * 4.2 / 16.4 GMAC per forward):
+ *   MPX_ARCH_RESNEXT + 50 / 101   resnext50_32x4d / resnext101_32x8d; every other id in [11000, 12000) is MPX_E_ARG (resnext101_64x4d included)
+ * A ResNeXt engine is the ResNet-50 / ResNet-101 engine -- the same stem and both stagings (mpx_mask_apply_normalize and the stem table), the
+ * same layer names, block depths (3, 4, 6, 3) / (3, 4, 23, 3), block outputs 256, 512, 1024, 2048, conv3 + downsample launches
+ * (mpx_conv_dual_bn_act), average pool and fc -- with an inner width of planes * width_per_group / 64 * 32 instead of planes: 128, 256, 512,
+ * 1024 (32x4d) or 256, 512, 1024, 2048 (32x8d).  conv1 and conv3 are dense 1x1 layers of those widths.  conv2 is the GROUPED 3x3 conv, width ->
+ * width in 32 groups of cg = width / 32 = 4, 8, 16, 32 (32x4d) or 8, 16, 32, 64 (32x8d) channels, stride 2 in the first block of layer2 / 3 /
+ * 4: mpx_conv_groups reports 32 on it, its weight tensor is torchvision's [width][cg][3][3], and it runs the grouped kernel, tile 16
+ * (csrc/mpx_gconv.h), through mpx_conv_bn_act like any other layer.  Its descriptor keeps mpx_conv_desc's layout with cin = cout = cout_pad =
+ * width and k_packed = the K of ONE channel block of max(cg, 16) channels, 9 * max(cg, 16) rounded up to 32 (160, 288 or 576); mpx_pack_conv_weights,
+ * which sees the descriptor alone, stays the dense packer and does not serve it.  No block tails and no pointwise tails (their shapes are
+ * the ResNets').  Four activation buffers of 56 * 56 * 256 elements per image as on a ResNet (14.5 MB per slot with the staging and the
+ * pooled stem planes) for 32x4d; of 56 * 56 * 512 (layer2.0.conv1's output) for 32x8d: 27.3 MB per slot.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -188,6 +202,7 @@ enum {
 #define MPX_ARCH_GOOGLENET 8000
 #define MPX_ARCH_SHUFFLENET 9000
 #define MPX_ARCH_EFFICIENTNET 10000
+#define MPX_ARCH_RESNEXT 11000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -213,7 +228,7 @@ int mpx_max_batch(const mpx_engine* h);
  * one workgroup per CU, so a forward batch is best a whole number of `num_cus * 256`-pixel rounds of the 14x14 maps
  * (engine.whole_round_batch). */
 int mpx_num_cus(const mpx_engine* h);
-/* 224/3/1000/1000 for the ImageNet ResNets, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, the ShuffleNetV2s and EfficientNet-B0, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
+/* 224/3/1000/1000 for the ImageNet ResNets and ResNeXts, the VGG networks, AlexNet, the DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, the ShuffleNetV2s and EfficientNet-B0, 28/1/10/16 and 32/3/10/16 for the small networks; any pointer may be NULL */
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch);
 size_t mpx_workspace_bytes(const mpx_engine* h);
 
@@ -237,6 +252,9 @@ int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
  * layer reads a WHOLE two-half stage map (cin = 2 bf logical channels at pitch 2 hp): its weight column of logical channel l sits at l
  * (l < bf) or hp + l - bf; 0, 0 for every other layer.  Any pointer may be NULL. */
 int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp);
+/* Groups of layer i: 32 on the conv2 of a ResNeXt engine's blocks (cin / 32 input channels per output channel: mpx_set_conv_weights takes
+ * [cout][cin / 32][3][3] there, and the layer runs tile 16 and nothing else), 1 on every other layer of every engine. */
+int mpx_conv_groups(const mpx_engine* h, int i, int* groups);
 /* The activation torchvision puts behind layer i that the layer itself does NOT apply because its one consumer takes it on load: *act = 0
  * none (every layer of every other network; ReLU6's clamp is reported by mpx_dwconv_desc.clamp_in), 1 SiLU (an EfficientNet-B0 engine's stem,
  * expand convs and features.8: mpx_conv_bn_act returns bn(conv(x)) there). */
@@ -342,6 +360,8 @@ int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1
  *       tile (7 and 2 force their own dual kernels), tile 7's or tile 2's dual kernel runs (bit-identical);
  *  12 = the patch kernel (6) as ONE persistent workgroup per CU: weight ring and patch buffers run on across tiles, register
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
+ *  16 = the grouped 3x3 kernel (csrc/mpx_gconv.h): one wave per 16 output pixels x channel block of max(cg, 16) channels, operands straight
+ *       from global memory (the conv2 of a ResNeXt block: its only tile, and the tile of nothing else; ids 15 and 17 are unassigned).
  * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default (a DenseNet's conv2, 3x3 128 -> 32,
  * defaults to 6, its topology's own choice: the cout <= 64 rule above was judged on 64 -> 64 layers and would give it 1).  (Ids 3, 5, 8 and 11 of
  * earlier rounds -- kernels that were measured and never became a default -- were removed; commit e4ccec8 is the last that has

@@ -140,6 +140,8 @@ SIGNATURES = {
     "mpx_se_scale": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_global_avgpool_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_se": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 8),
+    # ResNeXt: the groups of a layer (32 on a block's conv2, the grouped 3x3 kernel's layers)
+    "mpx_conv_groups": (_i, [_vp, _i, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@
 #include "mpx_pool3c.h"
 #include "mpx_shuffle.h"
 #include "mpx_mbconv.h"
+#include "mpx_gconv.h"
 
 #include <algorithm>
 #include <cmath>
@@ -77,6 +78,8 @@ struct ConvLayer {
     // 2 * in_hp = cin_pad; the packer puts logical weight column l at l (l < in_bf) or in_hp + l - in_bf.  in_hp = 0: columns as they come.
     int in_bf = 0;
     int in_hp = 0;
+    int groups = 1;         // > 1: a grouped 3x3 layer (a ResNeXt conv2: cin = cout = the width, cin / groups channels per group), whose packed planes
+                            // are mpx_gconv.h's -- cout_pad = cout rows of k_packed = gconv_kp(max(cin / groups, 16)), the K of ONE channel block
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
     int tile_default = -1;  // the layer's default where the topology sets one of its own (DenseNet's conv2); -1: default_tile(d)
     // downsample fusion (bottleneck blocks): the block's last 1x1 conv ("main") and its downsample 1x1 conv ("ds")
@@ -297,6 +300,8 @@ void set_name(char* dst, const std::string& s) {
 int default_tile(const mpx_conv_desc& d);
 bool patch_eligible(const mpx_conv_desc& d);
 
+constexpr int kGconvTile = 16;      // the grouped 3x3 kernel (mpx_gconv.h); ids 15 and 17 stay unassigned
+
 // torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
 int build_topology_small(mpx_engine* h);
 int build_topology_vgg(mpx_engine* h);
@@ -321,7 +326,14 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
+    // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
+    int groups = 1, wpg = 64;
     switch (h->arch) {
+        case MPX_ARCH_RESNEXT + 50: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = true; groups = 32; wpg = 4; break;
+        case MPX_ARCH_RESNEXT + 101:
+            depths[0] = 3; depths[1] = 4; depths[2] = 23; depths[3] = 3; h->bottleneck = true; groups = 32; wpg = 8;
+            h->act_elems_per_image = 2 * kActElemsPerImage;     // layer2.0.conv1 writes 56 * 56 * 512
+            break;
         case 18: depths[0] = 2; depths[1] = 2; depths[2] = 2; depths[3] = 2; h->bottleneck = false; break;
         case 34: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = false; break;
         case 50: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = true; break;
@@ -345,6 +357,26 @@ int build_topology(mpx_engine* h) {
         L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * cin;
         L.d.cout_pad = (int)round_up(cout, 128);
         L.tile = default_tile(L.d);
+        // (a ResNeXt engine hands the persistent kernels -- tiles 9, 10, 13, 14 and the dual form of 13 -- dense shapes that no served ResNet
+        // has: DESIGN.md 21 goes through every (shape, default tile) pair; none needed a default of its own)
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    // the grouped 3x3 conv2 of a ResNeXt block (mpx_gconv.h): w -> w, `groups` groups
+    auto add_gconv = [&](const std::string& name, const std::string& bn, int w, int stride, int hin) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = w; L.d.cout = w; L.d.ksize = 3; L.d.stride = stride; L.d.pad = 1;
+        L.d.hin = hin; L.d.hout = (hin + 2 - 3) / stride + 1;
+        L.d.relu = 1; L.d.residual = 0;
+        L.cin_pad = w;
+        L.cout_store = w;
+        L.groups = groups;
+        L.d.k_packed = gconv_kp(gconv_cb(w / groups));
+        L.d.cout_pad = w;
+        L.tile = L.tile_default = kGconvTile;
         h->convs.push_back(L);
         return (int)h->convs.size() - 1;
     };
@@ -365,15 +397,16 @@ int build_topology(mpx_engine* h) {
     add_op(OP_CONV, c, BUF_INPUT, 0, BUF_NONE, 0, 0);
     add_op(OP_MAXPOOL, -1, 0, BUF_STEM, BUF_NONE, 112, 64);      // the pooled planes have a buffer of their own: nothing overwrites them
     int X = BUF_STEM, cin = 64, hcur = 56;
-    const int widths[4] = {64, 128, 256, 512};
+    const int planes[4] = {64, 128, 256, 512};
     struct BlockRec { int c1, c2, c3, ds, hin; };
     std::vector<BlockRec> blocks;       // bottleneck blocks in forward order (the block-tail plan below is built from them)
     for (int s = 0; s < 4; ++s) {
-        const int w = widths[s];
+        const int pl = planes[s];                   // the block's output is pl * exp channels
+        const int w = pl * wpg / 64 * groups;       // its inner width (= pl on a ResNet)
         for (int b = 0; b < depths[s]; ++b) {
             const int stride = (b == 0 && s > 0) ? 2 : 1;
             const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
-            const bool ds = (b == 0) && (stride != 1 || cin != w * exp);
+            const bool ds = (b == 0) && (stride != 1 || cin != pl * exp);
             const int hout = hcur / stride;
             if (!h->bottleneck) {
                 const int T1 = pick({X});
@@ -396,16 +429,16 @@ int build_topology(mpx_engine* h) {
                 R.c1 = c = add_conv(p + "conv1", p + "bn1", cin, w, 1, 1, 0, hcur, 1, 0);
                 add_op(OP_CONV, c, X, T1, BUF_NONE, 0, 0);
                 const int T2 = pick({X, T1});
-                R.c2 = c = add_conv(p + "conv2", p + "bn2", w, w, 3, stride, 1, hcur, 1, 0);
+                R.c2 = c = groups > 1 ? add_gconv(p + "conv2", p + "bn2", w, stride, hcur) : add_conv(p + "conv2", p + "bn2", w, w, 3, stride, 1, hcur, 1, 0);
                 add_op(OP_CONV, c, T1, T2, BUF_NONE, 0, 0);
                 int res = X, dsc = -1;
                 if (ds) {
                     const int T3 = pick({X, T1, T2});
-                    R.ds = dsc = add_conv(p + "downsample.0", p + "downsample.1", cin, w * exp, 1, stride, 0, hcur, 0, 0);
+                    R.ds = dsc = add_conv(p + "downsample.0", p + "downsample.1", cin, pl * exp, 1, stride, 0, hcur, 0, 0);
                     add_op(OP_CONV, dsc, X, T3, BUF_NONE, 0, 0);
                     res = T3;
                 }
-                R.c3 = c = add_conv(p + "conv3", p + "bn3", w, w * exp, 1, 1, 0, hout, 1, 1);
+                R.c3 = c = add_conv(p + "conv3", p + "bn3", w, pl * exp, 1, 1, 0, hout, 1, 1);
                 add_op(OP_CONV, c, T2, T1, res, 0, 0, ds ? X : BUF_NONE);   // T1 is dead after conv2
                 if (ds) {
                     h->convs[c].fuse_partner = dsc; h->convs[c].fuse_main = true;
@@ -414,7 +447,7 @@ int build_topology(mpx_engine* h) {
                 blocks.push_back(R);
                 X = T1;
             }
-            cin = w * exp;
+            cin = pl * exp;
             hcur = hout;
         }
     }
@@ -1653,10 +1686,29 @@ int launch_patchp(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipS
     return patchp_fits<PatchTile0>(L.d) ? launch_conv_patchp<PatchTile0>(h, id, L, p, st) : launch_conv_patchp<PatchTile2>(h, id, L, p, st);
 }
 
+// The grouped 3x3 kernel (mpx_gconv.h, tile id 16): one wave per 16 output pixels x channel block, GCONV_WAVES blocks per workgroup.  The
+// grid is not capped: ceil(M / 16) <= 2^27 workgroups in x, the block quads in y.
+int launch_gconv(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    const int cg = L.groups > 1 ? L.d.cin / L.groups : 0, cb = gconv_cb(cg);
+    if (L.groups <= 1 || L.d.ksize != 3 || L.d.pad != 1 || (L.d.stride != 1 && L.d.stride != 2) || L.d.cin != L.d.cout || L.d.cin % L.groups ||
+        (cg != 4 && cg != 8 && cg != 16 && cg != 32 && cg != 64) || L.d.cin % (cb * GCONV_WAVES) || L.d.k_packed != gconv_kp(cb) || L.cin_pad != L.d.cin ||
+        L.cout_store != L.d.cout)
+        return fail(h, MPX_E_INTERNAL, "grouped conv: %s is not a 3x3 pad-1 layer of 4, 8, 16, 32 or 64 channels per group", L.d.name);
+    if (p.r_hi || p.y_f32 || p.k1) return fail(h, MPX_E_ARG, "grouped conv: %s takes no residual operand and no fp32 output", L.d.name);
+    p.n_tiles_c = L.d.cin / cb;
+    const dim3 grid((unsigned)(((long long)p.M + 15) / 16), (unsigned)(p.n_tiles_c / GCONV_WAVES)), block(64 * GCONV_WAVES);
+    switch (cb) {
+        case 16: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<16>, grid, block, 0, st, p); break;
+        case 32: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<32>, grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<64>, grid, block, 0, st, p); break;
+    }
+    return launched(h, id);
+}
+
 struct TileRow {
     int id;
     LaunchFn launch;
-    bool (*eligible)(const mpx_conv_desc&);     // nullptr: every layer
+    bool (*eligible)(const mpx_conv_desc&);     // nullptr: every layer (tile 16: every GROUPED layer -- a layer is grouped by ConvLayer::groups, not by its descriptor: eligible())
     const char* refusal;                        // why mpx_set_conv_tile refuses a layer that is not eligible
     int dual;       // the tile whose DUAL kernel (launch_conv_tile<Cfg, true>) runs the layer fused with its downsample conv; -1: none
     bool split;     // the images behind the last whole round of tiles go to tile 2 (launch_conv)
@@ -1679,6 +1731,7 @@ const TileRow kTiles[] = {
      "the persistent 256x256 kernel runs 1x1 stride-1 layers with cout % 256 == 0, cin % 64 == 0 and no residual operand", -1, true},
     {14, launch_convw, convw_eligible,
      "the weights-in-registers expanding-1x1 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin = 256", 7, false},
+    {kGconvTile, launch_gconv, nullptr, "the grouped 3x3 kernel runs grouped layers (a ResNeXt block's conv2) and nothing else", -1, false},
 };
 
 // Dynamic LDS ceiling of every conv kernel (mpx_create): the kernels of kTiles with their DUAL forms, the stem + pool kernel, the block
@@ -1731,6 +1784,7 @@ const TileRow* find_tile(int id) {
 // the 256-row kernels (mpx_conv256.h, mpx_conv256p.h, mpx_convx.h, mpx_convw.h) and the patch kernels (cin = k_per_tap is their row pitch)
 // read dense pixel rows.
 bool eligible(const TileRow& r, const ConvLayer& L) {
+    if (L.groups > 1 || r.id == kGconvTile) return L.groups > 1 && r.id == kGconvTile;     // a grouped layer runs tile 16, and tile 16 nothing else
     return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && !L.x_pitch && r.eligible(L.d));
 }
 
@@ -2310,6 +2364,44 @@ int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float*
     return 0;
 }
 
+// The packed planes of a grouped 3x3 layer (mpx_gconv.h) from torchvision's [cout][cin / groups][3][3]: per channel block of CB = max(cg, 16)
+// channels, rows = its output channels, k = (ky * 3 + kx) * CB + (the input channel's index within the block).  Output channel co of group g
+// reads input channels [g * cg, (g + 1) * cg): inside its block these are columns (g * cg - block * CB) + ci; every other column of the row
+// (the other groups of a cg = 4 / 8 block) and the K padding behind tap 8 stay exact zeros.  Row scaling, scale and shift are
+// pack_conv_weights'.
+int pack_gconv_weights(const mpx_conv_desc* d, int groups, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
+                       float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale, float* shift) {
+    const int C = d->cout, cg = C / groups, cb = gconv_cb(cg), K = gconv_kp(cb);
+    if (d->cin != C || C % groups || d->ksize != 3 || d->k_packed != K || d->cout_pad != C || C % cb || !gamma || !beta || !mean || !var) return MPX_E_ARG;
+    std::memset(w_hi, 0, (size_t)C * K * 2);
+    std::memset(w_lo, 0, (size_t)C * K * 2);
+    for (int co = 0; co < C; ++co) {
+        const float* wc = w + (size_t)co * cg * 9;
+        float mx = 0.f;
+        for (int j = 0; j < cg * 9; ++j) mx = std::fmax(mx, std::fabs(wc[j]));
+        int e = 0;
+        if (mx > 0.f && std::isfinite(mx)) {
+            int ex;
+            std::frexp(mx, &ex);
+            e = 10 - ex;
+        }
+        const int blk = co / cb, r = co - blk * cb, c0 = co / cg * cg - blk * cb;
+        for (int t = 0; t < 9; ++t)
+            for (int ci = 0; ci < cg; ++ci) {
+                const float sv = std::ldexp(wc[(size_t)ci * 9 + t], e);
+                const half_t hi = (half_t)sv;
+                const half_t lo = (half_t)(sv - (float)hi);
+                const size_t at = gconv_w_index(blk, r, t * cb + c0 + ci, cb);
+                w_hi[at] = half_bits(hi);
+                w_lo[at] = half_bits(lo);
+            }
+        const double s = (double)gamma[co] / std::sqrt((double)var[co] + (double)eps);
+        scale[co] = (float)std::ldexp(s, -e);
+        shift[co] = (float)((double)beta[co] - (double)mean[co] * s);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2478,7 +2570,8 @@ int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv
     const size_t n = (size_t)L.d.cout_pad * L.d.k_packed;
     std::vector<uint16_t> hi(n), lo(n);
     std::vector<float> sc(L.d.cout_pad), sh(L.d.cout_pad);
-    int rc = pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data());
+    int rc = L.groups > 1 ? pack_gconv_weights(&L.d, L.groups, w, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data())
+                          : pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data());
     if (rc) return fail(h, rc, "pack failed for %s", L.d.name);
     MPX_SET_DEVICE(h);
     MPX_HIP(h, hipMemcpy(L.w_hi, hi.data(), n * 2, hipMemcpyHostToDevice));
@@ -2536,6 +2629,8 @@ int mpx_set_conv_tile(mpx_engine* h, int i, int tile) {
         for (const TileRow& k : kTiles) ids += (ids.empty() ? "" : ", ") + std::to_string(k.id);
         return fail(h, MPX_E_ARG, "set_conv_tile: unknown tile %d (product ids: %s)", tile, ids.c_str());
     }
+    if (L.groups > 1 && tile != kGconvTile)
+        return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: a grouped layer runs the grouped 3x3 kernel (tile %d) only (%s is one)", tile, kGconvTile, L.d.name);
     if (!eligible(*r, L)) return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: %s (%s is not one)", tile, r->refusal, L.d.name);
     L.tile = tile;
     return 0;
@@ -3193,6 +3288,12 @@ int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_l
     return 0;
 }
 
+int mpx_conv_groups(const mpx_engine* h, int i, int* groups) {
+    if (!h || !groups || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    *groups = h->convs[i].groups;
+    return 0;
+}
+
 int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset) {
     if (!h || !pitch || !offset || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
     const ConvLayer& L = h->convs[i];
@@ -3628,7 +3729,7 @@ double mpx_flops_per_forward(const mpx_engine* h) {
     if (!h) return 0.0;
     double macs = 0.0;
     for (const ConvLayer& L : h->convs)
-        macs += (double)L.d.hout * L.d.hout * L.d.cout * L.d.cin * L.d.ksize * L.d.ksize;
+        macs += (double)L.d.hout * L.d.hout * L.d.cout * (L.d.cin / L.groups) * L.d.ksize * L.d.ksize;
     for (const DwLayer& D : h->dws) {
         const int ho = (D.d.hin - 1) / D.d.stride + 1;
         macs += (double)ho * ho * D.d.channels * D.ksize * D.ksize;

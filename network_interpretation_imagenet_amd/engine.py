@@ -35,6 +35,7 @@ ARCH_IDS["squeezenet1_1"] = 7011  # torchvision's SqueezeNet 1.1 (MPX_ARCH_SQUEE
 ARCH_IDS["googlenet"] = 8000      # torchvision's GoogLeNet without the aux classifiers (MPX_ARCH_GOOGLENET); inception_v3 is not served
 # torchvision's ShuffleNetV2 family (MPX_ARCH_SHUFFLENET + 10 x the width multiplier)
 ARCH_IDS.update({"shufflenet_v2_x0_5": 9005, "shufflenet_v2_x1_0": 9010, "shufflenet_v2_x1_5": 9015, "shufflenet_v2_x2_0": 9020})
+ARCH_IDS.update({"resnext50_32x4d": 11050, "resnext101_32x8d": 11101})    # torchvision's 32-group ResNeXts (MPX_ARCH_RESNEXT + 50 / 101); resnext101_64x4d and the Wide ResNets are not served
 ARCH_IDS["efficientnet_b0"] = 10000     # torchvision's EfficientNet-B0 (MPX_ARCH_EFFICIENTNET + 0); B1 .. B7 (trained at 240 and more) are not served
 
 
@@ -131,6 +132,9 @@ class MaskedForwardEngine:
         An EfficientNet-B0 slot holds 15.3 MB -- three 112x112x96 split-fp16 activation buffers (features.2.0's expanded map, MobileNetV2's
         size: a block's input, its expanded map and the depthwise output the SE layer scales in place: 14.5 MB), the input staging and the
         SE gates -- and keeps the default of 512 (7.8 GB).
+        A ResNeXt-50 32x4d slot is a ResNet slot (14.5 MB: its largest map is 56x56x256 too).  A ResNeXt-101 32x8d slot holds 27.3 MB -- four
+        56x56x512 split-fp16 activation buffers (layer2.0.conv1's output: 25.7 MB), the input staging and the pooled stem planes -- and
+        keeps the default of 512 (14 GB).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -141,7 +145,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -186,6 +190,11 @@ class MaskedForwardEngine:
             sd_ = _lib.SeDesc()
             _lib.check(h, self._lib.mpx_se_info(h, k, C.byref(sd_)), "mpx_se_info")
             self.ses.append(sd_)
+        self.groups = []        # groups per conv layer: 32 on a ResNeXt block's conv2 (weight [cout][cin / 32][3][3]), 1 everywhere else
+        for i in range(len(self.layers)):
+            gr = C.c_int()
+            _lib.check(h, self._lib.mpx_conv_groups(h, i, C.byref(gr)), "mpx_conv_groups")
+            self.groups.append(int(gr.value))
         self.flops_per_forward = float(self._lib.mpx_flops_per_forward(h))
         self.num_cus = int(self._lib.mpx_num_cus(h))        # what the persistent kernels' grids are sized from (whole_round_batch)
         self._mean, self._std = _f3(MEAN), _f3(STD)
@@ -255,7 +264,7 @@ class MaskedForwardEngine:
 
     # ---- weights ----
     def load_state_dict(self, sd, eps=None, only=None):
-        """`sd`: torchvision ResNet / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet / ShuffleNetV2 / EfficientNet-B0 state_dict (key names as `models.<arch>().state_dict()`), e.g.
+        """`sd`: torchvision ResNet / ResNeXt (conv2.weight [width][width / 32][3][3], what mpx_conv_groups says) / VGG / AlexNet / DenseNet / MobileNetV2 / SqueezeNet 1.1 / GoogLeNet / ShuffleNetV2 / EfficientNet-B0 state_dict (key names as `models.<arch>().state_dict()`), e.g.
         torch.load(local_path, weights_only=True); keys the engine has no use for (`num_batches_tracked`, the `aux1.` / `aux2.` classifiers
         of torchvision's GoogLeNet checkpoint) are ignored.  `eps`: the BatchNorms' epsilon; None = default_bn_eps(arch), torchvision's value
         for the architecture (1e-5; 1e-3 for googlenet).  `module.` prefixes (DataParallel) are accepted.  `only`: conv names
@@ -286,8 +295,8 @@ class MaskedForwardEngine:
             name, bn = d.name.decode(), d.bn_name.decode()
             if only is not None and name not in only:
                 continue
-            w4 = (d.cout, d.cin, d.ksize, d.ksize)
-            wshape = (d.cout, d.cin * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
+            w4 = (d.cout, d.cin // self.groups[i], d.ksize, d.ksize)
+            wshape = (d.cout, w4[1] * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
             # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7] (AlexNet's classifier.1 [4096, 256 * 6 * 6]), channel-major as torch.flatten of NCHW
             w = get(name + ".weight", wshape).reshape(w4).contiguous()
             if not bn and self.norms and i != len(self.layers) - 1:

@@ -46,6 +46,11 @@ ARCH_DEPTHS = {
     "resnet152": ("bottleneck", (3, 8, 36, 3)),
 }
 FC_GAIN = 2.5
+# torchvision's 32-group ResNeXts: (block depths, width_per_group, gain of every bn3); groups = 32, inner width = planes * width_per_group / 64 * 32.
+# The ResNets' bn3 gain of 0.1 leaves the fp64 softmax of the masked rows flat (its peak 0.005 .. 0.04 on the rows tests/resnext_ref.py
+# scores); 0.45 / 0.25 puts the peak of every such row inside [0.05, 0.95] with a top-two margin above 1e-2 (tests/test_resnext_cpu.py).
+RESNEXT_ARCHS = {"resnext50_32x4d": ((3, 4, 6, 3), 4, 0.45), "resnext101_32x8d": ((3, 4, 23, 3), 8, 0.25)}
+RESNEXT_GROUPS = 32
 
 # torchvision vgg.py cfgs ("M" = MaxPool2d(2, 2))
 VGG_CFGS = {
@@ -439,12 +444,44 @@ def make_efficientnet_state_dict(seed=7):
     return sd
 
 
+def make_resnext_state_dict(arch, seed=7):
+    """OrderedDict with the key set and shapes of models.resnext50_32x4d() / resnext101_32x8d(): the ResNets' names, conv1 [width][cin][1][1],
+    conv2 [width][width / 32][3][3] (32 groups), conv3 [4 * planes][width][1][1].  Conv gains come from the fan-in (9 * cg for conv2); the
+    BatchNorm draws are the ResNets', with a larger gain on bn3 (RESNEXT_ARCHS)."""
+    depths, wpg, last = RESNEXT_ARCHS[arch]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    _conv(sd, "conv1", 3, 64, 7, g)
+    _bn(sd, "bn1", 64, g)
+    cin = 64
+    for s, (pl, d) in enumerate(zip((64, 128, 256, 512), depths)):
+        w = pl * wpg // 64 * RESNEXT_GROUPS
+        for b in range(d):
+            stride = 2 if (b == 0 and s > 0) else 1
+            p = "layer%d.%d." % (s + 1, b)
+            _conv(sd, p + "conv1", cin, w, 1, g)
+            _bn(sd, p + "bn1", w, g)
+            _conv(sd, p + "conv2", w // RESNEXT_GROUPS, w, 3, g)
+            _bn(sd, p + "bn2", w, g)
+            _conv(sd, p + "conv3", w, pl * 4, 1, g)
+            _bn(sd, p + "bn3", pl * 4, g, last=last)
+            if b == 0 and (stride != 1 or cin != pl * 4):
+                _conv(sd, p + "downsample.0", cin, pl * 4, 1, g)
+                _bn(sd, p + "downsample.1", pl * 4, g)
+            cin = pl * 4
+    sd["fc.weight"] = torch.randn(1000, cin, generator=g) * (FC_GAIN / cin ** 0.5)
+    sd["fc.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict) key set."""
     if arch == "efficientnet_b0":
         return make_efficientnet_state_dict(seed)
+    if arch in RESNEXT_ARCHS:
+        return make_resnext_state_dict(arch, seed)
     if arch in SHUFFLENET_WIDTHS:
         return make_shufflenet_state_dict(arch, seed)
     if arch == "googlenet":

@@ -1,0 +1,171 @@
+"""ResNeXt-50 32x4d / ResNeXt-101 32x8d without a GPU: the synthetic state_dict with torchvision's keys and shapes, the published parameter
+counts, the MACs counted two ways, the arch ids, the names that stay unserved, the new C-ABI symbol, and the conditions on exactly the rows
+the GPU test scores (tests/resnext_ref.py E2E_CASES): the fp64 top-two margin, the softmax peak, and that grouping is live on them."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import resnext_ref as ref
+from network_interpretation_imagenet_amd import _lib, engine, synth
+from oracle import scorer
+
+ARCHS = ("resnext50_32x4d", "resnext101_32x8d")
+PARAMS = {"resnext50_32x4d": 25028904, "resnext101_32x8d": 88791336}       # torchvision's published parameter counts
+# depths, inner widths, block outputs, channels per group: the issue's table
+TABLE = {"resnext50_32x4d": ((3, 4, 6, 3), (128, 256, 512, 1024), (256, 512, 1024, 2048), (4, 8, 16, 32)),
+         "resnext101_32x8d": ((3, 4, 23, 3), (256, 512, 1024, 2048), (256, 512, 1024, 2048), (8, 16, 32, 64))}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bn_keys(prefix, c):
+    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,))]
+
+
+def _expected_keys(arch):
+    """models.<arch>().state_dict() without num_batches_tracked: key -> shape, written out from the table."""
+    depths, widths, outs, cgs = TABLE[arch]
+    out = [("conv1.weight", (64, 3, 7, 7))] + _bn_keys("bn1", 64)
+    cin = 64
+    for s in range(4):
+        for b in range(depths[s]):
+            p = "layer%d.%d." % (s + 1, b)
+            out += [(p + "conv1.weight", (widths[s], cin, 1, 1))] + _bn_keys(p + "bn1", widths[s])
+            out += [(p + "conv2.weight", (widths[s], cgs[s], 3, 3))] + _bn_keys(p + "bn2", widths[s])
+            out += [(p + "conv3.weight", (outs[s], widths[s], 1, 1))] + _bn_keys(p + "bn3", outs[s])
+            if b == 0:
+                out += [(p + "downsample.0.weight", (outs[s], cin, 1, 1))] + _bn_keys(p + "downsample.1", outs[s])
+            cin = outs[s]
+    return out + [("fc.weight", (1000, 2048)), ("fc.bias", (1000,))]
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_synth_resnext_state_dict_has_torchvisions_keys_shapes_and_parameter_count(arch):
+    sd = synth.make_state_dict(arch)
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _expected_keys(arch)
+    assert list(sd) == list(synth.make_resnext_state_dict(arch))
+    assert all(v.dtype == torch.float32 for v in sd.values())
+    params = sum(v.numel() for k, v in sd.items() if k.endswith((".weight", ".bias")))     # nn.Parameters: no running statistics
+    assert params == PARAMS[arch] == ref.ARCHS[arch][2]
+    assert not any(k.endswith(".bias") and sd[k[:-4] + "weight"].dim() == 4 for k in sd)    # no conv has a bias
+    # the conv gain comes from the fan-in: 9 cg on a grouped layer
+    depths, widths, _outs, cgs = TABLE[arch]
+    for s in range(4):
+        w = sd["layer%d.1.conv2.weight" % (s + 1)]
+        assert abs(w.std().item() / (2.0 / (9 * cgs[s])) ** 0.5 - 1) < 0.05
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_macs_two_ways_and_the_topology_is_the_table(arch):
+    """From the conv list, and by counting inside the reference's own conv calls on a real forward (no hooks: the reference counts from
+    the tensors each call sees)."""
+    depths, widths, outs, cgs = TABLE[arch]
+    convs = ref.topology(arch)
+    count = [0]
+    with torch.no_grad():
+        ref.forward(synth.make_state_dict(arch), torch.zeros(1, 3, 224, 224), arch, count=count)
+    by_hand = 112 * 112 * 64 * 147 + 2048 * 1000
+    cin, h = 64, 56
+    for s in range(4):
+        for b in range(depths[s]):
+            stride = 2 if (b == 0 and s > 0) else 1
+            ho = h // stride
+            by_hand += h * h * cin * widths[s] + ho * ho * widths[s] * cgs[s] * 9 + ho * ho * widths[s] * outs[s]
+            if b == 0:
+                by_hand += ho * ho * cin * outs[s]
+            cin, h = outs[s], ho
+    print("%s: %d MACs per forward, %d convs" % (arch, count[0], len(convs)))
+    assert ref.macs(arch) == count[0] == by_hand
+    assert len(convs) == 1 + 3 * sum(depths) + 4 + 1 and convs[-1][0] == "fc" and len({c[0] for c in convs}) == len(convs)
+    grouped = [c for c in convs if c[11] > 1]
+    assert len(grouped) == sum(depths) == {"resnext50_32x4d": 16, "resnext101_32x8d": 33}[arch]
+    assert all(c[11] == 32 and c[4] == 3 and c[6] == 1 and c[2] == c[3] and c[0].endswith(".conv2") for c in grouped)
+    assert sorted({c[2] // 32 for c in grouped}) == list(cgs)
+    assert [(c[2], c[5]) for c in grouped if c[0].endswith(".0.conv2")] == [(widths[0], 1), (widths[1], 2), (widths[2], 2), (widths[3], 2)]
+    # the largest activation: what the engine sizes its buffers from
+    assert max(c[3] * c[8] * c[8] for c in convs[1:]) == (56 * 56 * 256 if arch == "resnext50_32x4d" else 56 * 56 * 512)
+    # the pitch of a grouped layer's planes is a multiple of 128: no pad channels
+    assert all(c[2] % 128 == 0 for c in grouped)
+
+
+def test_resnext_arch_ids_are_unique_and_the_neighbours_stay_unsupported():
+    assert engine.ARCH_IDS["resnext50_32x4d"] == 11050 and engine.ARCH_IDS["resnext101_32x8d"] == 11101
+    ids = list(engine.ARCH_IDS.values())
+    assert len(ids) == len(set(ids))
+    for name in ("resnext101_64x4d", "wide_resnet50_2", "wide_resnet101_2"):
+        assert name not in engine.ARCH_IDS
+        with pytest.raises(ValueError, match="ResNeXt"):
+            engine.MaskedForwardEngine(name)
+    for name in ("mobilenet_v3_small", "efficientnet_b1", "efficientnet_v2_s", "mnasnet1_0", "regnet_y_400mf", "inception_v3", "squeezenet1_0", "densenet161"):
+        with pytest.raises(ValueError, match="AlexNet"):
+            engine.MaskedForwardEngine(name)
+    assert all(engine.default_bn_eps(a) == 1e-5 for a in ARCHS)
+
+
+@pytest.mark.parametrize("arch_id", [11000, 11051, 11999])
+def test_unknown_resnext_id_is_refused(mpx_lib, arch_id):
+    """mpx_create rejects the id before it touches a device."""
+    h = C.c_void_p()
+    assert mpx_lib.mpx_create(arch_id, 4, 0, C.byref(h)) == -1 and not h.value
+
+
+def test_new_c_abi_symbol_is_in_the_header_the_binding_and_the_library(mpx_lib):
+    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
+        header = fh.read()
+    assert "#define MPX_ARCH_RESNEXT 11000" in header
+    assert re.search(r"\bint mpx_conv_groups\(const mpx_engine\* h, int i, int\* groups\);", header)
+    assert "mpx_conv_groups" in _lib.SIGNATURES
+    assert getattr(mpx_lib, "mpx_conv_groups") is not None
+    g = C.c_int(7)
+    assert mpx_lib.mpx_conv_groups(None, 0, C.byref(g)) == -1 and g.value == 7       # a null engine is refused before anything is written
+    # the descriptor keeps its layout
+    assert [f[0] for f in _lib.ConvDesc._fields_] == ["name", "bn_name", "cin", "cout", "ksize", "stride", "pad", "hin", "hout", "relu", "residual",
+                                                      "k_packed", "cout_pad"]
+    assert C.sizeof(_lib.ConvDesc) == 96 + 11 * 4
+
+
+def test_restatement_is_torch_conv2d_with_groups_and_the_dense_switch_is_the_tiled_dense_conv():
+    """The `dense` switch of the restatement is what its docstring says: a dense conv whose weight is the grouped one tiled over all 32
+    input groups (zero-extended, then every off-block entry set to the group's own weights)."""
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 128, 9, 9, generator=g, dtype=torch.float64)
+    w = torch.randn(128, 4, 3, 3, generator=g, dtype=torch.float64)
+    for stride in (1, 2):
+        dense = w.repeat(1, 32, 1, 1)
+        want = F.conv2d(x, dense, None, stride, 1)
+        assert (ref.conv2(x, w, stride, dense=True) - want).abs().max() <= 1e-12 * want.abs().max()
+        zero_ext = torch.zeros(128, 128, 3, 3, dtype=torch.float64)
+        for co in range(128):
+            zero_ext[co, co // 4 * 4:co // 4 * 4 + 4] = w[co]
+        want = F.conv2d(x, zero_ext, None, stride, 1)
+        assert (ref.conv2(x, w, stride) - want).abs().max() <= 1e-12 * want.abs().max()
+        assert (dense[zero_ext != 0] == zero_ext[zero_ext != 0]).all()       # the block diagonal is the grouped weight itself
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_preconditions_on_the_rows_the_gpu_test_scores(golden_dir, arch):
+    """EVERY row of resnext_ref.E2E_CASES: fp64 top-two logit margin >= 1e-3 and fp64 softmax peak inside [0.05, 0.95] -- the GPU test then
+    compares the argmax of every row, none excluded -- and with groups treated as 1 at least half of the rows move by more than 2e-3: a
+    kernel that ignored grouping could not pass."""
+    sd = synth.make_state_dict(arch)
+    total = 0
+    for kind, (img, seg, onoff, label, s64, logits64) in ref.e2e_rows(golden_dir, arch).items():
+        top2 = np.sort(logits64, axis=1)[:, -2:]
+        gap = top2[:, 1] - top2[:, 0]
+        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
+        s_dense, _l = ref.score_masks_fp64(sd, arch, scorer.to_tensor_normalize(img), seg, onoff, label, dense=True)
+        moved = np.abs(s_dense - s64)
+        n = int((moved > 2e-3).sum())
+        print("%s %s: %d rows, label %d, scores %.4f .. %.4f, smallest fp64 top-two margin %.4f, softmax peak %.4f .. %.4f; groups as 1: %d rows move by more than 2e-3 (median %.4f)"
+              % (arch, kind, len(s64), label, s64.min(), s64.max(), gap.min(), peaks.min(), peaks.max(), n, np.median(moved)))
+        assert gap.min() >= 1e-3
+        assert peaks.min() >= 0.05 and peaks.max() <= 0.95
+        assert 2 * n >= len(s64), np.sort(moved)
+        assert np.isfinite(logits64).all() and np.abs(logits64).max() < 1e3
+        total += len(s64)
+    assert total == {"resnext50_32x4d": 12, "resnext101_32x8d": 4}[arch]
+    assert [c[:2] for c in ref.E2E_CASES["resnext50_32x4d"]] == [("felz", 8), ("grid", 4)]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer conv timing (HIP events inside the engine) for one forward batch.
-usage: python tools/layer_profile.py [arch] [batch] [reps]
+usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d add the
+                                                                 grouped 3x3 launches as rows of their own, with their bytes and TB/s)
        MPX_PER_LAYER=1 ...    one row per conv with its tile
 A conv + downsample conv that run as ONE launch (K-concatenated) are booked on the main conv; they get rows of their own, with both convs'
 FLOPs, under the grouped table (the grouped rows count the main conv's FLOPs only).
@@ -109,14 +110,16 @@ ptail_of = {c3: n1 for c3, n1 in eng.pointwise_tails() if prof["per_conv_ms"][n1
 ptail_next = {n1: c3 for c3, n1 in ptail_of.items()}
 
 
-def conv_flops(d):
-    return 2.0 * batch * d.hout * d.hout * d.cout * d.cin * d.ksize * d.ksize
+def conv_flops(li):
+    """FLOPs of conv layer `li` over the batch; a grouped layer (eng.groups: 32 on a ResNeXt block's conv2) reads cin / groups channels."""
+    d = eng.layers[li]
+    return 2.0 * batch * d.hout * d.hout * d.cout * (d.cin // eng.groups[li]) * d.ksize * d.ksize
 
 
 print("%-26s %5s %5s %2s %2s %4s %9s %9s %8s" % ("layer", "cin", "cout", "k", "s", "hout", "ms", "GFLOP", "TFLOP/s"))
 for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
     ms /= reps
-    fl = conv_flops(d)
+    fl = conv_flops(li)
     key = (d.cin, d.cout, d.ksize, d.stride, d.hout)
     a = groups.setdefault(key, [0, 0.0, 0.0])
     a[0] += 1
@@ -125,9 +128,9 @@ for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
     tot += ms
     if os.environ.get("MPX_PER_LAYER"):     # tool-only: one row per conv (a fused launch is booked on its main conv)
         if li in fused:     # the launch's own work: both K segments
-            fl += conv_flops(eng.layers[fused[li]])
+            fl += conv_flops(fused[li])
         if li in ptail_of and ms > 0:       # the pointwise tail's own work: conv3 and the next conv1
-            fl += conv_flops(eng.layers[ptail_of[li]])
+            fl += conv_flops(ptail_of[li])
         note = ""
         if li in fused:
             note = "   + %s in the same launch (K = %d + %d)" % (names[fused[li]], d.cin * d.ksize * d.ksize, eng.layers[fused[li]].cin)
@@ -144,9 +147,40 @@ if fused:       # the grouped rows above book these launches under their main co
     print("-- conv + downsample conv in one launch (K-concatenated), rows of their own; GFLOP = both convs --")
     for li, lj in sorted(fused.items()):
         d, ms = eng.layers[li], prof["per_conv_ms"][li] / reps
-        fl = conv_flops(d) + conv_flops(eng.layers[lj])
+        fl = conv_flops(li) + conv_flops(lj)
         print("%-16s + %-24s K %4d + %-4d out%-3d %8.3f ms %5.1f%% %9.1f GFLOP %8.1f TFLOP/s" % (
             names[li], names[lj], d.cin * d.ksize * d.ksize, eng.layers[lj].cin, d.hout, ms, 100 * ms / tot, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
+if max(eng.groups) > 1:     # ResNeXt: the grouped 3x3 launches (csrc/mpx_gconv.h, tile 16) as rows of their own, by their bytes and by their MFMA work
+    print("-- grouped 3x3 convs (tile 16: one launch each); bytes = split-fp16 input + output planes once; MFMA TFLOP/s = the three f16 products over "
+          "channel blocks of max(cg, 16) and K padded to 32 (4x / 2x the algorithmic FLOPs at cg = 4 / 8) --")
+    tot_g = g_bytes = g_fl = 0.0
+    by_shape = {}
+    for li, (d, ms) in enumerate(zip(eng.layers, prof["per_conv_ms"])):
+        if eng.groups[li] == 1:
+            continue
+        ms /= reps
+        cg = d.cin // eng.groups[li]
+        cb = max(cg, 16)
+        nbytes = batch * 4.0 * d.cin * (d.hin * d.hin + d.hout * d.hout)
+        mfma_fl = 3 * 2.0 * batch * d.hout * d.hout * d.cout * d.k_packed     # every output channel x the padded K of its block, three products
+        tot_g += ms
+        g_bytes += nbytes
+        g_fl += conv_flops(li)
+        a = by_shape.setdefault((d.cin, cg, d.stride, d.hin), [0, 0.0, 0.0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += ms
+        a[2] += nbytes
+        a[3] += conv_flops(li)
+        a[4] += mfma_fl
+        if os.environ.get("MPX_PER_LAYER"):
+            print("%-18s C %4d cg %2d (block %2d, K %3d) s%d %3dx%-3d %8.3f ms %8.1f MB %6.2f TB/s %7.1f TFLOP/s algorithmic %7.1f MFMA TFLOP/s" % (
+                d.name.decode(), d.cin, cg, cb, d.k_packed, d.stride, d.hin, d.hin, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9,
+                conv_flops(li) / max(ms, 1e-9) / 1e9, mfma_fl / max(ms, 1e-9) / 1e9))
+    for (c, cg, st, hin), (n, ms, nbytes, fl, mfl) in sorted(by_shape.items(), key=lambda kv: -kv[1][1]):
+        print("C %4d cg %2d s%d %3dx%-3d x%-2d %8.3f ms %5.1f%% of the convs %9.1f MB %6.2f TB/s %7.1f TFLOP/s algorithmic %7.1f MFMA TFLOP/s" % (
+            c, cg, st, hin, hin, n, ms, 100 * ms / tot, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9, fl / max(ms, 1e-9) / 1e9, mfl / max(ms, 1e-9) / 1e9))
+    print("grouped convs total %.3f ms/batch = %.1f %% of the conv time (%.1f %% of their FLOPs), %.1f MB -> %.2f TB/s, %.1f TFLOP/s algorithmic"
+          % (tot_g, 100 * tot_g / tot, 100 * g_fl / (eng.flops_per_forward * batch), g_bytes / 1e6, g_bytes / max(tot_g, 1e-9) / 1e9, g_fl / max(tot_g, 1e-9) / 1e9))
 if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + ReLU once per consumer of a block's concatenation, the transitions' pools
     print("-- concat-append + BN + ReLU (mpx_concat_bn_relu: one launch per stand-alone BatchNorm), grouped by map; bytes = split-fp16 read + written --")
     by_map = {}
@@ -265,7 +299,7 @@ if arch.startswith("squeezenet"):     # SqueezeNet: the Fire modules' convs by t
         tot_ms[kind] += ms
         print("%-22s %4d->%-4d k%d %3dx%-3d pitch %4d offset %3d tile %d %8.3f ms %8.1f MB %6.2f TB/s %7.1f TFLOP/s" % (
             d.name.decode(), d.cin, d.cout, d.ksize, d.hout, d.hout, pitch.value, off.value, eng.conv_tile(li), ms, nbytes / 1e6,
-            nbytes / max(ms, 1e-9) / 1e9, conv_flops(d) / max(ms, 1e-9) / 1e9))
+            nbytes / max(ms, 1e-9) / 1e9, conv_flops(li) / max(ms, 1e-9) / 1e9))
     for kind in tot_bytes:
         print("%-10s total %8.3f ms/batch %9.1f MB -> %5.2f TB/s" % (kind, tot_ms[kind], tot_bytes[kind] / 1e6, tot_bytes[kind] / max(tot_ms[kind], 1e-9) / 1e9))
     # the average pool (mpx_global_avgpool_logits) shares the profile's 'pool' kind with the three max pools: timed here as a launch of its own
@@ -347,7 +381,7 @@ if ptail_of:
     names = [d.name.decode() for d in eng.layers]
     print("-- pointwise tails (one launch each: conv3 + identity -> next conv1; the time is booked on the conv3 row) --")
     for c3, n1 in sorted(ptail_of.items()):
-        fl = conv_flops(eng.layers[c3]) + conv_flops(eng.layers[n1])
+        fl = conv_flops(c3) + conv_flops(n1)
         ms = prof["per_conv_ms"][c3] / reps
         print("  %-16s + %-16s %8.3f ms %9.1f GFLOP %8.1f TFLOP/s" % (names[c3], names[n1], ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 layer1 = sum(ms for d, ms in zip(eng.layers, prof["per_conv_ms"]) if d.name.startswith(b"layer1.") or d.name == b"layer2.0.conv1") / reps
@@ -370,7 +404,7 @@ if os.environ.get("MPX_TILE_SWEEP"):     # tool-only: every eligible tile of eve
     for li, d in enumerate(eng.layers):
         default = eng.conv_tile(li)
         cells = []
-        for t in (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14):
+        for t in (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14, 16):
             try:
                 eng.set_conv_tile(li, t)
             except MpxError:

@@ -188,6 +188,35 @@ enum {
  * which sees the descriptor alone, stays the dense packer and does not serve it.  No block tails and no pointwise tails (their shapes are
  * the ResNets').  Four activation buffers of 56 * 56 * 256 elements per image as on a ResNet (14.5 MB per slot with the staging and the
  * pooled stem planes) for 32x4d; of 56 * 56 * 512 (layer2.0.conv1's output) for 32x8d: 27.3 MB per slot.
+ * -- or one of torchvision's two ConvNeXts of width 96, the first networks here with LayerNorm and GELU instead of BatchNorm and a ReLU-family
+ * activation (28,589,128 / 50,223,688 parameters, 4,455,531,264 / 8,683,712,256 MAC per forward):
+ *   MPX_ARCH_CONVNEXT + 1 / 2     convnext_tiny / convnext_small (depths (3, 3, 9, 3) / (3, 3, 27, 3), dims (96, 192, 384, 768)); every other id
+ *                                 in [12000, 13000) is MPX_E_ARG (convnext_base / convnext_large -- dims from 128 / 192 -- included)
+ * A ConvNeXt engine runs features.0.0 (3 -> 96, 4x4 stride 4 WITHOUT padding, bias, 224 -> 56, reading the padded NHWC4 staging 3 pixels into
+ * its border: k_packed = 4 * 32 = 128 under the `ky*32 + px*4 + c` rule, zero weights on px >= 4) and features.0.1 = LayerNorm2d(96) as a launch
+ * of its own (mpx_layernorm_c), then four stages features.1 / .3 / .5 / .7 of CNBlocks of width C = 96, 192, 384, 768 on 56 / 28 / 14 / 7 maps.
+ * A CNBlock features.S.B is block.0 = depthwise 7x7 (pad 3, bias) and block.2 = LayerNorm(C) over the channels of each pixel in ONE launch
+ * (mpx_dwconv7x7_ln), block.3 = Linear(C, 4C) + GELU and block.5 = Linear(4C, C) as 1x1 entries of the conv list, and output = input +
+ * layer_scale * block(input) with nothing behind the add.  features.2 / .4 / .6 are LayerNorm2d(C_prev) (.0: mpx_layernorm_c) and Conv2d(C_prev,
+ * C, 2, stride 2, bias) (.1: an ordinary 2x2 entry of the conv list, k_packed = 4 * C_prev); the head is the global average pool with
+ * classifier.0 = LayerNorm2d(768) behind it in one launch (mpx_global_avgpool_ln) and classifier.2 = Linear(768, 1000), the logit layer and
+ * last conv entry.  Every LayerNorm has eps 1e-6.  41 / 77 entries in the conv list ("features.0.0", "features.1.0.block.3",
+ * "features.1.0.block.5", ..., "features.2.1", ..., "classifier.2"), 18 / 36 depthwise layers ("features.1.0.block.0", ...; bn_name is the
+ * LayerNorm's prefix "features.1.0.block.2"; mpx_dwconv_shape reports ksize 7, mpx_dwconv_ln the fused LayerNorm; mpx_load_dwconv_ln loads
+ * them), 5 stand-alone LayerNorms (mpx_num_lnorms: "features.0.1", "features.2.0", "features.4.0", "features.6.0", "classifier.0").
+ * mpx_forward launches the stem conv, its LayerNorm, per block depthwise + LayerNorm, block.3, block.5, per stage boundary the LayerNorm and
+ * the 2x2 conv, then the pooled LayerNorm, classifier.2 and the head: 2 + 3 * 18 + 2 * 3 + 3 = 65 launches (tiny), 2 + 3 * 36 + 6 + 3 = 119 (small).
+ * GELU IS IN THE EPILOGUE.  block.3's consumer is another MFMA conv, so its activation cannot ride on a consumer's load: the generic kernel's
+ * epilogue has the exact GELU as a compile-time constant of the tile class (csrc/mpx_conv.h, ConvGelu).  mpx_conv_epilogue_act reports 1 on
+ * such a layer, relu is 0 in its descriptor and mpx_conv_consumer_act stays 0; mpx_conv_bn_act returns gelu(W x + b).  Such a layer runs the
+ * generic tiles 0, 1, 2, 4 and 7 only (default 7).
+ * LAYER SCALE IS THE SCALE OF block.5's EPILOGUE.  block.5 is an ordinary entry with residual = 1, relu = 0 whose bn_name is the block's
+ * "features.S.B.layer_scale": the caller passes conv_bias = block.5.bias, gamma = layer_scale, beta = 0, mean = 0, var = 1 and eps = 0, which
+ * the packer turns into scale = layer_scale * 2^-e, shift = bias * layer_scale exactly.
+ * Every channel count (96 .. 3072) is a multiple of 32: no padded pitches.  Three activation buffers of 56 * 56 * 384 elements per image
+ * (block.3's output in stage 0, 1.5 x a ResNet buffer, MobileNetV2's size: 14.45 MB) -- X the block input and residual, T1 the LayerNorm
+ * output and then, dead after block.3, the block output, T2 the hidden map -- plus the staging (0.85 MB): 15.3 MB per slot.  It stages through
+ * mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -203,6 +232,7 @@ enum {
 #define MPX_ARCH_SHUFFLENET 9000
 #define MPX_ARCH_EFFICIENTNET 10000
 #define MPX_ARCH_RESNEXT 11000
+#define MPX_ARCH_CONVNEXT 12000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -259,6 +289,10 @@ int mpx_conv_groups(const mpx_engine* h, int i, int* groups);
  * none (every layer of every other network; ReLU6's clamp is reported by mpx_dwconv_desc.clamp_in), 1 SiLU (an EfficientNet-B0 engine's stem,
  * expand convs and features.8: mpx_conv_bn_act returns bn(conv(x)) there). */
 int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act);
+/* The activation layer i DOES apply in its epilogue besides what mpx_conv_desc.relu says: *act = 0 none (every layer of every other network),
+ * 1 exact GELU (a ConvNeXt engine's block.3 layers: mpx_conv_bn_act returns gelu(W x + b), the layer runs the generic tiles 0, 1, 2, 4 and 7
+ * only, and mpx_set_conv_tile refuses every other tile on it).  mpx_conv_desc keeps its layout. */
+int mpx_conv_epilogue_act(const mpx_engine* h, int i, int* act);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
  * w = conv weight OIHW [cout][cin][k][k]; conv_bias = the conv's own bias [cout] or NULL (torchvision's ResNet convs have
@@ -316,6 +350,32 @@ int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp)
  * layer takes SiLU on load / applies SiLU behind its BatchNorm (every depthwise layer of an EfficientNet-B0 engine, whose clamp_in is 0:
  * mpx_forward runs mpx_dwconv_bn_act on it), 0 / 0 on every other engine.  Any pointer may be NULL. */
 int mpx_dwconv_shape(const mpx_engine* h, int k, int* ksize, int* act_in, int* act_out);
+/* Still more of what mpx_dwconv_desc has no field for: *ln = 1 when the layer is a ConvNeXt block's depthwise 7x7 conv WITH BIAS and the
+ * LayerNorm over the channels fused behind it (mpx_dwconv_shape reports ksize 7 there; mpx_dwconv_desc.bn_name is the LayerNorm's prefix
+ * "features.S.B.block.2"; mpx_forward runs mpx_dwconv7x7_ln on it), 0 on every other engine; *bias = the DEV f32[channels] conv bias (NULL
+ * when *ln is 0), *eps = the LayerNorm's epsilon as loaded.  On such a layer mpx_dwconv_params returns w = the tap-major weights [49][channels],
+ * scale = the LayerNorm's weight (gamma) and shift = its bias (beta).  Any pointer may be NULL.
+ * mpx_load_dwconv's signature has no room for the conv bias, so a layer with *ln = 1 loads through mpx_load_dwconv_ln: HOST f32 w =
+ * <name>.weight [channels][1][7][7], conv_bias = <name>.bias, ln_weight / ln_bias = <bn_name>.weight / .bias [channels], eps = 1e-6.
+ * mpx_load_dwconv on such a layer, and mpx_load_dwconv_ln on any other, return MPX_E_ARG. */
+int mpx_dwconv_ln(const mpx_engine* h, int k, int* ln, const float** bias, float* eps);
+int mpx_load_dwconv_ln(mpx_engine* h, int k, const float* w, const float* conv_bias, const float* ln_weight, const float* ln_bias, float eps);
+
+/* ---- stand-alone LayerNorms (ConvNeXt) ---------------------------------------------------------
+ * LayerNorm k in [0, mpx_num_lnorms): the LayerNorm2d modules that are launches of their own, in forward order -- "features.0.1" (behind the
+ * stem), "features.2.0" / "features.4.0" / "features.6.0" (in front of the 2x2 stride-2 convs; mpx_layernorm_c) and "classifier.0" (fused
+ * behind the global average pool: mpx_global_avgpool_ln; hw = 1); 0 on every other architecture.  mpx_load_lnorm takes the HOST
+ * f32[channels] tensors <name>.weight / <name>.bias and the module's eps (1e-6) and uploads them, synchronously, as they are.
+ * mpx_lnorm_params returns their DEV pointers and the epsilon.  mpx_weights_complete and mpx_forward count them. */
+typedef struct mpx_lnorm_desc {
+    char name[64];       /* torchvision state_dict prefix of the LayerNorm2d */
+    int32_t channels;    /* C: the channels of a pixel it normalises over */
+    int32_t hw;          /* side of the square map it runs on at 224x224 input (1 for classifier.0, which runs on the pooled row) */
+} mpx_lnorm_desc;
+int mpx_num_lnorms(const mpx_engine* h);
+int mpx_lnorm_info(const mpx_engine* h, int k, mpx_lnorm_desc* out);
+int mpx_load_lnorm(mpx_engine* h, int k, const float* weight, const float* bias, float eps);
+int mpx_lnorm_params(const mpx_engine* h, int k, const float** weight, const float** bias, float* eps);
 
 /* ---- Squeeze-and-Excitation layers (EfficientNet-B0) --------------------------------------------
  * SE layer k in [0, mpx_num_se): the SqueezeExcitation modules in forward order ("features.1.0.block.1", "features.2.0.block.2", ...); 0 on
@@ -652,6 +712,33 @@ int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float
 int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
                  void* stream);
 
+/* ---- ConvNeXt: the LayerNorm over the channels of a pixel, alone and fused ---------------------------------------------------------
+ * THE ARITHMETIC all three entries share, per pixel with channel values v_c, in fp32 with one rounding per operator (csrc/mpx_cnext.h):
+ *     mean = (sum_c v_c) / C;  d_c = v_c - mean;  var = (sum_c d_c * d_c) / C  (two-pass: centred and biased, never E[v^2] - mean^2);
+ *     rstd = 1 / sqrt(var + eps)  (IEEE square root and division);  y_c = ((d_c * rstd) * weight_c) + bias_c;  the re-split.
+ * Both sums run in ONE fixed order -- the 8 channels of a 16-byte group ascending, then the C / 8 groups ascending --, through the LDS and
+ * without atomics, so a pixel's result has the same bits in any batch, at any position of it and on any grid.  weight / bias: DEV f32[C].
+ * C a positive multiple of 8 up to 2048; every pointer 16-byte aligned; the planes must not overlap; offsets are 64-bit.  max_blocks > 0 caps
+ * the grid (a test hook: the result does not depend on it), 0 = the entry's own cap.  ONE launch each. */
+/* replaces: `block.0` = nn.Conv2d(dim, dim, 7, padding=3, groups=dim, bias=True), the Permute and `block.2` = nn.LayerNorm(dim, eps=1e-6) of
+ *           torchvision's convnext.py CNBlock inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * in / out: DEV planes [B][hin][hin][C].  w: DEV f32[49][C], tap-major (tap = ky * 7 + kx); conv_bias: DEV f32[C] (mpx_dwconv_params,
+ * mpx_dwconv_ln).  v_c = acc_c + conv_bias_c with acc_c = fma(w[tap][c], x[tap][c], acc_c) over the taps inside the map in row-major order
+ * from acc_c = 0, x = hi + lo (exact); v is never rounded to split-fp16 and never stored.  MPX_E_ARG for ksize != 7 (a 3x3 / 5x5 layer runs
+ * mpx_dwconv_bn_act), stride != 1, a null or misaligned pointer, B <= 0, hin <= 0, C not a multiple of 8 or above 2048. */
+int mpx_dwconv7x7_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* conv_bias, const float* ln_weight,
+                     const float* ln_bias, float eps, void* out_hi, void* out_lo, int B, int hin, int C, int ksize, int stride, int max_blocks,
+                     void* stream);
+/* replaces: a LayerNorm2d(C, eps=1e-6) of torchvision's convnext.py (features.0.1, features.2.0 / .4.0 / .6.0) inside model(masked_img_tensor).
+ * in / out: DEV planes [rows][C], rows = B * h * w pixels; v_c = hi + lo (exact). */
+int mpx_layernorm_c(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
+                    void* out_lo, long long rows, int C, int max_blocks, void* stream);
+/* replaces: `self.avgpool(x)` (AdaptiveAvgPool2d(1)) and `classifier.0` = LayerNorm2d(768, eps=1e-6) of torchvision's ConvNeXt.
+ * in: DEV planes [B][hw][C] (hw = PIXELS per image); out: DEV planes [B][C], what classifier.2 reads.  v_c = (the hw values hi + lo summed in
+ * pixel order in fp32, mpx_global_avgpool's order) / hw, not re-split before the LayerNorm. */
+int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps,
+                          void* out_hi, void* out_lo, int B, int hw, int C, void* stream);
+
 /* ---- ShuffleNetV2: channel_shuffle(cat(a, b), 2) into the two-half layout ------------------------------------------------------
  * replaces: `torch.cat((x1, self.branch2(x2)), dim=1)` / `torch.cat((self.branch1(x), self.branch2(x)), dim=1)` and `channel_shuffle(out, 2)`
  *           of torchvision's shufflenetv2.py InvertedResidual.forward inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
@@ -773,6 +860,11 @@ int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long l
 int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms);
+/* The same with ConvNeXt's split of kind 2: per_lnorm_ms (HOST f64[mpx_num_lnorms], may be NULL) gets the launch of every stand-alone
+ * LayerNorm (classifier.0's is the pooled LayerNorm launch); the depthwise + LayerNorm launches are per_dw_ms's. */
+int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                           double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                           double* per_se_scale_ms, double* per_lnorm_ms);
 /* Algorithmic FLOPs (2*MAC, convs + depthwise convs + the SE layers' two FCs + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 

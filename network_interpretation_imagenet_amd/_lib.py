@@ -44,6 +44,10 @@ class SeDesc(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("channels", C.c_int32), ("pitch", C.c_int32), ("q", C.c_int32), ("hw", C.c_int32)]
 
 
+class LnormDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 64), ("channels", C.c_int32), ("hw", C.c_int32)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -142,6 +146,18 @@ SIGNATURES = {
     "mpx_profile_collect_se": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 8),
     # ResNeXt: the groups of a layer (32 on a block's conv2, the grouped 3x3 kernel's layers)
     "mpx_conv_groups": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    # ConvNeXt: GELU in a conv's epilogue, the depthwise 7x7 + LayerNorm layers, the stand-alone LayerNorms, their three kernels
+    "mpx_conv_epilogue_act": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    "mpx_dwconv_ln": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(_vp), C.POINTER(C.c_float)]),
+    "mpx_load_dwconv_ln": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f]),
+    "mpx_num_lnorms": (_i, [_vp]),
+    "mpx_lnorm_info": (_i, [_vp, _i, C.POINTER(LnormDesc)]),
+    "mpx_load_lnorm": (_i, [_vp, _i, _vp, _vp, _f]),
+    "mpx_lnorm_params": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_float)]),
+    "mpx_dwconv7x7_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mpx_layernorm_c": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp]),
+    "mpx_global_avgpool_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
+    "mpx_profile_collect_ln": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 9),
 }
 
 _lib = None

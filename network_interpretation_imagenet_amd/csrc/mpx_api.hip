@@ -16,6 +16,7 @@
 #include "mpx_shuffle.h"
 #include "mpx_mbconv.h"
 #include "mpx_gconv.h"
+#include "mpx_cnext.h"
 
 #include <algorithm>
 #include <cmath>
@@ -42,11 +43,12 @@ constexpr size_t kMobileActElemsPerImage = 112 * 112 * 96;   // MobileNetV2: fea
 constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: the output of features.0 (the largest concatenation is 55 * 55 * 128)
 constexpr size_t kShuffleActElemsPerImage = 112 * 112 * 32; // ShuffleNetV2: conv1's output, 24 channels at pitch 32 (= x2_0's stage2.0.branch2.0 map, 56 * 56 * 128)
 constexpr size_t kEffActElemsPerImage = 112 * 112 * 96;  // EfficientNet-B0: features.2.0's expanded map (= MobileNetV2's buffer)
+constexpr size_t kCnextActElemsPerImage = 56 * 56 * 384;  // ConvNeXt: block.3's output in stage 0 (the same number of elements again)
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
               OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14,
-              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17, OP_PTAIL = 18 };
+              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17, OP_PTAIL = 18, OP_LNORM = 19, OP_AVGPOOLLN = 20 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -59,6 +61,7 @@ struct ConvLayer {
     bool is_fc = false;
     bool is_stem = false;
     int consumer_act = 0;   // 1: torchvision follows this conv with SiLU, which its one consumer takes on load (mpx_mbconv.h); relu is 0 then
+    int epi_act = 0;        // 1: exact GELU in the epilogue (a ConvNeXt block.3: ConvGelu, mpx_conv.h); the layer runs the generic tiles only
     bool has_bias = false;  // the reference module is nn.Conv2d(bias=True) (small nets): state_dict has <name>.bias
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
     int cout_store = 0;     // channels per pixel of the output planes (row pitch and store bound)
@@ -140,9 +143,22 @@ struct DwLayer {
     int ksize = 3;          // 3 or 5 (EfficientNet-B0): weights [ksize * ksize][pitch]
     bool mb = false;        // EfficientNet-B0: dwconv_bn_act_kernel (mpx_mbconv.h) with SiLU on load (act_in) and in the epilogue (act_out)
     int act_in = 0, act_out = 0;
+    bool ln = false;        // ConvNeXt: depthwise 7x7 + bias + LayerNorm over the channels (dwconv7x7_ln_kernel, mpx_cnext.h); scale / shift hold the
+                            // LayerNorm's weight / bias, `bias` the conv's own bias, `eps` the LayerNorm's epsilon as loaded
+    float* bias = nullptr;
+    float eps = 0.f;
     float* w = nullptr;
     float* scale = nullptr;
     float* shift = nullptr;
+    bool loaded = false;
+};
+
+// A LayerNorm over the channels that is a launch of its own (ConvNeXt; mpx_cnext.h): the module's weight and bias as they are
+struct LnLayer {
+    mpx_lnorm_desc d;
+    float* gamma = nullptr;
+    float* beta = nullptr;
+    float eps = 0.f;
     bool loaded = false;
 };
 
@@ -161,6 +177,7 @@ constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max po
 constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shuffle k (mpx_engine::shuffles) kProfSubShuffle - k
 constexpr int kProfSubSeGate = -3000000;    // ... of EfficientNet's SE layer k (mpx_engine::ses): its gate launch kProfSubSeGate - k,
 constexpr int kProfSubSeScale = -4000000;   //     its scale launch kProfSubSeScale - k
+constexpr int kProfSubLnorm = -5000000;     // ... of ConvNeXt's stand-alone LayerNorm k (mpx_engine::lnorms) kProfSubLnorm - k
 
 // A channel shuffle of the op list (ShuffleNetV2; mpx_shuffle.h): a = Op::in at a_pitch, b = Op::res advanced by b_offset at b_pitch
 struct ShuffleOp {
@@ -204,6 +221,8 @@ struct mpx_engine {
     std::vector<SeLayer> ses;       // its Squeeze-and-Excitation layers in forward order
     float* se_gate = nullptr;       // f32[max_batch][se_pitch_max]: the gates of the SE layer in flight
     int se_pitch_max = 0;
+    bool convnext = false;          // torchvision ConvNeXt-Tiny / -Small: CNBlocks over three activation buffers, staged through K0 only
+    std::vector<LnLayer> lnorms;    // its stand-alone LayerNorms in forward order
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -312,6 +331,7 @@ int build_topology_squeezenet(mpx_engine* h);
 int build_topology_googlenet(mpx_engine* h);
 int build_topology_shufflenet(mpx_engine* h);
 int build_topology_efficientnet(mpx_engine* h);
+int build_topology_convnext(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -324,6 +344,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_GOOGLENET && h->arch < MPX_ARCH_GOOGLENET + 1000) return build_topology_googlenet(h);
     if (h->arch >= MPX_ARCH_SHUFFLENET && h->arch < MPX_ARCH_SHUFFLENET + 1000) return build_topology_shufflenet(h);
     if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
+    if (h->arch >= MPX_ARCH_CONVNEXT && h->arch < MPX_ARCH_CONVNEXT + 1000) return build_topology_convnext(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
@@ -1451,6 +1472,103 @@ int build_topology_efficientnet(mpx_engine* h) {
     return 0;
 }
 
+// torchvision ConvNeXt-Tiny / -Small (convnext.py, eval mode): features.0 = Conv2d(3, 96, 4, stride 4, bias) + LayerNorm2d(96), four stages
+// features.1 / .3 / .5 / .7 of depths (3, 3, 9, 3) / (3, 3, 27, 3) CNBlocks of width 96, 192, 384, 768 on 56 / 28 / 14 / 7 maps, features.2 / .4 /
+// .6 = LayerNorm2d(C_prev) + Conv2d(C_prev, C, 2, stride 2, bias), global average pool, classifier.0 = LayerNorm2d(768), classifier.2 =
+// Linear(768, 1000).  A CNBlock is block.0 = depthwise 7x7 (pad 3, bias), block.2 = LayerNorm(C) over the channels of each pixel, block.3 =
+// Linear(C, 4C) + GELU, block.5 = Linear(4C, C), output = input + layer_scale * block(input); StochasticDepth is the identity in eval.  Every
+// LayerNorm has eps 1e-6.  Every channel count is a multiple of 32: no padded pitches.
+// GELU: block.3's consumer is block.5, an MFMA conv, so the activation is block.3's own epilogue (ConvLayer::epi_act, ConvGelu in mpx_conv.h);
+// such a layer runs the generic tiles only and defaults to tile 7, what default_tile gives the one stage (96 -> 384) whose shape no
+// persistent kernel takes.  block.5 is an ordinary layer with a residual operand and the layer scale as its "BatchNorm" gamma (bn_name =
+// "features.S.B.layer_scale": mean 0, var 1, eps 0, beta 0, the conv's own bias as conv_bias), on default_tile's choice.
+// The stem reads the padded NHWC4 staging 3 pixels into its border, one 8-pixel run per kernel row (4 of them real): k_packed = 4 * 32.
+// Op list, 65 / 119 launches: stem conv | its LayerNorm | per block (depthwise + LayerNorm, block.3, block.5) | per stage boundary
+// (LayerNorm, 2x2 conv) | pool + LayerNorm | classifier.2 | OP_HEAD.  41 / 77 conv entries, 18 / 36 depthwise layers, 5 LayerNorms.
+// Buffers: three of 56 * 56 * 384 elements per image (block.3's output in stage 0): X the block input and residual, T1 the LayerNorm
+// output and then -- dead after block.3 -- the block output, T2 the hidden map.
+int build_topology_convnext(mpx_engine* h) {
+    int depths[4] = {3, 3, 9, 3};
+    if (h->arch == MPX_ARCH_CONVNEXT + 2) depths[2] = 27;
+    else if (h->arch != MPX_ARCH_CONVNEXT + 1) return MPX_E_ARG;
+    static const int dims[4] = {96, 192, 384, 768};
+    h->convnext = true;
+    h->n_act_bufs = 3;
+    h->act_elems_per_image = kCnextActElemsPerImage;
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int hin, int residual, int act, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = 0;
+        L.d.hin = hin; L.d.hout = (hin - k) / stride + 1;
+        L.d.relu = 0; L.d.residual = residual;
+        L.epi_act = act;
+        L.is_fc = fc;
+        L.has_bias = true;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 4, pad 0)
+        L.cin_pad = cin;
+        L.cout_store = cout;
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * cin;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        if (act) L.tile = L.tile_default = 7;
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto add_ln = [&](const std::string& name, int c, int hw) {
+        LnLayer N;
+        std::memset(&N.d, 0, sizeof N.d);
+        std::snprintf(N.d.name, sizeof N.d.name, "%s", name.c_str());
+        N.d.channels = c; N.d.hw = hw;
+        h->lnorms.push_back(N);
+        return (int)h->lnorms.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
+    int c = add_conv("features.0.0", "", 3, dims[0], 4, 4, MPX_IMG, 0, 0, false);
+    conv_op(c, BUF_INPUT, 0, BUF_NONE);
+    int hcur = 56;
+    h->ops.push_back(Op{OP_LNORM, add_ln("features.0.1", dims[0], hcur), 0, 1, BUF_NONE, hcur, dims[0], BUF_NONE});
+    int X = 1;
+    for (int s = 0; s < 4; ++s) {
+        const int C = dims[s];
+        if (s > 0) {
+            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3, cp = dims[s - 1];
+            const std::string p = "features." + std::to_string(2 * s) + ".";
+            h->ops.push_back(Op{OP_LNORM, add_ln(p + "0", cp, hcur), X, T1, BUF_NONE, hcur, cp, BUF_NONE});
+            c = add_conv(p + "1", "", cp, C, 2, 2, hcur, 0, 0, false);
+            conv_op(c, T1, T2, BUF_NONE);
+            X = T2;
+            hcur /= 2;
+        }
+        if ((size_t)hcur * hcur * 4 * C > kCnextActElemsPerImage) return MPX_E_INTERNAL;
+        for (int b = 0; b < depths[s]; ++b) {
+            const std::string p = "features." + std::to_string(2 * s + 1) + "." + std::to_string(b) + ".";
+            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
+            DwLayer D;
+            std::memset(&D.d, 0, sizeof D.d);
+            set_name(D.d.name, p + "block.0");
+            set_name(D.d.bn_name, p + "block.2");
+            D.d.channels = C; D.d.pitch = C; D.d.stride = 1; D.d.hin = hcur; D.d.clamp_in = 0;
+            D.ksize = CN_DW_K; D.ln = true;
+            h->dws.push_back(D);
+            h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, X, T1, BUF_NONE, hcur, C, BUF_NONE});
+            c = add_conv(p + "block.3", "", C, 4 * C, 1, 1, hcur, 0, 1, false);
+            conv_op(c, T1, T2, BUF_NONE);
+            c = add_conv(p + "block.5", p + "layer_scale", 4 * C, C, 1, 1, hcur, 1, 0, false);
+            conv_op(c, T2, T1, X);          // T1 is dead after block.3
+            X = T1;
+        }
+    }
+    if (hcur != 7) return MPX_E_INTERNAL;
+    h->feat = dims[3];
+    h->ops.push_back(Op{OP_AVGPOOLLN, add_ln("classifier.0", dims[3], 1), X, BUF_POOL, BUF_NONE, hcur, dims[3], BUF_NONE});
+    c = add_conv("classifier.2", "", dims[3], MPX_NUM_CLASSES, 1, 1, 1, 0, 0, true);
+    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -1569,6 +1687,12 @@ int launch_conv_tile(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, h
         if (p.r_hi || p.y_f32 || p.k1 || p.y_pitch != L.y_pitch)
             return fail(h, MPX_E_INTERNAL, "slice conv: %s takes no residual operand, no fp32 output and no second K segment", L.d.name);
         hipLaunchKernelGGL((conv_f16x3_kernel<Cfg, false, false, true>), dim3((unsigned)tiles), dim3(Cfg::NT), Cfg::LDS, st, p);
+        return launched(h, id);
+    }
+    if (L.epi_act) {        // GELU in the epilogue (a ConvNeXt block.3): the same tile with ACT = 1, whatever else the row offers
+        if (L.epi_act != 1 || p.r_hi || p.y_f32 || p.k1 || p.relu)
+            return fail(h, MPX_E_INTERNAL, "GELU conv: %s takes no residual operand, no fp32 output, no second K segment and no ReLU", L.d.name);
+        hipLaunchKernelGGL((conv_f16x3_kernel<ConvGelu<Cfg>>), dim3((unsigned)tiles), dim3(Cfg::NT), Cfg::LDS, st, p);
         return launched(h, id);
     }
     if constexpr (DUAL) {
@@ -1759,6 +1883,11 @@ const KernelLds kKernelLds[] = {
     {(const void*)conv_f16x3_kernel<ConvTile2, false, false, true>, ConvTile2::LDS},
     {(const void*)conv_f16x3_kernel<ConvTile4, false, false, true>, ConvTile4::LDS},
     {(const void*)conv_f16x3_kernel<ConvTile7, false, false, true>, ConvTile7::LDS},
+    {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile0>>, ConvTile0::LDS},
+    {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile1>>, ConvTile1::LDS},
+    {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile2>>, ConvTile2::LDS},
+    {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile4>>, ConvTile4::LDS},
+    {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile7>>, ConvTile7::LDS},
     {(const void*)btail_f16x3_kernel<BtResC64>, BtResC64::LDS},
     {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
     {(const void*)btail_f16x3_kernel<BtDualC64>, BtDualC64::LDS},
@@ -1785,6 +1914,7 @@ const TileRow* find_tile(int id) {
 // read dense pixel rows.
 bool eligible(const TileRow& r, const ConvLayer& L) {
     if (L.groups > 1 || r.id == kGconvTile) return L.groups > 1 && r.id == kGconvTile;     // a grouped layer runs tile 16, and tile 16 nothing else
+    if (L.epi_act && r.eligible) return false;      // only the generic kernel's epilogue has an activation other than ReLU (ConvGelu)
     return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && !L.x_pitch && r.eligible(L.d));
 }
 
@@ -2219,6 +2349,41 @@ int launch_mbdw(mpx_engine* h, const MbDwParams& p, int ksize, int stride, int d
     return 0;
 }
 
+// Grid of a ConvNeXt LayerNorm kernel (mpx_cnext.h): `units` slots of work, R = cn_slots(C) per workgroup and iteration, about `per_cu`
+// workgroups per CU striding over the rest; max_blocks > 0 caps it further (the public entries' test hook: results do not depend on it)
+unsigned cn_grid(const mpx_engine* h, long long units, int C, int per_cu, int max_blocks) {
+    const long long R = cn_slots(C);
+    long long grid = std::min<long long>((units + R - 1) / R, (long long)h->num_cus * per_cu);
+    if (max_blocks > 0) grid = std::min<long long>(grid, max_blocks);
+    return (unsigned)std::max<long long>(grid, 1);
+}
+
+// one dwconv7x7_ln_kernel launch; `dw` = the engine's depthwise layer it runs for (profile record), -1 from the stand-alone entry.  The
+// kernel holds 4 x 8 accumulators and one input row of 10 x 8 values per thread (two workgroups per CU): 4 workgroups per CU cover a tail
+int launch_cn_dwln(mpx_engine* h, CnDwLnParams& p, int B, int max_blocks, int dw, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+    p.units = (long long)B * p.H * ((p.H + CN_DW_W - 1) / CN_DW_W);
+    hipLaunchKernelGGL(dwconv7x7_ln_kernel, dim3(cn_grid(h, p.units, p.C, 4, max_blocks)), dim3(CN_NT), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one layernorm_c_kernel launch; `k` = the engine's LayerNorm it runs for (profile record), -1 from the stand-alone entry
+int launch_cn_ln(mpx_engine* h, const CnLnParams& p, int max_blocks, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+    hipLaunchKernelGGL(layernorm_c_kernel, dim3(cn_grid(h, p.rows, p.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one global_avgpool_ln_kernel launch
+int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+    hipLaunchKernelGGL(global_avgpool_ln_kernel, dim3(cn_grid(h, p.B, p.C, 8, 0)), dim3(CN_NT), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 // dynamic LDS of one se_gate_kernel launch: part[S][pitch] | pooled[pitch] | s1[q]
 size_t se_gate_lds(int pitch, int q) { return ((size_t)se_gate_slices(pitch) * pitch + pitch + q) * sizeof(float); }
 
@@ -2277,10 +2442,12 @@ int launch_pool3c(mpx_engine* h, const half_t* in_hi, const half_t* in_lo, half_
 
 // mpx_pack_conv_weights with the input's channel layout: in_hp = 0 puts logical input channel ci in column ci of its tap; in_hp > 0 (the
 // layer reads a whole two-half stage map, mpx_shuffle.h: 2 * in_bf logical channels at pitch 2 * in_hp = cin_pad) puts ci < in_bf at ci and
-// ci >= in_bf at in_hp + ci - in_bf; the columns of the gaps stay zero.
+// ci >= in_bf at in_hp + ci - in_bf; the columns of the gaps stay zero.  even_stem: the layer is a stem with an EVEN kernel that reads the
+// padded NHWC4 staging (ConvNeXt's 4x4 stride-4 patchify conv, K = 4 * 32) -- the row-run layout, which the descriptor alone cannot ask for:
+// cin = 3, k = 4, K = 128 is also a generic layout (cin_pad = 8), and that meaning stays mpx_pack_conv_weights'.
 int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float* w, const float* conv_bias, const float* gamma,
                       const float* beta, const float* mean, const float* var, float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale,
-                      float* shift);
+                      float* shift, bool even_stem = false);
 
 }  // namespace
 
@@ -2299,7 +2466,7 @@ namespace {
 
 int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float* w, const float* conv_bias, const float* gamma,
                       const float* beta, const float* mean, const float* var, float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale,
-                      float* shift) {
+                      float* shift, bool even_stem) {
     if (!d || !w || !w_hi || !w_lo || !scale || !shift) return MPX_E_ARG;
     const int cin = d->cin, cout = d->cout, k = d->ksize, K = d->k_packed;
     if (k <= 0 || cin <= 0 || cout <= 0 || cout > d->cout_pad || d->cout_pad % 16 != 0) return MPX_E_ARG;
@@ -2309,7 +2476,7 @@ int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float*
     // AlexNet's 11x11 first layer is the two-run form: 16 pixels x 4 channels = two K steps per kernel row, K = 11 * 64 = 704 (a
     // descriptor the generic layout refuses: 704 is not 121 * cin_pad).
     const int run = (cin == 3 && k == 11 && K == 11 * 64) ? 64 : 32;
-    const bool stem = run == 64 || (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7);
+    const bool stem = run == 64 || (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7) || (even_stem && cin == 3 && K == k * 32 && k <= 8);
     if (cin == 3 && k == kStemK && !stem) return MPX_E_ARG;
     // K = k*k*cin_pad: the input planes may carry more channels per pixel than the layer reads (small nets pad to 32)
     const int cin_pad = stem ? 0 : K / (k * k);
@@ -2436,7 +2603,8 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     }
     for (const TailBlock& tb : h->tails) wbytes += 2 * round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
     for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
-    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256) + 2 * round_up((size_t)D.d.pitch * 4, 256);
+    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256) + (D.ln ? 3 : 2) * round_up((size_t)D.d.pitch * 4, 256);
+    for (const LnLayer& N : h->lnorms) wbytes += 2 * round_up((size_t)N.d.channels * 4, 256);
     for (const SeLayer& E : h->ses)
         wbytes += 2 * round_up((size_t)E.d.q * E.d.pitch * 4, 256) + round_up((size_t)E.d.q * 4, 256) + round_up((size_t)E.d.pitch * 4, 256);
     const size_t se_gate_bytes = round_up((size_t)max_batch * h->se_pitch_max * 4, 256);
@@ -2512,6 +2680,11 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
         D.w = (float*)take(round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256));
         D.scale = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
         D.shift = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
+        if (D.ln) D.bias = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
+    }
+    for (LnLayer& N : h->lnorms) {
+        N.gamma = (float*)take(round_up((size_t)N.d.channels * 4, 256));
+        N.beta = (float*)take(round_up((size_t)N.d.channels * 4, 256));
     }
     for (SeLayer& E : h->ses) {
         E.w1 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
@@ -2571,7 +2744,8 @@ int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv
     std::vector<uint16_t> hi(n), lo(n);
     std::vector<float> sc(L.d.cout_pad), sh(L.d.cout_pad);
     int rc = L.groups > 1 ? pack_gconv_weights(&L.d, L.groups, w, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data())
-                          : pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data());
+                          : pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data(),
+                                              L.is_stem && !(L.d.ksize & 1));
     if (rc) return fail(h, rc, "pack failed for %s", L.d.name);
     MPX_SET_DEVICE(h);
     MPX_HIP(h, hipMemcpy(L.w_hi, hi.data(), n * 2, hipMemcpyHostToDevice));
@@ -2631,6 +2805,8 @@ int mpx_set_conv_tile(mpx_engine* h, int i, int tile) {
     }
     if (L.groups > 1 && tile != kGconvTile)
         return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: a grouped layer runs the grouped 3x3 kernel (tile %d) only (%s is one)", tile, kGconvTile, L.d.name);
+    if (L.epi_act && r->eligible)
+        return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: %s applies GELU in its epilogue, which only the generic kernel (tiles 0, 1, 2, 4 and 7) has", tile, L.d.name);
     if (!eligible(*r, L)) return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: %s (%s is not one)", tile, r->refusal, L.d.name);
     L.tile = tile;
     return 0;
@@ -2651,7 +2827,39 @@ int mpx_weights_complete(const mpx_engine* h) {
         if (!D.loaded) return 0;
     for (const SeLayer& E : h->ses)
         if (!E.loaded) return 0;
+    for (const LnLayer& N : h->lnorms)
+        if (!N.loaded) return 0;
     return 1;
+}
+
+int mpx_num_lnorms(const mpx_engine* h) { return h ? (int)h->lnorms.size() : MPX_E_ARG; }
+
+int mpx_lnorm_info(const mpx_engine* h, int k, mpx_lnorm_desc* out) {
+    if (!h || !out || k < 0 || k >= (int)h->lnorms.size()) return MPX_E_ARG;
+    *out = h->lnorms[k].d;
+    return 0;
+}
+
+int mpx_load_lnorm(mpx_engine* h, int k, const float* weight, const float* bias, float eps) {
+    if (!h) return MPX_E_ARG;
+    if (k < 0 || k >= (int)h->lnorms.size()) return fail(h, MPX_E_ARG, "load_lnorm: bad LayerNorm index %d (this engine has %d)", k, (int)h->lnorms.size());
+    LnLayer& N = h->lnorms[k];
+    if (!weight || !bias) return fail(h, MPX_E_ARG, "load_lnorm: weight or bias missing for %s", N.d.name);
+    if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(h, MPX_E_ARG, "load_lnorm: eps must be finite and >= 0");
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(N.gamma, weight, (size_t)N.d.channels * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(N.beta, bias, (size_t)N.d.channels * 4, hipMemcpyHostToDevice));
+    N.eps = eps;
+    N.loaded = true;
+    return 0;
+}
+
+int mpx_lnorm_params(const mpx_engine* h, int k, const float** weight, const float** bias, float* eps) {
+    if (!h || k < 0 || k >= (int)h->lnorms.size()) return MPX_E_ARG;
+    if (weight) *weight = h->lnorms[k].gamma;
+    if (bias) *bias = h->lnorms[k].beta;
+    if (eps) *eps = h->lnorms[k].eps;
+    return 0;
 }
 
 int mpx_num_norms(const mpx_engine* h) { return h ? (int)h->norms.size() : MPX_E_ARG; }
@@ -2724,7 +2932,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2 and EfficientNet-B0 stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0 and ConvNeXt stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -3015,6 +3223,7 @@ int mpx_load_dwconv(mpx_engine* h, int k, const float* w, const float* gamma, co
     if (!h) return MPX_E_ARG;
     if (k < 0 || k >= (int)h->dws.size()) return fail(h, MPX_E_ARG, "load_dwconv: bad depthwise index %d (this engine has %d)", k, (int)h->dws.size());
     DwLayer& D = h->dws[k];
+    if (D.ln) return fail(h, MPX_E_ARG, "load_dwconv: %s has a conv bias and a LayerNorm behind it; use mpx_load_dwconv_ln", D.d.name);
     if (!w || !gamma || !beta || !mean || !var) return fail(h, MPX_E_ARG, "load_dwconv: weight or BatchNorm tensors missing for %s", D.d.name);
     const int n = D.d.channels, pitch = D.d.pitch, taps = D.ksize * D.ksize;     // w: [channels][1][ksize][ksize]
     std::vector<float> wt((size_t)taps * pitch, 0.f), sc(pitch, 0.f), sh(pitch, 0.f);     // zeros on the padded channels
@@ -3094,6 +3303,97 @@ int mpx_dwconv_shape(const mpx_engine* h, int k, int* ksize, int* act_in, int* a
     if (act_in) *act_in = h->dws[k].act_in;
     if (act_out) *act_out = h->dws[k].act_out;
     return 0;
+}
+
+int mpx_dwconv_ln(const mpx_engine* h, int k, int* ln, const float** bias, float* eps) {
+    if (!h || k < 0 || k >= (int)h->dws.size()) return MPX_E_ARG;
+    if (ln) *ln = h->dws[k].ln ? 1 : 0;
+    if (bias) *bias = h->dws[k].bias;
+    if (eps) *eps = h->dws[k].eps;
+    return 0;
+}
+
+int mpx_load_dwconv_ln(mpx_engine* h, int k, const float* w, const float* conv_bias, const float* ln_weight, const float* ln_bias, float eps) {
+    if (!h) return MPX_E_ARG;
+    if (k < 0 || k >= (int)h->dws.size()) return fail(h, MPX_E_ARG, "load_dwconv_ln: bad depthwise index %d (this engine has %d)", k, (int)h->dws.size());
+    DwLayer& D = h->dws[k];
+    if (!D.ln) return fail(h, MPX_E_ARG, "load_dwconv_ln: %s has a BatchNorm behind it, not a LayerNorm; use mpx_load_dwconv", D.d.name);
+    if (!w || !conv_bias || !ln_weight || !ln_bias) return fail(h, MPX_E_ARG, "load_dwconv_ln: weight, bias or LayerNorm tensors missing for %s", D.d.name);
+    if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(h, MPX_E_ARG, "load_dwconv_ln: eps must be finite and >= 0");
+    const int n = D.d.channels, taps = D.ksize * D.ksize;      // w: [channels][1][7][7] -> tap-major [49][channels]; channels == pitch
+    std::vector<float> wt((size_t)taps * n);
+    for (int c = 0; c < n; ++c)
+        for (int t = 0; t < taps; ++t) wt[(size_t)t * n + c] = w[(size_t)c * taps + t];
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(D.w, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(D.bias, conv_bias, (size_t)n * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(D.scale, ln_weight, (size_t)n * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(D.shift, ln_bias, (size_t)n * 4, hipMemcpyHostToDevice));
+    D.eps = eps;
+    D.loaded = true;
+    return 0;
+}
+
+int mpx_conv_epilogue_act(const mpx_engine* h, int i, int* act) {
+    if (!h || !act || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    *act = h->convs[i].epi_act;
+    return 0;
+}
+
+int mpx_dwconv7x7_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* conv_bias, const float* ln_weight,
+                     const float* ln_bias, float eps, void* out_hi, void* out_lo, int B, int hin, int C, int ksize, int stride, int max_blocks,
+                     void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !w || !conv_bias || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv7x7_ln: null pointer");
+    if (ksize != CN_DW_K || stride != 1)
+        return fail(h, MPX_E_ARG, "dwconv7x7_ln: ksize %d stride %d: this entry runs the 7x7 stride-1 layers with a LayerNorm behind them (3x3 and 5x5 layers run mpx_dwconv_bn_act)", ksize, stride);
+    if (B <= 0 || hin <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f) || (long long)B * hin * hin > 0x7fffffffLL)
+        return fail(h, MPX_E_ARG, "dwconv7x7_ln: B > 0, hin > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(conv_bias) || misaligned(ln_weight) || misaligned(ln_bias) ||
+        misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "dwconv7x7_ln: every pointer must be 16-byte aligned");
+    CnDwLnParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.w = w; p.bias = conv_bias; p.gamma = ln_weight; p.beta = ln_bias;
+    p.H = hin; p.C = C; p.eps = eps;
+    MPX_SET_DEVICE(h);
+    return launch_cn_dwln(h, p, B, max_blocks, -1, as_stream(stream));
+}
+
+int mpx_layernorm_c(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
+                    void* out_lo, long long rows, int C, int max_blocks, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "layernorm_c: null pointer");
+    if (rows <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
+        return fail(h, MPX_E_ARG, "layernorm_c: rows > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "layernorm_c: every pointer must be 16-byte aligned");
+    CnLnParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.gamma = ln_weight; p.beta = ln_bias; p.rows = rows; p.C = C; p.eps = eps;
+    MPX_SET_DEVICE(h);
+    return launch_cn_ln(h, p, max_blocks, -1, as_stream(stream));
+}
+
+int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps,
+                          void* out_hi, void* out_lo, int B, int hw, int C, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "global_avgpool_ln: null pointer");
+    if (B <= 0 || hw <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
+        return fail(h, MPX_E_ARG, "global_avgpool_ln: B > 0, hw > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "global_avgpool_ln: every pointer must be 16-byte aligned");
+    CnPoolLnParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.gamma = ln_weight; p.beta = ln_bias; p.B = B; p.hw = hw; p.C = C; p.eps = eps;
+    MPX_SET_DEVICE(h);
+    return launch_cn_poolln(h, p, -1, as_stream(stream));
 }
 
 int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
@@ -3430,6 +3730,15 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             }
             case OP_DWCONV: {
                 const DwLayer& D = h->dws[o.conv];
+                if (D.ln) {
+                    CnDwLnParams q;
+                    std::memset(&q, 0, sizeof q);
+                    q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
+                    q.w = D.w; q.bias = D.bias; q.gamma = D.scale; q.beta = D.shift;
+                    q.H = D.d.hin; q.C = D.d.channels; q.eps = D.eps;
+                    rc = launch_cn_dwln(h, q, B, 0, o.conv, as_stream(stream));
+                    break;
+                }
                 if (D.mb) {
                     MbDwParams q;
                     std::memset(&q, 0, sizeof q);
@@ -3471,6 +3780,24 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 break;
             }
             case OP_AVGPOOLSILU: rc = mpx_global_avgpool_silu(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
+            case OP_LNORM: {
+                const LnLayer& N = h->lnorms[o.conv];
+                CnLnParams q;
+                std::memset(&q, 0, sizeof q);
+                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
+                q.gamma = N.gamma; q.beta = N.beta; q.rows = (long long)B * o.hin * o.hin; q.C = o.c; q.eps = N.eps;
+                rc = launch_cn_ln(h, q, 0, o.conv, as_stream(stream));
+                break;
+            }
+            case OP_AVGPOOLLN: {
+                const LnLayer& N = h->lnorms[o.conv];
+                CnPoolLnParams q;
+                std::memset(&q, 0, sizeof q);
+                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
+                q.gamma = N.gamma; q.beta = N.beta; q.B = B; q.hw = o.hin * o.hin; q.C = o.c; q.eps = N.eps;
+                rc = launch_cn_poolln(h, q, o.conv, as_stream(stream));
+                break;
+            }
             case OP_SHUFFLE: {
                 const ShuffleOp& S = h->shuffles[o.conv];
                 ShuffleParams p;
@@ -3689,6 +4016,13 @@ int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long l
 int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms) {
+    return mpx_profile_collect_ln(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                  per_se_gate_ms, per_se_scale_ms, nullptr);
+}
+
+int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                           double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                           double* per_se_scale_ms, double* per_lnorm_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -3711,6 +4045,8 @@ int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launch
             per_se_gate_ms[kProfSubSeGate - r.sub] += ms;
         if (per_se_scale_ms && r.kind == 2 && r.sub <= kProfSubSeScale && kProfSubSeScale - r.sub < (int)h->ses.size())
             per_se_scale_ms[kProfSubSeScale - r.sub] += ms;
+        if (per_lnorm_ms && r.kind == 2 && r.sub <= kProfSubLnorm && kProfSubLnorm - r.sub < (int)h->lnorms.size())
+            per_lnorm_ms[kProfSubLnorm - r.sub] += ms;
     }
     h->prof_used = 0;
     return 0;

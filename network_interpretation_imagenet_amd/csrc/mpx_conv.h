@@ -153,6 +153,27 @@ constexpr int POOL_CY = 2 * POOL_PY + 1, POOL_CX = 2 * POOL_PX + 1;        // co
 // store bound, which is what keeps a 128-wide tile of a 64-channel slice out of its neighbour's half.  expand1x1 and expand3x3 thus write
 // the two halves of one buffer and the concatenation is never copied.  No residual operand and no fp32 output (the host refuses both).
 // K loop and phases 0 / 1 are the other forms'; every other instantiation compiles to what it was (the template parameter is a constant).
+//
+// ACT (ConvNeXt's fc1 = block.3, whose consumer is another MFMA conv, so the activation cannot ride on a consumer's load): an activation
+// in the epilogue other than ReLU, a compile-time constant of the TILE CLASS -- ConvGelu<Cfg> is Cfg with ACT = 1 -- so that every
+// instantiation on a plain ConvCfg keeps its name and compiles to what it was.  ACT = 1: phase 2 takes gelu(v) of v = acc * scale + shift in
+// fp32, before the residual add (no GELU layer has one), the ReLU test (relu is 0 on such a layer) and split_f32.
+//     gelu(v) = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)),   the exact (erf) form of nn.GELU()
+__device__ __forceinline__ float gelu_f32(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
+template <class Cfg>
+struct ConvGelu : Cfg {
+    static constexpr int ACT = 1;
+};
+template <class C, class = void>
+struct conv_epilogue_act {
+    static constexpr int value = 0;
+};
+template <class C>
+struct conv_epilogue_act<C, std::void_t<decltype(C::ACT)>> {
+    static constexpr int value = C::ACT;
+};
+
 template <class C, bool DUAL = false, bool POOL = false, bool SLICE = false>
 __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (buffer-resource builtins are device-only)
@@ -545,6 +566,10 @@ __global__ __launch_bounds__(C::NT, C::MINB) void conv_f16x3_kernel(const ConvPa
         const f4 v0 = *(const f4*)(smem + pl * RP + (((2 * g) ^ (pl & 7)) << 4));
         const f4 v1 = *(const f4*)(smem + pl * RP + (((2 * g + 1) ^ (pl & 7)) << 4));
         float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+        if constexpr (conv_epilogue_act<C>::value == 1) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = gelu_f32(v[j]);
+        }
         if (!SLICE && p.r_hi) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += (float)rh[it][j] + (float)rl[it][j];

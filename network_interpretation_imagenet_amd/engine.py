@@ -37,6 +37,8 @@ ARCH_IDS["googlenet"] = 8000      # torchvision's GoogLeNet without the aux clas
 ARCH_IDS.update({"shufflenet_v2_x0_5": 9005, "shufflenet_v2_x1_0": 9010, "shufflenet_v2_x1_5": 9015, "shufflenet_v2_x2_0": 9020})
 ARCH_IDS.update({"resnext50_32x4d": 11050, "resnext101_32x8d": 11101})    # torchvision's 32-group ResNeXts (MPX_ARCH_RESNEXT + 50 / 101); resnext101_64x4d and the Wide ResNets are not served
 ARCH_IDS["efficientnet_b0"] = 10000     # torchvision's EfficientNet-B0 (MPX_ARCH_EFFICIENTNET + 0); B1 .. B7 (trained at 240 and more) are not served
+ARCH_IDS.update({"convnext_tiny": 12001, "convnext_small": 12002})    # torchvision's ConvNeXts of width 96 (MPX_ARCH_CONVNEXT + 1 / 2); convnext_base / convnext_large are not served
+CONVNEXT_LN_EPS = 1e-6      # torchvision convnext.py: every LayerNorm / LayerNorm2d is built with eps=1e-6
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -67,7 +69,10 @@ def whole_round_batch(limit, num_cus=None):
 
 
 def default_bn_eps(arch):
-    """The epsilon of torchvision's BatchNorm layers in `arch`: BatchNorm2d's default 1e-5, except GoogLeNet's BasicConv2d (1e-3)."""
+    """The epsilon of torchvision's BatchNorm layers in `arch`: BatchNorm2d's default 1e-5, except GoogLeNet's BasicConv2d (1e-3).  A
+    ConvNeXt has no BatchNorm: the value is its LayerNorms' 1e-6."""
+    if arch.startswith("convnext"):
+        return CONVNEXT_LN_EPS
     return GOOGLENET_BN_EPS if arch == "googlenet" else BN_EPS
 
 
@@ -135,6 +140,9 @@ class MaskedForwardEngine:
         A ResNeXt-50 32x4d slot is a ResNet slot (14.5 MB: its largest map is 56x56x256 too).  A ResNeXt-101 32x8d slot holds 27.3 MB -- four
         56x56x512 split-fp16 activation buffers (layer2.0.conv1's output: 25.7 MB), the input staging and the pooled stem planes -- and
         keeps the default of 512 (14 GB).
+        A ConvNeXt-Tiny / -Small slot holds 15.3 MB -- three 56x56x384 split-fp16 activation buffers (block.3's output in stage 0,
+        MobileNetV2's size: a block's input, its LayerNorm output and then its output, the hidden map: 14.5 MB) and the input staging -- and
+        keeps the default of 512 (7.8 GB).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -145,7 +153,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d and ConvNeXt-Tiny / -Small: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -185,6 +193,21 @@ class MaskedForwardEngine:
             ks = C.c_int()
             _lib.check(h, self._lib.mpx_dwconv_shape(h, k, C.byref(ks), None, None), "mpx_dwconv_shape")
             self.dw_ksizes.append(int(ks.value))
+        self.dw_ln = []         # 1 where the layer is a ConvNeXt block's depthwise 7x7 with bias and the LayerNorm fused behind it (mpx_dwconv_ln)
+        for k in range(len(self.dwconvs)):
+            ln = C.c_int()
+            _lib.check(h, self._lib.mpx_dwconv_ln(h, k, C.byref(ln), None, None), "mpx_dwconv_ln")
+            self.dw_ln.append(int(ln.value))
+        self.lnorms = []        # the LayerNorms that are launches of their own (ConvNeXt: the stem's, the downsample norms, classifier.0)
+        for k in range(self._lib.mpx_num_lnorms(h)):
+            ld = _lib.LnormDesc()
+            _lib.check(h, self._lib.mpx_lnorm_info(h, k, C.byref(ld)), "mpx_lnorm_info")
+            self.lnorms.append(ld)
+        self.epilogue_acts = []     # per conv layer: 1 = exact GELU in its epilogue (a ConvNeXt block.3), 0 everywhere else
+        for i in range(len(self.layers)):
+            a = C.c_int()
+            _lib.check(h, self._lib.mpx_conv_epilogue_act(h, i, C.byref(a)), "mpx_conv_epilogue_act")
+            self.epilogue_acts.append(int(a.value))
         self.ses = []           # the Squeeze-and-Excitation layers (EfficientNet-B0), a list of their own as well
         for k in range(self._lib.mpx_num_se(h)):
             sd_ = _lib.SeDesc()
@@ -217,8 +240,8 @@ class MaskedForwardEngine:
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
         which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s,
-        EfficientNet-B0 and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet"))
+        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool) and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -299,7 +322,16 @@ class MaskedForwardEngine:
             wshape = (d.cout, w4[1] * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
             # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7] (AlexNet's classifier.1 [4096, 256 * 6 * 6]), channel-major as torch.flatten of NCHW
             w = get(name + ".weight", wshape).reshape(w4).contiguous()
-            if not bn and self.norms and i != len(self.layers) - 1:
+            layer_eps = eps
+            if bn.endswith(".layer_scale"):
+                # ConvNeXt's block.5: fc2 + layer scale + residual is the ordinary epilogue with the layer scale as gamma over mean 0,
+                # var 1, eps 0 and beta 0 -- scale = layer_scale * 2^-e, shift = bias * layer_scale, exactly
+                cb = get(name + ".bias", (d.cout,))
+                g = get(bn, (d.cout, 1, 1)).reshape(d.cout).contiguous()
+                zero, one = torch.zeros(d.cout), torch.ones(d.cout)
+                args = (_ptr(w), _ptr(cb), _ptr(g), _ptr(zero), _ptr(zero), _ptr(one))
+                layer_eps = 0.0
+            elif not bn and self.norms and i != len(self.layers) - 1:
                 # DenseNet's conv2 / transition convs: no BatchNorm behind them, no ReLU and no bias (scale = 2^-e, shift = 0)
                 args = (_ptr(w), None, None, None, None, None)
             elif not bn:        # no BatchNorm: fc, or the MNIST net's conv6 -- the layer's own bias goes in as `beta`
@@ -312,11 +344,16 @@ class MaskedForwardEngine:
                 m = get(bn + ".running_mean", (d.cout,))
                 v = get(bn + ".running_var", (d.cout,))
                 args = (_ptr(w), _ptr(cb), _ptr(g), _ptr(b), _ptr(m), _ptr(v))
-            _lib.check(self._h, self._lib.mpx_set_conv_weights(self._h, i, *args, float(eps)),
+            _lib.check(self._h, self._lib.mpx_set_conv_weights(self._h, i, *args, float(layer_eps)),
                        "mpx_set_conv_weights(%s)" % name)
         for k, dd in enumerate(self.dwconvs):
             name, bn = dd.name.decode(), dd.bn_name.decode()
             if only is not None and name not in only:
+                continue
+            if self.dw_ln[k]:       # ConvNeXt: depthwise 7x7 with bias, `bn` is the LayerNorm behind it
+                t = [get(name + ".weight", (dd.channels, 1, self.dw_ksizes[k], self.dw_ksizes[k])), get(name + ".bias", (dd.channels,)),
+                     get(bn + ".weight", (dd.channels,)), get(bn + ".bias", (dd.channels,))]
+                _lib.check(self._h, self._lib.mpx_load_dwconv_ln(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_dwconv_ln(%s)" % name)
                 continue
             t = [get(name + ".weight", (dd.channels, 1, self.dw_ksizes[k], self.dw_ksizes[k]))]
             t += [get("%s.%s" % (bn, key), (dd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
@@ -333,6 +370,10 @@ class MaskedForwardEngine:
                 name = nd.name.decode()
                 t = [get("%s.%s" % (name, key), (nd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
                 _lib.check(self._h, self._lib.mpx_load_norm(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_norm(%s)" % name)
+            for k, ld in enumerate(self.lnorms):        # ... and so do ConvNeXt's stand-alone LayerNorms
+                name = ld.name.decode()
+                t = [get(name + ".weight", (ld.channels,)), get(name + ".bias", (ld.channels,))]
+                _lib.check(self._h, self._lib.mpx_load_lnorm(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_lnorm(%s)" % name)
         return self
 
     # ---- kernels ----
@@ -786,7 +827,9 @@ class MaskedForwardEngine:
         transitions' average pools) split what a DenseNet engine books under 'pool'; empty / 0 on every other architecture.  'per_dw_ms'
         (one entry per depthwise layer) is the same split on a MobileNetV2 engine, 'per_clip_pool_ms' (one entry per clipped 3x3 max pool,
         mpx_clip_pool_info) on a GoogLeNet engine, 'per_shuffle_ms' (one entry per channel shuffle, mpx_shuffle_info) on a ShuffleNetV2 engine,
-        'per_se_gate_ms' / 'per_se_scale_ms' (one entry per SE layer: its gate and its scale launch) on an EfficientNet-B0 engine."""
+        'per_se_gate_ms' / 'per_se_scale_ms' (one entry per SE layer: its gate and its scale launch) on an EfficientNet-B0 engine,
+        'per_lnorm_ms' (one entry per stand-alone LayerNorm, mpx_lnorm_info; the depthwise + LayerNorm launches are per_dw_ms's) on a
+        ConvNeXt engine."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
@@ -799,9 +842,11 @@ class MaskedForwardEngine:
         per_sh = (C.c_double * max(1, n_sh))()
         per_sg = (C.c_double * max(1, len(self.ses)))()
         per_ss = (C.c_double * max(1, len(self.ses)))()
-        _lib.check(self._h, self._lib.mpx_profile_collect_se(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh, per_sg, per_ss), "mpx_profile_collect_se")
+        per_ln = (C.c_double * max(1, len(self.lnorms)))()
+        _lib.check(self._h, self._lib.mpx_profile_collect_ln(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh, per_sg, per_ss, per_ln), "mpx_profile_collect_ln")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
                 "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
                 "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp], "per_shuffle_ms": list(per_sh)[:n_sh],
-                "per_se_gate_ms": list(per_sg)[:len(self.ses)], "per_se_scale_ms": list(per_ss)[:len(self.ses)]}
+                "per_se_gate_ms": list(per_sg)[:len(self.ses)], "per_se_scale_ms": list(per_ss)[:len(self.ses)],
+                "per_lnorm_ms": list(per_ln)[:len(self.lnorms)]}

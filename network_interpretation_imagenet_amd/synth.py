@@ -444,6 +444,69 @@ def make_efficientnet_state_dict(seed=7):
     return sd
 
 
+CONVNEXT_DEPTHS = {"convnext_tiny": (3, 3, 9, 3), "convnext_small": (3, 3, 27, 3)}
+CONVNEXT_DIMS = (96, 192, 384, 768)
+# ConvNeXt's synthetic gains.  Every block normalises its own input (LayerNorm behind the depthwise conv), so a block's update has a scale of
+# its own -- layer_scale x the fc2 gain x the RMS of gelu(.) -- whatever the trunk's, and the trunk can only grow additively: variance 1 behind a
+# stem or downsample LayerNorm plus the sum of the updates' of the stage.  torchvision initialises layer_scale to 1e-6, which switches every
+# block off; trained networks have O(0.1 .. 1), which is what is drawn here (U(0.1, 1)).  CONVNEXT_FC1_GAIN spreads the GELU pre-activations
+# over about +-3 times their standard deviation of 1.5 (negative lobe and linear part both exercised); CONVNEXT_FC2_GAIN keeps 27 adds of one
+# stage within a factor of two; CONVNEXT_FC_GAIN is the standard deviation of the logits (the head's LayerNorm hands classifier.2 a
+# unit-variance row), chosen for a peaked, unsaturated softmax.  Surveyed on the CPU in fp64 on the rows tests/convnext_ref.E2E_CASES scores
+# (felzenszwalb / grid picture).  convnext_tiny: trunk RMS 1.04 .. 1.38 over the 18 blocks, GELU pre-activations std 1.53 with 1 % / 99 %
+# quantiles -3.5 / +3.6 (a quarter below -1, a quarter above +1), unmasked softmax peak 0.14 / 0.087, rows' peaks 0.53 .. 0.61 / 0.55 .. 0.58,
+# top-two logit margins >= 2.56 / 2.70; with every layer_scale at 1e-6 the rows' scores move by 0.42 .. 0.53, with ReLU for GELU by 0.021 ..
+# 0.106, with each block LayerNorm's statistics taken over the whole map by 0.017 .. 0.027.  convnext_small: trunk RMS 1.04 .. 1.89 over the 36
+# blocks, unmasked peak 0.54 / 0.73, rows' peaks 0.54 .. 0.62 / 0.43 .. 0.68, margins >= 1.39 / 1.43, smallest moves 0.0107 (GELU) / 0.0052 (map
+# statistics).  tests/test_convnext_cpu.py asserts the bounds on exactly those rows.
+CONVNEXT_FC1_GAIN = 1.5
+CONVNEXT_FC2_GAIN = 0.5
+CONVNEXT_FC_GAIN = {"convnext_tiny": 2.0, "convnext_small": 3.0}    # tiny at 3.0: rows' softmax peaks up to 0.952; small at 2.0: two of the rows the GPU
+                                                                    # test scores move by under 2e-3 with ReLU for GELU / the LayerNorm over the map
+
+
+def make_convnext_state_dict(arch, seed=7):
+    """OrderedDict with the key set, order and shapes of models.convnext_tiny() / convnext_small().state_dict(): features.0.0.{weight, bias}
+    (Conv2d(3, 96, 4, 4)), features.0.1.{weight, bias} (LayerNorm2d), per block features.S.B.layer_scale [C][1][1], block.0.{weight, bias}
+    ([C][1][7][7]), block.2.{weight, bias} (LayerNorm), block.3.{weight, bias} (Linear: [4C][C]), block.5.{weight, bias} ([C][4C]), the
+    downsample modules features.{2,4,6}.0.{weight, bias} (LayerNorm2d(C_prev)) and .1.{weight, bias} (Conv2d(C_prev, C, 2, 2)) in module order
+    between the stages, classifier.0.{weight, bias} (LayerNorm2d(768)) and classifier.2.{weight, bias}: 28,589,128 / 50,223,688 parameters.
+    Draws: convs N(0, sqrt(1 / fan_in)) with bias N(0, 0.1) (a LayerNorm follows every one of them but block.3 / block.5); LayerNorm weight
+    U(0.9, 1.1), bias N(0, 0.1); block.3 N(0, CONVNEXT_FC1_GAIN / sqrt(C)) with bias N(0, 0.2); block.5 N(0, CONVNEXT_FC2_GAIN / sqrt(4C)) with
+    bias N(0, 0.05); layer_scale U(0.1, 1); classifier.2 N(0, CONVNEXT_FC_GAIN[arch] / sqrt(768)) with bias N(0, 0.1)."""
+    depths = CONVNEXT_DEPTHS[arch]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def conv(name, cin, cout, k, groups=1):
+        sd[name + ".weight"] = torch.randn(cout, cin // groups, k, k, generator=g) * (1.0 / (k * k * cin // groups)) ** 0.5
+        sd[name + ".bias"] = torch.randn(cout, generator=g) * 0.1
+
+    def ln(name, c):
+        sd[name + ".weight"] = 0.9 + 0.2 * torch.rand(c, generator=g)
+        sd[name + ".bias"] = torch.randn(c, generator=g) * 0.1
+
+    conv("features.0.0", 3, CONVNEXT_DIMS[0], 4)
+    ln("features.0.1", CONVNEXT_DIMS[0])
+    for s, (c, d) in enumerate(zip(CONVNEXT_DIMS, depths)):
+        if s:
+            ln("features.%d.0" % (2 * s), CONVNEXT_DIMS[s - 1])
+            conv("features.%d.1" % (2 * s), CONVNEXT_DIMS[s - 1], c, 2)
+        for b in range(d):
+            p = "features.%d.%d." % (2 * s + 1, b)
+            sd[p + "layer_scale"] = 0.1 + 0.9 * torch.rand(c, 1, 1, generator=g)
+            conv(p + "block.0", c, c, 7, groups=c)
+            ln(p + "block.2", c)
+            sd[p + "block.3.weight"] = torch.randn(4 * c, c, generator=g) * (CONVNEXT_FC1_GAIN / c ** 0.5)
+            sd[p + "block.3.bias"] = torch.randn(4 * c, generator=g) * 0.2
+            sd[p + "block.5.weight"] = torch.randn(c, 4 * c, generator=g) * (CONVNEXT_FC2_GAIN / (4 * c) ** 0.5)
+            sd[p + "block.5.bias"] = torch.randn(c, generator=g) * 0.05
+    ln("classifier.0", CONVNEXT_DIMS[3])
+    sd["classifier.2.weight"] = torch.randn(1000, CONVNEXT_DIMS[3], generator=g) * (CONVNEXT_FC_GAIN[arch] / CONVNEXT_DIMS[3] ** 0.5)
+    sd["classifier.2.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_resnext_state_dict(arch, seed=7):
     """OrderedDict with the key set and shapes of models.resnext50_32x4d() / resnext101_32x8d(): the ResNets' names, conv1 [width][cin][1][1],
     conv2 [width][width / 32][3][3] (32 groups), conv3 [4 * planes][width][1][1].  Conv gains come from the fan-in (9 * cg for conv2); the
@@ -480,6 +543,8 @@ def make_state_dict(arch, seed=7):
     make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict) key set."""
     if arch == "efficientnet_b0":
         return make_efficientnet_state_dict(seed)
+    if arch in CONVNEXT_DEPTHS:
+        return make_convnext_state_dict(arch, seed)
     if arch in RESNEXT_ARCHS:
         return make_resnext_state_dict(arch, seed)
     if arch in SHUFFLENET_WIDTHS:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-layer conv timing (HIP events inside the engine) for one forward batch.
 usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d add the
-                                                                 grouped 3x3 launches as rows of their own, with their bytes and TB/s)
+                                                                 grouped 3x3 launches as rows of their own, with their bytes and TB/s;
+                                                                 convnext_tiny / convnext_small the depthwise 7x7 + LayerNorm launches and the
+                                                                 stand-alone LayerNorms, with bytes, TB/s and the shares by op class)
        MPX_PER_LAYER=1 ...    one row per conv with its tile
 A conv + downsample conv that run as ONE launch (K-concatenated) are booked on the main conv; they get rows of their own, with both convs'
 FLOPs, under the grouped table (the grouped rows count the main conv's FLOPs only).
@@ -203,7 +205,43 @@ if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + 
     print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
           % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
 shuffle_net = arch.startswith("shufflenet")
-if eng.ses:     # EfficientNet-B0: the depthwise k x k + BN + SiLU, SE gate and SE scale launches between the 1x1 convs
+if eng.lnorms:  # ConvNeXt: the depthwise 7x7 + LayerNorm launches and the stand-alone LayerNorms between the MFMA convs
+    print("-- depthwise 7x7 + bias + LayerNorm over C (mpx_dwconv7x7_ln: one launch per block); bytes = split-fp16 planes read once + written once: the launch's floor --")
+    tot_dw = dw_bytes = tot_ln = ln_bytes = 0.0
+    by_map = {}
+    for dd, ms in zip(eng.dwconvs, prof["per_dw_ms"]):
+        ms /= reps
+        nbytes = batch * 4.0 * dd.channels * 2 * dd.hin * dd.hin
+        tot_dw += ms
+        dw_bytes += nbytes
+        a = by_map.setdefault((dd.channels, dd.hin), [0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += ms
+        a[2] += nbytes
+        if os.environ.get("MPX_PER_LAYER"):
+            print("%-24s C %4d k7 %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (dd.name.decode(), dd.channels, dd.hin, dd.hin, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    for (c, hin), (n, ms, nbytes) in sorted(by_map.items()):
+        print("depthwise 7x7 + LayerNorm C %4d %3dx%-3d x%-2d %9.3f ms %8.1f MB %7.2f TB/s" % (c, hin, hin, n, ms, nbytes / 1e6, nbytes / max(ms, 1e-9) / 1e9))
+    print("-- stand-alone LayerNorms (mpx_layernorm_c; classifier.0 = mpx_global_avgpool_ln, which reads the 7x7 map and writes one row); bytes = read + written --")
+    for ld, ms in zip(eng.lnorms, prof["per_lnorm_ms"]):
+        ms /= reps
+        pooled = ld.name == b"classifier.0"
+        nbytes = batch * 4.0 * ld.channels * ((49 + 1) if pooled else 2 * ld.hw * ld.hw)
+        tot_ln += ms
+        ln_bytes += nbytes
+        print("%-16s C %4d %3dx%-3d %9.3f ms %8.1f MB %7.2f TB/s" % (ld.name.decode(), ld.channels, 7 if pooled else ld.hw, 7 if pooled else ld.hw, ms, nbytes / 1e6,
+                                                                   nbytes / max(ms, 1e-9) / 1e9))
+    gelu_ms = sum(ms for a, ms in zip(eng.epilogue_acts, prof["per_conv_ms"]) if a) / reps
+    gelu_fl = sum(conv_flops(li) for li, a in enumerate(eng.epilogue_acts) if a)
+    allms = sum(prof["ms"].values()) / reps
+    print("depthwise + LayerNorm total %.3f ms/batch, %.1f MB -> %.2f TB/s; stand-alone LayerNorms %.3f ms/batch -> %.2f TB/s; GELU convs (block.3, tile %s) %.3f ms/batch -> %.1f TFLOP/s; conv total %.3f ms/batch"
+          % (tot_dw, dw_bytes / 1e6, dw_bytes / max(tot_dw, 1e-9) / 1e9, tot_ln, ln_bytes / max(tot_ln, 1e-9) / 1e9,
+             sorted({eng.conv_tile(li) for li, a in enumerate(eng.epilogue_acts) if a}), gelu_ms, gelu_fl / max(gelu_ms, 1e-9) / 1e9, tot))
+    print("share of the forward by op class: conv (MFMA) %.1f %% (of which the GELU convs %.1f %% of the forward), depthwise + LayerNorm (%d launches) %.1f %%, "
+          "LayerNorms (%d) %.1f %%, staging (K0) %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
+          % (100 * tot / allms, 100 * gelu_ms / allms, len(eng.dwconvs), 100 * tot_dw / allms, len(eng.lnorms), 100 * tot_ln / allms,
+             100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * prof["ms"]["head"] / reps / allms, allms, sum(prof["launches"].values()) // reps - 1))
+elif eng.ses:     # EfficientNet-B0: the depthwise k x k + BN + SiLU, SE gate and SE scale launches between the 1x1 convs
     print("-- depthwise k x k + BN with SiLU on load and in the epilogue (mpx_dwconv_bn_act); bytes = split-fp16 planes read + written, pitch channels per pixel --")
     tot_dw = dw_bytes = tot_g = g_bytes = tot_s = s_bytes = 0.0
     by_class = {}
@@ -385,7 +423,7 @@ if ptail_of:
         ms = prof["per_conv_ms"][c3] / reps
         print("  %-16s + %-16s %8.3f ms %9.1f GFLOP %8.1f TFLOP/s" % (names[c3], names[n1], ms, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 layer1 = sum(ms for d, ms in zip(eng.layers, prof["per_conv_ms"]) if d.name.startswith(b"layer1.") or d.name == b"layer2.0.conv1") / reps
-if not eng.ses:     # (a ResNet's line; an EfficientNet engine has no layer1)
+if not eng.ses and not eng.lnorms:     # (a ResNet's line; an EfficientNet or ConvNeXt engine has no layer1)
     print("layer1 (+ layer2.0.conv1): %.3f ms/batch" % layer1)
 allfl = eng.flops_per_forward * batch
 print("conv total %.3f ms/batch -> %.1f TFLOP/s algorithmic; other kinds ms/batch: %s" % (

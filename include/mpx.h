@@ -217,6 +217,31 @@ enum {
  * (block.3's output in stage 0, 1.5 x a ResNet buffer, MobileNetV2's size: 14.45 MB) -- X the block input and residual, T1 the LayerNorm
  * output and then, dead after block.3, the block output, T2 the hidden map -- plus the staging (0.85 MB): 15.3 MB per slot.  It stages through
  * mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
+ * -- or one of torchvision's two ViT-Base networks, the first here that are no CNN (86,567,656 / 88,224,232 parameters, 17,563,828,224 /
+ * 4,409,186,304 MAC per forward, the attention products Q K^T and P V counted: 2 * T^2 * 64 * 12 per layer):
+ *   MPX_ARCH_VIT + 16 / 32        vit_b_16 / vit_b_32 (patch 16 / 32, T = 197 / 50 tokens, 12 layers of width D = 768, 12 heads of 64, MLP 3072);
+ *                                 every other id in [13000, 14000) is MPX_E_ARG (vit_l_16 / vit_l_32 / vit_h_14 and the Swin family are not served)
+ * A ViT engine runs conv_proj (3 -> 768, p x p stride p WITHOUT padding, bias, reading the padded NHWC4 staging 3 pixels into its border: one
+ * p-pixel x 4-channel run per kernel row, k_packed = p * 4p = 16 * 64 / 32 * 128, zero weights on channel 3) into planes [B][T - 1][768], the token
+ * assembly (mpx_tokens_assemble: class_token and encoder.pos_embedding, mpx_load_tokens), then 12 encoder layers of 7 launches each -- ln_1
+ * (mpx_layernorm_c on the B * T rows), self_attention.in_proj (768 -> 2304, bias), the attention (mpx_attention), self_attention.out_proj
+ * (768 -> 768, bias, residual), ln_2, mlp.0 (768 -> 3072, GELU in the epilogue as a ConvNeXt block.3: mpx_conv_epilogue_act) and mlp.3 (3072 ->
+ * 768, bias, residual) --, encoder.ln on the class-token row of each image alone (mpx_layernorm_rows, rows T apart -> planes [B][768]),
+ * heads.head (the logit layer and last conv entry) and the head: 2 + 7 * 12 + 3 = 89 launches.  Every LayerNorm has eps 1e-6.
+ * TOKEN LAYERS ARE NO SQUARE MAPS (197 is prime): the Linear layers of the encoder are 1x1 entries of the conv list that report hin = hout = 0;
+ * mpx_conv_rows reports their T rows per image (0 on every layer of every other engine), and their planes are [B][T][cin] -> [B][T][cout].
+ * DESCRIPTOR NAMES DROP THE LEADING "encoder.layers." (name[48] cannot hold "encoder.layers.encoder_layer_11.self_attention.out_proj"):
+ * "encoder_layer_11.self_attention.out_proj", "encoder_layer_0.ln_1", "encoder_layer_3.self_attention"; a loader puts the prefix back on every
+ * name that starts with "encoder_layer_".  in_proj's tensors are `<prefix>.self_attention.in_proj_weight` / `in_proj_bias` in torchvision's
+ * state_dict (an underscore, nn.MultiheadAttention's parameters), every other layer's `<name>.weight` / `<name>.bias`.
+ * A bias-only layer has no bn_name; mpx_set_conv_weights takes its bias as conv_bias with gamma = 1, beta = 0, mean = 0, var = 1, eps = 0, which
+ * packs to scale = 2^-e, shift = bias exactly -- there is no second epilogue form.  50 entries in the conv list ("conv_proj",
+ * "encoder_layer_0.self_attention.in_proj", "....out_proj", "encoder_layer_0.mlp.0", "encoder_layer_0.mlp.3", ..., "heads.head"), 25 stand-alone
+ * LayerNorms ("encoder_layer_0.ln_1", "encoder_layer_0.ln_2", ..., "encoder.ln"; hw = 0), 12 attention launches (mpx_num_attn).
+ * Four activation buffers per image, each of its own size: X (T * 768, the residual stream), T1 (T * 768: the patch planes, a LayerNorm's
+ * output, the attention's), QKV (T * 2304: in_proj's output and then, dead behind the attention, out_proj's) and H (T * 3072): 5.45 MB / 1.38 MB
+ * plus the staging (0.85 MB): 6.3 / 2.2 MB per slot.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry
+ * points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -233,6 +258,7 @@ enum {
 #define MPX_ARCH_EFFICIENTNET 10000
 #define MPX_ARCH_RESNEXT 11000
 #define MPX_ARCH_CONVNEXT 12000
+#define MPX_ARCH_VIT 13000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -293,6 +319,10 @@ int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act);
  * 1 exact GELU (a ConvNeXt engine's block.3 layers: mpx_conv_bn_act returns gelu(W x + b), the layer runs the generic tiles 0, 1, 2, 4 and 7
  * only, and mpx_set_conv_tile refuses every other tile on it).  mpx_conv_desc keeps its layout. */
 int mpx_conv_epilogue_act(const mpx_engine* h, int i, int* act);
+/* The rows per image of layer i where they are no square map: *rows_per_image = T on a ViT engine's token layers (in_proj, out_proj, mlp.0,
+ * mlp.3: mpx_conv_desc reports hin = hout = 0 there and the planes are [B][T][channels]), 0 on every layer of every other engine and on a ViT
+ * engine's conv_proj (a 14 x 14 / 7 x 7 map) and heads.head (one row per image). */
+int mpx_conv_rows(const mpx_engine* h, int i, int* rows_per_image);
 
 /* replaces: the state_dict tensors torchvision loads (same line as above).  HOST pointers, f32:
  * w = conv weight OIHW [cout][cin][k][k]; conv_bias = the conv's own bias [cout] or NULL (torchvision's ResNet convs have
@@ -739,6 +769,48 @@ int mpx_layernorm_c(mpx_engine* h, const void* in_hi, const void* in_lo, const f
 int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps,
                           void* out_hi, void* out_lo, int B, int hw, int C, void* stream);
 
+/* ---- ViT: scaled-dot-product attention, the token assembly, LayerNorm of strided rows ----------------------------------------------
+ * replaces: `self.self_attention(x, x, x, need_weights=False)` of torchvision's vision_transformer.py EncoderBlock.forward BEHIND its input
+ *           projection -- the softmax(Q K^T / 8) V of every head -- inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * qkv: DEV split planes [B][T][3 D], D = heads * 64 (head_dim is 64): Q at channel 0, K at D, V at 2 D, head h owning channels 64 h .. 64 h + 63
+ * of each -- what in_proj writes.  out: DEV split planes [B][T][D], what out_proj reads.  Both products run on the fp16 MFMA pipe as the three
+ * products A_hi B_lo, A_lo B_hi, A_hi B_hi into fp32.  THE CONTRACT per query row i of one (image, head), fp32, one rounding per operator
+ * (csrc/mpx_attn.h):
+ *     s_ij = 0.125f * (q_i . k_j);  m_i = max_j s_ij;  e_ij = expf(s_ij - m_i);
+ *     l_i = ((part_0 + part_1) + part_2) + part_3 with part_g = the e_ij of the keys with (j >> 2) & 3 == g summed in ascending j;
+ *     o_id = (sum_j split(1024 e_ij) v_jd) / (1024 l_i): one IEEE division per element behind the whole sum; the re-split.
+ * Keys j >= T of the last step of 32 contribute exactly nothing (zero operands, the constant 0.f for e, no part in the maximum); query rows
+ * >= T are never written.  An output row's bits depend on its image's data alone: not on B, the image's position in the batch or the grid.
+ * MPX_E_ARG with a message for T < 1 or T > 512, heads outside 1 .. 64 (the width IS heads * 64), B <= 0, a null or misaligned (16 bytes) plane.
+ * max_blocks > 0 caps the grid (a test hook: the result does not depend on it), 0 = the entry's own cap.  ONE launch. */
+int mpx_attention(mpx_engine* h, const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int T, int heads, int max_blocks,
+                  void* stream);
+/* replaces: `torch.cat([batch_class_token, x], dim=1)` of VisionTransformer.forward and `input + self.pos_embedding` of Encoder.forward.
+ * patch: DEV split planes [B][T - 1][D] (conv_proj's output); class_token: DEV f32[D]; pos_embedding: DEV f32[T][D] (mpx_token_params);
+ * out: DEV split planes [B][T][D].  out[b][0] = class_token + pos[0], out[b][1 + i] = (hi + lo of patch[b][i], exact) + pos[1 + i]: one fp32 add
+ * each, re-split.  MPX_E_STATE on an engine that is no ViT; MPX_E_ARG for T < 1, D no positive multiple of 8, a null or misaligned pointer. */
+int mpx_tokens_assemble(mpx_engine* h, const void* patch_hi, const void* patch_lo, const float* class_token, const float* pos_embedding,
+                        void* out_hi, void* out_lo, int B, int T, int D, int max_blocks, void* stream);
+/* replaces: `self.ln(...)` of Encoder.forward as far as `x[:, 0]` reads it: the LayerNorm of input rows that lie in_stride rows apart.
+ * in: DEV split planes [rows * in_stride][C] of which row r * in_stride is read; out: DEV split planes [rows][C].  mpx_layernorm_c's contract
+ * unchanged (it is that kernel with a row stride on its loads); in_stride = T normalises the class-token row of each of `rows` images. */
+int mpx_layernorm_rows(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
+                       void* out_lo, long long rows, long long in_stride, int C, int max_blocks, void* stream);
+/* The attention launches of the op list in forward order (12 on a ViT engine, 0 on every other). */
+typedef struct mpx_attn_desc {
+    char name[48];       /* the module's state_dict prefix without "encoder.layers.": "encoder_layer_3.self_attention" */
+    int32_t tokens;      /* T */
+    int32_t heads;
+    int32_t head_dim;    /* 64 */
+} mpx_attn_desc;
+int mpx_num_attn(const mpx_engine* h);
+int mpx_attn_info(const mpx_engine* h, int k, mpx_attn_desc* out);
+/* A ViT engine's two parameters that belong to no layer: HOST f32 class_token [1][1][D] and encoder.pos_embedding [1][T][D], uploaded
+ * synchronously as they are; mpx_weights_complete and mpx_forward count them.  MPX_E_STATE on an engine that is no ViT.  mpx_token_params
+ * returns their DEV pointers, T and D (NULL, NULL, 0, 0 on every other engine); any pointer may be NULL. */
+int mpx_load_tokens(mpx_engine* h, const float* class_token, const float* pos_embedding);
+int mpx_token_params(const mpx_engine* h, const float** class_token, const float** pos_embedding, int* tokens, int* width);
+
 /* ---- ShuffleNetV2: channel_shuffle(cat(a, b), 2) into the two-half layout ------------------------------------------------------
  * replaces: `torch.cat((x1, self.branch2(x2)), dim=1)` / `torch.cat((self.branch1(x), self.branch2(x)), dim=1)` and `channel_shuffle(out, 2)`
  *           of torchvision's shufflenetv2.py InvertedResidual.forward inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
@@ -865,7 +937,12 @@ int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launch
 int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms, double* per_lnorm_ms);
-/* Algorithmic FLOPs (2*MAC, convs + depthwise convs + the SE layers' two FCs + fc) of one masked forward. */
+/* The same with a ViT's split of kind 2: per_attn_ms (HOST f64[mpx_num_attn], may be NULL) gets every attention launch, *tokens_ms (may be
+ * NULL) the token assembly; the LayerNorms (encoder.ln's strided launch included) are per_lnorm_ms's. */
+int mpx_profile_collect_attn(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                             double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                             double* per_se_scale_ms, double* per_lnorm_ms, double* per_attn_ms, double* tokens_ms);
+/* Algorithmic FLOPs (2*MAC, convs + depthwise convs + the SE layers' two FCs + a ViT's attention products + fc) of one masked forward. */
 double mpx_flops_per_forward(const mpx_engine* h);
 
 #ifdef __cplusplus

@@ -48,6 +48,10 @@ class LnormDesc(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("channels", C.c_int32), ("hw", C.c_int32)]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [("name", C.c_char * 48), ("tokens", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -158,6 +162,16 @@ SIGNATURES = {
     "mpx_layernorm_c": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp]),
     "mpx_global_avgpool_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_ln": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 9),
+    # ViT: the token layers' rows, the attention launches, class token + position embedding, the three kernels of csrc/mpx_attn.h
+    "mpx_conv_rows": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    "mpx_num_attn": (_i, [_vp]),
+    "mpx_attn_info": (_i, [_vp, _i, C.POINTER(AttnDesc)]),
+    "mpx_load_tokens": (_i, [_vp, _vp, _vp]),
+    "mpx_token_params": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mpx_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpx_tokens_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpx_layernorm_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _vp]),
+    "mpx_profile_collect_attn": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 11),
 }
 
 _lib = None

@@ -17,6 +17,7 @@
 #include "mpx_mbconv.h"
 #include "mpx_gconv.h"
 #include "mpx_cnext.h"
+#include "mpx_attn.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,11 +45,13 @@ constexpr size_t kSqueezeActElemsPerImage = 111 * 111 * 64;  // SqueezeNet 1.1: 
 constexpr size_t kShuffleActElemsPerImage = 112 * 112 * 32; // ShuffleNetV2: conv1's output, 24 channels at pitch 32 (= x2_0's stage2.0.branch2.0 map, 56 * 56 * 128)
 constexpr size_t kEffActElemsPerImage = 112 * 112 * 96;  // EfficientNet-B0: features.2.0's expanded map (= MobileNetV2's buffer)
 constexpr size_t kCnextActElemsPerImage = 56 * 56 * 384;  // ConvNeXt: block.3's output in stage 0 (the same number of elements again)
+constexpr int kVitWidth = 768, kVitHeads = 12, kVitMlp = 3072, kVitLayers = 12;     // torchvision vit_b_16 / vit_b_32
 constexpr int kSmallCPad = 32;                         // small nets: channels are stored padded to a multiple of 32
 
 enum OpKind { OP_CONV = 0, OP_MAXPOOL = 1, OP_AVGPOOL = 2, OP_HEAD = 3, OP_AVGPAD = 4, OP_BTAIL = 5, OP_MAXPOOL2 = 6, OP_MAXPOOL3P0 = 7,
               OP_CATNORM = 8, OP_AVGPOOL2 = 9, OP_DWCONV = 10, OP_AVGPOOL6 = 11, OP_AVGLOGITS = 12, OP_MAXPOOL3C = 13, OP_SHUFFLE = 14,
-              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17, OP_PTAIL = 18, OP_LNORM = 19, OP_AVGPOOLLN = 20 };
+              OP_SEGATE = 15, OP_SESCALE = 16, OP_AVGPOOLSILU = 17, OP_PTAIL = 18, OP_LNORM = 19, OP_AVGPOOLLN = 20,
+              OP_TOKENS = 21, OP_ATTN = 22, OP_LNORMROWS = 23 };
 enum Buf { BUF_INPUT = -1, BUF_POOL = -2, BUF_NONE = -3, BUF_STEM = -4 };   // BUF_STEM: the pooled stem output (planes of its own)
 
 struct ConvLayer {
@@ -61,6 +64,8 @@ struct ConvLayer {
     bool is_fc = false;
     bool is_stem = false;
     int consumer_act = 0;   // 1: torchvision follows this conv with SiLU, which its one consumer takes on load (mpx_mbconv.h); relu is 0 then
+    int rows = 0;           // > 0: a token layer (ViT): the layer runs on `rows` = T rows per image that are no square map -- d.hin = d.hout = 0
+                            // and conv_params hands the kernels hin = ho = rows, win = wo = 1 (mpx_conv_rows)
     int epi_act = 0;        // 1: exact GELU in the epilogue (a ConvNeXt block.3: ConvGelu, mpx_conv.h); the layer runs the generic tiles only
     bool has_bias = false;  // the reference module is nn.Conv2d(bias=True) (small nets): state_dict has <name>.bias
     int cin_pad = 0;        // channels per pixel of the input planes (= cin except for the small nets, which pad to 32)
@@ -162,6 +167,11 @@ struct LnLayer {
     bool loaded = false;
 };
 
+// An attention launch of the op list (ViT; mpx_attn.h): in = the in_proj planes [B][T][3 D], out = planes [B][T][D]
+struct AttnLayer {
+    mpx_attn_desc d;
+};
+
 // A Squeeze-and-Excitation layer (EfficientNet-B0; mpx_mbconv.h): fp32 fc weights and biases of its own, laid out for se_gate_kernel
 struct SeLayer {
     mpx_se_desc d;
@@ -178,6 +188,8 @@ constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shu
 constexpr int kProfSubSeGate = -3000000;    // ... of EfficientNet's SE layer k (mpx_engine::ses): its gate launch kProfSubSeGate - k,
 constexpr int kProfSubSeScale = -4000000;   //     its scale launch kProfSubSeScale - k
 constexpr int kProfSubLnorm = -5000000;     // ... of ConvNeXt's stand-alone LayerNorm k (mpx_engine::lnorms) kProfSubLnorm - k
+constexpr int kProfSubAttn = -6000000;      // ... of a ViT's attention launch k (mpx_engine::attns) kProfSubAttn - k
+constexpr int kProfSubTokens = -7000000;    // ... of a ViT's token assembly
 
 // A channel shuffle of the op list (ShuffleNetV2; mpx_shuffle.h): a = Op::in at a_pitch, b = Op::res advanced by b_offset at b_pitch
 struct ShuffleOp {
@@ -223,6 +235,13 @@ struct mpx_engine {
     int se_pitch_max = 0;
     bool convnext = false;          // torchvision ConvNeXt-Tiny / -Small: CNBlocks over three activation buffers, staged through K0 only
     std::vector<LnLayer> lnorms;    // its stand-alone LayerNorms in forward order
+    bool vit = false;               // torchvision vit_b_16 / vit_b_32: an encoder over four activation buffers of sizes of their own, staged through K0 only
+    int vit_T = 0, vit_D = 0;       // tokens per image (197 / 50) and width (768)
+    std::vector<AttnLayer> attns;   // its attention launches in forward order
+    float* cls_token = nullptr;     // DEV f32[D]: class_token
+    float* pos_emb = nullptr;       // DEV f32[T][D]: encoder.pos_embedding
+    bool tokens_loaded = false;
+    size_t act_elems_buf[4] = {0, 0, 0, 0};     // elements per image of each activation buffer where they differ (ViT); 0: act_elems_per_image
     int n_act_bufs = kActBufs;      // activation buffers the op list uses (mpx_create allocates these only)
     size_t act_elems_per_image = 0;
     float* k0_scratch = nullptr;    // small nets: f32[2 + 4096 + max_batch]: image min, max-min, per-superpixel max, per-mask max
@@ -332,6 +351,7 @@ int build_topology_googlenet(mpx_engine* h);
 int build_topology_shufflenet(mpx_engine* h);
 int build_topology_efficientnet(mpx_engine* h);
 int build_topology_convnext(mpx_engine* h);
+int build_topology_vit(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -345,6 +365,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_SHUFFLENET && h->arch < MPX_ARCH_SHUFFLENET + 1000) return build_topology_shufflenet(h);
     if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
     if (h->arch >= MPX_ARCH_CONVNEXT && h->arch < MPX_ARCH_CONVNEXT + 1000) return build_topology_convnext(h);
+    if (h->arch >= MPX_ARCH_VIT && h->arch < MPX_ARCH_VIT + 1000) return build_topology_vit(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
@@ -1569,6 +1590,88 @@ int build_topology_convnext(mpx_engine* h) {
     return 0;
 }
 
+// torchvision vit_b_16 / vit_b_32 (vision_transformer.py, eval mode, dropout 0): conv_proj = Conv2d(3, 768, p, stride p, bias), the class
+// token in front of the 14 x 14 / 7 x 7 patch rows, + encoder.pos_embedding, 12 EncoderBlocks of width 768 (ln_1, MultiheadAttention with 12
+// heads of 64, residual, ln_2, Linear(768, 3072) + GELU, Linear(3072, 768), residual), encoder.ln, heads.head = Linear(768, 1000) on the
+// class-token row.  Every LayerNorm has eps 1e-6.  Every Linear is a 1x1 entry of the conv list whose rows are the B * T tokens: T = 197 /
+// 50 rows per image are no square map, so such a layer reports hin = hout = 0, mpx_conv_rows reports T and conv_params hands the kernels
+// hin = ho = T, win = wo = 1 (ConvLayer::rows).  default_tile sees the descriptor as always: in_proj runs tile 10, out_proj and mlp.3 (residual
+// operand) tile 9, mlp.0 (GELU in the epilogue, ConvGelu) the generic tile 7, heads.head tile 7, the stem tile 2.
+// The stem reads the padded NHWC4 staging 3 pixels into its border, one p-pixel x 4-channel run per kernel row: k_per_tap = 4 p (64: AlexNet's
+// two-step form; 128: four steps), k_packed = p * 4 p.  Rows and columns reach staging index 3 + 14 * 16 - 1 = 3 + 7 * 32 - 1 = 226 < 230.
+// Descriptor names drop the leading "encoder.layers." (name[48] cannot hold "encoder.layers.encoder_layer_11.self_attention.out_proj"); the
+// loader puts it back.  A bias-only layer has no bn_name: scale = 2^-e, shift = bias, what gamma 1, beta 0, mean 0, var 1, eps 0 pack to.
+// Op list, 2 + 7 * 12 + 3 = 89 launches: conv_proj | token assembly | per layer (ln_1, in_proj, attention, out_proj + residual, ln_2, mlp.0 +
+// GELU, mlp.3 + residual) | encoder.ln on the class rows | heads.head | OP_HEAD.  50 conv entries, 25 LayerNorms, 12 attention launches.
+// Buffers, each of its own size: 0 = X [T][768] the residual stream, 1 = T1 [T][768] the patch planes, then a LayerNorm's output and the
+// attention's, 2 = QKV [T][2304] in_proj's output and then -- dead behind the attention -- out_proj's, 3 = H [T][3072] the hidden rows.
+int build_topology_vit(mpx_engine* h) {
+    const int patch = h->arch - MPX_ARCH_VIT;
+    if (patch != 16 && patch != 32) return MPX_E_ARG;
+    const int side = MPX_IMG / patch, T = side * side + 1, D = kVitWidth;
+    h->vit = true;
+    h->vit_T = T; h->vit_D = D;
+    h->n_act_bufs = 4;
+    h->act_elems_buf[0] = (size_t)T * D; h->act_elems_buf[1] = (size_t)T * D;
+    h->act_elems_buf[2] = (size_t)T * 3 * D; h->act_elems_buf[3] = (size_t)T * kVitMlp;
+    h->act_elems_per_image = h->act_elems_buf[3];
+    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int rows, int residual, int act, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = k; L.d.pad = 0;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one p-pixel x 4-channel run per kernel row (stride p, pad 0)
+        L.rows = (L.is_stem || fc) ? 0 : rows;
+        L.d.hin = L.is_stem ? MPX_IMG : (fc ? 1 : 0);
+        L.d.hout = L.is_stem ? side : (fc ? 1 : 0);
+        L.d.relu = 0; L.d.residual = residual;
+        L.epi_act = act;
+        L.is_fc = fc;
+        L.has_bias = true;
+        L.cin_pad = cin;
+        L.cout_store = cout;
+        L.d.k_packed = L.is_stem ? k * 4 * k : cin;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        if (act) L.tile = L.tile_default = 7;
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto add_ln = [&](const std::string& name) {
+        LnLayer N;
+        std::memset(&N.d, 0, sizeof N.d);
+        std::snprintf(N.d.name, sizeof N.d.name, "%s", name.c_str());
+        N.d.channels = D; N.d.hw = 0;
+        h->lnorms.push_back(N);
+        return (int)h->lnorms.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
+    const int X = 0, T1 = 1, QKV = 2, H = 3;
+    conv_op(add_conv("conv_proj", 3, D, patch, 0, 0, 0, false), BUF_INPUT, T1, BUF_NONE);
+    h->ops.push_back(Op{OP_TOKENS, -1, T1, X, BUF_NONE, T, D, BUF_NONE});
+    for (int l = 0; l < kVitLayers; ++l) {
+        const std::string p = "encoder_layer_" + std::to_string(l) + ".";
+        h->ops.push_back(Op{OP_LNORM, add_ln(p + "ln_1"), X, T1, BUF_NONE, T, D, BUF_NONE});
+        conv_op(add_conv(p + "self_attention.in_proj", D, 3 * D, 1, T, 0, 0, false), T1, QKV, BUF_NONE);
+        AttnLayer A;
+        std::memset(&A.d, 0, sizeof A.d);
+        set_name(A.d.name, p + "self_attention");
+        A.d.tokens = T; A.d.heads = kVitHeads; A.d.head_dim = AT_HD;
+        h->attns.push_back(A);
+        h->ops.push_back(Op{OP_ATTN, (int)h->attns.size() - 1, QKV, T1, BUF_NONE, T, D, BUF_NONE});
+        conv_op(add_conv(p + "self_attention.out_proj", D, D, 1, T, 1, 0, false), T1, QKV, X);      // QKV is dead behind the attention
+        h->ops.push_back(Op{OP_LNORM, add_ln(p + "ln_2"), QKV, T1, BUF_NONE, T, D, BUF_NONE});
+        conv_op(add_conv(p + "mlp.0", D, kVitMlp, 1, T, 0, 1, false), T1, H, BUF_NONE);
+        conv_op(add_conv(p + "mlp.3", kVitMlp, D, 1, T, 1, 0, false), H, X, QKV);
+    }
+    if (kVitHeads * AT_HD != D) return MPX_E_INTERNAL;
+    h->feat = D;
+    h->ops.push_back(Op{OP_LNORMROWS, add_ln("encoder.ln"), X, BUF_POOL, BUF_NONE, T, D, BUF_NONE});
+    conv_op(add_conv("heads.head", D, MPX_NUM_CLASSES, 1, 0, 0, 0, true), BUF_POOL, BUF_NONE, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
+}
+
 uint16_t half_bits(half_t v) {
     uint16_t u;
     std::memcpy(&u, &v, 2);
@@ -1888,6 +1991,7 @@ const KernelLds kKernelLds[] = {
     {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile2>>, ConvTile2::LDS},
     {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile4>>, ConvTile4::LDS},
     {(const void*)conv_f16x3_kernel<ConvGelu<ConvTile7>>, ConvTile7::LDS},
+    {(const void*)attention_f16x3_kernel, (int)((size_t)2 * AT_HD * (AT_MAX_T + 8) * 2)},
     {(const void*)btail_f16x3_kernel<BtResC64>, BtResC64::LDS},
     {(const void*)btail_f16x3_kernel<BtResC128>, BtResC128::LDS},
     {(const void*)btail_f16x3_kernel<BtDualC64>, BtDualC64::LDS},
@@ -2005,6 +2109,10 @@ int conv_params(mpx_engine* h, const ConvLayer& L, const half_t* in_hi, const ha
         p.kh = L.d.ksize; p.kw = L.d.ksize; p.stride = L.d.stride; p.pad = L.d.pad; p.k_per_tap = L.cin_pad;
     }
     p.ho = L.d.hout; p.wo = L.d.hout;
+    if (L.rows > 0) {       // a token layer (ViT): `rows` rows per image that are no square map -- a column of rows x 1 pixels
+        p.hin = L.rows; p.win = 1;
+        p.ho = L.rows; p.wo = 1;
+    }
     const long long M = (long long)B * p.ho * p.wo;
     if (M > 0x7fffffffLL) return fail(h, MPX_E_ARG, "batch too large for 32-bit pixel indices");
     p.M = (int)M;
@@ -2376,6 +2484,37 @@ int launch_cn_ln(mpx_engine* h, const CnLnParams& p, int max_blocks, int k, hipS
     return 0;
 }
 
+// one layernorm_rows_kernel launch (mpx_attn.h); `k` as launch_cn_ln's
+int launch_ln_rows(mpx_engine* h, const CnLnRowsParams& p, int max_blocks, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+    hipLaunchKernelGGL(layernorm_rows_kernel, dim3(cn_grid(h, p.ln.rows, p.ln.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one tokens_assemble_kernel launch (mpx_attn.h); `own` = the engine's own token assembly (profile record)
+int launch_tokens(mpx_engine* h, TokParams& p, int B, int max_blocks, bool own, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, own ? kProfSubTokens : -1);
+    p.chunks = (long long)B * p.T * (p.D >> 3);
+    long long grid = std::min<long long>((p.chunks + AT_NT - 1) / AT_NT, (long long)h->num_cus * 8);
+    if (max_blocks > 0) grid = std::min<long long>(grid, max_blocks);
+    hipLaunchKernelGGL(tokens_assemble_kernel, dim3((unsigned)std::max<long long>(grid, 1)), dim3(AT_NT), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// one attention_f16x3_kernel launch (mpx_attn.h): a unit is one (image, head); one head's V^T in the LDS (59 KB at T = 197) leaves room for
+// two workgroups per CU; `k` = the engine's attention launch it runs for (profile record), -1 from the stand-alone entry
+int launch_attn(mpx_engine* h, AttnParams& p, int B, int max_blocks, int k, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubAttn - k : -1);
+    p.units = (long long)B * p.heads;
+    long long grid = std::min<long long>(p.units, (long long)h->num_cus * 2);
+    if (max_blocks > 0) grid = std::min<long long>(grid, max_blocks);
+    hipLaunchKernelGGL(attention_f16x3_kernel, dim3((unsigned)std::max<long long>(grid, 1)), dim3(AT_NT), at_lds_bytes(p.T), st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
 // one global_avgpool_ln_kernel launch
 int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, int k, hipStream_t st) {
     ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
@@ -2475,8 +2614,10 @@ int pack_conv_weights(const mpx_conv_desc* d, int in_bf, int in_hp, const float*
     // k in [3, 7] only: no descriptor the generic layout accepts (k = 1, 2, 4, 8 with K = k * 32) changes meaning.
     // AlexNet's 11x11 first layer is the two-run form: 16 pixels x 4 channels = two K steps per kernel row, K = 11 * 64 = 704 (a
     // descriptor the generic layout refuses: 704 is not 121 * cin_pad).
-    const int run = (cin == 3 && k == 11 && K == 11 * 64) ? 64 : 32;
-    const bool stem = run == 64 || (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7) || (even_stem && cin == 3 && K == k * 32 && k <= 8);
+    // A ViT's patchify stems (even_stem again: 16x16 stride 16 and 32x32 stride 32) are one p-pixel run per kernel row: K = 16 * 64 / 32 * 128.
+    const bool patch_stem = even_stem && cin == 3 && ((k == 16 && K == 16 * 64) || (k == 32 && K == 32 * 128));
+    const int run = (cin == 3 && k == 11 && K == 11 * 64) ? 64 : (patch_stem ? 4 * k : 32);
+    const bool stem = run >= 64 || (cin == 3 && K == k * 32 && (k & 1) && k >= 3 && k <= 7) || (even_stem && cin == 3 && K == k * 32 && k <= 8);
     if (cin == 3 && k == kStemK && !stem) return MPX_E_ARG;
     // K = k*k*cin_pad: the input planes may carry more channels per pixel than the layer reads (small nets pad to 32)
     const int cin_pad = stem ? 0 : K / (k * k);
@@ -2591,7 +2732,11 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     // one arena: scratch | input planes | activation planes | pooled | logits | weights
     const size_t in_elems = h->small ? (size_t)h->img * h->img * kSmallCPad : (size_t)MPX_IMG_PAD * MPX_IMG_PAD * 4;
     const size_t in_plane = round_up((size_t)max_batch * in_elems * 2 + 256, 256);
-    const size_t act_plane = round_up((size_t)max_batch * h->act_elems_per_image * 2, 256);
+    size_t act_plane_buf[kActBufs], act_bytes = 0;       // one size for all buffers, except where the topology sizes each (ViT)
+    for (int b = 0; b < h->n_act_bufs; ++b) {
+        act_plane_buf[b] = round_up((size_t)max_batch * (h->act_elems_buf[b] ? h->act_elems_buf[b] : h->act_elems_per_image) * 2, 256);
+        act_bytes += 2 * act_plane_buf[b];
+    }
     const size_t pool_plane = round_up((size_t)max_batch * round_up(h->feat, kSmallCPad) * 2, 256);
     const size_t logit_bytes = round_up((size_t)max_batch * h->logit_pitch * 4, 256);
     const size_t k0_bytes = h->small ? round_up((size_t)(2 + 4096 + max_batch) * sizeof(float), 256) : 0;
@@ -2605,6 +2750,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
     for (const DwLayer& D : h->dws) wbytes += round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256) + (D.ln ? 3 : 2) * round_up((size_t)D.d.pitch * 4, 256);
     for (const LnLayer& N : h->lnorms) wbytes += 2 * round_up((size_t)N.d.channels * 4, 256);
+    if (h->vit) wbytes += round_up((size_t)h->vit_D * 4, 256) + round_up((size_t)h->vit_T * h->vit_D * 4, 256);
     for (const SeLayer& E : h->ses)
         wbytes += 2 * round_up((size_t)E.d.q * E.d.pitch * 4, 256) + round_up((size_t)E.d.q * 4, 256) + round_up((size_t)E.d.pitch * 4, 256);
     const size_t se_gate_bytes = round_up((size_t)max_batch * h->se_pitch_max * 4, 256);
@@ -2624,7 +2770,7 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     // only ever stages through K0, stem = "conv", never pays for it)
     const size_t stemtab_bytes = 2 * stem_plane + stem_w_bytes;
     h->tab_sizes[0] = tab_int_bytes; h->tab_sizes[1] = tab_lab_bytes; h->tab_sizes[2] = tab_vec_bytes; h->tab_sizes[3] = tab_bits_bytes;
-    const size_t total = scratch_bytes + 2 * in_plane + 2 * (size_t)h->n_act_bufs * act_plane + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes + se_gate_bytes;
+    const size_t total = scratch_bytes + 2 * in_plane + act_bytes + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes + se_gate_bytes;
     e = hipMalloc((void**)&h->arena, total);
     if (e != hipSuccess) { delete h; return (int)e; }
     h->arena_bytes = total;
@@ -2634,8 +2780,8 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     h->in_hi = (half_t*)take(in_plane);
     h->in_lo = (half_t*)take(in_plane);
     for (int b = 0; b < h->n_act_bufs; ++b) {
-        h->act_hi[b] = (half_t*)take(act_plane);
-        h->act_lo[b] = (half_t*)take(act_plane);
+        h->act_hi[b] = (half_t*)take(act_plane_buf[b]);
+        h->act_lo[b] = (half_t*)take(act_plane_buf[b]);
     }
     h->pool_hi = (half_t*)take(pool_plane);
     h->pool_lo = (half_t*)take(pool_plane);
@@ -2685,6 +2831,10 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
     for (LnLayer& N : h->lnorms) {
         N.gamma = (float*)take(round_up((size_t)N.d.channels * 4, 256));
         N.beta = (float*)take(round_up((size_t)N.d.channels * 4, 256));
+    }
+    if (h->vit) {
+        h->cls_token = (float*)take(round_up((size_t)h->vit_D * 4, 256));
+        h->pos_emb = (float*)take(round_up((size_t)h->vit_T * h->vit_D * 4, 256));
     }
     for (SeLayer& E : h->ses) {
         E.w1 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
@@ -2829,6 +2979,7 @@ int mpx_weights_complete(const mpx_engine* h) {
         if (!E.loaded) return 0;
     for (const LnLayer& N : h->lnorms)
         if (!N.loaded) return 0;
+    if (h->vit && !h->tokens_loaded) return 0;
     return 1;
 }
 
@@ -2932,7 +3083,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0 and ConvNeXt stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt and ViT stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -3396,6 +3547,94 @@ int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, c
     return launch_cn_poolln(h, p, -1, as_stream(stream));
 }
 
+int mpx_conv_rows(const mpx_engine* h, int i, int* rows_per_image) {
+    if (!h || !rows_per_image || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
+    *rows_per_image = h->convs[i].rows;
+    return 0;
+}
+
+int mpx_num_attn(const mpx_engine* h) { return h ? (int)h->attns.size() : MPX_E_ARG; }
+
+int mpx_attn_info(const mpx_engine* h, int k, mpx_attn_desc* out) {
+    if (!h || !out || k < 0 || k >= (int)h->attns.size()) return MPX_E_ARG;
+    *out = h->attns[k].d;
+    return 0;
+}
+
+int mpx_load_tokens(mpx_engine* h, const float* class_token, const float* pos_embedding) {
+    if (!h) return MPX_E_ARG;
+    if (!h->vit) return fail(h, MPX_E_STATE, "load_tokens: this architecture has no class token and no position embedding (a ViT engine has)");
+    if (!class_token || !pos_embedding) return fail(h, MPX_E_ARG, "load_tokens: class_token or encoder.pos_embedding missing");
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipMemcpy(h->cls_token, class_token, (size_t)h->vit_D * 4, hipMemcpyHostToDevice));
+    MPX_HIP(h, hipMemcpy(h->pos_emb, pos_embedding, (size_t)h->vit_T * h->vit_D * 4, hipMemcpyHostToDevice));
+    h->tokens_loaded = true;
+    return 0;
+}
+
+int mpx_token_params(const mpx_engine* h, const float** class_token, const float** pos_embedding, int* tokens, int* width) {
+    if (!h) return MPX_E_ARG;
+    if (class_token) *class_token = h->cls_token;
+    if (pos_embedding) *pos_embedding = h->pos_emb;
+    if (tokens) *tokens = h->vit_T;
+    if (width) *width = h->vit_D;
+    return 0;
+}
+
+int mpx_attention(mpx_engine* h, const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int T, int heads, int max_blocks,
+                  void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!qkv_hi || !qkv_lo || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "attention: null pointer");
+    if (T < 1 || T > AT_MAX_T) return fail(h, MPX_E_ARG, "attention: T = %d: a sequence has 1 .. %d tokens (one head's V^T must fit the LDS)", T, AT_MAX_T);
+    if (heads < 1 || heads > 64) return fail(h, MPX_E_ARG, "attention: heads = %d: the width is D = heads * 64 with 1 .. 64 heads (head_dim is 64)", heads);
+    if (B <= 0 || (long long)B * T > 0x7fffffffLL) return fail(h, MPX_E_ARG, "attention: B > 0 and B * T below 2^31");
+    if (misaligned(qkv_hi) || misaligned(qkv_lo) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "attention: every plane must be 16-byte aligned");
+    AttnParams p;
+    std::memset(&p, 0, sizeof p);
+    p.qkv_hi = (const half_t*)qkv_hi; p.qkv_lo = (const half_t*)qkv_lo; p.o_hi = (half_t*)out_hi; p.o_lo = (half_t*)out_lo;
+    p.T = T; p.heads = heads; p.D = heads * AT_HD;
+    MPX_SET_DEVICE(h);
+    return launch_attn(h, p, B, max_blocks, -1, as_stream(stream));
+}
+
+int mpx_tokens_assemble(mpx_engine* h, const void* patch_hi, const void* patch_lo, const float* class_token, const float* pos_embedding,
+                        void* out_hi, void* out_lo, int B, int T, int D, int max_blocks, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!h->vit) return fail(h, MPX_E_STATE, "tokens_assemble: this architecture has no token sequence (a ViT engine has)");
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!patch_hi || !patch_lo || !class_token || !pos_embedding || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "tokens_assemble: null pointer");
+    if (T < 1) return fail(h, MPX_E_ARG, "tokens_assemble: T = %d: a sequence has at least the class token", T);
+    if (B <= 0 || D <= 0 || (D & 7) || (long long)B * T > 0x7fffffffLL) return fail(h, MPX_E_ARG, "tokens_assemble: B > 0, D a positive multiple of 8, B * T below 2^31");
+    if (misaligned(patch_hi) || misaligned(patch_lo) || misaligned(class_token) || misaligned(pos_embedding) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "tokens_assemble: every pointer must be 16-byte aligned");
+    TokParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)patch_hi; p.x_lo = (const half_t*)patch_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.cls = class_token; p.pos = pos_embedding; p.T = T; p.D = D;
+    MPX_SET_DEVICE(h);
+    return launch_tokens(h, p, B, max_blocks, false, as_stream(stream));
+}
+
+int mpx_layernorm_rows(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
+                       void* out_lo, long long rows, long long in_stride, int C, int max_blocks, void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "layernorm_rows: null pointer");
+    if (rows <= 0 || in_stride < 1 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
+        return fail(h, MPX_E_ARG, "layernorm_rows: rows > 0, in_stride >= 1, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "layernorm_rows: every pointer must be 16-byte aligned");
+    CnLnRowsParams p;
+    std::memset(&p, 0, sizeof p);
+    p.ln.x_hi = (const half_t*)in_hi; p.ln.x_lo = (const half_t*)in_lo; p.ln.y_hi = (half_t*)out_hi; p.ln.y_lo = (half_t*)out_lo;
+    p.ln.gamma = ln_weight; p.ln.beta = ln_bias; p.ln.rows = rows; p.ln.C = C; p.ln.eps = eps;
+    p.in_stride = in_stride;
+    MPX_SET_DEVICE(h);
+    return launch_ln_rows(h, p, max_blocks, -1, as_stream(stream));
+}
+
 int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
     if (!h || !act || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;
     *act = h->convs[i].consumer_act;
@@ -3785,8 +4024,36 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 CnLnParams q;
                 std::memset(&q, 0, sizeof q);
                 q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                q.gamma = N.gamma; q.beta = N.beta; q.rows = (long long)B * o.hin * o.hin; q.C = o.c; q.eps = N.eps;
+                q.gamma = N.gamma; q.beta = N.beta; q.rows = h->vit ? (long long)B * o.hin : (long long)B * o.hin * o.hin; q.C = o.c; q.eps = N.eps;
                 rc = launch_cn_ln(h, q, 0, o.conv, as_stream(stream));
+                break;
+            }
+            case OP_LNORMROWS: {        // ViT: encoder.ln on the class-token row of each image (o.hin = T rows apart)
+                const LnLayer& N = h->lnorms[o.conv];
+                CnLnRowsParams q;
+                std::memset(&q, 0, sizeof q);
+                q.ln.x_hi = hi(o.in); q.ln.x_lo = lo(o.in); q.ln.y_hi = hi(o.out); q.ln.y_lo = lo(o.out);
+                q.ln.gamma = N.gamma; q.ln.beta = N.beta; q.ln.rows = B; q.ln.C = o.c; q.ln.eps = N.eps;
+                q.in_stride = o.hin;
+                rc = launch_ln_rows(h, q, 0, o.conv, as_stream(stream));
+                break;
+            }
+            case OP_TOKENS: {
+                TokParams q;
+                std::memset(&q, 0, sizeof q);
+                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
+                q.cls = h->cls_token; q.pos = h->pos_emb; q.T = o.hin; q.D = o.c;
+                rc = launch_tokens(h, q, B, 0, true, as_stream(stream));
+                break;
+            }
+            case OP_ATTN: {
+                const AttnLayer& A = h->attns[o.conv];
+                if (A.d.heads * A.d.head_dim != o.c) { rc = fail(h, MPX_E_INTERNAL, "attention: heads * 64 != D on %s", A.d.name); break; }
+                AttnParams q;
+                std::memset(&q, 0, sizeof q);
+                q.qkv_hi = hi(o.in); q.qkv_lo = lo(o.in); q.o_hi = hi(o.out); q.o_lo = lo(o.out);
+                q.T = A.d.tokens; q.heads = A.d.heads; q.D = o.c;
+                rc = launch_attn(h, q, B, 0, o.conv, as_stream(stream));
                 break;
             }
             case OP_AVGPOOLLN: {
@@ -4023,6 +4290,13 @@ int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launch
 int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms, double* per_lnorm_ms) {
+    return mpx_profile_collect_attn(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                    per_se_gate_ms, per_se_scale_ms, per_lnorm_ms, nullptr, nullptr);
+}
+
+int mpx_profile_collect_attn(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
+                             double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
+                             double* per_se_scale_ms, double* per_lnorm_ms, double* per_attn_ms, double* tokens_ms) {
     if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
     if (h->prof_used == 0) return 0;
     MPX_SET_DEVICE(h);
@@ -4047,6 +4321,9 @@ int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launch
             per_se_scale_ms[kProfSubSeScale - r.sub] += ms;
         if (per_lnorm_ms && r.kind == 2 && r.sub <= kProfSubLnorm && kProfSubLnorm - r.sub < (int)h->lnorms.size())
             per_lnorm_ms[kProfSubLnorm - r.sub] += ms;
+        if (per_attn_ms && r.kind == 2 && r.sub <= kProfSubAttn && kProfSubAttn - r.sub < (int)h->attns.size())
+            per_attn_ms[kProfSubAttn - r.sub] += ms;
+        if (tokens_ms && r.kind == 2 && r.sub == kProfSubTokens) *tokens_ms += ms;
     }
     h->prof_used = 0;
     return 0;
@@ -4065,7 +4342,8 @@ double mpx_flops_per_forward(const mpx_engine* h) {
     if (!h) return 0.0;
     double macs = 0.0;
     for (const ConvLayer& L : h->convs)
-        macs += (double)L.d.hout * L.d.hout * L.d.cout * (L.d.cin / L.groups) * L.d.ksize * L.d.ksize;
+        macs += (L.rows > 0 ? (double)L.rows : (double)L.d.hout * L.d.hout) * L.d.cout * (L.d.cin / L.groups) * L.d.ksize * L.d.ksize;
+    for (const AttnLayer& A : h->attns) macs += 2.0 * A.d.tokens * A.d.tokens * A.d.head_dim * A.d.heads;      // Q K^T and P V
     for (const DwLayer& D : h->dws) {
         const int ho = (D.d.hin - 1) / D.d.stride + 1;
         macs += (double)ho * ho * D.d.channels * D.ksize * D.ksize;

@@ -39,6 +39,19 @@ ARCH_IDS.update({"resnext50_32x4d": 11050, "resnext101_32x8d": 11101})    # torc
 ARCH_IDS["efficientnet_b0"] = 10000     # torchvision's EfficientNet-B0 (MPX_ARCH_EFFICIENTNET + 0); B1 .. B7 (trained at 240 and more) are not served
 ARCH_IDS.update({"convnext_tiny": 12001, "convnext_small": 12002})    # torchvision's ConvNeXts of width 96 (MPX_ARCH_CONVNEXT + 1 / 2); convnext_base / convnext_large are not served
 CONVNEXT_LN_EPS = 1e-6      # torchvision convnext.py: every LayerNorm / LayerNorm2d is built with eps=1e-6
+# torchvision's ViT-Base networks (MPX_ARCH_VIT + the patch size); vit_l_16 / vit_l_32 / vit_h_14 and the Swin family are not served.  The engine's
+# descriptor names drop the leading "encoder.layers." (mpx_conv_desc.name holds 48 characters, "encoder.layers.encoder_layer_11.self_attention.
+# out_proj" has 55): state_dict_name() puts it back, and in_proj's tensors are `...self_attention.in_proj_weight` / `in_proj_bias` (an
+# underscore: nn.MultiheadAttention's own parameters, not a submodule's)
+ARCH_IDS.update({"vit_b_16": 13016, "vit_b_32": 13032})
+VIT_LN_EPS = 1e-6           # torchvision vision_transformer.py: norm_layer = partial(nn.LayerNorm, eps=1e-6)
+VIT_LAYER_PREFIX = "encoder.layers."
+
+
+def state_dict_name(name):
+    """The state_dict prefix of a descriptor name: a ViT engine's "encoder_layer_<i>...." names get torchvision's "encoder.layers." back;
+    every other name is its own prefix."""
+    return VIT_LAYER_PREFIX + name if name.startswith("encoder_layer_") else name
 
 
 COMPUTE_UNITS = 256        # MI355X; only what whole_round_batch falls back to when no GPU is visible (CPU tests, documentation)
@@ -73,6 +86,8 @@ def default_bn_eps(arch):
     ConvNeXt has no BatchNorm: the value is its LayerNorms' 1e-6."""
     if arch.startswith("convnext"):
         return CONVNEXT_LN_EPS
+    if arch.startswith("vit_"):
+        return VIT_LN_EPS
     return GOOGLENET_BN_EPS if arch == "googlenet" else BN_EPS
 
 
@@ -143,6 +158,9 @@ class MaskedForwardEngine:
         A ConvNeXt-Tiny / -Small slot holds 15.3 MB -- three 56x56x384 split-fp16 activation buffers (block.3's output in stage 0,
         MobileNetV2's size: a block's input, its LayerNorm output and then its output, the hidden map: 14.5 MB) and the input staging -- and
         keeps the default of 512 (7.8 GB).
+        A ViT-B/16 slot holds 6.3 MB -- four split-fp16 activation buffers of sizes of their own (the residual stream and a LayerNorm's /
+        the attention's output, 197 x 768 each, in_proj's 197 x 2304 and the hidden 197 x 3072 rows: 5.45 MB) and the input staging --, a
+        ViT-B/32 slot 2.2 MB (50 tokens); both keep the default of 512 (3.6 / 1.5 GB with the packed weights).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -153,7 +171,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d and ConvNeXt-Tiny / -Small: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d, ConvNeXt-Tiny / -Small and ViT-B/16 / ViT-B/32: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -208,6 +226,16 @@ class MaskedForwardEngine:
             a = C.c_int()
             _lib.check(h, self._lib.mpx_conv_epilogue_act(h, i, C.byref(a)), "mpx_conv_epilogue_act")
             self.epilogue_acts.append(int(a.value))
+        self.conv_rows = []     # per conv layer: the rows per image of a ViT's token layers (197 / 50; their descriptors say hin = hout = 0), 0 everywhere else
+        for i in range(len(self.layers)):
+            r = C.c_int()
+            _lib.check(h, self._lib.mpx_conv_rows(h, i, C.byref(r)), "mpx_conv_rows")
+            self.conv_rows.append(int(r.value))
+        self.attns = []         # the attention launches (ViT: one per encoder layer), a list of their own
+        for k in range(self._lib.mpx_num_attn(h)):
+            ad = _lib.AttnDesc()
+            _lib.check(h, self._lib.mpx_attn_info(h, k, C.byref(ad)), "mpx_attn_info")
+            self.attns.append(ad)
         self.ses = []           # the Squeeze-and-Excitation layers (EfficientNet-B0), a list of their own as well
         for k in range(self._lib.mpx_num_se(h)):
             sd_ = _lib.SeDesc()
@@ -240,8 +268,9 @@ class MaskedForwardEngine:
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
         which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s,
-        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool) and the small networks stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext"))
+        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool), the ViTs (a 16x16 / 32x32 patchify stem) and the small networks
+        stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext", "vit_"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from
@@ -319,6 +348,17 @@ class MaskedForwardEngine:
             if only is not None and name not in only:
                 continue
             w4 = (d.cout, d.cin // self.groups[i], d.ksize, d.ksize)
+            if self.attns:
+                # a ViT: every layer is bias-only -- the ordinary epilogue with gamma 1, beta 0, mean 0, var 1, eps 0 (scale = 2^-e, shift =
+                # bias exactly, as ConvNeXt's block.5 carries its layer scale); in_proj's tensors have an underscore in their names
+                full = state_dict_name(name)
+                wkey, bkey = (full + "_weight", full + "_bias") if name.endswith(".in_proj") else (full + ".weight", full + ".bias")
+                w = get(wkey, w4 if d.ksize > 1 else (d.cout, d.cin)).reshape(w4).contiguous()
+                cb = get(bkey, (d.cout,))
+                zero, one = torch.zeros(d.cout), torch.ones(d.cout)
+                _lib.check(self._h, self._lib.mpx_set_conv_weights(self._h, i, _ptr(w), _ptr(cb), _ptr(one), _ptr(zero), _ptr(zero), _ptr(one), 0.0),
+                           "mpx_set_conv_weights(%s)" % name)
+                continue
             wshape = (d.cout, w4[1] * d.ksize * d.ksize) if (name + ".weight") in sd and sd[name + ".weight"].dim() == 2 else w4
             # a Linear layer as a conv: VGG's classifier.0 is [4096, 25088] = [4096, 512 * 7 * 7] (AlexNet's classifier.1 [4096, 256 * 6 * 6]), channel-major as torch.flatten of NCHW
             w = get(name + ".weight", wshape).reshape(w4).contiguous()
@@ -371,9 +411,14 @@ class MaskedForwardEngine:
                 t = [get("%s.%s" % (name, key), (nd.channels,)) for key in ("weight", "bias", "running_mean", "running_var")]
                 _lib.check(self._h, self._lib.mpx_load_norm(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_norm(%s)" % name)
             for k, ld in enumerate(self.lnorms):        # ... and so do ConvNeXt's stand-alone LayerNorms
-                name = ld.name.decode()
+                name = state_dict_name(ld.name.decode())
                 t = [get(name + ".weight", (ld.channels,)), get(name + ".bias", (ld.channels,))]
                 _lib.check(self._h, self._lib.mpx_load_lnorm(self._h, k, *[_ptr(v) for v in t], float(eps)), "mpx_load_lnorm(%s)" % name)
+            if self.attns:      # ... and a ViT's class token and position embedding
+                tk, wd = C.c_int(), C.c_int()
+                _lib.check(self._h, self._lib.mpx_token_params(self._h, None, None, C.byref(tk), C.byref(wd)), "mpx_token_params")
+                t = [get("class_token", (1, 1, wd.value)), get("encoder.pos_embedding", (1, tk.value, wd.value))]
+                _lib.check(self._h, self._lib.mpx_load_tokens(self._h, *[_ptr(v) for v in t]), "mpx_load_tokens")
         return self
 
     # ---- kernels ----
@@ -829,7 +874,8 @@ class MaskedForwardEngine:
         mpx_clip_pool_info) on a GoogLeNet engine, 'per_shuffle_ms' (one entry per channel shuffle, mpx_shuffle_info) on a ShuffleNetV2 engine,
         'per_se_gate_ms' / 'per_se_scale_ms' (one entry per SE layer: its gate and its scale launch) on an EfficientNet-B0 engine,
         'per_lnorm_ms' (one entry per stand-alone LayerNorm, mpx_lnorm_info; the depthwise + LayerNorm launches are per_dw_ms's) on a
-        ConvNeXt engine."""
+        ConvNeXt engine, 'per_attn_ms' (one entry per attention launch, mpx_attn_info) and 'tokens_ms' (the token assembly) on a ViT engine,
+        whose LayerNorms are per_lnorm_ms's."""
         ms = (C.c_double * 4)()
         n = (C.c_longlong * 4)()
         per = (C.c_double * len(self.layers))()
@@ -843,10 +889,13 @@ class MaskedForwardEngine:
         per_sg = (C.c_double * max(1, len(self.ses)))()
         per_ss = (C.c_double * max(1, len(self.ses)))()
         per_ln = (C.c_double * max(1, len(self.lnorms)))()
-        _lib.check(self._h, self._lib.mpx_profile_collect_ln(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh, per_sg, per_ss, per_ln), "mpx_profile_collect_ln")
+        per_at = (C.c_double * max(1, len(self.attns)))()
+        tok = (C.c_double * 1)()
+        _lib.check(self._h, self._lib.mpx_profile_collect_attn(self._h, ms, n, per, per_norm, avg2, per_dw, per_cp, per_sh, per_sg, per_ss, per_ln, per_at, tok),
+                   "mpx_profile_collect_attn")
         kinds = ("conv", "mask_apply_normalize", "pool", "head")
         return {"ms": dict(zip(kinds, list(ms))), "launches": dict(zip(kinds, list(n))),
                 "per_conv_ms": list(per), "per_norm_ms": list(per_norm)[:len(self.norms)], "avgpool2_ms": float(avg2[0]),
                 "per_dw_ms": list(per_dw)[:len(self.dwconvs)], "per_clip_pool_ms": list(per_cp)[:n_cp], "per_shuffle_ms": list(per_sh)[:n_sh],
                 "per_se_gate_ms": list(per_sg)[:len(self.ses)], "per_se_scale_ms": list(per_ss)[:len(self.ses)],
-                "per_lnorm_ms": list(per_ln)[:len(self.lnorms)]}
+                "per_lnorm_ms": list(per_ln)[:len(self.lnorms)], "per_attn_ms": list(per_at)[:len(self.attns)], "tokens_ms": float(tok[0])}

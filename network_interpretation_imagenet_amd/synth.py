@@ -507,6 +507,67 @@ def make_convnext_state_dict(arch, seed=7):
     return sd
 
 
+VIT_PATCH = {"vit_b_16": 16, "vit_b_32": 32}
+VIT_WIDTH, VIT_HEADS, VIT_MLP, VIT_LAYERS = 768, 12, 3072, 12
+# ViT's synthetic gains.  torchvision zero-initialises heads.head and draws the position embedding with std 0.02, which would switch both off;
+# trained networks have neither.  Every sub-block normalises its own input, so an update has a scale of its own and the residual stream can
+# only grow additively.  VIT_QK_GAIN is the standard deviation of a query / key channel behind ln_1: the attention logits q . k / 8 then
+# have a standard deviation of about VIT_QK_GAIN ^ 2, i.e. rows between near-uniform and a few dominant keys; VIT_POS_STD and the class token's
+# unit variance make both visible next to patch embeddings of about unit variance; VIT_FC1_GAIN / VIT_FC2_GAIN are ConvNeXt's (GELU
+# pre-activations over about +-3 times 1.5); VIT_HEAD_GAIN is the standard deviation of the logits (encoder.ln hands heads.head a unit-variance
+# row).  Surveyed on the CPU in fp64 on the rows tests/vit_ref.E2E_CASES scores; the figures stand in tests/test_vit_cpu.py's docstring,
+# which asserts the bounds on exactly those rows.
+VIT_QK_GAIN = 1.5
+VIT_POS_STD = 0.5
+VIT_OUT_GAIN = 1.0
+VIT_FC1_GAIN = 1.5
+VIT_FC2_GAIN = 0.5
+VIT_HEAD_GAIN = {"vit_b_16": 3.0, "vit_b_32": 2.5}      # vit_b_32 at 3.0: the unmasked grid picture's softmax peak is 0.952
+
+
+def make_vit_state_dict(arch, seed=7):
+    """OrderedDict with the key set, order and shapes of models.vit_b_16() / vit_b_32().state_dict(): class_token [1][1][768], conv_proj.{weight,
+    bias} (Conv2d(3, 768, p, p)), encoder.pos_embedding [1][T][768], per layer encoder.layers.encoder_layer_i.ln_1.{weight, bias},
+    .self_attention.in_proj_weight [2304][768] / in_proj_bias, .self_attention.out_proj.{weight, bias}, .ln_2.{weight, bias}, .mlp.0.{weight,
+    bias} ([3072][768]), .mlp.3.{weight, bias} ([768][3072]), then encoder.ln.{weight, bias} and heads.head.{weight, bias}: 86,567,656 /
+    88,224,232 parameters.  Draws: conv_proj N(0, sqrt(1 / fan_in)) with bias N(0, 0.1); class_token N(0, 1); pos_embedding N(0, VIT_POS_STD);
+    LayerNorm weight U(0.9, 1.1), bias N(0, 0.1); in_proj N(0, g / sqrt(768)) with g = VIT_QK_GAIN on the query and key rows and 1 on the
+    value rows, bias N(0, 0.1); out_proj N(0, VIT_OUT_GAIN / sqrt(768)) with bias N(0, 0.05); mlp.0 N(0, VIT_FC1_GAIN / sqrt(768)) with bias
+    N(0, 0.2); mlp.3 N(0, VIT_FC2_GAIN / sqrt(3072)) with bias N(0, 0.05); heads.head N(0, VIT_HEAD_GAIN[arch] / sqrt(768)) with bias N(0, 0.1)."""
+    p = VIT_PATCH[arch]
+    t = (224 // p) ** 2 + 1
+    d = VIT_WIDTH
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+
+    def ln(name):
+        sd[name + ".weight"] = 0.9 + 0.2 * torch.rand(d, generator=g)
+        sd[name + ".bias"] = torch.randn(d, generator=g) * 0.1
+
+    sd["class_token"] = torch.randn(1, 1, d, generator=g)
+    sd["conv_proj.weight"] = torch.randn(d, 3, p, p, generator=g) * (1.0 / (3 * p * p)) ** 0.5
+    sd["conv_proj.bias"] = torch.randn(d, generator=g) * 0.1
+    sd["encoder.pos_embedding"] = torch.randn(1, t, d, generator=g) * VIT_POS_STD
+    for i in range(VIT_LAYERS):
+        q = "encoder.layers.encoder_layer_%d." % i
+        ln(q + "ln_1")
+        w = torch.randn(3 * d, d, generator=g) / d ** 0.5
+        w[:2 * d] *= VIT_QK_GAIN
+        sd[q + "self_attention.in_proj_weight"] = w
+        sd[q + "self_attention.in_proj_bias"] = torch.randn(3 * d, generator=g) * 0.1
+        sd[q + "self_attention.out_proj.weight"] = torch.randn(d, d, generator=g) * (VIT_OUT_GAIN / d ** 0.5)
+        sd[q + "self_attention.out_proj.bias"] = torch.randn(d, generator=g) * 0.05
+        ln(q + "ln_2")
+        sd[q + "mlp.0.weight"] = torch.randn(VIT_MLP, d, generator=g) * (VIT_FC1_GAIN / d ** 0.5)
+        sd[q + "mlp.0.bias"] = torch.randn(VIT_MLP, generator=g) * 0.2
+        sd[q + "mlp.3.weight"] = torch.randn(d, VIT_MLP, generator=g) * (VIT_FC2_GAIN / VIT_MLP ** 0.5)
+        sd[q + "mlp.3.bias"] = torch.randn(d, generator=g) * 0.05
+    ln("encoder.ln")
+    sd["heads.head.weight"] = torch.randn(1000, d, generator=g) * (VIT_HEAD_GAIN[arch] / d ** 0.5)
+    sd["heads.head.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_resnext_state_dict(arch, seed=7):
     """OrderedDict with the key set and shapes of models.resnext50_32x4d() / resnext101_32x8d(): the ResNets' names, conv1 [width][cin][1][1],
     conv2 [width][width / 32][3][3] (32 groups), conv3 [4 * planes][width][1][1].  Conv gains come from the fan-in (9 * cg for conv2); the
@@ -540,11 +601,13 @@ def make_resnext_state_dict(arch, seed=7):
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict, ConvNeXt: make_convnext_state_dict, ViT: make_vit_state_dict) key set."""
     if arch == "efficientnet_b0":
         return make_efficientnet_state_dict(seed)
     if arch in CONVNEXT_DEPTHS:
         return make_convnext_state_dict(arch, seed)
+    if arch in VIT_PATCH:
+        return make_vit_state_dict(arch, seed)
     if arch in RESNEXT_ARCHS:
         return make_resnext_state_dict(arch, seed)
     if arch in SHUFFLENET_WIDTHS:

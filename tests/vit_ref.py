@@ -1,0 +1,175 @@
+"""CPU restatement of torchvision's vit_b_16 / vit_b_32 forward (test infrastructure only; oracle/ stays ResNet-only).
+
+torchvision vision_transformer.py in eval mode with dropout 0: conv_proj = Conv2d(3, 768, p, stride p, bias), the patches flattened row-major
+into T - 1 tokens, the class token in front, + encoder.pos_embedding, 12 EncoderBlocks -- x = x + out_proj(attention(in_proj(ln_1(x)))), x = x
++ mlp.3(gelu(mlp.0(ln_2(x)))) with 12 heads of 64 and the exact (erf) GELU --, encoder.ln, heads.head on the class-token row.  Every LayerNorm
+has eps 1e-6.  Written with torch.nn.functional on the state_dict, in whatever dtype the tensors have (fp64 for yardsticks), plus the
+reference-style batch-1 fp32 scoring loop of oracle.scorer with this forward in place of the ResNet one.  Three switches show that the new
+arithmetic is live on the rows the tests score: `uniform_attention=True` replaces every row of softmax weights by 1 / T, `pos=False` leaves
+the position embedding out, `class_token=False` puts zeros in the class token's place.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from oracle.scorer import apply_mask, onoff_mask_u8
+
+ARCHS = ("vit_b_16", "vit_b_32")
+PATCH = {"vit_b_16": 16, "vit_b_32": 32}
+TOKENS = {"vit_b_16": 197, "vit_b_32": 50}
+LAYERS, WIDTH, HEADS, MLP = 12, 768, 12, 3072
+EPS = 1e-6
+PARAMS = {"vit_b_16": 86567656, "vit_b_32": 88224232}
+MACS = {"vit_b_16": 17563828224, "vit_b_32": 4409186304}
+PREFIX = "encoder.layers."
+
+# The rows the end-to-end checks score: (label map, number of mask rows, seed of synth.random_onoff)
+E2E_CASES = (("felz", 3, 8), ("grid", 2, 1))
+
+
+def cast(sd, dtype):
+    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def arch_of(sd):
+    return "vit_b_32" if sd["conv_proj.weight"].shape[-1] == 32 else "vit_b_16"
+
+
+def topology(arch):
+    """The network's launches in forward order, under the engine's descriptor names (no leading "encoder.layers.").  convs: (name, cin, cout,
+    ksize, rows per image the layer runs on, token layer?, residual, epilogue act); lnorms: names; attns: (name, T, heads, head_dim)."""
+    p, t = PATCH[arch], TOKENS[arch]
+    convs = [("conv_proj", 3, WIDTH, p, t - 1, False, 0, 0)]
+    lnorms, attns = [], []
+    for i in range(LAYERS):
+        q = "encoder_layer_%d." % i
+        lnorms += [q + "ln_1", q + "ln_2"]
+        convs.append((q + "self_attention.in_proj", WIDTH, 3 * WIDTH, 1, t, True, 0, 0))
+        attns.append((q + "self_attention", t, HEADS, WIDTH // HEADS))
+        convs.append((q + "self_attention.out_proj", WIDTH, WIDTH, 1, t, True, 1, 0))
+        convs.append((q + "mlp.0", WIDTH, MLP, 1, t, True, 0, 1))
+        convs.append((q + "mlp.3", MLP, WIDTH, 1, t, True, 1, 0))
+    lnorms.append("encoder.ln")
+    convs.append(("heads.head", WIDTH, 1000, 1, 1, False, 0, 0))
+    return convs, lnorms, attns
+
+
+def macs(arch):
+    """Multiply-accumulates of one forward: the patch embedding, every Linear on its rows, and the attention products Q K^T and P V (2 * T^2 *
+    64 per head); LayerNorm, softmax, GELU and the adds are not MACs."""
+    convs, _ln, attns = topology(arch)
+    return sum(c[4] * c[2] * c[1] * c[3] * c[3] for c in convs) + sum(2 * t * t * hd * h for _n, t, h, hd in attns)
+
+
+def attention(q, k, v, uniform=False):
+    """softmax(q k^T / sqrt(head_dim)) v per head; q, k, v: [N, T, heads * 64]."""
+    n, t, d = q.shape
+    hd = d // HEADS
+    q, k, v = (z.reshape(n, t, HEADS, hd).permute(0, 2, 1, 3) for z in (q, k, v))
+    w = F.softmax(q @ k.transpose(-1, -2) * (1.0 / hd ** 0.5), -1)
+    if uniform:
+        w = torch.full_like(w, 1.0 / t)
+    return (w @ v).permute(0, 2, 1, 3).reshape(n, t, d)
+
+
+def tokens(sd, x, pos=True, class_token=True):
+    """[N, T, 768]: the patch embedding with the class token in front, plus the position embedding."""
+    p = sd["conv_proj.weight"].shape[-1]
+    x = F.conv2d(x, sd["conv_proj.weight"], sd["conv_proj.bias"], p).flatten(2).transpose(1, 2)
+    cls = sd["class_token"] if class_token else torch.zeros_like(sd["class_token"])
+    x = torch.cat([cls.expand(x.shape[0], -1, -1), x], 1)
+    return x + sd["encoder.pos_embedding"] if pos else x
+
+
+def forward(sd, x, trace=None, uniform_attention=False, pos=True, class_token=True):
+    """logits [N, 1000] of torchvision's vit_b_16 / vit_b_32 for the normalised NCHW batch x.  `trace` (a list) receives (name, tensor): the
+    assembled tokens, per layer the attention logits' input ("<layer>.qkv"), the residual stream behind the attention and behind the MLP
+    ("<layer>.attn", "<layer>"), the GELU pre-activation ("<layer>.pre")."""
+    def note(name, t):
+        if trace is not None:
+            trace.append((name, t))
+        return t
+
+    x = note("tokens", tokens(sd, x, pos, class_token))
+    for i in range(LAYERS):
+        p = PREFIX + "encoder_layer_%d." % i
+        y = F.layer_norm(x, (WIDTH,), sd[p + "ln_1.weight"], sd[p + "ln_1.bias"], EPS)
+        qkv = note(p + "qkv", F.linear(y, sd[p + "self_attention.in_proj_weight"], sd[p + "self_attention.in_proj_bias"]))
+        y = attention(*qkv.split(WIDTH, -1), uniform=uniform_attention)
+        x = note(p + "attn", x + F.linear(y, sd[p + "self_attention.out_proj.weight"], sd[p + "self_attention.out_proj.bias"]))
+        y = F.layer_norm(x, (WIDTH,), sd[p + "ln_2.weight"], sd[p + "ln_2.bias"], EPS)
+        y = F.gelu(note(p + "pre", F.linear(y, sd[p + "mlp.0.weight"], sd[p + "mlp.0.bias"])))
+        x = note(p[:-1], x + F.linear(y, sd[p + "mlp.3.weight"], sd[p + "mlp.3.bias"]))
+    x = F.layer_norm(x[:, 0], (WIDTH,), sd["encoder.ln.weight"], sd["encoder.ln.bias"], EPS)
+    return F.linear(x, sd["heads.head.weight"], sd["heads.head.bias"])
+
+
+def masked_batch(x_chw, segments, onoff):
+    """f32[M, 3, 224, 224]: the masked images of the rows of `onoff`, as oracle.scorer stages them."""
+    return torch.from_numpy(np.stack([apply_mask(x_chw, onoff_mask_u8(segments, row)) for row in onoff]))
+
+
+def score_masks_reference_loop(sd, x_chw, segments, onoff, label, return_logits=False):
+    """oracle.scorer.score_masks_reference_loop with the ViT forward: one batch-1 fp32 forward per mask-vector.
+    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set."""
+    sd = cast(sd, torch.float32)
+    m = onoff.shape[0]
+    score = np.zeros(m, dtype=np.float32)
+    pred = np.zeros(m, dtype=np.int64)
+    rows = []
+    for i in range(m):
+        masked = apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
+        with torch.no_grad():
+            logits = forward(sd, torch.from_numpy(masked[None]))
+            prob = F.softmax(logits, dim=1)
+        score[i], pred[i] = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
+        rows.append(logits.numpy()[0])
+    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
+
+
+def score_masks_fp64(sd, x_chw, segments, onoff, label, **switches):
+    """The yardstick: the same masks through the fp64 forward.  returns (score f64[M], logits f64[M, 1000])."""
+    sd = cast(sd, torch.float64)
+    with torch.no_grad():
+        logits = forward(sd, masked_batch(x_chw, segments, onoff).double(), None, **switches)
+        prob = F.softmax(logits, dim=1)
+    return prob[:, label].numpy(), logits.numpy()
+
+
+def e2e_inputs(golden_dir, kind):
+    """(image u8[224,224,3], label map) of an end-to-end case: the felzenszwalb fixture on the `blobs` image, or the 16-pixel grid."""
+    import os
+    from network_interpretation_imagenet_amd import synth
+    if kind == "felz":
+        g = np.load(os.path.join(golden_dir, "felzenszwalb_skimage0183.npz"))
+        return g["blobs224/image"], g["blobs224/labels"].astype(np.int64)
+    return synth.make_images(1)[0], synth.grid_segments().astype(np.int64)
+
+
+SWITCHES = (("uniform_attention=True", dict(uniform_attention=True)), ("pos=False", dict(pos=False)), ("class_token=False", dict(class_token=False)))
+_ROWS = {}
+
+
+def e2e_rows(golden_dir, arch):
+    """The fp64 yardstick of the scored rows, computed once per network and process and shared by the tests that need it: per case (image,
+    label map, onoff, label, unmasked softmax, trace, fp64 scores, fp64 logits, the scores under each of the three switches)."""
+    from network_interpretation_imagenet_amd import synth
+    from oracle import scorer
+    if arch not in _ROWS:
+        sd = synth.make_state_dict(arch)
+        sd64 = cast(sd, torch.float64)
+        out = {}
+        for kind, m, seed in E2E_CASES:
+            img, seg = e2e_inputs(golden_dir, kind)
+            x = scorer.to_tensor_normalize(img)
+            trace = []
+            with torch.no_grad():
+                logits = forward(sd64, torch.as_tensor(x)[None].double(), trace)
+            p = F.softmax(logits, 1)[0]
+            label = int(p.argmax())
+            onoff = synth.random_onoff(m, len(np.unique(seg)), seed=seed)
+            s64, logits64 = score_masks_fp64(sd, x, seg, onoff, label)
+            moved = {name: score_masks_fp64(sd, x, seg, onoff, label, **sw)[0] for name, sw in SWITCHES}
+            out[kind] = dict(img=img, seg=seg, x=x, onoff=onoff, label=label, p=p, trace=trace, s64=s64, logits64=logits64, moved=moved)
+        _ROWS[arch] = out
+    return _ROWS[arch]

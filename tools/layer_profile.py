@@ -3,7 +3,9 @@
 usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d add the
                                                                  grouped 3x3 launches as rows of their own, with their bytes and TB/s;
                                                                  convnext_tiny / convnext_small the depthwise 7x7 + LayerNorm launches and the
-                                                                 stand-alone LayerNorms, with bytes, TB/s and the shares by op class)
+                                                                 stand-alone LayerNorms, with bytes, TB/s and the shares by op class;
+                                                                 vit_b_16 / vit_b_32 the attention, token assembly and LayerNorm launches
+                                                                 with bytes, TB/s and the attention's MFMA TFLOP/s against its two floors)
        MPX_PER_LAYER=1 ...    one row per conv with its tile
 A conv + downsample conv that run as ONE launch (K-concatenated) are booked on the main conv; they get rows of their own, with both convs'
 FLOPs, under the grouped table (the grouped rows count the main conv's FLOPs only).
@@ -115,7 +117,8 @@ ptail_next = {n1: c3 for c3, n1 in ptail_of.items()}
 def conv_flops(li):
     """FLOPs of conv layer `li` over the batch; a grouped layer (eng.groups: 32 on a ResNeXt block's conv2) reads cin / groups channels."""
     d = eng.layers[li]
-    return 2.0 * batch * d.hout * d.hout * d.cout * (d.cin // eng.groups[li]) * d.ksize * d.ksize
+    rows = eng.conv_rows[li] or d.hout * d.hout         # a ViT's token layers run on T rows per image that are no square map (hout = 0)
+    return 2.0 * batch * rows * d.cout * (d.cin // eng.groups[li]) * d.ksize * d.ksize
 
 
 print("%-26s %5s %5s %2s %2s %4s %9s %9s %8s" % ("layer", "cin", "cout", "k", "s", "hout", "ms", "GFLOP", "TFLOP/s"))
@@ -205,7 +208,40 @@ if eng.norms:     # DenseNet: the ops between the convs -- concat-append + BN + 
     print("concat-append + BN + ReLU total %.3f ms/batch, %.1f MB -> %.2f TB/s; transitions' 2x2 average pools %.3f ms/batch; conv total %.3f ms/batch"
           % (tot_norm, tot_bytes / 1e6, tot_bytes / max(tot_norm, 1e-9) / 1e9, prof["avgpool2_ms"] / reps, tot))
 shuffle_net = arch.startswith("shufflenet")
-if eng.lnorms:  # ConvNeXt: the depthwise 7x7 + LayerNorm launches and the stand-alone LayerNorms between the MFMA convs
+if eng.attns:   # ViT: the attention launches, the token assembly and the LayerNorms between the MFMA convs
+    t, width = eng.attns[0].tokens, eng.attns[0].heads * eng.attns[0].head_dim
+    print("-- attention (mpx_attention: one launch per encoder layer); bytes = the QKV planes read once + the output planes written once; FLOPs = Q K^T and P V --")
+    tot_at = sum(prof["per_attn_ms"]) / reps
+    at_bytes = batch * 4.0 * t * (3 * width + width)
+    at_fl = 2.0 * batch * 2 * t * t * width
+    for ad, ms in zip(eng.attns, prof["per_attn_ms"]):
+        ms /= reps
+        if os.environ.get("MPX_PER_LAYER"):
+            print("%-34s T %3d heads %2d %9.3f ms %8.1f MB %7.2f TB/s %8.1f GFLOP %7.1f TFLOP/s" % (ad.name.decode(), ad.tokens, ad.heads, ms, at_bytes / 1e6,
+                                                                                             at_bytes / max(ms, 1e-9) / 1e9, at_fl / 1e9, at_fl / max(ms, 1e-9) / 1e9))
+    n_at = len(eng.attns)
+    print("attention T %3d heads %2d x%-2d %9.3f ms %8.1f MB %7.2f TB/s %8.1f GFLOP %7.1f TFLOP/s (MFMA work as issued: 1.5 x -- Q K^T runs twice)"
+          % (t, eng.attns[0].heads, n_at, tot_at, n_at * at_bytes / 1e6, n_at * at_bytes / max(tot_at, 1e-9) / 1e9, n_at * at_fl / 1e9, n_at * at_fl / max(tot_at, 1e-9) / 1e9))
+    tok_ms = prof["tokens_ms"] / reps
+    tok_bytes = batch * 4.0 * width * (2 * t - 1)
+    print("token assembly                    %9.3f ms %8.1f MB %7.2f TB/s" % (tok_ms, tok_bytes / 1e6, tok_bytes / max(tok_ms, 1e-9) / 1e9))
+    ln_ms = sum(prof["per_lnorm_ms"][:-1]) / reps
+    ln_bytes = (len(eng.lnorms) - 1) * batch * 4.0 * width * 2 * t
+    cls_ms = prof["per_lnorm_ms"][-1] / reps
+    print("LayerNorm on B x T rows       x%-2d %9.3f ms %8.1f MB %7.2f TB/s; encoder.ln on the class rows %.3f ms" % (len(eng.lnorms) - 1, ln_ms, ln_bytes / 1e6, ln_bytes / max(ln_ms, 1e-9) / 1e9, cls_ms))
+    gelu_ms = sum(ms for a, ms in zip(eng.epilogue_acts, prof["per_conv_ms"]) if a) / reps
+    gelu_fl = sum(conv_flops(li) for li, a in enumerate(eng.epilogue_acts) if a)
+    allms = sum(prof["ms"].values()) / reps
+    ln_rate = ln_bytes / max(ln_ms, 1e-9) / 1e9          # TB/s the LayerNorm kernel reaches here
+    conv_rate = sum(conv_flops(li) for li in range(len(eng.layers))) / max(tot, 1e-9) / 1e9     # TFLOP/s the conv kernels reach here
+    print("attention against its floors, per launch: %.3f ms measured; %.3f ms for its planes at the LayerNorm kernel's %.2f TB/s; %.3f ms for its MFMA work at the conv kernels' %.1f TFLOP/s"
+          % (tot_at / n_at, at_bytes / 1e9 / max(ln_rate, 1e-9), ln_rate, at_fl / 1e9 / max(conv_rate, 1e-9), conv_rate))
+    print("share of the forward by op class: conv (MFMA) %.1f %% (of which the GELU convs mlp.0, tile %s, %.1f %% of the forward at %.1f TFLOP/s), attention (%d launches) %.1f %%, "
+          "LayerNorms (%d) %.1f %%, token assembly %.1f %%, staging (K0) %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
+          % (100 * tot / allms, sorted({eng.conv_tile(li) for li, a in enumerate(eng.epilogue_acts) if a}), 100 * gelu_ms / allms, gelu_fl / max(gelu_ms, 1e-9) / 1e9, n_at,
+             100 * tot_at / allms, len(eng.lnorms), 100 * (ln_ms + cls_ms) / allms, 100 * tok_ms / allms, 100 * prof["ms"]["mask_apply_normalize"] / reps / allms,
+             100 * prof["ms"]["head"] / reps / allms, allms, sum(prof["launches"].values()) // reps - 1))
+elif eng.lnorms:  # ConvNeXt: the depthwise 7x7 + LayerNorm launches and the stand-alone LayerNorms between the MFMA convs
     print("-- depthwise 7x7 + bias + LayerNorm over C (mpx_dwconv7x7_ln: one launch per block); bytes = split-fp16 planes read once + written once: the launch's floor --")
     tot_dw = dw_bytes = tot_ln = ln_bytes = 0.0
     by_map = {}

@@ -11,7 +11,9 @@
 // staged input: K0's 846 KB per masked image are neither written nor read, and the 118 MMAC of the stem conv per mask become ~20 adds
 // per pooled pixel and channel.  Arithmetic: the table entries are fp32 FMA chains over the taps in raster order (the reference's own
 // arithmetic type), the mask sum adds them in the order of first occurrence of their label in the window; the result differs from the
-// MFMA stem (22-bit operands, another summation order) by rounding only.
+// MFMA stem (22-bit operands, another summation order) by rounding only.  Per conv pixel v = v + R over the kept entries in entry order,
+// y = max(fma(v, s, t), 0), the pool over the conv pixels inside the map, split_f32 with a -0 residual stored as +0 (stem_split_packed):
+// tests/stemtab_draws.py restates exactly this on the CPU and tests/test_gpu_stem_table_edges.py holds both planes to it bit for bit.
 //
 // Table layout (CSR over the 112 x 112 conv output pixels, row-major): off[q] .. off[q+1] index the entries of pixel q;
 // lab[e] = superpixel rank of entry e, vec[e][64] = its 64 output channels (pre-BatchNorm).  Labels outside [0, S) and taps in the zero
@@ -192,12 +194,19 @@ __device__ __forceinline__ void stem_store4_packed(const StemApplyParams& p, uns
     }
 }
 
-__device__ __forceinline__ void stem_store4(const StemApplyParams& p, unsigned (*s_out)[4][4][ST_C], int m, int mcount, int wave, int lane,
-                                            float best, size_t out0_row) {
+// The pooled value as the two planes' bits, hi | lo << 16.  split_f32's lo is -0 where v - hi is negative and rounds to zero in fp16 (a residual
+// of -2^-25 or less in magnitude: v < 0.5 whose low fp32 bits lie just under a value of hi's grid; 2 in 10^5 to 3 in 10^3 elements).  The planes
+// store +0 there: best is never negative, so neither plane ever carries the bits 0x8000, and a -0 in them can only be a mistake.
+__device__ __forceinline__ unsigned stem_split_packed(float best) {
     half_t hi, lo;
     split_f32(best, hi, lo);
-    stem_store4_packed(p, s_out, m, mcount, wave, lane,
-                       (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16), out0_row);
+    const unsigned lob = __builtin_bit_cast(unsigned short, lo);
+    return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((lob == 0x8000u ? 0u : lob) << 16);
+}
+
+__device__ __forceinline__ void stem_store4(const StemApplyParams& p, unsigned (*s_out)[4][4][ST_C], int m, int mcount, int wave, int lane,
+                                            float best, size_t out0_row) {
+    stem_store4_packed(p, s_out, m, mcount, wave, lane, stem_split_packed(best), out0_row);
 }
 
 // One wave = one pooled pixel x one block of 32 masks; lane = channel.  The entries of the (up to) 3 x 3 conv pixels under the pooled
@@ -445,11 +454,10 @@ __global__ __launch_bounds__(256) void stem_apply_heavy_kernel(const StemApplyPa
     for (int k = 0; k < SA_MG; ++k) {
         if (k < mcount) {
             const float b = g.n_e > 0 ? fmaxf(best[k], fmaxf(fmaf(v[k], sc, sh), 0.f)) : best[k];
-            half_t hi, lo;
-            split_f32(b, hi, lo);
+            const unsigned packed = stem_split_packed(b);
             const size_t o = out0 + (size_t)k * ST_POOLED * ST_POOLED * ST_C;
-            p.out_hi[o] = hi;
-            p.out_lo[o] = lo;
+            p.out_hi[o] = __builtin_bit_cast(half_t, (unsigned short)(packed & 0xffffu));
+            p.out_lo[o] = __builtin_bit_cast(half_t, (unsigned short)(packed >> 16));
         }
     }
     __builtin_amdgcn_wave_barrier();            // the next pixel's first chunk overwrites this wave's factors

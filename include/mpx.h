@@ -242,6 +242,27 @@ enum {
  * output, the attention's), QKV (T * 2304: in_proj's output and then, dead behind the attention, out_proj's) and H (T * 3072): 5.45 MB / 1.38 MB
  * plus the staging (0.85 MB): 6.3 / 2.2 MB per slot.  It stages through mpx_mask_apply_normalize only: the stem-table and stem + pool entry
  * points return MPX_E_STATE.
+ * -- or one of torchvision's five RegNetX networks up to 8 GF, whose bottleneck's 3x3 is grouped by a fixed GROUP WIDTH, so that the group count
+ * is whatever the stage width gives (5,495,976 / 7,259,656 / 9,190,136 / 15,296,552 / 39,572,648 parameters, 413,812,608 / 799,699,712 /
+ * 1,602,849,792 / 3,176,621,952 / 7,995,132,416 MAC per forward):
+ *   MPX_ARCH_REGNET + 4 / 8 / 16 / 32 / 80   regnet_x_400mf / _800mf / _1_6gf / _3_2gf / _8gf (ten times the GF figure); every other id in
+ *                                            [14000, 15000) is MPX_E_ARG (regnet_x_16gf / _32gf and the RegNetY family included)
+ *   stage widths (32, 64, 160, 400) (64, 128, 288, 672) (72, 168, 408, 912) (96, 192, 432, 1008) (80, 240, 720, 1920), depths (1, 2, 7, 12)
+ *   (1, 3, 7, 5) (2, 4, 10, 2) (2, 6, 15, 2) (2, 5, 15, 1), group width 16, 16, 24, 48, 120 -- groups (2, 4, 10, 25) (4, 8, 18, 42) (3, 7, 17, 38)
+ *   (2, 4, 9, 21) (1, 2, 6, 16); 72 / 54 / 60 / 81 / 75 entries in the conv list.
+ * A RegNetX engine runs stem.0 (3 -> 32, 3x3 stride 2 pad 1, BatchNorm stem.1, ReLU: MobileNetV2's features.0.0 shape, k_packed = 96, no max
+ * pool) and four stages trunk_output.block{s}.block{s}-{j} of bottlenecks of ratio 1: f.a.0 (1x1 w_in -> w, BN f.a.1, ReLU, at the input
+ * resolution), f.b.0 (3x3 w -> w pad 1 in w / gw groups, stride 2 in block 0 of EVERY stage, BN f.b.1, ReLU), f.c.0 (1x1 w -> w, BN f.c.1,
+ * residual = 1: ReLU(shortcut + f.c)), with proj.0 (1x1 stride 2, BN proj.1, no activation) as the shortcut in block 0 -- a launch of its
+ * own, listed in front of f.a.0 as in torchvision's state_dict -- and the identity elsewhere; then the global average pool, fc and the head.
+ * f.b IS THE GROUPED LAYER: mpx_conv_groups reports w / gw on it (1 on the dense 80 -> 80 3x3 of regnet_x_8gf's first stage, an ordinary
+ * entry on the ordinary kernels), its weight tensor is torchvision's [w][gw][3][3], and it runs tile 18 (csrc/mpx_gconvw.h).  Its descriptor
+ * has cin = cout = w, k_packed = 9 * gw rounded up to 32 (160, 224, 448, 1088) and cout_pad = groups * ceil(gw / 16) * 16, the rows of its packed
+ * planes; mpx_pack_conv_weights does not serve it.
+ * Widths that are no multiple of 32 (72, 80, 168, 240, 400, 408, 432, 720, 912, 1008) are stored with a pitch of the next multiple of 32
+ * (exact zeros in the padded channels, as MobileNetV2: the grouped kernel writes them itself); such dense layers run the generic tiles only.
+ * Four activation buffers of the network's largest map (112 * 112 * 32 / 64 / 96 / 96 / 96 elements per image) plus the staging.  It stages
+ * through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -259,6 +280,7 @@ enum {
 #define MPX_ARCH_RESNEXT 11000
 #define MPX_ARCH_CONVNEXT 12000
 #define MPX_ARCH_VIT 13000
+#define MPX_ARCH_REGNET 14000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -309,7 +331,8 @@ int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
  * (l < bf) or hp + l - bf; 0, 0 for every other layer.  Any pointer may be NULL. */
 int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp);
 /* Groups of layer i: 32 on the conv2 of a ResNeXt engine's blocks (cin / 32 input channels per output channel: mpx_set_conv_weights takes
- * [cout][cin / 32][3][3] there, and the layer runs tile 16 and nothing else), 1 on every other layer of every engine. */
+ * [cout][cin / 32][3][3] there, and the layer runs tile 16 and nothing else), w / gw = 2 .. 42 on the f.b of a RegNetX engine's blocks
+ * ([w][gw][3][3]; tile 18, and tile 16 where the shape is one of that kernel's), 1 on every other layer of every engine. */
 int mpx_conv_groups(const mpx_engine* h, int i, int* groups);
 /* The activation torchvision puts behind layer i that the layer itself does NOT apply because its one consumer takes it on load: *act = 0
  * none (every layer of every other network; ReLU6's clamp is reported by mpx_dwconv_desc.clamp_in), 1 SiLU (an EfficientNet-B0 engine's stem,
@@ -452,6 +475,10 @@ int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
  *  16 = the grouped 3x3 kernel (csrc/mpx_gconv.h): one wave per 16 output pixels x channel block of max(cg, 16) channels, operands straight
  *       from global memory (the conv2 of a ResNeXt block: its only tile, and the tile of nothing else; ids 15 and 17 are unassigned).
+ *  18 = the grouped 3x3 kernel for any group count, group widths 16 / 24 / 48 / 120 and planes at a pitch >= the width (csrc/mpx_gconvw.h): one
+ *       wave per 32 output pixels x group x chunk of at most four 16-row fragments; it writes the output's pad channels as +0 itself (the
+ *       f.b of a RegNetX block: its default; such a layer with 16 channels per group, a width that is a multiple of 64 and pitch = width also
+ *       accepts tile 16, which gives the same bits.  Every layer that is not such a grouped layer is refused).
  * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default (a DenseNet's conv2, 3x3 128 -> 32,
  * defaults to 6, its topology's own choice: the cout <= 64 rule above was judged on 64 -> 64 layers and would give it 1).  (Ids 3, 5, 8 and 11 of
  * earlier rounds -- kernels that were measured and never became a default -- were removed; commit e4ccec8 is the last that has

@@ -16,6 +16,7 @@
 #include "mpx_shuffle.h"
 #include "mpx_mbconv.h"
 #include "mpx_gconv.h"
+#include "mpx_gconvw.h"
 #include "mpx_cnext.h"
 #include "mpx_attn.h"
 
@@ -88,6 +89,9 @@ struct ConvLayer {
     int in_hp = 0;
     int groups = 1;         // > 1: a grouped 3x3 layer (a ResNeXt conv2: cin = cout = the width, cin / groups channels per group), whose packed planes
                             // are mpx_gconv.h's -- cout_pad = cout rows of k_packed = gconv_kp(max(cin / groups, 16)), the K of ONE channel block
+    bool gw = false;        // a grouped layer in mpx_gconvw.h's form (a RegNetX f.b: any group count, cin / groups = 16, 24, 48 or 120, planes at a
+                            // pitch of cin_pad / cout_store >= the width): packed planes [groups][ceil(cg / 16)][k_packed / 32][64][8], i.e.
+                            // cout_pad = groups * ceil(cg / 16) * 16 rows of k_packed = gconvw_kp(cg).  Runs tile 18, and tile 16 where that accepts it
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
     int tile_default = -1;  // the layer's default where the topology sets one of its own (DenseNet's conv2); -1: default_tile(d)
     // downsample fusion (bottleneck blocks): the block's last 1x1 conv ("main") and its downsample 1x1 conv ("ds")
@@ -235,6 +239,7 @@ struct mpx_engine {
     int se_pitch_max = 0;
     bool convnext = false;          // torchvision ConvNeXt-Tiny / -Small: CNBlocks over three activation buffers, staged through K0 only
     std::vector<LnLayer> lnorms;    // its stand-alone LayerNorms in forward order
+    bool regnet = false;            // torchvision RegNetX 400MF .. 8GF: bottleneck blocks with a grouped 3x3 over four activation buffers, staged through K0 only
     bool vit = false;               // torchvision vit_b_16 / vit_b_32: an encoder over four activation buffers of sizes of their own, staged through K0 only
     int vit_T = 0, vit_D = 0;       // tokens per image (197 / 50) and width (768)
     std::vector<AttnLayer> attns;   // its attention launches in forward order
@@ -339,6 +344,7 @@ int default_tile(const mpx_conv_desc& d);
 bool patch_eligible(const mpx_conv_desc& d);
 
 constexpr int kGconvTile = 16;      // the grouped 3x3 kernel (mpx_gconv.h); ids 15 and 17 stay unassigned
+constexpr int kGconvwTile = 18;     // the grouped 3x3 kernel for any group count, width and pitch (mpx_gconvw.h)
 
 // torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
 int build_topology_small(mpx_engine* h);
@@ -352,6 +358,7 @@ int build_topology_shufflenet(mpx_engine* h);
 int build_topology_efficientnet(mpx_engine* h);
 int build_topology_convnext(mpx_engine* h);
 int build_topology_vit(mpx_engine* h);
+int build_topology_regnet(mpx_engine* h);
 
 int build_topology(mpx_engine* h) {
     if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
@@ -366,6 +373,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
     if (h->arch >= MPX_ARCH_CONVNEXT && h->arch < MPX_ARCH_CONVNEXT + 1000) return build_topology_convnext(h);
     if (h->arch >= MPX_ARCH_VIT && h->arch < MPX_ARCH_VIT + 1000) return build_topology_vit(h);
+    if (h->arch >= MPX_ARCH_REGNET && h->arch < MPX_ARCH_REGNET + 1000) return build_topology_regnet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
@@ -1915,11 +1923,17 @@ int launch_patchp(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipS
 
 // The grouped 3x3 kernel (mpx_gconv.h, tile id 16): one wave per 16 output pixels x channel block, GCONV_WAVES blocks per workgroup.  The
 // grid is not capped: ceil(M / 16) <= 2^27 workgroups in x, the block quads in y.
+bool gconv_accepts(const ConvLayer& L) {
+    const int cg = L.groups > 1 ? L.d.cin / L.groups : 0, cb = gconv_cb(cg);
+    return !(L.groups <= 1 || L.d.ksize != 3 || L.d.pad != 1 || (L.d.stride != 1 && L.d.stride != 2) || L.d.cin != L.d.cout || L.d.cin % L.groups ||
+             (cg != 4 && cg != 8 && cg != 16 && cg != 32 && cg != 64) || L.d.cin % (cb * GCONV_WAVES) || L.d.k_packed != gconv_kp(cb) || L.cin_pad != L.d.cin ||
+             L.cout_store != L.d.cout);
+}
+
 int launch_gconv(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
     const int cg = L.groups > 1 ? L.d.cin / L.groups : 0, cb = gconv_cb(cg);
-    if (L.groups <= 1 || L.d.ksize != 3 || L.d.pad != 1 || (L.d.stride != 1 && L.d.stride != 2) || L.d.cin != L.d.cout || L.d.cin % L.groups ||
-        (cg != 4 && cg != 8 && cg != 16 && cg != 32 && cg != 64) || L.d.cin % (cb * GCONV_WAVES) || L.d.k_packed != gconv_kp(cb) || L.cin_pad != L.d.cin ||
-        L.cout_store != L.d.cout)
+    // (a layer in mpx_gconvw.h's form has tile 16's planes only where a channel block is one group of 16: cg = 16)
+    if (!gconv_accepts(L) || (L.gw && cg != 16))
         return fail(h, MPX_E_INTERNAL, "grouped conv: %s is not a 3x3 pad-1 layer of 4, 8, 16, 32 or 64 channels per group", L.d.name);
     if (p.r_hi || p.y_f32 || p.k1) return fail(h, MPX_E_ARG, "grouped conv: %s takes no residual operand and no fp32 output", L.d.name);
     p.n_tiles_c = L.d.cin / cb;
@@ -1928,6 +1942,34 @@ int launch_gconv(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipSt
         case 16: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<16>, grid, block, 0, st, p); break;
         case 32: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<32>, grid, block, 0, st, p); break;
         default: hipLaunchKernelGGL(gconv3x3_f16x3_kernel<64>, grid, block, 0, st, p); break;
+    }
+    return launched(h, id);
+}
+
+// The grouped 3x3 kernel for any group count (mpx_gconvw.h, tile id 18): one wave per GCONVW_NT tiles of 16 output pixels x group x chunk of row
+// fragments, GCONVW_WAVES units per workgroup.  The grid is not capped: ceil(M / (16 GCONVW_NT)) < 2^27 workgroups in x, the unit quads in y.
+bool gconvw_accepts(const ConvLayer& L) {
+    const int cg = L.groups > 1 ? L.d.cin / L.groups : 0;
+    return L.gw && L.groups > 1 && L.d.ksize == 3 && L.d.pad == 1 && (L.d.stride == 1 || L.d.stride == 2) && L.d.cin == L.d.cout && L.d.cin % L.groups == 0 &&
+           (cg == 16 || cg == 24 || cg == 48 || cg == 120) && L.d.k_packed == gconvw_kp(cg) && L.d.cout_pad == L.groups * gconvw_rf(cg) * 16 &&
+           L.cin_pad >= L.d.cin && L.cin_pad % 8 == 0 && L.cout_store >= L.d.cout && L.cout_store % 8 == 0 && !L.x_pitch && !L.y_pitch;
+}
+
+int launch_gconvw(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (!gconvw_accepts(L))
+        return fail(h, MPX_E_INTERNAL, "grouped conv: %s is not a 3x3 pad-1 layer of 16, 24, 48 or 120 channels per group in the any-width form", L.d.name);
+    if (p.r_hi || p.y_f32 || p.k1) return fail(h, MPX_E_ARG, "grouped conv: %s takes no residual operand and no fp32 output", L.d.name);
+    const int cg = L.d.cin / L.groups;
+    p.n_tiles_c = L.groups;
+    p.k_per_tap = L.d.cin;      // the layer's width: where the output's pad channels begin
+    const int units = L.groups * gconvw_nch(cg);
+    const int per_wg = 16 * GCONVW_NT;
+    const dim3 grid((unsigned)(((long long)p.M + per_wg - 1) / per_wg), (unsigned)((units + GCONVW_WAVES - 1) / GCONVW_WAVES)), block(64 * GCONVW_WAVES);
+    switch (cg) {
+        case 16: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<16, GCONVW_NT>), grid, block, 0, st, p); break;
+        case 24: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<24, GCONVW_NT>), grid, block, 0, st, p); break;
+        case 48: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<48, GCONVW_NT>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<120, GCONVW_NT>), grid, block, 0, st, p); break;
     }
     return launched(h, id);
 }
@@ -1959,6 +2001,8 @@ const TileRow kTiles[] = {
     {14, launch_convw, convw_eligible,
      "the weights-in-registers expanding-1x1 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin = 256", 7, false},
     {kGconvTile, launch_gconv, nullptr, "the grouped 3x3 kernel runs grouped layers (a ResNeXt block's conv2) and nothing else", -1, false},
+    {kGconvwTile, launch_gconvw, nullptr,
+     "the any-width grouped 3x3 kernel runs grouped layers of 16, 24, 48 or 120 channels per group (a RegNetX block's f.b) and nothing else", -1, false},
 };
 
 // Dynamic LDS ceiling of every conv kernel (mpx_create): the kernels of kTiles with their DUAL forms, the stem + pool kernel, the block
@@ -2017,6 +2061,8 @@ const TileRow* find_tile(int id) {
 // the 256-row kernels (mpx_conv256.h, mpx_conv256p.h, mpx_convx.h, mpx_convw.h) and the patch kernels (cin = k_per_tap is their row pitch)
 // read dense pixel rows.
 bool eligible(const TileRow& r, const ConvLayer& L) {
+    // a RegNetX grouped layer runs tile 18, and tile 16 where its shape is one of tile 16's (cg = 16, width % 64 == 0, pitch = width); tile 18 nothing else
+    if (L.gw || r.id == kGconvwTile) return L.gw && ((r.id == kGconvwTile && gconvw_accepts(L)) || (r.id == kGconvTile && gconv_accepts(L) && L.d.cin / L.groups == 16));
     if (L.groups > 1 || r.id == kGconvTile) return L.groups > 1 && r.id == kGconvTile;     // a grouped layer runs tile 16, and tile 16 nothing else
     if (L.epi_act && r.eligible) return false;      // only the generic kernel's epilogue has an activation other than ReLU (ConvGelu)
     return !r.eligible || (!L.is_fc && !L.is_stem && L.cin_pad == L.d.cin && !L.y_pitch && !L.x_pitch && r.eligible(L.d));
@@ -2076,6 +2122,119 @@ int default_tile(const mpx_conv_desc& d) {
 #endif
     if (conv256_eligible(d)) return conv256p_eligible(d) ? 13 : 9;
     return 2;
+}
+
+// torchvision RegNetX (regnet.py; BlockParams.from_init_params quantises the widths to 8 and makes each divisible by min(group width, width)):
+//   name             id     stage widths          depths        group width   groups per stage
+//   regnet_x_400mf   14004  32, 64, 160, 400      1, 2, 7, 12   16            2, 4, 10, 25
+//   regnet_x_800mf   14008  64, 128, 288, 672     1, 3, 7, 5    16            4, 8, 18, 42
+//   regnet_x_1_6gf   14016  72, 168, 408, 912     2, 4, 10, 2   24            3, 7, 17, 38
+//   regnet_x_3_2gf   14032  96, 192, 432, 1008    2, 6, 15, 2   48            2, 4, 9, 21
+//   regnet_x_8gf     14080  80, 240, 720, 1920    2, 5, 15, 1   120           1 (80 channels: a dense 3x3), 2, 6, 16
+// stem.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN (stem.1) + ReLU, no max pool (MobileNetV2's features.0.0: the row-run form on the padded NHWC4
+// staging).  trunk_output.block{s}.block{s}-{j} is a bottleneck of ratio 1: f.a 1x1 w_in -> w + BN + ReLU at the input resolution, f.b 3x3
+// w -> w with w / gw groups (stride 2 in block 0 of every stage) + BN + ReLU, f.c 1x1 w -> w + BN, out = ReLU(shortcut + f.c); the shortcut is
+// proj (1x1 stride 2 + BN) in block 0 of every stage and the identity elsewhere.  Global average pool, fc.  No conv has a bias.
+// Channels: every plane has a pitch of round_up(width, 32) (cin_pad / cout_store as MobileNetV2: zero weight columns, zero scale and shift
+// on the padded rows); the grouped kernel writes its pad channels as +0 itself (mpx_gconvw.h).  Such layers run the generic tiles (eligible()).
+// Launches: one per conv -- proj is a launch of its own in every stage (the K-concatenated dual form reads planes whose pitch is their cin).
+// Buffers: four, sized by the largest map of the network (f.a of block 0 runs at the previous stage's resolution): X the block input, T1
+// f.a's output and then -- dead after f.b -- the block output, T2 f.b's output, T3 proj's output.
+int build_topology_regnet(mpx_engine* h) {
+    struct Row { int id; int widths[4]; int depths[4]; int gw; };
+    static const Row rows[] = {
+        {MPX_ARCH_REGNET + 4, {32, 64, 160, 400}, {1, 2, 7, 12}, 16},
+        {MPX_ARCH_REGNET + 8, {64, 128, 288, 672}, {1, 3, 7, 5}, 16},
+        {MPX_ARCH_REGNET + 16, {72, 168, 408, 912}, {2, 4, 10, 2}, 24},
+        {MPX_ARCH_REGNET + 32, {96, 192, 432, 1008}, {2, 6, 15, 2}, 48},
+        {MPX_ARCH_REGNET + 80, {80, 240, 720, 1920}, {2, 5, 15, 1}, 120},
+    };
+    const Row* R = nullptr;
+    for (const Row& r : rows)
+        if (r.id == h->arch) R = &r;
+    if (!R) return MPX_E_ARG;
+    h->regnet = true;
+    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
+    size_t act_max = 0;
+    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu,
+                        int residual, bool fc) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
+        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
+        L.d.relu = relu; L.d.residual = residual;
+        L.is_fc = fc;
+        L.has_bias = fc;
+        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
+        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
+        L.cout_store = fc ? cout : pitch_of(cout);
+        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
+        L.d.cout_pad = (int)round_up(cout, 128);
+        L.tile = default_tile(L.d);
+        const TileRow* r = find_tile(L.tile);
+        if (!r || !eligible(*r, L)) L.tile = L.tile_default = 2;       // (no layer of the five networks: default_tile hands them generic tiles only)
+        if (!fc) act_max = std::max(act_max, (size_t)L.d.hout * L.d.hout * L.cout_store);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    // f.b: w -> w in w / gw groups of gw channels (mpx_gconvw.h)
+    auto add_gconvw = [&](const std::string& name, const std::string& bn, int w, int gw, int stride, int hin) {
+        ConvLayer L;
+        std::memset(&L.d, 0, sizeof L.d);
+        set_name(L.d.name, name);
+        set_name(L.d.bn_name, bn);
+        L.d.cin = w; L.d.cout = w; L.d.ksize = 3; L.d.stride = stride; L.d.pad = 1;
+        L.d.hin = hin; L.d.hout = (hin + 2 - 3) / stride + 1;
+        L.d.relu = 1; L.d.residual = 0;
+        L.cin_pad = pitch_of(w);
+        L.cout_store = pitch_of(w);
+        L.groups = w / gw;
+        L.gw = true;
+        L.d.k_packed = gconvw_kp(gw);
+        L.d.cout_pad = L.groups * gconvw_rf(gw) * 16;
+        L.tile = L.tile_default = kGconvwTile;
+        act_max = std::max(act_max, (size_t)L.d.hout * L.d.hout * L.cout_store);
+        h->convs.push_back(L);
+        return (int)h->convs.size() - 1;
+    };
+    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
+    int c = add_conv("stem.0", "stem.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
+    conv_op(c, BUF_INPUT, 0, BUF_NONE);
+    int X = 0, cin = 32, hcur = 112;
+    for (int s = 0; s < 4; ++s) {
+        const int w = R->widths[s], gw = std::min(R->gw, w);
+        if (w % gw || w % 8) return MPX_E_INTERNAL;
+        for (int j = 0; j < R->depths[s]; ++j) {
+            const int stride = j == 0 ? 2 : 1, hout = (hcur - 1) / stride + 1;
+            const std::string p = "trunk_output.block" + std::to_string(s + 1) + ".block" + std::to_string(s + 1) + "-" + std::to_string(j) + ".";
+            const int T1 = (X + 1) % 4, T2 = (X + 2) % 4, T3 = (X + 3) % 4;
+            int res = X;
+            if (j == 0) {
+                c = add_conv(p + "proj.0", p + "proj.1", cin, w, 1, 2, 0, hcur, 0, 0, false);
+                conv_op(c, X, T3, BUF_NONE);
+                res = T3;
+            }
+            c = add_conv(p + "f.a.0", p + "f.a.1", cin, w, 1, 1, 0, hcur, 1, 0, false);
+            conv_op(c, X, T1, BUF_NONE);
+            c = w / gw > 1 ? add_gconvw(p + "f.b.0", p + "f.b.1", w, gw, stride, hcur) : add_conv(p + "f.b.0", p + "f.b.1", w, w, 3, stride, 1, hcur, 1, 0, false);
+            conv_op(c, T1, T2, BUF_NONE);
+            c = add_conv(p + "f.c.0", p + "f.c.1", w, w, 1, 1, 0, hout, 1, 1, false);
+            conv_op(c, T2, T1, res);        // T1 is dead after f.b
+            X = T1;
+            cin = w;
+            hcur = hout;
+        }
+    }
+    h->n_act_bufs = 4;
+    h->act_elems_per_image = act_max;
+    h->feat = cin;
+    h->ops.push_back(Op{OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hcur, pitch_of(cin), BUF_NONE});
+    c = add_conv("fc", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
+    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
+    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
+    return 0;
 }
 
 // The ConvParams of layer L over B images: its packed weights, the input planes in_* (the ImageNet stem: the engine's padded NHWC4 staging,
@@ -2710,6 +2869,44 @@ int pack_gconv_weights(const mpx_conv_desc* d, int groups, const float* w, const
     return 0;
 }
 
+// The packed planes of a grouped 3x3 layer in mpx_gconvw.h's form from torchvision's [w][cg][3][3]: per group ceil(cg / 16) row fragments of 16
+// output channels, k = (ky * 3 + kx) * cg + ci over the group's own cg input channels.  The rows >= cg of a group's last fragment and the K
+// padding behind tap 8 stay exact zeros.  Row scaling, scale and shift are pack_gconv_weights'; scale and shift are indexed by the channel.
+int pack_gconvw_weights(const mpx_conv_desc* d, int groups, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
+                        float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale, float* shift) {
+    if (groups <= 0 || d->cout % groups) return MPX_E_ARG;
+    const int C = d->cout, cg = C / groups, K = gconvw_kp(cg), rows = groups * gconvw_rf(cg) * 16;
+    if (d->cin != C || cg % 8 || d->ksize != 3 || d->k_packed != K || d->cout_pad != rows || !gamma || !beta || !mean || !var) return MPX_E_ARG;
+    std::memset(w_hi, 0, (size_t)rows * K * 2);
+    std::memset(w_lo, 0, (size_t)rows * K * 2);
+    for (int r = 0; r < rows; ++r) scale[r] = shift[r] = 0.f;
+    for (int co = 0; co < C; ++co) {
+        const float* wc = w + (size_t)co * cg * 9;
+        float mx = 0.f;
+        for (int j = 0; j < cg * 9; ++j) mx = std::fmax(mx, std::fabs(wc[j]));
+        int e = 0;
+        if (mx > 0.f && std::isfinite(mx)) {
+            int ex;
+            std::frexp(mx, &ex);
+            e = 10 - ex;
+        }
+        const int g = co / cg, r = co - g * cg;
+        for (int t = 0; t < 9; ++t)
+            for (int ci = 0; ci < cg; ++ci) {
+                const float sv = std::ldexp(wc[(size_t)ci * 9 + t], e);
+                const half_t hi = (half_t)sv;
+                const half_t lo = (half_t)(sv - (float)hi);
+                const size_t at = gconvw_w_index(g, r, t * cg + ci, cg);
+                w_hi[at] = half_bits(hi);
+                w_lo[at] = half_bits(lo);
+            }
+        const double s = (double)gamma[co] / std::sqrt((double)var[co] + (double)eps);
+        scale[co] = (float)std::ldexp(s, -e);
+        shift[co] = (float)((double)beta[co] - (double)mean[co] * s);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2893,7 +3090,8 @@ int mpx_set_conv_weights(mpx_engine* h, int i, const float* w, const float* conv
     const size_t n = (size_t)L.d.cout_pad * L.d.k_packed;
     std::vector<uint16_t> hi(n), lo(n);
     std::vector<float> sc(L.d.cout_pad), sh(L.d.cout_pad);
-    int rc = L.groups > 1 ? pack_gconv_weights(&L.d, L.groups, w, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data())
+    int rc = L.gw      ? pack_gconvw_weights(&L.d, L.groups, w, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data())
+           : L.groups > 1 ? pack_gconv_weights(&L.d, L.groups, w, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data())
                           : pack_conv_weights(&L.d, L.in_bf, L.in_hp, w, conv_bias, gamma, beta, mean, var, eps, hi.data(), lo.data(), sc.data(), sh.data(),
                                               L.is_stem && !(L.d.ksize & 1));
     if (rc) return fail(h, rc, "pack failed for %s", L.d.name);
@@ -2953,7 +3151,9 @@ int mpx_set_conv_tile(mpx_engine* h, int i, int tile) {
         for (const TileRow& k : kTiles) ids += (ids.empty() ? "" : ", ") + std::to_string(k.id);
         return fail(h, MPX_E_ARG, "set_conv_tile: unknown tile %d (product ids: %s)", tile, ids.c_str());
     }
-    if (L.groups > 1 && tile != kGconvTile)
+    if (L.gw && tile != kGconvwTile && !eligible(*r, L))
+        return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: a grouped layer of this network runs the any-width grouped 3x3 kernel (tile %d), and tile %d where its shape is one of that kernel's (%s is not)", tile, kGconvwTile, kGconvTile, L.d.name);
+    if (L.groups > 1 && !L.gw && tile != kGconvTile)
         return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: a grouped layer runs the grouped 3x3 kernel (tile %d) only (%s is one)", tile, kGconvTile, L.d.name);
     if (L.epi_act && r->eligible)
         return fail(h, MPX_E_ARG, "set_conv_tile: tile %d: %s applies GELU in its epilogue, which only the generic kernel (tiles 0, 1, 2, 4 and 7) has", tile, L.d.name);
@@ -3083,7 +3283,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt and ViT stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit || h->regnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT and RegNetX stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");

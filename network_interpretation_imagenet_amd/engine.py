@@ -44,6 +44,8 @@ CONVNEXT_LN_EPS = 1e-6      # torchvision convnext.py: every LayerNorm / LayerNo
 # out_proj" has 55): state_dict_name() puts it back, and in_proj's tensors are `...self_attention.in_proj_weight` / `in_proj_bias` (an
 # underscore: nn.MultiheadAttention's own parameters, not a submodule's)
 ARCH_IDS.update({"vit_b_16": 13016, "vit_b_32": 13032})
+# torchvision's RegNetX networks up to 8 GF (MPX_ARCH_REGNET + ten times the GF figure): a bottleneck whose 3x3 is grouped by a fixed group width
+ARCH_IDS.update({"regnet_x_400mf": 14004, "regnet_x_800mf": 14008, "regnet_x_1_6gf": 14016, "regnet_x_3_2gf": 14032, "regnet_x_8gf": 14080})
 VIT_LN_EPS = 1e-6           # torchvision vision_transformer.py: norm_layer = partial(nn.LayerNorm, eps=1e-6)
 VIT_LAYER_PREFIX = "encoder.layers."
 
@@ -161,6 +163,9 @@ class MaskedForwardEngine:
         A ViT-B/16 slot holds 6.3 MB -- four split-fp16 activation buffers of sizes of their own (the residual stream and a LayerNorm's /
         the attention's output, 197 x 768 each, in_proj's 197 x 2304 and the hidden 197 x 3072 rows: 5.45 MB) and the input staging --, a
         ViT-B/32 slot 2.2 MB (50 tokens); both keep the default of 512 (3.6 / 1.5 GB with the packed weights).
+        A RegNetX slot holds four split-fp16 activation buffers of the network's largest map -- 112x112x32 (400MF: 7.3 MB with the input
+        staging), 112x112x64 (800MF: 13.7 MB) or 112x112x96 (1.6GF, 3.2GF, 8GF: block1-0.f.a's output at a pitch of 96, 20.1 MB) -- and keeps
+        the default of 512 (3.7 / 7.0 / 10.3 GB).
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -171,7 +176,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d, ConvNeXt-Tiny / -Small and ViT-B/16 / ViT-B/32: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d, ConvNeXt-Tiny / -Small, ViT-B/16 / ViT-B/32 and RegNetX-400MF .. -8GF: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -241,7 +246,7 @@ class MaskedForwardEngine:
             sd_ = _lib.SeDesc()
             _lib.check(h, self._lib.mpx_se_info(h, k, C.byref(sd_)), "mpx_se_info")
             self.ses.append(sd_)
-        self.groups = []        # groups per conv layer: 32 on a ResNeXt block's conv2 (weight [cout][cin / 32][3][3]), 1 everywhere else
+        self.groups = []        # groups per conv layer: 32 on a ResNeXt block's conv2 (weight [cout][cin / 32][3][3]), width / group width on a RegNetX block's f.b, 1 everywhere else
         for i in range(len(self.layers)):
             gr = C.c_int()
             _lib.check(h, self._lib.mpx_conv_groups(h, i, C.byref(gr)), "mpx_conv_groups")
@@ -268,9 +273,9 @@ class MaskedForwardEngine:
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
         which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s,
-        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool), the ViTs (a 16x16 / 32x32 patchify stem) and the small networks
-        stage through K0 only."""
-        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext", "vit_"))
+        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool), the ViTs (a 16x16 / 32x32 patchify stem), the RegNetXs (a 3x3
+        stride-2 stem, no pool) and the small networks stage through K0 only."""
+        return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext", "vit_", "regnet"))
 
     def stem_for_rows(self, rows_per_image):
         """The staging an IMAGE that brings `rows_per_image` mask rows to a job gets on this engine: "table" (the stem by superposition) from

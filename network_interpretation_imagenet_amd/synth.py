@@ -598,10 +598,53 @@ def make_resnext_state_dict(arch, seed=7):
     return sd
 
 
+# torchvision's RegNetX networks up to 8 GF: (stage widths, stage depths, group width, gain of every f.c BatchNorm) -- the widths and depths
+# are what BlockParams.from_init_params makes of (depth, w_0, w_a, w_m, group width) (tests/regnet_ref.py derives them from that rule).  The
+# gain of f.c's BatchNorm plays the part of the ResNets' bn3 gain: it keeps the trunk from growing through up to 22 residual adds and puts
+# the fp64 softmax peak of the rows tests/regnet_ref.py scores inside [0.05, 0.95] (tests/test_regnet_cpu.py).
+REGNET_ARCHS = {
+    "regnet_x_400mf": ((32, 64, 160, 400), (1, 2, 7, 12), 16, 0.4),
+    "regnet_x_800mf": ((64, 128, 288, 672), (1, 3, 7, 5), 16, 0.3),
+    "regnet_x_1_6gf": ((72, 168, 408, 912), (2, 4, 10, 2), 24, 0.4),
+    "regnet_x_3_2gf": ((96, 192, 432, 1008), (2, 6, 15, 2), 48, 0.3),
+    "regnet_x_8gf": ((80, 240, 720, 1920), (2, 5, 15, 1), 120, 0.4),
+}
+
+
+def make_regnet_state_dict(arch, seed=7):
+    """OrderedDict with the key set, order and shapes of models.regnet_x_400mf() .. regnet_x_8gf(): stem.0.weight [32][3][3][3], stem.1.*, then
+    per block trunk_output.block{s}.block{s}-{j}. proj.0 / proj.1 (block 0 of every stage), f.a.0 [w][w_in][1][1] / f.a.1, f.b.0 [w][gw][3][3]
+    (w / gw groups, gw = min(group width, w)) / f.b.1, f.c.0 [w][w][1][1] / f.c.1, then fc.weight / fc.bias.  Conv gains come from the fan-in
+    (9 * gw for f.b); the BatchNorm draws are the ResNets', with the gain of REGNET_ARCHS on f.c's."""
+    widths, depths, gw, last = REGNET_ARCHS[arch]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    _conv(sd, "stem.0", 3, 32, 3, g)
+    _bn(sd, "stem.1", 32, g)
+    cin = 32
+    for s, (w, d) in enumerate(zip(widths, depths)):
+        cg = min(gw, w)
+        for j in range(d):
+            p = "trunk_output.block%d.block%d-%d." % (s + 1, s + 1, j)
+            if j == 0:
+                _conv(sd, p + "proj.0", cin, w, 1, g)
+                _bn(sd, p + "proj.1", w, g)
+            _conv(sd, p + "f.a.0", cin, w, 1, g)
+            _bn(sd, p + "f.a.1", w, g)
+            _conv(sd, p + "f.b.0", cg, w, 3, g)
+            _bn(sd, p + "f.b.1", w, g)
+            _conv(sd, p + "f.c.0", w, w, 1, g)
+            _bn(sd, p + "f.c.1", w, g, last=last)
+            cin = w
+    sd["fc.weight"] = torch.randn(1000, cin, generator=g) * (FC_GAIN / cin ** 0.5)
+    sd["fc.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict, ConvNeXt: make_convnext_state_dict, ViT: make_vit_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict, ConvNeXt: make_convnext_state_dict, ViT: make_vit_state_dict, RegNetX: make_regnet_state_dict) key set."""
     if arch == "efficientnet_b0":
         return make_efficientnet_state_dict(seed)
     if arch in CONVNEXT_DEPTHS:
@@ -610,6 +653,8 @@ def make_state_dict(arch, seed=7):
         return make_vit_state_dict(arch, seed)
     if arch in RESNEXT_ARCHS:
         return make_resnext_state_dict(arch, seed)
+    if arch in REGNET_ARCHS:
+        return make_regnet_state_dict(arch, seed)
     if arch in SHUFFLENET_WIDTHS:
         return make_shufflenet_state_dict(arch, seed)
     if arch == "googlenet":

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-layer conv timing (HIP events inside the engine) for one forward batch.
-usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d add the
-                                                                 grouped 3x3 launches as rows of their own, with their bytes and TB/s;
+usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d and
+                                                                 regnet_x_400mf .. regnet_x_8gf add the grouped 3x3 launches as rows of
+                                                                 their own, with their bytes, TB/s and MFMA TFLOP/s;
                                                                  convnext_tiny / convnext_small the depthwise 7x7 + LayerNorm launches and the
                                                                  stand-alone LayerNorms, with bytes, TB/s and the shares by op class;
                                                                  vit_b_16 / vit_b_32 the attention, token assembly and LayerNorm launches
@@ -156,7 +157,7 @@ if fused:       # the grouped rows above book these launches under their main co
         print("%-16s + %-24s K %4d + %-4d out%-3d %8.3f ms %5.1f%% %9.1f GFLOP %8.1f TFLOP/s" % (
             names[li], names[lj], d.cin * d.ksize * d.ksize, eng.layers[lj].cin, d.hout, ms, 100 * ms / tot, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 if max(eng.groups) > 1:     # ResNeXt: the grouped 3x3 launches (csrc/mpx_gconv.h, tile 16) as rows of their own, by their bytes and by their MFMA work
-    print("-- grouped 3x3 convs (tile 16: one launch each); bytes = split-fp16 input + output planes once; MFMA TFLOP/s = the three f16 products over "
+    print("-- grouped 3x3 convs (tile 16, RegNetX: csrc/mpx_gconvw.h, tile 18 -- row fragments of 16 channels per group: one launch each); bytes = split-fp16 input + output planes once; MFMA TFLOP/s = the three f16 products over "
           "channel blocks of max(cg, 16) and K padded to 32 (4x / 2x the algorithmic FLOPs at cg = 4 / 8) --")
     tot_g = g_bytes = g_fl = 0.0
     by_shape = {}
@@ -167,7 +168,7 @@ if max(eng.groups) > 1:     # ResNeXt: the grouped 3x3 launches (csrc/mpx_gconv.
         cg = d.cin // eng.groups[li]
         cb = max(cg, 16)
         nbytes = batch * 4.0 * d.cin * (d.hin * d.hin + d.hout * d.hout)
-        mfma_fl = 3 * 2.0 * batch * d.hout * d.hout * d.cout * d.k_packed     # every output channel x the padded K of its block, three products
+        mfma_fl = 3 * 2.0 * batch * d.hout * d.hout * d.cout_pad * d.k_packed     # every row of the packed planes (= cout on a ResNeXt) x the padded K of its block, three products
         tot_g += ms
         g_bytes += nbytes
         g_fl += conv_flops(li)

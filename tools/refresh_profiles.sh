@@ -39,4 +39,10 @@ python tools/latency_bench.py resnet101 10 2>&1 | grep -v amdgpu.ids > $O/${R}_l
 cat $O/${R}_latency_cfg5.txt
 ( python tools/api_throughput.py resnet101 32 $B noise; python tools/api_throughput.py resnet101 32 $B blobs ) 2>&1 | grep -v amdgpu.ids > $O/${R}_api_throughput.txt
 python tools/probes/btail_phases.py $B 2>&1 | grep -v amdgpu.ids > $O/${R}_btail_phases.txt
+# RegNetX: per-layer tables at batch 512 (the grouped 3x3 launches as rows of their own) and the benchmark of every network
+# -> profiles/regnet_layers_<arch>_b512.txt, profiles/regnet_bench.txt
+for A in regnet_x_400mf regnet_x_800mf regnet_x_1_6gf regnet_x_3_2gf regnet_x_8gf; do
+  MPX_PER_LAYER=1 python tools/layer_profile.py $A 512 3 2>&1 | grep -v amdgpu.ids > $O/regnet_layers_${A}_b512.txt
+  python bench.py --arch $A 2>/dev/null | tail -1 >> $O/regnet_bench.txt
+done
 rm -rf $O/stats $O/pmc_fetch_* $O/pmc_write_*

@@ -246,7 +246,7 @@ enum {
  * is whatever the stage width gives (5,495,976 / 7,259,656 / 9,190,136 / 15,296,552 / 39,572,648 parameters, 413,812,608 / 799,699,712 /
  * 1,602,849,792 / 3,176,621,952 / 7,995,132,416 MAC per forward):
  *   MPX_ARCH_REGNET + 4 / 8 / 16 / 32 / 80   regnet_x_400mf / _800mf / _1_6gf / _3_2gf / _8gf (ten times the GF figure); every other id in
- *                                            [14000, 15000) is MPX_E_ARG (regnet_x_16gf / _32gf and the RegNetY family included)
+ *                                            [14000, 15000) is MPX_E_ARG (regnet_x_16gf / _32gf included)
  *   stage widths (32, 64, 160, 400) (64, 128, 288, 672) (72, 168, 408, 912) (96, 192, 432, 1008) (80, 240, 720, 1920), depths (1, 2, 7, 12)
  *   (1, 3, 7, 5) (2, 4, 10, 2) (2, 6, 15, 2) (2, 5, 15, 1), group width 16, 16, 24, 48, 120 -- groups (2, 4, 10, 25) (4, 8, 18, 42) (3, 7, 17, 38)
  *   (2, 4, 9, 21) (1, 2, 6, 16); 72 / 54 / 60 / 81 / 75 entries in the conv list.
@@ -263,6 +263,19 @@ enum {
  * (exact zeros in the padded channels, as MobileNetV2: the grouped kernel writes them itself); such dense layers run the generic tiles only.
  * Four activation buffers of the network's largest map (112 * 112 * 32 / 64 / 96 / 96 / 96 elements per image) plus the staging.  It stages
  * through mpx_mask_apply_normalize only: the stem-table and stem + pool entry points return MPX_E_STATE.
+ * -- or one of torchvision's RegNetY networks from 800 MF to 8 GF: RegNetX's trunk with a Squeeze-and-Excitation gate in every block
+ * (6,432,512 / 11,202,430 / 19,436,338 / 39,381,472 parameters):
+ *   MPX_ARCH_REGNET_Y + 8 / 16 / 32 / 80     regnet_y_800mf / _1_6gf / _3_2gf / _8gf (ten times the GF figure); every other id in
+ *                                            [15000, 16000) is MPX_E_ARG (regnet_y_400mf: a group width of 8, below the grouped kernel's 16;
+ *                                            regnet_y_16gf / _32gf: group widths 112 / 232 = 7 / 15 row fragments, no whole number of chunks)
+ *   stage widths (64, 144, 320, 784) (48, 120, 336, 888) (72, 216, 576, 1512) (224, 448, 896, 2016), depths (1, 3, 8, 2) (2, 6, 17, 2)
+ *   (2, 5, 13, 1) (2, 4, 10, 1), group width 16, 24, 24, 56 -- groups (4, 9, 20, 49) (2, 5, 14, 37) (3, 9, 24, 63) (4, 8, 16, 36); 48 / 87 / 69 /
+ *   57 entries in the conv list, 14 / 27 / 21 / 17 in the SE list.
+ * Stem, blocks, pitches, buffers and staging are RegNetX's.  The one addition: between f.b and f.c every block has f.se =
+ * SqueezeExcitation(w, q) with q = the BLOCK's input width / 4 (32 / 4 = 8 in block1-0, the previous stage's width / 4 in the other stage
+ * openers), fc1 and fc2 1x1 convs WITH bias, ReLU behind fc1 and sigmoid behind fc2: mpx_forward runs mpx_se_gate_relu and mpx_se_scale in
+ * place on f.b's output (mpx_num_se, mpx_se_info, mpx_load_se, mpx_se_params, mpx_se_act = 1; state_dict keys <block>.f.se.fc1.weight / .bias,
+ * .fc2.weight / .bias).  regnet_y_8gf's group width 56 is tile 18's fifth instantiation (4 row fragments, K = 504 padded to 512).
  * Small-network engines stage inputs with mpx_mask_apply_minmax (their scorers' mask convention) instead of
  * mpx_mask_apply_normalize, keep activations as NHWC planes with channels padded to a multiple of 32, and score 10 classes
  * (logit rows are 16 floats apart: mpx_geometry). */
@@ -281,6 +294,7 @@ enum {
 #define MPX_ARCH_CONVNEXT 12000
 #define MPX_ARCH_VIT 13000
 #define MPX_ARCH_REGNET 14000
+#define MPX_ARCH_REGNET_Y 15000
 typedef struct mpx_engine mpx_engine;
 
 typedef struct mpx_conv_desc {
@@ -331,7 +345,7 @@ int mpx_conv_out_slice(const mpx_engine* h, int i, int* pitch, int* offset);
  * (l < bf) or hp + l - bf; 0, 0 for every other layer.  Any pointer may be NULL. */
 int mpx_conv_in_slice(const mpx_engine* h, int i, int* pitch, int* offset, int* bf, int* hp);
 /* Groups of layer i: 32 on the conv2 of a ResNeXt engine's blocks (cin / 32 input channels per output channel: mpx_set_conv_weights takes
- * [cout][cin / 32][3][3] there, and the layer runs tile 16 and nothing else), w / gw = 2 .. 42 on the f.b of a RegNetX engine's blocks
+ * [cout][cin / 32][3][3] there, and the layer runs tile 16 and nothing else), w / gw = 2 .. 63 on the f.b of a RegNetX / RegNetY engine's blocks
  * ([w][gw][3][3]; tile 18, and tile 16 where the shape is one of that kernel's), 1 on every other layer of every engine. */
 int mpx_conv_groups(const mpx_engine* h, int i, int* groups);
 /* The activation torchvision puts behind layer i that the layer itself does NOT apply because its one consumer takes it on load: *act = 0
@@ -448,6 +462,9 @@ int mpx_num_se(const mpx_engine* h);
 int mpx_se_info(const mpx_engine* h, int k, mpx_se_desc* out);
 int mpx_load_se(mpx_engine* h, int k, const float* w1, const float* b1, const float* w2, const float* b2);
 int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1, const float** w2, const float** b2);
+/* The activation behind fc1 of SE layer k: *act = 0 SiLU (every layer of an EfficientNet-B0 engine: mpx_forward runs mpx_se_gate), 1 ReLU
+ * (every f.se of a RegNetY engine, q = block input width / 4: mpx_se_gate_relu).  MPX_E_ARG for a null pointer or a bad index. */
+int mpx_se_act(const mpx_engine* h, int k, int* act);
 
 /* Kernel variant of layer i (tuning / test hook; results are identical up to fp32 summation order).  The ids are exactly the
  * kernels some layer class runs by default:
@@ -475,9 +492,9 @@ int mpx_se_params(const mpx_engine* h, int k, const float** w1, const float** b1
  *       epilogue (layers eligible for 6 with cout >= 128 and no residual operand; the default on 28x28 / 14x14 maps; bit-identical to 6).
  *  16 = the grouped 3x3 kernel (csrc/mpx_gconv.h): one wave per 16 output pixels x channel block of max(cg, 16) channels, operands straight
  *       from global memory (the conv2 of a ResNeXt block: its only tile, and the tile of nothing else; ids 15 and 17 are unassigned).
- *  18 = the grouped 3x3 kernel for any group count, group widths 16 / 24 / 48 / 120 and planes at a pitch >= the width (csrc/mpx_gconvw.h): one
+ *  18 = the grouped 3x3 kernel for any group count, group widths 16 / 24 / 48 / 56 / 120 and planes at a pitch >= the width (csrc/mpx_gconvw.h): one
  *       wave per 32 output pixels x group x chunk of at most four 16-row fragments; it writes the output's pad channels as +0 itself (the
- *       f.b of a RegNetX block: its default; such a layer with 16 channels per group, a width that is a multiple of 64 and pitch = width also
+ *       f.b of a RegNetX / RegNetY block: its default; such a layer with 16 channels per group, a width that is a multiple of 64 and pitch = width also
  *       accepts tile 16, which gives the same bits.  Every layer that is not such a grouped layer is refused).
  * A tile a layer is not eligible for, or any other id, returns MPX_E_ARG; tile < 0 = the layer's default (a DenseNet's conv2, 3x3 128 -> 32,
  * defaults to 6, its topology's own choice: the cout <= 64 rule above was judged on 64 -> 64 layers and would give it 1).  (Ids 3, 5, 8 and 11 of
@@ -766,8 +783,34 @@ int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float
  * in_hi|lo, out_hi|lo: DEV planes [B][hw][pitch] (hw = pixels per image); gate: DEV f32[B][pitch].  Element-wise: one fp32 multiply of the
  * exact hi + lo, the re-split.  out may be in (mpx_forward scales in place); any other overlap is undefined.  Same argument discipline as
  * mpx_se_gate.  ONE launch. */
+/* ---- RegNetY: the Squeeze-and-Excitation gate with ReLU, gate = sigmoid(fc2(relu(fc1(mean over the map)))) per image --------------------
+ * replaces: torchvision's SqueezeExcitation._scale with its default activation ReLU (regnet.py: ResBottleneckBlock's f.se) inside
+ *           model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246).
+ * mpx_se_gate in every respect -- operands, layouts, summation orders, the exact +0 gates of the pad channels, the refusals, ONE launch -- but
+ * for fc1's activation: s1[j] = (v <= 0 ? 0 : v) with v = b1[j] + sum_c w1[j][c] pooled[c]. */
+int mpx_se_gate_relu(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2,
+                     float* gate, int B, int hw, int pitch, int q, void* stream);
+
 int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
                  void* stream);
+
+/* ---- RegNetX / RegNetY: the any-width grouped 3x3 kernel (tile 18) on the caller's planes -------------------------------------------------
+ * replaces: `self.b = Conv2dNormActivation(w_b, w_b, kernel_size=3, stride=stride, groups=g, ...)` of torchvision's BottleneckTransform
+ *           (regnet.py) inside model(masked_img_tensor) (generate_gp_training_data_imagenet.py:246), outside any engine's layer list.
+ * mpx_pack_gconvw_weights (HOST, no engine): torchvision's weight [width][cg][3][3] (cg = width / groups = 16, 24, 48, 56 or 120) and the
+ * BatchNorm vectors [width] -> the packed planes of csrc/mpx_gconvw.h, w_hi | w_lo: groups * ceil(cg / 16) * 16 rows of K = 9 cg rounded up
+ * to 32 fp16 bit patterns each, scale | shift: one float per ROW (indexed by the channel; the tail zero).  MPX_E_ARG for anything else.
+ * mpx_gconvw3x3_bn_act: in_hi|lo DEV planes [B][hin][hin][in_pitch], out_hi|lo DEV planes [B][hout][hout][out_pitch] (hout = (hin - 1) /
+ * stride + 1; pad 1), w_hi|lo, scale, shift DEV copies of what the packer wrote.  The channels [width, out_pitch) of every output pixel are
+ * written as +0; those of the input are never read.  groups = 1 is served here (one unit: three of a workgroup's four waves exit); an engine
+ * layer of one group is an ordinary dense layer instead.  An output element's bits depend on its own pixel and group alone: not on B, the
+ * image's index or the grid.  MPX_E_ARG for a null or misaligned (16 bytes) pointer, B <= 0, hin <= 0, a stride other than 1 or 2, a width
+ * that is no multiple of groups, another group width, a pitch below the width or no multiple of 8.  ONE launch; mpx_last_conv_kernels = 1 << 18. */
+int mpx_pack_gconvw_weights(int width, int groups, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
+                            float eps, uint16_t* w_hi, uint16_t* w_lo, float* scale, float* shift);
+int mpx_gconvw3x3_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* scale,
+                         const float* shift, void* out_hi, void* out_lo, int B, int hin, int width, int groups, int in_pitch, int out_pitch,
+                         int stride, int relu, void* stream);
 
 /* ---- ConvNeXt: the LayerNorm over the channels of a pixel, alone and fused ---------------------------------------------------------
  * THE ARITHMETIC all three entries share, per pixel with channel values v_c, in fp32 with one rounding per operator (csrc/mpx_cnext.h):

@@ -146,6 +146,12 @@ SIGNATURES = {
     "mpx_se_params": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "mpx_se_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpx_se_scale": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    # RegNetY: the SE gate with ReLU behind fc1, and which of the two gates an SE layer runs
+    "mpx_se_gate_relu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpx_se_act": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    # RegNetX / RegNetY: the any-width grouped 3x3 kernel (tile 18) on the caller's planes, and its host packer
+    "mpx_pack_gconvw_weights": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "mpx_gconvw3x3_bn_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mpx_global_avgpool_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_se": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 8),
     # ResNeXt: the groups of a layer (32 on a block's conv2, the grouped 3x3 kernel's layers)

@@ -89,7 +89,7 @@ struct ConvLayer {
     int in_hp = 0;
     int groups = 1;         // > 1: a grouped 3x3 layer (a ResNeXt conv2: cin = cout = the width, cin / groups channels per group), whose packed planes
                             // are mpx_gconv.h's -- cout_pad = cout rows of k_packed = gconv_kp(max(cin / groups, 16)), the K of ONE channel block
-    bool gw = false;        // a grouped layer in mpx_gconvw.h's form (a RegNetX f.b: any group count, cin / groups = 16, 24, 48 or 120, planes at a
+    bool gw = false;        // a grouped layer in mpx_gconvw.h's form (a RegNetX / RegNetY f.b: any group count, cin / groups = 16, 24, 48, 56 or 120, planes at a
                             // pitch of cin_pad / cout_store >= the width): packed planes [groups][ceil(cg / 16)][k_packed / 32][64][8], i.e.
                             // cout_pad = groups * ceil(cg / 16) * 16 rows of k_packed = gconvw_kp(cg).  Runs tile 18, and tile 16 where that accepts it
     int tile = 0;           // ConvTile<n> variant (mpx_set_conv_tile)
@@ -176,20 +176,21 @@ struct AttnLayer {
     mpx_attn_desc d;
 };
 
-// A Squeeze-and-Excitation layer (EfficientNet-B0; mpx_mbconv.h): fp32 fc weights and biases of its own, laid out for se_gate_kernel
+// A Squeeze-and-Excitation layer (EfficientNet-B0, RegNetY; mpx_mbconv.h): fp32 fc weights and biases of its own, laid out for se_gate_kernel
 struct SeLayer {
     mpx_se_desc d;
     float* w1 = nullptr;    // [q][pitch]
     float* b1 = nullptr;    // [q]
     float* w2 = nullptr;    // [q][pitch], j-major
     float* b2 = nullptr;    // [pitch], -inf on the pad channels
+    bool relu = false;      // fc1's activation: ReLU (a RegNetY block's f.se) instead of SiLU (mpx_se_act)
     bool loaded = false;
 };
 
 constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
 constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max pool k (mpx_engine::pools3c) kProfSubPool3c - k
 constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shuffle k (mpx_engine::shuffles) kProfSubShuffle - k
-constexpr int kProfSubSeGate = -3000000;    // ... of EfficientNet's SE layer k (mpx_engine::ses): its gate launch kProfSubSeGate - k,
+constexpr int kProfSubSeGate = -3000000;    // ... of SE layer k (mpx_engine::ses; EfficientNet, RegNetY): its gate launch kProfSubSeGate - k,
 constexpr int kProfSubSeScale = -4000000;   //     its scale launch kProfSubSeScale - k
 constexpr int kProfSubLnorm = -5000000;     // ... of ConvNeXt's stand-alone LayerNorm k (mpx_engine::lnorms) kProfSubLnorm - k
 constexpr int kProfSubAttn = -6000000;      // ... of a ViT's attention launch k (mpx_engine::attns) kProfSubAttn - k
@@ -234,12 +235,13 @@ struct mpx_engine {
     bool shufflenet = false;        // torchvision ShuffleNetV2: split / shuffle blocks over three activation buffers, staged through K0 only
     std::vector<ShuffleOp> shuffles;    // its channel shuffles in forward order
     bool efficientnet = false;      // torchvision EfficientNet-B0: MBConv blocks with SE over three activation buffers, staged through K0 only
-    std::vector<SeLayer> ses;       // its Squeeze-and-Excitation layers in forward order
+    std::vector<SeLayer> ses;       // its Squeeze-and-Excitation layers in forward order (a RegNetY engine's too)
     float* se_gate = nullptr;       // f32[max_batch][se_pitch_max]: the gates of the SE layer in flight
     int se_pitch_max = 0;
     bool convnext = false;          // torchvision ConvNeXt-Tiny / -Small: CNBlocks over three activation buffers, staged through K0 only
     std::vector<LnLayer> lnorms;    // its stand-alone LayerNorms in forward order
     bool regnet = false;            // torchvision RegNetX 400MF .. 8GF: bottleneck blocks with a grouped 3x3 over four activation buffers, staged through K0 only
+    bool regnet_y = false;          // ... and RegNetY 800MF .. 8GF (regnet is set too): an SE gate with ReLU between f.b and f.c of every block
     bool vit = false;               // torchvision vit_b_16 / vit_b_32: an encoder over four activation buffers of sizes of their own, staged through K0 only
     int vit_T = 0, vit_D = 0;       // tokens per image (197 / 50) and width (768)
     std::vector<AttnLayer> attns;   // its attention launches in forward order
@@ -373,7 +375,7 @@ int build_topology(mpx_engine* h) {
     if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
     if (h->arch >= MPX_ARCH_CONVNEXT && h->arch < MPX_ARCH_CONVNEXT + 1000) return build_topology_convnext(h);
     if (h->arch >= MPX_ARCH_VIT && h->arch < MPX_ARCH_VIT + 1000) return build_topology_vit(h);
-    if (h->arch >= MPX_ARCH_REGNET && h->arch < MPX_ARCH_REGNET + 1000) return build_topology_regnet(h);
+    if (h->arch >= MPX_ARCH_REGNET && h->arch < MPX_ARCH_REGNET_Y + 1000) return build_topology_regnet(h);
     h->act_elems_per_image = kActElemsPerImage;
     int depths[4];
     // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
@@ -1951,26 +1953,32 @@ int launch_gconv(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipSt
 bool gconvw_accepts(const ConvLayer& L) {
     const int cg = L.groups > 1 ? L.d.cin / L.groups : 0;
     return L.gw && L.groups > 1 && L.d.ksize == 3 && L.d.pad == 1 && (L.d.stride == 1 || L.d.stride == 2) && L.d.cin == L.d.cout && L.d.cin % L.groups == 0 &&
-           (cg == 16 || cg == 24 || cg == 48 || cg == 120) && L.d.k_packed == gconvw_kp(cg) && L.d.cout_pad == L.groups * gconvw_rf(cg) * 16 &&
+           (cg == 16 || cg == 24 || cg == 48 || cg == 56 || cg == 120) && L.d.k_packed == gconvw_kp(cg) && L.d.cout_pad == L.groups * gconvw_rf(cg) * 16 &&
            L.cin_pad >= L.d.cin && L.cin_pad % 8 == 0 && L.cout_store >= L.d.cout && L.cout_store % 8 == 0 && !L.x_pitch && !L.y_pitch;
 }
 
-int launch_gconvw(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
-    if (!gconvw_accepts(L))
-        return fail(h, MPX_E_INTERNAL, "grouped conv: %s is not a 3x3 pad-1 layer of 16, 24, 48 or 120 channels per group in the any-width form", L.d.name);
-    if (p.r_hi || p.y_f32 || p.k1) return fail(h, MPX_E_ARG, "grouped conv: %s takes no residual operand and no fp32 output", L.d.name);
-    const int cg = L.d.cin / L.groups;
-    p.n_tiles_c = L.groups;
-    p.k_per_tap = L.d.cin;      // the layer's width: where the output's pad channels begin
-    const int units = L.groups * gconvw_nch(cg);
+// the launch itself: width -> width in `groups` groups of 16, 24, 48, 56 or 120 channels (the callers check), p complete but for the two fields below
+void gconvw_launch(int width, int groups, ConvParams& p, hipStream_t st) {
+    const int cg = width / groups;
+    p.n_tiles_c = groups;
+    p.k_per_tap = width;        // the layer's width: where the output's pad channels begin
+    const int units = groups * gconvw_nch(cg);
     const int per_wg = 16 * GCONVW_NT;
     const dim3 grid((unsigned)(((long long)p.M + per_wg - 1) / per_wg), (unsigned)((units + GCONVW_WAVES - 1) / GCONVW_WAVES)), block(64 * GCONVW_WAVES);
     switch (cg) {
         case 16: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<16, GCONVW_NT>), grid, block, 0, st, p); break;
         case 24: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<24, GCONVW_NT>), grid, block, 0, st, p); break;
         case 48: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<48, GCONVW_NT>), grid, block, 0, st, p); break;
+        case 56: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<56, GCONVW_NT>), grid, block, 0, st, p); break;
         default: hipLaunchKernelGGL((gconvw3x3_f16x3_kernel<120, GCONVW_NT>), grid, block, 0, st, p); break;
     }
+}
+
+int launch_gconvw(mpx_engine* h, int id, const ConvLayer& L, ConvParams& p, hipStream_t st) {
+    if (!gconvw_accepts(L))
+        return fail(h, MPX_E_INTERNAL, "grouped conv: %s is not a 3x3 pad-1 layer of 16, 24, 48, 56 or 120 channels per group in the any-width form", L.d.name);
+    if (p.r_hi || p.y_f32 || p.k1) return fail(h, MPX_E_ARG, "grouped conv: %s takes no residual operand and no fp32 output", L.d.name);
+    gconvw_launch(L.d.cin, L.groups, p, st);
     return launched(h, id);
 }
 
@@ -2002,7 +2010,7 @@ const TileRow kTiles[] = {
      "the weights-in-registers expanding-1x1 kernel runs 1x1 stride-1 layers with cout % 256 == 0 and cin = 256", 7, false},
     {kGconvTile, launch_gconv, nullptr, "the grouped 3x3 kernel runs grouped layers (a ResNeXt block's conv2) and nothing else", -1, false},
     {kGconvwTile, launch_gconvw, nullptr,
-     "the any-width grouped 3x3 kernel runs grouped layers of 16, 24, 48 or 120 channels per group (a RegNetX block's f.b) and nothing else", -1, false},
+     "the any-width grouped 3x3 kernel runs grouped layers of 16, 24, 48, 56 or 120 channels per group (a RegNetX / RegNetY block's f.b) and nothing else", -1, false},
 };
 
 // Dynamic LDS ceiling of every conv kernel (mpx_create): the kernels of kTiles with their DUAL forms, the stem + pool kernel, the block
@@ -2140,6 +2148,17 @@ int default_tile(const mpx_conv_desc& d) {
 // Launches: one per conv -- proj is a launch of its own in every stage (the K-concatenated dual form reads planes whose pitch is their cin).
 // Buffers: four, sized by the largest map of the network (f.a of block 0 runs at the previous stage's resolution): X the block input, T1
 // f.a's output and then -- dead after f.b -- the block output, T2 f.b's output, T3 proj's output.
+//
+// torchvision RegNetY 800MF .. 8GF: the same trunk with f.se = SqueezeExcitation(w, q) between f.b and f.c in EVERY block, q = round(0.25 w_in)
+// of the BLOCK's input width (32 for block1-0, the previous stage's width for the other stage openers): fc1 / fc2 are 1x1 convs with bias, ReLU
+// behind fc1, sigmoid behind fc2, f.b's output times the gate.  Two launches per block on T2, in place (se_gate_kernel<true>, se_scale_kernel).
+//   name             id     stage widths          depths        group width   groups per stage
+//   regnet_y_800mf   15008  64, 144, 320, 784     1, 3, 8, 2    16            4, 9, 20, 49
+//   regnet_y_1_6gf   15016  48, 120, 336, 888     2, 6, 17, 2   24            2, 5, 14, 37
+//   regnet_y_3_2gf   15032  72, 216, 576, 1512    2, 5, 13, 1   24            3, 9, 24, 63
+//   regnet_y_8gf     15080  224, 448, 896, 2016   2, 4, 10, 1   56            4, 8, 16, 36
+// (regnet_y_400mf has a group width of 8, below the grouped kernel's 16; regnet_y_16gf / _32gf have 112 / 232: 7 / 15 row fragments, no whole
+// number of 4-fragment chunks.  Not served.)
 int build_topology_regnet(mpx_engine* h) {
     struct Row { int id; int widths[4]; int depths[4]; int gw; };
     static const Row rows[] = {
@@ -2148,12 +2167,17 @@ int build_topology_regnet(mpx_engine* h) {
         {MPX_ARCH_REGNET + 16, {72, 168, 408, 912}, {2, 4, 10, 2}, 24},
         {MPX_ARCH_REGNET + 32, {96, 192, 432, 1008}, {2, 6, 15, 2}, 48},
         {MPX_ARCH_REGNET + 80, {80, 240, 720, 1920}, {2, 5, 15, 1}, 120},
+        {MPX_ARCH_REGNET_Y + 8, {64, 144, 320, 784}, {1, 3, 8, 2}, 16},
+        {MPX_ARCH_REGNET_Y + 16, {48, 120, 336, 888}, {2, 6, 17, 2}, 24},
+        {MPX_ARCH_REGNET_Y + 32, {72, 216, 576, 1512}, {2, 5, 13, 1}, 24},
+        {MPX_ARCH_REGNET_Y + 80, {224, 448, 896, 2016}, {2, 4, 10, 1}, 56},
     };
     const Row* R = nullptr;
     for (const Row& r : rows)
         if (r.id == h->arch) R = &r;
     if (!R) return MPX_E_ARG;
     h->regnet = true;
+    h->regnet_y = h->arch >= MPX_ARCH_REGNET_Y;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
     size_t act_max = 0;
     auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu,
@@ -2220,6 +2244,17 @@ int build_topology_regnet(mpx_engine* h) {
             conv_op(c, X, T1, BUF_NONE);
             c = w / gw > 1 ? add_gconvw(p + "f.b.0", p + "f.b.1", w, gw, stride, hcur) : add_conv(p + "f.b.0", p + "f.b.1", w, w, 3, stride, 1, hcur, 1, 0, false);
             conv_op(c, T1, T2, BUF_NONE);
+            if (h->regnet_y) {      // f.se on f.b's output, in place
+                SeLayer E;
+                std::memset(&E.d, 0, sizeof E.d);
+                std::snprintf(E.d.name, sizeof E.d.name, "%sf.se", p.c_str());
+                E.d.channels = w; E.d.pitch = pitch_of(w); E.d.q = (int)std::lround(0.25 * cin); E.d.hw = hout;
+                E.relu = true;
+                h->ses.push_back(E);
+                h->se_pitch_max = std::max(h->se_pitch_max, E.d.pitch);
+                h->ops.push_back(Op{OP_SEGATE, (int)h->ses.size() - 1, T2, BUF_NONE, BUF_NONE, hout, E.d.pitch, BUF_NONE});
+                h->ops.push_back(Op{OP_SESCALE, (int)h->ses.size() - 1, T2, T2, BUF_NONE, hout, E.d.pitch, BUF_NONE});
+            }
             c = add_conv(p + "f.c.0", p + "f.c.1", w, w, 1, 1, 0, hout, 1, 1, false);
             conv_op(c, T2, T1, res);        // T1 is dead after f.b
             X = T1;
@@ -2686,9 +2721,13 @@ int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, int k, hipStream_t 
 size_t se_gate_lds(int pitch, int q) { return ((size_t)se_gate_slices(pitch) * pitch + pitch + q) * sizeof(float); }
 
 // one se_gate_kernel launch, one workgroup per image; `k` = the engine's SE layer it runs for (profile record), -1 from the stand-alone entry
-int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, int k, hipStream_t st) {
+// relu: fc1's activation is ReLU (a RegNetY block's gate), not SiLU (EfficientNet's)
+int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, int k, bool relu, hipStream_t st) {
     ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubSeGate - k : -1);
-    hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)B), dim3(256), se_gate_lds(p.pitch, p.q), st, p);
+    if (relu)
+        hipLaunchKernelGGL(se_gate_kernel<true>, dim3((unsigned)B), dim3(256), se_gate_lds(p.pitch, p.q), st, p);
+    else
+        hipLaunchKernelGGL(se_gate_kernel<false>, dim3((unsigned)B), dim3(256), se_gate_lds(p.pitch, p.q), st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -3283,7 +3322,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit || h->regnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT and RegNetX stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit || h->regnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT, RegNetX and RegNetY stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -3861,22 +3900,33 @@ int mpx_dwconv_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const
     return launch_mbdw(h, p, ksize, stride, -1, as_stream(stream));
 }
 
-int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
-                int B, int hw, int pitch, int q, void* stream) {
+// mpx_se_gate / mpx_se_gate_relu: one set of argument checks, the fc1 activation apart
+static int se_gate_entry(mpx_engine* h, const char* who, bool relu, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2,
+                  const float* b2, float* gate, int B, int hw, int pitch, int q, void* stream) {
     if (!h) return MPX_E_ARG;
     auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
-    if (!in_hi || !in_lo || !w1 || !b1 || !w2 || !b2 || !gate) return fail(h, MPX_E_ARG, "se_gate: null pointer");
-    if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7) || q <= 0) return fail(h, MPX_E_ARG, "se_gate: B > 0, hw > 0, pitch a positive multiple of 8, q > 0");
+    if (!in_hi || !in_lo || !w1 || !b1 || !w2 || !b2 || !gate) return fail(h, MPX_E_ARG, "%s: null pointer", who);
+    if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7) || q <= 0) return fail(h, MPX_E_ARG, "%s: B > 0, hw > 0, pitch a positive multiple of 8, q > 0", who);
     if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) || misaligned(gate))
-        return fail(h, MPX_E_ARG, "se_gate: every pointer must be 16-byte aligned");
-    if (se_gate_lds(pitch, q) > 64 * 1024) return fail(h, MPX_E_ARG, "se_gate: pitch %d and q %d need more than 64 KB of LDS", pitch, q);
+        return fail(h, MPX_E_ARG, "%s: every pointer must be 16-byte aligned", who);
+    if (se_gate_lds(pitch, q) > 64 * 1024) return fail(h, MPX_E_ARG, "%s: pitch %d and q %d need more than 64 KB of LDS", who, pitch, q);
     SeGateParams p;
     std::memset(&p, 0, sizeof p);
     p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo;
     p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.gate = gate;
     p.hw = hw; p.pitch = pitch; p.q = q;
     MPX_SET_DEVICE(h);
-    return launch_se_gate(h, p, B, -1, as_stream(stream));
+    return launch_se_gate(h, p, B, -1, relu, as_stream(stream));
+}
+
+int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                int B, int hw, int pitch, int q, void* stream) {
+    return se_gate_entry(h, "se_gate", false, in_hi, in_lo, w1, b1, w2, b2, gate, B, hw, pitch, q, stream);
+}
+
+int mpx_se_gate_relu(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2,
+                     float* gate, int B, int hw, int pitch, int q, void* stream) {
+    return se_gate_entry(h, "se_gate_relu", true, in_hi, in_lo, w1, b1, w2, b2, gate, B, hw, pitch, q, stream);
 }
 
 int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
@@ -3897,11 +3947,61 @@ int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const floa
     return launch_se_scale(h, p, -1, as_stream(stream));
 }
 
+int mpx_pack_gconvw_weights(int width, int groups, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
+                            uint16_t* w_hi, uint16_t* w_lo, float* scale, float* shift) {
+    if (width <= 0 || groups <= 0 || width % groups || !w || !w_hi || !w_lo || !scale || !shift) return MPX_E_ARG;
+    const int cg = width / groups;
+    if (cg != 16 && cg != 24 && cg != 48 && cg != 56 && cg != 120) return MPX_E_ARG;
+    mpx_conv_desc d;
+    std::memset(&d, 0, sizeof d);
+    d.cin = d.cout = width; d.ksize = 3; d.pad = 1; d.stride = 1;
+    d.k_packed = gconvw_kp(cg);
+    d.cout_pad = groups * gconvw_rf(cg) * 16;
+    return pack_gconvw_weights(&d, groups, w, gamma, beta, mean, var, eps, w_hi, w_lo, scale, shift);
+}
+
+int mpx_gconvw3x3_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* scale, const float* shift,
+                         void* out_hi, void* out_lo, int B, int hin, int width, int groups, int in_pitch, int out_pitch, int stride, int relu,
+                         void* stream) {
+    if (!h) return MPX_E_ARG;
+    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (!in_hi || !in_lo || !w_hi || !w_lo || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "gconvw3x3: null pointer");
+    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w_hi) || misaligned(w_lo) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) ||
+        misaligned(out_lo))
+        return fail(h, MPX_E_ARG, "gconvw3x3: every pointer must be 16-byte aligned");
+    if (B <= 0 || hin <= 0 || width <= 0 || groups <= 0 || width % groups || (stride != 1 && stride != 2))
+        return fail(h, MPX_E_ARG, "gconvw3x3: B > 0, hin > 0, width a positive multiple of groups > 0, stride 1 or 2");
+    const int cg = width / groups;
+    if (cg != 16 && cg != 24 && cg != 48 && cg != 56 && cg != 120)
+        return fail(h, MPX_E_ARG, "gconvw3x3: %d channels per group; the kernel has 16, 24, 48, 56 and 120", cg);
+    if (in_pitch < width || (in_pitch & 7) || out_pitch < width || (out_pitch & 7))
+        return fail(h, MPX_E_ARG, "gconvw3x3: both pitches must be multiples of 8 and at least the width %d", width);
+    const int hout = (hin - 1) / stride + 1;
+    if ((long long)B * hin * hin > 0x7fffffffLL || (long long)B * hout * hout > 0x7fffffffLL) return fail(h, MPX_E_ARG, "gconvw3x3: batch too large for 32-bit pixel indices");
+    ConvParams p;
+    std::memset(&p, 0, sizeof p);
+    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.w_hi = (const half_t*)w_hi; p.w_lo = (const half_t*)w_lo;
+    p.scale = scale; p.shift = shift; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.hin = hin; p.win = hin; p.pix_stride = in_pitch; p.ho = hout; p.wo = hout;
+    p.kh = 3; p.kw = 3; p.stride = stride; p.pad = 1;
+    p.ktot = gconvw_kp(cg); p.cout = out_pitch; p.M = B * hout * hout; p.relu = relu ? 1 : 0;
+    MPX_SET_DEVICE(h);
+    h->last_kernels = 0;
+    gconvw_launch(width, groups, p, as_stream(stream));
+    return launched(h, kGconvwTile);
+}
+
 int mpx_num_se(const mpx_engine* h) { return h ? (int)h->ses.size() : MPX_E_ARG; }
 
 int mpx_se_info(const mpx_engine* h, int k, mpx_se_desc* out) {
     if (!h || !out || k < 0 || k >= (int)h->ses.size()) return MPX_E_ARG;
     *out = h->ses[k].d;
+    return 0;
+}
+
+int mpx_se_act(const mpx_engine* h, int k, int* act) {
+    if (!h || !act || k < 0 || k >= (int)h->ses.size()) return MPX_E_ARG;
+    *act = h->ses[k].relu ? 1 : 0;
     return 0;
 }
 
@@ -4204,7 +4304,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 p.x_hi = hi(o.in); p.x_lo = lo(o.in);
                 p.w1 = E.w1; p.b1 = E.b1; p.w2 = E.w2; p.b2 = E.b2; p.gate = h->se_gate;
                 p.hw = E.d.hw * E.d.hw; p.pitch = E.d.pitch; p.q = E.d.q;
-                rc = launch_se_gate(h, p, B, o.conv, as_stream(stream));
+                rc = launch_se_gate(h, p, B, o.conv, E.relu, as_stream(stream));
                 break;
             }
             case OP_SESCALE: {

@@ -1,8 +1,8 @@
 // mpx_gconvw.h -- grouped 3x3 conv (pad 1, stride 1 or 2) + BatchNorm + ReLU for ANY group count and any group width that is a multiple
-// of 8, on planes whose pixel pitch may exceed the layer's width, gfx950: the f.b of a RegNetX block (tile id 18).
+// of 8, on planes whose pixel pitch may exceed the layer's width, gfx950: the f.b of a RegNetX / RegNetY block (tile id 18).
 //
-// The layer is width -> width in G = width / CG groups of CG channels (16, 24, 48 or 120 in torchvision's RegNetX up to 8GF; G is whatever the
-// stage width gives: 2 .. 42, 7, 17, 25 and 38 among them).  Input pixels are x_pitch = p.pix_stride channels apart, output pixels p.cout
+// The layer is width -> width in G = width / CG groups of CG channels (16, 24, 48 or 120 in torchvision's RegNetX up to 8GF, 16, 24 or 56 in its
+// RegNetY from 800MF to 8GF; G is whatever the stage width gives: 2 .. 63, 7, 17, 25, 37 and 49 among them; the stand-alone entry also runs G = 1).  Input pixels are x_pitch = p.pix_stride channels apart, output pixels p.cout
 // channels, both >= width and multiples of 8.  Per group g the conv is mpx_gconv.h's small GEMM
 //   D[co][pixel] = sum_k W[co][k] * X[pixel][k],   k = (ky, kx, ci), ci fastest over the group's CG channels, K = 9 * CG padded to a multiple of 32
 // on v_mfma_f32_16x16x32_f16, the K steps ascending, each step the three products W_hi*X_lo, W_lo*X_hi, W_hi*X_hi in that order into one fp32
@@ -10,13 +10,14 @@
 // the packed planes of such a layer are the same planes.
 //
 // Against mpx_gconv.h:
-//   - a group has RF = ceil(CG / 16) row fragments; the rows >= CG of the last one (CG = 24, 120) are exact-zero weights in the packed planes and
+//   - a group has RF = ceil(CG / 16) row fragments; the rows >= CG of the last one (CG = 24, 56, 120) are exact-zero weights in the packed planes and
 //     their accumulator quads are never stored (CG % 8 == 0: a lane's quad of 4 channels lies wholly inside or outside the group);
-//   - K is the flattened (tap, ci) index, so a 32-wide K step may straddle taps (CG = 24, 48, 120); a lane's 8 elements are still 8 consecutive
+//   - K is the flattened (tap, ci) index, so a 32-wide K step may straddle taps (CG = 24, 48, 56, 120); a lane's 8 elements are still 8 consecutive
 //     channels of ONE tap (CG % 8 == 0), and the padding behind tap 8 is an operand of exact zeros by the same clamp-and-AND as a tap outside
 //     the map -- bit arithmetic, no branch around a load;
 //   - the unit of work of a wave is (NT = 2 tiles of 16 consecutive output pixels) x (one group) x (a CHUNK of at most 4 row fragments): CG = 120
-//     is 8 fragments = 2 chunks, so that a wave's double-buffered A fragments stay at 64 VGPRs (164 VGPRs in all, no scratch).  Unit u = group * NCH + chunk; the 4 waves of a workgroup take 4
+//     is 8 fragments = 2 chunks, so that a wave's double-buffered A fragments stay at 64 VGPRs (164 VGPRs in all, no scratch); CG = 56 is 4 fragments = one whole
+//     chunk with the same 64 (142 VGPRs in all, no scratch; K = 504 padded to 512: its last K step holds 8 padding elements behind tap 8).  Unit u = group * NCH + chunk; the 4 waves of a workgroup take 4
 //     consecutive units of the same pixels -- the chunks of one group, then the neighbouring groups -- so the pixel lines they read are shared
 //     in L1.  The last workgroup in y is ragged for any G: a wave whose unit does not exist exits, wave-uniformly;
 //   - the wave of unit 0 also writes the output's pad channels [width, p.cout) of its pixels as +0 in both planes: the arena's buffers are
@@ -34,7 +35,7 @@ constexpr int GCONVW_WAVES = 4;     // units per workgroup
 constexpr int GCONVW_CHUNK = 4;     // row fragments per unit, at most
 
 __host__ __device__ constexpr int gconvw_rf(int cg) { return (cg + 15) / 16; }
-__host__ __device__ constexpr int gconvw_kp(int cg) { return (9 * cg + 31) / 32 * 32; }     // 160, 224, 448, 1088 for CG = 16, 24, 48, 120
+__host__ __device__ constexpr int gconvw_kp(int cg) { return (9 * cg + 31) / 32 * 32; }     // 160, 224, 448, 512, 1088 for CG = 16, 24, 48, 56, 120
 __host__ __device__ constexpr int gconvw_nch(int cg) { return (gconvw_rf(cg) + GCONVW_CHUNK - 1) / GCONVW_CHUNK; }
 
 // Element index of weight (row r of group g, k) within a packed plane

@@ -132,7 +132,8 @@ __global__ __launch_bounds__(256) void dwconv_bn_act_kernel(const MbDwParams p) 
 }
 
 // ------------------------------------------------------------------------------------------
-// The SE gate of one image per workgroup: gate = sigmoid(fc2(silu(fc1(mean over the hw pixels of x)))), planes [B][hw][pitch] -> f32
+// The SE gate of one image per workgroup: gate = sigmoid(fc2(act(fc1(mean over the hw pixels of x)))), act = SiLU (EfficientNet) or ReLU (RegNetY:
+// the template parameter below), planes [B][hw][pitch] -> f32
 // [B][pitch].  256 threads, three phases with a barrier between them; every summation order is a fixed function of (hw, pitch, q), never of
 // B, the grid or timing, so an image's gate has the same bits alone and anywhere in any batch.  No atomics.
 //   POOL.  G = pitch / 8 groups of 8 channels.  S = max(1, 256 / G) slices: thread t < S * G takes group t % G and the pixels s, s + S,
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(256) void dwconv_bn_act_kernel(const MbDwParams p) 
 //       groups t, t + 256, ...  Then pooled[c] = (part[0][c] + part[1][c] + ... + part[S - 1][c]) / hw, slices ascending, one division.
 //       Consecutive threads read consecutive 16-byte units: a wave reads whole pixels.
 //   FC1.  One wave per output j = wave, wave + 4, ... < q: lane l sums fma(w1[j][c], pooled[c], .) over c = l, l + 64, ... ascending, the 64
-//       lane sums are folded by the xor butterfly 32, 16, 8, 4, 2, 1 (the same tree in every lane), and s1[j] = silu(b1[j] + sum).
+//       lane sums are folded by the xor butterfly 32, 16, 8, 4, 2, 1 (the same tree in every lane), and s1[j] = act(b1[j] + sum): silu, or ReLU as `v <= 0 ? 0 : v`.
 //   FC2.  Thread t takes the channels c = t, t + 256, ...: z = fma(w2[j][c], s1[j], z) over j ascending from z = 0, gate[c] = 1 / (1 +
 //       expf(-(b2[c] + z))).
 // w1: f32 [q][pitch] (fc1.weight, zero columns on the pad channels); b1: f32 [q]; w2: f32 [q][pitch], j-major (w2[j][c] = fc2.weight[c][j]:
@@ -164,6 +165,9 @@ struct SeGateParams {
 
 __host__ __device__ inline int se_gate_slices(int pitch) { return (pitch >> 3) >= 256 ? 1 : 256 / (pitch >> 3); }
 
+// RELU = false: the gate above (EfficientNet).  RELU = true: fc1 ends in ReLU instead of SiLU -- s1[j] = (v <= 0 ? 0 : v) with v = b1[j] + sum, the
+// project's ReLU form -- which is torchvision's default SqueezeExcitation and the gate of a RegNetY block; POOL and FC2 are the same code.
+template <bool RELU>
 __global__ __launch_bounds__(256) void se_gate_kernel(const SeGateParams p) {
     extern __shared__ __attribute__((aligned(16))) float se_lds[];
     const int G = p.pitch >> 3, S = se_gate_slices(p.pitch);
@@ -207,7 +211,10 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const SeGateParams p) {
         for (int c = lane; c < p.pitch; c += 64) sum = __fmaf_rn(wr[c], pooled[c], sum);
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
-        if (lane == 0) s1[j] = silu_f32(p.b1[j] + sum);
+        if (lane == 0) {
+            const float v = p.b1[j] + sum;
+            s1[j] = RELU ? (v <= 0.f ? 0.f : v) : silu_f32(v);
+        }
     }
     __syncthreads();
     // ---- fc2

@@ -46,6 +46,9 @@ CONVNEXT_LN_EPS = 1e-6      # torchvision convnext.py: every LayerNorm / LayerNo
 ARCH_IDS.update({"vit_b_16": 13016, "vit_b_32": 13032})
 # torchvision's RegNetX networks up to 8 GF (MPX_ARCH_REGNET + ten times the GF figure): a bottleneck whose 3x3 is grouped by a fixed group width
 ARCH_IDS.update({"regnet_x_400mf": 14004, "regnet_x_800mf": 14008, "regnet_x_1_6gf": 14016, "regnet_x_3_2gf": 14032, "regnet_x_8gf": 14080})
+# torchvision's RegNetY networks from 800 MF to 8 GF (MPX_ARCH_REGNET_Y + ten times the GF figure): RegNetX's trunk with a Squeeze-and-Excitation
+# gate (ReLU, sigmoid) in every block.  regnet_y_400mf (group width 8) and regnet_y_16gf / regnet_y_32gf (group widths 112 / 232) are not served
+ARCH_IDS.update({"regnet_y_800mf": 15008, "regnet_y_1_6gf": 15016, "regnet_y_3_2gf": 15032, "regnet_y_8gf": 15080})
 VIT_LN_EPS = 1e-6           # torchvision vision_transformer.py: norm_layer = partial(nn.LayerNorm, eps=1e-6)
 VIT_LAYER_PREFIX = "encoder.layers."
 
@@ -165,7 +168,8 @@ class MaskedForwardEngine:
         ViT-B/32 slot 2.2 MB (50 tokens); both keep the default of 512 (3.6 / 1.5 GB with the packed weights).
         A RegNetX slot holds four split-fp16 activation buffers of the network's largest map -- 112x112x32 (400MF: 7.3 MB with the input
         staging), 112x112x64 (800MF: 13.7 MB) or 112x112x96 (1.6GF, 3.2GF, 8GF: block1-0.f.a's output at a pitch of 96, 20.1 MB) -- and keeps
-        the default of 512 (3.7 / 7.0 / 10.3 GB).
+        the default of 512 (3.7 / 7.0 / 10.3 GB).  A RegNetY slot follows the same rule -- 112x112x64 (800MF), 112x112x64 (1.6GF: 48 channels at a
+        pitch of 64), 112x112x96 (3.2GF) or 112x112x224 (8GF: 46 MB, 23.6 GB at 512) -- plus one gate row of the widest stage, and keeps 512 too.
         transform_input: torchvision's GoogLeNet flag (on in its pretrained model): a per-channel affine re-normalisation behind the
         caller's Normalize, after which a masked pixel is no longer 0.  The engine stages masked pixels as exact zeros and does not serve it:
         True raises ValueError; False, the default, is models.googlenet() without weights.
@@ -176,7 +180,7 @@ class MaskedForwardEngine:
         stem otherwise (a BO round's 28 .. 118 windows); "conv": always
         K0 into the input staging, then the MFMA stem + max pool inside the forward (rounds 1-3).  stage_masks() is always K0."""
         if arch not in ARCH_IDS:
-            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d, ConvNeXt-Tiny / -Small, ViT-B/16 / ViT-B/32 and RegNetX-400MF .. -8GF: %s)" % (arch, sorted(ARCH_IDS)))
+            raise ValueError("unsupported arch %r (torchvision ResNets, VGGs, AlexNet, DenseNets, MobileNetV2, SqueezeNet 1.1, GoogLeNet, ShuffleNetV2s and EfficientNet-B0 and the reference's small networks, and torchvision's ResNeXt-50 32x4d / ResNeXt-101 32x8d, ConvNeXt-Tiny / -Small, ViT-B/16 / ViT-B/32, RegNetX-400MF .. -8GF and RegNetY-800MF .. -8GF: %s)" % (arch, sorted(ARCH_IDS)))
         if transform_input:
             raise ValueError("%s: transform_input=True is not served -- the engine stages masked pixels as exact zeros, and torchvision's "
                              "re-normalisation behind the caller's Normalize would move them (INTEGRATION.md)" % arch)
@@ -241,12 +245,17 @@ class MaskedForwardEngine:
             ad = _lib.AttnDesc()
             _lib.check(h, self._lib.mpx_attn_info(h, k, C.byref(ad)), "mpx_attn_info")
             self.attns.append(ad)
-        self.ses = []           # the Squeeze-and-Excitation layers (EfficientNet-B0), a list of their own as well
+        self.ses = []           # the Squeeze-and-Excitation layers (EfficientNet-B0, RegNetY), a list of their own as well
         for k in range(self._lib.mpx_num_se(h)):
             sd_ = _lib.SeDesc()
             _lib.check(h, self._lib.mpx_se_info(h, k, C.byref(sd_)), "mpx_se_info")
             self.ses.append(sd_)
-        self.groups = []        # groups per conv layer: 32 on a ResNeXt block's conv2 (weight [cout][cin / 32][3][3]), width / group width on a RegNetX block's f.b, 1 everywhere else
+        self.se_acts = []       # per SE layer: fc1's activation, 0 SiLU (EfficientNet-B0), 1 ReLU (RegNetY)
+        for k in range(len(self.ses)):
+            a = C.c_int()
+            _lib.check(h, self._lib.mpx_se_act(h, k, C.byref(a)), "mpx_se_act")
+            self.se_acts.append(int(a.value))
+        self.groups = []        # groups per conv layer: 32 on a ResNeXt block's conv2 (weight [cout][cin / 32][3][3]), width / group width on a RegNetX / RegNetY block's f.b, 1 everywhere else
         for i in range(len(self.layers)):
             gr = C.c_int()
             _lib.check(h, self._lib.mpx_conv_groups(h, i, C.byref(gr)), "mpx_conv_groups")
@@ -273,7 +282,7 @@ class MaskedForwardEngine:
     def has_stem_table(self):
         """The stem by superposition needs the ImageNet ResNets' 7x7 stem + max pool; VGG, AlexNet, DenseNet (whose stem has that shape, but
         which keeps no table), MobileNetV2, SqueezeNet 1.1, GoogLeNet (that stem shape again, but another pool behind it), the ShuffleNetV2s,
-        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool), the ViTs (a 16x16 / 32x32 patchify stem), the RegNetXs (a 3x3
+        EfficientNet-B0, the ConvNeXts (a 4x4 stride-4 patchify stem, no pool), the ViTs (a 16x16 / 32x32 patchify stem), the RegNetXs and RegNetYs (a 3x3
         stride-2 stem, no pool) and the small networks stage through K0 only."""
         return not self.small and not getattr(self, "arch", "").startswith(("vgg", "alexnet", "densenet", "mobilenet", "squeezenet", "googlenet", "shufflenet", "efficientnet", "convnext", "vit_", "regnet"))
 
@@ -330,7 +339,7 @@ class MaskedForwardEngine:
         load with the convs, and `only` takes their names ("features.2.conv.1.0", "stage2.0.branch1.0") too.  A ShuffleNetV2 state_dict loads
         as saved: the engine places the columns of a layer that reads a two-half stage map itself.  EfficientNet-B0's depthwise and
         Squeeze-and-Excitation layers load with the convs too (fc1 / fc2 weight and bias of every `features.S.B.block.J`), and `only` takes
-        the SE layers' names as well."""
+        the SE layers' names as well; so do a RegNetY's (`trunk_output.blockS.blockS-J.f.se`)."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         if eps is None:
             eps = default_bn_eps(self.arch)

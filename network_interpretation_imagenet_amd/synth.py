@@ -641,10 +641,58 @@ def make_regnet_state_dict(arch, seed=7):
     return sd
 
 
+# torchvision's RegNetY networks from 800 MF to 8 GF: (stage widths, stage depths, group width, gain of every f.c BatchNorm) as REGNET_ARCHS --
+# what BlockParams.from_init_params makes of (depth, w_0, w_a, w_m, group width) (tests/regnety_ref.py derives them from that rule).  The gates
+# average about a half, which takes that factor off every block's update: the f.c gains are those that put the fp64 softmax peak of the rows
+# tests/regnety_ref.py scores inside [0.05, 0.95] (tests/test_regnety_cpu.py).
+REGNET_Y_ARCHS = {
+    "regnet_y_800mf": ((64, 144, 320, 784), (1, 3, 8, 2), 16, 0.85),
+    "regnet_y_1_6gf": ((48, 120, 336, 888), (2, 6, 17, 2), 24, 0.55),
+    "regnet_y_3_2gf": ((72, 216, 576, 1512), (2, 5, 13, 1), 24, 0.6),
+    "regnet_y_8gf": ((224, 448, 896, 2016), (2, 4, 10, 1), 56, 0.85),
+}
+REGNET_Y_SE_GAIN = 4.0      # fc2 is N(0, sqrt(REGNET_Y_SE_GAIN / q)) with bias N(0, 0.5), as EfficientNet's: the gates spread over (0, 1)
+
+
+def make_regnet_y_state_dict(arch, seed=7):
+    """OrderedDict with the key set, order and shapes of models.regnet_y_800mf() .. regnet_y_8gf(): make_regnet_state_dict's, and per block,
+    between f.b.1.* and f.c.0.weight, f.se.fc1.weight [q][w][1][1], f.se.fc1.bias [q], f.se.fc2.weight [w][q][1][1], f.se.fc2.bias [w] with
+    q = round(0.25 w_in) of the block's input width.  fc1 is N(0, sqrt(2 / w)) with bias N(0, 0.1) -- the pooled f.b output is >= 0, so its
+    pre-activations take both signs through the weights' --, fc2 N(0, sqrt(REGNET_Y_SE_GAIN / q)) with bias N(0, 0.5)."""
+    widths, depths, gw, last = REGNET_Y_ARCHS[arch]
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    _conv(sd, "stem.0", 3, 32, 3, g)
+    _bn(sd, "stem.1", 32, g)
+    cin = 32
+    for s, (w, d) in enumerate(zip(widths, depths)):
+        cg = min(gw, w)
+        for j in range(d):
+            p = "trunk_output.block%d.block%d-%d." % (s + 1, s + 1, j)
+            q = int(round(0.25 * cin))
+            if j == 0:
+                _conv(sd, p + "proj.0", cin, w, 1, g)
+                _bn(sd, p + "proj.1", w, g)
+            _conv(sd, p + "f.a.0", cin, w, 1, g)
+            _bn(sd, p + "f.a.1", w, g)
+            _conv(sd, p + "f.b.0", cg, w, 3, g)
+            _bn(sd, p + "f.b.1", w, g)
+            sd[p + "f.se.fc1.weight"] = torch.randn(q, w, 1, 1, generator=g) * (2.0 / w) ** 0.5
+            sd[p + "f.se.fc1.bias"] = torch.randn(q, generator=g) * 0.1
+            sd[p + "f.se.fc2.weight"] = torch.randn(w, q, 1, 1, generator=g) * (REGNET_Y_SE_GAIN / q) ** 0.5
+            sd[p + "f.se.fc2.bias"] = torch.randn(w, generator=g) * 0.5
+            _conv(sd, p + "f.c.0", w, w, 1, g)
+            _bn(sd, p + "f.c.1", w, g, last=last)
+            cin = w
+    sd["fc.weight"] = torch.randn(1000, cin, generator=g) * (FC_GAIN / cin ** 0.5)
+    sd["fc.bias"] = torch.randn(1000, generator=g) * 0.1
+    return sd
+
+
 def make_state_dict(arch, seed=7):
     """OrderedDict of f32 CPU tensors with the torchvision ResNet (or VGG: make_vgg_state_dict, AlexNet: make_alexnet_state_dict,
     DenseNet: make_densenet_state_dict, MobileNetV2: make_mobilenetv2_state_dict, SqueezeNet 1.1: make_squeezenet_state_dict, GoogLeNet:
-    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict, ConvNeXt: make_convnext_state_dict, ViT: make_vit_state_dict, RegNetX: make_regnet_state_dict) key set."""
+    make_googlenet_state_dict, ShuffleNetV2: make_shufflenet_state_dict, EfficientNet-B0: make_efficientnet_state_dict, ResNeXt: make_resnext_state_dict, ConvNeXt: make_convnext_state_dict, ViT: make_vit_state_dict, RegNetX: make_regnet_state_dict, RegNetY: make_regnet_y_state_dict) key set."""
     if arch == "efficientnet_b0":
         return make_efficientnet_state_dict(seed)
     if arch in CONVNEXT_DEPTHS:
@@ -655,6 +703,8 @@ def make_state_dict(arch, seed=7):
         return make_resnext_state_dict(arch, seed)
     if arch in REGNET_ARCHS:
         return make_regnet_state_dict(arch, seed)
+    if arch in REGNET_Y_ARCHS:
+        return make_regnet_y_state_dict(arch, seed)
     if arch in SHUFFLENET_WIDTHS:
         return make_shufflenet_state_dict(arch, seed)
     if arch == "googlenet":

@@ -1,0 +1,286 @@
+"""RegNetY-800MF .. -8GF without a GPU: the table of the four networks held three ways (torchvision's BlockParams rule on the generating
+parameters, the restatement's topology, the published parameter counts), the synthetic state_dict with torchvision's keys, order and shapes,
+the arch ids and the ids that stay refused, the header / binding / library, the conditions on exactly the rows the GPU test scores
+(tests/regnety_ref.py E2E_CASES) -- the fp64 top-two margin, the softmax peak, and that the gates are live on them --, and the numpy emulation
+of the group-width-56 arithmetic of csrc/mpx_gconvw.h with the constant of its per-element bound (tests/regnety_draws.py).
+
+Surveyed with the gains of synth.REGNET_Y_ARCHS (fp64, rows of E2E_CASES; smallest top-two margin, softmax peak, smallest move of a score when
+every gate is replaced by 0.5):
+  regnet_y_800mf (f.c gain 0.85)  felz 4 rows: margin 0.0143, peak 0.076 .. 0.530, move 0.0475;  grid 2 rows: margin 0.973, peak 0.633 .. 0.677, move 0.629
+  regnet_y_1_6gf (0.55)           felz 4 rows: margin 0.440,  peak 0.113 .. 0.527, move 0.0256;  grid 2 rows: margin 0.295, peak 0.422 .. 0.458, move 0.0676
+  regnet_y_3_2gf (0.6)            felz 4 rows: margin 0.0816, peak 0.083 .. 0.488, move 0.0542;  grid 2 rows: margin 1.20,  peak 0.725 .. 0.787, move 0.717
+  regnet_y_8gf   (0.85)           felz 3 rows: margin 0.120,  peak 0.077 .. 0.825, move 0.0421
+The gates average about a half, so the gains are higher than RegNetX's: at 0.6 the 800MF felz peaks fall to 0.021, at 0.7 the 1.6GF and 3.2GF
+grid rows saturate (peak 0.97 / 0.998), at 0.9 an 8GF row moves by 2e-3 only.
+"""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import regnet_ref as xref
+import regnety_draws as yd
+import regnety_ref as ref
+import test_regnet_bounds_cpu as xb       # the packer's and the kernel's arithmetic in numpy (pack, emulate): generic in the group width
+from network_interpretation_imagenet_amd import _lib, engine, synth
+from oracle import scorer
+
+ARCHS = ref.ARCHS
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# the issue's table: name -> (id, (depth, w_0, w_a, w_m, group width), stage widths, stage depths, parameters)
+ISSUE_TABLE = {
+    "regnet_y_800mf": (15008, (14, 56, 38.84, 2.4, 16), (64, 144, 320, 784), (1, 3, 8, 2), 6432512),
+    "regnet_y_1_6gf": (15016, (27, 48, 20.71, 2.65, 24), (48, 120, 336, 888), (2, 6, 17, 2), 11202430),
+    "regnet_y_3_2gf": (15032, (21, 80, 42.63, 2.66, 24), (72, 216, 576, 1512), (2, 5, 13, 1), 19436338),
+    "regnet_y_8gf": (15080, (17, 192, 76.82, 2.19, 56), (224, 448, 896, 2016), (2, 4, 10, 1), 39381472),
+}
+
+
+def _bn_keys(prefix, c):
+    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,))]
+
+
+def _expected_keys(arch):
+    """models.<arch>().state_dict() without num_batches_tracked: key -> shape, written out from the table."""
+    _id, widths, depths, _gw, groups, _p, _n, _k = ref.TABLE[arch]
+    out = [("stem.0.weight", (32, 3, 3, 3))] + _bn_keys("stem.1", 32)
+    cin = 32
+    for s in range(4):
+        w = widths[s]
+        for j in range(depths[s]):
+            p = "trunk_output.block%d.block%d-%d." % (s + 1, s + 1, j)
+            q = cin // 4
+            if j == 0:
+                out += [(p + "proj.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "proj.1", w)
+            out += [(p + "f.a.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "f.a.1", w)
+            out += [(p + "f.b.0.weight", (w, w // groups[s], 3, 3))] + _bn_keys(p + "f.b.1", w)
+            out += [(p + "f.se.fc1.weight", (q, w, 1, 1)), (p + "f.se.fc1.bias", (q,)), (p + "f.se.fc2.weight", (w, q, 1, 1)), (p + "f.se.fc2.bias", (w,))]
+            out += [(p + "f.c.0.weight", (w, w, 1, 1))] + _bn_keys(p + "f.c.1", w)
+            cin = w
+    return out + [("fc.weight", (1000, cin)), ("fc.bias", (1000,))]
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_generating_parameters_widths_depths_and_parameter_count_agree(arch):
+    """The three columns of the table: the width rule on the generating parameters gives the widths and depths, and the topology they give
+    has the published parameter count (counted from the conv and SE lists and from the synthetic state_dict)."""
+    arch_id, init, widths, depths, n_params = ISSUE_TABLE[arch]
+    assert ref.INIT[arch] == init and ref.TABLE[arch][:3] == (arch_id, widths, depths) and ref.TABLE[arch][5] == n_params
+    r_widths, r_depths, r_gws = ref.block_params(arch)
+    assert (r_widths, r_depths) == (widths, depths) and sum(depths) == init[0]
+    gw = init[4]
+    assert r_gws == (gw,) * 4 and ref.TABLE[arch][3] == gw and ref.TABLE[arch][4] == tuple(w // gw for w in widths)
+    assert all(w % 8 == 0 and w % gw == 0 for w in widths)
+    convs, ses = ref.topology(arch), ref.se_layers(arch)
+    assert len(convs) == ref.TABLE[arch][6] == 1 + 3 * sum(depths) + 4 + 1 and len(ses) == ref.TABLE[arch][7] == sum(depths)
+    assert all(len(c[0]) < 48 and len(c[1]) < 48 for c in convs) and all(len(s[0]) < 48 for s in ses)
+    fb = [c for c in convs if c[0].endswith(".f.b.0")]
+    assert [c[11] for c in fb] == [w // gw for w, d in zip(widths, depths) for _ in range(d)] and min(c[11] for c in fb) > 1
+    # q = round(0.25 w_in) of the BLOCK's input: 32 / 4 in block1-0, the previous stage's width / 4 in the other stage openers
+    w_in = [32] + [w for w, d in zip(widths, depths) for _ in range(d)][:-1]
+    assert [s[3] for s in ses] == [int(round(0.25 * w)) for w in w_in] == [w // 4 for w in w_in]
+    assert ses[0][3] == 8 and [s[1:3] for s in ses] == [(c[3], ref.pitch(c[3])) for c in fb] and [s[4] for s in ses] == [c[8] for c in fb]
+    assert ref.params(arch) == n_params
+    sd = synth.make_state_dict(arch)
+    assert sum(v.numel() for k, v in sd.items() if k.endswith((".weight", ".bias"))) == n_params
+    print("%s: %d parameters, %d MACs per forward, %d convs, %d SE layers" % (arch, n_params, ref.macs(arch), len(convs), len(ses)))
+    assert engine.ARCH_IDS[arch] == arch_id == 15000 + {"800mf": 8, "1_6gf": 16, "3_2gf": 32, "8gf": 80}[arch[len("regnet_y_"):]]
+
+
+def test_the_width_rule_is_regnetxs_and_the_group_widths_are_the_kernels():
+    """block_params is regnet_ref's rule: on RegNetX's generating parameters it gives RegNetX's table.  Group widths {16, 24, 56}; the padded
+    widths of this family."""
+    saved = dict(ref.INIT)
+    try:
+        for arch in xref.ARCHS:
+            ref.INIT[arch] = xref.INIT[arch]
+            assert ref.block_params(arch) == xref.block_params(arch)
+    finally:
+        ref.INIT.clear()
+        ref.INIT.update(saved)
+    assert {c[2] // c[11] for a in ARCHS for c in ref.topology(a) if c[11] > 1} == {16, 24, 56}
+    assert {c[2] // c[11] for c in ref.topology("regnet_y_8gf") if c[0].endswith("f.b.0")} == {56}
+    assert (9 * 56 + 31) // 32 * 32 == 512 and 512 - 9 * 56 == 8 and -(-56 // 16) == 4
+    odd = sorted({w for a in ARCHS for w in ref.TABLE[a][1] if w % 32})
+    assert odd == [48, 72, 120, 144, 216, 336, 784, 888, 1512]
+    assert [ref.pitch(w) for w in (144, 120, 2016)] == [160, 128, 2016]
+    assert max(g for a in ARCHS for g in ref.TABLE[a][4]) == 63
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_synth_regnet_y_state_dict_has_torchvisions_keys_order_shapes(arch):
+    sd = synth.make_state_dict(arch)
+    assert [(k, tuple(v.shape)) for k, v in sd.items()] == _expected_keys(arch)
+    assert list(sd) == list(synth.make_regnet_y_state_dict(arch))
+    assert all(v.dtype == torch.float32 for v in sd.values())
+    biased = [k[:-5] for k in sd if k.endswith(".bias") and sd[k[:-4] + "weight"].dim() == 4]
+    assert biased and all(k.endswith((".f.se.fc1", ".f.se.fc2")) for k in biased)        # only the SE layers' 1x1 convs have a bias
+    assert synth.REGNET_Y_ARCHS[arch][:3] == ref.TABLE[arch][1:4]
+    keys = list(sd)
+    p = "trunk_output.block2.block2-0."
+    i = keys.index(p + "f.se.fc1.weight")
+    assert keys[i - 1] == p + "f.b.1.running_var" and keys[i:i + 5] == [p + "f.se.fc1.weight", p + "f.se.fc1.bias", p + "f.se.fc2.weight",
+                                                                      p + "f.se.fc2.bias", p + "f.c.0.weight"]
+
+
+def test_regnet_y_arch_ids_are_unique_and_the_error_text_keeps_its_words():
+    ids = list(engine.ARCH_IDS.values())
+    assert len(ids) == len(set(ids))
+    assert sorted(v for v in ids if 15000 <= v < 16000) == [15008, 15016, 15032, 15080]
+    assert sorted(k for k, v in engine.ARCH_IDS.items() if 15000 <= v < 16000) == sorted(ARCHS)
+    with pytest.raises(ValueError, match="AlexNet") as e:
+        engine.MaskedForwardEngine("no_such_network")
+    assert "RegNetX" in str(e.value) and "RegNetY" in str(e.value)
+    assert all(engine.default_bn_eps(a) == 1e-5 for a in ARCHS)
+    for name in ("regnet_y_400mf", "regnet_y_16gf", "regnet_y_32gf"):
+        assert name not in engine.ARCH_IDS
+        with pytest.raises(ValueError, match="unsupported arch"):
+            engine.MaskedForwardEngine(name)
+        assert name not in synth.REGNET_Y_ARCHS
+
+
+@pytest.mark.parametrize("arch_id", [15000, 15004, 15009, 15160, 15320, 15999])
+def test_unknown_regnet_y_id_is_refused(mpx_lib, arch_id):
+    """mpx_create rejects the id before it touches a device."""
+    h = C.c_void_p()
+    assert mpx_lib.mpx_create(arch_id, 4, 0, C.byref(h)) == -1 and not h.value
+
+
+def test_the_id_the_entries_and_the_kernels_are_in_the_header_the_binding_and_the_library(mpx_lib):
+    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
+        header = fh.read()
+    assert "#define MPX_ARCH_REGNET_Y 15000" in header
+    assert re.search(r"^ \*  18 = the grouped 3x3 kernel for any group count, group widths 16 / 24 / 48 / 56 / 120", header, re.M)
+    assert "regnet_y_800mf / _1_6gf / _3_2gf / _8gf" in header
+    with open(os.path.join(ROOT, "network_interpretation_imagenet_amd", "libmpx.so"), "rb") as fh:
+        blob = fh.read()
+    for entry in ("mpx_se_gate_relu", "mpx_se_act", "mpx_gconvw3x3_bn_act", "mpx_pack_gconvw_weights"):
+        assert re.search(r"^int %s\(" % entry, header, re.M), entry
+        assert entry in _lib.SIGNATURES and getattr(mpx_lib, entry) is not None and entry.encode() in blob, entry
+    assert _lib.SIGNATURES["mpx_se_gate_relu"] == _lib.SIGNATURES["mpx_se_gate"]
+    for cg in (16, 24, 48, 56, 120):        # the five group widths of the kernel (Itanium mangling: the first template argument as Li<cg>E)
+        assert ("gconvw3x3_f16x3_kernelILi%dELi" % cg).encode() in blob, cg
+    for act in (0, 1):                      # both gates: se_gate_kernel<false> (SiLU) and <true> (ReLU)
+        assert ("se_gate_kernelILb%dEE" % act).encode() in blob, act
+    # the descriptors keep their layout
+    assert C.sizeof(_lib.SeDesc) == 48 + 4 * 4 and C.sizeof(_lib.ConvDesc) == 96 + 11 * 4
+
+
+def test_restatement_gate_is_relu_then_sigmoid_by_hand():
+    """se_gate against the formulas written out, on a block whose fc1 pre-activations take both signs."""
+    g = torch.Generator().manual_seed(5)
+    t = torch.randn(2, 24, 5, 5, generator=g, dtype=torch.float64).relu()
+    sd = {"p.f.se.fc1.weight": torch.randn(6, 24, 1, 1, generator=g, dtype=torch.float64), "p.f.se.fc1.bias": torch.randn(6, generator=g, dtype=torch.float64),
+          "p.f.se.fc2.weight": torch.randn(24, 6, 1, 1, generator=g, dtype=torch.float64), "p.f.se.fc2.bias": torch.randn(24, generator=g, dtype=torch.float64)}
+    gate, z1 = ref.se_gate(sd, "p.", t)
+    pooled = t.mean((2, 3))
+    z = pooled @ sd["p.f.se.fc1.weight"].view(6, 24).t() + sd["p.f.se.fc1.bias"]
+    assert (z < 0).any() and (z > 0).any() and (z1.view(2, 6) - z).abs().max() < 1e-12
+    want = 1 / (1 + torch.exp(-(torch.clamp(z, min=0) @ sd["p.f.se.fc2.weight"].view(24, 6).t() + sd["p.f.se.fc2.bias"])))
+    assert (gate.view(2, 24) - want).abs().max() < 1e-12
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+def test_preconditions_on_the_rows_the_gpu_test_scores(golden_dir, arch):
+    """EVERY row of regnety_ref.E2E_CASES: fp64 top-two logit margin >= 1e-3 and fp64 softmax peak inside [0.05, 0.95]; with every gate
+    replaced by 0.5 some score moves by more than 1e-3 (here: EVERY row does); the gates of the unmasked picture spread over (0, 1), and
+    fc1's pre-activations take both signs (ReLU is live)."""
+    sd = synth.make_state_dict(arch)
+    total = 0
+    for kind, (img, seg, onoff, label, s64, logits64) in ref.e2e_rows(golden_dir, arch).items():
+        top2 = np.sort(logits64, axis=1)[:, -2:]
+        gap = top2[:, 1] - top2[:, 0]
+        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
+        s_half, _l = ref.score_masks_fp64(sd, arch, scorer.to_tensor_normalize(img), seg, onoff, label, gate_half=True)
+        moved = np.abs(s_half - s64)
+        print("%s %s: %d rows, label %d, scores %.4f .. %.4f, smallest fp64 top-two margin %.4f, softmax peak %.4f .. %.4f; gates at 0.5: smallest move %.4f (largest %.4f)"
+              % (arch, kind, len(s64), label, s64.min(), s64.max(), gap.min(), peaks.min(), peaks.max(), moved.min(), moved.max()))
+        assert gap.min() >= 1e-3
+        assert peaks.min() >= 0.05 and peaks.max() <= 0.95
+        assert moved.max() > 1e-3 and moved.min() > 1e-3, np.sort(moved)
+        assert np.isfinite(logits64).all() and np.abs(logits64).max() < 1e3
+        total += len(s64)
+    assert total == {"regnet_y_800mf": 6, "regnet_y_1_6gf": 6, "regnet_y_3_2gf": 6, "regnet_y_8gf": 3}[arch]
+    img, _seg = ref.e2e_inputs(golden_dir, "felz")
+    gates = []
+    with torch.no_grad():
+        ref.forward(ref.cast(sd, torch.float64), scorer.to_tensor_normalize(img)[None].double(), arch, gates=gates)
+    allg = torch.cat([g.flatten() for g in gates])
+    print("%s: gates of the unmasked picture: 5 %% / 50 %% / 95 %% quantiles %.3f / %.3f / %.3f" % (arch, *[allg.quantile(q).item() for q in (0.05, 0.5, 0.95)]))
+    inside = [((g > 0.05) & (g < 0.95)).double().mean().item() for g in gates]
+    print("%s: share of the gates inside (0.05, 0.95): %.2f over all layers, per layer %.2f .. %.2f" % (
+        arch, ((allg > 0.05) & (allg < 0.95)).double().mean().item(), min(inside), max(inside)))
+    # the trunk grows to an RMS of 3 .. 9 towards the last stage, where the gates lean to 0 / 1: over all layers 48 .. 68 % lie inside
+    # (0.05, 0.95), in every single layer at least 17 %, and every layer has gates on both sides of a half
+    assert len(gates) == ref.TABLE[arch][7] and allg.quantile(0.05) < 0.25 and allg.quantile(0.95) > 0.75
+    assert ((allg > 0.05) & (allg < 0.95)).double().mean() >= 0.4 and min(inside) >= 0.15
+    assert all(g.min() < 0.25 and g.max() > 0.75 for g in gates)
+
+
+# ------------------------------------------------------------------------------------------------
+# the group-width-56 arithmetic of tile 18, emulated
+# ------------------------------------------------------------------------------------------------
+_measured = {}
+
+
+def measure(d):
+    if d.name not in _measured:
+        sd = yd.weights(d)
+        x = yd.draws(d, yd.BATCHES[-1])
+        pre, want, b = (t.reshape(-1, d.width) for t in yd.reference(sd, d, x[2]))
+        hi, lo = xb.emulate(d, xb.pack(sd, d), x[0], x[1])
+        got = torch.from_numpy(hi.astype(np.float64) + lo.astype(np.float64))
+        r_ref = ((got - want).abs() / (2.0 ** -22 * b + 2.0 ** -24)).max().item()
+        _measured[d.name] = (pre, want, b, hi, lo, got, r_ref)
+    return _measured[d.name]
+
+
+def test_the_cg56_cases_are_the_ones_the_kernel_can_go_wrong_at():
+    by = {d.name: d for d in yd.CASES}
+    assert len(by) == len(yd.CASES) == 12 and all(d.cg == 56 and d.width == 56 * d.groups for d in yd.CASES)
+    assert (by["g1"].groups, by["g1"].width, yd.pitch(by["g1"].width)) == (1, 56, 64)
+    assert (by["g3"].groups, by["g3"].width, yd.pitch(by["g3"].width)) == (3, 168, 192)
+    own = sorted((d.groups, d.hin, d.stride, d.hout) for d in yd.CASES if d.name.startswith("y8-"))
+    assert own == sorted((g, hin, s, 7) for g in ref.TABLE["regnet_y_8gf"][4] for hin, s in ((7, 1), (14, 2)))
+    assert (by["m5-s1"].hin, by["m5-s1"].stride, by["m5-s1"].hout) == (5, 1, 5) and (by["m5-s2"].hin, by["m5-s2"].stride, by["m5-s2"].hout) == (9, 2, 5)
+    assert 3 * 5 * 5 == 75 and 75 % 16 and 49 % 16          # tiles of 16 pixels cross rows and images
+    assert set(yd.R_REF) == set(by) == set(yd.C_TOL) and len({yd.draw_seed(d) for d in yd.CASES}) == 12
+
+
+@pytest.mark.parametrize("d", yd.CASES, ids=[d.name for d in yd.CASES])
+def test_emulated_cg56_arithmetic_stays_inside_the_bound_and_the_constant_follows(d):
+    pre, want, b, hi, lo, got, r_ref = measure(d)
+    print("r_ref %s cg %d groups %2d stride %d map %2d: %.3f (recorded %.3f, C %g)" % (d.name, d.cg, d.groups, d.stride, d.hin, r_ref, yd.R_REF[d.name], yd.C_TOL[d.name]))
+    assert yd.R_REF[d.name] / 2 <= r_ref <= 2 * yd.R_REF[d.name], "regnety_draws.R_REF is not what this file measures: %.3f" % r_ref
+    assert yd.C_TOL[d.name] == 2.0 ** math.ceil(math.log2(4 * yd.R_REF[d.name]))
+    assert ((got - want).abs() <= yd.tol(d, b)).all()
+    neg = (pre < -yd.tol(d, b)).numpy()
+    assert neg.any() and (hi.view(np.uint16)[neg] == 0).all() and (lo.view(np.uint16)[neg] == 0).all()
+    top, small = yd.preconditions(want)
+    assert (b >= want.abs()).all()
+
+
+def test_the_last_k_step_of_cg56_holds_eight_padding_elements_behind_tap_8():
+    """The packed planes of the emulation: K = 512, the columns 504 .. 511 are zeros, and column 503 is tap 8's last channel."""
+    d = yd.case("g3")
+    sd = yd.weights(d)
+    w_hi, w_lo, scale, shift = xb.pack(sd, d)
+    assert w_hi.shape == (3, 56, 512) and (w_hi[:, :, 504:] == 0).all() and (w_lo[:, :, 504:] == 0).all() and (w_hi[:, :, 503] != 0).any()
+    w = sd[d.name + ".weight"]
+    e = 10 - np.frexp(np.abs(w.numpy()).reshape(168, -1).max(1))[1]
+    assert np.array_equal(w_hi[2, 5, 8 * 56 + 55], np.float16(np.ldexp(w[2 * 56 + 5, 55, 2, 2].item(), int(e[2 * 56 + 5]))).astype(np.float64))
+
+
+def test_the_cg56_reference_is_torch_conv2d_with_groups():
+    for name in ("g1", "y8-g4-14s2", "m5-s2"):
+        d = yd.case(name)
+        x = yd.draws(d, 1)[2]
+        w = yd.weights(d)[d.name + ".weight"].double()
+        want = F.conv2d(x.double().permute(0, 3, 1, 2), w, None, d.stride, 1, 1, d.groups).permute(0, 2, 3, 1)
+        assert (yd.xgd.gconv64(x, w, d) - want).abs().max() <= 1e-12 * want.abs().max()

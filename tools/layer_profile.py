@@ -3,6 +3,8 @@
 usage: python tools/layer_profile.py [arch] [batch] [reps]      (arch: any name of engine.ARCH_IDS; resnext50_32x4d / resnext101_32x8d and
                                                                  regnet_x_400mf .. regnet_x_8gf add the grouped 3x3 launches as rows of
                                                                  their own, with their bytes, TB/s and MFMA TFLOP/s;
+                                                                 regnet_y_800mf .. regnet_y_8gf those and the SE gate and SE scale launches
+                                                                 with bytes, TB/s and their share of the forward;
                                                                  convnext_tiny / convnext_small the depthwise 7x7 + LayerNorm launches and the
                                                                  stand-alone LayerNorms, with bytes, TB/s and the shares by op class;
                                                                  vit_b_16 / vit_b_32 the attention, token assembly and LayerNorm launches
@@ -157,7 +159,7 @@ if fused:       # the grouped rows above book these launches under their main co
         print("%-16s + %-24s K %4d + %-4d out%-3d %8.3f ms %5.1f%% %9.1f GFLOP %8.1f TFLOP/s" % (
             names[li], names[lj], d.cin * d.ksize * d.ksize, eng.layers[lj].cin, d.hout, ms, 100 * ms / tot, fl / 1e9, fl / max(ms, 1e-9) / 1e9))
 if max(eng.groups) > 1:     # ResNeXt: the grouped 3x3 launches (csrc/mpx_gconv.h, tile 16) as rows of their own, by their bytes and by their MFMA work
-    print("-- grouped 3x3 convs (tile 16, RegNetX: csrc/mpx_gconvw.h, tile 18 -- row fragments of 16 channels per group: one launch each); bytes = split-fp16 input + output planes once; MFMA TFLOP/s = the three f16 products over "
+    print("-- grouped 3x3 convs (tile 16, RegNetX / RegNetY: csrc/mpx_gconvw.h, tile 18 -- row fragments of 16 channels per group: one launch each); bytes = split-fp16 input + output planes once; MFMA TFLOP/s = the three f16 products over "
           "channel blocks of max(cg, 16) and K padded to 32 (4x / 2x the algorithmic FLOPs at cg = 4 / 8) --")
     tot_g = g_bytes = g_fl = 0.0
     by_shape = {}
@@ -278,6 +280,37 @@ elif eng.lnorms:  # ConvNeXt: the depthwise 7x7 + LayerNorm launches and the sta
           "LayerNorms (%d) %.1f %%, staging (K0) %.1f %%, head %.1f %% of %.3f ms/batch (%d launches per forward batch)"
           % (100 * tot / allms, 100 * gelu_ms / allms, len(eng.dwconvs), 100 * tot_dw / allms, len(eng.lnorms), 100 * tot_ln / allms,
              100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * prof["ms"]["head"] / reps / allms, allms, sum(prof["launches"].values()) // reps - 1))
+elif eng.ses and not eng.dwconvs:     # RegNetY: the SE gate (ReLU) and SE scale launches between a block's grouped 3x3 and its closing 1x1
+    print("-- SE gate (mpx_se_gate_relu: pool + fc1 + fc2, one workgroup per image; bytes = f.b's output read once) and SE scale (mpx_se_scale, in place; bytes = the map read + written) --")
+    tot_g = g_bytes = tot_s = s_bytes = 0.0
+    by_shape = {}
+    for se, gms, sms in zip(eng.ses, prof["per_se_gate_ms"], prof["per_se_scale_ms"]):
+        gms /= reps
+        sms /= reps
+        gb = batch * 4.0 * se.pitch * se.hw * se.hw
+        tot_g += gms
+        g_bytes += gb
+        tot_s += sms
+        s_bytes += 2 * gb
+        a = by_shape.setdefault((se.channels, se.pitch, se.q, se.hw), [0, 0.0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += gms
+        a[2] += sms
+        a[3] += gb
+        if os.environ.get("MPX_PER_LAYER"):
+            print("%-36s C %4d pitch %4d q %3d %3dx%-3d gate %8.3f ms %8.1f MB %6.2f TB/s   scale %8.3f ms %8.1f MB %6.2f TB/s" % (
+                se.name.decode(), se.channels, se.pitch, se.q, se.hw, se.hw, gms, gb / 1e6, gb / max(gms, 1e-9) / 1e9, sms, 2 * gb / 1e6, 2 * gb / max(sms, 1e-9) / 1e9))
+    for (c, pitch, q, hw), (n, gms, sms, gb) in sorted(by_shape.items(), key=lambda kv: -(kv[1][1] + kv[1][2])):
+        print("C %4d pitch %4d q %3d %3dx%-3d x%-2d gate %8.3f ms %8.1f MB %6.2f TB/s   scale %8.3f ms %8.1f MB %6.2f TB/s" % (
+            c, pitch, q, hw, hw, n, gms, gb / 1e6, gb / max(gms, 1e-9) / 1e9, sms, 2 * gb / 1e6, 2 * gb / max(sms, 1e-9) / 1e9))
+    pool_ms = prof["ms"]["pool"] / reps - tot_g - tot_s
+    allms = sum(prof["ms"].values()) / reps
+    print("SE gates %.3f ms/batch, %.1f MB -> %.2f TB/s; SE scales %.3f ms/batch, %.1f MB -> %.2f TB/s; global pool %.3f ms/batch; conv total %.3f ms/batch"
+          % (tot_g, g_bytes / 1e6, g_bytes / max(tot_g, 1e-9) / 1e9, tot_s, s_bytes / 1e6, s_bytes / max(tot_s, 1e-9) / 1e9, pool_ms, tot))
+    print("share of the forward by op class: conv (MFMA) %.1f %%, SE gate (%d launches) %.1f %%, SE scale (%d) %.1f %% -- the three extra passes over f.b's output (gate read, scale read + write) "
+          "%.1f %% together --, staging (K0) %.1f %%, global pool %.1f %%, head %.1f %% of %.3f ms/batch"
+          % (100 * tot / allms, len(eng.ses), 100 * tot_g / allms, len(eng.ses), 100 * tot_s / allms, 100 * (tot_g + tot_s) / allms,
+             100 * prof["ms"]["mask_apply_normalize"] / reps / allms, 100 * pool_ms / allms, 100 * prof["ms"]["head"] / reps / allms, allms))
 elif eng.ses:     # EfficientNet-B0: the depthwise k x k + BN + SiLU, SE gate and SE scale launches between the 1x1 convs
     print("-- depthwise k x k + BN with SiLU on load and in the epilogue (mpx_dwconv_bn_act); bytes = split-fp16 planes read + written, pitch channels per pixel --")
     tot_dw = dw_bytes = tot_g = g_bytes = tot_s = s_bytes = 0.0

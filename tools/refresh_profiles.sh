@@ -45,4 +45,12 @@ for A in regnet_x_400mf regnet_x_800mf regnet_x_1_6gf regnet_x_3_2gf regnet_x_8g
   MPX_PER_LAYER=1 python tools/layer_profile.py $A 512 3 2>&1 | grep -v amdgpu.ids > $O/regnet_layers_${A}_b512.txt
   python bench.py --arch $A 2>/dev/null | tail -1 >> $O/regnet_bench.txt
 done
+# RegNetY: per-layer tables at batch 512 (the grouped 3x3, SE gate and SE scale launches as rows of their own) and the benchmark of every network,
+# the RegNetX networks of the same run beside them -> profiles/regnety_layers_<arch>_b512.txt, profiles/regnety_bench.txt
+for A in regnet_y_800mf regnet_y_1_6gf regnet_y_3_2gf regnet_y_8gf; do
+  MPX_PER_LAYER=1 python tools/layer_profile.py $A 512 3 2>&1 | grep -v amdgpu.ids > $O/regnety_layers_${A}_b512.txt
+done
+for A in regnet_y_800mf regnet_y_1_6gf regnet_y_3_2gf regnet_y_8gf regnet_x_800mf regnet_x_1_6gf regnet_x_3_2gf regnet_x_8gf; do
+  python bench.py --arch $A 2>/dev/null | tail -1 >> $O/regnety_bench.txt
+done
 rm -rf $O/stats $O/pmc_fetch_* $O/pmc_write_*

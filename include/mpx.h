@@ -562,6 +562,48 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream);
 int mpx_stem_table_apply(mpx_engine* h, const uint8_t* onoff, int M, int S, int slot0, void* stream);
 
+/* ---- K0 for real-valued per-pixel masks: explicit weights, or RISE's grids synthesised in the kernel ---------------------------
+ * extends: mpx_mask_apply_normalize, whose masks are binary unions of superpixels (the reference's windows,
+ *          generate_gp_training_data_imagenet.py:223-245), to a weight w_m(p) in place of `keep`: masked = normalised image * w_m, the
+ *          other common masked-perturbation convention.  There is no reference line: the RISE entry follows Petsiuk, Das, Saenko, "RISE:
+ *          Randomized Input Sampling for Explanation of Black-box Models" (BMVC 2018) -- a random s x s grid upsampled bilinearly and
+ *          cropped at a random shift --, the explicit entry takes whatever the caller computed (soft-edged occlusion windows, ...).
+ * img_u8_hwc / img_f32_chw, mean, std, slot0, out_f32_nchw: as mpx_mask_apply_normalize (exactly one image pointer; the u8 image is
+ * normalised with K0's op sequence; channel 3 of the padded NHWC4 planes is written as zero, the 3-pixel border is not touched).
+ * o = v * w is ONE fp32 multiply, then the hi / lo split (hi = f16(o), lo = f16(o - f32(hi))).  For w in {0, 1} the planes and
+ * out_f32_nchw equal mpx_mask_apply_normalize's bit for bit, the -0.0 of a removed negative pixel included (hi -0.0, lo +0.0 in the
+ * planes).  No masked image is materialised on the way.
+ * mpx_softmask_apply: weights DEV f32[M][224][224].
+ * mpx_rise_apply: cells DEV u8[M][s][s] (non-zero = keep), shift DEV i32[M][2] = (dy, dx), 2 <= s <= 32.  With cell = ceil(224 / s) and
+ *   U = (s + 1) * cell the weight of pixel (y, x) is the bilinear upsampling of the grid to U x U with half-pixel centres
+ *   (torch.nn.functional.interpolate(.., size=(U, U), mode="bilinear", align_corners=False)), cropped at (dy, dx), computed as
+ *     Y = y + dy;  t = max((2Y + 1) * s - U, 0);  i0 = t / (2U);  r = t - i0 * 2U;  fy = float(r) / float(2U);  i1 = min(i0 + 1, s - 1)
+ *     (the same along x: j0, j1, fx)
+ *     w = (1 - fy) * ((1 - fx) * g[i0][j0] + fx * g[i0][j1]) + fy * ((1 - fx) * g[i1][j0] + fx * g[i1][j1])
+ *   with integer t, i0, r, one correctly rounded fp32 division per axis, and every difference, product and sum of the last line rounded to
+ *   fp32 on its own in the order written (products before their sum, no FMA): csrc/mpx_softmask.h, restated by masks.rise_weights.
+ *   A shift outside [0, cell) is outside the contract and its result undefined (the kernels clamp it so that nothing is read out of
+ *   bounds); the Python layer refuses it before upload.
+ * Both mark slots [slot0, slot0 + M) as input-staged, as mpx_mask_apply_normalize does: mpx_forward runs the stem on them, and a batch
+ * mixed with slots staged by mpx_stem_table_apply fails as it does today.  MPX_E_STATE on an engine of one of the small networks (their
+ * convention is mpx_mask_apply_minmax's).  MPX_E_ARG, with nothing written, for s outside [2, 32], M < 0 or slot0 + M > max_batch, both
+ * or neither image pointer, a NULL mask pointer.  M == 0 succeeds and writes nothing. */
+int mpx_softmask_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* weights, int M,
+                       const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream);
+int mpx_rise_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const uint8_t* cells, const int32_t* shift,
+                   int M, int s, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream);
+
+/* ---- the score-weighted sum of real-valued masks (RISE's saliency map, before its normalisation) -------------------------------
+ * extends: mpx_heatmap_accumulate (counts of binary masks) to  sal[p] <- sal[p] + weight[m] * w_m(p)  for m = 0 .. M - 1 in this order,
+ *          accumulated in place in fp32 from the value already in sal (RISE's Monte Carlo estimate: the masks weighted by the class score).
+ * Each step is a multiply and an add, each rounded to fp32 -- not an FMA.  One thread owns a pixel and walks the masks in order (no
+ * atomics, no reduction tree): a pixel's bits depend neither on the launch geometry nor on how the rows are cut into consecutive calls.
+ * weights / cells / shift / s: as the apply entries; weight DEV f32[M] (the scores of the forward that just ran); sal DEV f32[224][224].
+ * MPX_E_STATE on the small networks, MPX_E_ARG for a NULL pointer, M < 0 or s outside [2, 32]; M == 0 succeeds and writes nothing. */
+int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weight, int M, float* sal, void* stream);
+int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal,
+                      void* stream);
+
 /* ---- K0 of the small networks: the CIFAR / MNIST scorers' mask convention ---------------------------
  * replaces: the in-place min-max rescale of the picture to [0,255] (generate_gp_training_data_cifar.py:274-279,
  *           generate_gp_training_data_mnist.py:167-171), `mask.fill(255); mask[segments == segVal] = 0` for the SELECTED

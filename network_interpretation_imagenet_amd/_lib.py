@@ -178,7 +178,14 @@ SIGNATURES = {
     "mpx_tokens_assemble": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpx_layernorm_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _vp]),
     "mpx_profile_collect_attn": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 11),
+    # real-valued per-pixel masks (csrc/mpx_softmask.h): explicit weights or RISE's grids, applied like K0 and summed with the scores
+    "mpx_softmask_apply": (_i, [_vp, _vp, _vp, _vp, _i, _fp, _fp, _i, _vp, _vp]),
+    "mpx_rise_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _fp, _fp, _i, _vp, _vp]),
+    "mpx_softmask_saliency": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "mpx_rise_saliency": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
+
+SOFTMASK_TILE = 32      # csrc/mpx_softmask.h SM_MT: the masks one block of the apply kernels loops over
 
 _lib = None
 

@@ -524,3 +524,10 @@ def score_masks(model, image, segments, onoff, label, stem=None):
     count; a caller that scores PART of an image's rows (several calls, several ranks) passes model.stem_for_rows(all of them) so that every
     part carries the bits of the unsplit call (engine.MaskedForwardEngine.stem_for_rows, shard.job_stem)."""
     return model.score_masks(image, segments, onoff, label) if stem is None else model.score_masks(image, segments, onoff, label, stem=stem)
+
+
+def rise_saliency(model, image, label, n_masks=4000, s=7, p1=0.5, seed=0, out=None):
+    """RISE (Petsiuk, Das, Saenko, BMVC 2018) next to the superpixel windows: -> f32[224,224], the masks.rise_masks(n_masks, s, p1, seed)
+    masks summed with their class scores on the device and divided by n_masks * p1 (engine.MaskedForwardEngine.rise_saliency).  The masks
+    are real-valued per pixel, so they always take the conv staging; every 224 x 224 network the engine serves takes them."""
+    return model.rise_saliency(image, label, n_masks=n_masks, s=s, p1=p1, seed=seed, out=out)

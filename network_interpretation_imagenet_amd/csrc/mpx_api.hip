@@ -19,6 +19,7 @@
 #include "mpx_gconvw.h"
 #include "mpx_cnext.h"
 #include "mpx_attn.h"
+#include "mpx_softmask.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3316,6 +3317,101 @@ int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const flo
     MPX_HIP(h, hipGetLastError());
     std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
     return 0;
+}
+
+// ---- real-valued masks (mpx_softmask.h): explicit weights or RISE's grids, applied like K0 and summed with the scores ----
+extern "C++" {
+static void soft_rise_geometry(SoftParams& p, int s) {
+    p.s = s;
+    p.cell = (MPX_IMG + s - 1) / s;
+    p.U2 = 2 * (s + 1) * p.cell;
+    p.f_U2 = (float)p.U2;
+    p.inv_U2 = 1.0f / p.f_U2;
+}
+
+template <class WS>
+static int soft_apply(mpx_engine* h, const char* what, const uint8_t* img_u8_hwc, const float* img_f32_chw, const void* mask, const void* mask2,
+                      int M, int s, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's", what);
+    if (WS::kLds && (s < SM_S_MIN || s > SM_S_MAX)) return fail(h, MPX_E_ARG, "%s: s=%d outside [%d, %d]", what, s, SM_S_MIN, SM_S_MAX);
+    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "%s: exactly one of img_u8_hwc / img_f32_chw must be given", what);
+    if (!mask || (WS::kLds && !mask2)) return fail(h, MPX_E_ARG, "%s: null mask pointer", what);
+    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "%s: mean/std required for u8 input", what);
+    if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
+        return fail(h, MPX_E_ARG, "%s: slots [%d,%lld) outside [0, max_batch=%d)", what, slot0, (long long)slot0 + M, h->max_batch);
+    if (M == 0) return 0;
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw;
+    if (WS::kLds) {
+        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
+        soft_rise_geometry(p, s);
+    } else {
+        p.weights = (const float*)mask;
+    }
+    p.out_hi = h->in_hi; p.out_lo = h->in_lo; p.out_f32 = out_f32_nchw;
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean ? mean[c] : 0.f;
+        p.std[c] = std ? std[c] : 1.f;
+    }
+    p.M = M; p.slot0 = slot0;
+    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 1, -1);
+    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + SM_MT - 1) / SM_MT);
+    hipLaunchKernelGGL(softmask_apply_kernel<WS>, grid, dim3(256), WS::lds_bytes(s), st, p);
+    MPX_HIP(h, hipGetLastError());
+    std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
+    return 0;
+}
+
+template <class WS>
+static int soft_saliency(mpx_engine* h, const char* what, const void* mask, const void* mask2, const float* weight, int M, int s, float* sal,
+                         void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks (no 224 x 224 input)", what);
+    if (WS::kLds && (s < SM_S_MIN || s > SM_S_MAX)) return fail(h, MPX_E_ARG, "%s: s=%d outside [%d, %d]", what, s, SM_S_MIN, SM_S_MAX);
+    if (!mask || (WS::kLds && !mask2) || !weight || !sal) return fail(h, MPX_E_ARG, "%s: null pointer", what);
+    if (M < 0) return fail(h, MPX_E_ARG, "%s: M=%d", what, M);
+    if (M == 0) return 0;
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (WS::kLds) {
+        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
+        soft_rise_geometry(p, s);
+    } else {
+        p.weights = (const float*)mask;
+    }
+    p.score = weight; p.sal = sal; p.M = M;
+    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmask_saliency_kernel<WS>, dim3((MPX_IMG * MPX_IMG + SM_SAL_THREADS - 1) / SM_SAL_THREADS), dim3(SM_SAL_THREADS),
+                       WS::lds_bytes(s), st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+}  // extern "C++"
+
+int mpx_softmask_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* weights, int M, const float mean[3],
+                       const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    return soft_apply<ExplicitWeights>(h, "softmask_apply", img_u8_hwc, img_f32_chw, weights, nullptr, M, 0, mean, std, slot0, out_f32_nchw, stream);
+}
+
+int mpx_rise_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const uint8_t* cells, const int32_t* shift, int M, int s,
+                   const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    return soft_apply<RiseWeights>(h, "rise_apply", img_u8_hwc, img_f32_chw, cells, shift, M, s, mean, std, slot0, out_f32_nchw, stream);
+}
+
+int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weight, int M, float* sal, void* stream) {
+    return soft_saliency<ExplicitWeights>(h, "softmask_saliency", weights, nullptr, weight, M, 0, sal, stream);
+}
+
+int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal, void* stream) {
+    return soft_saliency<RiseWeights>(h, "rise_saliency", cells, shift, weight, M, s, sal, stream);
 }
 
 int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg, int S,

@@ -40,6 +40,14 @@ __device__ __forceinline__ void split_f32(float v, half_t& hi, half_t& lo) {
     lo = (half_t)(v - (float)hi);
 }
 
+// A value as the fp32 register it was rounded into.  Where a product goes straight into split_f32, hipcc folds f16(a * b) into
+// v_fma_mixlo_f16 (a * b + 0.0 rounded to fp16 ONCE): the exact product is not rounded to fp32 first, and a product of -0.0 comes out as
+// +0.0.  A kernel whose planes are stated bit for bit (K0, the soft-mask apply) pins the product with this before the split.
+__device__ __forceinline__ float fp32_value(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 struct ConvParams {
     const half_t* x_hi;      // input planes, NHWC (pix_stride elements per pixel)
     const half_t* x_lo;

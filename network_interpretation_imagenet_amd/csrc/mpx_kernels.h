@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void mask_apply_normalize_kernel(const MaskPar
         h4 oh, ol;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            o[c] = v[c] * keep;     // x * mask, as numpy does it (-x*0 = -0.0)
+            o[c] = fp32_value(v[c] * keep);     // x * mask, as numpy does it (-x*0 = -0.0), also in the planes: hi -0.0, lo +0.0 (fp32_value)
             half_t hi, lo;
             split_f32(o[c], hi, lo);
             oh[c] = hi;

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, masks
 from ._lib import MpxError, IMG, NUM_CLASSES
 
 # transforms.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])
@@ -837,6 +837,163 @@ class MaskedForwardEngine:
             self.heatmap_accumulate(t(seg_rank, np.int32), t(onoff, np.uint8), t(pred, np.int32),
                                     torch.full((m,), int(label), dtype=torch.int32, device=self.device), heat)
         return heat.cpu().numpy().astype(np.float64)
+
+    # ---- real-valued per-pixel masks (csrc/mpx_softmask.h): explicit weights, RISE's grids ----
+    def _soft_args(self, image, out_f32, m):
+        """(u8 pointer, f32 pointer) of a device image for the soft-mask apply entries, with stage_masks' checks."""
+        if image.device != self.device or not image.is_contiguous():
+            raise ValueError("image must be a contiguous tensor on %s" % self.device)
+        if image.dtype == torch.uint8 and tuple(image.shape) == (IMG, IMG, 3):
+            ptrs = _ptr(image), None
+        elif image.dtype == torch.float32 and tuple(image.shape) == (3, IMG, IMG):
+            ptrs = None, _ptr(image)
+        else:
+            raise ValueError("image must be uint8[224,224,3] or float32[3,224,224], got %s%s" % (image.dtype, tuple(image.shape)))
+        if out_f32 is not None and (out_f32.dtype != torch.float32 or tuple(out_f32.shape) != (m, 3, IMG, IMG)
+                                    or out_f32.device != self.device or not out_f32.is_contiguous()):
+            raise ValueError("out_f32 must be contiguous float32[M,3,224,224] on %s" % self.device)
+        return ptrs
+
+    def _soft_weights(self, weights):
+        if (weights.device != self.device or weights.dtype != torch.float32 or weights.dim() != 3 or tuple(weights.shape[1:]) != (IMG, IMG)
+                or not weights.is_contiguous()):
+            raise ValueError("weights must be a contiguous float32[M,224,224] tensor on %s" % self.device)
+        return int(weights.shape[0])
+
+    def _rise_grids(self, cells, shifts, s):
+        s = int(s)
+        if not masks.RISE_S_MIN <= s <= masks.RISE_S_MAX:
+            raise ValueError("s=%r outside [%d, %d]" % (s, masks.RISE_S_MIN, masks.RISE_S_MAX))
+        if (cells.device != self.device or cells.dtype != torch.uint8 or cells.dim() != 3 or tuple(cells.shape[1:]) != (s, s)
+                or not cells.is_contiguous()):
+            raise ValueError("cells must be a contiguous uint8[M,%d,%d] tensor on %s" % (s, s, self.device))
+        m = int(cells.shape[0])
+        if shifts.device != self.device or shifts.dtype != torch.int32 or tuple(shifts.shape) != (m, 2) or not shifts.is_contiguous():
+            raise ValueError("shifts must be a contiguous int32[%d,2] tensor on %s" % (m, self.device))
+        return m, s
+
+    def stage_soft_masks(self, image, weights, slot0=0, out_f32=None):
+        """mpx_softmask_apply: K0 with a weight per pixel.  image as stage_masks; weights: device f32[M,224,224].  Fills input slots
+        [slot0, slot0+M) with normalised image * weights[m] (one fp32 multiply, then the hi / lo split); binary weights give K0's planes bit for bit."""
+        m = self._soft_weights(weights)
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_softmask_apply(self._h, u8, f32, _ptr(weights), m, self._mean, self._std, int(slot0),
+                                                         _ptr(out_f32), self._stream()), "mpx_softmask_apply")
+
+    def stage_rise(self, image, cells, shifts, s, slot0=0, out_f32=None):
+        """mpx_rise_apply: the same with RISE's weights synthesised in the kernel from cells (device u8[M,s,s], non-zero = keep) and shifts
+        (device i32[M,2] = (dy, dx)); the weights are masks.rise_weights(cells, shifts, s) bit for bit.  The shifts are the caller's contract
+        (each in [0, ceil(224 / s)); masks.check_rise verifies host arrays before they are uploaded)."""
+        m, s = self._rise_grids(cells, shifts, s)
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_rise_apply(self._h, u8, f32, _ptr(cells), _ptr(shifts), m, s, self._mean, self._std, int(slot0),
+                                                     _ptr(out_f32), self._stream()), "mpx_rise_apply")
+
+    def _sal_args(self, weight, sal, m):
+        if weight.device != self.device or weight.dtype != torch.float32 or weight.numel() != m or not weight.is_contiguous():
+            raise ValueError("weight must be a contiguous float32[%d] tensor on %s" % (m, self.device))
+        self._sal_map(sal)
+
+    def _sal_map(self, sal):
+        if sal.device != self.device or sal.dtype != torch.float32 or tuple(sal.shape) != (IMG, IMG) or not sal.is_contiguous():
+            raise ValueError("sal must be a contiguous float32[224,224] tensor on %s" % self.device)
+
+    def soft_saliency_accumulate(self, weights, weight, sal):
+        """mpx_softmask_saliency: sal[p] <- sal[p] + weight[m] * weights[m][p] for m ascending, in place, on the device (a rounded multiply and
+        a rounded add per step; one thread per pixel, so the bits do not depend on how the rows are cut into calls).  weights: device
+        f32[M,224,224]; weight: device f32[M], e.g. the scores of the forward that just ran; sal: device f32[224,224]."""
+        m = self._soft_weights(weights)
+        self._sal_args(weight, sal, m)
+        _lib.check(self._h, self._lib.mpx_softmask_saliency(self._h, _ptr(weights), _ptr(weight), m, _ptr(sal), self._stream()),
+                   "mpx_softmask_saliency")
+        return sal
+
+    def rise_saliency_accumulate(self, cells, shifts, s, weight, sal):
+        """mpx_rise_saliency: soft_saliency_accumulate with the weights synthesised from RISE's cells and shifts (as stage_rise)."""
+        m, s = self._rise_grids(cells, shifts, s)
+        self._sal_args(weight, sal, m)
+        _lib.check(self._h, self._lib.mpx_rise_saliency(self._h, _ptr(cells), _ptr(shifts), _ptr(weight), m, s, _ptr(sal), self._stream()),
+                   "mpx_rise_saliency")
+        return sal
+
+    def _score_staged(self, m, stage, label, return_logits, after=None):
+        """Forwards of up to max_batch slots over m rows that stage(s0, b) writes into slots [0, b), always through the input staging (the
+        conv path: a real-valued mask has no stem table).  Scores and predictions stay on the device until ONE download at the end;
+        after(s0, b, score_chunk), if given, runs behind each forward.  -> (score f32[m], pred i32[m][, logits f32[m,1000]]) host arrays."""
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        if not 0 <= int(label) < NUM_CLASSES:
+            raise ValueError("label %r outside [0,1000)" % (label,))
+        score = torch.empty(m, dtype=torch.float32, device=self.device)
+        pred = torch.empty(m, dtype=torch.int32, device=self.device)
+        labels = torch.full((min(m, self.max_batch),), int(label), dtype=torch.int32, device=self.device)
+        rows = []
+        for s0 in range(0, m, self.max_batch):
+            b = min(self.max_batch, m - s0)
+            stage(s0, b)
+            out = self.forward(b, labels[:b], want_logits=return_logits, score_out=score[s0:s0 + b], pred_out=pred[s0:s0 + b])
+            if return_logits:
+                rows.append(out[2].cpu().numpy())
+            if after is not None:
+                after(s0, b, score[s0:s0 + b])
+        res = (score.cpu().numpy(), pred.cpu().numpy())
+        if return_logits:
+            res += (np.concatenate(rows) if rows else np.empty((0, NUM_CLASSES), dtype=np.float32),)
+        return res
+
+    def score_soft_masks(self, image, weights, label, return_logits=False):
+        """(image, weights f32[M,224,224], label) -> (score f32[M], pred i32[M][, logits f32[M,1000]]):
+        score[m] = softmax(model(normalised_image * weights[m]))[label] for real-valued per-pixel masks (soft-edged occlusion windows, RISE
+        masks built elsewhere, ...).  The masked images are never materialised: each chunk of max_batch weight maps is uploaded and staged
+        by mpx_softmask_apply.  Always the conv staging; for weights in {0, 1} the scores are score_masks(..., stem="conv")'s bit for bit."""
+        w = np.ascontiguousarray(weights)
+        if w.dtype != np.float32 or w.ndim != 3 or w.shape[1:] != (IMG, IMG):
+            raise ValueError("weights must be float32[M,224,224], got %s%s" % (w.dtype, w.shape))
+        img_d = self._image_to_device(image)
+
+        def stage(s0, b):
+            self.stage_soft_masks(img_d, torch.from_numpy(w[s0:s0 + b]).to(self.device), 0)
+
+        return self._score_staged(int(w.shape[0]), stage, label, return_logits)
+
+    def score_rise(self, image, cells, shifts, s, label, return_logits=False):
+        """(image, cells u8[M,s,s], shifts i32[M,2], s, label) -> (score f32[M], pred i32[M][, logits f32[M,1000]]): the scores of RISE's
+        masks (masks.rise_cells / masks.rise_shifts), whose weights masks.rise_weights(cells, shifts, s) are synthesised in the apply
+        kernel -- s * s bytes and a shift go to the device per mask instead of a 200 KB weight map.  Shifts outside [0, ceil(224 / s)) and
+        s outside [2, 32] are refused here, before anything is uploaded."""
+        cells, shifts = masks.check_rise(cells, shifts, s)
+        img_d = self._image_to_device(image)
+        cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
+
+        def stage(s0, b):
+            self.stage_rise(img_d, cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, 0)
+
+        return self._score_staged(int(cells.shape[0]), stage, label, return_logits)
+
+    def rise_saliency(self, image, label, n_masks=4000, s=7, p1=0.5, seed=0, out=None):
+        """RISE's saliency map of `label` (Petsiuk, Das, Saenko, BMVC 2018): sum_m score[m] * w_m / (n_masks * p1) over n_masks random masks --
+        cells, shifts = masks.rise_masks(n_masks, s, p1, seed).  Chunks of max_batch masks run apply -> forward -> accumulation on the device
+        (mpx_rise_apply, mpx_forward, mpx_rise_saliency) with no host round trip in between; the sum is fp32 in mask order.
+        out: None -> a host f32[224,224]; a contiguous device f32[224,224] is overwritten with the map and returned (nothing is downloaded)."""
+        if not 0.0 < float(p1) <= 1.0 or int(n_masks) <= 0:
+            raise ValueError("n_masks > 0 and p1 in (0, 1], got n_masks=%r p1=%r" % (n_masks, p1))
+        cells, shifts = masks.rise_masks(n_masks, s, p1, seed)
+        sal = torch.zeros(IMG, IMG, dtype=torch.float32, device=self.device) if out is None else out
+        self._sal_map(sal)
+        if out is not None:
+            sal.zero_()
+        img_d = self._image_to_device(image)
+        cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
+
+        def stage(s0, b):
+            self.stage_rise(img_d, cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, 0)
+
+        def after(s0, b, score):
+            self.rise_saliency_accumulate(cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, score, sal)
+
+        self._score_staged(int(n_masks), stage, label, False, after=after)
+        sal.div_(float(n_masks) * float(p1))
+        return sal.cpu().numpy() if out is None else sal
 
     # ---- kernel variants (tuning / tests) ----
     def set_conv_tile(self, layer, tile):

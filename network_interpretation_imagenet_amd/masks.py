@@ -1,8 +1,11 @@
-"""Mask-vector construction (host logic, integer only).
+"""Mask construction (host logic; the superpixel mask-vectors are integer only).
 
 A mask-vector is onoff in {0,1}^S over the S distinct superpixel labels in np.unique(segments)
 order; the reference only ever uses contiguous windows of k = int(0.4*S) labels
 (generate_gp_training_data_imagenet.py:223-230, bayesian_active_learning_imagenet.py:173-178).
+
+The second convention, real-valued per-pixel masks, has its host side here too: RISE's draws (rise_cells, rise_shifts, rise_masks) and
+rise_weights, the numpy fp32 restatement of the weights csrc/mpx_softmask.h synthesises on the device.
 """
 import random
 
@@ -56,6 +59,99 @@ def expand_pixel_mask(seg_rank, onoff_row):
     """u8[H,W] in {0,1}: mask[y,x] = onoff[seg[y,x]] (host mirror of what K0 does on the device;
     used for the PNG wire format and heat-map reduction)."""
     return np.asarray(onoff_row, dtype=np.uint8)[seg_rank]
+
+
+# ---- RISE: real-valued masks from random grids (Petsiuk, Das, Saenko, BMVC 2018) -----------------------------------------
+RISE_IMG = 224
+RISE_S_MIN, RISE_S_MAX = 2, 32      # csrc/mpx_softmask.h SM_S_MIN / SM_S_MAX (a mask's s x s cells are staged in at most 1 KB of LDS); the one Python copy
+
+
+def rise_geometry(s):
+    """(cell, U) of an s x s grid: cell = ceil(224 / s) pixels per cell, U = (s + 1) * cell the side of the upsampled grid the 224 x 224
+    mask is cropped from.  s = 2, 7, 13, 32 -> (112, 336), (32, 256), (18, 252), (7, 231)."""
+    s = int(s)
+    if not RISE_S_MIN <= s <= RISE_S_MAX:
+        raise ValueError("s=%r outside [%d, %d]" % (s, RISE_S_MIN, RISE_S_MAX))
+    cell = -(-RISE_IMG // s)
+    return cell, (s + 1) * cell
+
+
+def _rise_rng(rng):
+    return rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+
+
+def rise_cells(M, s, p1=0.5, rng=None):
+    """u8[M,s,s]: each cell is kept (1) with probability p1 (RISE's binary grids).  rng: a numpy Generator, a seed, or None."""
+    rise_geometry(s)
+    if int(M) < 0 or not 0.0 <= float(p1) <= 1.0:
+        raise ValueError("M >= 0 and p1 in [0, 1], got M=%r p1=%r" % (M, p1))
+    return (_rise_rng(rng).random((int(M), int(s), int(s))) < float(p1)).astype(np.uint8)
+
+
+def rise_shifts(M, s, rng=None):
+    """i32[M,2]: (dy, dx) uniform in [0, cell)^2, where the 224 x 224 mask is cropped from the upsampled grid."""
+    cell, _ = rise_geometry(s)
+    if int(M) < 0:
+        raise ValueError("M >= 0, got %r" % (M,))
+    return _rise_rng(rng).integers(0, cell, size=(int(M), 2), dtype=np.int32)
+
+
+def rise_masks(M, s, p1=0.5, seed=0):
+    """(cells u8[M,s,s], shifts i32[M,2]) of one seeded job: the cells, then the shifts, from ONE np.random.default_rng(seed) -- the draws
+    MaskedForwardEngine.rise_saliency makes, so that a caller can restate its sum."""
+    rng = np.random.default_rng(seed)
+    return rise_cells(M, s, p1, rng), rise_shifts(M, s, rng)
+
+
+def check_rise(cells, shifts, s):
+    """What the device entries leave to the caller (include/mpx.h: a shift outside [0, cell) is undefined there): cells u8[M,s,s], shifts
+    i32[M,2] in [0, cell), 2 <= s <= 32.  -> (cells, shifts) as contiguous arrays; ValueError otherwise."""
+    cell, _ = rise_geometry(s)
+    cells, shifts = np.asarray(cells), np.asarray(shifts)
+    if cells.dtype != np.uint8 or cells.ndim != 3 or cells.shape[1:] != (int(s), int(s)):
+        raise ValueError("cells must be uint8[M,%d,%d], got %s%s" % (s, s, cells.dtype, cells.shape))
+    if shifts.dtype != np.int32 or shifts.shape != (cells.shape[0], 2):
+        raise ValueError("shifts must be int32[%d,2], got %s%s" % (cells.shape[0], shifts.dtype, shifts.shape))
+    if shifts.size and (shifts.min() < 0 or shifts.max() >= cell):
+        raise ValueError("shifts must lie in [0, cell=%d) for s=%d, got [%d, %d]" % (cell, s, shifts.min(), shifts.max()))
+    return np.ascontiguousarray(cells), np.ascontiguousarray(shifts)
+
+
+def _rise_axis(Y, s, U):
+    """One axis of the upsampling at the shifted coordinates Y (int64): (i0, i1, f) -- integers up to the ONE fp32 division r / 2U."""
+    t = np.maximum((2 * Y + 1) * s - U, 0)
+    i0 = t // (2 * U)
+    r = t - i0 * (2 * U)
+    f = r.astype(np.float32) / np.float32(2 * U)
+    return i0, np.minimum(i0 + 1, s - 1), f
+
+
+def rise_weights(cells, shifts, s):
+    """f32[M,224,224]: the weight of every pixel under every mask, the numpy fp32 restatement of csrc/mpx_softmask.h (the device is held to it
+    bit for bit): the s x s grid upsampled bilinearly to U x U with half-pixel centres -- torch.nn.functional.interpolate(size=(U, U),
+    mode="bilinear", align_corners=False) --, cropped at (dy, dx).  i0, i1 and the remainder r are integers, f = fl(r / 2U) is one fp32
+    division per axis, and  w = fl(fl(fl(1 - fy) * top) + fl(fy * bot))  with  top = fl(fl(fl(1 - fx) * g[i0][j0]) + fl(fx * g[i0][j1])),
+    bot the same on row i1: every product and sum rounded on its own, products before their sum, no FMA."""
+    cells, shifts = check_rise(cells, shifts, s)
+    s = int(s)
+    _, U = rise_geometry(s)
+    m_all = cells.shape[0]
+    out = np.empty((m_all, RISE_IMG, RISE_IMG), dtype=np.float32)
+    pix = np.arange(RISE_IMG, dtype=np.int64)
+    one = np.float32(1.0)
+    for a in range(0, m_all, 64):       # in blocks: the gathers below hold four [M,224,224] temporaries
+        b = min(m_all, a + 64)
+        g = (cells[a:b] != 0).astype(np.float32)
+        i0, i1, fy = _rise_axis(pix[None, :] + shifts[a:b, 0:1].astype(np.int64), s, U)
+        j0, j1, fx = _rise_axis(pix[None, :] + shifts[a:b, 1:2].astype(np.int64), s, U)
+        mi = np.arange(b - a)[:, None, None]
+        i0, i1, fy = i0[:, :, None], i1[:, :, None], fy[:, :, None]
+        j0, j1, fx = j0[:, None, :], j1[:, None, :], fx[:, None, :]
+        omx, omy = one - fx, one - fy
+        top = omx * g[mi, i0, j0] + fx * g[mi, i0, j1]
+        bot = omx * g[mi, i1, j0] + fx * g[mi, i1, j1]
+        out[a:b] = omy * top + fy * bot
+    return out
 
 
 # ---- the small networks' sampler (SURVEY.md 8 f4) ------------------------------------------------------------------------

@@ -604,6 +604,37 @@ int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weig
 int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal,
                       void* stream);
 
+/* ---- a second pixel source for the staging: rows selected on a per-pixel rank, and the blurred image ------------------------------
+ * extends: mpx_mask_apply_normalize and the soft-mask entries, whose removed pixel is always zero, to a FILL IMAGE: row m takes the pixels
+ *          of rank below thresh[m] from one source and the others from the other.  There is no reference line: these are the rows of the
+ *          deletion and insertion curves of Petsiuk, Das, Saenko, "RISE" (BMVC 2018), section 4.1 -- deletion replaces the most salient
+ *          pixels by a substrate `step` at a time, insertion reveals them on a blurred image (csrc/mpx_rankmask.h).
+ * mpx_rank_apply: img_u8_hwc / img_f32_chw, mean, std, slot0, out_f32_nchw as mpx_mask_apply_normalize (exactly one image pointer).
+ *   rank DEV i32[224][224], thresh DEV i32[M], fill_f32_chw DEV f32[3][224][224] or NULL, keep_top 0 or 1.  Per row m, pixel p, channel c:
+ *     V   = the normalised pixel, mpx_mask_apply_normalize's op sequence bit for bit (or the f32 as given)
+ *     F   = fill[c][p], or, without a fill image, V * 0.0f: mpx_mask_apply_normalize's removed pixel, the -0.0 of a negative pixel included
+ *     top = rank[p] < thresh[m]     (signed integer compare; nothing else is asked of rank or thresh: they need be no permutation)
+ *     o   = keep_top ? (top ? V : F) : (top ? F : V)
+ *   then the hi / lo split, channel 3 = +0.0, the 3-pixel border untouched, out_f32_nchw[m][c][p] = o when given.  No multiply touches a
+ *   kept pixel.  Without a fill image and with keep_top = 0, rows of thresholds i * step equal mpx_mask_apply_normalize's planes over the
+ *   pseudo-segments rank / step bit for bit.  Marks slots [slot0, slot0 + M) input-staged, as mpx_softmask_apply does.
+ *   MPX_E_STATE on the small networks; MPX_E_ARG, with nothing written, for both or neither image pointer, a NULL rank or thresh, M < 0,
+ *   slot0 + M > max_batch, keep_top outside {0, 1}.  M == 0 succeeds and writes nothing.
+ * mpx_blur_fill: out[3][224][224] = the separable correlation of the normalised image with taps (HOST f32[klen], read during the call as
+ *   mean / std are), zero padding, klen odd in [1, 31], r = klen / 2:
+ *     h[c][y][x]   = sum over k = 0 .. klen-1 with 0 <= x + k - r < 224, k ascending, from +0.0:  acc = fl(acc + fl(taps[k] * V[c][y][x + k - r]))
+ *     out[c][y][x] = the same along y over h
+ *   every product and sum rounded to fp32 on its own (no FMA); h stays in fp32 in the LDS.  With Gaussian taps this is what RISE's
+ *   insertion starts from (its Conv2d(3, 3, klen, padding = klen / 2) on the normalised tensor); the result is a fill image for
+ *   mpx_rank_apply.  MPX_E_STATE on the small networks; MPX_E_ARG, with nothing written, for both or neither image pointer, a NULL taps or
+ *   out, klen even or outside [1, 31], out_f32_chw == img_f32_chw.
+ * Both: no allocation, no host synchronisation. */
+int mpx_rank_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* rank, const int32_t* thresh, int M,
+                   const float* fill_f32_chw, int keep_top, const float mean[3], const float std[3], int slot0, float* out_f32_nchw,
+                   void* stream);
+int mpx_blur_fill(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* taps, int klen, const float mean[3],
+                  const float std[3], float* out_f32_chw, void* stream);
+
 /* ---- K0 of the small networks: the CIFAR / MNIST scorers' mask convention ---------------------------
  * replaces: the in-place min-max rescale of the picture to [0,255] (generate_gp_training_data_cifar.py:274-279,
  *           generate_gp_training_data_mnist.py:167-171), `mask.fill(255); mask[segments == segVal] = 0` for the SELECTED

@@ -183,9 +183,14 @@ SIGNATURES = {
     "mpx_rise_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _fp, _fp, _i, _vp, _vp]),
     "mpx_softmask_saliency": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "mpx_rise_saliency": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # a second pixel source (csrc/mpx_rankmask.h): rows selected between the image and a fill image on a per-pixel rank; RISE's blur
+    "mpx_rank_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _fp, _fp, _i, _vp, _vp]),
+    "mpx_blur_fill": (_i, [_vp, _vp, _vp, _fp, _i, _fp, _fp, _vp, _vp]),
 }
 
 SOFTMASK_TILE = 32      # csrc/mpx_softmask.h SM_MT: the masks one block of the apply kernels loops over
+RANKMASK_TILE = 32      # csrc/mpx_rankmask.h RM_MT: the rows one block of rank_apply_kernel loops over
+BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes
 
 _lib = None
 

@@ -531,3 +531,18 @@ def rise_saliency(model, image, label, n_masks=4000, s=7, p1=0.5, seed=0, out=No
     masks summed with their class scores on the device and divided by n_masks * p1 (engine.MaskedForwardEngine.rise_saliency).  The masks
     are real-valued per pixel, so they always take the conv staging; every 224 x 224 network the engine serves takes them."""
     return model.rise_saliency(image, label, n_masks=n_masks, s=s, p1=p1, seed=seed, out=out)
+
+
+def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
+    """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
+    salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on
+    a blurred image (insertion: a HIGH area is good).  -> {thresholds, del_scores, ins_scores, del_pred, ins_pred, del_auc, ins_auc}
+    (engine.MaskedForwardEngine.deletion_insertion).  saliency: a host array or the device map rise_saliency(out=...) returned.  Always
+    the conv staging; every 224 x 224 network the engine serves takes it."""
+    return model.deletion_insertion(image, saliency, label, step=step, del_fill=del_fill, ins_fill=ins_fill, taps=taps)
+
+
+def deletion_insertion_many(model, images, saliencies, labels, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
+    """deletion_insertion over several images, their rows packed into full forward batches with one download of all scores
+    (engine.MaskedForwardEngine.deletion_insertion_many); every image scores as it does alone."""
+    return model.deletion_insertion_many(images, saliencies, labels, step=step, del_fill=del_fill, ins_fill=ins_fill, taps=taps)

@@ -20,6 +20,7 @@
 #include "mpx_cnext.h"
 #include "mpx_attn.h"
 #include "mpx_softmask.h"
+#include "mpx_rankmask.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3412,6 +3413,66 @@ int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weig
 
 int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal, void* stream) {
     return soft_saliency<RiseWeights>(h, "rise_saliency", cells, shift, weight, M, s, sal, stream);
+}
+
+// ---- a second pixel source (mpx_rankmask.h): rows that select between the image and a fill image on a per-pixel rank, and RISE's blur ----
+int mpx_rank_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* rank, const int32_t* thresh, int M,
+                   const float* fill_f32_chw, int keep_top, const float mean[3], const float std[3], int slot0, float* out_f32_nchw,
+                   void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "rank_apply: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's");
+    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "rank_apply: exactly one of img_u8_hwc / img_f32_chw must be given");
+    if (!rank || !thresh) return fail(h, MPX_E_ARG, "rank_apply: null rank or thresh pointer");
+    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "rank_apply: mean/std required for u8 input");
+    if (keep_top != 0 && keep_top != 1) return fail(h, MPX_E_ARG, "rank_apply: keep_top=%d is neither 0 nor 1", keep_top);
+    if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
+        return fail(h, MPX_E_ARG, "rank_apply: slots [%d,%lld) outside [0, max_batch=%d)", slot0, (long long)slot0 + M, h->max_batch);
+    if (M == 0) return 0;
+    RankParams p;
+    std::memset(&p, 0, sizeof p);
+    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw;
+    p.rank = rank; p.thresh = thresh; p.fill = fill_f32_chw;
+    p.out_hi = h->in_hi; p.out_lo = h->in_lo; p.out_f32 = out_f32_nchw;
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean ? mean[c] : 0.f;
+        p.std[c] = std ? std[c] : 1.f;
+    }
+    p.M = M; p.slot0 = slot0; p.keep_top = keep_top;
+    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 1, -1);
+    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + RM_MT - 1) / RM_MT);
+    hipLaunchKernelGGL(rank_apply_kernel, grid, dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
+    return 0;
+}
+
+int mpx_blur_fill(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* taps, int klen, const float mean[3],
+                  const float std[3], float* out_f32_chw, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "blur_fill: this engine runs one of the small networks (no 224 x 224 input)");
+    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "blur_fill: exactly one of img_u8_hwc / img_f32_chw must be given");
+    if (!taps || !out_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: null taps or out pointer");
+    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "blur_fill: mean/std required for u8 input");
+    if (klen < 1 || klen > BF_KMAX || (klen & 1) == 0) return fail(h, MPX_E_ARG, "blur_fill: klen=%d is not an odd number in [1, %d]", klen, BF_KMAX);
+    if (out_f32_chw == img_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: out_f32_chw must not be the image (every block reads its neighbours' pixels)");
+    BlurParams p;
+    std::memset(&p, 0, sizeof p);
+    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw; p.out = out_f32_chw;
+    for (int k = 0; k < klen; ++k) p.taps[k] = taps[k];
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean ? mean[c] : 0.f;
+        p.std[c] = std ? std[c] : 1.f;
+    }
+    p.klen = klen; p.size = MPX_IMG;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    dim3 grid((MPX_IMG + BF_TW - 1) / BF_TW, (MPX_IMG + BF_TH - 1) / BF_TH, 3);
+    hipLaunchKernelGGL(blur_fill_kernel, grid, dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
 }
 
 int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg, int S,

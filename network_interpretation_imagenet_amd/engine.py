@@ -995,6 +995,165 @@ class MaskedForwardEngine:
         sal.div_(float(n_masks) * float(p1))
         return sal.cpu().numpy() if out is None else sal
 
+    # ---- a second pixel source (csrc/mpx_rankmask.h): rows selected on a per-pixel rank, the blurred image, the causal metrics ----
+    def _chw_to_device(self, t, name):
+        """A host or device f32[3,224,224] as a contiguous device tensor."""
+        t = torch.as_tensor(t)
+        if t.dtype != torch.float32 or tuple(t.shape) != (3, IMG, IMG):
+            raise ValueError("%s must be float32[3,224,224], got %s%s" % (name, t.dtype, tuple(t.shape)))
+        if t.is_cuda and t.device != self.device:
+            raise ValueError("%s must be a host array or a tensor on %s" % (name, self.device))
+        return t.contiguous().to(self.device)
+
+    def blur_fill(self, image, taps=None, out=None):
+        """mpx_blur_fill: -> device f32[3,224,224], the separable correlation of the normalised image with `taps` (host f32[klen], klen odd
+        in [1, 31]; None = masks.gaussian_taps(), RISE's klen 11 and sigma 5), zero padding -- masks.blur_fill(x, taps) bit for bit.  image:
+        u8[224,224,3] or normalised f32[3,224,224], host or device; out: a contiguous device f32[3,224,224] to write into (not the image)."""
+        if self.small:
+            raise ValueError("%s has no 224 x 224 input to blur" % self.arch)
+        taps = masks.gaussian_taps() if taps is None else masks._check_taps(taps)
+        img_d = self._image_to_device(image)
+        if out is None:
+            out = torch.empty(3, IMG, IMG, dtype=torch.float32, device=self.device)
+        u8, f32 = self._soft_args(img_d, None, 0)
+        if out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (3, IMG, IMG) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32[3,224,224] tensor on %s" % self.device)
+        _lib.check(self._h, self._lib.mpx_blur_fill(self._h, u8, f32, taps.ctypes.data_as(C.POINTER(C.c_float)), int(taps.size), self._mean,
+                                                    self._std, _ptr(out), self._stream()), "mpx_blur_fill")
+        return out
+
+    def stage_rank_masks(self, image, rank, thresh, fill=None, keep_top=False, slot0=0, out_f32=None):
+        """mpx_rank_apply.  image as stage_masks; rank: device i32[224,224]; thresh: device i32[M]; fill: device f32[3,224,224] or None.
+        Fills input slots [slot0, slot0+M): row m takes pixel p from the image where (rank[p] < thresh[m]) == keep_top and from `fill`
+        elsewhere (None: image * 0.0, the binary masks' removed pixel) -- masks.rank_masks_apply bit for bit."""
+        if rank.device != self.device or rank.dtype != torch.int32 or tuple(rank.shape) != (IMG, IMG) or not rank.is_contiguous():
+            raise ValueError("rank must be a contiguous int32[224,224] tensor on %s" % self.device)
+        if thresh.device != self.device or thresh.dtype != torch.int32 or thresh.dim() != 1 or not thresh.is_contiguous():
+            raise ValueError("thresh must be a contiguous int32[M] tensor on %s" % self.device)
+        if fill is not None and (fill.device != self.device or fill.dtype != torch.float32 or tuple(fill.shape) != (3, IMG, IMG)
+                                 or not fill.is_contiguous()):
+            raise ValueError("fill must be a contiguous float32[3,224,224] tensor on %s" % self.device)
+        m = int(thresh.shape[0])
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_rank_apply(self._h, u8, f32, _ptr(rank), _ptr(thresh), m, _ptr(fill), int(bool(keep_top)), self._mean,
+                                                     self._std, int(slot0), _ptr(out_f32), self._stream()), "mpx_rank_apply")
+
+    def score_rank_masks(self, image, rank, thresh, label, fill=None, keep_top=False, return_logits=False):
+        """(image, rank i32[224,224], thresh i32[M], label) -> (score f32[M], pred i32[M][, logits f32[M,1000]]): the scores of the rows
+        masks.rank_masks_apply(x, rank, thresh, fill, keep_top) describes, staged by mpx_rank_apply (always the conv staging).  fill: None
+        or an f32[3,224,224], host or device.  Without a fill and with keep_top False, thresholds i * step give the scores of
+        score_masks(..., stem="conv") over the pseudo-segments rank // step bit for bit."""
+        rank, thresh = np.ascontiguousarray(rank), np.ascontiguousarray(thresh)
+        if rank.dtype != np.int32 or rank.shape != (IMG, IMG):
+            raise ValueError("rank must be int32[224,224], got %s%s" % (rank.dtype, rank.shape))
+        if thresh.dtype != np.int32 or thresh.ndim != 1:
+            raise ValueError("thresh must be int32[M], got %s%s" % (thresh.dtype, thresh.shape))
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        img_d = self._image_to_device(image)
+        fill_d = None if fill is None else self._chw_to_device(fill, "fill")
+        rank_d, thresh_d = torch.from_numpy(rank).to(self.device), torch.from_numpy(thresh).to(self.device)
+
+        def stage(s0, b):
+            self.stage_rank_masks(img_d, rank_d, thresh_d[s0:s0 + b], fill_d, keep_top, 0)
+
+        return self._score_staged(int(thresh.shape[0]), stage, label, return_logits)
+
+    def saliency_rank(self, sal):
+        """masks.saliency_rank on the device: device f32[224,224] -> device i32[224,224], rank[p] = the position of pixel p in the stable
+        sort by falling saliency (ties, +0.0 against -0.0 included, to the lower pixel index).  The key is 0 - sal, which is -sal with both
+        zeros as +0.0, so that a sort that orders bit patterns cannot tell them apart.  A NaN or an infinity raises ValueError, as on
+        the host (one flag is downloaded for it; the map is not)."""
+        self._sal_map(sal)
+        if not bool(torch.isfinite(sal).all()):
+            raise ValueError("saliency holds a NaN or an infinity: its pixels have no order")
+        order = torch.sort(0.0 - sal.flatten(), stable=True).indices
+        rank = torch.empty(IMG * IMG, dtype=torch.int32, device=self.device)
+        rank[order] = torch.arange(IMG * IMG, dtype=torch.int32, device=self.device)
+        return rank.view(IMG, IMG)
+
+    def _curve_fill(self, fill, img_d, taps, name):
+        """One image's fill: None, "blur" (mpx_blur_fill of the image), or an f32[3,224,224]."""
+        if fill is None:
+            return None
+        if isinstance(fill, str):
+            if fill != "blur":
+                raise ValueError('%s must be None, "blur" or a float32[3,224,224] image, got %r' % (name, fill))
+            return self.blur_fill(img_d, taps)
+        return self._chw_to_device(fill, name)
+
+    def deletion_insertion_many(self, images, saliencies, labels, step=masks.CURVE_STEP, del_fill=None, ins_fill="blur", taps=None):
+        """The deletion and the insertion curve (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) of one saliency map per image -> a list of
+        dicts {thresholds i32[T], del_scores / ins_scores f32[T], del_pred / ins_pred i32[T], del_auc, ins_auc}, T = ceil(50176 / step) + 1.
+        Deletion row i replaces the thresholds[i] = min(i * step, 50176) most salient pixels by del_fill (None: zero, the binary masks'
+        removed pixel); insertion row i shows them on ins_fill ("blur": mpx_blur_fill of the image with `taps`, None = masks.gaussian_taps()).
+        A fill is None, "blur" or an f32[3,224,224] used for every image, or a list with one of these per image.  saliencies: host arrays
+        or device f32[224,224] tensors (what rise_saliency(out=...) returns: nothing is downloaded in between); the ranks are
+        masks.saliency_rank's.  The 2 T rows of consecutive images -- an image's deletion rows, then its insertion rows -- are packed into
+        forwards of up to max_batch slots, one mpx_rank_apply per (image, curve, row range); all scores stay on the device until ONE
+        download.  A row's bits depend neither on its slot nor on its neighbours: an image scores the same alone and packed."""
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        n = len(images)
+        if not (len(saliencies) == len(labels) == n):
+            raise ValueError("images, saliencies and labels must have the same length")
+        fills = []
+        for name, f in (("del_fill", del_fill), ("ins_fill", ins_fill)):
+            per_image = isinstance(f, (list, tuple))
+            if per_image and len(f) != n:
+                raise ValueError("%s: a list needs one entry per image" % name)
+            fills.append(list(f) if per_image else [f] * n)
+        for lab in labels:
+            if not 0 <= int(lab) < NUM_CLASSES:
+                raise ValueError("label %r outside [0,1000)" % (lab,))
+        if taps is not None:
+            taps = masks._check_taps(taps)
+        thresh = masks.curve_thresholds(step)
+        t_rows = int(thresh.size)
+        if n == 0:
+            return []
+        thresh_d = torch.from_numpy(thresh).to(self.device)
+        total = 2 * t_rows * n
+        label_rows = torch.from_numpy(np.repeat(np.asarray([int(v) for v in labels], dtype=np.int32), 2 * t_rows)).to(self.device)
+        score = torch.empty(total, dtype=torch.float32, device=self.device)
+        pred = torch.empty(total, dtype=torch.int32, device=self.device)
+        done = used = 0         # rows already handed to a forward; slots staged for the next one
+
+        def flush():
+            nonlocal done, used
+            self.forward(used, label_rows[done:done + used], score_out=score[done:done + used], pred_out=pred[done:done + used])
+            done += used
+            used = 0
+
+        for i in range(n):
+            img_d = self._image_to_device(images[i])
+            sal = saliencies[i]
+            if isinstance(sal, torch.Tensor) and sal.is_cuda:
+                rank_d = self.saliency_rank(sal)
+            else:
+                rank_d = torch.from_numpy(masks.saliency_rank(np.asarray(sal))).to(self.device)
+            for keep_top, fill in ((False, self._curve_fill(fills[0][i], img_d, taps, "del_fill")),
+                                   (True, self._curve_fill(fills[1][i], img_d, taps, "ins_fill"))):
+                r = 0
+                while r < t_rows:
+                    take = min(t_rows - r, self.max_batch - used)
+                    self.stage_rank_masks(img_d, rank_d, thresh_d[r:r + take], fill, keep_top, used)
+                    used += take
+                    r += take
+                    if used == self.max_batch:
+                        flush()
+        if used:
+            flush()
+        score, pred = score.cpu().numpy().reshape(n, 2, t_rows), pred.cpu().numpy().reshape(n, 2, t_rows)
+        return [{"thresholds": thresh.copy(),
+                 "del_scores": score[i, 0].copy(), "ins_scores": score[i, 1].copy(),
+                 "del_pred": pred[i, 0].copy(), "ins_pred": pred[i, 1].copy(),
+                 "del_auc": masks.curve_auc(score[i, 0]), "ins_auc": masks.curve_auc(score[i, 1])} for i in range(n)]
+
+    def deletion_insertion(self, image, saliency, label, step=masks.CURVE_STEP, del_fill=None, ins_fill="blur", taps=None):
+        """deletion_insertion_many for one image: its deletion rows and its insertion rows go through the forward together."""
+        return self.deletion_insertion_many([image], [saliency], [label], step=step, del_fill=del_fill, ins_fill=ins_fill, taps=taps)[0]
+
     # ---- kernel variants (tuning / tests) ----
     def set_conv_tile(self, layer, tile):
         """Select the conv kernel variant of one layer (index or torchvision name); tile < 0 = default."""

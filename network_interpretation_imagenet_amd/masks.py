@@ -6,6 +6,9 @@ order; the reference only ever uses contiguous windows of k = int(0.4*S) labels
 
 The second convention, real-valued per-pixel masks, has its host side here too: RISE's draws (rise_cells, rise_shifts, rise_masks) and
 rise_weights, the numpy fp32 restatement of the weights csrc/mpx_softmask.h synthesises on the device.
+
+The deletion / insertion curves that score a saliency map (saliency_rank, curve_thresholds, rank_masks_apply, gaussian_taps, blur_fill,
+curve_auc) restate csrc/mpx_rankmask.h the same way.
 """
 import random
 
@@ -152,6 +155,111 @@ def rise_weights(cells, shifts, s):
         bot = omx * g[mi, i1, j0] + fx * g[mi, i1, j1]
         out[a:b] = omy * top + fy * bot
     return out
+
+
+# ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------
+# The numpy restatements csrc/mpx_rankmask.h is held to bit for bit: a rank per pixel, a threshold per row, a fill image.
+BLUR_KLEN_MAX = 31                  # csrc/mpx_rankmask.h BF_KMAX
+CURVE_STEP = RISE_IMG * 8           # RISE's default: 8 image rows' worth of pixels per step, 29 rows per curve
+
+
+def saliency_rank(sal):
+    """i32[224,224]: rank[p] = the position of pixel p when the pixels are sorted by falling saliency -- order = argsort(-sal.ravel(),
+    kind="stable"), rank[order[k]] = k.  Ties, +0.0 against -0.0 included, go to the lower pixel index (raster order).  A map with a NaN or
+    an infinity has no such order: ValueError."""
+    sal = np.asarray(sal)
+    if sal.shape != (RISE_IMG, RISE_IMG) or not np.issubdtype(sal.dtype, np.floating):
+        raise ValueError("saliency must be a floating-point [224,224] map, got %s%s" % (sal.dtype, sal.shape))
+    if not np.isfinite(sal).all():
+        raise ValueError("saliency holds a NaN or an infinity: its pixels have no order")
+    order = np.argsort(-sal.ravel(), kind="stable")
+    rank = np.empty(order.size, dtype=np.int32)
+    rank[order] = np.arange(order.size, dtype=np.int32)
+    return rank.reshape(RISE_IMG, RISE_IMG)
+
+
+def curve_thresholds(step, hw=RISE_IMG * RISE_IMG):
+    """i32[n_steps + 1]: n_i = min(i * step, hw) pixels are replaced (deletion) or revealed (insertion) in row i, n_steps = ceil(hw / step).
+    step = 224 * 8 -> 29 rows, 0 .. 50176."""
+    step, hw = int(step), int(hw)
+    if step <= 0 or hw <= 0:
+        raise ValueError("step and hw must be positive, got step=%r hw=%r" % (step, hw))
+    n_steps = -(-hw // step)
+    return np.minimum(np.arange(n_steps + 1, dtype=np.int64) * step, hw).astype(np.int32)
+
+
+def rank_masks_apply(x, rank, thresh, fill=None, keep_top=False):
+    """f32[M,3,224,224], what mpx_rank_apply stages (bit for bit): row m takes pixel p from x where (rank[p] < thresh[m]) == keep_top and
+    from the fill image elsewhere.  fill None: x * 0.0f, the removed pixel of the binary masks (-0.0 under a negative pixel).
+    keep_top False = a deletion curve's rows, True = an insertion curve's."""
+    x = np.asarray(x)
+    rank, thresh = np.asarray(rank), np.asarray(thresh)
+    if x.dtype != np.float32 or x.shape != (3, RISE_IMG, RISE_IMG):
+        raise ValueError("x must be float32[3,224,224], got %s%s" % (x.dtype, x.shape))
+    if rank.dtype != np.int32 or rank.shape != (RISE_IMG, RISE_IMG):
+        raise ValueError("rank must be int32[224,224], got %s%s" % (rank.dtype, rank.shape))
+    if thresh.dtype != np.int32 or thresh.ndim != 1:
+        raise ValueError("thresh must be int32[M], got %s%s" % (thresh.dtype, thresh.shape))
+    if fill is None:
+        fill = x * np.float32(0.0)
+    else:
+        fill = np.asarray(fill)
+        if fill.dtype != np.float32 or fill.shape != x.shape:
+            raise ValueError("fill must be float32[3,224,224], got %s%s" % (fill.dtype, fill.shape))
+    top = (rank[None] < thresh[:, None, None])[:, None]
+    return np.where(top, x[None], fill[None]) if keep_top else np.where(top, fill[None], x[None])
+
+
+def _check_taps(taps):
+    taps = np.asarray(taps)
+    if taps.dtype != np.float32 or taps.ndim != 1 or not 1 <= taps.size <= BLUR_KLEN_MAX or taps.size % 2 == 0:
+        raise ValueError("taps must be float32[klen], klen odd in [1, %d], got %s%s" % (BLUR_KLEN_MAX, taps.dtype, taps.shape))
+    return np.ascontiguousarray(taps)
+
+
+def gaussian_taps(klen=11, sigma=5.0):
+    """f32[klen]: the sampled Gaussian exp(-(k - r)^2 / (2 sigma^2)), r = klen // 2, normalised to sum 1 in fp64, then rounded to fp32.
+    The outer product of these taps with themselves is a normalised sampled 2-D Gaussian.  (RISE's own `gkern` filters an impulse with
+    scipy's gaussian_filter instead; it is separable too, and a caller who wants it passes its 1-D profile as `taps`.)"""
+    klen = int(klen)
+    if not 1 <= klen <= BLUR_KLEN_MAX or klen % 2 == 0 or not float(sigma) > 0.0:
+        raise ValueError("klen odd in [1, %d] and sigma > 0, got klen=%r sigma=%r" % (BLUR_KLEN_MAX, klen, sigma))
+    d = np.arange(klen, dtype=np.float64) - (klen // 2)
+    g = np.exp(-(d * d) / (2.0 * float(sigma) ** 2))
+    return (g / g.sum()).astype(np.float32)
+
+
+def _correlate_last(v, taps):
+    """acc = fl(acc + fl(t[k] * v[.., x + k - r])) over the k whose pixel lies inside, k ascending, from +0.0, along the last axis."""
+    n, klen = v.shape[-1], taps.size
+    r = klen // 2
+    acc = np.zeros_like(v)
+    for k in range(klen):
+        d = k - r
+        lo, hi = max(0, -d), min(n, n - d)          # the x with 0 <= x + d < n
+        if lo < hi:
+            acc[..., lo:hi] = acc[..., lo:hi] + taps[k] * v[..., lo + d:hi + d]
+    return acc
+
+
+def blur_fill(x, taps):
+    """f32[3,224,224], what mpx_blur_fill writes (bit for bit): the separable correlation of x with taps, zero padding, in fp32 in the written
+    order -- the row pass h, then the same along y over h; every product and every sum rounded on its own.  With gaussian_taps() this is
+    RISE's insertion substrate, its Conv2d(3, 3, klen, padding=klen // 2) applied to the normalised image."""
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.shape != (3, RISE_IMG, RISE_IMG):
+        raise ValueError("x must be float32[3,224,224], got %s%s" % (x.dtype, x.shape))
+    taps = _check_taps(taps)
+    h = _correlate_last(x, taps)
+    return np.ascontiguousarray(_correlate_last(h.transpose(0, 2, 1), taps).transpose(0, 2, 1))
+
+
+def curve_auc(scores):
+    """(sum(s) - s[0] / 2 - s[-1] / 2) / (len(s) - 1) in fp64: the trapezoid rule on a unit interval, RISE's `auc`."""
+    s = np.asarray(scores, dtype=np.float64)
+    if s.ndim != 1 or s.size < 2:
+        raise ValueError("a curve needs at least two scores, got shape %s" % (s.shape,))
+    return float((s.sum() - s[0] / 2 - s[-1] / 2) / (s.size - 1))
 
 
 # ---- the small networks' sampler (SURVEY.md 8 f4) ------------------------------------------------------------------------

@@ -604,6 +604,33 @@ int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weig
 int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal,
                       void* stream);
 
+/* ---- many classes from the same forwards: K gathers per row of logits, and the saliency sum with a tile of classes per thread --------
+ * extends: mpx_head_softmax_gather (one label per row) and mpx_softmask_saliency / mpx_rise_saliency (one weight per mask) to RISE's
+ *          estimator as published, sal[k] = sum_m p_k(I * M_m) * M_m for every class k of the SAME forwards (csrc/mpx_saliency_classes.h).
+ * mpx_softmax_gather_classes: logits DEV f32[B][logit_pitch] (mpx_forward's logits_out), classes DEV i32[K] or NULL (class k = k, and then
+ *   K must be num_classes), scores DEV f32[B][score_pitch], score_pitch >= K.
+ *     scores[b * score_pitch + k] = softmax(logits[b])[classes[k]]
+ *   BIT FOR BIT what mpx_head_softmax_gather writes as score[b] for label[b] = classes[k]: one wave per row, lane l sums the terms
+ *   expf(row[i] - max) of columns l, l + 64, .. in order, the lanes are reduced by xor-shuffles 32, 16, .., 1, the output is one correctly
+ *   rounded division expf(row[c] - max) / sum.  A class outside [0, num_classes) gives 0.0f.  The padding [K, score_pitch) of a row is not
+ *   written.  No argmax is returned (mpx_forward's pred is that).
+ * mpx_softmask_saliency_classes / mpx_rise_saliency_classes: weights / cells / shift / s as the single-class entries, scores DEV
+ *   f32[M][score_pitch], sal DEV f32[K][224][224].  For every class k and pixel p, for m = 0 .. M - 1 in this order, from the value
+ *   already in sal:
+ *     sal[k][p] <- fl(sal[k][p] + fl(scores[m * score_pitch + k] * w_m(p)))
+ *   a multiply and an add, each rounded to fp32 -- not an FMA; w_m(p) is the weight of the apply entries.  Map k is BIT FOR BIT what
+ *   mpx_softmask_saliency / mpx_rise_saliency leave in sal[k] when called with weight[m] = scores[m * score_pitch + k].  One thread owns a
+ *   pixel and a tile of classes and walks the masks in order (no atomics, no reduction tree): the bits depend neither on the launch
+ *   geometry nor on how the rows are cut into consecutive calls.  Nothing is read beyond scores[..][K) or written beyond sal[K).
+ * All three: MPX_E_STATE on the small networks; MPX_E_ARG, with nothing launched, for a NULL pointer (classes excepted), B, M or K <= 0,
+ * score_pitch < K, classes == NULL with K != num_classes, s outside [2, 32]. */
+int mpx_softmax_gather_classes(mpx_engine* h, const float* logits, const int32_t* classes, int K, float* scores, int score_pitch, int B,
+                               void* stream);
+int mpx_softmask_saliency_classes(mpx_engine* h, const float* weights, const float* scores, int score_pitch, int M, int K, float* sal,
+                                  void* stream);
+int mpx_rise_saliency_classes(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* scores, int score_pitch, int M,
+                              int K, int s, float* sal, void* stream);
+
 /* ---- a second pixel source for the staging: rows selected on a per-pixel rank, and the blurred image ------------------------------
  * extends: mpx_mask_apply_normalize and the soft-mask entries, whose removed pixel is always zero, to a FILL IMAGE: row m takes the pixels
  *          of rank below thresh[m] from one source and the others from the other.  There is no reference line: these are the rows of the

@@ -183,6 +183,10 @@ SIGNATURES = {
     "mpx_rise_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _fp, _fp, _i, _vp, _vp]),
     "mpx_softmask_saliency": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "mpx_rise_saliency": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    # many classes from the same forwards (csrc/mpx_saliency_classes.h): K gathers per row of logits, the class-tiled saliency sums
+    "mpx_softmax_gather_classes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "mpx_softmask_saliency_classes": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mpx_rise_saliency_classes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     # a second pixel source (csrc/mpx_rankmask.h): rows selected between the image and a fill image on a per-pixel rank; RISE's blur
     "mpx_rank_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _fp, _fp, _i, _vp, _vp]),
     "mpx_blur_fill": (_i, [_vp, _vp, _vp, _fp, _i, _fp, _fp, _vp, _vp]),
@@ -190,6 +194,7 @@ SIGNATURES = {
 
 SOFTMASK_TILE = 32      # csrc/mpx_softmask.h SM_MT: the masks one block of the apply kernels loops over
 RANKMASK_TILE = 32      # csrc/mpx_rankmask.h RM_MT: the rows one block of rank_apply_kernel loops over
+SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes
 
 _lib = None

@@ -533,6 +533,15 @@ def rise_saliency(model, image, label, n_masks=4000, s=7, p1=0.5, seed=0, out=No
     return model.rise_saliency(image, label, n_masks=n_masks, s=s, p1=p1, seed=seed, out=out)
 
 
+def rise_saliency_classes(model, image_u8, classes=None, top=None, n_masks=4000, s=7, p1=0.5, seed=0, out=None):
+    """RISE's maps of SEVERAL classes from one pass over the masks: -> (classes i32[K], sal f32[K,224,224]).  classes: a sequence of class
+    indices; top=k: the k largest logits of the unmasked image; neither: all 1000.  Map i is rise_saliency(model, image, classes[i], ...)
+    bit for bit -- the same masks, the same forwards, each mask's weight computed once and spent on every class
+    (engine.MaskedForwardEngine.rise_saliency_classes).  The curves of several classes need nothing new: pass the image once per class to
+    deletion_insertion_many, with its map and its class."""
+    return model.rise_saliency_classes(image_u8, classes=classes, top=top, n_masks=n_masks, s=s, p1=p1, seed=seed, out=out)
+
+
 def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
     """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
     salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on

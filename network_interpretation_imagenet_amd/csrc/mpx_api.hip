@@ -20,6 +20,7 @@
 #include "mpx_cnext.h"
 #include "mpx_attn.h"
 #include "mpx_softmask.h"
+#include "mpx_saliency_classes.h"
 #include "mpx_rankmask.h"
 
 #include <algorithm>
@@ -3413,6 +3414,62 @@ int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weig
 
 int mpx_rise_saliency(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* weight, int M, int s, float* sal, void* stream) {
     return soft_saliency<RiseWeights>(h, "rise_saliency", cells, shift, weight, M, s, sal, stream);
+}
+
+// ---- many classes from the same forwards (mpx_saliency_classes.h): K gathers per row of logits, the saliency sum with a tile of classes ----
+int mpx_softmax_gather_classes(mpx_engine* h, const float* logits, const int32_t* classes, int K, float* scores, int score_pitch, int B,
+                               void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "softmax_gather_classes: this engine runs one of the small networks (no 224 x 224 input)");
+    if (!logits || !scores) return fail(h, MPX_E_ARG, "softmax_gather_classes: null pointer");
+    if (B <= 0 || K <= 0) return fail(h, MPX_E_ARG, "softmax_gather_classes: B=%d K=%d", B, K);
+    if (score_pitch < K) return fail(h, MPX_E_ARG, "softmax_gather_classes: score_pitch=%d < K=%d", score_pitch, K);
+    if (!classes && K != h->ncls) return fail(h, MPX_E_ARG, "softmax_gather_classes: classes == NULL means all %d classes, K=%d", h->ncls, K);
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_gather_classes_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, classes, K, scores, score_pitch, B, h->ncls,
+                       h->logit_pitch);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+extern "C++" {
+template <class WS>
+static int soft_saliency_classes(mpx_engine* h, const char* what, const void* mask, const void* mask2, const float* scores, int score_pitch,
+                                 int M, int K, int s, float* sal, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks (no 224 x 224 input)", what);
+    if (WS::kLds && (s < SM_S_MIN || s > SM_S_MAX)) return fail(h, MPX_E_ARG, "%s: s=%d outside [%d, %d]", what, s, SM_S_MIN, SM_S_MAX);
+    if (!mask || (WS::kLds && !mask2) || !scores || !sal) return fail(h, MPX_E_ARG, "%s: null pointer", what);
+    if (M <= 0 || K <= 0) return fail(h, MPX_E_ARG, "%s: M=%d K=%d", what, M, K);
+    if (score_pitch < K) return fail(h, MPX_E_ARG, "%s: score_pitch=%d < K=%d", what, score_pitch, K);
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (WS::kLds) {
+        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
+        soft_rise_geometry(p, s);
+    } else {
+        p.weights = (const float*)mask;
+    }
+    p.score = scores; p.sal = sal; p.M = M;
+    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((MPX_IMG * MPX_IMG + SC_THREADS - 1) / SC_THREADS, (K + SC_KT - 1) / SC_KT);
+    hipLaunchKernelGGL(saliency_classes_kernel<WS>, grid, dim3(SC_THREADS), WS::lds_bytes(s), st, p, score_pitch, K);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+
+int mpx_softmask_saliency_classes(mpx_engine* h, const float* weights, const float* scores, int score_pitch, int M, int K, float* sal,
+                                  void* stream) {
+    return soft_saliency_classes<ExplicitWeights>(h, "softmask_saliency_classes", weights, nullptr, scores, score_pitch, M, K, 0, sal, stream);
+}
+
+int mpx_rise_saliency_classes(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* scores, int score_pitch, int M, int K,
+                              int s, float* sal, void* stream) {
+    return soft_saliency_classes<RiseWeights>(h, "rise_saliency_classes", cells, shift, scores, score_pitch, M, K, s, sal, stream);
 }
 
 // ---- a second pixel source (mpx_rankmask.h): rows that select between the image and a fill image on a per-pixel rank, and RISE's blur ----

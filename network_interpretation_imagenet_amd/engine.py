@@ -995,6 +995,160 @@ class MaskedForwardEngine:
         sal.div_(float(n_masks) * float(p1))
         return sal.cpu().numpy() if out is None else sal
 
+    # ---- many classes from the same forwards (csrc/mpx_saliency_classes.h): K gathers per row of logits, the class-tiled sums ----
+    def _classes_to_device(self, classes):
+        """None (all classes) or a device i32[K] tensor of a host sequence / tensor of class indices -> (device tensor or None, K)."""
+        if classes is None:
+            return None, self.num_classes
+        t = classes if isinstance(classes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(classes, dtype=np.int32))
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() == 0:
+            raise ValueError("classes must be a non-empty int32[K], got %s%s" % (t.dtype, tuple(t.shape)))
+        return t.contiguous().to(self.device), int(t.numel())
+
+    def _class_score_rows(self, scores, m, k, name="scores"):
+        """Rows of class scores: device f32[m, k] whose rows lie score_pitch = stride(0) >= k floats apart -> score_pitch."""
+        if (scores.device != self.device or scores.dtype != torch.float32 or tuple(scores.shape) != (m, k) or scores.stride(1) != 1
+                or (m > 1 and scores.stride(0) < k)):
+            raise ValueError("%s must be a float32[%d,%d] tensor on %s with unit column stride and a row stride >= %d"
+                             % (name, m, k, self.device, k))
+        return int(scores.stride(0)) if m > 1 else max(int(scores.stride(0)), k)
+
+    def class_scores(self, logits, classes=None, out=None):
+        """mpx_softmax_gather_classes: device f32[B, K], out[b][k] = softmax(logits[b])[classes[k]] -- the head's score for label classes[k]
+        bit for bit, for K classes of the same rows.  logits: what forward(want_logits=True) returns (device f32[B, num_classes], rows
+        logit_pitch apart); classes: None (all num_classes classes, K = num_classes) or int32[K] (a class outside [0, num_classes) scores
+        0.0); out: a device f32[B, K] with unit column stride (a column block of a wider tensor: its padding is not written)."""
+        if (logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] == 0
+                or logits.shape[1] not in (self.num_classes, self.logit_pitch) or logits.stride(1) != 1
+                or (logits.shape[0] > 1 and logits.stride(0) != self.logit_pitch)):
+            raise ValueError("logits must be float32[B,%d] on %s with rows %d floats apart (forward(want_logits=True))"
+                             % (self.num_classes, self.device, self.logit_pitch))
+        b = int(logits.shape[0])
+        cls_d, k = self._classes_to_device(classes)
+        if out is None:
+            out = torch.empty(b, k, dtype=torch.float32, device=self.device)
+        pitch = self._class_score_rows(out, b, k, "out")
+        _lib.check(self._h, self._lib.mpx_softmax_gather_classes(self._h, _ptr(logits), _ptr(cls_d), k, _ptr(out), pitch, b, self._stream()),
+                   "mpx_softmax_gather_classes")
+        return out
+
+    def _sal_maps(self, sal, k):
+        if sal.device != self.device or sal.dtype != torch.float32 or tuple(sal.shape) != (k, IMG, IMG) or not sal.is_contiguous():
+            raise ValueError("sal must be a contiguous float32[%d,224,224] tensor on %s" % (k, self.device))
+
+    def _sal_classes_args(self, scores, sal, m):
+        if scores.dim() != 2 or sal.dim() != 3:
+            raise ValueError("scores must be float32[M,K] and sal float32[K,224,224]")
+        k = int(sal.shape[0])
+        self._sal_maps(sal, k)
+        return k, self._class_score_rows(scores, m, k)
+
+    def soft_saliency_accumulate_classes(self, weights, scores, sal):
+        """mpx_softmask_saliency_classes: sal[k][p] <- sal[k][p] + scores[m][k] * weights[m][p] for m ascending, in place (a rounded multiply
+        and a rounded add per step).  Map k is soft_saliency_accumulate(weights, scores[:, k], sal[k]) bit for bit; every weight is read once
+        per tile of _lib.SALIENCY_CLASS_TILE classes.  weights: device f32[M,224,224]; scores: device f32[M,K] (class_scores' output);
+        sal: device f32[K,224,224]."""
+        m = self._soft_weights(weights)
+        k, pitch = self._sal_classes_args(scores, sal, m)
+        _lib.check(self._h, self._lib.mpx_softmask_saliency_classes(self._h, _ptr(weights), _ptr(scores), pitch, m, k, _ptr(sal),
+                                                                    self._stream()), "mpx_softmask_saliency_classes")
+        return sal
+
+    def rise_saliency_accumulate_classes(self, cells, shifts, s, scores, sal):
+        """mpx_rise_saliency_classes: soft_saliency_accumulate_classes with the weights synthesised from RISE's cells and shifts (as
+        stage_rise), once per mask and pixel for a whole tile of classes."""
+        m, s = self._rise_grids(cells, shifts, s)
+        k, pitch = self._sal_classes_args(scores, sal, m)
+        _lib.check(self._h, self._lib.mpx_rise_saliency_classes(self._h, _ptr(cells), _ptr(shifts), _ptr(scores), pitch, m, k, s, _ptr(sal),
+                                                                self._stream()), "mpx_rise_saliency_classes")
+        return sal
+
+    def _score_classes_staged(self, m, stage, cls_d, k, after=None):
+        """_score_staged's loop with the logits kept: chunks of up to max_batch rows run stage(s0, b) -> forward(want_logits=True) ->
+        class_scores on the stream; after(s0, b, scores_chunk), if given, runs behind each chunk.  -> (scores f32[m, k], pred i32[m]) on
+        the device."""
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        scores = torch.empty(m, k, dtype=torch.float32, device=self.device)
+        pred = torch.empty(m, dtype=torch.int32, device=self.device)
+        labels = torch.zeros(min(m, self.max_batch), dtype=torch.int32, device=self.device)    # the head's own gather is not used
+        unused = torch.empty_like(labels, dtype=torch.float32)
+        for s0 in range(0, m, self.max_batch):
+            b = min(self.max_batch, m - s0)
+            stage(s0, b)
+            logits = self.forward(b, labels[:b], want_logits=True, score_out=unused[:b], pred_out=pred[s0:s0 + b])[2]
+            self.class_scores(logits, cls_d, out=scores[s0:s0 + b])
+            if after is not None:
+                after(s0, b, scores[s0:s0 + b])
+        return scores, pred
+
+    def score_soft_masks_classes(self, image, weights, classes):
+        """score_soft_masks for several classes of the same forwards: -> (scores f32[M,K], pred i32[M]); column i is
+        score_soft_masks(image, weights, classes[i])'s scores bit for bit.  classes: a sequence of class indices, or None for all."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        w = np.ascontiguousarray(weights)
+        if w.dtype != np.float32 or w.ndim != 3 or w.shape[1:] != (IMG, IMG):
+            raise ValueError("weights must be float32[M,224,224], got %s%s" % (w.dtype, w.shape))
+        img_d = self._image_to_device(image)
+        cls_d, k = self._classes_to_device(cls)
+
+        def stage(s0, b):
+            self.stage_soft_masks(img_d, torch.from_numpy(w[s0:s0 + b]).to(self.device), 0)
+
+        scores, pred = self._score_classes_staged(int(w.shape[0]), stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def score_rise_classes(self, image, cells, shifts, s, classes):
+        """score_rise for several classes of the same forwards: -> (scores f32[M,K], pred i32[M]); column i is
+        score_rise(image, cells, shifts, s, classes[i])'s scores bit for bit.  classes: a sequence of class indices, or None for all."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        cells, shifts = masks.check_rise(cells, shifts, s)
+        img_d = self._image_to_device(image)
+        cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
+        cls_d, k = self._classes_to_device(cls)
+
+        def stage(s0, b):
+            self.stage_rise(img_d, cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, 0)
+
+        scores, pred = self._score_classes_staged(int(cells.shape[0]), stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def rise_saliency_classes(self, image, classes=None, top=None, n_masks=4000, s=7, p1=0.5, seed=0, out=None):
+        """RISE's estimator as published, sal[k] = sum_m p_k(I * M_m) * M_m / (n_masks * p1): the maps of K classes from ONE pass over the
+        masks of rise_saliency (masks.rise_masks(n_masks, s, p1, seed)).  -> (classes i32[K], sal f32[K,224,224]); map i is
+        rise_saliency(image, classes[i], ...) bit for bit.  Exactly one of classes (a sequence of indices in [0, 1000)) and top (an int:
+        the `top` largest logits of the unmasked forward, ties to the lower index) may be given; neither means all 1000 classes.
+        Chunks of max_batch masks run apply -> forward -> class_scores -> rise_saliency_accumulate_classes on the stream with no host round
+        trip in between.  out: None -> host arrays; a contiguous device f32[K,224,224] is overwritten with the maps and returned in
+        their place (nothing is downloaded)."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        if not 0.0 < float(p1) <= 1.0 or int(n_masks) <= 0:
+            raise ValueError("n_masks > 0 and p1 in (0, 1], got n_masks=%r p1=%r" % (n_masks, p1))
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        if top is not None:
+            logits = self.score_masks(image, np.zeros((IMG, IMG), dtype=np.int32), np.ones((1, 1), dtype=np.uint8), 0, return_logits=True)[3]
+            cls = masks.top_classes(logits[0], top)
+        cells, shifts = masks.rise_masks(n_masks, s, p1, seed)
+        cls_d, k = self._classes_to_device(cls)
+        sal = torch.zeros(k, IMG, IMG, dtype=torch.float32, device=self.device) if out is None else out
+        self._sal_maps(sal, k)
+        if out is not None:
+            sal.zero_()
+        img_d = self._image_to_device(image)
+        cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
+
+        def stage(s0, b):
+            self.stage_rise(img_d, cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, 0)
+
+        def after(s0, b, scores):
+            self.rise_saliency_accumulate_classes(cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, scores, sal)
+
+        self._score_classes_staged(int(n_masks), stage, cls_d, k, after=after)
+        sal.div_(float(n_masks) * float(p1))
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        return cls, (sal.cpu().numpy() if out is None else sal)
+
     # ---- a second pixel source (csrc/mpx_rankmask.h): rows selected on a per-pixel rank, the blurred image, the causal metrics ----
     def _chw_to_device(self, t, name):
         """A host or device f32[3,224,224] as a contiguous device tensor."""

@@ -157,6 +157,49 @@ def rise_weights(cells, shifts, s):
     return out
 
 
+def saliency_sum_classes(sal0, scores, w):
+    """f32[K,224,224]: the class-tiled saliency sum in numpy fp32, the restatement csrc/mpx_saliency_classes.h is held to bit for bit:
+    sal[k] <- fl(sal[k] + fl(scores[m][k] * w[m])) for m ascending, from sal0 -- a rounded product and a rounded sum, no FMA.
+    sal0 f32[K,H,W], scores f32[M,K], w f32[M,H,W].  Column k is the single-class sum with weight[m] = scores[m][k]."""
+    acc = np.array(sal0, dtype=np.float32, copy=True)
+    scores, w = np.asarray(scores, dtype=np.float32), np.asarray(w, dtype=np.float32)
+    if acc.ndim != 3 or scores.ndim != 2 or w.ndim != 3 or scores.shape != (w.shape[0], acc.shape[0]) or w.shape[1:] != acc.shape[1:]:
+        raise ValueError("sal0 [K,H,W], scores [M,K], w [M,H,W]; got %s, %s, %s" % (acc.shape, scores.shape, w.shape))
+    for m in range(scores.shape[0]):
+        prod = scores[m][:, None, None] * w[m][None]
+        acc = acc + prod
+    return acc
+
+
+def class_selection(classes, top, num_classes=1000):
+    """The classes a many-class call names: at most one of `classes` (a non-empty sequence of indices in [0, num_classes)) and `top` (an int
+    in [1, num_classes]: that many of the largest logits) -> (i32[K] or None, top or None); (None, None) means all num_classes classes.
+    ValueError otherwise -- checked on the host before anything is uploaded."""
+    if classes is not None and top is not None:
+        raise ValueError("give classes or top, not both")
+    if top is not None:
+        if isinstance(top, bool) or int(top) != top or not 0 < int(top) <= num_classes:
+            raise ValueError("top=%r outside [1, %d]" % (top, num_classes))
+        return None, int(top)
+    if classes is None:
+        return None, None
+    cls = np.asarray(classes)
+    if cls.ndim != 1 or cls.size == 0 or cls.dtype.kind not in "iu":
+        raise ValueError("classes must be a non-empty sequence of integers, got %s%s" % (cls.dtype, cls.shape))
+    if cls.min() < 0 or cls.max() >= num_classes:
+        raise ValueError("classes outside [0,%d): [%d, %d]" % (num_classes, cls.min(), cls.max()))
+    return np.ascontiguousarray(cls, dtype=np.int32), None
+
+
+def top_classes(logits, k):
+    """i32[k]: the classes of the k largest logits, ties to the lower index (a stable sort of the negated logits)."""
+    logits = np.asarray(logits).reshape(-1)
+    k = int(k)
+    if not 0 < k <= logits.size:
+        raise ValueError("top=%r outside [1, %d]" % (k, logits.size))
+    return np.argsort(-logits, kind="stable")[:k].astype(np.int32)
+
+
 # ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------
 # The numpy restatements csrc/mpx_rankmask.h is held to bit for bit: a rank per pixel, a threshold per row, a fill image.
 BLUR_KLEN_MAX = 31                  # csrc/mpx_rankmask.h BF_KMAX

@@ -190,15 +190,6 @@ struct SeLayer {
     bool loaded = false;
 };
 
-constexpr int kProfSubDw = -100;    // ProfRec::sub of depthwise layer k is kProfSubDw - k
-constexpr int kProfSubPool3c = -1000000;    // ... of GoogLeNet's clipped max pool k (mpx_engine::pools3c) kProfSubPool3c - k
-constexpr int kProfSubShuffle = -2000000;   // ... of ShuffleNetV2's channel shuffle k (mpx_engine::shuffles) kProfSubShuffle - k
-constexpr int kProfSubSeGate = -3000000;    // ... of SE layer k (mpx_engine::ses; EfficientNet, RegNetY): its gate launch kProfSubSeGate - k,
-constexpr int kProfSubSeScale = -4000000;   //     its scale launch kProfSubSeScale - k
-constexpr int kProfSubLnorm = -5000000;     // ... of ConvNeXt's stand-alone LayerNorm k (mpx_engine::lnorms) kProfSubLnorm - k
-constexpr int kProfSubAttn = -6000000;      // ... of a ViT's attention launch k (mpx_engine::attns) kProfSubAttn - k
-constexpr int kProfSubTokens = -7000000;    // ... of a ViT's token assembly
-
 // A channel shuffle of the op list (ShuffleNetV2; mpx_shuffle.h): a = Op::in at a_pitch, b = Op::res advanced by b_offset at b_pitch
 struct ShuffleOp {
     int side, bf, hp, a_pitch, b_pitch, b_offset;
@@ -209,12 +200,21 @@ struct ClipPool {
     int hin, stride, pad, pitch;
 };
 
+// The per-family list of the profile that a launch of kind 2 is booked on next to 'pool' (mpx_profile_collect*), in the order of the public
+// argument lists; `index` is the launch's position in that list (the engine's norm, depthwise layer, clipped pool ... k; 0 where the family is
+// one number).  PF_NONE: no list -- every launch of another kind, every plain pool, and every launch a stand-alone entry makes.
+enum ProfFamily { PF_NONE = 0, PF_NORM, PF_AVGPOOL2, PF_DW, PF_POOL3C, PF_SHUFFLE, PF_SE_GATE, PF_SE_SCALE, PF_LNORM, PF_ATTN, PF_TOKENS, PF_COUNT };
+
+struct ProfTag {
+    ProfFamily family = PF_NONE;
+    int index = 0;
+};
+
 struct ProfRec {
     hipEvent_t t0, t1;
     int kind;
     int conv;
-    int sub;        // kind 2: -1 = any pool, -2 = a DenseNet transition's average pool, k >= 0 = the launch of DenseNet norm k,
-                    // kProfSubDw - k = a depthwise layer k, kProfSubPool3c - k = GoogLeNet's clipped max pool k, kProfSubShuffle - k = ShuffleNetV2's shuffle k
+    ProfTag tag;
 };
 
 }  // namespace
@@ -226,25 +226,17 @@ struct mpx_engine {
     // the reference's two small networks (28x28x1 / 32x32x3, staging [B][H][W][32] read by a generic 3x3 conv, 10 classes)
     int img = MPX_IMG, in_ch = 3, ncls = MPX_NUM_CLASSES, logit_pitch = MPX_NUM_CLASSES;
     bool small = false;
-    bool vgg = false;               // torchvision VGG: a plain chain, two activation buffers, no 7x7 stem
-    bool alexnet = false;           // torchvision AlexNet: as VGG a plain chain over two activation buffers, staged through K0 only
     bool densenet = false;          // torchvision DenseNet (growth rate 32): the ResNet stem shape, dense blocks over a raw concatenation
     std::vector<NormLayer> norms;   // its stand-alone BatchNorms in forward order
-    bool mobilenet = false;         // torchvision MobileNetV2: inverted residuals over three activation buffers, staged through K0 only
-    std::vector<DwLayer> dws;       // its depthwise layers in forward order
-    bool squeezenet = false;        // torchvision SqueezeNet 1.1: Fire modules over three activation buffers, staged through K0 only
+    std::vector<DwLayer> dws;       // the depthwise layers in forward order (MobileNetV2, ShuffleNetV2, EfficientNet-B0, ConvNeXt)
     bool googlenet = false;         // torchvision GoogLeNet: Inception modules over three activation buffers, staged through K0 only
     std::vector<ClipPool> pools3c;  // its clipped-window 3x3 max pools in forward order
-    bool shufflenet = false;        // torchvision ShuffleNetV2: split / shuffle blocks over three activation buffers, staged through K0 only
-    std::vector<ShuffleOp> shuffles;    // its channel shuffles in forward order
-    bool efficientnet = false;      // torchvision EfficientNet-B0: MBConv blocks with SE over three activation buffers, staged through K0 only
-    std::vector<SeLayer> ses;       // its Squeeze-and-Excitation layers in forward order (a RegNetY engine's too)
+    std::vector<ShuffleOp> shuffles;    // ShuffleNetV2's channel shuffles in forward order
+    std::vector<SeLayer> ses;       // the Squeeze-and-Excitation layers in forward order (EfficientNet-B0, RegNetY)
     float* se_gate = nullptr;       // f32[max_batch][se_pitch_max]: the gates of the SE layer in flight
     int se_pitch_max = 0;
-    bool convnext = false;          // torchvision ConvNeXt-Tiny / -Small: CNBlocks over three activation buffers, staged through K0 only
-    std::vector<LnLayer> lnorms;    // its stand-alone LayerNorms in forward order
-    bool regnet = false;            // torchvision RegNetX 400MF .. 8GF: bottleneck blocks with a grouped 3x3 over four activation buffers, staged through K0 only
-    bool regnet_y = false;          // ... and RegNetY 800MF .. 8GF (regnet is set too): an SE gate with ReLU between f.b and f.c of every block
+    std::vector<LnLayer> lnorms;    // the stand-alone LayerNorms in forward order (ConvNeXt, ViT)
+    bool regnet_y = false;          // torchvision RegNetY 800MF .. 8GF (a RegNetX trunk, build_topology_regnet): an SE gate with ReLU between f.b and f.c of every block
     bool vit = false;               // torchvision vit_b_16 / vit_b_32: an encoder over four activation buffers of sizes of their own, staged through K0 only
     int vit_T = 0, vit_D = 0;       // tokens per image (197 / 50) and width (768)
     std::vector<AttnLayer> attns;   // its attention launches in forward order
@@ -757,7 +749,6 @@ int build_topology_vgg(mpx_engine* h) {
         case 19: cfg = cfg_e; n = (int)(sizeof cfg_e / sizeof *cfg_e); break;
         default: return MPX_E_ARG;
     }
-    h->vgg = true;
     h->n_act_bufs = 2;
     h->act_elems_per_image = kVggActElemsPerImage;
     auto add_conv = [&](const std::string& name, const std::string& bn_name, int cin, int cout, int k, int pad, int hin, int relu, bool fc) {
@@ -819,7 +810,6 @@ int build_topology_vgg(mpx_engine* h) {
 // AdaptiveAvgPool2d((6, 6)) on a 6x6 map and Dropout in eval are identities.  The op list ping-pongs between two activation buffers.
 int build_topology_alexnet(mpx_engine* h) {
     if (h->arch != MPX_ARCH_ALEXNET) return MPX_E_ARG;
-    h->alexnet = true;
     h->n_act_bufs = 2;
     h->act_elems_per_image = kAlexActElemsPerImage;
     auto add_conv = [&](const char* name, int cin, int cout, int k, int stride, int pad, int hin, int relu, bool fc) {
@@ -978,7 +968,6 @@ int build_topology_densenet(mpx_engine* h) {
 // dead after the depthwise layer -- the block output, T2 the depthwise output.
 int build_topology_mobilenet(mpx_engine* h) {
     if (h->arch != MPX_ARCH_MOBILENET + 2) return MPX_E_ARG;
-    h->mobilenet = true;
     h->n_act_bufs = 3;
     h->act_elems_per_image = kMobileActElemsPerImage;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
@@ -1070,7 +1059,6 @@ int build_topology_mobilenet(mpx_engine* h) {
 // Buffers: three of 111 * 111 * 64 elements per image: X the module input, S the squeeze map, Y the concatenation, which is the next X.
 int build_topology_squeezenet(mpx_engine* h) {
     if (h->arch != MPX_ARCH_SQUEEZENET + 11) return MPX_E_ARG;
-    h->squeezenet = true;
     h->n_act_bufs = 3;
     h->act_elems_per_image = kSqueezeActElemsPerImage;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
@@ -1297,7 +1285,6 @@ int build_topology_shufflenet(mpx_engine* h) {
         case 20: w = widths[3]; break;
         default: return MPX_E_ARG;
     }
-    h->shufflenet = true;
     h->n_act_bufs = 3;
     h->act_elems_per_image = kShuffleActElemsPerImage;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
@@ -1425,7 +1412,6 @@ int build_topology_shufflenet(mpx_engine* h) {
 // -- dead after the depthwise layer -- the block output, T2 the depthwise output, scaled in place.  The gates: f32[max_batch][1152].
 int build_topology_efficientnet(mpx_engine* h) {
     if (h->arch != MPX_ARCH_EFFICIENTNET) return MPX_E_ARG;
-    h->efficientnet = true;
     h->n_act_bufs = 3;
     h->act_elems_per_image = kEffActElemsPerImage;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
@@ -1526,7 +1512,6 @@ int build_topology_convnext(mpx_engine* h) {
     if (h->arch == MPX_ARCH_CONVNEXT + 2) depths[2] = 27;
     else if (h->arch != MPX_ARCH_CONVNEXT + 1) return MPX_E_ARG;
     static const int dims[4] = {96, 192, 384, 768};
-    h->convnext = true;
     h->n_act_bufs = 3;
     h->act_elems_per_image = kCnextActElemsPerImage;
     auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int hin, int residual, int act, bool fc) {
@@ -1697,12 +1682,12 @@ struct ProfScope {
     mpx_engine* h;
     hipStream_t st;
     ProfRec* rec = nullptr;
-    ProfScope(mpx_engine* h_, hipStream_t st_, int kind, int conv, int sub = -1) : h(h_), st(st_) {
+    ProfScope(mpx_engine* h_, hipStream_t st_, int kind, int conv, ProfTag tag = ProfTag()) : h(h_), st(st_) {
         if (h->prof_on && h->prof_used < (int)h->prof_pool.size()) {
             rec = &h->prof_pool[h->prof_used++];
             rec->kind = kind;
             rec->conv = conv;
-            rec->sub = sub;
+            rec->tag = tag;
             h->prof_stream = st;
             (void)hipEventRecord(rec->t0, st);
         }
@@ -2179,7 +2164,6 @@ int build_topology_regnet(mpx_engine* h) {
     for (const Row& r : rows)
         if (r.id == h->arch) R = &r;
     if (!R) return MPX_E_ARG;
-    h->regnet = true;
     h->regnet_y = h->arch >= MPX_ARCH_REGNET_Y;
     auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
     size_t act_max = 0;
@@ -2602,9 +2586,160 @@ int build_fused(mpx_engine* h, int main) {
     return 0;
 }
 
-// one concat_bn_relu_kernel launch; `norm` = the engine's norm it runs for (profile record), -1 from the stand-alone entry
-int launch_catnorm(mpx_engine* h, const CatNormParams& p, int norm, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, norm);
+// ---- kernel arguments of the ops beside the convs ---------------------------------------------------------------------------------
+// One builder per *Params struct: the ONLY place that fills it and computes its derived fields (output side, pixel / row / unit counts,
+// channel range).  A stand-alone entry checks its arguments and calls the builder with them; mpx_forward's case calls it with the layer
+// record's fields.  The launchers below take the finished struct and the launch's profile tag (ProfTag() from a stand-alone entry).
+
+template <class P>
+P zeroed() {
+    P p;
+    std::memset(&p, 0, sizeof p);
+    return p;
+}
+
+template <class P>
+void set_planes(P& p, const void* x_hi, const void* x_lo, void* y_hi, void* y_lo) {
+    p.x_hi = (const half_t*)x_hi; p.x_lo = (const half_t*)x_lo; p.y_hi = (half_t*)y_hi; p.y_lo = (half_t*)y_lo;
+}
+
+// true when one of the pointers is not 16-byte aligned (a null pointer is: an entry checks for those first, where it forbids them)
+bool planes_misaligned(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if ((uintptr_t)q & 15) return true;
+    return false;
+}
+
+// output side of a depthwise layer (padding (k - 1) / 2)
+int dw_out_side(int hin, int stride) { return (hin - 1) / stride + 1; }
+
+CatNormParams catnorm_params(const void* fresh_hi, const void* fresh_lo, int g, int fresh_stride, void* raw_hi, void* raw_lo, int c_total,
+                             int c_old, const float* scale, const float* shift, void* out_hi, void* out_lo, int c_norm, long long npix) {
+    CatNormParams p = zeroed<CatNormParams>();
+    const bool norm = out_hi != nullptr;
+    p.f_hi = (const half_t*)fresh_hi; p.f_lo = (const half_t*)fresh_lo;
+    p.r_hi = (half_t*)raw_hi; p.r_lo = (half_t*)raw_lo;
+    p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
+    p.scale = scale; p.shift = shift;
+    p.npix = npix; p.f_stride = fresh_stride; p.c_total = c_total; p.c_old = c_old;
+    p.c_begin = norm ? 0 : c_old;
+    p.c_end = norm ? c_norm : c_old + g;
+    return p;
+}
+
+DwParams dw_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* w, const float* scale, const float* shift, int B,
+                   int hin, int pitch, int stride, int clamp_in) {
+    DwParams p = zeroed<DwParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.w = w; p.scale = scale; p.shift = shift;
+    p.hin = hin; p.ho = dw_out_side(hin, stride); p.pitch = pitch; p.stride = stride; p.clamp_in = clamp_in != 0;
+    p.npix = (long long)B * p.ho * p.ho;
+    return p;
+}
+
+MbDwParams mbdw_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* w, const float* scale, const float* shift, int B,
+                       int hin, int pitch, int stride, int act_in, int act_out) {
+    MbDwParams p = zeroed<MbDwParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.w = w; p.scale = scale; p.shift = shift;
+    p.hin = hin; p.ho = dw_out_side(hin, stride); p.pitch = pitch; p.act_in = act_in; p.act_out = act_out;
+    p.rows = (long long)B * p.ho;
+    return p;
+}
+
+CnDwLnParams cn_dwln_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* w, const float* bias, const float* gamma,
+                            const float* beta, float eps, int B, int hin, int C) {
+    CnDwLnParams p = zeroed<CnDwLnParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.w = w; p.bias = bias; p.gamma = gamma; p.beta = beta;
+    p.H = hin; p.C = C; p.eps = eps;
+    p.units = (long long)B * p.H * ((p.H + CN_DW_W - 1) / CN_DW_W);
+    return p;
+}
+
+CnLnParams cn_ln_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* gamma, const float* beta, float eps,
+                        long long rows, int C) {
+    CnLnParams p = zeroed<CnLnParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.gamma = gamma; p.beta = beta; p.rows = rows; p.C = C; p.eps = eps;
+    return p;
+}
+
+CnLnRowsParams ln_rows_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* gamma, const float* beta, float eps,
+                              long long rows, long long in_stride, int C) {
+    CnLnRowsParams p = zeroed<CnLnRowsParams>();
+    p.ln = cn_ln_params(x_hi, x_lo, y_hi, y_lo, gamma, beta, eps, rows, C);
+    p.in_stride = in_stride;
+    return p;
+}
+
+CnPoolLnParams cn_poolln_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* gamma, const float* beta, float eps,
+                                int B, int hw, int C) {
+    CnPoolLnParams p = zeroed<CnPoolLnParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.gamma = gamma; p.beta = beta; p.B = B; p.hw = hw; p.C = C; p.eps = eps;
+    return p;
+}
+
+TokParams tok_params(const void* x_hi, const void* x_lo, const float* cls, const float* pos, void* y_hi, void* y_lo, int B, int T, int D) {
+    TokParams p = zeroed<TokParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.cls = cls; p.pos = pos; p.T = T; p.D = D;
+    p.chunks = (long long)B * p.T * (p.D >> 3);
+    return p;
+}
+
+AttnParams attn_params(const void* qkv_hi, const void* qkv_lo, void* o_hi, void* o_lo, int B, int T, int heads) {
+    AttnParams p = zeroed<AttnParams>();
+    p.qkv_hi = (const half_t*)qkv_hi; p.qkv_lo = (const half_t*)qkv_lo; p.o_hi = (half_t*)o_hi; p.o_lo = (half_t*)o_lo;
+    p.T = T; p.heads = heads; p.D = heads * AT_HD;
+    p.units = (long long)B * p.heads;
+    return p;
+}
+
+SeGateParams se_gate_params(const void* x_hi, const void* x_lo, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                            int hw, int pitch, int q) {
+    SeGateParams p = zeroed<SeGateParams>();
+    p.x_hi = (const half_t*)x_hi; p.x_lo = (const half_t*)x_lo;
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.gate = gate;
+    p.hw = hw; p.pitch = pitch; p.q = q;
+    return p;
+}
+
+SeScaleParams se_scale_params(const void* x_hi, const void* x_lo, const float* gate, void* y_hi, void* y_lo, int B, int hw, int pitch) {
+    SeScaleParams p = zeroed<SeScaleParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    p.gate = gate; p.pitch = pitch;
+    p.per_image = (long long)hw * (pitch / 8);
+    p.units = (long long)B * p.per_image;
+    return p;
+}
+
+ShuffleParams shuffle_params(const void* a_hi, const void* a_lo, int a_pitch, const void* b_hi, const void* b_lo, int b_pitch, void* y_hi,
+                             void* y_lo, int B, int side, int bf, int hp) {
+    ShuffleParams p = zeroed<ShuffleParams>();
+    p.a_hi = (const half_t*)a_hi; p.a_lo = (const half_t*)a_lo; p.b_hi = (const half_t*)b_hi; p.b_lo = (const half_t*)b_lo;
+    p.y_hi = (half_t*)y_hi; p.y_lo = (half_t*)y_lo;
+    p.npix = (long long)B * side * side;
+    p.a_pitch = a_pitch; p.b_pitch = b_pitch; p.bf = bf; p.hp = hp;
+    return p;
+}
+
+Pool3cParams pool3c_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, int B, int hin, int stride, int pad, int pitch) {
+    Pool3cParams p = zeroed<Pool3cParams>();
+    set_planes(p, x_hi, x_lo, y_hi, y_lo);
+    const int W = stride == 1 ? Pool3c<1>::W : Pool3c<2>::W;
+    p.hin = hin; p.ho = pool3c_out_side(hin, stride, pad); p.pitch = pitch; p.pad = pad;
+    p.runs = (p.ho + W - 1) / W;
+    p.units = (long long)B * p.ho * p.runs * (pitch / 8);
+    return p;
+}
+
+// ---- launchers of those ops ---------------------------------------------------------------------------------------------------------
+
+// one concat_bn_relu_kernel launch
+int launch_catnorm(mpx_engine* h, const CatNormParams& p, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     const unsigned long long units = (unsigned long long)p.npix * (unsigned)((p.c_end - p.c_begin) / 8);
     // Guideline 13 of the HIP guide for HBM-bound kernels: about 8 workgroups per CU, striding over the rest
     const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
@@ -2613,10 +2748,9 @@ int launch_catnorm(mpx_engine* h, const CatNormParams& p, int norm, hipStream_t 
     return 0;
 }
 
-// one dwconv3x3_bn_relu6_kernel launch; `dw` = the engine's depthwise layer it runs for (profile record), -1 from the stand-alone entry
-// (`linear`: ShuffleNetV2's form without activation and clamps, dwconv3x3_bn_kernel of mpx_shuffle.h)
-int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st, bool linear = false) {
-    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+// one dwconv3x3_bn_relu6_kernel launch (`linear`: ShuffleNetV2's form without activation and clamps, dwconv3x3_bn_kernel of mpx_shuffle.h)
+int launch_dwconv(mpx_engine* h, const DwParams& p, bool linear, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     if (linear) {
         // the run form: a unit is a run of 4 (stride 1) or 2 (stride 2) output pixels.  Grid cap, blocks per CU, measured at batch 2340 next to
         // the one-pixel form, ms at 8 / 4 / 2: 28x28 x 64 stride 1 0.262 / 0.263 / 0.257, 14x14 x 128 0.139 / 0.144 / 0.142,
@@ -2639,10 +2773,10 @@ int launch_dwconv(mpx_engine* h, const DwParams& p, int dw, hipStream_t st, bool
     return 0;
 }
 
-// one dwconv_bn_act_kernel launch (mpx_mbconv.h); `dw` = the engine's depthwise layer it runs for (profile record), -1 from the
-// stand-alone entry.  Grid cap as launch_dwconv's run form: 8 blocks per CU at stride 1, 2 at stride 2, striding over the rest.
-int launch_mbdw(mpx_engine* h, const MbDwParams& p, int ksize, int stride, int dw, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
+// one dwconv_bn_act_kernel launch (mpx_mbconv.h).  Grid cap as launch_dwconv's run form: 8 blocks per CU at stride 1, 2 at stride 2, striding
+// over the rest.
+int launch_mbdw(mpx_engine* h, const MbDwParams& p, int ksize, int stride, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     const int W = stride == 1 ? 4 : 2;
     const unsigned long long units = (unsigned long long)p.rows * (unsigned)((p.ho + W - 1) / W) * (unsigned)(p.pitch / 8);
     const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (stride == 1 ? 8 : 2));
@@ -2663,36 +2797,34 @@ unsigned cn_grid(const mpx_engine* h, long long units, int C, int per_cu, int ma
     return (unsigned)std::max<long long>(grid, 1);
 }
 
-// one dwconv7x7_ln_kernel launch; `dw` = the engine's depthwise layer it runs for (profile record), -1 from the stand-alone entry.  The
-// kernel holds 4 x 8 accumulators and one input row of 10 x 8 values per thread (two workgroups per CU): 4 workgroups per CU cover a tail
-int launch_cn_dwln(mpx_engine* h, CnDwLnParams& p, int B, int max_blocks, int dw, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, dw >= 0 ? kProfSubDw - dw : -1);
-    p.units = (long long)B * p.H * ((p.H + CN_DW_W - 1) / CN_DW_W);
+// one dwconv7x7_ln_kernel launch.  The kernel holds 4 x 8 accumulators and one input row of 10 x 8 values per thread (two workgroups per
+// CU): 4 workgroups per CU cover a tail
+int launch_cn_dwln(mpx_engine* h, const CnDwLnParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     hipLaunchKernelGGL(dwconv7x7_ln_kernel, dim3(cn_grid(h, p.units, p.C, 4, max_blocks)), dim3(CN_NT), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
 
-// one layernorm_c_kernel launch; `k` = the engine's LayerNorm it runs for (profile record), -1 from the stand-alone entry
-int launch_cn_ln(mpx_engine* h, const CnLnParams& p, int max_blocks, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+// one layernorm_c_kernel launch
+int launch_cn_ln(mpx_engine* h, const CnLnParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     hipLaunchKernelGGL(layernorm_c_kernel, dim3(cn_grid(h, p.rows, p.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
 
-// one layernorm_rows_kernel launch (mpx_attn.h); `k` as launch_cn_ln's
-int launch_ln_rows(mpx_engine* h, const CnLnRowsParams& p, int max_blocks, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+// one layernorm_rows_kernel launch (mpx_attn.h)
+int launch_ln_rows(mpx_engine* h, const CnLnRowsParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     hipLaunchKernelGGL(layernorm_rows_kernel, dim3(cn_grid(h, p.ln.rows, p.ln.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
 
-// one tokens_assemble_kernel launch (mpx_attn.h); `own` = the engine's own token assembly (profile record)
-int launch_tokens(mpx_engine* h, TokParams& p, int B, int max_blocks, bool own, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, own ? kProfSubTokens : -1);
-    p.chunks = (long long)B * p.T * (p.D >> 3);
+// one tokens_assemble_kernel launch (mpx_attn.h)
+int launch_tokens(mpx_engine* h, const TokParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     long long grid = std::min<long long>((p.chunks + AT_NT - 1) / AT_NT, (long long)h->num_cus * 8);
     if (max_blocks > 0) grid = std::min<long long>(grid, max_blocks);
     hipLaunchKernelGGL(tokens_assemble_kernel, dim3((unsigned)std::max<long long>(grid, 1)), dim3(AT_NT), 0, st, p);
@@ -2701,10 +2833,9 @@ int launch_tokens(mpx_engine* h, TokParams& p, int B, int max_blocks, bool own, 
 }
 
 // one attention_f16x3_kernel launch (mpx_attn.h): a unit is one (image, head); one head's V^T in the LDS (59 KB at T = 197) leaves room for
-// two workgroups per CU; `k` = the engine's attention launch it runs for (profile record), -1 from the stand-alone entry
-int launch_attn(mpx_engine* h, AttnParams& p, int B, int max_blocks, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubAttn - k : -1);
-    p.units = (long long)B * p.heads;
+// two workgroups per CU
+int launch_attn(mpx_engine* h, const AttnParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     long long grid = std::min<long long>(p.units, (long long)h->num_cus * 2);
     if (max_blocks > 0) grid = std::min<long long>(grid, max_blocks);
     hipLaunchKernelGGL(attention_f16x3_kernel, dim3((unsigned)std::max<long long>(grid, 1)), dim3(AT_NT), at_lds_bytes(p.T), st, p);
@@ -2713,8 +2844,8 @@ int launch_attn(mpx_engine* h, AttnParams& p, int B, int max_blocks, int k, hipS
 }
 
 // one global_avgpool_ln_kernel launch
-int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubLnorm - k : -1);
+int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     hipLaunchKernelGGL(global_avgpool_ln_kernel, dim3(cn_grid(h, p.B, p.C, 8, 0)), dim3(CN_NT), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
@@ -2723,10 +2854,9 @@ int launch_cn_poolln(mpx_engine* h, const CnPoolLnParams& p, int k, hipStream_t 
 // dynamic LDS of one se_gate_kernel launch: part[S][pitch] | pooled[pitch] | s1[q]
 size_t se_gate_lds(int pitch, int q) { return ((size_t)se_gate_slices(pitch) * pitch + pitch + q) * sizeof(float); }
 
-// one se_gate_kernel launch, one workgroup per image; `k` = the engine's SE layer it runs for (profile record), -1 from the stand-alone entry
-// relu: fc1's activation is ReLU (a RegNetY block's gate), not SiLU (EfficientNet's)
-int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, int k, bool relu, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubSeGate - k : -1);
+// one se_gate_kernel launch, one workgroup per image.  relu: fc1's activation is ReLU (a RegNetY block's gate), not SiLU (EfficientNet's)
+int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, bool relu, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     if (relu)
         hipLaunchKernelGGL(se_gate_kernel<true>, dim3((unsigned)B), dim3(256), se_gate_lds(p.pitch, p.q), st, p);
     else
@@ -2736,18 +2866,18 @@ int launch_se_gate(mpx_engine* h, const SeGateParams& p, int B, int k, bool relu
 }
 
 // one se_scale_kernel launch; about 8 workgroups per CU, striding over the rest
-int launch_se_scale(mpx_engine* h, const SeScaleParams& p, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubSeScale - k : -1);
+int launch_se_scale(mpx_engine* h, const SeScaleParams& p, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     const unsigned grid = (unsigned)std::min<long long>((p.units + 255) / 256, (long long)h->num_cus * 8);
     hipLaunchKernelGGL(se_scale_kernel, dim3(grid), dim3(256), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
 
-// one shuffle2_concat_kernel launch; `k` = the engine's shuffle it runs for (profile record), -1 from the stand-alone entry.  The load width
-// follows the alignment of the sources (mpx_shuffle.h): 8-byte loads when bf % 8 == 0, 2-byte loads otherwise.
-int launch_shuffle(mpx_engine* h, const ShuffleParams& p, int k, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubShuffle - k : -1);
+// one shuffle2_concat_kernel launch.  The load width follows the alignment of the sources (mpx_shuffle.h): 8-byte loads when bf % 8 == 0,
+// 2-byte loads otherwise.
+int launch_shuffle(mpx_engine* h, const ShuffleParams& p, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     const unsigned long long units = (unsigned long long)p.npix * (unsigned)(2 * p.hp / 8);
     // as launch_dwconv: about 8 workgroups per CU, striding over the rest
     const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
@@ -2759,16 +2889,9 @@ int launch_shuffle(mpx_engine* h, const ShuffleParams& p, int k, hipStream_t st)
     return 0;
 }
 
-// one maxpool3x3_clip_kernel launch over B images; `k` = the engine's clipped pool it runs for (profile record), -1 from the stand-alone entry
-int launch_pool3c(mpx_engine* h, const half_t* in_hi, const half_t* in_lo, half_t* out_hi, half_t* out_lo, int B, int hin, int stride, int pad,
-                  int pitch, int k, hipStream_t st) {
-    Pool3cParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = in_hi; p.x_lo = in_lo; p.y_hi = out_hi; p.y_lo = out_lo;
-    p.hin = hin; p.ho = pool3c_out_side(hin, stride, pad); p.pitch = pitch; p.pad = pad;
-    p.runs = (p.ho + (stride == 1 ? Pool3c<1>::W : Pool3c<2>::W) - 1) / (stride == 1 ? Pool3c<1>::W : Pool3c<2>::W);
-    p.units = (long long)B * p.ho * p.runs * (pitch / 8);
-    ProfScope ps(h, st, 2, -1, k >= 0 ? kProfSubPool3c - k : -1);
+// one maxpool3x3_clip_kernel launch
+int launch_pool3c(mpx_engine* h, const Pool3cParams& p, int stride, ProfTag tag, hipStream_t st) {
+    ProfScope ps(h, st, 2, -1, tag);
     // a thread keeps the 18 (stride 1) or 15 (stride 2) loads per plane of its run in flight, so two workgroups per CU already cover the
     // latency; the grid strides over the rest
     const unsigned grid = (unsigned)std::min<long long>((p.units + 255) / 256, (long long)h->num_cus * 2);
@@ -2776,6 +2899,28 @@ int launch_pool3c(mpx_engine* h, const half_t* in_hi, const half_t* in_lo, half_
         hipLaunchKernelGGL(maxpool3x3_clip_kernel<1>, dim3(grid), dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL(maxpool3x3_clip_kernel<2>, dim3(grid), dim3(256), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// The nine plane-to-plane pools (mpx_maxpool3x3s2 .. mpx_global_avgpool_logits) differ in their kernel, their number of 8-channel units and
+// their grid rule only.  This is the rest: the engine's device, the profile record, the grid of 256-thread workgroups over `units`, the
+// launch and its error check.
+enum GridRule {
+    GRID_CAP_16K,   // min(ceil(units / 256), 256 * 64), striding over the rest
+    GRID_PER_CU,    // min(ceil(units / 256), 8 workgroups per CU), striding over the rest
+    GRID_ALL        // ceil(units / 256): one thread per unit
+};
+
+template <class Kernel, class... Args>
+int launch_planes(mpx_engine* h, Kernel kernel, size_t units, GridRule rule, ProfTag tag, void* stream, Args... args) {
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 2, -1, tag);
+    size_t grid = (units + 255) / 256;
+    if (rule == GRID_CAP_16K) grid = std::min<size_t>(grid, 256 * 64);
+    if (rule == GRID_PER_CU) grid = std::min<size_t>(grid, (size_t)h->num_cus * 8);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, args...);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -2968,120 +3113,80 @@ int mpx_create(int arch_id, int max_batch, int device, mpx_engine** out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->num_cus = cus;
     }
 
-    // one arena: scratch | input planes | activation planes | pooled | logits | weights
+    // one arena: scratch | input planes | activation planes | pooled | logits | stem planes and weights | weights | SE gates.  layout()
+    // below is its ONE description: it hands every buffer its `take(bytes)` in order, and runs twice -- over a null base to count the bytes,
+    // over the allocation to assign the pointers -- so that no buffer's size is written down a second time.
     const size_t in_elems = h->small ? (size_t)h->img * h->img * kSmallCPad : (size_t)MPX_IMG_PAD * MPX_IMG_PAD * 4;
     const size_t in_plane = round_up((size_t)max_batch * in_elems * 2 + 256, 256);
-    size_t act_plane_buf[kActBufs], act_bytes = 0;       // one size for all buffers, except where the topology sizes each (ViT)
-    for (int b = 0; b < h->n_act_bufs; ++b) {
-        act_plane_buf[b] = round_up((size_t)max_batch * (h->act_elems_buf[b] ? h->act_elems_buf[b] : h->act_elems_per_image) * 2, 256);
-        act_bytes += 2 * act_plane_buf[b];
-    }
     const size_t pool_plane = round_up((size_t)max_batch * round_up(h->feat, kSmallCPad) * 2, 256);
-    const size_t logit_bytes = round_up((size_t)max_batch * h->logit_pitch * 4, 256);
-    const size_t k0_bytes = h->small ? round_up((size_t)(2 + 4096 + max_batch) * sizeof(float), 256) : 0;
-    size_t wbytes = 0;
-    for (const ConvLayer& L : h->convs) {
-        wbytes += 2 * round_up((size_t)L.d.cout_pad * L.d.k_packed * 2, 256) + 2 * round_up((size_t)L.d.cout_pad * 4, 256);
-        if (L.fuse_main)
-            wbytes += 2 * round_up((size_t)L.d.cout_pad * (L.d.cin + h->convs[L.fuse_partner].d.cin) * 2, 256) + 2 * round_up((size_t)L.d.cout_pad * 4, 256);
-    }
-    for (const TailBlock& tb : h->tails) wbytes += 2 * round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
-    for (const NormLayer& nl : h->norms) wbytes += 2 * round_up((size_t)nl.d.channels * 4, 256);
-    for (const DwLayer& D : h->dws) wbytes += round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256) + (D.ln ? 3 : 2) * round_up((size_t)D.d.pitch * 4, 256);
-    for (const LnLayer& N : h->lnorms) wbytes += 2 * round_up((size_t)N.d.channels * 4, 256);
-    if (h->vit) wbytes += round_up((size_t)h->vit_D * 4, 256) + round_up((size_t)h->vit_T * h->vit_D * 4, 256);
-    for (const SeLayer& E : h->ses)
-        wbytes += 2 * round_up((size_t)E.d.q * E.d.pitch * 4, 256) + round_up((size_t)E.d.q * 4, 256) + round_up((size_t)E.d.pitch * 4, 256);
-    const size_t se_gate_bytes = round_up((size_t)max_batch * h->se_pitch_max * 4, 256);
     const size_t scratch_bytes = 4096 * sizeof(float);
     // the stem by superposition (ImageNet ResNets): pooled stem planes, fp32 stem weights + BatchNorm vectors, one image's table (worst case:
     // 49 entries per conv output pixel), the bit planes of one staging call
     const bool stemtab = stem_pool_eligible(h);
-    const int tab_nmb = (max_batch + 31) / 32 + 1;
-    const size_t stem_plane = stemtab ? round_up((size_t)max_batch * ST_POOLED * ST_POOLED * ST_C * 2, 256) : 0;
     const bool stemw = stemtab && !h->densenet;     // a DenseNet engine runs the fused stem + pool launch but keeps no stem table
-    const size_t stem_w_bytes = stemw ? round_up((size_t)ST_TAPS * 3 * ST_C * 4, 256) + 2 * 256 : 0;
-    const size_t tab_int_bytes = stemtab ? round_up((size_t)(ST_NPIX + 1) * 4, 256) : 0;
-    const size_t tab_lab_bytes = stemtab ? round_up((size_t)ST_MAX_ENTRIES * 4, 256) : 0;
-    const size_t tab_vec_bytes = stemtab ? round_up((size_t)ST_MAX_ENTRIES * ST_C * 4, 256) : 0;
-    const size_t tab_bits_bytes = stemtab ? round_up((size_t)4096 * tab_nmb * 4, 256) : 0;
+    const int tab_nmb = (max_batch + 31) / 32 + 1;
     // (the table itself -- 3 * tab_int + tab_lab + tab_vec + tab_bits, 160 MB -- is allocated by the first mpx_stem_table_build: an engine that
     // only ever stages through K0, stem = "conv", never pays for it)
-    const size_t stemtab_bytes = 2 * stem_plane + stem_w_bytes;
-    h->tab_sizes[0] = tab_int_bytes; h->tab_sizes[1] = tab_lab_bytes; h->tab_sizes[2] = tab_vec_bytes; h->tab_sizes[3] = tab_bits_bytes;
-    const size_t total = scratch_bytes + 2 * in_plane + act_bytes + 2 * pool_plane + logit_bytes + k0_bytes + wbytes + stemtab_bytes + se_gate_bytes;
+    h->tab_sizes[0] = stemtab ? round_up((size_t)(ST_NPIX + 1) * 4, 256) : 0;
+    h->tab_sizes[1] = stemtab ? round_up((size_t)ST_MAX_ENTRIES * 4, 256) : 0;
+    h->tab_sizes[2] = stemtab ? round_up((size_t)ST_MAX_ENTRIES * ST_C * 4, 256) : 0;
+    h->tab_sizes[3] = stemtab ? round_up((size_t)4096 * tab_nmb * 4, 256) : 0;
+    auto layout = [&](char* base) -> size_t {
+        size_t off = 0;
+        auto take = [&](size_t n) { char* r = base ? base + off : nullptr; off += n; return r; };
+        // `count` elements rounded up to 256 bytes, for one pointer or for a pair of equal buffers (hi / lo planes, scale / shift vectors)
+        auto f32 = [&](float*& q, size_t count) { q = (float*)take(round_up(count * 4, 256)); };
+        auto f16 = [&](half_t*& q, size_t count) { q = (half_t*)take(round_up(count * 2, 256)); };
+        auto f32x2 = [&](float*& q0, float*& q1, size_t count) { f32(q0, count); f32(q1, count); };
+        auto f16x2 = [&](half_t*& q0, half_t*& q1, size_t count) { f16(q0, count); f16(q1, count); };
+        h->seg_scratch = (float*)take(scratch_bytes);
+        h->in_hi = (half_t*)take(in_plane);
+        h->in_lo = (half_t*)take(in_plane);
+        for (int b = 0; b < h->n_act_bufs; ++b)         // one size for all buffers, except where the topology sizes each (ViT)
+            f16x2(h->act_hi[b], h->act_lo[b], (size_t)max_batch * (h->act_elems_buf[b] ? h->act_elems_buf[b] : h->act_elems_per_image));
+        h->pool_hi = (half_t*)take(pool_plane);
+        h->pool_lo = (half_t*)take(pool_plane);
+        f32(h->logits, (size_t)max_batch * h->logit_pitch);
+        if (h->small) f32(h->k0_scratch, (size_t)2 + 4096 + max_batch);
+        if (stemtab) f16x2(h->stem_hi, h->stem_lo, (size_t)max_batch * ST_POOLED * ST_POOLED * ST_C);
+        if (stemw) {
+            f32(h->stem_w32, (size_t)ST_TAPS * 3 * ST_C);
+            f32x2(h->stem_s32, h->stem_t32, ST_C);
+        }
+        for (ConvLayer& L : h->convs) {
+            f16x2(L.w_hi, L.w_lo, (size_t)L.d.cout_pad * L.d.k_packed);
+            f32x2(L.scale, L.shift, (size_t)L.d.cout_pad);
+            if (L.fuse_main) {
+                f16x2(L.fw_hi, L.fw_lo, (size_t)L.d.cout_pad * (L.d.cin + h->convs[L.fuse_partner].d.cin));
+                f32x2(L.fscale, L.fshift, (size_t)L.d.cout_pad);
+            }
+        }
+        for (TailBlock& tb : h->tails) f16x2(tb.w3p_hi, tb.w3p_lo, (size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID);
+        for (NormLayer& nl : h->norms) f32x2(nl.scale, nl.shift, (size_t)nl.d.channels);
+        for (DwLayer& D : h->dws) {
+            f32(D.w, (size_t)D.ksize * D.ksize * D.d.pitch);
+            f32x2(D.scale, D.shift, (size_t)D.d.pitch);
+            if (D.ln) f32(D.bias, (size_t)D.d.pitch);
+        }
+        for (LnLayer& N : h->lnorms) f32x2(N.gamma, N.beta, (size_t)N.d.channels);
+        if (h->vit) {
+            f32(h->cls_token, (size_t)h->vit_D);
+            f32(h->pos_emb, (size_t)h->vit_T * h->vit_D);
+        }
+        for (SeLayer& E : h->ses) {
+            f32x2(E.w1, E.w2, (size_t)E.d.q * E.d.pitch);
+            f32(E.b1, (size_t)E.d.q);
+            f32(E.b2, (size_t)E.d.pitch);
+        }
+        if (h->se_pitch_max) f32(h->se_gate, (size_t)max_batch * h->se_pitch_max);
+        return off;
+    };
+    const size_t total = layout(nullptr);
     e = hipMalloc((void**)&h->arena, total);
     if (e != hipSuccess) { delete h; return (int)e; }
     h->arena_bytes = total;
-    char* cur = h->arena;
-    auto take = [&](size_t n) { char* r = cur; cur += n; return r; };
-    h->seg_scratch = (float*)take(scratch_bytes);
-    h->in_hi = (half_t*)take(in_plane);
-    h->in_lo = (half_t*)take(in_plane);
-    for (int b = 0; b < h->n_act_bufs; ++b) {
-        h->act_hi[b] = (half_t*)take(act_plane_buf[b]);
-        h->act_lo[b] = (half_t*)take(act_plane_buf[b]);
-    }
-    h->pool_hi = (half_t*)take(pool_plane);
-    h->pool_lo = (half_t*)take(pool_plane);
-    h->logits = (float*)take(logit_bytes);
-    if (k0_bytes) h->k0_scratch = (float*)take(k0_bytes);
-    if (stemtab) {
-        h->stem_hi = (half_t*)take(stem_plane);
-        h->stem_lo = (half_t*)take(stem_plane);
-    }
-    if (stemw) {
-        h->stem_w32 = (float*)take(stem_w_bytes - 512);
-        h->stem_s32 = (float*)take(256);
-        h->stem_t32 = (float*)take(256);
-    }
+    layout(h->arena);
     h->slot_src.assign((size_t)max_batch, 0);
-    for (ConvLayer& L : h->convs) {
-        const size_t wb = round_up((size_t)L.d.cout_pad * L.d.k_packed * 2, 256);
-        const size_t sb = round_up((size_t)L.d.cout_pad * 4, 256);
-        L.w_hi = (half_t*)take(wb);
-        L.w_lo = (half_t*)take(wb);
-        L.scale = (float*)take(sb);
-        L.shift = (float*)take(sb);
-        if (L.fuse_main) {
-            const size_t fb = round_up((size_t)L.d.cout_pad * (L.d.cin + h->convs[L.fuse_partner].d.cin) * 2, 256);
-            L.fw_hi = (half_t*)take(fb);
-            L.fw_lo = (half_t*)take(fb);
-            L.fscale = (float*)take(sb);
-            L.fshift = (float*)take(sb);
-        }
-    }
-    for (TailBlock& tb : h->tails) {
-        const size_t pb = round_up((size_t)BT_OUT * (tb.ds >= 0 ? 2 : 1) * BT_MID * 2, 256);
-        tb.w3p_hi = (half_t*)take(pb);
-        tb.w3p_lo = (half_t*)take(pb);
-    }
-    for (NormLayer& nl : h->norms) {
-        const size_t nb = round_up((size_t)nl.d.channels * 4, 256);
-        nl.scale = (float*)take(nb);
-        nl.shift = (float*)take(nb);
-    }
-    for (DwLayer& D : h->dws) {
-        D.w = (float*)take(round_up((size_t)D.ksize * D.ksize * D.d.pitch * 4, 256));
-        D.scale = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
-        D.shift = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
-        if (D.ln) D.bias = (float*)take(round_up((size_t)D.d.pitch * 4, 256));
-    }
-    for (LnLayer& N : h->lnorms) {
-        N.gamma = (float*)take(round_up((size_t)N.d.channels * 4, 256));
-        N.beta = (float*)take(round_up((size_t)N.d.channels * 4, 256));
-    }
-    if (h->vit) {
-        h->cls_token = (float*)take(round_up((size_t)h->vit_D * 4, 256));
-        h->pos_emb = (float*)take(round_up((size_t)h->vit_T * h->vit_D * 4, 256));
-    }
-    for (SeLayer& E : h->ses) {
-        E.w1 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
-        E.w2 = (float*)take(round_up((size_t)E.d.q * E.d.pitch * 4, 256));
-        E.b1 = (float*)take(round_up((size_t)E.d.q * 4, 256));
-        E.b2 = (float*)take(round_up((size_t)E.d.pitch * 4, 256));
-    }
-    if (se_gate_bytes) h->se_gate = (float*)take(se_gate_bytes);
     // the never-written borders (ImageNet) / padding channels (small nets) of the input staging must be zero, and so must
     // the pooled planes' padding channels
     e = hipMemset(h->arena, 0, scratch_bytes + 2 * in_plane);
@@ -3536,7 +3641,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
                          const float mean[3], const float std[3], void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
-    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", h->vgg || h->alexnet || h->mobilenet || h->squeezenet || h->googlenet || h->shufflenet || h->efficientnet || h->convnext || h->vit || h->regnet ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT, RegNetX and RegNetY stage through mpx_mask_apply_normalize)" : "");
+    if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", !h->small ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT, RegNetX and RegNetY stage through mpx_mask_apply_normalize)" : "");
     if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
         return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
@@ -3643,17 +3748,9 @@ int mpx_avgpool2_pad(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || cin_p <= 0 || (cin_p & 7) || cout_p < cin_p || (cout_p & 7))
         return fail(h, MPX_E_ARG, "avgpool2_pad: bad arguments (hin even, channel counts multiples of 8, cout_p >= cin_p)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "avgpool2_pad: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (cout_p / 8);
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
-    hipLaunchKernelGGL(avgpool2_pad_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hin, cin_p, cout_p);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "avgpool2_pad: the planes must be 16-byte aligned");
+    return launch_planes(h, avgpool2_pad_kernel, (size_t)B * (hin / 2) * (hin / 2) * (cout_p / 8), GRID_CAP_16K, ProfTag(), stream,
+                         (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, cin_p, cout_p);
 }
 
 int mpx_geometry(const mpx_engine* h, int* image_size, int* in_channels, int* num_classes, int* logit_pitch) {
@@ -3693,17 +3790,9 @@ int mpx_maxpool3x3s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool3x3s2: bad arguments (hin even, c multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "maxpool3x3s2: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (c / 8);
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool3x3s2: the planes must be 16-byte aligned");
+    return launch_planes(h, maxpool3x3s2_kernel, (size_t)B * (hin / 2) * (hin / 2) * (c / 8), GRID_CAP_16K, ProfTag(), stream,
+                         (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
 int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin,
@@ -3711,17 +3800,9 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool2x2s2: bad arguments (hin even, c multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "maxpool2x2s2: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (c / 8);
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
-    hipLaunchKernelGGL(maxpool2x2s2_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool2x2s2: the planes must be 16-byte aligned");
+    return launch_planes(h, maxpool2x2s2_kernel, (size_t)B * (hin / 2) * (hin / 2) * (c / 8), GRID_CAP_16K, ProfTag(), stream,
+                         (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
 int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin,
@@ -3729,18 +3810,10 @@ int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin < 3 || !(hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool3x3s2p0: bad arguments (hin odd and >= 3, c multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "maxpool3x3s2p0: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool3x3s2p0: the planes must be 16-byte aligned");
     const int ho = (hin - 3) / 2 + 1;
-    const size_t total = (size_t)B * ho * ho * (c / 8);
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 64);
-    hipLaunchKernelGGL(maxpool3x3s2p0_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    return launch_planes(h, maxpool3x3s2p0_kernel, (size_t)B * ho * ho * (c / 8), GRID_CAP_16K, ProfTag(), stream, (const half_t*)in_hi,
+                         (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
 int mpx_maxpool3x3_clip(mpx_engine* h, const void* in_hi, const void* in_lo, void* out_hi, void* out_lo, int B, int hin, int stride, int pad,
@@ -3749,11 +3822,9 @@ int mpx_maxpool3x3_clip(mpx_engine* h, const void* in_hi, const void* in_lo, voi
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (stride != 1 && stride != 2) || (pad != 0 && pad != 1) || pitch <= 0 ||
         (pitch & 7) || pool3c_out_side(hin, stride, pad) <= 0)
         return fail(h, MPX_E_ARG, "maxpool3x3_clip: bad arguments (stride 1 or 2, pad 0 or 1, hin + 2 * pad >= 3, pitch a multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "maxpool3x3_clip: the planes must be 16-byte aligned");
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool3x3_clip: the planes must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_pool3c(h, (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, stride, pad, pitch, -1,
-                         as_stream(stream));
+    return launch_pool3c(h, pool3c_params(in_hi, in_lo, out_hi, out_lo, B, hin, stride, pad, pitch), stride, ProfTag(), as_stream(stream));
 }
 
 int mpx_num_clip_pools(const mpx_engine* h) { return h ? (int)h->pools3c.size() : MPX_E_ARG; }
@@ -3773,16 +3844,9 @@ int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool: bad arguments (c multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "global_avgpool: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const int total = B * (c / 8);
-    hipLaunchKernelGGL(global_avgpool_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi,
-                       (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "global_avgpool: the planes must be 16-byte aligned");
+    return launch_planes(h, global_avgpool_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi, (const half_t*)in_lo,
+                         (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
 int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo, int g, int fresh_stride, void* raw_hi, void* raw_lo,
@@ -3790,7 +3854,6 @@ int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo
                        long long npix, void* stream) {
     if (!h) return MPX_E_ARG;
     const bool fresh = fresh_hi != nullptr, norm = out_hi != nullptr;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!raw_hi || !raw_lo || (fresh_hi == nullptr) != (fresh_lo == nullptr) || (out_hi == nullptr) != (out_lo == nullptr) || (!fresh && !norm))
         return fail(h, MPX_E_ARG, "concat_bn_relu: raw planes and at least one of fresh / out planes, planes in pairs");
     if (npix <= 0 || c_total <= 0 || (c_total & 7) || c_old < 0 || (c_old & 7))
@@ -3799,20 +3862,11 @@ int mpx_concat_bn_relu(mpx_engine* h, const void* fresh_hi, const void* fresh_lo
         return fail(h, MPX_E_ARG, "concat_bn_relu: g a positive multiple of 8 with c_old + g <= c_total and fresh_stride >= g a multiple of 8 (g = 0 without fresh planes)");
     if (norm ? (!scale || !shift || c_norm <= 0 || (c_norm & 7) || (fresh ? c_norm != c_old + g : c_norm > c_total)) : (c_norm != 0 || scale || shift))
         return fail(h, MPX_E_ARG, "concat_bn_relu: c_norm = c_old + g with fresh planes, a positive multiple of 8 <= c_total without; scale / shift with out planes only");
-    if (misaligned(fresh_hi) || misaligned(fresh_lo) || misaligned(raw_hi) || misaligned(raw_lo) || misaligned(out_hi) || misaligned(out_lo) ||
-        misaligned(scale) || misaligned(shift))
+    if (planes_misaligned({fresh_hi, fresh_lo, raw_hi, raw_lo, out_hi, out_lo, scale, shift}))
         return fail(h, MPX_E_ARG, "concat_bn_relu: every pointer must be 16-byte aligned");
-    CatNormParams p;
-    std::memset(&p, 0, sizeof p);
-    p.f_hi = (const half_t*)fresh_hi; p.f_lo = (const half_t*)fresh_lo;
-    p.r_hi = (half_t*)raw_hi; p.r_lo = (half_t*)raw_lo;
-    p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.scale = scale; p.shift = shift;
-    p.npix = npix; p.f_stride = fresh_stride; p.c_total = c_total; p.c_old = c_old;
-    p.c_begin = norm ? 0 : c_old;
-    p.c_end = norm ? c_norm : c_old + g;
     MPX_SET_DEVICE(h);
-    return launch_catnorm(h, p, -1, as_stream(stream));
+    return launch_catnorm(h, catnorm_params(fresh_hi, fresh_lo, g, fresh_stride, raw_hi, raw_lo, c_total, c_old, scale, shift, out_hi, out_lo, c_norm, npix),
+                          ProfTag(), as_stream(stream));
 }
 
 int mpx_num_dwconvs(const mpx_engine* h) { return h ? (int)h->dws.size() : MPX_E_ARG; }
@@ -3857,40 +3911,27 @@ int mpx_dwconv_params(const mpx_engine* h, int k, const float** w, const float**
 int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift,
                            void* out_hi, void* out_lo, int B, int hin, int pitch, int stride, int clamp_in, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo)
         return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: null pointer");
     if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (stride != 1 && stride != 2))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: B > 0, hin > 0, pitch a positive multiple of 8, stride 1 or 2");
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: every pointer must be 16-byte aligned");
-    DwParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.w = w; p.scale = scale; p.shift = shift;
-    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.stride = stride; p.clamp_in = clamp_in != 0;
-    p.npix = (long long)B * p.ho * p.ho;
     MPX_SET_DEVICE(h);
-    return launch_dwconv(h, p, -1, as_stream(stream));
+    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, clamp_in), false, ProfTag(),
+                         as_stream(stream));
 }
 
 int mpx_dwconv3x3_bn(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift, void* out_hi,
                      void* out_lo, int B, int hin, int pitch, int stride, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv3x3_bn: null pointer");
     if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (stride != 1 && stride != 2))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn: B > 0, hin > 0, pitch a positive multiple of 8, stride 1 or 2");
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn: every pointer must be 16-byte aligned");
-    DwParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.w = w; p.scale = scale; p.shift = shift;
-    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.stride = stride; p.clamp_in = 0;
-    p.npix = (long long)B * p.ho * p.ho;
     MPX_SET_DEVICE(h);
-    return launch_dwconv(h, p, -1, as_stream(stream), true);
+    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, 0), true, ProfTag(), as_stream(stream));
 }
 
 int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp) {
@@ -3948,56 +3989,40 @@ int mpx_dwconv7x7_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const 
                      const float* ln_bias, float eps, void* out_hi, void* out_lo, int B, int hin, int C, int ksize, int stride, int max_blocks,
                      void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !w || !conv_bias || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv7x7_ln: null pointer");
     if (ksize != CN_DW_K || stride != 1)
         return fail(h, MPX_E_ARG, "dwconv7x7_ln: ksize %d stride %d: this entry runs the 7x7 stride-1 layers with a LayerNorm behind them (3x3 and 5x5 layers run mpx_dwconv_bn_act)", ksize, stride);
     if (B <= 0 || hin <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f) || (long long)B * hin * hin > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "dwconv7x7_ln: B > 0, hin > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(conv_bias) || misaligned(ln_weight) || misaligned(ln_bias) ||
-        misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, w, conv_bias, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv7x7_ln: every pointer must be 16-byte aligned");
-    CnDwLnParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.w = w; p.bias = conv_bias; p.gamma = ln_weight; p.beta = ln_bias;
-    p.H = hin; p.C = C; p.eps = eps;
     MPX_SET_DEVICE(h);
-    return launch_cn_dwln(h, p, B, max_blocks, -1, as_stream(stream));
+    return launch_cn_dwln(h, cn_dwln_params(in_hi, in_lo, out_hi, out_lo, w, conv_bias, ln_weight, ln_bias, eps, B, hin, C), max_blocks, ProfTag(),
+                          as_stream(stream));
 }
 
 int mpx_layernorm_c(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
                     void* out_lo, long long rows, int C, int max_blocks, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "layernorm_c: null pointer");
     if (rows <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
         return fail(h, MPX_E_ARG, "layernorm_c: rows > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "layernorm_c: every pointer must be 16-byte aligned");
-    CnLnParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.gamma = ln_weight; p.beta = ln_bias; p.rows = rows; p.C = C; p.eps = eps;
     MPX_SET_DEVICE(h);
-    return launch_cn_ln(h, p, max_blocks, -1, as_stream(stream));
+    return launch_cn_ln(h, cn_ln_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, C), max_blocks, ProfTag(), as_stream(stream));
 }
 
 int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps,
                           void* out_hi, void* out_lo, int B, int hw, int C, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "global_avgpool_ln: null pointer");
     if (B <= 0 || hw <= 0 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
         return fail(h, MPX_E_ARG, "global_avgpool_ln: B > 0, hw > 0, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "global_avgpool_ln: every pointer must be 16-byte aligned");
-    CnPoolLnParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.gamma = ln_weight; p.beta = ln_bias; p.B = B; p.hw = hw; p.C = C; p.eps = eps;
     MPX_SET_DEVICE(h);
-    return launch_cn_poolln(h, p, -1, as_stream(stream));
+    return launch_cn_poolln(h, cn_poolln_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, B, hw, C), ProfTag(), as_stream(stream));
 }
 
 int mpx_conv_rows(const mpx_engine* h, int i, int* rows_per_image) {
@@ -4037,55 +4062,39 @@ int mpx_token_params(const mpx_engine* h, const float** class_token, const float
 int mpx_attention(mpx_engine* h, const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int T, int heads, int max_blocks,
                   void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!qkv_hi || !qkv_lo || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "attention: null pointer");
     if (T < 1 || T > AT_MAX_T) return fail(h, MPX_E_ARG, "attention: T = %d: a sequence has 1 .. %d tokens (one head's V^T must fit the LDS)", T, AT_MAX_T);
     if (heads < 1 || heads > 64) return fail(h, MPX_E_ARG, "attention: heads = %d: the width is D = heads * 64 with 1 .. 64 heads (head_dim is 64)", heads);
     if (B <= 0 || (long long)B * T > 0x7fffffffLL) return fail(h, MPX_E_ARG, "attention: B > 0 and B * T below 2^31");
-    if (misaligned(qkv_hi) || misaligned(qkv_lo) || misaligned(out_hi) || misaligned(out_lo))
-        return fail(h, MPX_E_ARG, "attention: every plane must be 16-byte aligned");
-    AttnParams p;
-    std::memset(&p, 0, sizeof p);
-    p.qkv_hi = (const half_t*)qkv_hi; p.qkv_lo = (const half_t*)qkv_lo; p.o_hi = (half_t*)out_hi; p.o_lo = (half_t*)out_lo;
-    p.T = T; p.heads = heads; p.D = heads * AT_HD;
+    if (planes_misaligned({qkv_hi, qkv_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "attention: every plane must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_attn(h, p, B, max_blocks, -1, as_stream(stream));
+    return launch_attn(h, attn_params(qkv_hi, qkv_lo, out_hi, out_lo, B, T, heads), max_blocks, ProfTag(), as_stream(stream));
 }
 
 int mpx_tokens_assemble(mpx_engine* h, const void* patch_hi, const void* patch_lo, const float* class_token, const float* pos_embedding,
                         void* out_hi, void* out_lo, int B, int T, int D, int max_blocks, void* stream) {
     if (!h) return MPX_E_ARG;
     if (!h->vit) return fail(h, MPX_E_STATE, "tokens_assemble: this architecture has no token sequence (a ViT engine has)");
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!patch_hi || !patch_lo || !class_token || !pos_embedding || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "tokens_assemble: null pointer");
     if (T < 1) return fail(h, MPX_E_ARG, "tokens_assemble: T = %d: a sequence has at least the class token", T);
     if (B <= 0 || D <= 0 || (D & 7) || (long long)B * T > 0x7fffffffLL) return fail(h, MPX_E_ARG, "tokens_assemble: B > 0, D a positive multiple of 8, B * T below 2^31");
-    if (misaligned(patch_hi) || misaligned(patch_lo) || misaligned(class_token) || misaligned(pos_embedding) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({patch_hi, patch_lo, class_token, pos_embedding, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "tokens_assemble: every pointer must be 16-byte aligned");
-    TokParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)patch_hi; p.x_lo = (const half_t*)patch_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.cls = class_token; p.pos = pos_embedding; p.T = T; p.D = D;
     MPX_SET_DEVICE(h);
-    return launch_tokens(h, p, B, max_blocks, false, as_stream(stream));
+    return launch_tokens(h, tok_params(patch_hi, patch_lo, class_token, pos_embedding, out_hi, out_lo, B, T, D), max_blocks, ProfTag(), as_stream(stream));
 }
 
 int mpx_layernorm_rows(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps, void* out_hi,
                        void* out_lo, long long rows, long long in_stride, int C, int max_blocks, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !ln_weight || !ln_bias || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "layernorm_rows: null pointer");
     if (rows <= 0 || in_stride < 1 || C <= 0 || (C & 7) || C > 8 * CN_NT || !(eps >= 0.f))
         return fail(h, MPX_E_ARG, "layernorm_rows: rows > 0, in_stride >= 1, C a positive multiple of 8 up to %d, eps >= 0", 8 * CN_NT);
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(ln_weight) || misaligned(ln_bias) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "layernorm_rows: every pointer must be 16-byte aligned");
-    CnLnRowsParams p;
-    std::memset(&p, 0, sizeof p);
-    p.ln.x_hi = (const half_t*)in_hi; p.ln.x_lo = (const half_t*)in_lo; p.ln.y_hi = (half_t*)out_hi; p.ln.y_lo = (half_t*)out_lo;
-    p.ln.gamma = ln_weight; p.ln.beta = ln_bias; p.ln.rows = rows; p.ln.C = C; p.ln.eps = eps;
-    p.in_stride = in_stride;
     MPX_SET_DEVICE(h);
-    return launch_ln_rows(h, p, max_blocks, -1, as_stream(stream));
+    return launch_ln_rows(h, ln_rows_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, in_stride, C), max_blocks, ProfTag(),
+                          as_stream(stream));
 }
 
 int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
@@ -4097,40 +4106,27 @@ int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
 int mpx_dwconv_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w, const float* scale, const float* shift, void* out_hi,
                       void* out_lo, int B, int hin, int pitch, int ksize, int stride, int act_in, int act_out, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!in_hi || !in_lo || !w || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "dwconv_bn_act: null pointer");
     if (B <= 0 || hin <= 0 || pitch <= 0 || (pitch & 7) || (ksize != 3 && ksize != 5) || (stride != 1 && stride != 2) || (act_in != 0 && act_in != 1) ||
         (act_out != 0 && act_out != 1))
         return fail(h, MPX_E_ARG, "dwconv_bn_act: B > 0, hin > 0, pitch a positive multiple of 8, ksize 3 or 5, stride 1 or 2, act codes 0 (none) or 1 (SiLU)");
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv_bn_act: every pointer must be 16-byte aligned");
-    MbDwParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.w = w; p.scale = scale; p.shift = shift;
-    p.hin = hin; p.ho = (hin - 1) / stride + 1; p.pitch = pitch; p.act_in = act_in; p.act_out = act_out;
-    p.rows = (long long)B * p.ho;
     MPX_SET_DEVICE(h);
-    return launch_mbdw(h, p, ksize, stride, -1, as_stream(stream));
+    return launch_mbdw(h, mbdw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, act_in, act_out), ksize, stride, ProfTag(),
+                       as_stream(stream));
 }
 
 // mpx_se_gate / mpx_se_gate_relu: one set of argument checks, the fc1 activation apart
 static int se_gate_entry(mpx_engine* h, const char* who, bool relu, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2,
                   const float* b2, float* gate, int B, int hw, int pitch, int q, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
     if (!in_hi || !in_lo || !w1 || !b1 || !w2 || !b2 || !gate) return fail(h, MPX_E_ARG, "%s: null pointer", who);
     if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7) || q <= 0) return fail(h, MPX_E_ARG, "%s: B > 0, hw > 0, pitch a positive multiple of 8, q > 0", who);
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w1) || misaligned(b1) || misaligned(w2) || misaligned(b2) || misaligned(gate))
-        return fail(h, MPX_E_ARG, "%s: every pointer must be 16-byte aligned", who);
+    if (planes_misaligned({in_hi, in_lo, w1, b1, w2, b2, gate})) return fail(h, MPX_E_ARG, "%s: every pointer must be 16-byte aligned", who);
     if (se_gate_lds(pitch, q) > 64 * 1024) return fail(h, MPX_E_ARG, "%s: pitch %d and q %d need more than 64 KB of LDS", who, pitch, q);
-    SeGateParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo;
-    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.gate = gate;
-    p.hw = hw; p.pitch = pitch; p.q = q;
     MPX_SET_DEVICE(h);
-    return launch_se_gate(h, p, B, -1, relu, as_stream(stream));
+    return launch_se_gate(h, se_gate_params(in_hi, in_lo, w1, b1, w2, b2, gate, hw, pitch, q), B, relu, ProfTag(), as_stream(stream));
 }
 
 int mpx_se_gate(mpx_engine* h, const void* in_hi, const void* in_lo, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
@@ -4146,19 +4142,11 @@ int mpx_se_gate_relu(mpx_engine* h, const void* in_hi, const void* in_lo, const 
 int mpx_se_scale(mpx_engine* h, const void* in_hi, const void* in_lo, const float* gate, void* out_hi, void* out_lo, int B, int hw, int pitch,
                  void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
     if (!in_hi || !in_lo || !gate || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "se_scale: null pointer");
     if (B <= 0 || hw <= 0 || pitch <= 0 || (pitch & 7)) return fail(h, MPX_E_ARG, "se_scale: B > 0, hw > 0, pitch a positive multiple of 8");
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(gate) || misaligned(out_hi) || misaligned(out_lo))
-        return fail(h, MPX_E_ARG, "se_scale: every pointer must be 16-byte aligned");
-    SeScaleParams p;
-    std::memset(&p, 0, sizeof p);
-    p.x_hi = (const half_t*)in_hi; p.x_lo = (const half_t*)in_lo; p.gate = gate; p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.pitch = pitch;
-    p.per_image = (long long)hw * (pitch / 8);
-    p.units = (long long)B * p.per_image;
+    if (planes_misaligned({in_hi, in_lo, gate, out_hi, out_lo})) return fail(h, MPX_E_ARG, "se_scale: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_se_scale(h, p, -1, as_stream(stream));
+    return launch_se_scale(h, se_scale_params(in_hi, in_lo, gate, out_hi, out_lo, B, hw, pitch), ProfTag(), as_stream(stream));
 }
 
 int mpx_pack_gconvw_weights(int width, int groups, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
@@ -4178,10 +4166,8 @@ int mpx_gconvw3x3_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, co
                          void* out_hi, void* out_lo, int B, int hin, int width, int groups, int in_pitch, int out_pitch, int stride, int relu,
                          void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
     if (!in_hi || !in_lo || !w_hi || !w_lo || !scale || !shift || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "gconvw3x3: null pointer");
-    if (misaligned(in_hi) || misaligned(in_lo) || misaligned(w_hi) || misaligned(w_lo) || misaligned(scale) || misaligned(shift) || misaligned(out_hi) ||
-        misaligned(out_lo))
+    if (planes_misaligned({in_hi, in_lo, w_hi, w_lo, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "gconvw3x3: every pointer must be 16-byte aligned");
     if (B <= 0 || hin <= 0 || width <= 0 || groups <= 0 || width % groups || (stride != 1 && stride != 2))
         return fail(h, MPX_E_ARG, "gconvw3x3: B > 0, hin > 0, width a positive multiple of groups > 0, stride 1 or 2");
@@ -4256,35 +4242,21 @@ int mpx_global_avgpool_silu(mpx_engine* h, const void* in_hi, const void* in_lo,
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool_silu: bad arguments (c multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "global_avgpool_silu: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const int total = B * (c / 8);
-    hipLaunchKernelGGL(global_avgpool_silu_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "global_avgpool_silu: the planes must be 16-byte aligned");
+    return launch_planes(h, global_avgpool_silu_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
+                         (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
 int mpx_shuffle2_concat(mpx_engine* h, const void* a_hi, const void* a_lo, int a_pitch, const void* b_hi, const void* b_lo, int b_pitch,
                         void* out_hi, void* out_lo, int B, int hw, int bf, int hp, void* stream) {
     if (!h) return MPX_E_ARG;
-    auto misaligned = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
     if (!a_hi || !a_lo || !b_hi || !b_lo || !out_hi || !out_lo) return fail(h, MPX_E_ARG, "shuffle2_concat: null pointer");
     if (B <= 0 || hw <= 0 || bf <= 0 || (bf & 1) || hp < bf || (hp & 31) || a_pitch < bf || (a_pitch & 7) || b_pitch < bf || (b_pitch & 7))
         return fail(h, MPX_E_ARG, "shuffle2_concat: B > 0, hw > 0, bf even and > 0, hp >= bf a multiple of 32, pitches >= bf and multiples of 8");
-    if (misaligned(a_hi) || misaligned(a_lo) || misaligned(b_hi) || misaligned(b_lo) || misaligned(out_hi) || misaligned(out_lo))
+    if (planes_misaligned({a_hi, a_lo, b_hi, b_lo, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "shuffle2_concat: every pointer must be 16-byte aligned");
-    ShuffleParams p;
-    std::memset(&p, 0, sizeof p);
-    p.a_hi = (const half_t*)a_hi; p.a_lo = (const half_t*)a_lo; p.b_hi = (const half_t*)b_hi; p.b_lo = (const half_t*)b_lo;
-    p.y_hi = (half_t*)out_hi; p.y_lo = (half_t*)out_lo;
-    p.npix = (long long)B * hw * hw;
-    p.a_pitch = a_pitch; p.b_pitch = b_pitch; p.bf = bf; p.hp = hp;
     MPX_SET_DEVICE(h);
-    return launch_shuffle(h, p, -1, as_stream(stream));
+    return launch_shuffle(h, shuffle_params(a_hi, a_lo, a_pitch, b_hi, b_lo, b_pitch, out_hi, out_lo, B, hw, bf, hp), ProfTag(), as_stream(stream));
 }
 
 int mpx_num_shuffles(const mpx_engine* h) { return h ? (int)h->shuffles.size() : MPX_E_ARG; }
@@ -4315,14 +4287,9 @@ int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_l
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool_clamp6: bad arguments (c multiple of 8)");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const int total = B * (c / 8);
-    hipLaunchKernelGGL(global_avgpool_clamp6_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi,
-                       (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    // (no alignment check, unlike its eight siblings: DESIGN.md 31 records the gap; closing it would reject calls that are accepted today)
+    return launch_planes(h, global_avgpool_clamp6_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
+                         (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
 int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_lo, float* out_f32, int B, int hw, int c, int out_pitch,
@@ -4330,15 +4297,9 @@ int mpx_global_avgpool_logits(mpx_engine* h, const void* in_hi, const void* in_l
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_f32 || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || out_pitch < c || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool_logits: bad arguments (c a multiple of 8, out_pitch >= c)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo) & 15) return fail(h, MPX_E_ARG, "global_avgpool_logits: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1);
-    const int total = B * (c / 8);
-    hipLaunchKernelGGL(global_avgpool_logits_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const half_t*)in_hi,
-                       (const half_t*)in_lo, out_f32, B, hw, c, out_pitch);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo})) return fail(h, MPX_E_ARG, "global_avgpool_logits: the planes must be 16-byte aligned");
+    return launch_planes(h, global_avgpool_logits_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
+                         (const half_t*)in_lo, out_f32, B, hw, c, out_pitch);
 }
 
 int mpx_conv_groups(const mpx_engine* h, int i, int* groups) {
@@ -4360,17 +4321,9 @@ int mpx_avgpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!h) return MPX_E_ARG;
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "avgpool2x2s2: bad arguments (hin even and > 0, c a positive multiple of 8)");
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)
-        return fail(h, MPX_E_ARG, "avgpool2x2s2: the planes must be 16-byte aligned");
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 2, -1, -2);
-    const size_t total = (size_t)B * (hin / 2) * (hin / 2) * (c / 8);
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->num_cus * 8);
-    hipLaunchKernelGGL(avgpool2x2s2_kernel, dim3(grid), dim3(256), 0, st, (const half_t*)in_hi, (const half_t*)in_lo,
-                       (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
+    if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "avgpool2x2s2: the planes must be 16-byte aligned");
+    return launch_planes(h, avgpool2x2s2_kernel, (size_t)B * (hin / 2) * (hin / 2) * (c / 8), GRID_PER_CU, ProfTag{PF_AVGPOOL2, 0}, stream,
+                         (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
 int mpx_head_softmax_gather(mpx_engine* h, const float* logits, const int32_t* label, float* score, int32_t* pred,
@@ -4402,6 +4355,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
     // (BUF_INPUT stays NULL: layer 0 reads the engine's own staging, mpx_conv_bn_act)
     auto hi = [&](int b) -> half_t* { return b == BUF_POOL ? h->pool_hi : (b == BUF_STEM ? h->stem_hi : (b >= 0 ? h->act_hi[b] : nullptr)); };
     auto lo = [&](int b) -> half_t* { return b == BUF_POOL ? h->pool_lo : (b == BUF_STEM ? h->stem_lo : (b >= 0 ? h->act_lo[b] : nullptr)); };
+    const hipStream_t st = as_stream(stream);
     int rc = 0;
     bool skip_pool = false;
     // how the B slots were staged: by K0 into the input staging (the stem conv + max pool run here) or by mpx_stem_table_apply, which has
@@ -4478,129 +4432,77 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_AVGLOGITS: rc = mpx_global_avgpool_logits(h, hi(o.in), lo(o.in), logits, B, o.hin * o.hin, o.c, h->logit_pitch, stream); break;
             case OP_MAXPOOL3C: {
                 const ClipPool& P = h->pools3c[o.conv];
-                rc = launch_pool3c(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, P.hin, P.stride, P.pad, P.pitch, o.conv, as_stream(stream));
+                rc = launch_pool3c(h, pool3c_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, P.hin, P.stride, P.pad, P.pitch), P.stride,
+                                   {PF_POOL3C, o.conv}, st);
                 break;
             }
             case OP_DWCONV: {
                 const DwLayer& D = h->dws[o.conv];
-                if (D.ln) {
-                    CnDwLnParams q;
-                    std::memset(&q, 0, sizeof q);
-                    q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                    q.w = D.w; q.bias = D.bias; q.gamma = D.scale; q.beta = D.shift;
-                    q.H = D.d.hin; q.C = D.d.channels; q.eps = D.eps;
-                    rc = launch_cn_dwln(h, q, B, 0, o.conv, as_stream(stream));
-                    break;
-                }
-                if (D.mb) {
-                    MbDwParams q;
-                    std::memset(&q, 0, sizeof q);
-                    q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                    q.w = D.w; q.scale = D.scale; q.shift = D.shift;
-                    q.hin = D.d.hin; q.ho = (D.d.hin - 1) / D.d.stride + 1; q.pitch = D.d.pitch; q.act_in = D.act_in; q.act_out = D.act_out;
-                    q.rows = (long long)B * q.ho;
-                    rc = launch_mbdw(h, q, D.ksize, D.d.stride, o.conv, as_stream(stream));
-                    break;
-                }
-                DwParams p;
-                std::memset(&p, 0, sizeof p);
-                p.x_hi = hi(o.in); p.x_lo = lo(o.in); p.y_hi = hi(o.out); p.y_lo = lo(o.out);
-                p.w = D.w; p.scale = D.scale; p.shift = D.shift;
-                p.hin = D.d.hin; p.ho = (D.d.hin - 1) / D.d.stride + 1; p.pitch = D.d.pitch; p.stride = D.d.stride; p.clamp_in = D.d.clamp_in;
-                p.npix = (long long)B * p.ho * p.ho;
-                rc = launch_dwconv(h, p, o.conv, as_stream(stream), D.linear);
+                const ProfTag tag{PF_DW, o.conv};
+                if (D.ln)
+                    rc = launch_cn_dwln(h, cn_dwln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.bias, D.scale, D.shift, D.eps, B, D.d.hin, D.d.channels),
+                                        0, tag, st);
+                else if (D.mb)
+                    rc = launch_mbdw(h, mbdw_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.scale, D.shift, B, D.d.hin, D.d.pitch, D.d.stride, D.act_in, D.act_out),
+                                     D.ksize, D.d.stride, tag, st);
+                else
+                    rc = launch_dwconv(h, dw_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.scale, D.shift, B, D.d.hin, D.d.pitch, D.d.stride, D.d.clamp_in),
+                                       D.linear, tag, st);
                 break;
             }
             case OP_SEGATE: {
                 const SeLayer& E = h->ses[o.conv];
-                SeGateParams p;
-                std::memset(&p, 0, sizeof p);
-                p.x_hi = hi(o.in); p.x_lo = lo(o.in);
-                p.w1 = E.w1; p.b1 = E.b1; p.w2 = E.w2; p.b2 = E.b2; p.gate = h->se_gate;
-                p.hw = E.d.hw * E.d.hw; p.pitch = E.d.pitch; p.q = E.d.q;
-                rc = launch_se_gate(h, p, B, o.conv, E.relu, as_stream(stream));
+                rc = launch_se_gate(h, se_gate_params(hi(o.in), lo(o.in), E.w1, E.b1, E.w2, E.b2, h->se_gate, E.d.hw * E.d.hw, E.d.pitch, E.d.q), B, E.relu,
+                                    {PF_SE_GATE, o.conv}, st);
                 break;
             }
             case OP_SESCALE: {
                 const SeLayer& E = h->ses[o.conv];
-                SeScaleParams p;
-                std::memset(&p, 0, sizeof p);
-                p.x_hi = hi(o.in); p.x_lo = lo(o.in); p.gate = h->se_gate; p.y_hi = hi(o.out); p.y_lo = lo(o.out);
-                p.pitch = E.d.pitch;
-                p.per_image = (long long)E.d.hw * E.d.hw * (E.d.pitch / 8);
-                p.units = (long long)B * p.per_image;
-                rc = launch_se_scale(h, p, o.conv, as_stream(stream));
+                rc = launch_se_scale(h, se_scale_params(hi(o.in), lo(o.in), h->se_gate, hi(o.out), lo(o.out), B, E.d.hw * E.d.hw, E.d.pitch),
+                                     {PF_SE_SCALE, o.conv}, st);
                 break;
             }
             case OP_AVGPOOLSILU: rc = mpx_global_avgpool_silu(h, hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, o.hin * o.hin, o.c, stream); break;
-            case OP_LNORM: {
+            case OP_LNORM: {        // rows: the pixels of a square map (ConvNeXt) or the tokens (ViT: o.hin = T)
                 const LnLayer& N = h->lnorms[o.conv];
-                CnLnParams q;
-                std::memset(&q, 0, sizeof q);
-                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                q.gamma = N.gamma; q.beta = N.beta; q.rows = h->vit ? (long long)B * o.hin : (long long)B * o.hin * o.hin; q.C = o.c; q.eps = N.eps;
-                rc = launch_cn_ln(h, q, 0, o.conv, as_stream(stream));
+                const long long rows = (long long)B * o.hin * (h->vit ? 1 : o.hin);
+                rc = launch_cn_ln(h, cn_ln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, rows, o.c), 0, {PF_LNORM, o.conv}, st);
                 break;
             }
-            case OP_LNORMROWS: {        // ViT: encoder.ln on the class-token row of each image (o.hin = T rows apart)
+            case OP_LNORMROWS: {    // ViT: encoder.ln on the class-token row of each image (o.hin = T rows apart)
                 const LnLayer& N = h->lnorms[o.conv];
-                CnLnRowsParams q;
-                std::memset(&q, 0, sizeof q);
-                q.ln.x_hi = hi(o.in); q.ln.x_lo = lo(o.in); q.ln.y_hi = hi(o.out); q.ln.y_lo = lo(o.out);
-                q.ln.gamma = N.gamma; q.ln.beta = N.beta; q.ln.rows = B; q.ln.C = o.c; q.ln.eps = N.eps;
-                q.in_stride = o.hin;
-                rc = launch_ln_rows(h, q, 0, o.conv, as_stream(stream));
+                rc = launch_ln_rows(h, ln_rows_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, B, o.hin, o.c), 0,
+                                    {PF_LNORM, o.conv}, st);
                 break;
             }
-            case OP_TOKENS: {
-                TokParams q;
-                std::memset(&q, 0, sizeof q);
-                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                q.cls = h->cls_token; q.pos = h->pos_emb; q.T = o.hin; q.D = o.c;
-                rc = launch_tokens(h, q, B, 0, true, as_stream(stream));
+            case OP_TOKENS:
+                rc = launch_tokens(h, tok_params(hi(o.in), lo(o.in), h->cls_token, h->pos_emb, hi(o.out), lo(o.out), B, o.hin, o.c), 0, {PF_TOKENS, 0}, st);
                 break;
-            }
             case OP_ATTN: {
                 const AttnLayer& A = h->attns[o.conv];
+                // (head_dim is AT_HD, build_topology_vit: the builder's D = heads * AT_HD is o.c)
                 if (A.d.heads * A.d.head_dim != o.c) { rc = fail(h, MPX_E_INTERNAL, "attention: heads * 64 != D on %s", A.d.name); break; }
-                AttnParams q;
-                std::memset(&q, 0, sizeof q);
-                q.qkv_hi = hi(o.in); q.qkv_lo = lo(o.in); q.o_hi = hi(o.out); q.o_lo = lo(o.out);
-                q.T = A.d.tokens; q.heads = A.d.heads; q.D = o.c;
-                rc = launch_attn(h, q, B, 0, o.conv, as_stream(stream));
+                rc = launch_attn(h, attn_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), B, A.d.tokens, A.d.heads), 0, {PF_ATTN, o.conv}, st);
                 break;
             }
             case OP_AVGPOOLLN: {
                 const LnLayer& N = h->lnorms[o.conv];
-                CnPoolLnParams q;
-                std::memset(&q, 0, sizeof q);
-                q.x_hi = hi(o.in); q.x_lo = lo(o.in); q.y_hi = hi(o.out); q.y_lo = lo(o.out);
-                q.gamma = N.gamma; q.beta = N.beta; q.B = B; q.hw = o.hin * o.hin; q.C = o.c; q.eps = N.eps;
-                rc = launch_cn_poolln(h, q, o.conv, as_stream(stream));
+                rc = launch_cn_poolln(h, cn_poolln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, B, o.hin * o.hin, o.c),
+                                      {PF_LNORM, o.conv}, st);
                 break;
             }
             case OP_SHUFFLE: {
                 const ShuffleOp& S = h->shuffles[o.conv];
-                ShuffleParams p;
-                std::memset(&p, 0, sizeof p);
-                p.a_hi = hi(o.in); p.a_lo = lo(o.in); p.b_hi = hi(o.res) + S.b_offset; p.b_lo = lo(o.res) + S.b_offset;
-                p.y_hi = hi(o.out); p.y_lo = lo(o.out);
-                p.npix = (long long)B * S.side * S.side;
-                p.a_pitch = S.a_pitch; p.b_pitch = S.b_pitch; p.bf = S.bf; p.hp = S.hp;
-                rc = launch_shuffle(h, p, o.conv, as_stream(stream));
+                rc = launch_shuffle(h, shuffle_params(hi(o.in), lo(o.in), S.a_pitch, hi(o.res) + S.b_offset, lo(o.res) + S.b_offset, S.b_pitch, hi(o.out), lo(o.out),
+                                                      B, S.side, S.bf, S.hp), {PF_SHUFFLE, o.conv}, st);
                 break;
             }
             case OP_CATNORM: {
                 // append the fresh g channels (o.in, dense) to the block's raw concatenation (o.res) and write relu(bn(.)) of its
                 // first o.c channels into o.out, in one launch
                 const NormLayer& nl = h->norms[o.conv];
-                CatNormParams p;
-                std::memset(&p, 0, sizeof p);
-                p.f_hi = hi(o.in); p.f_lo = lo(o.in); p.r_hi = hi(o.res); p.r_lo = lo(o.res); p.y_hi = hi(o.out); p.y_lo = lo(o.out);
-                p.scale = nl.scale; p.shift = nl.shift;
-                p.npix = (long long)B * o.hin * o.hin;
-                p.f_stride = o.g; p.c_total = o.ctot; p.c_old = o.c - o.g; p.c_begin = 0; p.c_end = o.c;
-                rc = launch_catnorm(h, p, o.conv, as_stream(stream));
+                rc = launch_catnorm(h, catnorm_params(hi(o.in), lo(o.in), o.g, o.g, hi(o.res), lo(o.res), o.ctot, o.c - o.g, nl.scale, nl.shift, hi(o.out), lo(o.out),
+                                                      o.c, (long long)B * o.hin * o.hin), {PF_NORM, o.conv}, st);
                 break;
             }
         }
@@ -4769,78 +4671,87 @@ int mpx_profile_enable(mpx_engine* h, int on) {
     return 0;
 }
 
+// The optional outputs of a profile collection beside the totals per kind (null: not wanted), in the order of the public argument lists
+struct ProfOut {
+    double *per_conv_ms, *per_norm_ms, *avgpool2_ms, *per_dw_ms, *per_clip_pool_ms, *per_shuffle_ms, *per_se_gate_ms, *per_se_scale_ms, *per_lnorm_ms,
+        *per_attn_ms, *tokens_ms;
+};
+
+// Every mpx_profile_collect* entry: a record adds to the totals of its kind, to its conv layer, and to entry `index` of its family's list
+static int profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], const ProfOut& o) {
+    if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
+    if (h->prof_used == 0) return 0;
+    const struct { double* ms; size_t n; } lists[PF_COUNT] = {
+        {nullptr, 0},                               // PF_NONE
+        {o.per_norm_ms, h->norms.size()},           // PF_NORM
+        {o.avgpool2_ms, 1},                         // PF_AVGPOOL2
+        {o.per_dw_ms, h->dws.size()},               // PF_DW
+        {o.per_clip_pool_ms, h->pools3c.size()},    // PF_POOL3C
+        {o.per_shuffle_ms, h->shuffles.size()},     // PF_SHUFFLE
+        {o.per_se_gate_ms, h->ses.size()},          // PF_SE_GATE
+        {o.per_se_scale_ms, h->ses.size()},         // PF_SE_SCALE
+        {o.per_lnorm_ms, h->lnorms.size()},         // PF_LNORM
+        {o.per_attn_ms, h->attns.size()},           // PF_ATTN
+        {o.tokens_ms, 1},                           // PF_TOKENS
+    };
+    MPX_SET_DEVICE(h);
+    MPX_HIP(h, hipEventSynchronize(h->prof_pool[h->prof_used - 1].t1));
+    for (int i = 0; i < h->prof_used; ++i) {
+        const ProfRec& r = h->prof_pool[i];
+        float ms = 0.f;
+        MPX_HIP(h, hipEventElapsedTime(&ms, r.t0, r.t1));
+        ms_by_kind[r.kind] += ms;
+        launches_by_kind[r.kind] += 1;
+        if (o.per_conv_ms && r.kind == OP_CONV && r.conv >= 0) o.per_conv_ms[r.conv] += ms;
+        if (lists[r.tag.family].ms && (size_t)r.tag.index < lists[r.tag.family].n) lists[r.tag.family].ms[r.tag.index] += ms;
+    }
+    h->prof_used = 0;
+    return 0;
+}
+
 int mpx_profile_collect(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms) {
-    return mpx_profile_collect_ex(h, ms_by_kind, launches_by_kind, per_conv_ms, nullptr, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms});
 }
 
 int mpx_profile_collect_ex(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms) {
-    return mpx_profile_collect_dw(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms});
 }
 
 int mpx_profile_collect_dw(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                            double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms) {
-    return mpx_profile_collect_pool(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms});
 }
 
 int mpx_profile_collect_pool(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                              double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms) {
-    return mpx_profile_collect_shuffle(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms});
 }
 
 int mpx_profile_collect_shuffle(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms,
                                 double* per_norm_ms, double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms) {
-    return mpx_profile_collect_se(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
-                                  nullptr, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms});
 }
 
 int mpx_profile_collect_se(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms) {
-    return mpx_profile_collect_ln(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
-                                  per_se_gate_ms, per_se_scale_ms, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                                                     per_se_gate_ms, per_se_scale_ms});
 }
 
 int mpx_profile_collect_ln(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                            double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                            double* per_se_scale_ms, double* per_lnorm_ms) {
-    return mpx_profile_collect_attn(h, ms_by_kind, launches_by_kind, per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
-                                    per_se_gate_ms, per_se_scale_ms, per_lnorm_ms, nullptr, nullptr);
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                                                     per_se_gate_ms, per_se_scale_ms, per_lnorm_ms});
 }
 
 int mpx_profile_collect_attn(mpx_engine* h, double ms_by_kind[4], long long launches_by_kind[4], double* per_conv_ms, double* per_norm_ms,
                              double* avgpool2_ms, double* per_dw_ms, double* per_clip_pool_ms, double* per_shuffle_ms, double* per_se_gate_ms,
                              double* per_se_scale_ms, double* per_lnorm_ms, double* per_attn_ms, double* tokens_ms) {
-    if (!h || !ms_by_kind || !launches_by_kind) return MPX_E_ARG;
-    if (h->prof_used == 0) return 0;
-    MPX_SET_DEVICE(h);
-    MPX_HIP(h, hipEventSynchronize(h->prof_pool[h->prof_used - 1].t1));
-    for (int i = 0; i < h->prof_used; ++i) {
-        ProfRec& r = h->prof_pool[i];
-        float ms = 0.f;
-        MPX_HIP(h, hipEventElapsedTime(&ms, r.t0, r.t1));
-        ms_by_kind[r.kind] += ms;
-        launches_by_kind[r.kind] += 1;
-        if (per_conv_ms && r.kind == OP_CONV && r.conv >= 0) per_conv_ms[r.conv] += ms;
-        if (per_norm_ms && r.kind == 2 && r.sub >= 0 && r.sub < (int)h->norms.size()) per_norm_ms[r.sub] += ms;
-        if (avgpool2_ms && r.kind == 2 && r.sub == -2) *avgpool2_ms += ms;
-        if (per_dw_ms && r.kind == 2 && r.sub <= kProfSubDw && kProfSubDw - r.sub < (int)h->dws.size()) per_dw_ms[kProfSubDw - r.sub] += ms;
-        if (per_clip_pool_ms && r.kind == 2 && r.sub <= kProfSubPool3c && kProfSubPool3c - r.sub < (int)h->pools3c.size())
-            per_clip_pool_ms[kProfSubPool3c - r.sub] += ms;
-        if (per_shuffle_ms && r.kind == 2 && r.sub <= kProfSubShuffle && kProfSubShuffle - r.sub < (int)h->shuffles.size())
-            per_shuffle_ms[kProfSubShuffle - r.sub] += ms;
-        if (per_se_gate_ms && r.kind == 2 && r.sub <= kProfSubSeGate && kProfSubSeGate - r.sub < (int)h->ses.size())
-            per_se_gate_ms[kProfSubSeGate - r.sub] += ms;
-        if (per_se_scale_ms && r.kind == 2 && r.sub <= kProfSubSeScale && kProfSubSeScale - r.sub < (int)h->ses.size())
-            per_se_scale_ms[kProfSubSeScale - r.sub] += ms;
-        if (per_lnorm_ms && r.kind == 2 && r.sub <= kProfSubLnorm && kProfSubLnorm - r.sub < (int)h->lnorms.size())
-            per_lnorm_ms[kProfSubLnorm - r.sub] += ms;
-        if (per_attn_ms && r.kind == 2 && r.sub <= kProfSubAttn && kProfSubAttn - r.sub < (int)h->attns.size())
-            per_attn_ms[kProfSubAttn - r.sub] += ms;
-        if (tokens_ms && r.kind == 2 && r.sub == kProfSubTokens) *tokens_ms += ms;
-    }
-    h->prof_used = 0;
-    return 0;
+    return profile_collect(h, ms_by_kind, launches_by_kind, ProfOut{per_conv_ms, per_norm_ms, avgpool2_ms, per_dw_ms, per_clip_pool_ms, per_shuffle_ms,
+                                                                     per_se_gate_ms, per_se_scale_ms, per_lnorm_ms, per_attn_ms, tokens_ms});
 }
 
 #ifdef MPX_DIAG
@@ -4859,7 +4770,7 @@ double mpx_flops_per_forward(const mpx_engine* h) {
         macs += (L.rows > 0 ? (double)L.rows : (double)L.d.hout * L.d.hout) * L.d.cout * (L.d.cin / L.groups) * L.d.ksize * L.d.ksize;
     for (const AttnLayer& A : h->attns) macs += 2.0 * A.d.tokens * A.d.tokens * A.d.head_dim * A.d.heads;      // Q K^T and P V
     for (const DwLayer& D : h->dws) {
-        const int ho = (D.d.hin - 1) / D.d.stride + 1;
+        const int ho = dw_out_side(D.d.hin, D.d.stride);
         macs += (double)ho * ho * D.d.channels * D.ksize * D.ksize;
     }
     for (const SeLayer& E : h->ses) macs += 2.0 * E.d.channels * E.d.q;

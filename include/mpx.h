@@ -330,6 +330,13 @@ size_t mpx_workspace_bytes(const mpx_engine* h);
  * out of mpx_global_avgpool_logits. */
 int mpx_num_convs(const mpx_engine* h);
 int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out);
+/* The layer plan build_topology makes for arch_id, as text; no engine, no device, no HIP call.  One record per line, "<section> [<index>]
+ * key=value ...": `engine` (the geometry and buffer plan), `conv` (every mpx_conv_desc field and the layer's layout, tile and fusion
+ * fields), the four op lists `ops` / `ops_bt` / `ops_pt` / `ops_pt0`, then `tail`, `ptail`, `norm`, `dw`, `lnorm`, `attn`, `se`, `shuffle`,
+ * `pool3c`.  Deterministic for an arch id; no pointer, no device property.
+ * *len = bytes needed (without the NUL), always set; buf == NULL: only that.  cap <= *len: MPX_E_ARG, nothing written.
+ * An arch id mpx_create rejects returns what mpx_create returns for it. */
+int mpx_describe_plan(int arch_id, char* buf, size_t cap, size_t* len);
 /* Where layer i writes: *pitch = channels between adjacent pixels of its output planes, *offset = its first channel within a pixel.  An
  * ordinary layer fills whole pixel rows: its stored channel count (cout, or cout rounded up to 32 where the network pads) and 0.  A
  * SqueezeNet expand conv writes half of its Fire module's concatenation: 2 * cout and 0 (expand1x1) or cout (expand3x3).  A GoogLeNet branch's

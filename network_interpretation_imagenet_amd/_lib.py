@@ -65,6 +65,7 @@ SIGNATURES = {
     "mpx_workspace_bytes": (C.c_size_t, [_vp]),
     "mpx_num_convs": (_i, [_vp]),
     "mpx_conv_info": (_i, [_vp, _i, C.POINTER(ConvDesc)]),
+    "mpx_describe_plan": (_i, [_i, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "mpx_set_conv_weights": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f]),
     "mpx_geometry": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mpx_mask_apply_minmax": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -337,1338 +337,8 @@ void set_name(char* dst, const std::string& s) {
     std::snprintf(dst, 48, "%s", s.c_str());
 }
 
-int default_tile(const mpx_conv_desc& d);
-bool patch_eligible(const mpx_conv_desc& d);
-
 constexpr int kGconvTile = 16;      // the grouped 3x3 kernel (mpx_gconv.h); ids 15 and 17 stay unassigned
 constexpr int kGconvwTile = 18;     // the grouped 3x3 kernel for any group count, width and pitch (mpx_gconvw.h)
-
-// torchvision ResNet topology (models/resnet.py, un-vendored): conv list and op list.
-int build_topology_small(mpx_engine* h);
-int build_topology_vgg(mpx_engine* h);
-int build_topology_alexnet(mpx_engine* h);
-int build_topology_densenet(mpx_engine* h);
-int build_topology_mobilenet(mpx_engine* h);
-int build_topology_squeezenet(mpx_engine* h);
-int build_topology_googlenet(mpx_engine* h);
-int build_topology_shufflenet(mpx_engine* h);
-int build_topology_efficientnet(mpx_engine* h);
-int build_topology_convnext(mpx_engine* h);
-int build_topology_vit(mpx_engine* h);
-int build_topology_regnet(mpx_engine* h);
-
-int build_topology(mpx_engine* h) {
-    if (h->arch == MPX_ARCH_MNIST_NET || (h->arch > MPX_ARCH_CIFAR_RESNET && h->arch < MPX_ARCH_CIFAR_RESNET + 1000))
-        return build_topology_small(h);
-    if (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) return build_topology_vgg(h);
-    if (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) return build_topology_alexnet(h);
-    if (h->arch >= MPX_ARCH_DENSENET && h->arch < MPX_ARCH_DENSENET + 1000) return build_topology_densenet(h);
-    if (h->arch >= MPX_ARCH_MOBILENET && h->arch < MPX_ARCH_MOBILENET + 1000) return build_topology_mobilenet(h);
-    if (h->arch >= MPX_ARCH_SQUEEZENET && h->arch < MPX_ARCH_SQUEEZENET + 1000) return build_topology_squeezenet(h);
-    if (h->arch >= MPX_ARCH_GOOGLENET && h->arch < MPX_ARCH_GOOGLENET + 1000) return build_topology_googlenet(h);
-    if (h->arch >= MPX_ARCH_SHUFFLENET && h->arch < MPX_ARCH_SHUFFLENET + 1000) return build_topology_shufflenet(h);
-    if (h->arch >= MPX_ARCH_EFFICIENTNET && h->arch < MPX_ARCH_EFFICIENTNET + 1000) return build_topology_efficientnet(h);
-    if (h->arch >= MPX_ARCH_CONVNEXT && h->arch < MPX_ARCH_CONVNEXT + 1000) return build_topology_convnext(h);
-    if (h->arch >= MPX_ARCH_VIT && h->arch < MPX_ARCH_VIT + 1000) return build_topology_vit(h);
-    if (h->arch >= MPX_ARCH_REGNET && h->arch < MPX_ARCH_REGNET_Y + 1000) return build_topology_regnet(h);
-    h->act_elems_per_image = kActElemsPerImage;
-    int depths[4];
-    // ResNeXt (torchvision's Bottleneck with groups = 32): width = planes * width_per_group / 64 * groups; conv2 is the one grouped layer
-    int groups = 1, wpg = 64;
-    switch (h->arch) {
-        case MPX_ARCH_RESNEXT + 50: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = true; groups = 32; wpg = 4; break;
-        case MPX_ARCH_RESNEXT + 101:
-            depths[0] = 3; depths[1] = 4; depths[2] = 23; depths[3] = 3; h->bottleneck = true; groups = 32; wpg = 8;
-            h->act_elems_per_image = 2 * kActElemsPerImage;     // layer2.0.conv1 writes 56 * 56 * 512
-            break;
-        case 18: depths[0] = 2; depths[1] = 2; depths[2] = 2; depths[3] = 2; h->bottleneck = false; break;
-        case 34: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = false; break;
-        case 50: depths[0] = 3; depths[1] = 4; depths[2] = 6; depths[3] = 3; h->bottleneck = true; break;
-        case 101: depths[0] = 3; depths[1] = 4; depths[2] = 23; depths[3] = 3; h->bottleneck = true; break;
-        case 152: depths[0] = 3; depths[1] = 8; depths[2] = 36; depths[3] = 3; h->bottleneck = true; break;
-        default: return MPX_E_ARG;
-    }
-    const int exp = h->bottleneck ? 4 : 1;
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride,
-                        int pad, int hin, int relu, int residual) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu; L.d.residual = residual;
-        L.is_stem = (cin == 3);
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        // (a ResNeXt engine hands the persistent kernels -- tiles 9, 10, 13, 14 and the dual form of 13 -- dense shapes that no served ResNet
-        // has: DESIGN.md 21 goes through every (shape, default tile) pair; none needed a default of its own)
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    // the grouped 3x3 conv2 of a ResNeXt block (mpx_gconv.h): w -> w, `groups` groups
-    auto add_gconv = [&](const std::string& name, const std::string& bn, int w, int stride, int hin) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = w; L.d.cout = w; L.d.ksize = 3; L.d.stride = stride; L.d.pad = 1;
-        L.d.hin = hin; L.d.hout = (hin + 2 - 3) / stride + 1;
-        L.d.relu = 1; L.d.residual = 0;
-        L.cin_pad = w;
-        L.cout_store = w;
-        L.groups = groups;
-        L.d.k_packed = gconv_kp(gconv_cb(w / groups));
-        L.d.cout_pad = w;
-        L.tile = L.tile_default = kGconvTile;
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto add_op = [&](int kind, int conv, int in, int out, int res, int hin, int c, int in2 = BUF_NONE) {
-        Op o{kind, conv, in, out, res, hin, c, in2};
-        h->ops.push_back(o);
-    };
-    auto pick = [&](std::initializer_list<int> busy) {
-        for (int b = 0; b < kActBufs; ++b) {
-            bool used = false;
-            for (int u : busy) used |= (u == b);
-            if (!used) return b;
-        }
-        return -100;
-    };
-
-    int c = add_conv("conv1", "bn1", 3, 64, 7, 2, 3, 224, 1, 0);
-    add_op(OP_CONV, c, BUF_INPUT, 0, BUF_NONE, 0, 0);
-    add_op(OP_MAXPOOL, -1, 0, BUF_STEM, BUF_NONE, 112, 64);      // the pooled planes have a buffer of their own: nothing overwrites them
-    int X = BUF_STEM, cin = 64, hcur = 56;
-    const int planes[4] = {64, 128, 256, 512};
-    struct BlockRec { int c1, c2, c3, ds, hin; };
-    std::vector<BlockRec> blocks;       // bottleneck blocks in forward order (the block-tail plan below is built from them)
-    for (int s = 0; s < 4; ++s) {
-        const int pl = planes[s];                   // the block's output is pl * exp channels
-        const int w = pl * wpg / 64 * groups;       // its inner width (= pl on a ResNet)
-        for (int b = 0; b < depths[s]; ++b) {
-            const int stride = (b == 0 && s > 0) ? 2 : 1;
-            const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(b) + ".";
-            const bool ds = (b == 0) && (stride != 1 || cin != pl * exp);
-            const int hout = hcur / stride;
-            if (!h->bottleneck) {
-                const int T1 = pick({X});
-                c = add_conv(p + "conv1", p + "bn1", cin, w, 3, stride, 1, hcur, 1, 0);
-                add_op(OP_CONV, c, X, T1, BUF_NONE, 0, 0);
-                int res = X, T2 = -100;
-                if (ds) {
-                    T2 = pick({X, T1});
-                    c = add_conv(p + "downsample.0", p + "downsample.1", cin, w * exp, 1, stride, 0, hcur, 0, 0);
-                    add_op(OP_CONV, c, X, T2, BUF_NONE, 0, 0);
-                    res = T2;
-                }
-                const int O = pick({X, T1, T2});
-                c = add_conv(p + "conv2", p + "bn2", w, w, 3, 1, 1, hout, 1, 1);
-                add_op(OP_CONV, c, T1, O, res, 0, 0);
-                X = O;
-            } else {
-                BlockRec R{-1, -1, -1, -1, hcur};
-                const int T1 = pick({X});
-                R.c1 = c = add_conv(p + "conv1", p + "bn1", cin, w, 1, 1, 0, hcur, 1, 0);
-                add_op(OP_CONV, c, X, T1, BUF_NONE, 0, 0);
-                const int T2 = pick({X, T1});
-                R.c2 = c = groups > 1 ? add_gconv(p + "conv2", p + "bn2", w, stride, hcur) : add_conv(p + "conv2", p + "bn2", w, w, 3, stride, 1, hcur, 1, 0);
-                add_op(OP_CONV, c, T1, T2, BUF_NONE, 0, 0);
-                int res = X, dsc = -1;
-                if (ds) {
-                    const int T3 = pick({X, T1, T2});
-                    R.ds = dsc = add_conv(p + "downsample.0", p + "downsample.1", cin, pl * exp, 1, stride, 0, hcur, 0, 0);
-                    add_op(OP_CONV, dsc, X, T3, BUF_NONE, 0, 0);
-                    res = T3;
-                }
-                R.c3 = c = add_conv(p + "conv3", p + "bn3", w, pl * exp, 1, 1, 0, hout, 1, 1);
-                add_op(OP_CONV, c, T2, T1, res, 0, 0, ds ? X : BUF_NONE);   // T1 is dead after conv2
-                if (ds) {
-                    h->convs[c].fuse_partner = dsc; h->convs[c].fuse_main = true;
-                    h->convs[dsc].fuse_partner = c;
-                }
-                blocks.push_back(R);
-                X = T1;
-            }
-            cin = pl * exp;
-            hcur = hout;
-        }
-    }
-    // Block-tail plan (mpx_btail.h): a block whose conv2 is 64 -> 64 3x3 stride 1 on a 56x56 map, whose conv3 is 64 -> 256 and
-    // whose successor starts with a 1x1 stride-1 conv 256 -> 64 / 128 (layer1 of ResNet-50 / 101 / 152) runs conv2, conv3 (+ the
-    // identity or the K-concatenated downsample branch) and the successor's conv1 as ONE launch.  Four distinct buffers are live
-    // across such a launch (block input, t1, block output, next t1): other workgroups still read t1's halo while this one writes.
-    {
-        auto tail_ok = [&](size_t k) {
-            if (k + 1 >= blocks.size()) return false;
-            const mpx_conv_desc& d2 = h->convs[blocks[k].c2].d;
-            const mpx_conv_desc& d3 = h->convs[blocks[k].c3].d;
-            const mpx_conv_desc& n1 = h->convs[blocks[k + 1].c1].d;
-            if (!(d2.cin == BT_MID && d2.cout == BT_MID && d2.ksize == 3 && d2.stride == 1 && d2.hin == 56)) return false;
-            if (!(d3.cin == BT_MID && d3.cout == BT_OUT)) return false;
-            if (blocks[k].ds >= 0) {
-                const mpx_conv_desc& dd = h->convs[blocks[k].ds].d;
-                if (!(dd.cin == BT_MID && dd.stride == 1 && dd.ksize == 1)) return false;
-            }
-            return n1.cin == BT_OUT && n1.ksize == 1 && n1.stride == 1 && n1.hin == 56 && (n1.cout == 64 || n1.cout == 128) &&
-                   !(blocks[k].ds >= 0 && n1.cout != 64);
-        };
-        // Pointwise-tail plan (mpx_btail.h, BtPwCfg): a plain block (no downsample branch) whose conv3 is 128 -> 512 and whose successor
-        // starts with a 1x1 stride-1 conv 512 -> 128 (layer2's blocks 1 .. n-2) runs conv3 + identity and the successor's conv1 as ONE
-        // launch.  Four distinct buffers again: t2, the identity, the block output, the next t1.
-        auto ptail_ok = [&](size_t k) {
-            if (k + 1 >= blocks.size() || blocks[k].ds >= 0 || tail_ok(k)) return false;
-            const mpx_conv_desc& d3 = h->convs[blocks[k].c3].d;
-            const mpx_conv_desc& n1 = h->convs[blocks[k + 1].c1].d;
-            return d3.cin == BtPw128::MID && d3.cout == BtPw128::OUT && d3.ksize == 1 && d3.stride == 1 && d3.residual == 1 &&
-                   n1.cin == BtPw128::OUT && n1.cout == BtPw128::C1 && n1.ksize == 1 && n1.stride == 1 && n1.hin == d3.hin;
-        };
-        bool any = false;
-        for (size_t k = 0; k < blocks.size(); ++k) any |= tail_ok(k);
-        // one launch plan: layer1's block tails as OP_BTAIL (bt), layer2's pointwise tails as OP_PTAIL (pt); rec_bt / rec_pt: this plan is the
-        // one that fills h->tails / h->ptails (each list once: the other plans number their launches the same way)
-        auto plan = [&](std::vector<Op>& out, bool bt, bool pt, bool rec_bt, bool rec_pt) {
-            size_t n_bt = 0, n_pt = 0;
-            out.push_back(h->ops[0]);       // stem conv, max pool
-            out.push_back(h->ops[1]);
-            int Xb = BUF_STEM, T1c = -100;         // T1c: buffer of a t1 that the previous tail launch has already written
-            for (size_t k = 0; k < blocks.size(); ++k) {
-                const BlockRec& R = blocks[k];
-                int T1 = T1c;
-                // a tail with a downsample branch (layer1.0) runs its block's own conv1 too, on the patch of the block input: no conv1
-                // launch, no t1 tensor (in = BUF_NONE)
-#ifdef BT_NO_HEAD       // probe builds (tools/ab_lib.sh): layer1.0.conv1 stays a launch of its own
-                const bool whole = false;
-#else
-                const bool whole = bt && tail_ok(k) && R.ds >= 0 && T1 < 0;
-#endif
-                if (T1 < 0 && !whole) {
-                    T1 = pick({Xb});
-                    out.push_back(Op{OP_CONV, R.c1, Xb, T1, BUF_NONE, 0, 0, BUF_NONE});
-                }
-                T1c = -100;
-                if (bt && tail_ok(k)) {
-                    if (rec_bt) {
-                        TailBlock tb;
-                        tb.c1 = R.c1; tb.c2 = R.c2; tb.c3 = R.c3; tb.ds = R.ds; tb.next1 = blocks[k + 1].c1;
-                        h->tails.push_back(tb);
-                    }
-                    if (whole) T1 = BUF_NONE;
-                    const int O = pick({Xb, T1}), Z = pick({Xb, T1, O});
-                    Op o{OP_BTAIL, (int)n_bt++, T1, O, Xb, 0, 0, BUF_NONE};
-                    o.z = Z;
-                    out.push_back(o);
-                    Xb = O;
-                    T1c = Z;
-                    continue;
-                }
-                const int T2 = pick({Xb, T1});
-                out.push_back(Op{OP_CONV, R.c2, T1, T2, BUF_NONE, 0, 0, BUF_NONE});
-                if (pt && ptail_ok(k)) {
-                    if (rec_pt) h->ptails.push_back(PointTail{R.c3, blocks[k + 1].c1});
-                    const int O = pick({Xb, T2}), Z = pick({Xb, T2, O});
-                    Op o{OP_PTAIL, (int)n_pt++, T2, O, Xb, 0, 0, BUF_NONE};
-                    o.z = Z;
-                    out.push_back(o);
-                    Xb = O;
-                    T1c = Z;
-                    continue;
-                }
-                int res = Xb;
-                if (R.ds >= 0) {
-                    const int T3 = pick({Xb, T1, T2});
-                    out.push_back(Op{OP_CONV, R.ds, Xb, T3, BUF_NONE, 0, 0, BUF_NONE});
-                    res = T3;
-                }
-                out.push_back(Op{OP_CONV, R.c3, T2, T1, res, 0, 0, R.ds >= 0 ? Xb : BUF_NONE});
-                Xb = T1;
-            }
-            return Xb;
-        };
-        bool any_pt = false;
-        for (size_t k = 0; k < blocks.size(); ++k) any_pt |= ptail_ok(k);
-        if (any) h->ops_bt_x = plan(h->ops_bt, true, false, true, false);
-        if (any_pt) {       // (an arch with pointwise tails and no block tails gets ops_pt0 alone: mpx_forward never picks ops_pt then)
-            h->ops_pt0_x = plan(h->ops_pt0, false, true, false, true);
-            if (any) h->ops_pt_x = plan(h->ops_pt, true, true, false, false);
-        }
-    }
-    h->feat = cin;
-    add_op(OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hcur, cin);
-    c = add_conv("fc", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0);
-    h->convs[c].is_fc = true;
-    add_op(OP_CONV, c, BUF_POOL, BUF_NONE, BUF_NONE, 0, 0);
-    add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0);
-    for (auto lx : {std::make_pair(&h->ops_bt, h->ops_bt_x), std::make_pair(&h->ops_pt, h->ops_pt_x), std::make_pair(&h->ops_pt0, h->ops_pt0_x)}) {
-        if (lx.first->empty()) continue;
-        lx.first->push_back(Op{OP_AVGPOOL, -1, lx.second, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
-        lx.first->push_back(h->ops[h->ops.size() - 2]);
-        lx.first->push_back(h->ops[h->ops.size() - 1]);
-    }
-    return 0;
-}
-
-// The reference's small networks.  Channels are stored padded to 32 (zero weights / zero scale and
-// shift on the padding, so padded channels stay exactly 0 through ReLU and residual adds).
-//   MPX_ARCH_MNIST_NET: Classification_Net, generate_gp_training_data_mnist.py:86-105
-//       conv1..5 = Conv2d(3x3, pad 1, BIAS) + BN + ReLU (strides 1,1,2,1,2; 1->32->32->64->64->128), conv6 = Conv2d(128,128,3,pad 1)
-//       with bias and nothing else, mean over HxW, fc1 128->10.
-//   MPX_ARCH_CIFAR_RESNET + depth: ResNetCifar(depth = 6n+2), models/resnet.py:77-146: conv3x3(3->16)+BN+ReLU, three stages
-//       of n BasicBlocks (16, 32, 64 planes; the first block of stages 2 and 3 has stride 2 and DownsampleB = AvgPool2d(2) +
-//       zero channels on the identity, :64-74), AvgPool2d(8), fc 64->10.
-int build_topology_small(mpx_engine* h) {
-    h->small = true;
-    h->ncls = 10;
-    h->logit_pitch = 16;
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad,
-                        int hin, int relu, int residual, bool bias, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu; L.d.residual = residual;
-        L.has_bias = bias;
-        L.is_fc = fc;
-        L.cin_pad = (int)round_up(cin, kSmallCPad);
-        L.cout_store = fc ? h->logit_pitch : (int)round_up(cout, kSmallCPad);
-        L.d.k_packed = k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto add_op = [&](int kind, int conv, int in, int out, int res, int hin, int c) {
-        Op o{kind, conv, in, out, res, hin, c, BUF_NONE};
-        h->ops.push_back(o);
-    };
-    int feat = 0, hlast = 0, X = 0;
-    size_t act = 0;
-    auto track = [&](int hout, int c) { act = std::max(act, (size_t)hout * hout * round_up(c, kSmallCPad)); };
-    if (h->arch == MPX_ARCH_MNIST_NET) {
-        h->img = 28; h->in_ch = 1;
-        const int cfg[5][3] = {{1, 32, 1}, {32, 32, 1}, {32, 64, 2}, {64, 64, 1}, {64, 128, 2}};
-        int hcur = 28, in = BUF_INPUT;
-        for (int i = 0; i < 5; ++i) {
-            const std::string n = "conv" + std::to_string(i + 1);
-            const int c = add_conv(n + ".0", n + ".1", cfg[i][0], cfg[i][1], 3, cfg[i][2], 1, hcur, 1, 0, true, false);
-            const int out = (in == 0) ? 1 : 0;
-            add_op(OP_CONV, c, in, out, BUF_NONE, 0, 0);
-            in = out;
-            hcur = h->convs[c].d.hout;
-            track(hcur, cfg[i][1]);
-        }
-        const int c6 = add_conv("conv6", "", 128, 128, 3, 1, 1, hcur, 0, 0, true, false);     // bias only: packed like fc (gamma = NULL)
-        X = (in == 0) ? 1 : 0;
-        add_op(OP_CONV, c6, in, X, BUF_NONE, 0, 0);
-        feat = 128; hlast = hcur;
-        h->feat = feat;
-        add_op(OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hlast, feat);
-        const int cf = add_conv("fc1", "", feat, 10, 1, 1, 0, 1, 0, 0, true, true);
-        add_op(OP_CONV, cf, BUF_POOL, BUF_NONE, BUF_NONE, 0, 0);
-    } else {
-        const int depth = h->arch - MPX_ARCH_CIFAR_RESNET;
-        if (depth < 8 || (depth - 2) % 6 != 0) return MPX_E_ARG;
-        const int n = (depth - 2) / 6;
-        h->img = 32; h->in_ch = 3;
-        int c = add_conv("conv1", "bn1", 3, 16, 3, 1, 1, 32, 1, 0, false, false);
-        add_op(OP_CONV, c, BUF_INPUT, 0, BUF_NONE, 0, 0);
-        track(32, 16);
-        X = 0;
-        int inplanes = 16, hcur = 32;
-        const int planes_of[3] = {16, 32, 64};
-        for (int sidx = 0; sidx < 3; ++sidx) {
-            const int planes = planes_of[sidx];
-            for (int b = 0; b < n; ++b) {
-                const int stride = (sidx > 0 && b == 0) ? 2 : 1;
-                const std::string p = "layer" + std::to_string(sidx + 1) + "." + std::to_string(b) + ".";
-                int busy[3] = {X, -1, -1};
-                auto pick = [&]() {
-                    for (int q = 0; q < kActBufs; ++q)
-                        if (q != busy[0] && q != busy[1] && q != busy[2]) return q;
-                    return -100;
-                };
-                const int T1 = pick();
-                busy[1] = T1;
-                c = add_conv(p + "conv1", p + "bn1", inplanes, planes, 3, stride, 1, hcur, 1, 0, false, false);
-                add_op(OP_CONV, c, X, T1, BUF_NONE, 0, 0);
-                const int hout = h->convs[c].d.hout;
-                int res = X;
-                if (stride != 1 || inplanes != planes) {            // DownsampleB on the identity
-                    const int T2 = pick();
-                    busy[2] = T2;
-                    add_op(OP_AVGPAD, -1, X, T2, BUF_NONE, hcur, (int)round_up(inplanes, kSmallCPad) * 65536 + (int)round_up(planes, kSmallCPad));
-                    res = T2;
-                }
-                const int O = pick();
-                c = add_conv(p + "conv2", p + "bn2", planes, planes, 3, 1, 1, hout, 1, 1, false, false);
-                add_op(OP_CONV, c, T1, O, res, 0, 0);
-                X = O;
-                inplanes = planes;
-                hcur = hout;
-                track(hcur, planes);
-            }
-        }
-        feat = 64; hlast = hcur;
-        h->feat = feat;
-        add_op(OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hlast, feat);
-        const int cf = add_conv("fc", "", feat, 10, 1, 1, 0, 1, 0, 0, true, true);
-        add_op(OP_CONV, cf, BUF_POOL, BUF_NONE, BUF_NONE, 0, 0);
-    }
-    add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0);
-    h->act_elems_per_image = act;
-    return 0;
-}
-
-// torchvision VGG (vgg.py: make_layers over cfgs "A" / "B" / "D" / "E", then the classifier), depth 11 / 13 / 16 / 19, with or without
-// BatchNorm.  Names follow torchvision's module indices: a conv at features.i, its BatchNorm (the _bn variants) at features.(i+1), the ReLU
-// after them, one index per "M" (MaxPool2d(2, 2)).  Every conv has a bias.  The classifier runs as three more layers of the conv list:
-// classifier.0 = Linear(25088, 4096) as a 7x7 valid conv over the [B][7][7][512] map (torch.flatten of NCHW is channel-major, so the
-// [4096][25088] weight viewed as [4096][512][7][7] is its OIHW weight), classifier.3 = Linear(4096, 4096) as a 1x1 conv, classifier.6 =
-// Linear(4096, 1000), the logit layer.  AdaptiveAvgPool2d((7, 7)) on a 7x7 map and Dropout in eval are identities.  A plain chain: the
-// op list ping-pongs between two activation buffers.
-int build_topology_vgg(mpx_engine* h) {
-    const bool bn = h->arch > MPX_ARCH_VGG_BN;
-    const int depth = h->arch - (bn ? MPX_ARCH_VGG_BN : MPX_ARCH_VGG);
-    constexpr int M = 0;                                    // "M" of the cfgs
-    static const int cfg_a[] = {64, M, 128, M, 256, 256, M, 512, 512, M, 512, 512, M};
-    static const int cfg_b[] = {64, 64, M, 128, 128, M, 256, 256, M, 512, 512, M, 512, 512, M};
-    static const int cfg_d[] = {64, 64, M, 128, 128, M, 256, 256, 256, M, 512, 512, 512, M, 512, 512, 512, M};
-    static const int cfg_e[] = {64, 64, M, 128, 128, M, 256, 256, 256, 256, M, 512, 512, 512, 512, M, 512, 512, 512, 512, M};
-    const int* cfg = nullptr;
-    int n = 0;
-    switch (depth) {
-        case 11: cfg = cfg_a; n = (int)(sizeof cfg_a / sizeof *cfg_a); break;
-        case 13: cfg = cfg_b; n = (int)(sizeof cfg_b / sizeof *cfg_b); break;
-        case 16: cfg = cfg_d; n = (int)(sizeof cfg_d / sizeof *cfg_d); break;
-        case 19: cfg = cfg_e; n = (int)(sizeof cfg_e / sizeof *cfg_e); break;
-        default: return MPX_E_ARG;
-    }
-    h->n_act_bufs = 2;
-    h->act_elems_per_image = kVggActElemsPerImage;
-    auto add_conv = [&](const std::string& name, const std::string& bn_name, int cin, int cout, int k, int pad, int hin, int relu, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn_name);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = 1; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = hin + 2 * pad - k + 1;
-        L.d.relu = relu;
-        L.has_bias = true;
-        L.is_fc = fc;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto add_op = [&](int kind, int conv, int in, int out, int hin, int c) {
-        h->ops.push_back(Op{kind, conv, in, out, BUF_NONE, hin, c, BUF_NONE});
-    };
-    int X = BUF_INPUT, cin = 3, hcur = MPX_IMG, idx = 0;
-    for (int j = 0; j < n; ++j) {
-        const int O = X == 0 ? 1 : 0;
-        if (cfg[j] == M) {
-            add_op(OP_MAXPOOL2, -1, X, O, hcur, cin);
-            hcur /= 2;
-            idx += 1;
-        } else {
-            const int c = add_conv("features." + std::to_string(idx), bn ? "features." + std::to_string(idx + 1) : "", cin, cfg[j], 3, 1, hcur, 1, false);
-            add_op(OP_CONV, c, X, O, 0, 0);
-            cin = cfg[j];
-            idx += bn ? 3 : 2;
-        }
-        X = O;
-    }
-    // hcur = 7, cin = 512
-    int O = X == 0 ? 1 : 0;
-    int c = add_conv("classifier.0", "", cin, 4096, hcur, 0, hcur, 1, false);
-    add_op(OP_CONV, c, X, O, 0, 0);
-    X = O; O = X == 0 ? 1 : 0;
-    c = add_conv("classifier.3", "", 4096, 4096, 1, 0, 1, 1, false);
-    add_op(OP_CONV, c, X, O, 0, 0);
-    X = O;
-    c = add_conv("classifier.6", "", 4096, MPX_NUM_CLASSES, 1, 0, 1, 0, true);
-    add_op(OP_CONV, c, X, BUF_NONE, 0, 0);
-    add_op(OP_HEAD, -1, BUF_NONE, BUF_NONE, 0, 0);
-    return 0;
-}
-
-// torchvision AlexNet (alexnet.py): features = conv 11x11/4 pad 2 (3 -> 64), ReLU, MaxPool2d(3, 2), conv 5x5 pad 2 (64 -> 192), ReLU,
-// MaxPool2d(3, 2), conv 3x3 pad 1 (192 -> 384), ReLU, conv 3x3 pad 1 (384 -> 256), ReLU, conv 3x3 pad 1 (256 -> 256), ReLU, MaxPool2d(3, 2);
-// maps 224 -> 55 -> 27 -> 27 -> 13 -> 13 -> 13 -> 13 -> 6.  No BatchNorm, every layer has a bias.  The classifier runs as three more
-// layers of the conv list, as VGG's: classifier.1 = Linear(9216, 4096) as a 6x6 valid conv over the [B][6][6][256] map (the [4096][9216]
-// weight viewed as [4096][256][6][6] is its OIHW weight), classifier.4 = Linear(4096, 4096) as a 1x1 conv, classifier.6 = the logit layer.
-// AdaptiveAvgPool2d((6, 6)) on a 6x6 map and Dropout in eval are identities.  The op list ping-pongs between two activation buffers.
-int build_topology_alexnet(mpx_engine* h) {
-    if (h->arch != MPX_ARCH_ALEXNET) return MPX_E_ARG;
-    h->n_act_bufs = 2;
-    h->act_elems_per_image = kAlexActElemsPerImage;
-    auto add_conv = [&](const char* name, int cin, int cout, int k, int stride, int pad, int hin, int relu, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu;
-        L.has_bias = true;
-        L.is_fc = fc;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 16-pixel x 4-channel run (two K steps) per kernel row
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? k * 64 : k * k * cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    int X = BUF_INPUT, hcur = MPX_IMG, ccur = 3;
-    auto conv = [&](const char* name, int cout, int k, int stride, int pad, int relu = 1, bool fc = false) {
-        const int O = fc ? BUF_NONE : (X == 0 ? 1 : 0);
-        const int c = add_conv(name, ccur, cout, k, stride, pad, hcur, relu, fc);
-        h->ops.push_back(Op{OP_CONV, c, X, O, BUF_NONE, 0, 0, BUF_NONE});
-        hcur = h->convs[c].d.hout; ccur = cout; X = O;
-    };
-    auto pool = [&]() {
-        const int O = X == 0 ? 1 : 0;
-        h->ops.push_back(Op{OP_MAXPOOL3P0, -1, X, O, BUF_NONE, hcur, ccur, BUF_NONE});
-        hcur = (hcur - 3) / 2 + 1; X = O;
-    };
-    conv("features.0", 64, 11, 4, 2);       // 224 -> 55
-    pool();                                 // 55 -> 27
-    conv("features.3", 192, 5, 1, 2);
-    pool();                                 // 27 -> 13
-    conv("features.6", 384, 3, 1, 1);
-    conv("features.8", 256, 3, 1, 1);
-    conv("features.10", 256, 3, 1, 1);
-    pool();                                 // 13 -> 6
-    conv("classifier.1", 4096, hcur, 1, 0); // 6x6 valid conv: K = 9216
-    conv("classifier.4", 4096, 1, 1, 0);
-    conv("classifier.6", MPX_NUM_CLASSES, 1, 1, 0, 0, true);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision DenseNet (densenet.py; growth rate 32, bn_size 4, 64 initial features): features.conv0 (3 -> 64, 7x7 stride 2 pad 3) + norm0
-// + ReLU + MaxPool2d(3, 2, 1) -- the ResNet stem shape, so the fused stem + pool launch serves it --, four dense blocks with a transition
-// behind the first three, norm5 + ReLU, global average pool, classifier.  No conv has a bias.
-//   dense layer j of block b on C = C_in + 32 (j - 1) channels: norm1(C) -> ReLU -> conv1 1x1 C -> 128 -> norm2 -> ReLU -> conv2 3x3 pad 1
-//       128 -> 32, output concatenated behind the C input channels.  norm2 + ReLU are conv1's epilogue; conv2 has no epilogue at all.
-//   transition b: norm(C) -> ReLU -> conv 1x1 C -> C / 2 -> AvgPool2d(2, 2), in torchvision's order (the conv at full resolution).
-// Buffers: R = 0 the block's RAW concatenation [B][H][W][C_block], N = 1 its normalised first C channels (dense), T1 = 2 conv1's /
-// the transition conv's output, T2 = 3 conv2's / the average pool's output.  One OP_CATNORM per consumer of the concatenation appends
-// the fresh channels (the block input: the pooled stem / the pooled transition; then every conv2 output) to R and writes the consumer's
-// relu(bn(.)) into N.
-int build_topology_densenet(mpx_engine* h) {
-    int blocks[4];
-    switch (h->arch - MPX_ARCH_DENSENET) {
-        case 121: blocks[0] = 6; blocks[1] = 12; blocks[2] = 24; blocks[3] = 16; break;
-        case 169: blocks[0] = 6; blocks[1] = 12; blocks[2] = 32; blocks[3] = 32; break;
-        case 201: blocks[0] = 6; blocks[1] = 12; blocks[2] = 48; blocks[3] = 32; break;
-        default: return MPX_E_ARG;      // (densenet161: growth rate 48 from 96 features, C = 96 + 48 k is not a multiple of the 32-wide K step)
-    }
-    constexpr int G = 32, MID = 128, R = 0, N = 1, T1 = 2, T2 = 3;
-    h->densenet = true;
-    h->act_elems_per_image = kActElemsPerImage;
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu;
-        L.is_fc = fc;
-        L.is_stem = (cin == 3);
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        // conv2 (3x3, 128 -> 32) runs the patch kernel.  default_tile's rule for cout <= 64 is the 64-row tile 1, judged on the ResNets'
-        // 64 -> 64 layers (where the patch kernel lost 10 %) and left as it is; here half of those rows are padding either way, and the
-        // patch kernel stages the 128-channel input once per 32-channel chunk instead of once per tap.  DenseNet-121 in the network, the
-        // 58 conv2 layers, ms per batch 2340 / 512: tile 1 56.1 / 13.8, tiles 0, 2, 4, 7 47.8 .. 48.7 / 11.0 .. 12.4, tile 6 30.2 / 7.5 --
-        // faster on every map (56x56 30.3 -> 16.6, 28x28 16.4 -> 8.4, 14x14 8.2 -> 4.3, 7x7 1.18 -> 0.90).  A default of THIS
-        // topology's layers (tile_default), not a rule of default_tile: no other network's layer can change tile.
-        if (k == 3 && cout == G && patch_eligible(L.d)) L.tile = L.tile_default = 6;
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
-    auto catnorm = [&](const std::string& name, int fresh, int g, int c, int ctot, int hw) {
-        NormLayer nl;
-        std::memset(&nl.d, 0, sizeof nl.d);
-        std::snprintf(nl.d.name, sizeof nl.d.name, "%s", name.c_str());
-        nl.d.channels = c;
-        nl.d.hw = hw;
-        h->norms.push_back(nl);
-        Op o{OP_CATNORM, (int)h->norms.size() - 1, fresh, N, R, hw, c, BUF_NONE};
-        o.g = g; o.ctot = ctot;
-        h->ops.push_back(o);
-    };
-    int c = add_conv("features.conv0", "features.norm0", 3, 64, 7, 2, 3, 224, 1, false);
-    conv_op(c, BUF_INPUT, 0);
-    h->ops.push_back(Op{OP_MAXPOOL, -1, 0, BUF_STEM, BUF_NONE, 112, 64, BUF_NONE});
-    int X = BUF_STEM, cin = 64, hcur = 56;
-    for (int b = 0; b < 4; ++b) {
-        const int ctot = cin + G * blocks[b];
-        if ((size_t)hcur * hcur * ctot > kActElemsPerImage) return MPX_E_INTERNAL;
-        const std::string bp = "features.denseblock" + std::to_string(b + 1) + ".denselayer";
-        catnorm(bp + "1.norm1", X, cin, cin, ctot, hcur);          // the block input becomes the head of the concatenation
-        for (int j = 1; j <= blocks[b]; ++j) {
-            const std::string p = bp + std::to_string(j) + ".";
-            c = add_conv(p + "conv1", p + "norm2", cin, MID, 1, 1, 0, hcur, 1, false);
-            conv_op(c, N, T1);
-            c = add_conv(p + "conv2", "", MID, G, 3, 1, 1, hcur, 0, false);
-            conv_op(c, T1, T2);
-            cin += G;
-            const std::string next = j < blocks[b] ? bp + std::to_string(j + 1) + ".norm1"
-                                                   : (b < 3 ? "features.transition" + std::to_string(b + 1) + ".norm" : std::string("features.norm5"));
-            catnorm(next, T2, G, cin, ctot, hcur);
-        }
-        if (b < 3) {
-            c = add_conv("features.transition" + std::to_string(b + 1) + ".conv", "", cin, cin / 2, 1, 1, 0, hcur, 0, false);
-            conv_op(c, N, T1);
-            cin /= 2;
-            h->ops.push_back(Op{OP_AVGPOOL2, -1, T1, T2, BUF_NONE, hcur, cin, BUF_NONE});
-            hcur /= 2;
-            X = T2;
-        }
-    }
-    h->feat = cin;
-    h->ops.push_back(Op{OP_AVGPOOL, -1, N, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
-    c = add_conv("classifier", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, true);
-    conv_op(c, BUF_POOL, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision MobileNetV2 (mobilenetv2.py, width 1.0): features.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN + ReLU6, 17 inverted-residual blocks
-// (t, c, n, s) = (1,16,1,1) (6,24,2,2) (6,32,3,2) (6,64,4,2) (6,96,3,1) (6,160,3,2) (6,320,1,1), features.18 = conv 320 -> 1280 1x1 + BN +
-// ReLU6, global average pool, classifier.1 = Linear(1280, 1000).  A block is 1x1 expand + BN + ReLU6 (absent when t = 1), depthwise 3x3 +
-// BN + ReLU6, 1x1 project + BN without activation; with stride 1 and cin == cout the block input is added, no ReLU behind the add.  No
-// conv has a bias.
-// ReLU6: the MFMA convs run their ReLU epilogue and the consumer clamps at 6 as it loads (mpx_dw.h) -- every such conv is read by a
-// depthwise layer (clamp_in) or by the clamped global pool (OP_AVGPOOL6).
-// Channels: 16, 24 and 144 are stored with a pitch of 32, 32 and 160 (cin_pad / cout_store as the small networks: zero weight columns,
-// zero scale and shift on the padded rows, so padded channels are exact zeros wherever they are read -- the next conv, the depthwise
-// layer, the residual add).  Those layers are eligible for the generic tiles only (eligible()); every generic tile runs a one-step K
-// loop (K = 32: the 1x1 layers on 16, 24 or 32 channels) as it is -- its prologue stages dead steps past the end of K and the last-step
-// branch runs the one fragment set -- so no tile is refused and K is not padded.
-// Buffers: three of 112 * 112 * 96 elements per image (features.2's expanded map): X the block input, T1 the expanded map and then --
-// dead after the depthwise layer -- the block output, T2 the depthwise output.
-int build_topology_mobilenet(mpx_engine* h) {
-    if (h->arch != MPX_ARCH_MOBILENET + 2) return MPX_E_ARG;
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kMobileActElemsPerImage;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu,
-                        int residual, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu; L.d.residual = residual;
-        L.is_fc = fc;
-        L.has_bias = fc;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
-        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
-        L.cout_store = fc ? cout : pitch_of(cout);
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
-    auto add_dw = [&](const std::string& name, const std::string& bn, int c, int stride, int hin, int in, int out) {
-        DwLayer D;
-        std::memset(&D.d, 0, sizeof D.d);
-        set_name(D.d.name, name);
-        set_name(D.d.bn_name, bn);
-        D.d.channels = c; D.d.pitch = pitch_of(c); D.d.stride = stride; D.d.hin = hin;
-        D.d.clamp_in = 1;                   // every depthwise layer of this network reads an MFMA conv that torchvision follows with ReLU6
-        h->dws.push_back(D);
-        h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, in, out, BUF_NONE, hin, D.d.pitch, BUF_NONE});
-    };
-    int c = add_conv("features.0.0", "features.0.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
-    conv_op(c, BUF_INPUT, 0, BUF_NONE);
-    int X = 0, cin = 32, hcur = 112, idx = 1;
-    static const int cfg[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
-    for (const auto& row : cfg) {
-        for (int b = 0; b < row[2]; ++b, ++idx) {
-            const int t = row[0], cout = row[1], stride = b == 0 ? row[3] : 1, hidden = cin * t;
-            const bool use_res = stride == 1 && cin == cout;
-            const std::string p = "features." + std::to_string(idx) + ".conv.";
-            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
-            if ((size_t)hcur * hcur * pitch_of(hidden) > kMobileActElemsPerImage) return MPX_E_INTERNAL;
-            const int hout = (hcur - 1) / stride + 1;
-            if (t == 1) {
-                add_dw(p + "0.0", p + "0.1", hidden, stride, hcur, X, T2);
-                c = add_conv(p + "1", p + "2", hidden, cout, 1, 1, 0, hout, 0, use_res, false);
-            } else {
-                c = add_conv(p + "0.0", p + "0.1", cin, hidden, 1, 1, 0, hcur, 1, 0, false);
-                conv_op(c, X, T1, BUF_NONE);
-                add_dw(p + "1.0", p + "1.1", hidden, stride, hcur, T1, T2);
-                c = add_conv(p + "2", p + "3", hidden, cout, 1, 1, 0, hout, 0, use_res, false);
-            }
-            conv_op(c, T2, T1, use_res ? X : BUF_NONE);
-            X = T1;
-            cin = cout;
-            hcur = hout;
-        }
-    }
-    const int T = (X + 1) % 3;
-    c = add_conv("features.18.0", "features.18.1", cin, 1280, 1, 1, 0, hcur, 1, 0, false);
-    conv_op(c, X, T, BUF_NONE);
-    h->feat = 1280;
-    h->ops.push_back(Op{OP_AVGPOOL6, -1, T, BUF_POOL, BUF_NONE, hcur, 1280, BUF_NONE});
-    c = add_conv("classifier.1", "", 1280, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
-    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision SqueezeNet 1.1 (squeezenet.py, version "1_1"): features.0 = conv 3 -> 64 3x3 stride 2 WITHOUT padding (224 -> 111) + ReLU, eight
-// Fire modules features.N = Fire(cin, s, e, e) for (N, cin, s, e) = (3,64,16,64) (4,128,16,64) (6,128,32,128) (7,256,32,128) (9,256,48,192)
-// (10,384,48,192) (11,384,64,256) (12,512,64,256) with a MaxPool2d(3, 2, ceil_mode=True) in front of features.3, .6 and .9, then
-// classifier.1 = conv 512 -> 1000 1x1 + ReLU on the 13x13 map and a global average pool whose output is the logits (Dropout is the identity
-// in eval).  A Fire module is squeeze 1x1 + ReLU, then expand1x1 and expand3x3 (pad 1) on the squeeze map, each + ReLU, concatenated along
-// the channels.  Every conv has a bias and there is no BatchNorm: the layers load as the plain VGG convs do (the bias as `beta`).
-// Op list, 31 launches: stem | pool 111 -> 55 | Fire 3, Fire 4 | pool 55 -> 27 | Fire 6, Fire 7 | pool 27 -> 13 | Fire 9 .. 12 | classifier.1 |
-// average pool -> logits | K4b; a Fire module is three OP_CONV.
-// The max pools: 111 - 3, 55 - 3 and 27 - 3 are even, so ceil((hin - 3) / 2) = floor((hin - 3) / 2) -- the ceil-mode output has the floor-mode
-// size and its last window ends on the last row / column of the map, none hangs over the edge.  OP_MAXPOOL3P0 (AlexNet's unpadded
-// floor-mode 3x3 stride-2 pool) therefore IS this pool; no new pool kernel.  (squeezenet1_0's 109 -> 54 -> 27 -> 13 has an odd hin - 3 at 54: not served.)
-// The concatenation: expand1x1 writes channels [0, e) and expand3x3 channels [e, 2e) of the same planes [B][h][h][2e] (y_pitch / y_offset:
-// the SLICE form of the generic kernel), so nothing is copied and no op joins them.
-// Channels: the squeeze widths 16 and 48 are stored with a pitch of 32 and 64 (cin_pad / cout_store as MobileNetV2: zero weight columns,
-// zero scale and shift on the padded rows, exact zeros in the padded channels), so K = 32 / 32 / 64 / 64 for the 1x1 expands and 288 / 288 /
-// 576 / 576 for the 3x3 ones.
-// Buffers: three of 111 * 111 * 64 elements per image: X the module input, S the squeeze map, Y the concatenation, which is the next X.
-int build_topology_squeezenet(mpx_engine* h) {
-    if (h->arch != MPX_ARCH_SQUEEZENET + 11) return MPX_E_ARG;
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kSqueezeActElemsPerImage;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    // slice: 0 = an ordinary layer, 1 / 2 = the first / second half of a concatenation of 2 * cout channels
-    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int pad, int hin, int slice, bool head) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = 1;
-        L.has_bias = true;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 0)
-        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
-        L.cout_store = (head || slice) ? cout : pitch_of(cout);
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        if (slice) {
-            L.y_pitch = 2 * cout;
-            L.y_offset = slice == 2 ? cout : 0;
-            // default_tile judges the descriptor alone and would hand 64 -> 256 the 256x256 or patch kernels, which know no output pitch:
-            // its rules restricted to the generic tiles (64-row tiles for cout <= 64, tile 0 for 3x3, tile 7 for the expanding 1x1 layers)
-            L.tile = L.tile_default = cout <= 64 ? (k >= 3 ? 1 : 4) : (k == 3 ? 0 : 7);
-        }
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
-    int c = add_conv("features.0", 3, 64, 3, 2, 0, MPX_IMG, 0, false);
-    conv_op(c, BUF_INPUT, 0);
-    int X = 0, cin = 64, hcur = h->convs[c].d.hout;
-    static const int fires[8][3] = {{3, 16, 64}, {4, 16, 64}, {6, 32, 128}, {7, 32, 128}, {9, 48, 192}, {10, 48, 192}, {11, 64, 256}, {12, 64, 256}};
-    for (const auto& f : fires) {
-        const int N = f[0], s = f[1], e = f[2];
-        if (N == 3 || N == 6 || N == 9) {       // features.2 / .5 / .8
-            if ((hcur - 3) % 2 != 0) return MPX_E_INTERNAL;     // ceil mode would differ from the floor-mode kernel
-            const int O = (X + 1) % 3;
-            h->ops.push_back(Op{OP_MAXPOOL3P0, -1, X, O, BUF_NONE, hcur, cin, BUF_NONE});
-            hcur = (hcur - 3) / 2 + 1;
-            X = O;
-        }
-        const int S = (X + 1) % 3, Y = (X + 2) % 3;
-        if ((size_t)hcur * hcur * 2 * e > kSqueezeActElemsPerImage || (size_t)hcur * hcur * pitch_of(s) > kSqueezeActElemsPerImage) return MPX_E_INTERNAL;
-        const std::string p = "features." + std::to_string(N) + ".";
-        c = add_conv(p + "squeeze", cin, s, 1, 1, 0, hcur, 0, false);
-        conv_op(c, X, S);
-        c = add_conv(p + "expand1x1", s, e, 1, 1, 0, hcur, 1, false);
-        conv_op(c, S, Y);
-        c = add_conv(p + "expand3x3", s, e, 3, 1, 1, hcur, 2, false);
-        conv_op(c, S, Y);
-        X = Y;
-        cin = 2 * e;
-    }
-    // classifier.1 is the last entry of the conv list but NOT the logit layer (is_fc): it writes split planes [B][13][13][1000] like any
-    // other layer, and the average pool behind it writes the fp32 logits
-    const int T = (X + 1) % 3;
-    if ((size_t)hcur * hcur * MPX_NUM_CLASSES > kSqueezeActElemsPerImage) return MPX_E_INTERNAL;
-    c = add_conv("classifier.1", cin, MPX_NUM_CLASSES, 1, 1, 0, hcur, 0, true);
-    conv_op(c, X, T);
-    h->feat = MPX_NUM_CLASSES;
-    h->ops.push_back(Op{OP_AVGLOGITS, -1, T, BUF_NONE, BUF_NONE, hcur, MPX_NUM_CLASSES, BUF_NONE});
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision GoogLeNet (googlenet.py, aux_logits off, eval mode): conv1 7x7/2 pad 3 (3 -> 64, 224 -> 112: the ResNet stem's shape, run as a
-// launch of its own -- the pool behind it is not the ResNets') | maxpool1 3/2 ceil 112 -> 56 | conv2 1x1 64 -> 64 | conv3 3x3 pad 1 64 -> 192 |
-// maxpool2 3/2 ceil 56 -> 28 | inception3a, 3b | maxpool3 3/2 ceil 28 -> 14 | inception4a .. 4e | maxpool4 2x2/2 ceil 14 -> 7 (exact: the VGG
-// pool) | inception5a, 5b | global average pool | fc 1024 -> 1000.  Every conv is BasicConv2d = Conv2d(bias=False) + BatchNorm2d(eps 0.001) + ReLU.
-// Inception(in, c1, r3, c3, r5, c5, pp) concatenates branch1 (1x1 in -> c1), branch2 (1x1 in -> r3, 3x3 pad 1 r3 -> c3), branch3 (1x1 in -> r5,
-// 3x3 pad 1 r5 -> c5: torchvision's 3x3 where the paper has 5x5) and branch4 (MaxPool2d(3, 1, 1, ceil_mode=True), 1x1 in -> pp).
-// Op list, 73 launches: 57 OP_CONV (the stem, conv2, conv3, six per module, fc), 12 OP_MAXPOOL3C (mpx_pool3c.h: the three stride-2 ceil-mode
-// pools, whose last window hangs over the edge -- 112 - 3, 56 - 3 and 28 - 3 are odd --, and the nine stride-1 pad-1 pools), OP_MAXPOOL2,
-// OP_AVGPOOL, OP_HEAD.
-// THE CONCATENATION IS THE BRANCHES' EPILOGUE: branch1, branch2.1, branch3.1 and branch4.1 write channels [0, c1), [c1, c1 + c3), [c1 + c3,
-// c1 + c3 + c5) and [c1 + c3 + c5, out) of one buffer (y_pitch / y_offset: the SLICE form of the generic kernel); nothing is copied.  Every
-// offset is a multiple of 8.
-// Channels: the reduce widths 16, 24, 48, 112 and 144 are stored with pitch 32, 32, 64, 128 and 160 (zero weight columns in the 3x3 conv that
-// reads them, zero scale and shift on the padded rows: exact zeros).  inception4d's concatenation is 528 wide and feeds K = 528, not a
-// multiple of the 32-wide K step: it is stored with pitch 544, and its last slice (branch4.1, 64 channels at offset 464) stores 80 -- rows
-// 64 .. 79 of its weights, scale and shift are zero, so channels 528 .. 543 are WRITTEN as exact zeros by every forward.  inception4e's three
-// 1x1 convs on the module input (cin_pad 544), its pool (pitch 544: the max of zeros is zero) and branch4.1 behind the pool (cin_pad 544)
-// all read that pitch.
-// Buffers: three of 112 * 112 * 64 elements per image (the stem's output; conv3's 56 * 56 * 192 and every concatenation are smaller): X the
-// module input, T what one branch keeps between its two launches (the reduce map, the pooled input), Y the concatenation, the next X.
-int build_topology_googlenet(mpx_engine* h) {
-    if (h->arch != MPX_ARCH_GOOGLENET) return MPX_E_ARG;
-    h->googlenet = true;
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kActElemsPerImage;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    // y_pitch = 0: an ordinary layer (output pitch = cout rounded up to 32); else a slice of y_pitch-wide planes that stores `store` channels
-    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int pad, int hin, int y_pitch, int y_offset, int store) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name + ".conv");
-        set_name(L.d.bn_name, name + ".bn");
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = 1;
-        L.is_stem = (cin == 3);
-        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
-        L.cout_store = y_pitch ? store : pitch_of(cout);
-        L.d.k_packed = L.is_stem ? kStemK * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(std::max(cout, L.cout_store), 128);
-        L.tile = default_tile(L.d);
-        if (y_pitch) {
-            L.y_pitch = y_pitch;
-            L.y_offset = y_offset;
-            // default_tile judges the descriptor alone and may hand out kernels that know no output pitch: its rules restricted to the generic
-            // tiles, as build_topology_squeezenet (64-row tiles for cout <= 64, tile 0 for 3x3, tile 7 for the expanding 1x1 layers, tile 2 for
-            // the reducing ones)
-            L.tile = L.tile_default = cout <= 64 ? (k >= 3 ? 1 : 4) : (k == 3 ? 0 : (cout > cin ? 7 : 2));
-        }
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
-    // a clipped 3x3 max pool over planes of `pitch` channels per pixel; returns the output side
-    auto pool_op = [&](int in, int out, int hin, int stride, int pad, int pitch) {
-        h->pools3c.push_back(ClipPool{hin, stride, pad, pitch});
-        h->ops.push_back(Op{OP_MAXPOOL3C, (int)h->pools3c.size() - 1, in, out, BUF_NONE, hin, pitch, BUF_NONE});
-        return pool3c_out_side(hin, stride, pad);
-    };
-    int c = add_conv("conv1", 3, 64, 7, 2, 3, MPX_IMG, 0, 0, 0);
-    conv_op(c, BUF_INPUT, 0);
-    int hcur = pool_op(0, 1, 112, 2, 0, 64);                    // maxpool1: 112 -> 56
-    c = add_conv("conv2", 64, 64, 1, 1, 0, hcur, 0, 0, 0);
-    conv_op(c, 1, 2);
-    c = add_conv("conv3", 64, 192, 3, 1, 1, hcur, 0, 0, 0);
-    conv_op(c, 2, 0);
-    int X = 1;
-    hcur = pool_op(0, X, hcur, 2, 0, 192);                      // maxpool2: 56 -> 28
-    if (hcur != 28) return MPX_E_INTERNAL;
-    struct Mod { const char* name; int cin, c1, r3, c3, r5, c5, pp; };
-    static const Mod mods[9] = {{"inception3a", 192, 64, 96, 128, 16, 32, 32},   {"inception3b", 256, 128, 128, 192, 32, 96, 64},
-                                {"inception4a", 480, 192, 96, 208, 16, 48, 64},  {"inception4b", 512, 160, 112, 224, 24, 64, 64},
-                                {"inception4c", 512, 128, 128, 256, 24, 64, 64}, {"inception4d", 512, 112, 144, 288, 32, 64, 64},
-                                {"inception4e", 528, 256, 160, 320, 32, 128, 128}, {"inception5a", 832, 256, 160, 320, 32, 128, 128},
-                                {"inception5b", 832, 384, 192, 384, 48, 128, 128}};
-    int cin = 192;
-    for (int m = 0; m < 9; ++m) {
-        const Mod& M = mods[m];
-        if (M.cin != cin) return MPX_E_INTERNAL;
-        if (m == 2 || m == 7) {
-            const int O = (X + 1) % 3;
-            if (m == 2) {
-                hcur = pool_op(X, O, hcur, 2, 0, pitch_of(cin));    // maxpool3: 28 -> 14
-            } else {
-                h->ops.push_back(Op{OP_MAXPOOL2, -1, X, O, BUF_NONE, hcur, pitch_of(cin), BUF_NONE});   // maxpool4: 14 -> 7, every window inside the map
-                hcur /= 2;
-            }
-            X = O;
-        }
-        const int T = (X + 1) % 3, Y = (X + 2) % 3;
-        const int out = M.c1 + M.c3 + M.c5 + M.pp, P = pitch_of(out), Pin = pitch_of(cin);
-        if ((size_t)hcur * hcur * std::max(P, Pin) > kActElemsPerImage || (M.c1 | M.c3 | M.c5 | M.pp) & 7) return MPX_E_INTERNAL;
-        const std::string p = std::string(M.name) + ".";
-        c = add_conv(p + "branch1", cin, M.c1, 1, 1, 0, hcur, P, 0, M.c1);
-        conv_op(c, X, Y);
-        c = add_conv(p + "branch2.0", cin, M.r3, 1, 1, 0, hcur, 0, 0, 0);
-        conv_op(c, X, T);
-        c = add_conv(p + "branch2.1", M.r3, M.c3, 3, 1, 1, hcur, P, M.c1, M.c3);
-        conv_op(c, T, Y);
-        c = add_conv(p + "branch3.0", cin, M.r5, 1, 1, 0, hcur, 0, 0, 0);
-        conv_op(c, X, T);
-        c = add_conv(p + "branch3.1", M.r5, M.c5, 3, 1, 1, hcur, P, M.c1 + M.c3, M.c5);
-        conv_op(c, T, Y);
-        if (pool_op(X, T, hcur, 1, 1, Pin) != hcur) return MPX_E_INTERNAL;
-        // the last slice also writes the concatenation's pad channels [out, P), as zeros (inception4d: 64 -> 80)
-        c = add_conv(p + "branch4.1", cin, M.pp, 1, 1, 0, hcur, P, M.c1 + M.c3 + M.c5, M.pp + P - out);
-        conv_op(c, T, Y);
-        X = Y;
-        cin = out;
-    }
-    if (cin != 1024 || hcur != 7) return MPX_E_INTERNAL;
-    h->feat = cin;
-    h->ops.push_back(Op{OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hcur, cin, BUF_NONE});
-    {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, "fc");
-        L.d.cin = cin; L.d.cout = MPX_NUM_CLASSES; L.d.ksize = 1; L.d.stride = 1; L.d.hin = 1; L.d.hout = 1;
-        L.is_fc = true;
-        L.has_bias = true;
-        L.cin_pad = cin;
-        L.cout_store = MPX_NUM_CLASSES;
-        L.d.k_packed = cin;
-        L.d.cout_pad = (int)round_up(MPX_NUM_CLASSES, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        conv_op((int)h->convs.size() - 1, BUF_POOL, BUF_NONE);
-    }
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision ShuffleNetV2 (shufflenetv2.py; x0_5 / x1_0 / x1_5 / x2_0): conv1 = Conv2d(3, 24, 3, stride 2, pad 1) + BN + ReLU (224 -> 112) |
-// MaxPool2d(3, 2, 1) (112 -> 56) | stage2, stage3, stage4 of 4, 8, 4 InvertedResidual blocks on 28x28, 14x14, 7x7 maps (block 0 of a stage has
-// stride 2) | conv5 = 1x1 conv to 1024 (2048 for x2_0) + BN + ReLU | mean over the 7x7 map | fc.  No conv has a bias.  With bf = oup / 2:
-//   stride 1: x1, x2 = x[:, :bf], x[:, bf:];  out = cat(x1, branch2(x2))
-//   stride 2: out = cat(branch1(x), branch2(x))
-//   branch2 = 1x1 conv (bf -> bf on x2; stride 2: inp -> bf on x) + BN + ReLU, depthwise 3x3 (the block's stride) + BN, 1x1 conv bf -> bf + BN + ReLU
-//   branch1 = depthwise 3x3 stride 2 (groups = inp) + BN, 1x1 conv inp -> bf + BN + ReLU
-//   then channel_shuffle(out, 2): out'[2i] = out[i], out'[2i + 1] = out[bf + i].
-// Stage maps live in the TWO-HALF layout (mpx_shuffle.h): pitch 2 hp, hp = bf rounded up to 32, the second half at hp, exact zeros on the
-// pads.  A stride-1 block's branch2.0 reads the second half IN PLACE (ConvLayer::x_pitch / x_offset: the generic kernel's pix_stride is not
-// its K per tap), the shuffle reads the first half in place; whoever reads a whole stage map -- the next stage's branch1.0 (depthwise),
-// branch1.2, branch2.0 and conv5 -- has its weights packed at the physical channel positions (in_bf / in_hp).  conv1 and the max pool keep
-// the plain layout, 24 channels at pitch 32.  The depthwise layers have no activation (DwLayer::linear: dwconv3x3_bn_kernel).
-// Op list, 76 launches: conv1 | OP_MAXPOOL | 13 stride-1 blocks of 4 (branch2.0, branch2.3, branch2.5, shuffle) | 3 stride-2 blocks of 6
-// (branch1.0, branch1.2, branch2.0, branch2.3, branch2.5, shuffle) | conv5 | OP_AVGPOOL | fc | OP_HEAD.  38 conv entries, 19 depthwise, 16 shuffles.
-// Buffers: three of 112 * 112 * 32 elements per image.  Stride 1: X the block input, T1 branch2.0's output and then branch2.5's, T2 the
-// depthwise output and then the shuffled map, the next X.  Stride 2: branch1.0 X -> T1, branch1.2 T1 -> the first half of T2 (SLICE form),
-// branch2.0 X -> T1, branch2.3 T1 -> X (dead from here on), branch2.5 X -> the second half of T2, the shuffle T2 -> T1, the next X.
-int build_topology_shufflenet(mpx_engine* h) {
-    static const int widths[4][5] = {{24, 48, 96, 192, 1024}, {24, 116, 232, 464, 1024}, {24, 176, 352, 704, 1024}, {24, 244, 488, 976, 2048}};
-    const int* w = nullptr;
-    switch (h->arch - MPX_ARCH_SHUFFLENET) {
-        case 5: w = widths[0]; break;
-        case 10: w = widths[1]; break;
-        case 15: w = widths[2]; break;
-        case 20: w = widths[3]; break;
-        default: return MPX_E_ARG;
-    }
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kShuffleActElemsPerImage;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    struct ConvOpt { int cin_pad, cout_store, in_bf, in_hp, x_pitch, x_offset, y_pitch, y_offset; };
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, const ConvOpt& o) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = 1;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
-        L.cin_pad = L.is_stem ? cin : o.cin_pad;
-        L.cout_store = o.cout_store;
-        L.in_bf = o.in_bf; L.in_hp = o.in_hp;
-        L.x_pitch = o.x_pitch; L.x_offset = o.x_offset;
-        L.y_pitch = o.y_pitch; L.y_offset = o.y_offset;
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(std::max(cout, L.cout_store), 128);
-        L.tile = default_tile(L.d);
-        // default_tile judges the descriptor alone; a layer that reads or writes a channel slice, or whose planes are wider than its channels,
-        // runs the generic tiles only: its rules restricted to them, as build_topology_googlenet (all such layers here are 1x1)
-        if (!L.is_stem && (L.x_pitch || L.y_pitch || L.cin_pad != cin))
-            L.tile = L.tile_default = cout <= 64 ? 4 : (cout > cin ? 7 : 2);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out) { h->ops.push_back(Op{OP_CONV, c, in, out, BUF_NONE, 0, 0, BUF_NONE}); };
-    auto add_dw = [&](const std::string& name, const std::string& bn, int c, int pitch, int in_bf, int in_hp, int stride, int hin, int in, int out) {
-        DwLayer D;
-        std::memset(&D.d, 0, sizeof D.d);
-        set_name(D.d.name, name);
-        set_name(D.d.bn_name, bn);
-        D.d.channels = c; D.d.pitch = pitch; D.d.stride = stride; D.d.hin = hin;
-        D.d.clamp_in = 0;
-        D.linear = true;
-        D.in_bf = in_bf; D.in_hp = in_hp;
-        h->dws.push_back(D);
-        h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, in, out, BUF_NONE, hin, pitch, BUF_NONE});
-    };
-    auto shuffle_op = [&](int a, int b, int out, int side, int bf, int hp, int a_pitch, int b_pitch, int b_offset) {
-        h->shuffles.push_back(ShuffleOp{side, bf, hp, a_pitch, b_pitch, b_offset});
-        h->ops.push_back(Op{OP_SHUFFLE, (int)h->shuffles.size() - 1, a, out, b, side, 2 * hp, BUF_NONE});
-    };
-    auto fits = [&](int side, int pitch) { return (size_t)side * side * pitch <= kShuffleActElemsPerImage; };
-    int c = add_conv("conv1.0", "conv1.1", 3, w[0], 3, 2, 1, MPX_IMG, ConvOpt{3, pitch_of(w[0]), 0, 0, 0, 0, 0, 0});
-    conv_op(c, BUF_INPUT, 0);
-    h->ops.push_back(Op{OP_MAXPOOL, -1, 0, 1, BUF_NONE, 112, pitch_of(w[0]), BUF_NONE});
-    int X = 1, hcur = 56;
-    int ibf = 0, ihp = 0, Pin = pitch_of(w[0]);     // layout of the current map: plain (ihp = 0) at pitch Pin, or two halves of ibf at ihp
-    static const int repeats[3] = {4, 8, 4};
-    for (int s = 0; s < 3; ++s) {
-        const int inp = w[s], oup = w[s + 1], bf = oup / 2, hp = pitch_of(bf);
-        if ((oup & 3) || (s > 0 && inp != 2 * ibf)) return MPX_E_INTERNAL;      // bf even: a shuffle unit starts on an even logical channel
-        for (int b = 0; b < repeats[s]; ++b) {
-            const std::string p = "stage" + std::to_string(s + 2) + "." + std::to_string(b) + ".";
-            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
-            if (b == 0) {
-                const int ho = (hcur - 1) / 2 + 1;
-                if (!fits(hcur, Pin) || !fits(hcur, hp) || !fits(ho, 2 * hp)) return MPX_E_INTERNAL;
-                add_dw(p + "branch1.0", p + "branch1.1", inp, Pin, ibf, ihp, 2, hcur, X, T1);
-                c = add_conv(p + "branch1.2", p + "branch1.3", inp, bf, 1, 1, 0, ho, ConvOpt{Pin, hp, ibf, ihp, 0, 0, 2 * hp, 0});
-                conv_op(c, T1, T2);
-                c = add_conv(p + "branch2.0", p + "branch2.1", inp, bf, 1, 1, 0, hcur, ConvOpt{Pin, hp, ibf, ihp, 0, 0, 0, 0});
-                conv_op(c, X, T1);
-                add_dw(p + "branch2.3", p + "branch2.4", bf, hp, 0, 0, 2, hcur, T1, X);       // X is dead: both branches have read it
-                c = add_conv(p + "branch2.5", p + "branch2.6", bf, bf, 1, 1, 0, ho, ConvOpt{hp, hp, 0, 0, 0, 0, 2 * hp, hp});
-                conv_op(c, X, T2);
-                shuffle_op(T2, T2, T1, ho, bf, hp, 2 * hp, 2 * hp, hp);
-                X = T1;
-                hcur = ho;
-                ibf = bf; ihp = hp; Pin = 2 * hp;
-            } else {
-                if (!fits(hcur, 2 * hp)) return MPX_E_INTERNAL;
-                c = add_conv(p + "branch2.0", p + "branch2.1", bf, bf, 1, 1, 0, hcur, ConvOpt{hp, hp, 0, 0, 2 * hp, hp, 0, 0});
-                conv_op(c, X, T1);
-                add_dw(p + "branch2.3", p + "branch2.4", bf, hp, 0, 0, 1, hcur, T1, T2);
-                c = add_conv(p + "branch2.5", p + "branch2.6", bf, bf, 1, 1, 0, hcur, ConvOpt{hp, hp, 0, 0, 0, 0, 0, 0});
-                conv_op(c, T2, T1);
-                shuffle_op(X, T1, T2, hcur, bf, hp, 2 * hp, hp, 0);
-                X = T2;
-            }
-        }
-    }
-    if (hcur != 7) return MPX_E_INTERNAL;
-    const int T = (X + 1) % 3;
-    c = add_conv("conv5.0", "conv5.1", w[3], w[4], 1, 1, 0, hcur, ConvOpt{Pin, w[4], ibf, ihp, 0, 0, 0, 0});
-    conv_op(c, X, T);
-    h->feat = w[4];
-    h->ops.push_back(Op{OP_AVGPOOL, -1, T, BUF_POOL, BUF_NONE, hcur, w[4], BUF_NONE});
-    {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, "fc");
-        L.d.cin = w[4]; L.d.cout = MPX_NUM_CLASSES; L.d.ksize = 1; L.d.stride = 1; L.d.hin = 1; L.d.hout = 1;
-        L.is_fc = true;
-        L.has_bias = true;
-        L.cin_pad = w[4];
-        L.cout_store = MPX_NUM_CLASSES;
-        L.d.k_packed = w[4];
-        L.d.cout_pad = (int)round_up(MPX_NUM_CLASSES, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        conv_op((int)h->convs.size() - 1, BUF_POOL, BUF_NONE);
-    }
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision EfficientNet-B0 (efficientnet.py, eval mode): features.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN + SiLU, 16 MBConv blocks
-// features.S.B over seven stages (t, k, s, in, out, n) = (1,3,1,32,16,1) (6,3,2,16,24,2) (6,5,2,24,40,2) (6,3,2,40,80,3) (6,5,1,80,112,3)
-// (6,5,2,112,192,4) (6,3,1,192,320,1), features.8 = conv 320 -> 1280 1x1 + BN + SiLU, global average pool, classifier.1 = Linear(1280, 1000).
-// A block with input cin and e = t * cin is `block` = 1x1 expand + BN + SiLU (absent when t = 1: every index below is one less), depthwise
-// k x k (pad (k - 1) / 2, the block's stride) + BN + SiLU, SqueezeExcitation(e, max(1, cin / 4)) -- gate = sigmoid(fc2(silu(fc1(avgpool(x))))),
-// fc1 / fc2 1x1 convs WITH bias --, 1x1 project + BN without activation; with stride 1 and cin == out the block input is added, nothing
-// behind the add.  No conv but the SE's has a bias.  StochasticDepth and Dropout are the identity in eval.  BatchNorm eps 1e-5.
-// SiLU: the MFMA convs run WITHOUT an activation (relu = 0) and the consumer takes silu(x) as it loads (ConvLayer::consumer_act; mpx_mbconv.h):
-// every such conv is read by exactly one depthwise layer (act_in) or by the SiLU global pool (OP_AVGPOOLSILU).
-// Channels 16, 24, 40, 80, 112, 144 and 240 are stored with a pitch of 32, 32, 64, 96, 128, 160 and 256 (zero weight columns, zero scale and
-// shift: exact zeros, as MobileNetV2); those layers run the generic tiles only, and default_tile's rules give every one of them a generic tile.
-// Op list, 84 launches: stem | 16 x (expand, depthwise, SE gate, SE scale in place, project) without 1.0's expand | features.8 |
-// OP_AVGPOOLSILU | classifier.1 | OP_HEAD.  34 conv entries, 16 depthwise, 16 SE layers.
-// Buffers: three of 112 * 112 * 96 elements per image (2.0's expanded map), as MobileNetV2: X the block input, T1 the expanded map and then
-// -- dead after the depthwise layer -- the block output, T2 the depthwise output, scaled in place.  The gates: f32[max_batch][1152].
-int build_topology_efficientnet(mpx_engine* h) {
-    if (h->arch != MPX_ARCH_EFFICIENTNET) return MPX_E_ARG;
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kEffActElemsPerImage;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int act,
-                        int residual, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = 0; L.d.residual = residual;
-        L.consumer_act = act;
-        L.is_fc = fc;
-        L.has_bias = fc;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
-        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
-        L.cout_store = fc ? cout : pitch_of(cout);
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
-    int c = add_conv("features.0.0", "features.0.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
-    conv_op(c, BUF_INPUT, 0, BUF_NONE);
-    int X = 0, cin = 32, hcur = 112;
-    static const int cfg[7][5] = {{1, 3, 1, 16, 1}, {6, 3, 2, 24, 2}, {6, 5, 2, 40, 2}, {6, 3, 2, 80, 3}, {6, 5, 1, 112, 3}, {6, 5, 2, 192, 4}, {6, 3, 1, 320, 1}};
-    for (int s = 0; s < 7; ++s) {
-        for (int b = 0; b < cfg[s][4]; ++b) {
-            const int t = cfg[s][0], k = cfg[s][1], stride = b == 0 ? cfg[s][2] : 1, cout = cfg[s][3], e = cin * t;
-            const bool use_res = stride == 1 && cin == cout;
-            const std::string p = "features." + std::to_string(s + 1) + "." + std::to_string(b) + ".block.";
-            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3, P = pitch_of(e);
-            if ((size_t)hcur * hcur * P > kEffActElemsPerImage) return MPX_E_INTERNAL;
-            const int hout = (hcur - 1) / stride + 1;
-            int j = 0, dw_in = X;
-            if (t != 1) {
-                c = add_conv(p + "0.0", p + "0.1", cin, e, 1, 1, 0, hcur, 1, 0, false);
-                conv_op(c, X, T1, BUF_NONE);
-                j = 1; dw_in = T1;
-            }
-            const std::string js = std::to_string(j), se = p + std::to_string(j + 1), pj = p + std::to_string(j + 2);
-            DwLayer D;
-            std::memset(&D.d, 0, sizeof D.d);
-            set_name(D.d.name, p + js + ".0");
-            set_name(D.d.bn_name, p + js + ".1");
-            D.d.channels = e; D.d.pitch = P; D.d.stride = stride; D.d.hin = hcur;
-            D.d.clamp_in = 0;
-            D.ksize = k; D.mb = true; D.act_in = 1; D.act_out = 1;      // every depthwise layer reads an MFMA conv that SiLU follows (1.0: the stem)
-            h->dws.push_back(D);
-            h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, dw_in, T2, BUF_NONE, hcur, P, BUF_NONE});
-            SeLayer E;
-            std::memset(&E.d, 0, sizeof E.d);
-            std::snprintf(E.d.name, sizeof E.d.name, "%s", se.c_str());
-            E.d.channels = e; E.d.pitch = P; E.d.q = std::max(1, cin / 4); E.d.hw = hout;
-            h->ses.push_back(E);
-            h->se_pitch_max = std::max(h->se_pitch_max, P);
-            h->ops.push_back(Op{OP_SEGATE, (int)h->ses.size() - 1, T2, BUF_NONE, BUF_NONE, hout, P, BUF_NONE});
-            h->ops.push_back(Op{OP_SESCALE, (int)h->ses.size() - 1, T2, T2, BUF_NONE, hout, P, BUF_NONE});
-            c = add_conv(pj + ".0", pj + ".1", e, cout, 1, 1, 0, hout, 0, use_res, false);
-            conv_op(c, T2, T1, use_res ? X : BUF_NONE);
-            X = T1;
-            cin = cout;
-            hcur = hout;
-        }
-    }
-    if (hcur != 7 || cin != 320) return MPX_E_INTERNAL;
-    const int T = (X + 1) % 3;
-    c = add_conv("features.8.0", "features.8.1", cin, 1280, 1, 1, 0, hcur, 1, 0, false);
-    conv_op(c, X, T, BUF_NONE);
-    h->feat = 1280;
-    h->ops.push_back(Op{OP_AVGPOOLSILU, -1, T, BUF_POOL, BUF_NONE, hcur, 1280, BUF_NONE});
-    c = add_conv("classifier.1", "", 1280, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
-    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision ConvNeXt-Tiny / -Small (convnext.py, eval mode): features.0 = Conv2d(3, 96, 4, stride 4, bias) + LayerNorm2d(96), four stages
-// features.1 / .3 / .5 / .7 of depths (3, 3, 9, 3) / (3, 3, 27, 3) CNBlocks of width 96, 192, 384, 768 on 56 / 28 / 14 / 7 maps, features.2 / .4 /
-// .6 = LayerNorm2d(C_prev) + Conv2d(C_prev, C, 2, stride 2, bias), global average pool, classifier.0 = LayerNorm2d(768), classifier.2 =
-// Linear(768, 1000).  A CNBlock is block.0 = depthwise 7x7 (pad 3, bias), block.2 = LayerNorm(C) over the channels of each pixel, block.3 =
-// Linear(C, 4C) + GELU, block.5 = Linear(4C, C), output = input + layer_scale * block(input); StochasticDepth is the identity in eval.  Every
-// LayerNorm has eps 1e-6.  Every channel count is a multiple of 32: no padded pitches.
-// GELU: block.3's consumer is block.5, an MFMA conv, so the activation is block.3's own epilogue (ConvLayer::epi_act, ConvGelu in mpx_conv.h);
-// such a layer runs the generic tiles only and defaults to tile 7, what default_tile gives the one stage (96 -> 384) whose shape no
-// persistent kernel takes.  block.5 is an ordinary layer with a residual operand and the layer scale as its "BatchNorm" gamma (bn_name =
-// "features.S.B.layer_scale": mean 0, var 1, eps 0, beta 0, the conv's own bias as conv_bias), on default_tile's choice.
-// The stem reads the padded NHWC4 staging 3 pixels into its border, one 8-pixel run per kernel row (4 of them real): k_packed = 4 * 32.
-// Op list, 65 / 119 launches: stem conv | its LayerNorm | per block (depthwise + LayerNorm, block.3, block.5) | per stage boundary
-// (LayerNorm, 2x2 conv) | pool + LayerNorm | classifier.2 | OP_HEAD.  41 / 77 conv entries, 18 / 36 depthwise layers, 5 LayerNorms.
-// Buffers: three of 56 * 56 * 384 elements per image (block.3's output in stage 0): X the block input and residual, T1 the LayerNorm
-// output and then -- dead after block.3 -- the block output, T2 the hidden map.
-int build_topology_convnext(mpx_engine* h) {
-    int depths[4] = {3, 3, 9, 3};
-    if (h->arch == MPX_ARCH_CONVNEXT + 2) depths[2] = 27;
-    else if (h->arch != MPX_ARCH_CONVNEXT + 1) return MPX_E_ARG;
-    static const int dims[4] = {96, 192, 384, 768};
-    h->n_act_bufs = 3;
-    h->act_elems_per_image = kCnextActElemsPerImage;
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int hin, int residual, int act, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = 0;
-        L.d.hin = hin; L.d.hout = (hin - k) / stride + 1;
-        L.d.relu = 0; L.d.residual = residual;
-        L.epi_act = act;
-        L.is_fc = fc;
-        L.has_bias = true;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 4, pad 0)
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        if (act) L.tile = L.tile_default = 7;
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto add_ln = [&](const std::string& name, int c, int hw) {
-        LnLayer N;
-        std::memset(&N.d, 0, sizeof N.d);
-        std::snprintf(N.d.name, sizeof N.d.name, "%s", name.c_str());
-        N.d.channels = c; N.d.hw = hw;
-        h->lnorms.push_back(N);
-        return (int)h->lnorms.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
-    int c = add_conv("features.0.0", "", 3, dims[0], 4, 4, MPX_IMG, 0, 0, false);
-    conv_op(c, BUF_INPUT, 0, BUF_NONE);
-    int hcur = 56;
-    h->ops.push_back(Op{OP_LNORM, add_ln("features.0.1", dims[0], hcur), 0, 1, BUF_NONE, hcur, dims[0], BUF_NONE});
-    int X = 1;
-    for (int s = 0; s < 4; ++s) {
-        const int C = dims[s];
-        if (s > 0) {
-            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3, cp = dims[s - 1];
-            const std::string p = "features." + std::to_string(2 * s) + ".";
-            h->ops.push_back(Op{OP_LNORM, add_ln(p + "0", cp, hcur), X, T1, BUF_NONE, hcur, cp, BUF_NONE});
-            c = add_conv(p + "1", "", cp, C, 2, 2, hcur, 0, 0, false);
-            conv_op(c, T1, T2, BUF_NONE);
-            X = T2;
-            hcur /= 2;
-        }
-        if ((size_t)hcur * hcur * 4 * C > kCnextActElemsPerImage) return MPX_E_INTERNAL;
-        for (int b = 0; b < depths[s]; ++b) {
-            const std::string p = "features." + std::to_string(2 * s + 1) + "." + std::to_string(b) + ".";
-            const int T1 = (X + 1) % 3, T2 = (X + 2) % 3;
-            DwLayer D;
-            std::memset(&D.d, 0, sizeof D.d);
-            set_name(D.d.name, p + "block.0");
-            set_name(D.d.bn_name, p + "block.2");
-            D.d.channels = C; D.d.pitch = C; D.d.stride = 1; D.d.hin = hcur; D.d.clamp_in = 0;
-            D.ksize = CN_DW_K; D.ln = true;
-            h->dws.push_back(D);
-            h->ops.push_back(Op{OP_DWCONV, (int)h->dws.size() - 1, X, T1, BUF_NONE, hcur, C, BUF_NONE});
-            c = add_conv(p + "block.3", "", C, 4 * C, 1, 1, hcur, 0, 1, false);
-            conv_op(c, T1, T2, BUF_NONE);
-            c = add_conv(p + "block.5", p + "layer_scale", 4 * C, C, 1, 1, hcur, 1, 0, false);
-            conv_op(c, T2, T1, X);          // T1 is dead after block.3
-            X = T1;
-        }
-    }
-    if (hcur != 7) return MPX_E_INTERNAL;
-    h->feat = dims[3];
-    h->ops.push_back(Op{OP_AVGPOOLLN, add_ln("classifier.0", dims[3], 1), X, BUF_POOL, BUF_NONE, hcur, dims[3], BUF_NONE});
-    c = add_conv("classifier.2", "", dims[3], MPX_NUM_CLASSES, 1, 1, 1, 0, 0, true);
-    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
-
-// torchvision vit_b_16 / vit_b_32 (vision_transformer.py, eval mode, dropout 0): conv_proj = Conv2d(3, 768, p, stride p, bias), the class
-// token in front of the 14 x 14 / 7 x 7 patch rows, + encoder.pos_embedding, 12 EncoderBlocks of width 768 (ln_1, MultiheadAttention with 12
-// heads of 64, residual, ln_2, Linear(768, 3072) + GELU, Linear(3072, 768), residual), encoder.ln, heads.head = Linear(768, 1000) on the
-// class-token row.  Every LayerNorm has eps 1e-6.  Every Linear is a 1x1 entry of the conv list whose rows are the B * T tokens: T = 197 /
-// 50 rows per image are no square map, so such a layer reports hin = hout = 0, mpx_conv_rows reports T and conv_params hands the kernels
-// hin = ho = T, win = wo = 1 (ConvLayer::rows).  default_tile sees the descriptor as always: in_proj runs tile 10, out_proj and mlp.3 (residual
-// operand) tile 9, mlp.0 (GELU in the epilogue, ConvGelu) the generic tile 7, heads.head tile 7, the stem tile 2.
-// The stem reads the padded NHWC4 staging 3 pixels into its border, one p-pixel x 4-channel run per kernel row: k_per_tap = 4 p (64: AlexNet's
-// two-step form; 128: four steps), k_packed = p * 4 p.  Rows and columns reach staging index 3 + 14 * 16 - 1 = 3 + 7 * 32 - 1 = 226 < 230.
-// Descriptor names drop the leading "encoder.layers." (name[48] cannot hold "encoder.layers.encoder_layer_11.self_attention.out_proj"); the
-// loader puts it back.  A bias-only layer has no bn_name: scale = 2^-e, shift = bias, what gamma 1, beta 0, mean 0, var 1, eps 0 pack to.
-// Op list, 2 + 7 * 12 + 3 = 89 launches: conv_proj | token assembly | per layer (ln_1, in_proj, attention, out_proj + residual, ln_2, mlp.0 +
-// GELU, mlp.3 + residual) | encoder.ln on the class rows | heads.head | OP_HEAD.  50 conv entries, 25 LayerNorms, 12 attention launches.
-// Buffers, each of its own size: 0 = X [T][768] the residual stream, 1 = T1 [T][768] the patch planes, then a LayerNorm's output and the
-// attention's, 2 = QKV [T][2304] in_proj's output and then -- dead behind the attention -- out_proj's, 3 = H [T][3072] the hidden rows.
-int build_topology_vit(mpx_engine* h) {
-    const int patch = h->arch - MPX_ARCH_VIT;
-    if (patch != 16 && patch != 32) return MPX_E_ARG;
-    const int side = MPX_IMG / patch, T = side * side + 1, D = kVitWidth;
-    h->vit = true;
-    h->vit_T = T; h->vit_D = D;
-    h->n_act_bufs = 4;
-    h->act_elems_buf[0] = (size_t)T * D; h->act_elems_buf[1] = (size_t)T * D;
-    h->act_elems_buf[2] = (size_t)T * 3 * D; h->act_elems_buf[3] = (size_t)T * kVitMlp;
-    h->act_elems_per_image = h->act_elems_buf[3];
-    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int rows, int residual, int act, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = k; L.d.pad = 0;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one p-pixel x 4-channel run per kernel row (stride p, pad 0)
-        L.rows = (L.is_stem || fc) ? 0 : rows;
-        L.d.hin = L.is_stem ? MPX_IMG : (fc ? 1 : 0);
-        L.d.hout = L.is_stem ? side : (fc ? 1 : 0);
-        L.d.relu = 0; L.d.residual = residual;
-        L.epi_act = act;
-        L.is_fc = fc;
-        L.has_bias = true;
-        L.cin_pad = cin;
-        L.cout_store = cout;
-        L.d.k_packed = L.is_stem ? k * 4 * k : cin;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        if (act) L.tile = L.tile_default = 7;
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto add_ln = [&](const std::string& name) {
-        LnLayer N;
-        std::memset(&N.d, 0, sizeof N.d);
-        std::snprintf(N.d.name, sizeof N.d.name, "%s", name.c_str());
-        N.d.channels = D; N.d.hw = 0;
-        h->lnorms.push_back(N);
-        return (int)h->lnorms.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
-    const int X = 0, T1 = 1, QKV = 2, H = 3;
-    conv_op(add_conv("conv_proj", 3, D, patch, 0, 0, 0, false), BUF_INPUT, T1, BUF_NONE);
-    h->ops.push_back(Op{OP_TOKENS, -1, T1, X, BUF_NONE, T, D, BUF_NONE});
-    for (int l = 0; l < kVitLayers; ++l) {
-        const std::string p = "encoder_layer_" + std::to_string(l) + ".";
-        h->ops.push_back(Op{OP_LNORM, add_ln(p + "ln_1"), X, T1, BUF_NONE, T, D, BUF_NONE});
-        conv_op(add_conv(p + "self_attention.in_proj", D, 3 * D, 1, T, 0, 0, false), T1, QKV, BUF_NONE);
-        AttnLayer A;
-        std::memset(&A.d, 0, sizeof A.d);
-        set_name(A.d.name, p + "self_attention");
-        A.d.tokens = T; A.d.heads = kVitHeads; A.d.head_dim = AT_HD;
-        h->attns.push_back(A);
-        h->ops.push_back(Op{OP_ATTN, (int)h->attns.size() - 1, QKV, T1, BUF_NONE, T, D, BUF_NONE});
-        conv_op(add_conv(p + "self_attention.out_proj", D, D, 1, T, 1, 0, false), T1, QKV, X);      // QKV is dead behind the attention
-        h->ops.push_back(Op{OP_LNORM, add_ln(p + "ln_2"), QKV, T1, BUF_NONE, T, D, BUF_NONE});
-        conv_op(add_conv(p + "mlp.0", D, kVitMlp, 1, T, 0, 1, false), T1, H, BUF_NONE);
-        conv_op(add_conv(p + "mlp.3", kVitMlp, D, 1, T, 1, 0, false), H, X, QKV);
-    }
-    if (kVitHeads * AT_HD != D) return MPX_E_INTERNAL;
-    h->feat = D;
-    h->ops.push_back(Op{OP_LNORMROWS, add_ln("encoder.ln"), X, BUF_POOL, BUF_NONE, T, D, BUF_NONE});
-    conv_op(add_conv("heads.head", D, MPX_NUM_CLASSES, 1, 0, 0, 0, true), BUF_POOL, BUF_NONE, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
 
 uint16_t half_bits(half_t v) {
     uint16_t u;
@@ -2120,144 +790,11 @@ int default_tile(const mpx_conv_desc& d) {
     return 2;
 }
 
-// torchvision RegNetX (regnet.py; BlockParams.from_init_params quantises the widths to 8 and makes each divisible by min(group width, width)):
-//   name             id     stage widths          depths        group width   groups per stage
-//   regnet_x_400mf   14004  32, 64, 160, 400      1, 2, 7, 12   16            2, 4, 10, 25
-//   regnet_x_800mf   14008  64, 128, 288, 672     1, 3, 7, 5    16            4, 8, 18, 42
-//   regnet_x_1_6gf   14016  72, 168, 408, 912     2, 4, 10, 2   24            3, 7, 17, 38
-//   regnet_x_3_2gf   14032  96, 192, 432, 1008    2, 6, 15, 2   48            2, 4, 9, 21
-//   regnet_x_8gf     14080  80, 240, 720, 1920    2, 5, 15, 1   120           1 (80 channels: a dense 3x3), 2, 6, 16
-// stem.0 = conv 3 -> 32 3x3 stride 2 pad 1 + BN (stem.1) + ReLU, no max pool (MobileNetV2's features.0.0: the row-run form on the padded NHWC4
-// staging).  trunk_output.block{s}.block{s}-{j} is a bottleneck of ratio 1: f.a 1x1 w_in -> w + BN + ReLU at the input resolution, f.b 3x3
-// w -> w with w / gw groups (stride 2 in block 0 of every stage) + BN + ReLU, f.c 1x1 w -> w + BN, out = ReLU(shortcut + f.c); the shortcut is
-// proj (1x1 stride 2 + BN) in block 0 of every stage and the identity elsewhere.  Global average pool, fc.  No conv has a bias.
-// Channels: every plane has a pitch of round_up(width, 32) (cin_pad / cout_store as MobileNetV2: zero weight columns, zero scale and shift
-// on the padded rows); the grouped kernel writes its pad channels as +0 itself (mpx_gconvw.h).  Such layers run the generic tiles (eligible()).
-// Launches: one per conv -- proj is a launch of its own in every stage (the K-concatenated dual form reads planes whose pitch is their cin).
-// Buffers: four, sized by the largest map of the network (f.a of block 0 runs at the previous stage's resolution): X the block input, T1
-// f.a's output and then -- dead after f.b -- the block output, T2 f.b's output, T3 proj's output.
-//
-// torchvision RegNetY 800MF .. 8GF: the same trunk with f.se = SqueezeExcitation(w, q) between f.b and f.c in EVERY block, q = round(0.25 w_in)
-// of the BLOCK's input width (32 for block1-0, the previous stage's width for the other stage openers): fc1 / fc2 are 1x1 convs with bias, ReLU
-// behind fc1, sigmoid behind fc2, f.b's output times the gate.  Two launches per block on T2, in place (se_gate_kernel<true>, se_scale_kernel).
-//   name             id     stage widths          depths        group width   groups per stage
-//   regnet_y_800mf   15008  64, 144, 320, 784     1, 3, 8, 2    16            4, 9, 20, 49
-//   regnet_y_1_6gf   15016  48, 120, 336, 888     2, 6, 17, 2   24            2, 5, 14, 37
-//   regnet_y_3_2gf   15032  72, 216, 576, 1512    2, 5, 13, 1   24            3, 9, 24, 63
-//   regnet_y_8gf     15080  224, 448, 896, 2016   2, 4, 10, 1   56            4, 8, 16, 36
-// (regnet_y_400mf has a group width of 8, below the grouped kernel's 16; regnet_y_16gf / _32gf have 112 / 232: 7 / 15 row fragments, no whole
-// number of 4-fragment chunks.  Not served.)
-int build_topology_regnet(mpx_engine* h) {
-    struct Row { int id; int widths[4]; int depths[4]; int gw; };
-    static const Row rows[] = {
-        {MPX_ARCH_REGNET + 4, {32, 64, 160, 400}, {1, 2, 7, 12}, 16},
-        {MPX_ARCH_REGNET + 8, {64, 128, 288, 672}, {1, 3, 7, 5}, 16},
-        {MPX_ARCH_REGNET + 16, {72, 168, 408, 912}, {2, 4, 10, 2}, 24},
-        {MPX_ARCH_REGNET + 32, {96, 192, 432, 1008}, {2, 6, 15, 2}, 48},
-        {MPX_ARCH_REGNET + 80, {80, 240, 720, 1920}, {2, 5, 15, 1}, 120},
-        {MPX_ARCH_REGNET_Y + 8, {64, 144, 320, 784}, {1, 3, 8, 2}, 16},
-        {MPX_ARCH_REGNET_Y + 16, {48, 120, 336, 888}, {2, 6, 17, 2}, 24},
-        {MPX_ARCH_REGNET_Y + 32, {72, 216, 576, 1512}, {2, 5, 13, 1}, 24},
-        {MPX_ARCH_REGNET_Y + 80, {224, 448, 896, 2016}, {2, 4, 10, 1}, 56},
-    };
-    const Row* R = nullptr;
-    for (const Row& r : rows)
-        if (r.id == h->arch) R = &r;
-    if (!R) return MPX_E_ARG;
-    h->regnet_y = h->arch >= MPX_ARCH_REGNET_Y;
-    auto pitch_of = [](int c) { return (int)round_up((size_t)c, kSmallCPad); };
-    size_t act_max = 0;
-    auto add_conv = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int hin, int relu,
-                        int residual, bool fc) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = cin; L.d.cout = cout; L.d.ksize = k; L.d.stride = stride; L.d.pad = pad;
-        L.d.hin = hin; L.d.hout = (hin + 2 * pad - k) / stride + 1;
-        L.d.relu = relu; L.d.residual = residual;
-        L.is_fc = fc;
-        L.has_bias = fc;
-        L.is_stem = (cin == 3);             // reads the padded NHWC4 staging, one 8-pixel x 4-channel run per kernel row (stride 2, pad 1)
-        L.cin_pad = L.is_stem ? cin : pitch_of(cin);
-        L.cout_store = fc ? cout : pitch_of(cout);
-        L.d.k_packed = L.is_stem ? k * 32 : k * k * L.cin_pad;
-        L.d.cout_pad = (int)round_up(cout, 128);
-        L.tile = default_tile(L.d);
-        const TileRow* r = find_tile(L.tile);
-        if (!r || !eligible(*r, L)) L.tile = L.tile_default = 2;       // (no layer of the five networks: default_tile hands them generic tiles only)
-        if (!fc) act_max = std::max(act_max, (size_t)L.d.hout * L.d.hout * L.cout_store);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    // f.b: w -> w in w / gw groups of gw channels (mpx_gconvw.h)
-    auto add_gconvw = [&](const std::string& name, const std::string& bn, int w, int gw, int stride, int hin) {
-        ConvLayer L;
-        std::memset(&L.d, 0, sizeof L.d);
-        set_name(L.d.name, name);
-        set_name(L.d.bn_name, bn);
-        L.d.cin = w; L.d.cout = w; L.d.ksize = 3; L.d.stride = stride; L.d.pad = 1;
-        L.d.hin = hin; L.d.hout = (hin + 2 - 3) / stride + 1;
-        L.d.relu = 1; L.d.residual = 0;
-        L.cin_pad = pitch_of(w);
-        L.cout_store = pitch_of(w);
-        L.groups = w / gw;
-        L.gw = true;
-        L.d.k_packed = gconvw_kp(gw);
-        L.d.cout_pad = L.groups * gconvw_rf(gw) * 16;
-        L.tile = L.tile_default = kGconvwTile;
-        act_max = std::max(act_max, (size_t)L.d.hout * L.d.hout * L.cout_store);
-        h->convs.push_back(L);
-        return (int)h->convs.size() - 1;
-    };
-    auto conv_op = [&](int c, int in, int out, int res) { h->ops.push_back(Op{OP_CONV, c, in, out, res, 0, 0, BUF_NONE}); };
-    int c = add_conv("stem.0", "stem.1", 3, 32, 3, 2, 1, MPX_IMG, 1, 0, false);
-    conv_op(c, BUF_INPUT, 0, BUF_NONE);
-    int X = 0, cin = 32, hcur = 112;
-    for (int s = 0; s < 4; ++s) {
-        const int w = R->widths[s], gw = std::min(R->gw, w);
-        if (w % gw || w % 8) return MPX_E_INTERNAL;
-        for (int j = 0; j < R->depths[s]; ++j) {
-            const int stride = j == 0 ? 2 : 1, hout = (hcur - 1) / stride + 1;
-            const std::string p = "trunk_output.block" + std::to_string(s + 1) + ".block" + std::to_string(s + 1) + "-" + std::to_string(j) + ".";
-            const int T1 = (X + 1) % 4, T2 = (X + 2) % 4, T3 = (X + 3) % 4;
-            int res = X;
-            if (j == 0) {
-                c = add_conv(p + "proj.0", p + "proj.1", cin, w, 1, 2, 0, hcur, 0, 0, false);
-                conv_op(c, X, T3, BUF_NONE);
-                res = T3;
-            }
-            c = add_conv(p + "f.a.0", p + "f.a.1", cin, w, 1, 1, 0, hcur, 1, 0, false);
-            conv_op(c, X, T1, BUF_NONE);
-            c = w / gw > 1 ? add_gconvw(p + "f.b.0", p + "f.b.1", w, gw, stride, hcur) : add_conv(p + "f.b.0", p + "f.b.1", w, w, 3, stride, 1, hcur, 1, 0, false);
-            conv_op(c, T1, T2, BUF_NONE);
-            if (h->regnet_y) {      // f.se on f.b's output, in place
-                SeLayer E;
-                std::memset(&E.d, 0, sizeof E.d);
-                std::snprintf(E.d.name, sizeof E.d.name, "%sf.se", p.c_str());
-                E.d.channels = w; E.d.pitch = pitch_of(w); E.d.q = (int)std::lround(0.25 * cin); E.d.hw = hout;
-                E.relu = true;
-                h->ses.push_back(E);
-                h->se_pitch_max = std::max(h->se_pitch_max, E.d.pitch);
-                h->ops.push_back(Op{OP_SEGATE, (int)h->ses.size() - 1, T2, BUF_NONE, BUF_NONE, hout, E.d.pitch, BUF_NONE});
-                h->ops.push_back(Op{OP_SESCALE, (int)h->ses.size() - 1, T2, T2, BUF_NONE, hout, E.d.pitch, BUF_NONE});
-            }
-            c = add_conv(p + "f.c.0", p + "f.c.1", w, w, 1, 1, 0, hout, 1, 1, false);
-            conv_op(c, T2, T1, res);        // T1 is dead after f.b
-            X = T1;
-            cin = w;
-            hcur = hout;
-        }
-    }
-    h->n_act_bufs = 4;
-    h->act_elems_per_image = act_max;
-    h->feat = cin;
-    h->ops.push_back(Op{OP_AVGPOOL, -1, X, BUF_POOL, BUF_NONE, hcur, pitch_of(cin), BUF_NONE});
-    c = add_conv("fc", "", cin, MPX_NUM_CLASSES, 1, 1, 0, 1, 0, 0, true);
-    conv_op(c, BUF_POOL, BUF_NONE, BUF_NONE);
-    h->ops.push_back(Op{OP_HEAD, -1, BUF_NONE, BUF_NONE, BUF_NONE, 0, 0, BUF_NONE});
-    return 0;
-}
+}  // namespace
+
+#include "mpx_plan.h"
+
+namespace {
 
 // The ConvParams of layer L over B images: its packed weights, the input planes in_* (the ImageNet stem: the engine's padded NHWC4 staging,
 // where a (ky) tap is one 64-B run of 8 pixels x 4 channels, no bounds to check), the output planes y_*.  The output pixels must fit
@@ -3218,6 +1755,7 @@ int mpx_num_cus(const mpx_engine* h) { return h ? h->num_cus : MPX_E_ARG; }
 int mpx_last_conv_kernels(const mpx_engine* h) { return h ? (int)h->last_kernels : MPX_E_ARG; }
 size_t mpx_workspace_bytes(const mpx_engine* h) { return h ? h->arena_bytes + h->tab_arena_bytes : 0; }
 int mpx_num_convs(const mpx_engine* h) { return h ? (int)h->convs.size() : MPX_E_ARG; }
+int mpx_describe_plan(int arch_id, char* buf, size_t cap, size_t* len) { return describe_plan_of(arch_id, buf, cap, len); }
 
 int mpx_conv_info(const mpx_engine* h, int i, mpx_conv_desc* out) {
     if (!h || !out || i < 0 || i >= (int)h->convs.size()) return MPX_E_ARG;

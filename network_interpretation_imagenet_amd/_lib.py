@@ -169,7 +169,7 @@ SIGNATURES = {
     "mpx_layernorm_c": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp]),
     "mpx_global_avgpool_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
     "mpx_profile_collect_ln": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong)] + [C.POINTER(C.c_double)] * 9),
-    # ViT: the token layers' rows, the attention launches, class token + position embedding, the three kernels of csrc/mpx_attn.h
+    # ViT: the token layers' rows, the attention launches, class token + position embedding, the kernels of csrc/mpx_attn.h and the strided LayerNorm
     "mpx_conv_rows": (_i, [_vp, _i, C.POINTER(C.c_int)]),
     "mpx_num_attn": (_i, [_vp]),
     "mpx_attn_info": (_i, [_vp, _i, C.POINTER(AttnDesc)]),

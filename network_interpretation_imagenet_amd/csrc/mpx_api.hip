@@ -67,7 +67,7 @@ struct ConvLayer {
     bool loaded = false;
     bool is_fc = false;
     bool is_stem = false;
-    int consumer_act = 0;   // 1: torchvision follows this conv with SiLU, which its one consumer takes on load (mpx_mbconv.h); relu is 0 then
+    int consumer_act = 0;   // 1: torchvision follows this conv with SiLU, which its one consumer takes on load (mpx_dw.h); relu is 0 then
     int rows = 0;           // > 0: a token layer (ViT): the layer runs on `rows` = T rows per image that are no square map -- d.hin = d.hout = 0
                             // and conv_params hands the kernels hin = ho = rows, win = wo = 1 (mpx_conv_rows)
     int epi_act = 0;        // 1: exact GELU in the epilogue (a ConvNeXt block.3: ConvGelu, mpx_conv.h); the layer runs the generic tiles only
@@ -150,10 +150,10 @@ struct PointTail {
 // A depthwise 3x3 conv + BatchNorm + ReLU6 (MobileNetV2; mpx_dw.h): fp32 tap-major weights [9][pitch] and BatchNorm vectors of its own.
 struct DwLayer {
     mpx_dwconv_desc d;
-    bool linear = false;    // ShuffleNetV2: BatchNorm only, no activation and no clamp (dwconv3x3_bn_kernel, mpx_shuffle.h)
+    bool linear = false;    // ShuffleNetV2: BatchNorm only, no activation and no clamp (the run form without SiLU, mpx_dw.h)
     int in_bf = 0, in_hp = 0;   // its planes are a two-half stage map (channels = 2 * in_bf, pitch = 2 * in_hp): logical channel c loads to its physical position
     int ksize = 3;          // 3 or 5 (EfficientNet-B0): weights [ksize * ksize][pitch]
-    bool mb = false;        // EfficientNet-B0: dwconv_bn_act_kernel (mpx_mbconv.h) with SiLU on load (act_in) and in the epilogue (act_out)
+    bool mb = false;        // EfficientNet-B0: the run form (mpx_dw.h) with SiLU on load (act_in) and in the epilogue (act_out)
     int act_in = 0, act_out = 0;
     bool ln = false;        // ConvNeXt: depthwise 7x7 + bias + LayerNorm over the channels (dwconv7x7_ln_kernel, mpx_cnext.h); scale / shift hold the
                             // LayerNorm's weight / bias, `bias` the conv's own bias, `eps` the LayerNorm's epsilon as loaded
@@ -1164,23 +1164,16 @@ CatNormParams catnorm_params(const void* fresh_hi, const void* fresh_lo, int g, 
     return p;
 }
 
+// every depthwise + BatchNorm form (DwForm below): clamp_in is the one-pixel ReLU6 form's, act_in / act_out the run form's with SiLU
 DwParams dw_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* w, const float* scale, const float* shift, int B,
-                   int hin, int pitch, int stride, int clamp_in) {
+                   int hin, int pitch, int stride, int clamp_in, int act_in, int act_out) {
     DwParams p = zeroed<DwParams>();
     set_planes(p, x_hi, x_lo, y_hi, y_lo);
     p.w = w; p.scale = scale; p.shift = shift;
     p.hin = hin; p.ho = dw_out_side(hin, stride); p.pitch = pitch; p.stride = stride; p.clamp_in = clamp_in != 0;
-    p.npix = (long long)B * p.ho * p.ho;
-    return p;
-}
-
-MbDwParams mbdw_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* w, const float* scale, const float* shift, int B,
-                       int hin, int pitch, int stride, int act_in, int act_out) {
-    MbDwParams p = zeroed<MbDwParams>();
-    set_planes(p, x_hi, x_lo, y_hi, y_lo);
-    p.w = w; p.scale = scale; p.shift = shift;
-    p.hin = hin; p.ho = dw_out_side(hin, stride); p.pitch = pitch; p.act_in = act_in; p.act_out = act_out;
+    p.act_in = act_in; p.act_out = act_out;
     p.rows = (long long)B * p.ho;
+    p.npix = p.rows * p.ho;
     return p;
 }
 
@@ -1195,18 +1188,10 @@ CnDwLnParams cn_dwln_params(const void* x_hi, const void* x_lo, void* y_hi, void
 }
 
 CnLnParams cn_ln_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* gamma, const float* beta, float eps,
-                        long long rows, int C) {
+                        long long rows, long long in_stride, int C) {
     CnLnParams p = zeroed<CnLnParams>();
     set_planes(p, x_hi, x_lo, y_hi, y_lo);
-    p.gamma = gamma; p.beta = beta; p.rows = rows; p.C = C; p.eps = eps;
-    return p;
-}
-
-CnLnRowsParams ln_rows_params(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, const float* gamma, const float* beta, float eps,
-                              long long rows, long long in_stride, int C) {
-    CnLnRowsParams p = zeroed<CnLnRowsParams>();
-    p.ln = cn_ln_params(x_hi, x_lo, y_hi, y_lo, gamma, beta, eps, rows, C);
-    p.in_stride = in_stride;
+    p.gamma = gamma; p.beta = beta; p.rows = rows; p.in_stride = in_stride; p.C = C; p.eps = eps;
     return p;
 }
 
@@ -1285,42 +1270,41 @@ int launch_catnorm(mpx_engine* h, const CatNormParams& p, ProfTag tag, hipStream
     return 0;
 }
 
-// one dwconv3x3_bn_relu6_kernel launch (`linear`: ShuffleNetV2's form without activation and clamps, dwconv3x3_bn_kernel of mpx_shuffle.h)
-int launch_dwconv(mpx_engine* h, const DwParams& p, bool linear, ProfTag tag, hipStream_t st) {
+// The three depthwise + BatchNorm forms (mpx_dw.h)
+enum DwForm {
+    DW_RELU6,   // MobileNetV2: 3x3 + ReLU6, one thread per output pixel (dwconv3x3_bn_relu6_kernel)
+    DW_LINEAR,  // ShuffleNetV2: 3x3, no activation, the run form without SiLU code
+    DW_SILU     // EfficientNet-B0: 3x3 / 5x5, the run form with SiLU on load (act_in) and in the epilogue (act_out)
+};
+
+template <int K, bool SILU>
+void launch_dw_run(const DwParams& p, unsigned grid, hipStream_t st) {
+    if (p.stride == 1)
+        hipLaunchKernelGGL((dwconv_bn_act_kernel<K, 1, SILU>), dim3(grid), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL((dwconv_bn_act_kernel<K, 2, SILU>), dim3(grid), dim3(256), 0, st, p);
+}
+
+// one depthwise + BatchNorm launch
+int launch_dwconv(mpx_engine* h, const DwParams& p, DwForm form, int ksize, ProfTag tag, hipStream_t st) {
     ProfScope ps(h, st, 2, -1, tag);
-    if (linear) {
-        // the run form: a unit is a run of 4 (stride 1) or 2 (stride 2) output pixels.  Grid cap, blocks per CU, measured at batch 2340 next to
-        // the one-pixel form, ms at 8 / 4 / 2: 28x28 x 64 stride 1 0.262 / 0.263 / 0.257, 14x14 x 128 0.139 / 0.144 / 0.142,
-        // 7x7 x 256 0.058 / 0.063 / 0.065; 56x56 x 64 stride 2 0.495 / 0.484 / 0.460, 28x28 x 128 0.249 / 0.250 / 0.237: 8 at stride 1, 2 at stride 2
-        const int W = p.stride == 1 ? DwRun<1>::W : DwRun<2>::W;
-        const unsigned long long units = (unsigned long long)(p.npix / p.ho) * (unsigned)((p.ho + W - 1) / W) * (unsigned)(p.pitch / 8);
-        const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (p.stride == 1 ? 8 : 2));
-        if (p.stride == 1)
-            hipLaunchKernelGGL(dwconv3x3_bn_kernel<1>, dim3(grid), dim3(256), 0, st, p);
-        else
-            hipLaunchKernelGGL(dwconv3x3_bn_kernel<2>, dim3(grid), dim3(256), 0, st, p);
+    if (form == DW_RELU6) {
+        const unsigned long long units = (unsigned long long)p.npix * (unsigned)(p.pitch / 8);
+        // as launch_catnorm: about 8 workgroups per CU, striding over the rest
+        const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
+        hipLaunchKernelGGL(dwconv3x3_bn_relu6_kernel, dim3(grid), dim3(256), 0, st, p);
         MPX_HIP(h, hipGetLastError());
         return 0;
     }
-    const unsigned long long units = (unsigned long long)p.npix * (unsigned)(p.pitch / 8);
-    // as launch_catnorm: about 8 workgroups per CU, striding over the rest
-    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * 8);
-    hipLaunchKernelGGL(dwconv3x3_bn_relu6_kernel, dim3(grid), dim3(256), 0, st, p);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
-}
-
-// one dwconv_bn_act_kernel launch (mpx_mbconv.h).  Grid cap as launch_dwconv's run form: 8 blocks per CU at stride 1, 2 at stride 2, striding
-// over the rest.
-int launch_mbdw(mpx_engine* h, const MbDwParams& p, int ksize, int stride, ProfTag tag, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, tag);
-    const int W = stride == 1 ? 4 : 2;
+    // the run form: a unit is a run of 4 (stride 1) or 2 (stride 2) output pixels.  Grid cap, blocks per CU, measured at batch 2340 next to
+    // the one-pixel form, ms at 8 / 4 / 2: 28x28 x 64 stride 1 0.262 / 0.263 / 0.257, 14x14 x 128 0.139 / 0.144 / 0.142,
+    // 7x7 x 256 0.058 / 0.063 / 0.065; 56x56 x 64 stride 2 0.495 / 0.484 / 0.460, 28x28 x 128 0.249 / 0.250 / 0.237: 8 at stride 1, 2 at stride 2
+    const int W = p.stride == 1 ? DwRun<3, 1>::W : DwRun<3, 2>::W;        // (W does not depend on K)
     const unsigned long long units = (unsigned long long)p.rows * (unsigned)((p.ho + W - 1) / W) * (unsigned)(p.pitch / 8);
-    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (stride == 1 ? 8 : 2));
-    if (ksize == 3 && stride == 1) hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 1>), dim3(grid), dim3(256), 0, st, p);
-    else if (ksize == 3) hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 2>), dim3(grid), dim3(256), 0, st, p);
-    else if (stride == 1) hipLaunchKernelGGL((dwconv_bn_act_kernel<5, 1>), dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((dwconv_bn_act_kernel<5, 2>), dim3(grid), dim3(256), 0, st, p);
+    const unsigned grid = (unsigned)std::min<unsigned long long>((units + 255) / 256, (unsigned long long)h->num_cus * (p.stride == 1 ? 8 : 2));
+    if (form == DW_LINEAR) launch_dw_run<3, false>(p, grid, st);
+    else if (ksize == 3) launch_dw_run<3, true>(p, grid, st);
+    else launch_dw_run<5, true>(p, grid, st);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -1343,18 +1327,10 @@ int launch_cn_dwln(mpx_engine* h, const CnDwLnParams& p, int max_blocks, ProfTag
     return 0;
 }
 
-// one layernorm_c_kernel launch
+// one layernorm_c_kernel launch (ConvNeXt's and a ViT's LayerNorms; in_stride > 1: a ViT's encoder.ln)
 int launch_cn_ln(mpx_engine* h, const CnLnParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
     ProfScope ps(h, st, 2, -1, tag);
     hipLaunchKernelGGL(layernorm_c_kernel, dim3(cn_grid(h, p.rows, p.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
-    MPX_HIP(h, hipGetLastError());
-    return 0;
-}
-
-// one layernorm_rows_kernel launch (mpx_attn.h)
-int launch_ln_rows(mpx_engine* h, const CnLnRowsParams& p, int max_blocks, ProfTag tag, hipStream_t st) {
-    ProfScope ps(h, st, 2, -1, tag);
-    hipLaunchKernelGGL(layernorm_rows_kernel, dim3(cn_grid(h, p.ln.rows, p.ln.C, 8, max_blocks)), dim3(CN_NT), 0, st, p);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -2339,7 +2315,7 @@ int mpx_maxpool2x2s2(mpx_engine* h, const void* in_hi, const void* in_lo, void* 
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hin <= 0 || (hin & 1) || c <= 0 || (c & 7))
         return fail(h, MPX_E_ARG, "maxpool2x2s2: bad arguments (hin even, c multiple of 8)");
     if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool2x2s2: the planes must be 16-byte aligned");
-    return launch_planes(h, maxpool2x2s2_kernel, (size_t)B * (hin / 2) * (hin / 2) * (c / 8), GRID_CAP_16K, ProfTag(), stream,
+    return launch_planes(h, maxpool_s2p0_kernel<2>, (size_t)B * (hin / 2) * (hin / 2) * (c / 8), GRID_CAP_16K, ProfTag(), stream,
                          (const half_t*)in_hi, (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
@@ -2350,7 +2326,7 @@ int mpx_maxpool3x3s2p0(mpx_engine* h, const void* in_hi, const void* in_lo, void
         return fail(h, MPX_E_ARG, "maxpool3x3s2p0: bad arguments (hin odd and >= 3, c multiple of 8)");
     if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "maxpool3x3s2p0: the planes must be 16-byte aligned");
     const int ho = (hin - 3) / 2 + 1;
-    return launch_planes(h, maxpool3x3s2p0_kernel, (size_t)B * ho * ho * (c / 8), GRID_CAP_16K, ProfTag(), stream, (const half_t*)in_hi,
+    return launch_planes(h, maxpool_s2p0_kernel<3>, (size_t)B * ho * ho * (c / 8), GRID_CAP_16K, ProfTag(), stream, (const half_t*)in_hi,
                          (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hin, c);
 }
 
@@ -2383,7 +2359,7 @@ int mpx_global_avgpool(mpx_engine* h, const void* in_hi, const void* in_lo, void
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool: bad arguments (c multiple of 8)");
     if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "global_avgpool: the planes must be 16-byte aligned");
-    return launch_planes(h, global_avgpool_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi, (const half_t*)in_lo,
+    return launch_planes(h, global_avgpool_kernel<POOL_PLAIN>, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi, (const half_t*)in_lo,
                          (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
@@ -2456,7 +2432,7 @@ int mpx_dwconv3x3_bn_relu6(mpx_engine* h, const void* in_hi, const void* in_lo, 
     if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn_relu6: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, clamp_in), false, ProfTag(),
+    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, clamp_in, 0, 0), DW_RELU6, 3, ProfTag(),
                          as_stream(stream));
 }
 
@@ -2469,7 +2445,8 @@ int mpx_dwconv3x3_bn(mpx_engine* h, const void* in_hi, const void* in_lo, const 
     if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv3x3_bn: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, 0), true, ProfTag(), as_stream(stream));
+    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, 0, 0, 0), DW_LINEAR, 3, ProfTag(),
+                         as_stream(stream));
 }
 
 int mpx_dwconv_layout(const mpx_engine* h, int k, int* linear, int* bf, int* hp) {
@@ -2548,7 +2525,7 @@ int mpx_layernorm_c(mpx_engine* h, const void* in_hi, const void* in_lo, const f
     if (planes_misaligned({in_hi, in_lo, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "layernorm_c: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_cn_ln(h, cn_ln_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, C), max_blocks, ProfTag(), as_stream(stream));
+    return launch_cn_ln(h, cn_ln_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, 1, C), max_blocks, ProfTag(), as_stream(stream));
 }
 
 int mpx_global_avgpool_ln(mpx_engine* h, const void* in_hi, const void* in_lo, const float* ln_weight, const float* ln_bias, float eps,
@@ -2631,8 +2608,8 @@ int mpx_layernorm_rows(mpx_engine* h, const void* in_hi, const void* in_lo, cons
     if (planes_misaligned({in_hi, in_lo, ln_weight, ln_bias, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "layernorm_rows: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_ln_rows(h, ln_rows_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, in_stride, C), max_blocks, ProfTag(),
-                          as_stream(stream));
+    return launch_cn_ln(h, cn_ln_params(in_hi, in_lo, out_hi, out_lo, ln_weight, ln_bias, eps, rows, in_stride, C), max_blocks, ProfTag(),
+                        as_stream(stream));
 }
 
 int mpx_conv_consumer_act(const mpx_engine* h, int i, int* act) {
@@ -2651,8 +2628,8 @@ int mpx_dwconv_bn_act(mpx_engine* h, const void* in_hi, const void* in_lo, const
     if (planes_misaligned({in_hi, in_lo, w, scale, shift, out_hi, out_lo}))
         return fail(h, MPX_E_ARG, "dwconv_bn_act: every pointer must be 16-byte aligned");
     MPX_SET_DEVICE(h);
-    return launch_mbdw(h, mbdw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, act_in, act_out), ksize, stride, ProfTag(),
-                       as_stream(stream));
+    return launch_dwconv(h, dw_params(in_hi, in_lo, out_hi, out_lo, w, scale, shift, B, hin, pitch, stride, 0, act_in, act_out), DW_SILU, ksize,
+                         ProfTag(), as_stream(stream));
 }
 
 // mpx_se_gate / mpx_se_gate_relu: one set of argument checks, the fc1 activation apart
@@ -2781,7 +2758,7 @@ int mpx_global_avgpool_silu(mpx_engine* h, const void* in_hi, const void* in_lo,
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool_silu: bad arguments (c multiple of 8)");
     if (planes_misaligned({in_hi, in_lo, out_hi, out_lo})) return fail(h, MPX_E_ARG, "global_avgpool_silu: the planes must be 16-byte aligned");
-    return launch_planes(h, global_avgpool_silu_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
+    return launch_planes(h, global_avgpool_kernel<POOL_SILU>, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
                          (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
@@ -2826,7 +2803,7 @@ int mpx_global_avgpool_clamp6(mpx_engine* h, const void* in_hi, const void* in_l
     if (!in_hi || !in_lo || !out_hi || !out_lo || B <= 0 || hw <= 0 || c <= 0 || (c & 7) || (long long)B * (c / 8) > 0x7fffffffLL)
         return fail(h, MPX_E_ARG, "global_avgpool_clamp6: bad arguments (c multiple of 8)");
     // (no alignment check, unlike its eight siblings: DESIGN.md 31 records the gap; closing it would reject calls that are accepted today)
-    return launch_planes(h, global_avgpool_clamp6_kernel, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
+    return launch_planes(h, global_avgpool_kernel<POOL_CLAMP6>, (size_t)B * (c / 8), GRID_ALL, ProfTag(), stream, (const half_t*)in_hi,
                          (const half_t*)in_lo, (half_t*)out_hi, (half_t*)out_lo, B, hw, c);
 }
 
@@ -2980,12 +2957,10 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
                 if (D.ln)
                     rc = launch_cn_dwln(h, cn_dwln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.bias, D.scale, D.shift, D.eps, B, D.d.hin, D.d.channels),
                                         0, tag, st);
-                else if (D.mb)
-                    rc = launch_mbdw(h, mbdw_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.scale, D.shift, B, D.d.hin, D.d.pitch, D.d.stride, D.act_in, D.act_out),
-                                     D.ksize, D.d.stride, tag, st);
                 else
-                    rc = launch_dwconv(h, dw_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.scale, D.shift, B, D.d.hin, D.d.pitch, D.d.stride, D.d.clamp_in),
-                                       D.linear, tag, st);
+                    rc = launch_dwconv(h, dw_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), D.w, D.scale, D.shift, B, D.d.hin, D.d.pitch, D.d.stride, D.d.clamp_in,
+                                                    D.act_in, D.act_out),
+                                       D.mb ? DW_SILU : D.linear ? DW_LINEAR : DW_RELU6, D.ksize, tag, st);
                 break;
             }
             case OP_SEGATE: {
@@ -3004,13 +2979,12 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
             case OP_LNORM: {        // rows: the pixels of a square map (ConvNeXt) or the tokens (ViT: o.hin = T)
                 const LnLayer& N = h->lnorms[o.conv];
                 const long long rows = (long long)B * o.hin * (h->vit ? 1 : o.hin);
-                rc = launch_cn_ln(h, cn_ln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, rows, o.c), 0, {PF_LNORM, o.conv}, st);
+                rc = launch_cn_ln(h, cn_ln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, rows, 1, o.c), 0, {PF_LNORM, o.conv}, st);
                 break;
             }
             case OP_LNORMROWS: {    // ViT: encoder.ln on the class-token row of each image (o.hin = T rows apart)
                 const LnLayer& N = h->lnorms[o.conv];
-                rc = launch_ln_rows(h, ln_rows_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, B, o.hin, o.c), 0,
-                                    {PF_LNORM, o.conv}, st);
+                rc = launch_cn_ln(h, cn_ln_params(hi(o.in), lo(o.in), hi(o.out), lo(o.out), N.gamma, N.beta, N.eps, B, o.hin, o.c), 0, {PF_LNORM, o.conv}, st);
                 break;
             }
             case OP_TOKENS:

@@ -1,6 +1,6 @@
 // mpx_attn.h -- the kernels a Vision Transformer (torchvision's vit_b_16 / vit_b_32) adds to the conv list, gfx950: scaled-dot-product
-// attention over a token sequence on split-fp16 planes, the token assembly (class token + position embedding), and the LayerNorm over the
-// channels of rows that lie a fixed number of rows apart (encoder.ln on the class-token row of each image).
+// attention over a token sequence on split-fp16 planes and the token assembly (class token + position embedding).  (Its LayerNorms,
+// encoder.ln on the class-token row of each image included, are mpx_cnext.h's layernorm_c_kernel.)
 //
 // 1. ATTENTION.  Input: the planes [B][T][3 D] self_attention.in_proj wrote, Q at channel 0, K at D, V at 2 D, head h owning channels
 // 64 h .. 64 h + 63 of each (D = heads * 64); output: planes [B][T][D], what out_proj reads.  Q, K and V are split-fp16 as they come, i.e.
@@ -41,14 +41,10 @@
 //
 // 2. TOKEN ASSEMBLY: tok[b][0] = class_token + pos[0], tok[b][1 + i] = patch[b][i] + pos[1 + i]: one fp32 add of the exact hi + lo (or the
 // fp32 class token) and the fp32 position embedding, re-split.  Planes [B][T - 1][D] -> [B][T][D].
-//
-// 3. LayerNorm of strided rows: layernorm_c_kernel (mpx_cnext.h) with input row r at row r * in_stride of the input planes; the arithmetic,
-// the workgroup shape and the barriers are that kernel's, unchanged.
 #pragma once
 #include <cmath>
 
 #include "mpx_gconv.h"
-#include "mpx_cnext.h"
 
 namespace mpx {
 
@@ -256,41 +252,6 @@ __global__ __launch_bounds__(AT_NT) void tokens_assemble_kernel(const TokParams 
         const size_t o = (size_t)row * p.D + c;
         *(h8*)(p.y_hi + o) = oh;
         *(h8*)(p.y_lo + o) = ol;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// 3. LayerNorm over the C channels of rows that lie in_stride rows apart: planes [rows * in_stride][C] -> [rows][C].  Output row r is
-// layernorm_c_kernel's result for input row r * in_stride (a ViT's encoder.ln on the class-token row of each image: in_stride = T).
-// ------------------------------------------------------------------------------------------
-struct CnLnRowsParams {
-    CnLnParams ln;
-    long long in_stride;     // rows of the input planes between two rows that are normalised
-};
-
-__global__ __launch_bounds__(CN_NT) void layernorm_rows_kernel(const CnLnRowsParams q) {
-    const CnLnParams& p = q.ln;
-    __shared__ float psum[CN_NT], psq[CN_NT];
-    const int G = p.C >> 3, R = CN_NT / G;
-    const int slot = threadIdx.x / G, g = threadIdx.x - slot * G, c = g << 3;
-    const float fC = (float)p.C;
-    for (long long base = (long long)blockIdx.x * R; base < p.rows; base += (long long)gridDim.x * R) {
-        const long long u = base + slot;
-        const bool active = slot < R && u < p.rows;
-        float v[1][8], rstd[1];
-        if (active) {
-            const size_t at = (size_t)u * q.in_stride * p.C + c;
-            const h8 vh = *(const h8*)(p.x_hi + at);
-            const h8 vl = *(const h8*)(p.x_lo + at);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[0][j] = (float)vh[j] + (float)vl[j];
-        }
-        cn_ln_stats<1>(v, rstd, slot, g, G, active, fC, p.eps, psum, psq);
-        if (active) {
-            const f4 g0 = *(const f4*)(p.gamma + c), g1 = *(const f4*)(p.gamma + c + 4);
-            const f4 b0 = *(const f4*)(p.beta + c), b1 = *(const f4*)(p.beta + c + 4);
-            cn_ln_store(v[0], rstd[0], g0, g1, b0, b1, p.y_hi, p.y_lo, (size_t)u * p.C + c);
-        }
     }
 }
 

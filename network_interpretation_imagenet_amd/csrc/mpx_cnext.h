@@ -104,7 +104,7 @@ __device__ __forceinline__ void cn_ln_store(const float (&d)[8], float rstd, con
 // 1. Depthwise 7x7 conv (pad 3, stride 1) + bias + LayerNorm over C: planes [B][H][H][C] -> [B][H][H][C], one launch.
 //     acc_c = 0;  acc_c = fma(w[ky * 7 + kx][c], x[iy][ix][c], acc_c) over the taps inside the map, row-major;  v_c = acc_c + bias_c;
 //     then the LayerNorm above.  x = hi + lo (exact).  w: fp32 tap-major [49][C]; bias, gamma, beta: fp32 [C].
-// The depthwise part is the run form of dwconv_bn_act_kernel (mpx_mbconv.h): one thread = 8 channels of a run of W = 4 output pixels along
+// The depthwise part is the run form of dwconv_bn_act_kernel (mpx_dw.h): one thread = 8 channels of a run of W = 4 output pixels along
 // x; row by row it loads the run's 10 input columns once and feeds every output its 7 taps of that row, kx ascending.  A column outside
 // the map is loaded at a clamped index and its fma is not taken; a row outside the map is skipped.  A unit is (image, output row, run);
 // the G threads of a slot hold one unit, a workgroup R units at a time.  The grid is capped by the host; a workgroup strides over the
@@ -206,7 +206,9 @@ __global__ __launch_bounds__(CN_NT, 2) void dwconv7x7_ln_kernel(const CnDwLnPara
 }
 
 // ------------------------------------------------------------------------------------------
-// 2. Stand-alone LayerNorm over the C channels of each pixel: planes [rows][C] -> [rows][C], v = hi + lo (exact), the arithmetic above.
+// 2. Stand-alone LayerNorm over the C channels of each pixel: planes [rows * in_stride][C] -> [rows][C], v = hi + lo (exact), the arithmetic
+// above.  Output row r is the LayerNorm of input row r * in_stride: 1 for a map or a token sequence (mpx_layernorm_c), T for a ViT's
+// encoder.ln on the class-token row of each image (mpx_layernorm_rows).
 // One thread = 8 channels of one pixel, a slot = one pixel, a workgroup R pixels at a time; grid capped by the host, uniform trip count,
 // every thread at every barrier.  Offsets are 64-bit.  No atomics, no scratch; 2 KB of static LDS.
 // ------------------------------------------------------------------------------------------
@@ -218,6 +220,7 @@ struct CnLnParams {
     const float* gamma;      // [C]
     const float* beta;       // [C]
     long long rows;
+    long long in_stride;     // rows of the input planes between two rows that are normalised
     int C;
     float eps;
 };
@@ -231,8 +234,8 @@ __global__ __launch_bounds__(CN_NT) void layernorm_c_kernel(const CnLnParams p) 
         const long long u = base + slot;
         const bool active = slot < R && u < p.rows;
         float v[1][8], rstd[1];
-        const size_t at = (size_t)u * p.C + c;
         if (active) {
+            const size_t at = (size_t)u * p.in_stride * p.C + c;
             const h8 vh = *(const h8*)(p.x_hi + at);
             const h8 vl = *(const h8*)(p.x_lo + at);
 #pragma unroll
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(CN_NT) void layernorm_c_kernel(const CnLnParams p) 
         if (active) {
             const f4 g0 = *(const f4*)(p.gamma + c), g1 = *(const f4*)(p.gamma + c + 4);
             const f4 b0 = *(const f4*)(p.beta + c), b1 = *(const f4*)(p.beta + c + 4);
-            cn_ln_store(v[0], rstd[0], g0, g1, b0, b1, p.y_hi, p.y_lo, at);
+            cn_ln_store(v[0], rstd[0], g0, g1, b0, b1, p.y_hi, p.y_lo, (size_t)u * p.C + c);
         }
     }
 }

@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <type_traits>
 
 namespace mpx {
@@ -47,6 +48,11 @@ __device__ __forceinline__ float fp32_value(float v) {
     asm("" : "+v"(v));
     return v;
 }
+
+// silu(x) = x / (1 + e^-x): the accurate expf and an IEEE division.  For large negative x expf overflows to +inf and the quotient is -0,
+// the correct limit; silu(0) = 0, so pad channels stay exact zeros.  The one definition every kernel uses (the run-form depthwise conv of
+// mpx_dw.h, the SiLU global pool of mpx_kernels.h, the SE gate of mpx_mbconv.h).
+__device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)); }
 
 struct ConvParams {
     const half_t* x_hi;      // input planes, NHWC (pix_stride elements per pixel)

@@ -16,7 +16,7 @@ namespace mpx {
 // 3000, where an fp32 step is 2.4e-4, and 169 such roundings put the mean 1e-5 off -- more than four times what the fp32 CPU loop, whose
 // sum is a tree, is from fp64.  The loads of four pixels are issued before their four adds: the map is 169 pixels deep and a thread has
 // nothing else to hide the latency with.
-// A kernel of its own: global_avgpool_kernel and global_avgpool_clamp6_kernel stay as they are.
+// A kernel of its own, not an instantiation of global_avgpool_kernel<LOAD> (mpx_kernels.h): its sums are fp64 and its output is fp32.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void global_avgpool_logits_kernel(const half_t* __restrict__ in_hi,
                                                                      const half_t* __restrict__ in_lo,

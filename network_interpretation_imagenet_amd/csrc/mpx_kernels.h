@@ -140,60 +140,19 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const half_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------
-// K3 of the VGG family: maxpool 2x2 stride 2 (nn.MaxPool2d(2, 2), no padding) on split planes.  One thread = 8 channels of one
-// output pixel; the output pair is the (hi, lo) pair of the input element with the largest hi + lo (the first one on a tie), so the
-// merged output equals F.max_pool2d of the merged planes bit for bit.  Offsets are 64-bit: one plane of a 224x224x64 map passes
-// 2^31 elements from 669 images on.
+// K3 without padding: K x K stride-2 max pool on split planes, every window inside the map.  K = 2: nn.MaxPool2d(2, 2) of the VGG family
+// (hin even, ho = hin / 2).  K = 3: AlexNet's and SqueezeNet's MaxPool2d(3, 2) (hin odd, ho = (hin - 3) / 2 + 1).  One thread = 8 channels
+// of one output pixel (16-byte loads and stores, grid-stride); the output pair is the (hi, lo) PAIR of the window's largest hi + lo (the
+// sum of two fp16 is exact in fp32), the first in row-major window order on a tie, so the merged output equals F.max_pool2d of the merged
+// planes bit for bit, for any sign.  Offsets are 64-bit: one plane of a 224x224x64 map passes 2^31 elements from 669 images on.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void maxpool2x2s2_kernel(const half_t* __restrict__ in_hi,
+template <int K>
+__global__ __launch_bounds__(256) void maxpool_s2p0_kernel(const half_t* __restrict__ in_hi,
                                                             const half_t* __restrict__ in_lo,
                                                             half_t* __restrict__ out_hi,
                                                             half_t* __restrict__ out_lo, int B, int hin,
                                                             int c) {
-    const int ho = hin / 2;
-    const int cg = c / 8;
-    const size_t total = (size_t)B * ho * ho * cg;
-    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
-        const size_t g = t % cg;
-        const size_t pix = t / cg;                      // output pixel: (n * ho + oy) * ho + ox
-        const size_t ox = pix % ho;
-        const size_t ny = pix / ho;                     // n * ho + oy: input row 2 * ny of the image-stacked map
-        const size_t i00 = ((2 * ny) * hin + 2 * ox) * c + g * 8;
-        const size_t at[4] = {i00, i00 + c, i00 + (size_t)hin * c, i00 + (size_t)hin * c + c};
-        h8 bh = *(const h8*)(in_hi + at[0]);
-        h8 bl = *(const h8*)(in_lo + at[0]);
-        float best[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) best[j] = (float)bh[j] + (float)bl[j];
-#pragma unroll
-        for (int q = 1; q < 4; ++q) {
-            const h8 vh = *(const h8*)(in_hi + at[q]);
-            const h8 vl = *(const h8*)(in_lo + at[q]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = (float)vh[j] + (float)vl[j];
-                const bool take = v > best[j];
-                best[j] = take ? v : best[j];
-                bh[j] = take ? vh[j] : bh[j];
-                bl[j] = take ? vl[j] : bl[j];
-            }
-        }
-        const size_t o = pix * c + g * 8;
-        *(h8*)(out_hi + o) = bh;
-        *(h8*)(out_lo + o) = bl;
-    }
-}
-
-// 3x3 stride-2 max pool WITHOUT padding (AlexNet's MaxPool2d(3, 2)) on split-fp16 NHWC planes: ho = (hin - 3) / 2 + 1 with hin odd, so
-// every window lies inside the map.  One thread = 8 channels of an output pixel (16-byte loads and stores, 64-bit offsets, grid-stride).
-// As the 2x2 kernel it copies the (hi, lo) PAIR of the window's largest hi + lo (the sum of two fp16 is exact in fp32), the first in
-// row-major window order on a tie, so the merged output is max_pool2d of the merged input bit for bit, for any sign.
-__global__ __launch_bounds__(256) void maxpool3x3s2p0_kernel(const half_t* __restrict__ in_hi,
-                                                              const half_t* __restrict__ in_lo,
-                                                              half_t* __restrict__ out_hi,
-                                                              half_t* __restrict__ out_lo, int B, int hin,
-                                                              int c) {
-    const int ho = (hin - 3) / 2 + 1;
+    const int ho = (hin - K) / 2 + 1;
     const int cg = c / 8;
     const size_t total = (size_t)B * ho * ho * cg;
     const size_t row = (size_t)hin * c;
@@ -201,17 +160,22 @@ __global__ __launch_bounds__(256) void maxpool3x3s2p0_kernel(const half_t* __res
         const size_t g = t % cg;
         const size_t pix = t / cg;                      // output pixel: (n * ho + oy) * ho + ox
         const size_t ox = pix % ho;
-        const size_t ny = pix / ho;
-        const size_t n = ny / ho, oy = ny - n * ho;
-        const size_t i00 = ((n * hin + 2 * oy) * hin + 2 * ox) * c + g * 8;     // rows 2oy .. 2oy + 2 <= hin - 1, columns likewise
+        const size_t ny = pix / ho;                     // n * ho + oy
+        size_t i00;                                     // the window's first element: rows 2 oy .. 2 oy + K - 1 <= hin - 1, columns likewise
+        if constexpr (K == 2) {                         // hin = 2 ho: input row 2 * ny of the image-stacked map, no division by ho
+            i00 = ((2 * ny) * hin + 2 * ox) * c + g * 8;
+        } else {
+            const size_t n = ny / ho, oy = ny - n * ho;
+            i00 = ((n * hin + 2 * oy) * hin + 2 * ox) * c + g * 8;
+        }
         h8 bh = *(const h8*)(in_hi + i00);
         h8 bl = *(const h8*)(in_lo + i00);
         float best[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) best[j] = (float)bh[j] + (float)bl[j];
 #pragma unroll
-        for (int q = 1; q < 9; ++q) {
-            const size_t at = i00 + (q / 3) * row + (size_t)(q % 3) * c;
+        for (int q = 1; q < K * K; ++q) {
+            const size_t at = i00 + (q / K) * row + (size_t)(q % K) * c;
             const h8 vh = *(const h8*)(in_hi + at);
             const h8 vl = *(const h8*)(in_lo + at);
 #pragma unroll
@@ -230,8 +194,13 @@ __global__ __launch_bounds__(256) void maxpool3x3s2p0_kernel(const half_t* __res
 }
 
 // ------------------------------------------------------------------------------------------
-// K4a: global average pool [B][hw][c] -> [B][c] (one thread = 8 channels of one image)
+// K4a: global average pool [B][hw][c] -> [B][c] (one thread = 8 channels of one image): the hw values are summed in pixel order in fp32
+// and divided by hw once.  LOAD is what a value goes through as it is loaded: nothing; min(x, 6), the ReLU6 of the producing MFMA conv
+// (MobileNetV2's features.18, mpx_dw.h); silu(x), the SiLU of the producing MFMA conv (EfficientNet's features.8).
 // ------------------------------------------------------------------------------------------
+enum PoolLoad { POOL_PLAIN, POOL_CLAMP6, POOL_SILU };
+
+template <PoolLoad LOAD>
 __global__ __launch_bounds__(256) void global_avgpool_kernel(const half_t* __restrict__ in_hi,
                                                               const half_t* __restrict__ in_lo,
                                                               half_t* __restrict__ out_hi,
@@ -249,7 +218,10 @@ __global__ __launch_bounds__(256) void global_avgpool_kernel(const half_t* __res
         const h8 vh = *(const h8*)(in_hi + o);
         const h8 vl = *(const h8*)(in_lo + o);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) sum[j] += (float)vh[j] + (float)vl[j];
+        for (int j = 0; j < 8; ++j) {
+            const float x = (float)vh[j] + (float)vl[j];
+            sum[j] += LOAD == POOL_CLAMP6 ? fminf(x, 6.f) : LOAD == POOL_SILU ? silu_f32(x) : x;
+        }
     }
     h8 oh, ol;
     const float denom = (float)hw;

@@ -696,7 +696,7 @@ int build_topology_googlenet(mpx_engine* h) {
 // pads.  A stride-1 block's branch2.0 reads the second half IN PLACE (ConvLayer::x_pitch / x_offset: the generic kernel's pix_stride is not
 // its K per tap), the shuffle reads the first half in place; whoever reads a whole stage map -- the next stage's branch1.0 (depthwise),
 // branch1.2, branch2.0 and conv5 -- has its weights packed at the physical channel positions (in_bf / in_hp).  conv1 and the max pool keep
-// the plain layout, 24 channels at pitch 32.  The depthwise layers have no activation (DwLayer::linear: dwconv3x3_bn_kernel).
+// the plain layout, 24 channels at pitch 32.  The depthwise layers have no activation (DwLayer::linear: the run form without SiLU, mpx_dw.h).
 // Op list, 76 launches: conv1 | OP_MAXPOOL | 13 stride-1 blocks of 4 (branch2.0, branch2.3, branch2.5, shuffle) | 3 stride-2 blocks of 6
 // (branch1.0, branch1.2, branch2.0, branch2.3, branch2.5, shuffle) | conv5 | OP_AVGPOOL | fc | OP_HEAD.  38 conv entries, 19 depthwise, 16 shuffles.
 // Buffers: three of 112 * 112 * 32 elements per image.  Stride 1: X the block input, T1 branch2.0's output and then branch2.5's, T2 the
@@ -793,7 +793,7 @@ int build_topology_shufflenet(mpx_engine* h) {
 // k x k (pad (k - 1) / 2, the block's stride) + BN + SiLU, SqueezeExcitation(e, max(1, cin / 4)) -- gate = sigmoid(fc2(silu(fc1(avgpool(x))))),
 // fc1 / fc2 1x1 convs WITH bias --, 1x1 project + BN without activation; with stride 1 and cin == out the block input is added, nothing
 // behind the add.  No conv but the SE's has a bias.  StochasticDepth and Dropout are the identity in eval.  BatchNorm eps 1e-5.
-// SiLU: the MFMA convs run WITHOUT an activation (relu = 0) and the consumer takes silu(x) as it loads (ConvLayer::consumer_act; mpx_mbconv.h):
+// SiLU: the MFMA convs run WITHOUT an activation (relu = 0) and the consumer takes silu(x) as it loads (ConvLayer::consumer_act; mpx_dw.h):
 // every such conv is read by exactly one depthwise layer (act_in) or by the SiLU global pool (OP_AVGPOOLSILU).
 // Channels 16, 24, 40, 80, 112, 144 and 240 are stored with a pitch of 32, 32, 64, 96, 128, 160 and 256 (zero weight columns, zero scale and
 // shift: exact zeros, as MobileNetV2); those layers run the generic tiles only, and default_tile's rules give every one of them a generic tile.

@@ -3,7 +3,7 @@
 // torchvision's googlenet.py has twelve of them per forward: maxpool1 / 2 / 3 = MaxPool2d(3, stride 2, ceil_mode=True) on 112 -> 56 -> 28 -> 14
 // (hin - 3 is odd, so the ceil-mode map has one more row and column than the floor-mode one and its last window hangs over the edge), and
 // branch4.0 = MaxPool2d(3, stride 1, padding 1, ceil_mode=True) of every Inception module, whose border windows are clipped on every side.
-// maxpool3x3s2_kernel / maxpool3x3s2p0_kernel (mpx_kernels.h) assume windows that start at -1 with the floor-mode size, or that lie inside
+// maxpool3x3s2_kernel / maxpool_s2p0_kernel<3> (mpx_kernels.h) assume windows that start at -1 with the floor-mode size, or that lie inside
 // the map; they stay as they are.
 #pragma once
 #include "mpx_conv.h"
@@ -21,7 +21,7 @@ namespace mpx {
 // input columns once, keeps the maximum of each column's three rows, and an output is the maximum of its three column maxima: 18 loads per
 // plane for four stride-1 outputs where one thread per output pixel issues 36 (the depthwise kernel of that shape is bound by its load
 // instructions).  Max is exact, so the order changes no bit.
-// As maxpool2x2s2_kernel / maxpool3x3s2p0_kernel the output is the (hi, lo) PAIR of the winning input element (hi + lo is exact in fp32; a
+// As maxpool_s2p0_kernel<2> / <3> the output is the (hi, lo) PAIR of the winning input element (hi + lo is exact in fp32; a
 // later element wins only when strictly larger: rows top to bottom inside a column, then columns left to right), so the merged output equals
 // F.max_pool2d(merged, 3, stride, pad, 1, ceil_mode=True) bit for bit, for any sign.
 // Units (n, oy, run, 8-channel group) are 64-bit, consecutive lanes take consecutive 16-byte groups of a pixel; the grid is capped by the

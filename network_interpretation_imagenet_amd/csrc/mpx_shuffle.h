@@ -1,5 +1,5 @@
-// mpx_shuffle.h -- ShuffleNetV2's two element-wise kernels on split-fp16 NHWC planes, gfx950: the channel shuffle of a two-way concatenation
-// and the depthwise 3x3 conv + BatchNorm with NO activation behind it.
+// mpx_shuffle.h -- ShuffleNetV2's channel shuffle of a two-way concatenation on split-fp16 NHWC planes, gfx950.  (Its depthwise 3x3 conv +
+// BatchNorm with NO activation behind it is the run form of mpx_dw.h, dwconv_bn_act_kernel<3, STRIDE, false>.)
 //
 // The two-half layout.  A ShuffleNetV2 stage map has 2 * bf logical channels (bf = oup / 2) and every block splits it into its first and
 // second half.  It is stored with a pitch of 2 * hp, hp = bf rounded up to 32: logical channel l < bf at physical l, l >= bf at
@@ -7,7 +7,7 @@
 // 16-byte aligned and a whole number of 32-wide K steps: a stride-1 block's branch2.0 reads the second half in place (pointer + hp,
 // pix_stride 2 hp, K = hp) and the shuffle reads the first half in place.
 #pragma once
-#include "mpx_dw.h"      // DwParams
+#include "mpx_conv.h"
 
 namespace mpx {
 
@@ -77,107 +77,6 @@ __global__ __launch_bounds__(256) void shuffle2_concat_kernel(const ShuffleParam
         const size_t at_y = (size_t)pix * (2 * p.hp) + ((size_t)g << 3);
         *(h8*)(p.y_hi + at_y) = oh;
         *(h8*)(p.y_lo + at_y) = ol;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Depthwise 3x3 conv (pad 1, stride 1 or 2) + BatchNorm, LINEAR: no activation behind it and no clamp on load (ShuffleNetV2's branch1.0 /
-// branch2.3 with their BatchNorms branch1.1 / branch2.4).  Operand layout and arithmetic are dwconv3x3_bn_relu6_kernel's (mpx_dw.h) minus
-// its two clamps: planes [B][hin][hin][pitch] -> [B][ho][ho][pitch], ho = (hin - 1) / stride + 1; x = hi + lo exact in fp32; per output
-//     acc = 0;  for ky in 0..2, kx in 0..2 (row-major):  acc = fma(w[ky * 3 + kx][c], x[iy][ix][c], acc)
-// over the taps inside the map, then fl(fl(s * acc) + t) -- two roundings: the product and the sum are written with plain operators under
-// `#pragma clang fp contract(off)` (the __fmul_rn / __fadd_rn of this toolchain's headers are a plain * and + compiled under the default
-// contract(fast), and were fused into one fma when this kernel used them) --, the re-split and one 16-byte store per plane.
-// Negative results and results above 6 pass through unchanged.  Channels of the pitch beyond the layer's own -- the gaps of a two-half map included -- carry zero weights, scale and
-// shift and are written as exact zeros (their inputs are exact zeros wherever the engine produces them).
-// THE RUN FORM (DESIGN.md 16 has both times): one thread = 8 channels of a run of W output pixels along x (W = 4 at stride 1, 2 at stride 2),
-// as maxpool3x3_clip_kernel (mpx_pool3c.h).  Row by row it loads the run's NC = STRIDE * (W - 1) + 3 input columns once -- 18 loads per plane
-// for four stride-1 outputs where one thread per output pixel issues 36 -- and feeds every output its three taps of that row, kx ascending:
-// each output still sees its taps in row-major order, one fma each, so the result has the bits of the one-pixel form.  A column outside the
-// map is loaded at a clamped index (inside the planes) and its fma is not taken; a row outside the map is skipped.  Only one input row (NC x 8
-// values) is live at a time.
-// Units (n, oy, run, 8-channel group) are 64-bit, consecutive lanes take consecutive 16-byte groups of a pixel; the grid is capped by the
-// host and strides over the rest.  Offsets are 64-bit.  No atomics, no scratch (every array below is indexed by unrolled constants), no LDS.
-// A kernel of its own: dwconv3x3_bn_relu6_kernel stays as it is.
-// ------------------------------------------------------------------------------------------
-template <int STRIDE>
-struct DwRun {
-    static constexpr int W = STRIDE == 1 ? 4 : 2;       // output pixels per thread
-    static constexpr int NC = STRIDE * (W - 1) + 3;     // input columns under them
-};
-
-template <int STRIDE>
-__global__ __launch_bounds__(256) void dwconv3x3_bn_kernel(const DwParams p) {
-#pragma clang fp contract(off)
-    constexpr int W = DwRun<STRIDE>::W, NC = DwRun<STRIDE>::NC;
-    const long long cg = p.pitch >> 3;
-    const int runs = (p.ho + W - 1) / W;
-    const long long units = p.npix / p.ho * runs * cg;              // B * ho rows of `runs` runs
-    const int last = p.hin - 1;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < units; t += (long long)gridDim.x * 256) {
-        const long long g = t % cg;
-        long long r = t / cg;
-        const int run = (int)(r % runs);
-        r /= runs;
-        const int oy = (int)(r % p.ho);
-        const long long n = r / p.ho;
-        const int c = (int)g << 3;
-        const int ox0 = run * W;
-        const int iy0 = oy * STRIDE - 1, ix0 = ox0 * STRIDE - 1;
-        float acc[W][8];
-#pragma unroll
-        for (int k = 0; k < W; ++k)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = iy0 + ky;
-            if ((unsigned)iy >= (unsigned)p.hin) continue;
-            const size_t row = ((size_t)n * p.hin + iy) * p.hin * p.pitch + c;
-            float xm[NC][8];
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                const size_t at = row + (size_t)min(max(ix0 + q, 0), last) * p.pitch;
-                const h8 vh = *(const h8*)(p.x_hi + at);
-                const h8 vl = *(const h8*)(p.x_lo + at);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xm[q][j] = (float)vh[j] + (float)vl[j];
-            }
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const float* wt = p.w + (size_t)(ky * 3 + kx) * p.pitch + c;
-                const f4 w0 = *(const f4*)wt, w1 = *(const f4*)(wt + 4);
-#pragma unroll
-                for (int k = 0; k < W; ++k) {
-                    const bool in_map = (unsigned)(ix0 + STRIDE * k + kx) < (unsigned)p.hin;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float f = __fmaf_rn(j < 4 ? w0[j & 3] : w1[j & 3], xm[STRIDE * k + kx][j], acc[k][j]);
-                        acc[k][j] = in_map ? f : acc[k][j];
-                    }
-                }
-            }
-        }
-        const f4 s0 = *(const f4*)(p.scale + c), s1 = *(const f4*)(p.scale + c + 4);
-        const f4 t0 = *(const f4*)(p.shift + c), t1 = *(const f4*)(p.shift + c + 4);
-        const size_t out0 = (((size_t)n * p.ho + oy) * p.ho + ox0) * p.pitch + c;
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            if (ox0 + k >= p.ho) break;         // the last run of a row may be short
-            h8 oh, ol;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float s = j < 4 ? s0[j & 3] : s1[j & 3], sh = j < 4 ? t0[j & 3] : t1[j & 3];
-                const float m = s * acc[k][j];          // plain operators, inside this block's contract(off): two roundings
-                const float v = m + sh;
-                half_t hi, lo;
-                split_f32(v, hi, lo);
-                oh[j] = hi;
-                ol[j] = lo;
-            }
-            *(h8*)(p.y_hi + out0 + (size_t)k * p.pitch) = oh;
-            *(h8*)(p.y_lo + out0 + (size_t)k * p.pitch) = ol;
-        }
     }
 }
 

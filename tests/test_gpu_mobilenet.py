@@ -7,7 +7,9 @@ API and the error paths.
 Bounds.
   Depthwise, per element: |err| <= 2^-19 (|s| sum|w_i x_i| + |t|) + 2^-24.  An unfused nine-tap sum makes up to 9 products + 8 adds,
   the BatchNorm two more roundings, each 2^-24 relative to a partial result that sum|w_i x_i| (times |s|, plus |t|) bounds, and the
-  re-split 2^-22: 23 x 2^-24 < 2^-19.  (The kernel fuses each tap into one fma and stays well inside.)  Wherever the fp64 value lies
+  re-split 2^-22: 23 x 2^-24 < 2^-19.  (The kernel fuses each tap into one fma and stays well inside.  Its BatchNorm compiles to ONE fma
+  as well, one rounding where this count has two -- DESIGN.md 33 --, so the bound covers the kernel as it is and the two-rounding run form
+  of csrc/mpx_dw.h alike.)  Wherever the fp64 value lies
   above 6 or below 0 by more than the bound the result must be exactly 6 or exactly 0.
   Clamped pool, per element: (hw 2^-24 + 2^-22) mean|min(x_i, 6)| + 2^-24 -- hw - 1 sequential fp32 adds and the division (2^-24 each,
   relative to at most sum|.|), the re-split (2^-22), and lo's fp16 subnormal step as the absolute floor.

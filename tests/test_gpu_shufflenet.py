@@ -282,7 +282,7 @@ def test_linear_depthwise_on_a_two_half_pitch(small_engines, dev, hin, stride, b
     _dw_check(small_engines[X10], xh, xl, wt, sc, sh, phys, 128, hin, stride, "linear depthwise 2 x 58 at 128 %dx%d stride %d" % (hin, hin, stride))
 
 
-DW_RUN_W = {1: 4, 2: 2}         # output pixels per thread of the run form (csrc/mpx_shuffle.h, DwRun<STRIDE>::W)
+DW_RUN_W = {1: 4, 2: 2}         # output pixels per thread of the run form (csrc/mpx_dw.h, DwRun<K, STRIDE>::W)
 DW_GRID_CAP = {1: 8, 2: 2}      # blocks of 256 units per CU the host caps the grid at (launch_dwconv)
 
 

@@ -175,11 +175,13 @@ def test_pack_conv_weights_keeps_its_meaning_for_the_patch_stems_descriptors(mpx
 
 
 def test_the_new_kernels_have_no_scratch(mpx_lib):
-    """Read from the built library, no GPU: the attention, token assembly and strided LayerNorm kernels use no scratch and spill nothing, and
-    every kernel the parent had is still there under its own name."""
+    """Read from the built library, no GPU: the attention and token assembly kernels and the LayerNorm kernel (mpx_cnext.h's
+    layernorm_c_kernel, which takes the input row stride of encoder.ln: there is no strided copy of it) use no scratch and spill nothing,
+    and every conv kernel the parent had is still there under its own name."""
     ks = _device_kernels(_lib.LIB_PATH)
-    new = {n: k for n, k in ks.items() if any(t in n for t in ("attention_f16x3_kernel", "tokens_assemble_kernel", "layernorm_rows_kernel"))}
+    new = {n: k for n, k in ks.items() if any(t in n for t in ("attention_f16x3_kernel", "tokens_assemble_kernel", "layernorm_c_kernel"))}
     assert len(new) == 3, sorted(ks)
+    assert not any("layernorm_rows_kernel" in n for n in ks)
     for n, k in new.items():
         assert int(k["private_segment_fixed_size"]) == 0 and int(k.get("vgpr_spill_count", 0)) == 0, (n, k)
     assert len([n for n in ks if "conv_f16x3_kernel" in n and "ConvGelu" not in n]) == 13 and len([n for n in ks if "ConvGelu" in n]) == 5

@@ -1,7 +1,7 @@
 // probe: ShuffleNetV2's linear depthwise kernel -- the one-pixel-per-thread form (kept here only) against the committed run form
-// (csrc/mpx_shuffle.h) on the same planes in the same process, batch 2340, launches alternating; compares the outputs bit for bit.
+// (csrc/mpx_dw.h, dwconv_bn_act_kernel<3, STRIDE, false>) on the same planes in the same process, batch 2340, launches alternating; compares the outputs bit for bit.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/probes/dw_run_probe tools/probes/dw_run_probe.hip   (profiles/shufflenet_dw_run_probe.txt)
-#include "../../network_interpretation_imagenet_amd/csrc/mpx_shuffle.h"
+#include "../../network_interpretation_imagenet_amd/csrc/mpx_dw.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -10,7 +10,7 @@
 #include <vector>
 using namespace mpx;
 
-// the one-pixel-per-thread form, as first written for csrc/mpx_shuffle.h
+// the one-pixel-per-thread form, as first written for ShuffleNetV2
 __global__ __launch_bounds__(256) void dwconv3x3_bn_onepixel_kernel(const DwParams p) {
 #pragma clang fp contract(off)
     const unsigned cg = (unsigned)p.pitch >> 3;                     // units per pixel
@@ -103,7 +103,7 @@ int main() {
         CK(hipMemset(y0h, 0xff, nout * 2)); CK(hipMemset(y0l, 0xff, nout * 2)); CK(hipMemset(y1h, 0xee, nout * 2)); CK(hipMemset(y1l, 0xee, nout * 2));
         DwParams p; std::memset(&p, 0, sizeof p);
         p.x_hi = xh; p.x_lo = xl; p.y_hi = y0h; p.y_lo = y0l; p.w = dw; p.scale = ds; p.shift = dt;
-        p.npix = (long long)B * ho * ho; p.hin = hin; p.ho = ho; p.pitch = pitch; p.stride = stride;
+        p.npix = (long long)B * ho * ho; p.rows = (long long)B * ho; p.hin = hin; p.ho = ho; p.pitch = pitch; p.stride = stride;
         const unsigned long long units0 = (unsigned long long)p.npix * (pitch / 8);
         const unsigned grid0 = (unsigned)std::min<unsigned long long>((units0 + 255) / 256, (unsigned long long)cus * 8);
         DwParams q = p;
@@ -122,8 +122,8 @@ int main() {
                 CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
                 if (it >= 0) { best0 = std::min(best0, ms); sum0 += ms; }
                 CK(hipEventRecord(e0, 0));
-                if (stride == 1) hipLaunchKernelGGL(dwconv3x3_bn_kernel<1>, dim3(grid1), dim3(256), 0, 0, q);
-                else hipLaunchKernelGGL(dwconv3x3_bn_kernel<2>, dim3(grid1), dim3(256), 0, 0, q);
+                if (stride == 1) hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 1, false>), dim3(grid1), dim3(256), 0, 0, q);
+                else hipLaunchKernelGGL((dwconv_bn_act_kernel<3, 2, false>), dim3(grid1), dim3(256), 0, 0, q);
                 CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
                 if (it >= 0) { best1 = std::min(best1, ms); sum1 += ms; }
             }

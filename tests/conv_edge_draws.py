@@ -20,6 +20,7 @@ import math
 from collections import namedtuple
 
 import torch
+from gpu_common import merge, split
 
 ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
 GENERIC_TILES = (0, 1, 2, 4, 7)
@@ -260,16 +261,6 @@ def edge_batches(d, tile, num_cus=NUM_CUS, with_res=None, dual=False, limit=8192
 # ------------------------------------------------------------------------------------------------
 # draws
 # ------------------------------------------------------------------------------------------------
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
 def _images(shape, seed, batch, dim):
     """fp32 [batch] + shape, image n from a generator seeded by (seed, n) alone.  dim: an eighth of its pixels is multiplied by 2^-10."""
     out = torch.empty((batch,) + shape)

@@ -10,11 +10,11 @@ reference-style batch-1 fp32 scoring loop of oracle.scorer with this forward in 
 arithmetic is live on the rows the tests score: `layer_scale=1e-6` (any float) replaces every layer scale by that constant, `gelu=False`
 replaces every GELU by ReLU, `ln_map=True` takes each block LayerNorm's statistics over the whole map instead of per pixel.
 """
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-from oracle.scorer import apply_mask, onoff_mask_u8
+import netref
+from netref import cast, e2e_inputs, masked_batch  # noqa: F401  (re-exported: the tests use them through this module)
 
 ARCHS = ("convnext_tiny", "convnext_small")
 DEPTHS = {"convnext_tiny": (3, 3, 9, 3), "convnext_small": (3, 3, 27, 3)}
@@ -25,10 +25,6 @@ MACS = {"convnext_tiny": 4455531264, "convnext_small": 8683712256}
 
 # The rows the end-to-end checks score: (label map, number of mask rows, seed of synth.random_onoff)
 E2E_CASES = (("felz", 3, 11), ("grid", 2, 5))
-
-
-def cast(sd, dtype):
-    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
 
 
 def arch_of(sd):
@@ -110,43 +106,11 @@ def forward(sd, x, trace=None, layer_scale=None, gelu=True, ln_map=False):
     return F.linear(x, sd["classifier.2.weight"], sd["classifier.2.bias"])
 
 
-def masked_batch(x_chw, segments, onoff):
-    """f32[M, 3, 224, 224]: the masked images of the rows of `onoff`, as oracle.scorer stages them."""
-    return torch.from_numpy(np.stack([apply_mask(x_chw, onoff_mask_u8(segments, row)) for row in onoff]))
-
-
 def score_masks_reference_loop(sd, x_chw, segments, onoff, label, return_logits=False):
-    """oracle.scorer.score_masks_reference_loop with the ConvNeXt forward: one batch-1 fp32 forward per mask-vector.
-    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set."""
-    sd = cast(sd, torch.float32)
-    m = onoff.shape[0]
-    score = np.zeros(m, dtype=np.float32)
-    pred = np.zeros(m, dtype=np.int64)
-    rows = []
-    for i in range(m):
-        masked = apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
-        with torch.no_grad():
-            logits = forward(sd, torch.from_numpy(masked[None]))
-            prob = F.softmax(logits, dim=1)
-        score[i], pred[i] = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
-        rows.append(logits.numpy()[0])
-    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
+    """netref.score_masks_reference_loop with the ConvNeXt forward."""
+    return netref.score_masks_reference_loop(forward, sd, x_chw, segments, onoff, label, return_logits)
 
 
 def score_masks_fp64(sd, x_chw, segments, onoff, label, **switches):
-    """The yardstick: the same masks through the fp64 forward.  returns (score f64[M], logits f64[M, 1000])."""
-    sd = cast(sd, torch.float64)
-    with torch.no_grad():
-        logits = torch.cat([forward(sd, masked_batch(x_chw, segments, onoff[i:i + 5]).double(), None, **switches) for i in range(0, onoff.shape[0], 5)])
-        prob = F.softmax(logits, dim=1)
-    return prob[:, label].numpy(), logits.numpy()
-
-
-def e2e_inputs(golden_dir, kind):
-    """(image u8[224,224,3], label map) of an end-to-end case: the felzenszwalb fixture on the `blobs` image, or the 16-pixel grid."""
-    import os
-    from network_interpretation_imagenet_amd import synth
-    if kind == "felz":
-        g = np.load(os.path.join(golden_dir, "felzenszwalb_skimage0183.npz"))
-        return g["blobs224/image"], g["blobs224/labels"].astype(np.int64)
-    return synth.make_images(1)[0], synth.grid_segments().astype(np.int64)
+    """netref.score_masks_fp64 with the ConvNeXt forward, 5 rows at a time."""
+    return netref.score_masks_fp64(forward, sd, x_chw, segments, onoff, label, chunk=5, **switches)

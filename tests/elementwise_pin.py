@@ -7,12 +7,12 @@ case mixes in: -0.0 (in one plane and in both), values above 6, values below -90
 (an all -0.0 window and column), channel 2 one constant pair (ties inside every max window), channel 3 two DIFFERENT pairs of one sum drawn per
 pixel ((2, 0) and (1, 1): a tie that only "the first wins" decides), and the last two channels exact zeros (pad channels; the depthwise
 weights, scale and shift are zero there too).  Batch 3 everywhere, so the last workgroup is partial."""
-import ctypes as C
 import hashlib
 import zlib
 
 import numpy as np
 import torch
+from gpu_common import ptr as _p
 
 BATCH = 3
 EPS = 1e-6
@@ -108,10 +108,6 @@ def inputs_digest():
         for a in inputs(family, case_id, args):
             h.update(a.tobytes())
     return h.hexdigest()
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def run(eng, family, case_id, args):

@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 import resnext_ref as ref
+from gpu_common import merge, split
 
 BN_EPS = 1e-5
 GROUPS = ref.GROUPS
@@ -83,16 +84,6 @@ R_REF = {
 }
 # 4 x r_ref rounded up to a power of two
 C_TOL = {k: 2.0 ** math.ceil(math.log2(4 * v)) for k, v in R_REF.items()}        # 8 where r_ref > 1 (cg 4 and 8, and cg 16 on 32x8d's larger maps), else 4
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
 
 
 def draws(d, batch, seed=None, device=None):

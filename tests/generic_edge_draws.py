@@ -24,6 +24,7 @@ import torch
 
 import conv_edge_draws as ced
 import fused_edge_draws as fed
+from gpu_common import pitch_of
 
 PLANE_BYTES_CAP = 128 << 20                 # hi + lo input and output planes of one case, fences not counted
 R_REF_MAX = 1.499                           # tests/test_generic_bounds_cpu.py: the worst of its 104 cases to three decimals, a stem on the mixed draw
@@ -31,10 +32,6 @@ C_TOL = ced.C_TOL
 
 Spec = namedtuple("Spec", "arch d cin_pad x_pitch x_offset bf hp stored y_pitch y_offset eps affine f32 stem_run")
 Row = namedtuple("Row", "form arch name tiles all_classes")
-
-
-def pitch_of(c):
-    return -(-c // 32) * 32
 
 
 def _spec(arch, name, bn, cin, cout, k, stride, pad, hin, relu, affine="bn", eps=1e-5, cin_pad=None, x_pitch=None, x_offset=0, bf=0, hp=0,

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 import regnet_ref as ref
+from gpu_common import merge, split
 
 BN_EPS = 1e-5
 TILE = 18
@@ -103,16 +104,6 @@ R_REF = {
 }
 # 4 x r_ref rounded up to a power of two
 C_TOL = {k: 2.0 ** math.ceil(math.log2(4 * v)) for k, v in R_REF.items()}
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
 
 
 def draws(d, batch, seed=None, device=None):

@@ -9,12 +9,11 @@ on the rows the tests score: `gate_half=True` replaces every gate by 0.5.
 """
 import math
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
+import netref
 import regnet_ref as xref
-from oracle.scorer import apply_mask, onoff_mask_u8
 from regnet_ref import EPS, STEM, bn, cast, e2e_inputs, masked_batch, pitch  # noqa: F401  (re-exported: the tests use them through this module)
 
 # arch -> (depth, w_0, w_a, w_m, group width) of torchvision's regnet_y_* builders
@@ -130,32 +129,19 @@ def forward(sd, x, arch, trace=None, gate_half=False, gates=None):
     return F.linear(x, sd["fc.weight"], sd["fc.bias"])
 
 
+def bound(arch):
+    """The forward of `arch` as the forward(sd, x, **switches) that netref and the test drivers take."""
+    return netref.bound(forward, arch)
+
+
 def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label, return_logits=False):
-    """oracle.scorer.score_masks_reference_loop with the RegNetY forward: one batch-1 fp32 forward per mask-vector.
-    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set."""
-    sd = cast(sd, torch.float32)
-    m = onoff.shape[0]
-    score = np.zeros(m, dtype=np.float32)
-    pred = np.zeros(m, dtype=np.int64)
-    rows = []
-    for i in range(m):
-        masked = apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
-        with torch.no_grad():
-            logits = forward(sd, torch.from_numpy(masked[None]), arch)
-            prob = F.softmax(logits, dim=1)
-        score[i], pred[i] = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
-        rows.append(logits.numpy()[0])
-    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
+    """netref.score_masks_reference_loop with the RegNetY forward of `arch`."""
+    return netref.score_masks_reference_loop(bound(arch), sd, x_chw, segments, onoff, label, return_logits)
 
 
 def score_masks_fp64(sd, arch, x_chw, segments, onoff, label, gate_half=False):
-    """The yardstick: the same masks through the fp64 forward.  returns (score f64[M], logits f64[M, 1000])."""
-    sd = cast(sd, torch.float64)
-    with torch.no_grad():
-        logits = torch.cat([forward(sd, masked_batch(x_chw, segments, onoff[i:i + 4]).double(), arch, None, gate_half)
-                            for i in range(0, onoff.shape[0], 4)])
-        prob = F.softmax(logits, dim=1)
-    return prob[:, label].numpy(), logits.numpy()
+    """netref.score_masks_fp64 with the RegNetY forward of `arch`, 4 rows at a time."""
+    return netref.score_masks_fp64(bound(arch), sd, x_chw, segments, onoff, label, chunk=4, gate_half=gate_half)
 
 
 _E2E = {}
@@ -164,19 +150,6 @@ _E2E = {}
 def e2e_rows(golden_dir, arch):
     """Per case of E2E_CASES[arch], computed once per process and shared: dict kind -> (img, seg, onoff, label, s64, logits64).  The label is
     the fp64 argmax of the unmasked picture."""
-    from network_interpretation_imagenet_amd import synth
-    from oracle import scorer
     if arch not in _E2E:
-        sd = synth.make_state_dict(arch)
-        sd64 = cast(sd, torch.float64)
-        out = {}
-        for kind, m, seed in E2E_CASES[arch]:
-            img, seg = e2e_inputs(golden_dir, kind)
-            x = scorer.to_tensor_normalize(img)
-            with torch.no_grad():
-                label = int(forward(sd64, x[None].double(), arch).argmax(1)[0])
-            onoff = synth.random_onoff(m, len(np.unique(seg)), seed=seed)
-            s64, logits64 = score_masks_fp64(sd, arch, x, seg, onoff, label)
-            out[kind] = (img, seg, onoff, label, s64, logits64)
-        _E2E[arch] = out
+        _E2E[arch] = netref.e2e_rows(forward, E2E_CASES[arch], golden_dir, arch, chunk=4)
     return _E2E[arch]

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from oracle.scorer import apply_mask, onoff_mask_u8
+import netref
+from netref import cast, e2e_inputs, masked_batch  # noqa: F401  (re-exported: the tests use them through this module)
 
 ARCHS = ("shufflenet_v2_x0_5", "shufflenet_v2_x1_0", "shufflenet_v2_x1_5", "shufflenet_v2_x2_0")
 WIDTHS = {"shufflenet_v2_x0_5": (24, 48, 96, 192, 1024), "shufflenet_v2_x1_0": (24, 116, 232, 464, 1024),
@@ -34,12 +35,8 @@ E2E_CASES = (("felz", 20, 11), ("grid", 8, 5))
 E2E_ARCHS = ("shufflenet_v2_x1_0", "shufflenet_v2_x0_5")
 
 
-def cast(sd, dtype):
-    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
-
-
 def bn(sd, prefix, x):
-    return F.batch_norm(x, sd[prefix + ".running_mean"], sd[prefix + ".running_var"], sd[prefix + ".weight"], sd[prefix + ".bias"], False, 0.0, EPS)
+    return netref.bn(sd, prefix, x, EPS)
 
 
 def channel_shuffle(x, groups=2):
@@ -146,50 +143,20 @@ def forward(sd, arch, x, trace=None):
     return F.linear(x, sd["fc.weight"], sd["fc.bias"])
 
 
-def masked_batch(x_chw, segments, onoff):
-    """f32[M, 3, 224, 224]: the masked images of the rows of `onoff`, as oracle.scorer stages them."""
-    return torch.from_numpy(np.stack([apply_mask(x_chw, onoff_mask_u8(segments, row)) for row in onoff]))
+def bound(arch):
+    """The forward of `arch` as the forward(sd, x) that netref and the test drivers take."""
+    return lambda sd, x: forward(sd, arch, x)
 
 
 def score_masks_reference_loop(sd, arch, x_chw, segments, onoff, label, return_logits=False):
-    """oracle.scorer.score_masks_reference_loop with the ShuffleNetV2 forward: one batch-1 fp32 forward per mask-vector.
-    returns (score f32[M], pred i64[M]), and the fp32 logits f32[M, 1000] behind them when return_logits is set."""
-    sd = cast(sd, torch.float32)
-    m = onoff.shape[0]
-    score = np.zeros(m, dtype=np.float32)
-    pred = np.zeros(m, dtype=np.int64)
-    rows = []
-    for i in range(m):
-        masked = apply_mask(x_chw, onoff_mask_u8(segments, onoff[i]))
-        with torch.no_grad():
-            logits = forward(sd, arch, torch.from_numpy(masked[None]))
-            prob = F.softmax(logits, dim=1)
-        score[i], pred[i] = prob.numpy()[0][label], int(logits.max(1, keepdim=True)[1][0, 0])
-        rows.append(logits.numpy()[0])
-    return (score, pred, np.stack(rows)) if return_logits else (score, pred)
+    """netref.score_masks_reference_loop with the ShuffleNetV2 forward of `arch`."""
+    return netref.score_masks_reference_loop(bound(arch), sd, x_chw, segments, onoff, label, return_logits)
 
 
 def score_masks_fp64(sd, arch, x_chw, segments, onoff, label):
-    """The yardstick: the same masks through the fp64 forward.  returns (score f64[M], logits f64[M, 1000])."""
-    sd = cast(sd, torch.float64)
-    with torch.no_grad():
-        logits = torch.cat([forward(sd, arch, masked_batch(x_chw, segments, onoff[i:i + 8]).double()) for i in range(0, onoff.shape[0], 8)])
-        prob = F.softmax(logits, dim=1)
-    return prob[:, label].numpy(), logits.numpy()
+    """netref.score_masks_fp64 with the ShuffleNetV2 forward of `arch`, 8 rows at a time."""
+    return netref.score_masks_fp64(bound(arch), sd, x_chw, segments, onoff, label, chunk=8)
 
 
 def predict(sd, arch, x_chw):
-    """Unmasked fp32 forward: (argmax, softmax row as f64 numpy)."""
-    with torch.no_grad():
-        logits = forward(cast(sd, torch.float32), arch, x_chw[None])
-    return int(logits.argmax(1)[0]), F.softmax(logits.double(), dim=1)[0].numpy()
-
-
-def e2e_inputs(golden_dir, kind):
-    """(image u8[224,224,3], label map) of an end-to-end case: the felzenszwalb fixture on the `blobs` image, or the 16-pixel grid."""
-    import os
-    from network_interpretation_imagenet_amd import synth
-    if kind == "felz":
-        g = np.load(os.path.join(golden_dir, "felzenszwalb_skimage0183.npz"))
-        return g["blobs224/image"], g["blobs224/labels"].astype(np.int64)
-    return synth.make_images(1)[0], synth.grid_segments().astype(np.int64)
+    return netref.predict(bound(arch), sd, x_chw)

@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import densenet_ref
+import netref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
 
@@ -26,25 +27,20 @@ NEW_SYMBOLS = ("mpx_num_norms", "mpx_norm_info", "mpx_load_norm", "mpx_norm_para
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
-            (prefix + ".num_batches_tracked", ())]
-
-
 def _expected_keys(arch):
     """models.<arch>().state_dict(): key -> shape, in module order, written out from the block tuple."""
-    out = [("features.conv0.weight", (64, 3, 7, 7))] + _bn_keys("features.norm0", 64)
+    out = [("features.conv0.weight", (64, 3, 7, 7))] + netref.bn_keys("features.norm0", 64)
     c = 64
     for b, n in enumerate(BLOCKS[arch], 1):
         for j in range(1, n + 1):
             p = "features.denseblock%d.denselayer%d." % (b, j)
-            out += _bn_keys(p + "norm1", c) + [(p + "conv1.weight", (128, c, 1, 1))] + _bn_keys(p + "norm2", 128) + [(p + "conv2.weight", (32, 128, 3, 3))]
+            out += netref.bn_keys(p + "norm1", c) + [(p + "conv1.weight", (128, c, 1, 1))] + netref.bn_keys(p + "norm2", 128) + [(p + "conv2.weight", (32, 128, 3, 3))]
             c += 32
         if b < 4:
             p = "features.transition%d." % b
-            out += _bn_keys(p + "norm", c) + [(p + "conv.weight", (c // 2, c, 1, 1))]
+            out += netref.bn_keys(p + "norm", c) + [(p + "conv.weight", (c // 2, c, 1, 1))]
             c //= 2
-    return out + _bn_keys("features.norm5", c) + [("classifier.weight", (1000, c)), ("classifier.bias", (1000,))]
+    return out + netref.bn_keys("features.norm5", c) + [("classifier.weight", (1000, c)), ("classifier.bias", (1000,))]
 
 
 @pytest.mark.parametrize("arch", ARCHS)
@@ -91,13 +87,7 @@ def test_densenet_arch_ids_are_unique_and_161_is_not_served():
 
 
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_DENSENET 5000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_DENSENET 5000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     assert mpx_lib.mpx_num_norms(None) == -1
     assert mpx_lib.mpx_concat_bn_relu(None, None, None, 0, 0, None, None, 0, 0, None, None, None, None, 0, 0, None) == -1

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import efficientnet_ref as ref
+import netref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
 
@@ -44,28 +45,23 @@ E2E_BOUND = 2e-5            # the end-to-end bound of tests/test_gpu_efficientne
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
-            (prefix + ".num_batches_tracked", ())]
-
-
 def _expected_keys():
     """models.efficientnet_b0().state_dict(): key -> shape, in module order, written out from the table."""
-    out = [("features.0.0.weight", (32, 3, 3, 3))] + _bn_keys("features.0.1", 32)
+    out = [("features.0.0.weight", (32, 3, 3, 3))] + netref.bn_keys("features.0.1", 32)
     for s, (t, k, _st, cin, cout, n) in enumerate(TABLE):
         for b in range(n):
             e, q = cin * t, max(1, cin // 4)
             p = "features.%d.%d.block." % (s + 1, b)
             j = 0
             if e != cin:
-                out += [(p + "0.0.weight", (e, cin, 1, 1))] + _bn_keys(p + "0.1", e)
+                out += [(p + "0.0.weight", (e, cin, 1, 1))] + netref.bn_keys(p + "0.1", e)
                 j = 1
-            out += [(p + "%d.0.weight" % j, (e, 1, k, k))] + _bn_keys(p + "%d.1" % j, e)
+            out += [(p + "%d.0.weight" % j, (e, 1, k, k))] + netref.bn_keys(p + "%d.1" % j, e)
             se = p + "%d" % (j + 1)
             out += [(se + ".fc1.weight", (q, e, 1, 1)), (se + ".fc1.bias", (q,)), (se + ".fc2.weight", (e, q, 1, 1)), (se + ".fc2.bias", (e,))]
-            out += [(p + "%d.0.weight" % (j + 2), (cout, e, 1, 1))] + _bn_keys(p + "%d.1" % (j + 2), cout)
+            out += [(p + "%d.0.weight" % (j + 2), (cout, e, 1, 1))] + netref.bn_keys(p + "%d.1" % (j + 2), cout)
             cin = cout
-    out += [("features.8.0.weight", (1280, 320, 1, 1))] + _bn_keys("features.8.1", 1280)
+    out += [("features.8.0.weight", (1280, 320, 1, 1))] + netref.bn_keys("features.8.1", 1280)
     return out + [("classifier.1.weight", (1000, 1280)), ("classifier.1.bias", (1000,))]
 
 
@@ -132,13 +128,7 @@ def test_efficientnet_arch_id_is_unique_and_the_neighbours_stay_unsupported():
 
 
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_EFFICIENTNET 10000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_EFFICIENTNET 10000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     se = _lib.SeDesc()
     p = C.c_void_p()

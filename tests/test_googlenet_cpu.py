@@ -4,7 +4,6 @@ restatement (tests/googlenet_ref.py) against an independent nn.Module build, the
 transform_input refusal, and the statistics of the synthetic network on exactly the rows the GPU test scores."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import googlenet_ref
+import netref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
 
@@ -145,13 +145,7 @@ def test_unknown_googlenet_id_is_refused(mpx_lib, arch_id):
 
 
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_GOOGLENET 8000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_GOOGLENET 8000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     assert mpx_lib.mpx_maxpool3x3_clip(None, None, None, None, None, 1, 14, 1, 1, 64, None) == -1
     assert mpx_lib.mpx_num_clip_pools(None) == -1

@@ -14,7 +14,6 @@ SCORE_TOL_TIGHT = 4 x the larger of the first two (2.3e-5), rounded up to one di
     smallest fp64 top-1 - top-2 logit gap 0.0011 (no mask under 1e-3)"""
 import ctypes as C
 import os
-import random
 
 import numpy as np
 import pytest
@@ -22,7 +21,9 @@ import torch
 import torch.nn.functional as F
 
 import alexnet_ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
+from gpu_common import accepted_tiles, dev, FALLBACK, LAYER_TOL, merge, ptr, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_conv_layer, check_position_independence, Reference
+from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
 from logits_lens import LogitsLens
 from oracle import scorer
@@ -30,35 +31,10 @@ from oracle import scorer
 pytestmark = pytest.mark.gpu
 
 ARCH = "alexnet"
-SCORE_TOL = 1e-4
 SCORE_TOL_TIGHT = 3e-5      # from the measurement in the module docstring
-LAYER_TOL = 4e-6            # relative to max(|want|, 1): the tolerance of test_gpu_parity's per-layer sweeps (K <= 4608) ...
-LAYER_TOL_K = 4608          # ... grown with sqrt(K / 4608) beyond, as tests/test_gpu_vgg.py does: classifier.1 has K = 9216
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 CONVS = ["features.0", "features.3", "features.6", "features.8", "features.10", "classifier.1", "classifier.4", "classifier.6"]
 MACS = 714188480
 BATCHES = (5, 197)          # 197 images of a 13x13 map: 131 pixel tiles of 256, more than one persistent round and not a whole number of them
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -113,56 +89,9 @@ def _ref_layer(sd, d, x_nchw64):
     return F.relu(y) if d.relu else y
 
 
-def _run_layer(eng, i, batch, seed):
-    """One mpx_conv_bn_act of layer i on random post-ReLU-like inputs; -> (got, want) as [B][ho][ho][cout] f64 on the device."""
-    d = eng.layers[i]
-    dev = eng.device
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(batch, d.hin, d.hin, d.cin, generator=g).clamp_min(-0.5) * 1.5).to(dev)
-    xh, xl = split(x)
-    if i == 0:      # the first layer reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
-        in_h = in_l = None
-    else:
-        in_h, in_l = xh, xl
-    if i == len(eng.layers) - 1:
-        out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = out.double().view(batch, 1, 1, d.cout)
-    else:
-        oh = torch.full((batch, d.hout, d.hout, d.cout), float("nan"), dtype=torch.float16, device=dev)
-        ol = torch.full_like(oh, float("nan"))
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, _p(oh), _p(ol), None, batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = merge(oh, ol).double()
-    torch.cuda.synchronize()
-    want = _ref_layer(synth.make_state_dict(ARCH), d, merge(xh, xl).double().permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
-    return got, want
-
-
 def _check(eng, i, batch, tile=-1):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
-        got, want = _run_layer(eng, i, batch, seed=1000 * i + batch)
-        ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
-    d = eng.layers[i]
-    name = d.name.decode()
-    assert not torch.isnan(got).any(), name
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    tol = LAYER_TOL * max(1.0, (d.cin * d.ksize * d.ksize / LAYER_TOL_K) ** 0.5)
-    print("%s tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x" % (name, tile, batch, err, scale, tol * max(scale, 1.0), ran))
-    assert err <= tol * max(scale, 1.0), "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran
+    sd = synth.make_state_dict(ARCH)
+    return check_conv_layer(eng, i, batch, lambda d, x64, _r64: _ref_layer(sd, d, x64), tile)[0]
 
 
 @pytest.mark.parametrize("name", CONVS)
@@ -177,11 +106,7 @@ def test_alexnet_every_layer_default_tile(eng, name):
 @pytest.mark.parametrize("name", CONVS)
 def test_alexnet_every_accepted_tile(eng, name):
     i = CONVS.index(name)
-    accepted = []
-    for t in ALL_TILES:
-        if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0:
-            accepted.append(t)
-    eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+    accepted = accepted_tiles(eng, i)
     assert {0, 1, 2, 4, 7} <= set(accepted)
     if name in ("features.6", "features.8", "features.10"):
         assert {6, 12} <= set(accepted)         # the patch kernels take the odd 13x13 maps
@@ -222,7 +147,7 @@ def test_maxpool3x3s2p0_bit_exact(eng, dev, hin, c, batch):
     xh, xl = split(_pool_input(batch, hin, c, hin + c).to(dev))
     oh = torch.full((batch, ho, ho, c), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    rc = eng._lib.mpx_maxpool3x3s2p0(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hin, c, eng._stream())
+    rc = eng._lib.mpx_maxpool3x3s2p0(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hin, c, eng._stream())
     _lib.check(eng._h, rc, "mpx_maxpool3x3s2p0")
     torch.cuda.synchronize()
     want = F.max_pool2d(merge(xh, xl).permute(0, 3, 1, 2), 3, 2).permute(0, 2, 3, 1)
@@ -232,7 +157,7 @@ def test_maxpool3x3s2p0_bit_exact(eng, dev, hin, c, batch):
 
 def test_maxpool3x3s2p0_refuses_bad_shapes(eng, dev):
     z = torch.zeros(64, dtype=torch.float16, device=dev)
-    args = (_p(z), _p(z), _p(z), _p(z))
+    args = (ptr(z), ptr(z), ptr(z), ptr(z))
     assert eng._lib.mpx_maxpool3x3s2p0(eng._h, *args, 1, 1, 8, None) == -1      # hin < 3
     assert eng._lib.mpx_maxpool3x3s2p0(eng._h, *args, 1, 56, 8, None) == -1     # even hin
     assert eng._lib.mpx_maxpool3x3s2p0(eng._h, *args, 1, 55, 12, None) == -1    # c % 8 != 0
@@ -252,7 +177,7 @@ def test_maxpool3x3s2p0_planes_past_2_31_elements(eng, dev):
     oh = torch.full((B, ho, ho, c), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
     try:
-        rc = eng._lib.mpx_maxpool3x3s2p0(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), B, hin, c, eng._stream())
+        rc = eng._lib.mpx_maxpool3x3s2p0(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), B, hin, c, eng._stream())
         _lib.check(eng._h, rc, "mpx_maxpool3x3s2p0")
         torch.cuda.synchronize()
         for lo in list(range(0, B, 1000))[::3] + [B - 100]:         # every third block of 1000 images, and the last images
@@ -281,7 +206,7 @@ def test_first_layer_from_stage_masks(eng, dev, golden_dir, seg_kind, m):
     d = eng.layers[0]
     oh = torch.full((m, 55, 55, 64), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, 0, None, None, None, None, _p(oh), _p(ol), None, m, eng._stream()), "conv")
+    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, 0, None, None, None, None, ptr(oh), ptr(ol), None, m, eng._stream()), "conv")
     torch.cuda.synchronize()
     # the masked normalised images against the CPU staging of oracle.scorer, then the layer against F.conv2d(masked, w, b, 4, 2) + ReLU
     x = scorer.to_tensor_normalize(img)
@@ -335,63 +260,16 @@ def test_alexnet_end_to_end(eng, dev, golden_dir):
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(eng, dev, golden_dir):
-    img, seg = _felz(golden_dir)
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(8, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (37, 41, (0, 5, 36)), (300, 42, (1, 150, 299)), (512, 43, (0, 255, 511)), (700, 44, (3, 511, 512, 699))):
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(eng, *_felz(golden_dir),
+                                (8, ((1, 0, (0,)), (37, 41, (0, 5, 36)), (300, 42, (1, 150, 299)), (512, 43, (0, 255, 511)), (700, 44, (3, 511, 512, 699)))))
 
 
 # ------------------------------------------------------------------------------------------------
 # API and errors
 # ------------------------------------------------------------------------------------------------
-def _score_one(sd32, masked_chw, label):
-    with torch.no_grad():
-        logits = alexnet_ref.forward(sd32, torch.from_numpy(masked_chw[None]))
-    return F.softmax(logits, 1).numpy()[0][label], int(logits.argmax(1)[0])
-
-
 def test_api_on_an_alexnet_engine(eng, dev, golden_dir):
-    sd = synth.make_state_dict(ARCH)
-    sd32 = alexnet_ref.cast(sd, torch.float32)
-    img, seg = _felz(golden_dir)
-    x = scorer.to_tensor_normalize(img)
-    label, _ = alexnet_ref.predict(sd, x)
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    # api.score_masks and the single-process shard paths
-    onoff = synth.random_onoff(24, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = alexnet_ref.score_masks_reference_loop(sd, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_TOL_TIGHT
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    rank_map = rank_segments(seg)[0]
-    heat, n_ok = shard.heatmap_sharded(eng, img, rank_map, onoff, label)
-    want_heat = sum((onoff[i][rank_map] for i in range(24) if pred[i] == label), np.zeros((224, 224)))
-    assert n_ok == int((pred == label).sum()) and np.array_equal(heat.cpu().numpy().astype(np.float64), want_heat.astype(np.float64))
-    # the reference-named entry points
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 3, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want, _ = _score_one(sd32, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_TOL_TIGHT
-    table_s, table_p = api.SaliencySession(eng, x, label, segments=seg).table()
-    assert len(table_s) == S + 1
-    for f in range(0, S + 1, 7):
-        want, want_p = _score_one(sd32, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(table_s[f]) - float(want)) <= SCORE_TOL_TIGHT
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=40, rng=random.Random(3))
-    one = api.validate(list(loader), eng, None, 1, num_mask_samples=40, rng=random.Random(3))
-    assert many == {1: one}
+    ref = Reference(alexnet_ref, synth.make_state_dict(ARCH))
+    check_api(eng, ref, *_felz(golden_dir), rows=24, tol=SCORE_TOL_TIGHT, windows=(0, 3, 9), heatmaps=1, predict=False, table_step=7, validate=40)
 
 
 def test_alexnet_error_paths(eng, mpx_lib, dev):
@@ -406,9 +284,9 @@ def test_alexnet_error_paths(eng, mpx_lib, dev):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(z), _p(z), 1, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(z), ptr(z), 1, None) == -2
     hi, lo = C.c_void_p(1), C.c_void_p(1)
     assert eng._lib.mpx_stem_planes(eng._h, C.byref(hi), C.byref(lo)) == 0 and not hi.value and not lo.value
     for bad in (4001, 4099):

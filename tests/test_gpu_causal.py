@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import dev, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, api, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError
 from oracle import scorer
@@ -23,18 +24,8 @@ SCORE_TOL = 1e-4            # the project's tolerance of a score against the CPU
 MPX_E_ARG, MPX_E_STATE = -1, -2
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _bits(a):
     return np.ascontiguousarray(a).view(np.int32)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

@@ -10,30 +10,19 @@ to tol = C_TOL 2^-22 B + 2^-24 against the fp64 conv + BN (+ residual) (+ ReLU) 
 emulation in tests/test_conv_bounds_cpu.py is where C_TOL comes from), the suite's older max norm of 4e-6 stays as a second assertion,
 pre-activations clearly below zero must be +0 in both planes, and on the pointwise forms image 0 has the same bits alone and as the first
 image of the batch.  Inputs and references are built once per (layer, batch) on the device and shared by the tiles."""
-import ctypes as C
 
 import pytest
 import torch
 
 import conv_edge_draws as ced
+from gpu_common import dev, Fenced, layer_index as _index, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 
 pytestmark = pytest.mark.gpu
 
-F32_SENTINEL_BITS = 0x7fc01234          # an fp32 NaN with a payload no arithmetic produces
 WORST = {}                              # kernel form -> (worst err / tol, where)
 COVERED = {}                            # kernel form -> {(layer, residue class)}
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-@pytest.fixture(scope="module")
-def dev(mpx_lib):
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _engine(arch, sd):
@@ -68,41 +57,6 @@ def trained(dev):
     e = _engine("resnet101", sd)
     yield e, sd
     e.close()
-
-
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
-
-
-class Fenced:
-    """rows x cout elements between two fences of FENCE_ROWS x cout, everything prefilled with the sentinel."""
-
-    def __init__(self, rows, cout, dev, f32=False):
-        self.fence, self.rows, self.cout = ced.FENCE_ROWS * cout, rows, cout
-        self.sentinel = F32_SENTINEL_BITS if f32 else ced.SENTINEL_BITS
-        self.bits = torch.full((2 * self.fence + rows * cout,), self.sentinel, dtype=torch.int32 if f32 else torch.int16, device=dev)
-        self.values = self.bits.view(torch.float32 if f32 else torch.float16)
-
-    @property
-    def payload(self):
-        return self.values[self.fence:self.fence + self.rows * self.cout].view(self.rows, self.cout)
-
-    @property
-    def payload_bits(self):
-        return self.bits[self.fence:self.fence + self.rows * self.cout].view(self.rows, self.cout)
-
-    def problems(self):
-        """What a launch left wrong around and in the payload: [] when the fences are intact and every payload element was written."""
-        out = []
-        front, back = self.bits[:self.fence] != self.sentinel, self.bits[self.fence + self.rows * self.cout:] != self.sentinel
-        if front.any():
-            out.append("front fence: %d elements overwritten, the last at %d before the payload" % (int(front.sum()), self.fence - int(front.nonzero().max())))
-        if back.any():
-            out.append("back fence: %d elements overwritten, the first at %d behind the payload" % (int(back.sum()), int(back.nonzero().min())))
-        left = self.payload_bits == self.sentinel
-        if left.any():
-            out.append("payload: %d elements never written, the first in pixel row %d" % (int(left.sum()), int(left.nonzero()[0, 0])))
-        return out
 
 
 def test_the_fence_check_turns_red(dev):

@@ -9,7 +9,6 @@ sqrt(max(K, 4608) / 4608) of max(|want|, 1), the project's per-layer bound.  End
 SCORE_TOL = 1e-4, every argmax equal, all logits within 4 d_L (tests/logits_lens.py).
 Measured on one MI355X: DESIGN.md 22 has the figures; the tests print them on every run."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -18,49 +17,16 @@ import torch.nn.functional as F
 
 import cnext_draws as draws
 import convnext_ref as ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
+from gpu_common import accepted_tiles, dev, dev_view, FALLBACK, FencedPair, GENERIC, merge, ptr, SCORE_BOUND, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_conv_layer, check_position_independence, Reference
+from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14, 16)
-GENERIC = {0, 1, 2, 4, 7}
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 EPS = 1e-6
-FENCE = 256                 # sentinel rows in front of and behind every output plane
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def dev_view(ptr, n, dev):
-    class _V:
-        __cuda_array_interface__ = {"data": (ptr.value, False), "shape": (n,), "typestr": "<f4", "version": 2}
-    return torch.as_tensor(_V(), device=dev).clone().cpu()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
 @pytest.fixture(scope="module")
 def sds():
     return {a: synth.make_state_dict(a) for a in ref.ARCHS}
@@ -78,27 +44,6 @@ def engines(mpx_lib, dev, sds):
 @pytest.fixture(scope="module")
 def tiny(engines):
     return engines["convnext_tiny"]
-
-
-class Fenced:
-    """A pair of output planes of `rows` x `c` elements with FENCE sentinel rows in front of and behind each."""
-
-    def __init__(self, rows, c, dev):
-        self.rows, self.c = rows, c
-        self.hi = torch.full(((rows + 2 * FENCE) * c,), float("nan"), dtype=torch.float16, device=dev)
-        self.lo = torch.full_like(self.hi, float("nan"))
-
-    def ptrs(self):
-        off = FENCE * self.c * 2
-        return C.c_void_p(self.hi.data_ptr() + off), C.c_void_p(self.lo.data_ptr() + off)
-
-    def result(self):
-        torch.cuda.synchronize()
-        a, b = FENCE * self.c, (FENCE + self.rows) * self.c
-        for t in (self.hi, self.lo):
-            assert torch.isnan(t[:a]).all() and torch.isnan(t[b:]).all(), "a sentinel row was written"
-        assert not torch.isnan(self.hi[a:b]).any() and not torch.isnan(self.lo[a:b]).any()
-        return self.hi[a:b].clone(), self.lo[a:b].clone()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -175,10 +120,10 @@ def _dw_run(eng, x, w, bias, gamma, beta, dev, max_blocks=0):
     batch, hin, _, c = x.shape
     xh, xl = split(x.to(dev))
     wt = w.reshape(c, 49).t().contiguous().to(dev)
-    out = Fenced(batch * hin * hin, c, dev)
+    out = FencedPair(batch * hin * hin, c, dev)
     oh, ol = out.ptrs()
     vec = [t.contiguous().to(dev) for t in (bias, gamma, beta)]
-    rc = eng._lib.mpx_dwconv7x7_ln(eng._h, _p(xh), _p(xl), _p(wt), _p(vec[0]), _p(vec[1]), _p(vec[2]), EPS, oh, ol, batch, hin, c, 7, 1, max_blocks, eng._stream())
+    rc = eng._lib.mpx_dwconv7x7_ln(eng._h, ptr(xh), ptr(xl), ptr(wt), ptr(vec[0]), ptr(vec[1]), ptr(vec[2]), EPS, oh, ol, batch, hin, c, 7, 1, max_blocks, eng._stream())
     _lib.check(eng._h, rc, "mpx_dwconv7x7_ln")
     yh, yl = out.result()
     return yh.view(batch, hin, hin, c), yl.view(batch, hin, hin, c)
@@ -220,9 +165,9 @@ def test_dwconv7x7_ln_with_engine_layer_parameters(tiny, dev, sds):
     assert torch.equal(dev_view(pt, 384, dev), sd[lnn + ".bias"])
     x = draws.planes((2, 14, 14, 384), seed=5)
     xh, xl = split(x.to(dev))
-    out = Fenced(2 * 14 * 14, 384, dev)
+    out = FencedPair(2 * 14 * 14, 384, dev)
     oh, ol = out.ptrs()
-    rc = eng._lib.mpx_dwconv7x7_ln(eng._h, _p(xh), _p(xl), pw, pb, ps, pt, EPS, oh, ol, 2, 14, 384, 7, 1, 0, eng._stream())
+    rc = eng._lib.mpx_dwconv7x7_ln(eng._h, ptr(xh), ptr(xl), pw, pb, ps, pt, EPS, oh, ol, 2, 14, 384, 7, 1, 0, eng._stream())
     _lib.check(eng._h, rc, "mpx_dwconv7x7_ln")
     yh, yl = out.result()
     v64, bv64 = draws.dw_v(x, w, sd[name + ".bias"], torch.float64)
@@ -237,7 +182,7 @@ def test_dwconv7x7_ln_refuses_bad_arguments(tiny, engines, dev, mpx_lib):
     eng = tiny
     z = torch.zeros(8192, dtype=torch.float16, device=dev)
     f = torch.zeros(4096, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     call = eng._lib.mpx_dwconv7x7_ln
     assert call(eng._h, a, a, b, b, b, b, EPS, a, a, 1, 4, 16, 7, 1, 0, None) == 0
     torch.cuda.synchronize()
@@ -276,10 +221,10 @@ def test_dwconv7x7_ln_refuses_bad_arguments(tiny, engines, dev, mpx_lib):
 def _ln_run(eng, x, gamma, beta, dev, max_blocks=0):
     rows, c = x.shape
     xh, xl = split(x.to(dev))
-    out = Fenced(rows, c, dev)
+    out = FencedPair(rows, c, dev)
     oh, ol = out.ptrs()
     g, b = gamma.contiguous().to(dev), beta.contiguous().to(dev)
-    rc = eng._lib.mpx_layernorm_c(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, rows, c, max_blocks, eng._stream())
+    rc = eng._lib.mpx_layernorm_c(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, rows, c, max_blocks, eng._stream())
     _lib.check(eng._h, rc, "mpx_layernorm_c")
     yh, yl = out.result()
     return yh.view(rows, c), yl.view(rows, c)
@@ -309,10 +254,10 @@ def test_global_avgpool_ln_against_fp64(tiny, dev, hw, c, batch):
     x = draws.planes((batch, hw, c), seed=hw + c)
     gamma, beta = draws.ln_params(c, seed=3 * hw + c)
     xh, xl = split(x.to(dev))
-    out = Fenced(batch, c, dev)
+    out = FencedPair(batch, c, dev)
     oh, ol = out.ptrs()
     g, b = gamma.to(dev), beta.to(dev)
-    rc = eng._lib.mpx_global_avgpool_ln(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, batch, hw, c, eng._stream())
+    rc = eng._lib.mpx_global_avgpool_ln(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, batch, hw, c, eng._stream())
     _lib.check(eng._h, rc, "mpx_global_avgpool_ln")
     yh, yl = out.result()
     want, mag, var = draws.ln_want(x.double().mean(1), draws.pool_bv(x.double()), gamma, beta)
@@ -321,17 +266,17 @@ def test_global_avgpool_ln_against_fp64(tiny, dev, hw, c, batch):
     print("pooled LayerNorm hw %d x %d batch %d: worst err / bound %.3f (C_f %g)" % (hw, c, batch, worst, draws.C_F["pool", hw, c]))
     assert worst <= 1.0
     if batch == 2:          # the second image alone
-        out1 = Fenced(1, c, dev)
+        out1 = FencedPair(1, c, dev)
         o1h, o1l = out1.ptrs()
-        rc = eng._lib.mpx_global_avgpool_ln(eng._h, _p(xh[1:].contiguous()), _p(xl[1:].contiguous()), _p(g), _p(b), EPS, o1h, o1l, 1, hw, c, eng._stream())
+        rc = eng._lib.mpx_global_avgpool_ln(eng._h, ptr(xh[1:].contiguous()), ptr(xl[1:].contiguous()), ptr(g), ptr(b), EPS, o1h, o1l, 1, hw, c, eng._stream())
         _lib.check(eng._h, rc, "mpx_global_avgpool_ln")
         ah, al = out1.result()
         assert torch.equal(ah.view(torch.int16), yh[c:].view(torch.int16)) and torch.equal(al.view(torch.int16), yl[c:].view(torch.int16))
     call = eng._lib.mpx_global_avgpool_ln
-    assert call(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, batch, hw, c + 4, None) == -1
-    assert call(eng._h, _p(xh), _p(xl), None, _p(b), EPS, oh, ol, batch, hw, c, None) == -1
-    assert eng._lib.mpx_layernorm_c(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, 0, c, 0, None) == -1
-    assert eng._lib.mpx_layernorm_c(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, 1, 12, 0, None) == -1
+    assert call(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, batch, hw, c + 4, None) == -1
+    assert call(eng._h, ptr(xh), ptr(xl), None, ptr(b), EPS, oh, ol, batch, hw, c, None) == -1
+    assert eng._lib.mpx_layernorm_c(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, 0, c, 0, None) == -1
+    assert eng._lib.mpx_layernorm_c(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, 1, 12, 0, None) == -1
 
 
 # ------------------------------------------------------------------------------------------------
@@ -349,62 +294,14 @@ def _ref_layer(sd, d, act, x64, r64, shift=0.0):
     return y + r64 if r64 is not None else y
 
 
-def _run_layer(eng, sd, i, batch, seed):
-    d = eng.layers[i]
-    dev = eng.device
-    g = torch.Generator().manual_seed(seed)
-    last = i == len(eng.layers) - 1
-    x = torch.randn(batch, d.hin, d.hin, d.cin, generator=g) * 1.5
-    xh, xl = split(x.to(dev))
-    rh = rl = None
-    if d.residual:
-        rh, rl = split(torch.randn(batch, d.hout, d.hout, d.cout, generator=g).to(dev))
-    if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
-        in_h = in_l = None
-    else:
-        in_h, in_l = xh, xl
-    if last:
-        out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        torch.cuda.synchronize()
-        got = out.cpu().double().view(batch, 1, 1, d.cout)
-    else:
-        fo = Fenced(batch * d.hout * d.hout, d.cout, dev)
-        oh, ol = fo.ptrs()
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(rh), _p(rl), oh, ol, None, batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        yh, yl = fo.result()
-        got = merge(yh, yl).cpu().double().view(batch, d.hout, d.hout, d.cout)
-    x64 = merge(xh, xl).cpu().double().permute(0, 3, 1, 2)
-    r64 = merge(rh, rl).cpu().double().permute(0, 3, 1, 2) if d.residual else None
-    return got, x64, r64
-
-
 def _check(eng, sd, i, batch, tile=-1, shift=0.0):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
-        got, x64, r64 = _run_layer(eng, sd, i, batch, seed=1000 * i + batch)
-        ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
-    d = eng.layers[i]
-    want = _ref_layer(sd, d, eng.epilogue_acts[i], x64, r64, shift).permute(0, 2, 3, 1)
-    name = d.name.decode()
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d.k_packed, 4608) / 4608) * max(scale, 1.0)
-    print("%s %d->%d k%d h%d K %d res %d act %d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-          % (name, d.cin, d.cout, d.ksize, d.hin, d.k_packed, d.residual, eng.epilogue_acts[i], tile, batch, err, scale, bound, ran))
-    assert err <= bound, "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran, want
+    """-> (kernel mask, want); the fp64 reference is computed on the host."""
+    d, act = eng.layers[i], eng.epilogue_acts[i]
+    fields = "%d->%d k%d h%d K %d res %d act %d " % (d.cin, d.cout, d.ksize, d.hin, d.k_packed, d.residual, act)
+
+    def ref_layer(d, x64, r64):
+        return _ref_layer(sd, d, act, x64.cpu(), None if r64 is None else r64.cpu(), shift)
+    return check_conv_layer(eng, i, batch, ref_layer, tile, clamp=False, fenced=True, fields=fields)
 
 
 def test_gelu_epilogue_on_every_generic_tile_and_the_refusals(tiny, sds):
@@ -415,7 +312,7 @@ def test_gelu_epilogue_on_every_generic_tile_and_the_refusals(tiny, sds):
     for s in (1, 3, 5, 7):
         i = names.index("features.%d.0.block.3" % s)
         assert eng.epilogue_acts[i] == 1
-        accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
+        accepted = accepted_tiles(eng, i)
         assert set(accepted) == GENERIC, (names[i], accepted)
         for t in (6, 9, 10, 12, 13, 14):
             assert eng._lib.mpx_set_conv_tile(eng._h, i, t) == -1
@@ -460,8 +357,7 @@ def test_every_other_distinct_conv_shape_on_every_accepted_tile(tiny, sds):
         if key in seen or eng.epilogue_acts[i]:
             continue
         seen.add(key)
-        accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+        accepted = accepted_tiles(eng, i)
         assert eng._lib.mpx_get_conv_tile(eng._h, i) in accepted and GENERIC <= set(accepted), (d.name, accepted)
         if not (d.ksize == 1 and d.cout % 256 == 0 and i != len(eng.layers) - 1):
             assert set(accepted) == GENERIC, (d.name, accepted)
@@ -515,48 +411,12 @@ def test_convnext_end_to_end(engines, sds, golden_dir, arch):
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(tiny, golden_dir):
-    eng = tiny
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(3, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12))):       # 13 rows: two forwards of an 8-slot engine
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(tiny, *ref.e2e_inputs(golden_dir, "felz"), (3, ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12)))))
 
 
 def test_api_on_a_convnext_engine(tiny, sds, golden_dir):
-    eng, sd = tiny, sds["convnext_tiny"]
-    sd32 = ref.cast(sd, torch.float32)
-
-    def score_one(masked_chw, label):
-        with torch.no_grad():
-            logits = ref.forward(sd32, torch.from_numpy(masked_chw[None]))
-        return F.softmax(logits, 1).numpy()[0][label]
-
-    img, seg = ref.e2e_inputs(golden_dir, "grid")
-    x = scorer.to_tensor_normalize(img)
-    with torch.no_grad():
-        label = int(ref.forward(sd32, x[None]).argmax(1)[0])
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(4, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND and (pred == ref_pred).all()
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want = score_one(scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
+    check_api(tiny, Reference(ref, sds["convnext_tiny"]), *ref.e2e_inputs(golden_dir, "grid"),
+              rows=4, same_pred=True, heatmaps=0, predict=False, table_step=None, validate=None)
 
 
 def test_profile_lists_the_layernorm_launches(tiny, dev):
@@ -585,10 +445,10 @@ def test_convnext_error_paths(tiny, mpx_lib, dev, sds):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     buf = torch.zeros(64, dtype=torch.float16, device=dev)
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(buf), _p(buf), 1, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(buf), ptr(buf), 1, None) == -2
     for bad in (12000, 12003, 12999):
         h = C.c_void_p()
         assert mpx_lib.mpx_create(bad, 2, 0, C.byref(h)) == -1 and not h.value
@@ -608,14 +468,14 @@ def test_convnext_error_paths(tiny, mpx_lib, dev, sds):
         labels = torch.zeros(1, dtype=torch.int32, device=dev)
         score = torch.zeros(1, device=dev)
         pred = torch.zeros(1, dtype=torch.int32, device=dev)
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == -2       # missing LayerNorms
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == -2       # missing LayerNorms
         with pytest.raises((KeyError, ValueError)):     # another family's state_dict: features.0.0.weight has another shape
             fresh.load_state_dict(synth.make_state_dict("mobilenet_v2"))
         for k, d in enumerate(fresh.lnorms):
             n = d.name.decode()
             assert fresh._lib.mpx_load_lnorm(fresh._h, k, C.c_void_p(sd[n + ".weight"].data_ptr()), C.c_void_p(sd[n + ".bias"].data_ptr()), EPS) == 0
         assert fresh._lib.mpx_weights_complete(fresh._h) == 1
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == 0
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == 0
         torch.cuda.synchronize()
     finally:
         fresh.close()

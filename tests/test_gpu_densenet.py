@@ -18,7 +18,6 @@ felzenszwalb / grid; the fp32-loop-versus-fp64 distance is the yardstick:
     densenet169     2.8e-07 / 5.2e-07     2.0e-07 / 1.8e-07        4.0e-07 / 6.8e-07          0.37 / 0.13
     densenet201     2.2e-07 / 2.7e-07     2.3e-07 / 1.4e-07        1.6e-07 / 3.8e-07          0.0049 / 0.012"""
 import ctypes as C
-import random
 
 import numpy as np
 import pytest
@@ -26,8 +25,10 @@ import torch
 import torch.nn.functional as F
 
 import densenet_ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
-from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
+from gpu_common import accepted_tiles, dev, FALLBACK, merge, ptr, SCORE_BOUND, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_conv_layer, check_position_independence, Reference
+from network_interpretation_imagenet_amd import _lib, synth
+from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from logits_lens import LogitsLens
 from oracle import scorer
 
@@ -35,32 +36,7 @@ pytestmark = pytest.mark.gpu
 
 ARCHS = ("densenet121", "densenet169", "densenet201")
 MACS = {"densenet121": 2834161664, "densenet169": 3359843328, "densenet201": 4291365888}
-SCORE_TOL = 1e-4            # the project's tolerance on a score
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1): the per-layer bound (every K here is <= 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 EPS = 1e-5
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -153,55 +129,10 @@ def _ref_layer(sd, d, x_nchw64):
     return F.relu(y) if d.relu else y
 
 
-def _run_layer(eng, sd, i, batch, seed):
-    d = eng.layers[i]
-    dev = eng.device
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(batch, d.hin, d.hin, d.cin, generator=g).clamp_min(-0.5) * 1.5).to(dev)
-    xh, xl = split(x)
-    if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
-        in_h = in_l = None
-    else:
-        in_h, in_l = xh, xl
-    if i == len(eng.layers) - 1:
-        out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = out.double().view(batch, 1, 1, d.cout)
-    else:
-        oh = torch.full((batch, d.hout, d.hout, d.cout), float("nan"), dtype=torch.float16, device=dev)
-        ol = torch.full_like(oh, float("nan"))
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, _p(oh), _p(ol), None, batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = merge(oh, ol).double()
-    torch.cuda.synchronize()
-    want = _ref_layer(sd, d, merge(xh, xl).double().permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
-    return got, want
-
-
 def _check(eng, sd, i, batch, tile=-1):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
-        got, want = _run_layer(eng, sd, i, batch, seed=1000 * i + batch)
-        ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
     d = eng.layers[i]
-    name = d.name.decode()
-    assert not torch.isnan(got).any(), name
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    print("%s %d->%d k%d h%d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-          % (name, d.cin, d.cout, d.ksize, d.hin, tile, batch, err, scale, LAYER_TOL * max(scale, 1.0), ran))
-    assert err <= LAYER_TOL * max(scale, 1.0), "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran
+    fields = "%d->%d k%d h%d " % (d.cin, d.cout, d.ksize, d.hin)
+    return check_conv_layer(eng, i, batch, lambda d, x64, _r64: _ref_layer(sd, d, x64), tile, fields=fields)[0]
 
 
 def _distinct_shapes(eng, seen):
@@ -234,8 +165,7 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engines):
         for i in _distinct_shapes(eng, seen):
             d = eng.layers[i]
             default = eng._lib.mpx_get_conv_tile(eng._h, i)
-            accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-            eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+            accepted = accepted_tiles(eng, i)
             assert default in accepted and {0, 1, 2, 4, 7} <= set(accepted), (d.name, accepted)
             small, large = _layer_batches(d)
             for t in accepted:
@@ -313,7 +243,7 @@ def test_concat_append_bn_relu(small_engines, dev, hw, batch, c_old, g, c_total,
     ol = torch.full_like(oh, float("nan"))
     k, (gamma, beta, mean, var), sc, sh = _load_norm(eng, c, seed=c)
     try:
-        rc = eng._lib.mpx_concat_bn_relu(eng._h, _p(fh), _p(fl), g, fstride, _p(rh), _p(rl), c_total, c_old, sc, sh, _p(oh), _p(ol), c, npix, eng._stream())
+        rc = eng._lib.mpx_concat_bn_relu(eng._h, ptr(fh), ptr(fl), g, fstride, ptr(rh), ptr(rl), c_total, c_old, sc, sh, ptr(oh), ptr(ol), c, npix, eng._stream())
         _lib.check(eng._h, rc, "mpx_concat_bn_relu")
         torch.cuda.synchronize()
         # the append: bit for bit, and nothing else of the concatenation touched
@@ -330,8 +260,8 @@ def test_concat_append_bn_relu(small_engines, dev, hw, batch, c_old, g, c_total,
         rh2, rl2 = rh0.clone(), rl0.clone()
         oh2 = torch.full_like(oh, float("nan"))
         ol2 = torch.full_like(oh, float("nan"))
-        assert eng._lib.mpx_concat_bn_relu(eng._h, _p(fh), _p(fl), g, fstride, _p(rh2), _p(rl2), c_total, c_old, None, None, None, None, 0, npix, eng._stream()) == 0
-        assert eng._lib.mpx_concat_bn_relu(eng._h, None, None, 0, 0, _p(rh2), _p(rl2), c_total, 0, sc, sh, _p(oh2), _p(ol2), c, npix, eng._stream()) == 0
+        assert eng._lib.mpx_concat_bn_relu(eng._h, ptr(fh), ptr(fl), g, fstride, ptr(rh2), ptr(rl2), c_total, c_old, None, None, None, None, 0, npix, eng._stream()) == 0
+        assert eng._lib.mpx_concat_bn_relu(eng._h, None, None, 0, 0, ptr(rh2), ptr(rl2), c_total, 0, sc, sh, ptr(oh2), ptr(ol2), c, npix, eng._stream()) == 0
         torch.cuda.synchronize()
         assert torch.equal(rh2.view(torch.int16), rh.view(torch.int16)) and torch.equal(rl2.view(torch.int16), rl.view(torch.int16))
         assert torch.equal(oh2[: npix * c].view(torch.int16), oh[: npix * c].view(torch.int16)) and torch.equal(ol2[: npix * c].view(torch.int16), ol[: npix * c].view(torch.int16))
@@ -345,19 +275,19 @@ def test_concat_append_bn_relu_refuses_bad_arguments(small_engines, dev):
     eng = small_engines("densenet121")
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
     f = torch.zeros(1024, dtype=torch.float32, device=dev)
-    a = _p(z)
+    a = ptr(z)
     call = eng._lib.mpx_concat_bn_relu
-    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, _p(f), _p(f), a, a, 64, 4, None) == 0
+    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, ptr(f), ptr(f), a, a, 64, 4, None) == 0
     torch.cuda.synchronize()
-    assert call(eng._h, a, a, 32, 32, None, None, 64, 32, _p(f), _p(f), a, a, 64, 4, None) == -1        # no raw planes
-    assert call(eng._h, a, a, 12, 32, a, a, 64, 32, _p(f), _p(f), a, a, 44, 4, None) == -1              # g % 8
-    assert call(eng._h, a, a, 32, 32, a, a, 64, 48, _p(f), _p(f), a, a, 80, 4, None) == -1              # c_old + g > c_total
-    assert call(eng._h, a, a, 32, 16, a, a, 64, 32, _p(f), _p(f), a, a, 64, 4, None) == -1              # fresh_stride < g
-    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, _p(f), _p(f), a, a, 32, 4, None) == -1              # c_norm != c_old + g
+    assert call(eng._h, a, a, 32, 32, None, None, 64, 32, ptr(f), ptr(f), a, a, 64, 4, None) == -1        # no raw planes
+    assert call(eng._h, a, a, 12, 32, a, a, 64, 32, ptr(f), ptr(f), a, a, 44, 4, None) == -1              # g % 8
+    assert call(eng._h, a, a, 32, 32, a, a, 64, 48, ptr(f), ptr(f), a, a, 80, 4, None) == -1              # c_old + g > c_total
+    assert call(eng._h, a, a, 32, 16, a, a, 64, 32, ptr(f), ptr(f), a, a, 64, 4, None) == -1              # fresh_stride < g
+    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, ptr(f), ptr(f), a, a, 32, 4, None) == -1              # c_norm != c_old + g
     assert call(eng._h, a, a, 32, 32, a, a, 64, 32, None, None, a, a, 64, 4, None) == -1                # out planes without scale / shift
-    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, _p(f), _p(f), a, a, 64, 0, None) == -1              # no pixels
+    assert call(eng._h, a, a, 32, 32, a, a, 64, 32, ptr(f), ptr(f), a, a, 64, 0, None) == -1              # no pixels
     assert call(eng._h, None, None, 0, 0, a, a, 64, 0, None, None, None, None, 0, 4, None) == -1        # nothing to do
-    assert call(eng._h, C.c_void_p(z.data_ptr() + 2), a, 32, 32, a, a, 64, 32, _p(f), _p(f), a, a, 64, 4, None) == -1      # misaligned
+    assert call(eng._h, C.c_void_p(z.data_ptr() + 2), a, 32, 32, a, a, 64, 32, ptr(f), ptr(f), a, a, 64, 4, None) == -1      # misaligned
 
 
 def test_concat_append_bn_relu_planes_past_2_31_elements(small_engines, dev):
@@ -381,7 +311,7 @@ def test_concat_append_bn_relu_planes_past_2_31_elements(small_engines, dev):
     k, (gamma, beta, mean, var), sc, sh = _load_norm(eng, c_total, seed=1)
     try:
         tail_h, tail_l = rh[-1000:, :c_old].clone(), rl[-1000:, :c_old].clone()
-        rc = eng._lib.mpx_concat_bn_relu(eng._h, _p(fh), _p(fl), g, g, _p(rh), _p(rl), c_total, c_old, sc, sh, _p(oh), _p(ol), c_total, npix, eng._stream())
+        rc = eng._lib.mpx_concat_bn_relu(eng._h, ptr(fh), ptr(fl), g, g, ptr(rh), ptr(rl), c_total, c_old, sc, sh, ptr(oh), ptr(ol), c_total, npix, eng._stream())
         _lib.check(eng._h, rc, "mpx_concat_bn_relu")
         torch.cuda.synchronize()
         assert torch.equal(rh[:, c_old:].view(torch.int16), fh.view(torch.int16)) and torch.equal(rl[:, c_old:].view(torch.int16), fl.view(torch.int16))
@@ -410,7 +340,7 @@ def test_avgpool2x2s2_against_fp64(small_engines, dev, hin, c, batch):
     xh, xl = split(x.to(dev))
     oh = torch.full((batch, ho, ho, c), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    _lib.check(eng._h, eng._lib.mpx_avgpool2x2s2(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hin, c, eng._stream()), "mpx_avgpool2x2s2")
+    _lib.check(eng._h, eng._lib.mpx_avgpool2x2s2(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hin, c, eng._stream()), "mpx_avgpool2x2s2")
     torch.cuda.synchronize()
     x64 = merge(xh, xl).double().permute(0, 3, 1, 2)
     want = F.avg_pool2d(x64, 2, 2).permute(0, 2, 3, 1)
@@ -424,7 +354,7 @@ def test_avgpool2x2s2_against_fp64(small_engines, dev, hin, c, batch):
 def test_avgpool2x2s2_refuses_bad_shapes(small_engines, dev):
     eng = small_engines("densenet121")
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
-    args = (_p(z), _p(z), _p(z), _p(z))
+    args = (ptr(z), ptr(z), ptr(z), ptr(z))
     assert eng._lib.mpx_avgpool2x2s2(eng._h, *args, 1, 7, 8, None) == -1       # odd
     assert eng._lib.mpx_avgpool2x2s2(eng._h, *args, 1, 0, 8, None) == -1       # zero extent
     assert eng._lib.mpx_avgpool2x2s2(eng._h, *args, 0, 8, 8, None) == -1       # empty batch
@@ -482,65 +412,16 @@ def eng121(mpx_lib, dev):
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(eng121, golden_dir):
-    eng = eng121
-    img, seg = densenet_ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(8, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (37, 41, (0, 5, 36)), (512, 43, (0, 255, 511)), (700, 44, (3, 511, 512, 699))):
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(eng121, *densenet_ref.e2e_inputs(golden_dir, "felz"),
+                                (8, ((1, 0, (0,)), (37, 41, (0, 5, 36)), (512, 43, (0, 255, 511)), (700, 44, (3, 511, 512, 699)))))
 
 
 # ------------------------------------------------------------------------------------------------
 # API and errors
 # ------------------------------------------------------------------------------------------------
-def _score_one(sd32, arch, masked_chw, label):
-    with torch.no_grad():
-        logits = densenet_ref.forward(sd32, arch, torch.from_numpy(masked_chw[None]))
-    return F.softmax(logits, 1).numpy()[0][label], int(logits.argmax(1)[0])
-
-
 def test_api_on_a_densenet_engine(eng121, golden_dir):
-    eng, arch = eng121, "densenet121"
-    sd = synth.make_state_dict(arch)
-    sd32 = densenet_ref.cast(sd, torch.float32)
-    img, seg = densenet_ref.e2e_inputs(golden_dir, "felz")
-    x = scorer.to_tensor_normalize(img)
-    label, _ = densenet_ref.predict(sd, arch, x)
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(12, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = densenet_ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    rank_map = rank_segments(seg)[0]
-    heat, n_ok = shard.heatmap_sharded(eng, img, rank_map, onoff, label)
-    want_heat = sum((onoff[i][rank_map] for i in range(12) if pred[i] == label), np.zeros((224, 224)))
-    assert n_ok == int((pred == label).sum()) and np.array_equal(heat.cpu().numpy().astype(np.float64), want_heat.astype(np.float64))
-    assert np.array_equal(eng.heatmap(rank_map, onoff, pred, label), want_heat.astype(np.float64))
-    # the reference-named entry points
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want, _ = _score_one(sd32, arch, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
-    table_s, table_p = api.SaliencySession(eng, x, label, segments=seg).table()
-    assert len(table_s) == S + 1
-    for f in range(0, S + 1, 11):
-        want, want_p = _score_one(sd32, arch, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(table_s[f]) - float(want)) <= SCORE_BOUND
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=20, rng=random.Random(3))
-    one = api.validate(list(loader), eng, None, 1, num_mask_samples=20, rng=random.Random(3))
-    assert many == {1: one}
+    ref = Reference(densenet_ref, synth.make_state_dict("densenet121"), "densenet121")
+    check_api(eng121, ref, *densenet_ref.e2e_inputs(golden_dir, "felz"), predict=False)
 
 
 def test_profile_lists_the_new_ops(eng121, dev):
@@ -571,8 +452,8 @@ def test_densenet_error_paths(small_engines, mpx_lib, dev):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     for bad in (5000, 5161, 5122, 5999):
         h = C.c_void_p()
         assert mpx_lib.mpx_create(bad, 2, 0, C.byref(h)) == -1 and not h.value
@@ -592,7 +473,7 @@ def test_densenet_error_paths(small_engines, mpx_lib, dev):
         labels = torch.zeros(1, dtype=torch.int32, device=dev)
         score = torch.zeros(1, device=dev)
         pred = torch.zeros(1, dtype=torch.int32, device=dev)
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == -2
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == -2
         with pytest.raises(KeyError):
             fresh.load_state_dict(synth.make_state_dict("resnet18"))
         with pytest.raises((KeyError, ValueError)):

@@ -7,29 +7,15 @@ kernel must reproduce (same order of summation, same epilogue arithmetic).
 
 Tolerance of the fp64 comparison: the project's 4e-6 x max(|want|, 1) of test_conv_with_fused_downsample (split-fp16 operands, 22-bit
 products, fp32 accumulation over K <= 1536)."""
-import ctypes as C
 
 import pytest
 import torch
 
+from gpu_common import layer_index as _index, merge, ptr as _p, split
 from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
 
 
 @pytest.fixture(scope="module")
@@ -38,10 +24,6 @@ def eng101(mpx_lib):
     e = MaskedForwardEngine("resnet101", max_batch=8, device=0).load_state_dict(synth.make_state_dict("resnet101"))
     yield e
     e.close()
-
-
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
 
 
 def _inputs(eng, stage, batch):

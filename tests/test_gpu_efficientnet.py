@@ -30,64 +30,27 @@ d, the fp32 batch-1 CPU loop against fp64 (rows of efficientnet_ref.E2E_CASES: 2
 engine vs fp32 CPU loop 1.5e-06 / 2.1e-07.  The test prints every figure on every run."""
 import ctypes as C
 import math
-import random
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import efficientnet_ref as ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
-from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
-from logits_lens import LogitsLens
+from gpu_common import accepted_tiles, dev, dev_view, FALLBACK, GENERIC, merge, pitch_of, ptr, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_conv_layer, check_end_to_end, check_position_independence, e2e_rows, Reference
+from network_interpretation_imagenet_amd import _lib, synth
+from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
 ARCH = "efficientnet_b0"
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 EPS = 1e-5
 U = 2.0 ** -24
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def pitch_of(c):
-    return -(-c // 32) * 32
-
-
 def silu64(x):
     return x / (1.0 + torch.exp(-x))
-
-
-def dev_view(ptr, n, dev):
-    class _V:
-        __cuda_array_interface__ = {"data": (ptr.value, False), "shape": (n,), "typestr": "<f4", "version": 2}
-    return torch.as_tensor(_V(), device=dev).clone().cpu()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -204,7 +167,7 @@ def _dw_run(eng, xh, xl, wt, sc, sh, pitch, hin, k, stride, act_in, act_out):
     n_out = batch * ho * ho * pitch
     oh = torch.full((n_out + 64,), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    rc = eng._lib.mpx_dwconv_bn_act(eng._h, _p(xh), _p(xl), _p(wt), _p(sc), _p(sh), _p(oh), _p(ol), batch, hin, pitch, k, stride, act_in, act_out, eng._stream())
+    rc = eng._lib.mpx_dwconv_bn_act(eng._h, ptr(xh), ptr(xl), ptr(wt), ptr(sc), ptr(sh), ptr(oh), ptr(ol), batch, hin, pitch, k, stride, act_in, act_out, eng._stream())
     _lib.check(eng._h, rc, "mpx_dwconv_bn_act")
     torch.cuda.synchronize()
     assert torch.isnan(oh[n_out:]).all() and torch.isnan(ol[n_out:]).all()              # the neighbours behind the planes are untouched
@@ -312,7 +275,7 @@ def test_depthwise_refuses_bad_arguments(small_engine, dev):
     eng = small_engine
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
     f = torch.zeros(1024, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     call = eng._lib.mpx_dwconv_bn_act
     assert call(eng._h, a, a, b, b, b, a, a, 1, 4, 8, 5, 1, 1, 1, None) == 0
     torch.cuda.synchronize()
@@ -359,7 +322,7 @@ def _se_inputs(c, pitch, hw, q, batch, seed, dev):
 def _se_gate_run(eng, xh, xl, w1, b1, w2, b2, hw, pitch, q):
     batch = xh.shape[0]
     out = torch.full((batch * pitch + 64,), float("nan"), dtype=torch.float32, device=xh.device)
-    rc = eng._lib.mpx_se_gate(eng._h, _p(xh), _p(xl), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), batch, hw, pitch, q, eng._stream())
+    rc = eng._lib.mpx_se_gate(eng._h, ptr(xh), ptr(xl), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(out), batch, hw, pitch, q, eng._stream())
     _lib.check(eng._h, rc, "mpx_se_gate")
     torch.cuda.synchronize()
     assert torch.isnan(out[batch * pitch:]).all()
@@ -459,7 +422,7 @@ def test_se_scale_against_the_exact_product(small_engine, dev, c, pitch, hw, bat
         oh = torch.full((n + 64,), float("nan"), dtype=torch.float16, device=dev)
         ol = torch.full_like(oh, float("nan"))
         ih, il = xh, xl
-    _lib.check(eng._h, eng._lib.mpx_se_scale(eng._h, _p(ih), _p(il), _p(gate), _p(oh), _p(ol), batch, hw, pitch, eng._stream()), "mpx_se_scale")
+    _lib.check(eng._h, eng._lib.mpx_se_scale(eng._h, ptr(ih), ptr(il), ptr(gate), ptr(oh), ptr(ol), batch, hw, pitch, eng._stream()), "mpx_se_scale")
     torch.cuda.synchronize()
     assert torch.isnan(oh[n:]).all() and torch.isnan(ol[n:]).all()
     got = merge(oh[:n], ol[:n]).double().view(batch, hw, pitch)
@@ -474,9 +437,9 @@ def test_se_entries_refuse_bad_arguments(small_engine, dev):
     eng = small_engine
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
     f = torch.zeros(4096, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     gate, scale = eng._lib.mpx_se_gate, eng._lib.mpx_se_scale
-    assert gate(eng._h, a, a, b, b, b, b, _p(torch.zeros(64, device=dev)), 1, 4, 8, 3, None) == 0
+    assert gate(eng._h, a, a, b, b, b, b, ptr(torch.zeros(64, device=dev)), 1, 4, 8, 3, None) == 0
     assert scale(eng._h, a, a, b, a, a, 1, 4, 8, None) == 0
     torch.cuda.synchronize()
     off = C.c_void_p(f.data_ptr() + 4)
@@ -512,7 +475,7 @@ def test_silu_global_pool_against_fp64(small_engine, dev, hw, c, batch):
     xh, xl = split(x.to(dev))
     oh = torch.full((batch * c + 64,), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    _lib.check(eng._h, eng._lib.mpx_global_avgpool_silu(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hw, c, eng._stream()), "mpx_global_avgpool_silu")
+    _lib.check(eng._h, eng._lib.mpx_global_avgpool_silu(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hw, c, eng._stream()), "mpx_global_avgpool_silu")
     torch.cuda.synchronize()
     assert torch.isnan(oh[batch * c:]).all() and torch.isnan(ol[batch * c:]).all()
     x64 = merge(xh, xl).double()
@@ -525,7 +488,7 @@ def test_silu_global_pool_against_fp64(small_engine, dev, hw, c, batch):
           % (hw, c, batch, err.max().item(), (err / tol).max().item(), (x64.mean(1) - want).abs().max().item()))
     assert not torch.isnan(got).any() and (err <= tol).all()
     assert (x64.mean(1) - want).abs().max().item() > 0.01           # the plain pool of the same planes is a different number
-    z = _p(xh)
+    z = ptr(xh)
     assert eng._lib.mpx_global_avgpool_silu(eng._h, z, z, z, z, 1, 49, 12, None) == -1
     assert eng._lib.mpx_global_avgpool_silu(eng._h, z, z, z, z, 0, 49, 16, None) == -1
     assert eng._lib.mpx_global_avgpool_silu(eng._h, None, z, z, z, 1, 49, 16, None) == -1
@@ -550,69 +513,11 @@ def _ref_layer(sd, d, x64, res64):
     return y
 
 
-def _run_layer(eng, sd, i, batch, seed):
-    d = eng.layers[i]
-    dev = eng.device
-    last = i == len(eng.layers) - 1
-    cin_p = d.cin if d.cin == 3 else pitch_of(d.cin)
-    cout_p = d.cout if last else pitch_of(d.cout)
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(batch, d.hin, d.hin, cin_p, generator=g) * 1.5
-    x[..., d.cin:] = 0.0                                    # padded channels hold exact zeros wherever they are read
-    xh, xl = split(x.to(dev))
-    rh = rl = None
-    if d.residual:
-        res = torch.randn(batch, d.hout, d.hout, cout_p, generator=g)
-        res[..., d.cout:] = 0.0
-        rh, rl = split(res.to(dev))
-    if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
-        in_h = in_l = None
-    else:
-        in_h, in_l = xh, xl
-    if last:
-        out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = out.double().view(batch, 1, 1, d.cout)
-    else:
-        oh = torch.full((batch, d.hout, d.hout, cout_p), float("nan"), dtype=torch.float16, device=dev)
-        ol = torch.full_like(oh, float("nan"))
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(rh), _p(rl), _p(oh), _p(ol), None, batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        torch.cuda.synchronize()
-        assert (oh[..., d.cout:].view(torch.int16) == 0).all() and (ol[..., d.cout:].view(torch.int16) == 0).all(), d.name     # exact zeros
-        got = merge(oh, ol).double()[..., :d.cout]
-    torch.cuda.synchronize()
-    x64 = merge(xh, xl).double()[..., :d.cin].permute(0, 3, 1, 2)
-    r64 = merge(rh, rl).double()[..., :d.cout].permute(0, 3, 1, 2) if d.residual else None
-    want = _ref_layer(sd, d, x64, r64).permute(0, 2, 3, 1)
-    return got, want
-
-
 def _check(eng, sd, i, batch, tile=-1):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
-        got, want = _run_layer(eng, sd, i, batch, seed=1000 * i + batch)
-        ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
     d = eng.layers[i]
-    name = d.name.decode()
-    assert not torch.isnan(got).any(), name
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d.k_packed, 4608) / 4608) * max(scale, 1.0)
-    print("%s %d->%d k%d h%d K %d res %d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-          % (name, d.cin, d.cout, d.ksize, d.hin, d.k_packed, d.residual, tile, batch, err, scale, bound, ran))
-    assert err <= bound, "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    assert (want < -0.5).any()                              # negative outputs come through: the layer applied no ReLU
+    fields = "%d->%d k%d h%d K %d res %d " % (d.cin, d.cout, d.ksize, d.hin, d.k_packed, d.residual)
+    ran, want = check_conv_layer(eng, i, batch, lambda d, x64, r64: _ref_layer(sd, d, x64, r64), tile, clamp=False, pitched=True, fields=fields)
+    assert (want < -0.5).any()                  # the inputs are signed: a layer that applied ReLU would show
     return ran
 
 
@@ -629,8 +534,7 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engine, sd):
         if key in seen:
             continue
         seen.add(key)
-        accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+        accepted = accepted_tiles(eng, i)
         default = eng._lib.mpx_get_conv_tile(eng._h, i)
         assert default in accepted and GENERIC <= set(accepted), (d.name, accepted)
         if d.cin % 32 or d.cout % 32 and i != len(eng.layers) - 1:
@@ -655,110 +559,22 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engine, sd):
 # ------------------------------------------------------------------------------------------------
 # end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 def test_efficientnet_end_to_end(engine, sd, golden_dir):
     """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: efficientnet_b0 d_L 1.58e-05, engine 2.17e-05 (1.38)."""
-    lens = LogitsLens(ARCH)
-    eng = engine
-    rows = []
-    for kind, m, seed in ref.E2E_CASES:
-        img, seg = ref.e2e_inputs(golden_dir, kind)
-        x = scorer.to_tensor_normalize(img)
-        label, prob = ref.predict(sd, x)
-        assert 0.05 <= prob.max() <= 0.95
-        S = len(np.unique(seg))
-        onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, x, seg, onoff, label, return_logits=True)
-        s64, logits64 = ref.score_masks_fp64(sd, x, seg, onoff, label)
-        lens.add(kind, logits, ref_logits, logits64)
-        top2 = np.sort(logits64, axis=1)[:, -2:]
-        gap = top2[:, 1] - top2[:, 0]
-        err_engine = float(np.abs(score.astype(np.float64) - s64).max())
-        err_cpu = float(np.abs(ref_score.astype(np.float64) - s64).max())
-        err_both = float(np.abs(score.astype(np.float64) - ref_score.astype(np.float64)).max())
-        print("%s %s: %d masks, S %d, label %d, scores %.4f..%.4f" % (ARCH, kind, m, S, label, ref_score.min(), ref_score.max()))
-        print("%s %s: max|d| engine vs fp64 %.3e, fp32 CPU loop vs fp64 (the yardstick) %.3e, engine vs fp32 CPU loop %.3e, smallest fp64 logit gap %.4f"
-              % (ARCH, kind, err_engine, err_cpu, err_both, gap.min()))
-        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
-        assert gap.min() >= 1e-3 and peaks.min() >= 0.05 and peaks.max() <= 0.95      # every row: tests/test_efficientnet_cpu.py holds the weights to it
-        rows.append((kind, err_engine, err_cpu, err_both, pred, ref_pred, logits64.argmax(1)))
-        p_label, _ = eng.predict(img)
-        assert p_label == label
-    d = max(r[2] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
-    print("%s: yardstick distance %.3e over the 28 rows -> end-to-end bound %.1e" % (ARCH, d, bound))
-    for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
-        assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
-        assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
-    lens.check()
+    r = Reference(ref, sd)
+    check_end_to_end(engine, ARCH, r, e2e_rows(r, ref.E2E_CASES, golden_dir),
+                     "%(arch)s: yardstick distance %(d).3e over the 28 rows -> end-to-end bound %(bound).1e", peaks=True)
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engine, golden_dir):
-    eng = engine
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(8, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699))):
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engine, *ref.e2e_inputs(golden_dir, "felz"), (8, ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699)))))
 
 
 # ------------------------------------------------------------------------------------------------
 # API, profile and errors
 # ------------------------------------------------------------------------------------------------
-def _score_one(sd32, masked_chw, label):
-    with torch.no_grad():
-        logits = ref.forward(sd32, torch.from_numpy(masked_chw[None]))
-    return F.softmax(logits, 1).numpy()[0][label], int(logits.argmax(1)[0])
-
-
 def test_api_on_an_efficientnet_engine(engine, sd, golden_dir):
-    eng = engine
-    sd32 = ref.cast(sd, torch.float32)
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    x = scorer.to_tensor_normalize(img)
-    label, _ = ref.predict(sd, x)
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(12, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    rank_map = rank_segments(seg)[0]
-    heat, n_ok = shard.heatmap_sharded(eng, img, rank_map, onoff, label)
-    want_heat = sum((onoff[i][rank_map] for i in range(12) if pred[i] == label), np.zeros((224, 224)))
-    assert n_ok == int((pred == label).sum()) and np.array_equal(heat.cpu().numpy().astype(np.float64), want_heat.astype(np.float64))
-    assert np.array_equal(eng.heatmap(rank_map, onoff, pred, label), want_heat.astype(np.float64))
-    p_label, p_prob = eng.predict(img)
-    assert p_label == label and abs(float(p_prob.sum()) - 1.0) < 1e-5
-    # the reference-named entry points
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want, _ = _score_one(sd32, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
-    table_s, table_p = api.SaliencySession(eng, x, label, segments=seg).table()
-    assert len(table_s) == S + 1
-    for f in range(0, S + 1, 11):
-        want, want_p = _score_one(sd32, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(table_s[f]) - float(want)) <= SCORE_BOUND
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=20, rng=random.Random(3))
-    one = api.validate(list(loader), eng, None, 1, num_mask_samples=20, rng=random.Random(3))
-    assert many == {1: one}
+    check_api(engine, Reference(ref, sd), *ref.e2e_inputs(golden_dir, "felz"))
 
 
 def test_profile_lists_the_depthwise_and_se_launches(engine, dev):
@@ -792,10 +608,10 @@ def test_efficientnet_error_paths(small_engine, mpx_lib, dev, sd):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     buf = torch.zeros(64, dtype=torch.float16, device=dev)
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(buf), _p(buf), 1, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(buf), ptr(buf), 1, None) == -2
     for bad in (10001, 10010, 10999):
         h = C.c_void_p()
         assert mpx_lib.mpx_create(bad, 2, 0, C.byref(h)) == -1 and not h.value
@@ -816,14 +632,14 @@ def test_efficientnet_error_paths(small_engine, mpx_lib, dev, sd):
         labels = torch.zeros(1, dtype=torch.int32, device=dev)
         score = torch.zeros(1, device=dev)
         pred = torch.zeros(1, dtype=torch.int32, device=dev)
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == -2       # missing SE weights
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == -2       # missing SE weights
         with pytest.raises(KeyError):
             fresh.load_state_dict(synth.make_state_dict("mobilenet_v2"))
         with pytest.raises(KeyError):
             fresh.load_state_dict(sd, only=["features.2.0.block.9"])
         fresh.load_state_dict(sd, only=[d.name.decode() for d in fresh.ses])
         assert fresh._lib.mpx_weights_complete(fresh._h) == 1
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == 0
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == 0
         torch.cuda.synchronize()
     finally:
         fresh.close()

@@ -12,16 +12,15 @@ conv1' of the launch's OWN stored block output --, the block tail's block output
 of its window; the older max norm stays as a second assertion, and clearly negative pre-activations must be +0 in both planes.  References are
 built on the device in fp64, once per (form, batch).  On an MI355X the file's 46 tests take 10 s; the slowest is the first block-tail launch (0.8 s)
 behind 2.6 s of set-up for the trained-like engine."""
-import ctypes as C
 
 import pytest
 import torch
 
 import conv_edge_draws as ced
 import fused_edge_draws as fed
+from gpu_common import dev, Fenced, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
-from test_gpu_conv_edges import Fenced
 
 pytestmark = pytest.mark.gpu
 
@@ -29,16 +28,6 @@ WORST = {}                              # form -> (worst err / tol, where)
 CONFIGS = {(0, True): "BtHeadC64", (0, False): "BtDualC64", (1, False): "BtResC64", (2, False): "BtResC128"}
 WHICH = ("one image", "second tiles", "third tiles")
 PT_WHICH = ("ragged 16", "ragged 112", "whole tiles", "second tiles")
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-@pytest.fixture(scope="module")
-def dev(mpx_lib):
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _engine(arch, sd):

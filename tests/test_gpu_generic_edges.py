@@ -21,9 +21,9 @@ import torch
 
 import conv_edge_draws as ced
 import generic_edge_draws as ged
+from gpu_common import Fenced, layer_index as _index, ptr as _p
 from network_interpretation_imagenet_amd import _lib
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
-from test_gpu_conv_edges import Fenced
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +31,6 @@ WORST = {}                              # form -> (worst err / tol, where)
 COVERED = {}                            # form -> {(layer, residue class)}
 ON_TILE = {}                            # (form, tile) -> {residue class}
 ROW_IDS = ["%s-%s" % (r.arch, r.name) for r in ged.FORMS]
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 @pytest.fixture(scope="module")
@@ -51,10 +47,6 @@ def engines(mpx_lib):
     yield get
     for e in made.values():
         e.close()
-
-
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
 
 
 def _ints(fn, eng, i, n):

@@ -16,65 +16,29 @@ End-to-end figures (rows of googlenet_ref.E2E_CASES: 20 felzenszwalb + 8 grid ma
 case has run on an MI355X (DESIGN.md 15 says why); the test prints d, the bound and the three distances on every run, and DESIGN.md 15 is
 where they go."""
 import ctypes as C
-import math
-import random
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import googlenet_ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
-from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError, rank_segments
-from logits_lens import LogitsLens
+from gpu_common import accepted_tiles, bits, dev, FALLBACK, GENERIC, layer_bound, merge, pitch_of, ptr, split  # noqa: F401  (dev is a fixture)
+from net_harness import assert_layer_close, check_api, check_end_to_end, check_position_independence, conv_tile, e2e_rows, Reference, stage_stem_input
+from network_interpretation_imagenet_amd import _lib, synth
+from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
 ARCH = "googlenet"
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 SENTINEL = 0x7e00           # an fp16 NaN bit pattern no kernel here produces from finite inputs
 TAIL = 64
 SLICE_SUFFIXES = (b"branch1.conv", b"branch2.1.conv", b"branch3.1.conv", b"branch4.1.conv")      # the last conv of each Inception branch
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def pitch_of(c):
-    return -(-c // 32) * 32
-
-
-def bits(t):
-    return t.view(torch.int16).to(torch.int32) & 0xffff
-
-
 def sentinel_planes(n, dev):
     return (torch.full((n + TAIL,), SENTINEL, dtype=torch.int16, device=dev).view(torch.float16),
             torch.full((n + TAIL,), SENTINEL, dtype=torch.int16, device=dev).view(torch.float16))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -136,7 +100,7 @@ def _run_pool(eng, x, stride, pad):
     assert ho == googlenet_ref.pool_side(hin, 3, stride, pad)
     n = B * ho * ho * pitch
     oh, ol = sentinel_planes(n, dev)
-    rc = eng._lib.mpx_maxpool3x3_clip(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), B, hin, stride, pad, pitch, eng._stream())
+    rc = eng._lib.mpx_maxpool3x3_clip(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), B, hin, stride, pad, pitch, eng._stream())
     _lib.check(eng._h, rc, "mpx_maxpool3x3_clip")
     torch.cuda.synchronize()
     assert (bits(oh[n:]) == SENTINEL).all() and (bits(ol[n:]) == SENTINEL).all(), "wrote past the end"
@@ -285,33 +249,24 @@ class _Layer:
         self.xh, self.xl = split(x.to(dev))
         x64 = merge(self.xh, self.xl).double()[..., :d.cin].permute(0, 3, 1, 2)
         self.want = _ref_layer(sd, d, x64)
-        self.scale = self.want.abs().max().item()
-        self.bound = LAYER_TOL * math.sqrt(max(d.k_packed, 4608) / 4608) * max(self.scale, 1.0)
+        self.bound = layer_bound(d, self.want.abs().max().item())
 
     def run(self, tile, out=None):
         """out: (hi, lo) planes to write into instead of fresh sentinel-filled ones."""
         eng, d, i, batch = self.eng, self.d, self.i, self.batch
         dev = eng.device
-        assert eng._lib.mpx_set_conv_tile(eng._h, i, tile) == 0, eng._lib.mpx_last_error(eng._h)
-        try:
-            if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-                ih, il = eng.input_planes(batch)
-                ih.zero_()
-                il.zero_()
-                ih[:, 3:227, 3:227, :3] = self.xh
-                il[:, 3:227, 3:227, :3] = self.xl
-                eng.mark_input_staged(0, batch)
+        with conv_tile(eng, i, tile):
+            if i == 0:
+                stage_stem_input(eng, self.xh, self.xl, batch)
                 in_h = in_l = None
             else:
                 in_h, in_l = self.xh, self.xl
             n = batch * d.hout * d.hout * self.pitch
             oh, ol = out if out is not None else sentinel_planes(n, dev)
-            rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, _p(oh), _p(ol), None, batch, eng._stream())
+            rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), None, None, ptr(oh), ptr(ol), None, batch, eng._stream())
             _lib.check(eng._h, rc, "mpx_conv_bn_act")
             torch.cuda.synchronize()
             ran = eng._lib.mpx_last_conv_kernels(eng._h)
-        finally:
-            eng._lib.mpx_set_conv_tile(eng._h, i, -1)
         shape = (batch, d.hout, d.hout, self.pitch)
         return oh[:n].view(shape), ol[:n].view(shape), (oh[n:], ol[n:]), ran
 
@@ -322,21 +277,12 @@ class _Layer:
         mine = slice(self.off, self.off + d.cout)
         got = merge(oh[..., mine], ol[..., mine]).double()
         assert not torch.isnan(got).any(), d.name
-        err = (got - self.want).abs().max().item()
-        print("%s %d->%d k%d h%d K %d pitch %d offset %d stored %d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-              % (d.name.decode(), d.cin, d.cout, d.ksize, d.hin, d.k_packed, self.pitch, self.off, self.store, tile, self.batch, err, self.scale,
-                 self.bound, ran))
-        assert err <= self.bound, "%s tile %d batch %d: max err %.3e (scale %.2f)" % (d.name.decode(), tile, self.batch, err, self.scale)
+        fields = "%d->%d k%d h%d K %d pitch %d offset %d stored %d " % (d.cin, d.cout, d.ksize, d.hin, d.k_packed, self.pitch, self.off, self.store)
+        assert_layer_close(d, got, self.want, tile, self.batch, ran, fields)
         pad = slice(self.off + d.cout, self.off + self.store)
         assert (bits(oh[..., pad]) == 0).all() and (bits(ol[..., pad]) == 0).all(), (d.name, tile)      # pad channels: exact zeros
         for other in (slice(0, self.off), slice(self.off + self.store, self.pitch)):
             assert (bits(oh[..., other]) == SENTINEL).all() and (bits(ol[..., other]) == SENTINEL).all(), (d.name, tile, other)
-
-
-def _accepted(eng, i):
-    acc = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-    eng._lib.mpx_set_conv_tile(eng._h, i, -1)
-    return acc
 
 
 _GROUPS = ("conv",) + tuple(m[0] for m in googlenet_ref.MODULES)
@@ -364,7 +310,7 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engine, sd, grou
     for i, d in enumerate(eng.layers[:-1]):
         if not d.name.decode().startswith(group) or i not in first:
             continue
-        accepted = _accepted(eng, i)
+        accepted = accepted_tiles(eng, i)
         default = eng._lib.mpx_get_conv_tile(eng._h, i)
         assert default in accepted and GENERIC <= set(accepted), (d.name, accepted)
         layer = _Layer(eng, sd, i, 3, seed=1000 * i + 3)
@@ -397,7 +343,7 @@ def test_branch_convs_fill_their_ranges_of_one_buffer_and_nothing_else(small_eng
     assert all(l.d.hin == h for l in layers)
     tiles = None
     for l in layers:
-        accepted = _accepted(eng, l.i)
+        accepted = accepted_tiles(eng, l.i)
         assert set(accepted) == GENERIC, (l.d.name, accepted)
         tiles = accepted
         for t in accepted:
@@ -423,106 +369,22 @@ def test_branch_convs_fill_their_ranges_of_one_buffer_and_nothing_else(small_eng
 # ------------------------------------------------------------------------------------------------
 # end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 def test_googlenet_end_to_end(engine, sd, golden_dir):
     """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: googlenet d_L 9.11e-06, engine 1.54e-05 (1.69)."""
-    lens = LogitsLens(ARCH)
-    eng = engine
-    rows = []
-    for kind, m, seed in googlenet_ref.E2E_CASES:
-        img, seg = googlenet_ref.e2e_inputs(golden_dir, kind)
-        x = scorer.to_tensor_normalize(img)
-        label, prob = googlenet_ref.predict(sd, x)
-        assert 0.05 <= prob.max() <= 0.95
-        S = len(np.unique(seg))
-        onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        ref_score, ref_pred, ref_logits = googlenet_ref.score_masks_reference_loop(sd, x, seg, onoff, label, return_logits=True)
-        s64, logits64 = googlenet_ref.score_masks_fp64(sd, x, seg, onoff, label)
-        lens.add(kind, logits, ref_logits, logits64)
-        top2 = np.sort(logits64, axis=1)[:, -2:]
-        gap = top2[:, 1] - top2[:, 0]
-        err_engine = float(np.abs(score.astype(np.float64) - s64).max())
-        err_cpu = float(np.abs(ref_score.astype(np.float64) - s64).max())
-        err_both = float(np.abs(score.astype(np.float64) - ref_score.astype(np.float64)).max())
-        print("%s %s: %d masks, S %d, label %d, scores %.4f..%.4f" % (ARCH, kind, m, S, label, ref_score.min(), ref_score.max()))
-        print("%s %s: max|d| engine vs fp64 %.3e, fp32 CPU loop vs fp64 (the yardstick) %.3e, engine vs fp32 CPU loop %.3e, smallest fp64 logit gap %.4f"
-              % (ARCH, kind, err_engine, err_cpu, err_both, gap.min()))
-        assert gap.min() >= 1e-3
-        rows.append((kind, err_engine, err_cpu, err_both, pred, ref_pred, logits64.argmax(1)))
-        p_label, _ = eng.predict(img)
-        assert p_label == label
-    d = max(r[2] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
-    print("%s: yardstick distance d = %.3e over the 28 rows -> end-to-end bound %.1e" % (ARCH, d, bound))
-    for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
-        assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
-        assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
-    lens.check()
+    ref = Reference(googlenet_ref, sd)
+    check_end_to_end(engine, ARCH, ref, e2e_rows(ref, googlenet_ref.E2E_CASES, golden_dir),
+                     "%(arch)s: yardstick distance d = %(d).3e over the 28 rows -> end-to-end bound %(bound).1e")
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engine, golden_dir):
-    """Position independence inside a packed batch, and ragged batches: 1, 37 and 700 rows (700 = 512 + 188 on the default engine)."""
-    eng = engine
-    img, seg = googlenet_ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(8, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699))):
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engine, *googlenet_ref.e2e_inputs(golden_dir, "felz"), (8, ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699)))))
 
 
 # ------------------------------------------------------------------------------------------------
 # API, profile and errors
 # ------------------------------------------------------------------------------------------------
-def _score_one(sd32, masked_chw, label):
-    with torch.no_grad():
-        logits = googlenet_ref.forward(sd32, torch.from_numpy(masked_chw[None]))
-    return F.softmax(logits, 1).numpy()[0][label], int(logits.argmax(1)[0])
-
-
 def test_api_on_a_googlenet_engine(engine, sd, golden_dir):
-    eng = engine
-    sd32 = googlenet_ref.cast(sd, torch.float32)
-    img, seg = googlenet_ref.e2e_inputs(golden_dir, "felz")
-    x = scorer.to_tensor_normalize(img)
-    label, _ = googlenet_ref.predict(sd, x)
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(12, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    _o2, score2, pred2 = eng.score_masks(img, seg, onoff, label)
-    assert np.array_equal(score, score2) and np.array_equal(pred, pred2)
-    ref_score, ref_pred = googlenet_ref.score_masks_reference_loop(sd, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    rank_map = rank_segments(seg)[0]
-    p_label, p_prob = eng.predict(img)
-    assert p_label == label and abs(float(p_prob.sum()) - 1.0) < 1e-5
-    # the reference-named entry points
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want, _ = _score_one(sd32, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=20, rng=random.Random(3))
-    one = api.validate(list(loader), eng, None, 1, num_mask_samples=20, rng=random.Random(3))
-    assert many == {1: one}
-    heat, n_ok = shard.heatmap_sharded(eng, img, rank_map, onoff, label)
-    want_heat = sum((onoff[i][rank_map] for i in range(12) if pred[i] == label), np.zeros((224, 224)))
-    assert n_ok == int((pred == label).sum()) and np.array_equal(heat.cpu().numpy().astype(np.float64), want_heat.astype(np.float64))
+    check_api(engine, Reference(googlenet_ref, sd), *googlenet_ref.e2e_inputs(golden_dir, "felz"), heatmaps=1, table_step=None)
 
 
 def test_profile_times_every_pool_launch(engine, dev):
@@ -556,10 +418,10 @@ def test_googlenet_error_paths(small_engine, mpx_lib, dev, sd):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     buf = torch.zeros(64, dtype=torch.float16, device=dev)
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(buf), _p(buf), 1, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(buf), ptr(buf), 1, None) == -2
     for bad in (8001, 8999):
         h = C.c_void_p()
         assert mpx_lib.mpx_create(bad, 2, 0, C.byref(h)) == -1 and not h.value
@@ -568,21 +430,21 @@ def test_googlenet_error_paths(small_engine, mpx_lib, dev, sd):
     i = names.index("inception3a.branch1.conv")
     zz = torch.zeros(28 * 28 * 256 + TAIL, dtype=torch.float16, device=dev)
     f = torch.zeros(16, dtype=torch.float32, device=dev)
-    assert eng._lib.mpx_conv_bn_act(eng._h, i, _p(zz), _p(zz), _p(zz), _p(zz), _p(zz), _p(zz), None, 1, None) == -1
-    assert eng._lib.mpx_conv_bn_act(eng._h, i, _p(zz), _p(zz), None, None, _p(zz), _p(zz), _p(f), 1, None) == -1
+    assert eng._lib.mpx_conv_bn_act(eng._h, i, ptr(zz), ptr(zz), ptr(zz), ptr(zz), ptr(zz), ptr(zz), None, 1, None) == -1
+    assert eng._lib.mpx_conv_bn_act(eng._h, i, ptr(zz), ptr(zz), None, None, ptr(zz), ptr(zz), ptr(f), 1, None) == -1
     # the pool entry: stride 1 or 2, pad 0 or 1, a pitch that is a multiple of 8, a map the window fits
     call = eng._lib.mpx_maxpool3x3_clip
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 3, 0, 64, None) == -1       # stride 3
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 0, 0, 64, None) == -1       # stride 0
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 1, 2, 64, None) == -1       # pad 2
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 1, -1, 64, None) == -1      # pad -1
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 1, 1, 12, None) == -1       # pitch not a multiple of 8
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 14, 1, 1, 0, None) == -1
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 1, 2, 2, 0, 64, None) == -1        # a 3x3 window does not fit an unpadded 2x2 map
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), _p(zz), 0, 14, 1, 1, 64, None) == -1       # B <= 0
-    assert call(eng._h, None, _p(zz), _p(zz), _p(zz), 1, 14, 1, 1, 64, None) == -1         # null planes
-    assert call(eng._h, _p(zz), _p(zz), _p(zz), None, 1, 14, 1, 1, 64, None) == -1
-    assert call(eng._h, _p(zz[4:]), _p(zz), _p(zz), _p(zz), 1, 14, 1, 1, 64, None) == -1   # planes that are not 16-byte aligned
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 3, 0, 64, None) == -1       # stride 3
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 0, 0, 64, None) == -1       # stride 0
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, 2, 64, None) == -1       # pad 2
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, -1, 64, None) == -1      # pad -1
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, 1, 12, None) == -1       # pitch not a multiple of 8
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, 1, 0, None) == -1
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 1, 2, 2, 0, 64, None) == -1        # a 3x3 window does not fit an unpadded 2x2 map
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), ptr(zz), 0, 14, 1, 1, 64, None) == -1       # B <= 0
+    assert call(eng._h, None, ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, 1, 64, None) == -1         # null planes
+    assert call(eng._h, ptr(zz), ptr(zz), ptr(zz), None, 1, 14, 1, 1, 64, None) == -1
+    assert call(eng._h, ptr(zz[4:]), ptr(zz), ptr(zz), ptr(zz), 1, 14, 1, 1, 64, None) == -1   # planes that are not 16-byte aligned
     fresh = MaskedForwardEngine(ARCH, max_batch=2, device=0)
     try:
         assert fresh._lib.mpx_weights_complete(fresh._h) == 0

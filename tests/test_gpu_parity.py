@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import dev, merge, ptr as _p, split  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError
 from logits_lens import LogitsLens
@@ -22,26 +23,6 @@ pytestmark = pytest.mark.gpu
 
 SCORE_TOL = 1e-4        # north_star tolerance
 SCORE_TOL_TIGHT = 2e-5  # what split-fp16 should achieve
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

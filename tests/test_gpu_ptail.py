@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import dev, merge, ptr as _p, split  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 
@@ -23,28 +24,8 @@ KERNEL_TOL = 4e-6       # the project's per-kernel bound (tests/test_gpu_parity.
 HW = 28 * 28
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
 def _bits(t):
     return t.view(torch.int16)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

@@ -5,49 +5,23 @@ fp64, the descriptors, tiles and refusals, and the five networks end to end on t
 
 The grouped launch does not cap its grid (ceil(M / 16) workgroups in x, a quarter of the units in y), so there is no capped-grid case to run."""
 import ctypes as C
-import math
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import regnet_draws as gd
 import regnet_ref as ref
-from logits_lens import LogitsLens
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
+from gpu_common import dev, Fenced, GENERIC, layer_bound, layer_index, merge, ptr, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_end_to_end, check_position_independence, Reference, stage_stem_input
+from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
-from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
 ARCHS = ref.ARCHS
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
 DENSE_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
 EPS = 1e-5
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev(mpx_lib):
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -62,10 +36,6 @@ def engines(dev, sds):
     yield out
     for e in out.values():
         e.close()
-
-
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
 
 
 def _pitches(eng, i):
@@ -86,45 +56,16 @@ def _at_pitch(x, pitch, pad_sentinel=False):
     return out.contiguous()
 
 
-class Fenced:
-    """rows x pitch elements between two fences of FENCE_ROWS x pitch, everything prefilled with the sentinel."""
-
-    def __init__(self, rows, pitch, dev):
-        self.fence, self.rows, self.pitch = gd.FENCE_ROWS * pitch, rows, pitch
-        self.bits = torch.full((2 * self.fence + rows * pitch,), gd.SENTINEL_BITS, dtype=torch.int16, device=dev)
-        self.values = self.bits.view(torch.float16)
-
-    @property
-    def payload(self):
-        return self.values[self.fence:self.fence + self.rows * self.pitch].view(self.rows, self.pitch)
-
-    @property
-    def payload_bits(self):
-        return self.bits[self.fence:self.fence + self.rows * self.pitch].view(self.rows, self.pitch)
-
-    def problems(self):
-        out = []
-        front, back = self.bits[:self.fence] != gd.SENTINEL_BITS, self.bits[self.fence + self.rows * self.pitch:] != gd.SENTINEL_BITS
-        if front.any():
-            out.append("front fence: %d elements overwritten" % int(front.sum()))
-        if back.any():
-            out.append("back fence: %d elements overwritten, the first at %d behind the payload" % (int(back.sum()), int(back.nonzero().min())))
-        left = self.payload_bits == gd.SENTINEL_BITS
-        if left.any():
-            out.append("payload: %d elements never written, the first in pixel row %d" % (int(left.sum()), int(left.nonzero()[0, 0])))
-        return out
-
-
 def _launch_grouped(eng, d, x_hi, x_lo, batch, tile=gd.TILE, pad_sentinel=False):
     """mpx_conv_bn_act of grouped layer d over `batch` images (x_*: [batch][hin][hin][width], placed into planes at the layer's input pitch)
     -> fenced (hi, lo) at the output pitch; the kernel of `tile` and nothing else must have run.  Every pad channel of the output is +0."""
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     pin, pout = _pitches(eng, i)
     assert pin == pout == ref.pitch(d.width)
     rows = batch * d.hout * d.hout
     xh, xl = _at_pitch(x_hi, pin, pad_sentinel), _at_pitch(x_lo, pin, pad_sentinel)
     hi, lo = Fenced(rows, pout, eng.device), Fenced(rows, pout, eng.device)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(xh), _p(xl), None, None, _p(hi.payload), _p(lo.payload), None, batch, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(xh), ptr(xl), None, None, ptr(hi.payload), ptr(lo.payload), None, batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_bn_act(%s, batch %d)" % (d.name, batch))
     mask = eng._lib.mpx_last_conv_kernels(eng._h)
     torch.cuda.synchronize()
@@ -146,7 +87,7 @@ def test_grouped_layer_behind_fences_inside_the_per_element_bound(engines, sds, 
     """(cg, groups, stride, map) of every grouped layer: cg 16 / 24 / 48 / 120, 2 .. 42 groups (3, 7, 9, 17, 21, 25, 38 among them: a ragged last
     workgroup), stride 2 on 112 .. 14 maps and stride 1 on 56 .. 7.  On the 14 x 14 and 7 x 7 output maps M = 196 / 49 / 147 / 588 is no multiple of 16."""
     eng = engines[d.arch]
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     e = eng.layers[i]
     assert (e.cin, e.cout, e.ksize, e.stride, e.pad, e.hin, e.hout, e.relu, e.residual) == (d.width, d.width, 3, d.stride, 1, d.hin, d.hout, 1, 0)
     assert eng.groups[i] == d.groups and eng._lib.mpx_get_conv_tile(eng._h, i) == gd.TILE
@@ -207,7 +148,7 @@ def test_changing_one_groups_input_changes_that_groups_output_only(engines, arch
         y_hi[..., ch] = (y_hi[..., ch].float() * -1.5 + 0.25).half()
         y_lo[..., ch] = 0
         hi, lo = _launch_grouped(eng, d, y_hi, y_lo, 2)
-        other = torch.ones(hi.pitch, dtype=torch.bool, device=eng.device)
+        other = torch.ones(hi.cout, dtype=torch.bool, device=eng.device)
         other[ch] = False
         assert torch.equal(hi.payload_bits[:, other], base_hi.payload_bits[:, other]) and torch.equal(lo.payload_bits[:, other], base_lo.payload_bits[:, other]), \
             "%s: changing the input of group %d changed another group's output" % (name, g)
@@ -231,7 +172,7 @@ def test_weights_in_one_group_alone_give_exact_zeros_elsewhere(engines, sds, arc
             mod[d.bn_name + ".running_mean"] = torch.zeros(d.width)
             eng.load_state_dict(mod, only=[name])
             hi, lo = _launch_grouped(eng, d, x_hi, x_lo, 2)
-            other = torch.ones(hi.pitch, dtype=torch.bool, device=eng.device)
+            other = torch.ones(hi.cout, dtype=torch.bool, device=eng.device)
             other[ch] = False
             assert (hi.payload_bits[:, other] == 0).all() and (lo.payload_bits[:, other] == 0).all(), "%s: group %d's weights reach another group" % (name, g)
             _pre, want, b = (t.reshape(-1, d.width) for t in gd.reference(mod, d, x))
@@ -266,7 +207,7 @@ def test_tile_16_gives_the_same_bits_where_the_shape_is_one_of_its_own(engines, 
     """cg = 16, width 64 / 128 (a multiple of 64: 4 / 8 groups, pitch = width): mpx_set_conv_tile(i, 16) on such a RegNetX layer runs
     gconv3x3_f16x3_kernel<16> on the layer's own packed planes (for cg = 16 the two plane layouts coincide).  Identical bits."""
     eng, d = engines[arch], gd.layer(arch, name)
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     assert d.cg == 16 and d.width % 64 == 0
     x_hi, x_lo, _x = gd.draws(d, 3, device=eng.device)
     a_hi, a_lo = _launch_grouped(eng, d, x_hi, x_lo, 3)
@@ -315,18 +256,13 @@ def _run_dense(eng, sd, i, batch):
     if d.residual:
         rh, rl = split(torch.randn(batch, d.hout, d.hout, d.cout, generator=g, device=dev))
     if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
+        stage_stem_input(eng, xh, xl, batch)
         in_h = in_l = None
     else:
         in_h, in_l = _at_pitch(xh, pin), _at_pitch(xl, pin)
     oh, ol = _sentinel((batch + 1, d.hout, d.hout, pout), dev), _sentinel((batch + 1, d.hout, d.hout, pout), dev)
     res_h, res_l = (_at_pitch(rh, pout), _at_pitch(rl, pout)) if d.residual else (None, None)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(res_h), _p(res_l), _p(oh), _p(ol), None, batch, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), ptr(res_h), ptr(res_l), ptr(oh), ptr(ol), None, batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_bn_act")
     ran = eng._lib.mpx_last_conv_kernels(eng._h)
     torch.cuda.synchronize()
@@ -351,7 +287,7 @@ DENSE = [("regnet_x_400mf", "stem.0", 3, 32, 3, 0),
 @pytest.mark.parametrize("arch,name,cin,cout,k,res", DENSE, ids=["%s-%s" % (a, n) for a, n, *_ in DENSE])
 def test_dense_shape_on_its_default_tile_and_on_every_tile_that_accepts_it(engines, sds, arch, name, cin, cout, k, res):
     eng, sd = engines[arch], sds[arch]
-    i = _index(eng, name)
+    i = layer_index(eng, name)
     d = eng.layers[i]
     assert (d.cin, d.cout, d.ksize, d.residual) == (cin, cout, k, res) and eng.groups[i] == 1
     default = eng._lib.mpx_get_conv_tile(eng._h, i)
@@ -364,7 +300,7 @@ def test_dense_shape_on_its_default_tile_and_on_every_tile_that_accepts_it(engin
             got, want, ran = _run_dense(eng, sd, i, batch)
             assert not torch.isnan(got).any(), (name, tile)
             err, scale = (got - want).abs().max().item(), want.abs().max().item()
-            bound = LAYER_TOL * math.sqrt(max(d.cin * d.ksize * d.ksize, 4608) / 4608) * max(scale, 1.0)
+            bound = layer_bound(d, scale, k=d.cin * d.ksize * d.ksize)
             print("%s %s %d->%d k%d s%d h%d res %d tile %d%s batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
                   % (arch, name, d.cin, d.cout, d.ksize, d.stride, d.hin, d.residual, tile, " (default)" if tile == default else "", batch, err, scale, bound, ran))
             assert err <= bound, "%s tile %d: max err %.3e (scale %.2f, bound %.3e)" % (name, tile, err, scale, bound)
@@ -417,9 +353,9 @@ def test_descriptors_groups_tiles_and_refusals(engines, arch):
     assert not eng.has_stem_table and eng.stem == "conv"
     # staging is K0 only: the stem-table and stem + pool entry points return MPX_E_STATE
     lab = torch.zeros(224, 224, dtype=torch.int32, device=eng.device)
-    assert lib.mpx_stem_table_build(h, None, None, _p(lab), 1, None, None, None) == -2 and b"RegNetX" in lib.mpx_last_error(h)
+    assert lib.mpx_stem_table_build(h, None, None, ptr(lab), 1, None, None, None) == -2 and b"RegNetX" in lib.mpx_last_error(h)
     out = torch.zeros(8, dtype=torch.float16, device=eng.device)
-    assert lib.mpx_stem_conv_maxpool(h, _p(out), _p(out), 1, None) == -2 and b"7x7 stem" in lib.mpx_last_error(h)
+    assert lib.mpx_stem_conv_maxpool(h, ptr(out), ptr(out), 1, None) == -2 and b"7x7 stem" in lib.mpx_last_error(h)
 
 
 def test_unknown_ids_in_the_regnet_range_are_refused(dev):
@@ -437,7 +373,7 @@ def test_tile_18_is_refused_on_every_layer_of_other_engines(dev):
         try:
             assert eng._lib.mpx_set_conv_tile(eng._h, 1, 18) == -1 and b"grouped" in eng._lib.mpx_last_error(eng._h)
             if grouped:
-                i = _index(eng, grouped)
+                i = layer_index(eng, grouped)
                 assert eng._lib.mpx_set_conv_tile(eng._h, i, 18) == -1 and b"grouped" in eng._lib.mpx_last_error(eng._h)
                 assert eng._lib.mpx_get_conv_tile(eng._h, i) == 16
         finally:
@@ -448,11 +384,11 @@ def test_a_grouped_layer_refuses_a_residual_operand_and_wrong_weight_shapes(engi
     arch = "regnet_x_1_6gf"
     eng = engines[arch]
     d = gd.layer(arch, "trunk_output.block4.block4-1.f.b.0")
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     pitch = ref.pitch(d.width)
     x = torch.zeros(1, d.hin, d.hin, pitch, dtype=torch.float16, device=eng.device)
     out = torch.zeros(49, pitch, dtype=torch.float16, device=eng.device)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(x), _p(x), _p(out), _p(out), _p(out), _p(out.clone()), None, 1, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(x), ptr(x), ptr(out), ptr(out), ptr(out), ptr(out.clone()), None, 1, eng._stream())
     assert rc == -1 and b"residual" in eng._lib.mpx_last_error(eng._h)
     for shape in ((d.width, d.width, 3, 3), (d.width, 16, 3, 3)):           # the dense shape; another group width
         sd = dict(sds[arch])
@@ -488,91 +424,25 @@ def test_default_max_batch_and_bytes_per_slot(dev, arch):
 # ------------------------------------------------------------------------------------------------
 # 8. end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 @pytest.mark.parametrize("arch", ARCHS)
 def test_regnet_end_to_end(engines, sds, golden_dir, arch):
     """400MF: 8 felzenszwalb + 4 grid rows; 800MF / 1.6GF / 3.2GF: 4 + 2; 8GF: 3.  Scores by the MobileNetV2 rule (d = max |fp32 CPU loop - fp64|:
     bound 2e-5 when 4 d < 2e-5, else 4 d rounded up to one digit, never above 1e-4), all logits through the logits lens (4 d_L), every argmax
     equal."""
-    eng, sd = engines[arch], sds[arch]
-    lens = LogitsLens(arch)
-    rows = []
-    for kind, (img, seg, onoff, label, s64, logits64) in ref.e2e_rows(golden_dir, arch).items():
-        x = scorer.to_tensor_normalize(img)
-        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
-        top2 = np.sort(logits64, axis=1)[:, -2:]
-        gap = top2[:, 1] - top2[:, 0]
-        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
-        assert gap.min() >= 1e-3 and peaks.min() >= 0.05 and peaks.max() <= 0.95      # every row: tests/test_regnet_cpu.py holds the weights to it
-        err_cpu = float(np.abs(ref_score.astype(np.float64) - s64).max())
-        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        lens.add(kind, logits, ref_logits, logits64)
-        err_engine = float(np.abs(score.astype(np.float64) - s64).max())
-        err_both = float(np.abs(score.astype(np.float64) - ref_score.astype(np.float64)).max())
-        print("%s %s: %d masks, label %d, scores %.4f..%.4f" % (arch, kind, len(s64), label, ref_score.min(), ref_score.max()))
-        print("%s %s: max|d| engine vs fp64 %.3e, fp32 CPU loop vs fp64 (the yardstick) %.3e, engine vs fp32 CPU loop %.3e, smallest fp64 logit gap %.4f"
-              % (arch, kind, err_engine, err_cpu, err_both, gap.min()))
-        rows.append((kind, err_engine, err_cpu, err_both, pred, ref_pred, logits64.argmax(1)))
-        p_label, _ = eng.predict(img)
-        assert p_label == label
-    d = max(r[2] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
-    print("%s: yardstick distance %.3e over %d rows -> end-to-end bound %.1e" % (arch, d, sum(len(r[4]) for r in rows), bound))
-    for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
-        assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
-        assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
-    lens.check()
+    rows = [(kind,) + row for kind, row in ref.e2e_rows(golden_dir, arch).items()]
+    check_end_to_end(engines[arch], arch, Reference(ref, sds[arch], arch), rows,
+                     "%(arch)s: yardstick distance %(d).3e over %(n)d rows -> end-to-end bound %(bound).1e", segments=False, peaks=True)
 
 
 @pytest.mark.parametrize("arch", ("regnet_x_400mf", "regnet_x_8gf"))
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engines, golden_dir, arch):
-    eng = engines[arch]
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(3, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12))):       # 13 rows: two forwards of an 8-slot engine
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engines[arch], *ref.e2e_inputs(golden_dir, "felz"), (3, ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12)))))
 
 
 def test_api_on_a_regnet_engine(engines, sds, golden_dir):
     arch = "regnet_x_400mf"
-    eng, sd = engines[arch], sds[arch]
-    sd32 = ref.cast(sd, torch.float32)
-
-    def score_one(masked_chw, label):
-        with torch.no_grad():
-            logits = ref.forward(sd32, torch.from_numpy(masked_chw[None]), arch)
-        return F.softmax(logits, 1).numpy()[0][label]
-
-    img, seg = ref.e2e_inputs(golden_dir, "grid")
-    x = scorer.to_tensor_normalize(img)
-    with torch.no_grad():
-        label = int(ref.forward(sd32, x[None], arch).argmax(1)[0])
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(4, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND and (pred == ref_pred).all()
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want = score_one(scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
+    check_api(engines[arch], Reference(ref, sds[arch], arch), *ref.e2e_inputs(golden_dir, "grid"),
+              rows=4, same_pred=True, heatmaps=0, predict=False, table_step=None, validate=None)
 
 
 @pytest.mark.parametrize("arch", ("regnet_x_400mf", "regnet_x_8gf"))

@@ -26,57 +26,24 @@ worst err / tol 0.340 (DESIGN.md 27 has the table).  The 169 tests take 9.4 s.
 """
 import ctypes as C
 import math
-import random
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import regnety_draws as yd
 import regnety_ref as ref
-from logits_lens import LogitsLens
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
+from gpu_common import dev, dev_view, Fenced, GENERIC, layer_bound, layer_index, merge, ptr, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_api, check_end_to_end, check_position_independence, Reference, stage_stem_input
+from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
-from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
 ARCHS = ref.ARCHS
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
 DENSE_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
 EPS = 1e-5
 U = 2.0 ** -24
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def dev_view(ptr, n, dev):
-    """n floats at a device pointer the engine owns, copied to the host."""
-    class _V:
-        __cuda_array_interface__ = {"data": (ptr.value, False), "shape": (n,), "typestr": "<f4", "version": 2}
-    return torch.as_tensor(_V(), device=dev).clone().cpu()
-
-
-@pytest.fixture(scope="module")
-def dev(mpx_lib):
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -97,10 +64,6 @@ def engines(dev, sds):
 def eng(engines):
     """The engine the stand-alone entries are called on."""
     return engines["regnet_y_800mf"]
-
-
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
 
 
 def _pitches(eng, i):
@@ -151,7 +114,7 @@ def _se_inputs(c, pitch, hw, q, batch, seed, dev, sign=-1.0):
 def _se_gate_run(eng, xh, xl, w1, b1, w2, b2, hw, pitch, q, entry="mpx_se_gate_relu"):
     batch = xh.shape[0]
     out = torch.full((batch * pitch + 64,), float("nan"), dtype=torch.float32, device=xh.device)
-    rc = getattr(eng._lib, entry)(eng._h, _p(xh), _p(xl), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), batch, hw, pitch, q, eng._stream())
+    rc = getattr(eng._lib, entry)(eng._h, ptr(xh), ptr(xl), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(out), batch, hw, pitch, q, eng._stream())
     _lib.check(eng._h, rc, entry)
     torch.cuda.synchronize()
     assert torch.isnan(out[batch * pitch:]).all(), "%s wrote behind its output" % entry
@@ -230,9 +193,9 @@ def test_se_gate_relu_of_an_image_has_the_same_bits_alone_and_inside_a_batch(eng
 def test_se_gate_relu_refuses_bad_arguments(eng, dev):
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
     f = torch.zeros(4096, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     gate = eng._lib.mpx_se_gate_relu
-    assert gate(eng._h, a, a, b, b, b, b, _p(torch.zeros(64, device=dev)), 1, 4, 8, 3, None) == 0
+    assert gate(eng._h, a, a, b, b, b, b, ptr(torch.zeros(64, device=dev)), 1, 4, 8, 3, None) == 0
     torch.cuda.synchronize()
     off = C.c_void_p(f.data_ptr() + 4)
     assert gate(None, a, a, b, b, b, b, b, 1, 4, 8, 3, None) == -1
@@ -276,35 +239,6 @@ def test_se_gate_relu_with_engine_layer_parameters(eng, dev, sds):
 # ------------------------------------------------------------------------------------------------
 # 2. group width 56 on tile 18, behind fences, inside the per-element bound
 # ------------------------------------------------------------------------------------------------
-class Fenced:
-    """rows x pitch elements between two fences of FENCE_ROWS x pitch, everything prefilled with the sentinel."""
-
-    def __init__(self, rows, pitch, dev):
-        self.fence, self.rows, self.pitch = yd.FENCE_ROWS * pitch, rows, pitch
-        self.bits = torch.full((2 * self.fence + rows * pitch,), yd.SENTINEL_BITS, dtype=torch.int16, device=dev)
-        self.values = self.bits.view(torch.float16)
-
-    @property
-    def payload(self):
-        return self.values[self.fence:self.fence + self.rows * self.pitch].view(self.rows, self.pitch)
-
-    @property
-    def payload_bits(self):
-        return self.bits[self.fence:self.fence + self.rows * self.pitch].view(self.rows, self.pitch)
-
-    def problems(self):
-        out = []
-        front, back = self.bits[:self.fence] != yd.SENTINEL_BITS, self.bits[self.fence + self.rows * self.pitch:] != yd.SENTINEL_BITS
-        if front.any():
-            out.append("front fence: %d elements overwritten" % int(front.sum()))
-        if back.any():
-            out.append("back fence: %d elements overwritten, the first at %d behind the payload" % (int(back.sum()), int(back.nonzero().min())))
-        left = self.payload_bits == yd.SENTINEL_BITS
-        if left.any():
-            out.append("payload: %d elements never written, the first in pixel row %d" % (int(left.sum()), int(left.nonzero()[0, 0])))
-        return out
-
-
 _packed = {}
 
 
@@ -316,7 +250,7 @@ def _pack(eng, d):
         w_hi, w_lo = torch.zeros(rows * kp, dtype=torch.int16), torch.zeros(rows * kp, dtype=torch.int16)
         scale, shift = torch.zeros(rows), torch.zeros(rows)
         t = [sd[d.name + ".weight"].contiguous()] + [sd[d.bn_name + "." + k].contiguous() for k in ("weight", "bias", "running_mean", "running_var")]
-        rc = eng._lib.mpx_pack_gconvw_weights(d.width, d.groups, *[_p(v) for v in t], EPS, _p(w_hi), _p(w_lo), _p(scale), _p(shift))
+        rc = eng._lib.mpx_pack_gconvw_weights(d.width, d.groups, *[ptr(v) for v in t], EPS, ptr(w_hi), ptr(w_lo), ptr(scale), ptr(shift))
         assert rc == 0
         _packed[d.name] = (tuple(v.to(eng.device) for v in (w_hi, w_lo, scale, shift)), sd)
     return _packed[d.name]
@@ -330,7 +264,7 @@ def _launch_cg56(eng, d, x_hi, x_lo, batch, pad_sentinel=False):
     rows = batch * d.hout * d.hout
     xh, xl = _at_pitch(x_hi, pitch, pad_sentinel), _at_pitch(x_lo, pitch, pad_sentinel)
     hi, lo = Fenced(rows, pitch, eng.device), Fenced(rows, pitch, eng.device)
-    rc = eng._lib.mpx_gconvw3x3_bn_act(eng._h, _p(xh), _p(xl), _p(w_hi), _p(w_lo), _p(scale), _p(shift), _p(hi.payload), _p(lo.payload),
+    rc = eng._lib.mpx_gconvw3x3_bn_act(eng._h, ptr(xh), ptr(xl), ptr(w_hi), ptr(w_lo), ptr(scale), ptr(shift), ptr(hi.payload), ptr(lo.payload),
                                         batch, d.hin, d.width, d.groups, pitch, pitch, d.stride, 1, eng._stream())
     _lib.check(eng._h, rc, "mpx_gconvw3x3_bn_act(%s, batch %d)" % (d.name, batch))
     mask = eng._lib.mpx_last_conv_kernels(eng._h)
@@ -393,22 +327,22 @@ def test_the_stand_alone_grouped_entry_gives_an_engine_layers_bits(engines, sds)
     same state_dict, through mpx_gconvw3x3_bn_act: the same planes bit for bit."""
     eng, sd = engines["regnet_y_8gf"], sds["regnet_y_8gf"]
     name, bn = "trunk_output.block4.block4-0.f.b.0", "trunk_output.block4.block4-0.f.b.1"
-    i = _index(eng, name)
+    i = layer_index(eng, name)
     e = eng.layers[i]
     assert (e.cin, e.stride, e.hin, eng.groups[i]) == (2016, 2, 14, 36) and _pitches(eng, i) == (2016, 2016)
     d = yd.GDesc("regnet_y_8gf", name, bn, 2016, 56, 36, 2, 14, 7)
     x_hi, x_lo, _x = yd.xgd.draws(d, 3, seed=77, device=eng.device)
     a_hi, a_lo = _sentinel((3 * 49, 2016), eng.device), _sentinel((3 * 49, 2016), eng.device)
-    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, i, _p(x_hi), _p(x_lo), None, None, _p(a_hi), _p(a_lo), None, 3, eng._stream()), "mpx_conv_bn_act")
+    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, i, ptr(x_hi), ptr(x_lo), None, None, ptr(a_hi), ptr(a_lo), None, 3, eng._stream()), "mpx_conv_bn_act")
     assert eng._lib.mpx_last_conv_kernels(eng._h) == 1 << 18
     rows = 36 * 64
     w_hi, w_lo = torch.zeros(rows * 512, dtype=torch.int16), torch.zeros(rows * 512, dtype=torch.int16)
     scale, shift = torch.zeros(rows), torch.zeros(rows)
     t = [sd[name + ".weight"].contiguous()] + [sd[bn + "." + k].contiguous() for k in ("weight", "bias", "running_mean", "running_var")]
-    assert eng._lib.mpx_pack_gconvw_weights(2016, 36, *[_p(v) for v in t], EPS, _p(w_hi), _p(w_lo), _p(scale), _p(shift)) == 0
+    assert eng._lib.mpx_pack_gconvw_weights(2016, 36, *[ptr(v) for v in t], EPS, ptr(w_hi), ptr(w_lo), ptr(scale), ptr(shift)) == 0
     dv = [v.to(eng.device) for v in (w_hi, w_lo, scale, shift)]
     b_hi, b_lo = _sentinel((3 * 49, 2016), eng.device), _sentinel((3 * 49, 2016), eng.device)
-    rc = eng._lib.mpx_gconvw3x3_bn_act(eng._h, _p(x_hi), _p(x_lo), *[_p(v) for v in dv], _p(b_hi), _p(b_lo), 3, 14, 2016, 36, 2016, 2016, 2, 1, eng._stream())
+    rc = eng._lib.mpx_gconvw3x3_bn_act(eng._h, ptr(x_hi), ptr(x_lo), *[ptr(v) for v in dv], ptr(b_hi), ptr(b_lo), 3, 14, 2016, 36, 2016, 2016, 2, 1, eng._stream())
     _lib.check(eng._h, rc, "mpx_gconvw3x3_bn_act")
     torch.cuda.synchronize()
     assert not torch.isnan(a_hi).any() and (a_hi != 0).any()
@@ -418,7 +352,7 @@ def test_the_stand_alone_grouped_entry_gives_an_engine_layers_bits(engines, sds)
 def test_the_stand_alone_grouped_entry_refuses_bad_arguments(eng, dev):
     z = torch.zeros(1 << 16, dtype=torch.float16, device=dev)
     f = torch.zeros(4096, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     run = eng._lib.mpx_gconvw3x3_bn_act
     ok = dict(B=1, hin=3, width=56, groups=1, pin=64, pout=64, stride=1)
 
@@ -442,10 +376,10 @@ def test_the_stand_alone_grouped_entry_refuses_bad_arguments(eng, dev):
     w = torch.zeros(56 * 56 * 9)
     h16, f32 = torch.zeros(64 * 512, dtype=torch.int16), torch.zeros(64)
     v = torch.ones(56)
-    assert pack(56, 1, _p(w), _p(v), _p(v), _p(v), _p(v), EPS, _p(h16), _p(h16.clone()), _p(f32), _p(f32.clone())) == 0
-    assert pack(56, 7, _p(w), _p(v), _p(v), _p(v), _p(v), EPS, _p(h16), _p(h16), _p(f32), _p(f32)) == -1        # 8 channels per group
-    assert pack(56, 1, None, _p(v), _p(v), _p(v), _p(v), EPS, _p(h16), _p(h16), _p(f32), _p(f32)) == -1
-    assert pack(56, 1, _p(w), None, _p(v), _p(v), _p(v), EPS, _p(h16), _p(h16), _p(f32), _p(f32)) == -1
+    assert pack(56, 1, ptr(w), ptr(v), ptr(v), ptr(v), ptr(v), EPS, ptr(h16), ptr(h16.clone()), ptr(f32), ptr(f32.clone())) == 0
+    assert pack(56, 7, ptr(w), ptr(v), ptr(v), ptr(v), ptr(v), EPS, ptr(h16), ptr(h16), ptr(f32), ptr(f32)) == -1        # 8 channels per group
+    assert pack(56, 1, None, ptr(v), ptr(v), ptr(v), ptr(v), EPS, ptr(h16), ptr(h16), ptr(f32), ptr(f32)) == -1
+    assert pack(56, 1, ptr(w), None, ptr(v), ptr(v), ptr(v), EPS, ptr(h16), ptr(h16), ptr(f32), ptr(f32)) == -1
 
 
 # ------------------------------------------------------------------------------------------------
@@ -500,24 +434,24 @@ def test_descriptors_groups_tiles_se_layers_and_refusals(engines, arch):
     assert abs(eng.flops_per_forward - 2.0 * ref.macs(arch)) <= 1e-9 * eng.flops_per_forward
     assert not eng.has_stem_table and eng.stem == "conv"
     lab = torch.zeros(224, 224, dtype=torch.int32, device=eng.device)
-    assert lib.mpx_stem_table_build(h, None, None, _p(lab), 1, None, None, None) == -2 and b"RegNetY" in lib.mpx_last_error(h)
+    assert lib.mpx_stem_table_build(h, None, None, ptr(lab), 1, None, None, None) == -2 and b"RegNetY" in lib.mpx_last_error(h)
     out = torch.zeros(8, dtype=torch.float16, device=eng.device)
-    assert lib.mpx_stem_conv_maxpool(h, _p(out), _p(out), 1, None) == -2 and b"7x7 stem" in lib.mpx_last_error(h)
+    assert lib.mpx_stem_conv_maxpool(h, ptr(out), ptr(out), 1, None) == -2 and b"7x7 stem" in lib.mpx_last_error(h)
 
 
 def test_set_conv_tile_18_on_an_8gf_layer_and_where_it_was_refused_before(engines, dev):
     eng = engines["regnet_y_8gf"]
-    i = _index(eng, "trunk_output.block3.block3-1.f.b.0")
+    i = layer_index(eng, "trunk_output.block3.block3-1.f.b.0")
     assert eng.groups[i] == 16 and eng.layers[i].cin // 16 == 56
     assert eng._lib.mpx_set_conv_tile(eng._h, i, 18) == 0 and eng._lib.mpx_get_conv_tile(eng._h, i) == 18
     assert eng._lib.mpx_set_conv_tile(eng._h, i, 16) == -1 and eng._lib.mpx_set_conv_tile(eng._h, i, 2) == -1
-    assert eng._lib.mpx_set_conv_tile(eng._h, _index(eng, "trunk_output.block3.block3-1.f.a.0"), 18) == -1
+    assert eng._lib.mpx_set_conv_tile(eng._h, layer_index(eng, "trunk_output.block3.block3-1.f.a.0"), 18) == -1
     for arch, grouped in (("resnet18", None), ("resnext50_32x4d", "layer1.0.conv2"), ("efficientnet_b0", None)):
         other = MaskedForwardEngine(arch, max_batch=2, device=0)
         try:
             assert other._lib.mpx_set_conv_tile(other._h, 1, 18) == -1 and b"grouped" in other._lib.mpx_last_error(other._h)
             if grouped:
-                j = _index(other, grouped)
+                j = layer_index(other, grouped)
                 assert other._lib.mpx_set_conv_tile(other._h, j, 18) == -1 and other._lib.mpx_get_conv_tile(other._h, j) == 16
             if arch == "efficientnet_b0":       # every SE layer of an EfficientNet engine keeps SiLU
                 assert len(other.ses) == 16 and other.se_acts == [0] * 16
@@ -608,12 +542,7 @@ def _run_layer(eng, sd, i, batch):
     if d.residual:
         rh, rl = split(torch.randn(batch, d.hout, d.hout, d.cout, generator=g, device=dev))
     if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
+        stage_stem_input(eng, xh, xl, batch)
         in_h = in_l = None
     else:
         in_h, in_l = _at_pitch(xh, pin), _at_pitch(xl, pin)
@@ -621,14 +550,14 @@ def _run_layer(eng, sd, i, batch):
     want = _layer_want(sd, d, eng.groups[i], merge(xh, xl).double(), merge(rh, rl).double() if d.residual else None)
     if fc:          # the fc writes fp32 logits
         out = torch.full((batch + 1, 1000), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
+        rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), None, None, None, None, ptr(out), batch, eng._stream())
         _lib.check(eng._h, rc, "mpx_conv_bn_act(fc)")
         ran = eng._lib.mpx_last_conv_kernels(eng._h)
         torch.cuda.synchronize()
         assert torch.isnan(out[batch]).all()
         return out[:batch].double().view(batch, 1, 1, 1000), want, ran
     oh, ol = _sentinel((batch + 1, d.hout, d.hout, pout), dev), _sentinel((batch + 1, d.hout, d.hout, pout), dev)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(res_h), _p(res_l), _p(oh), _p(ol), None, batch, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), ptr(res_h), ptr(res_l), ptr(oh), ptr(ol), None, batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_bn_act")
     ran = eng._lib.mpx_last_conv_kernels(eng._h)
     torch.cuda.synchronize()
@@ -657,7 +586,7 @@ SHAPES = _distinct_shapes()
 @pytest.mark.parametrize("arch,name", SHAPES, ids=["%s-%s" % s for s in SHAPES])
 def test_conv_shape_on_its_default_tile_and_on_every_tile_that_accepts_it(engines, sds, arch, name):
     eng, sd = engines[arch], sds[arch]
-    i = _index(eng, name)
+    i = layer_index(eng, name)
     d = eng.layers[i]
     default = eng._lib.mpx_get_conv_tile(eng._h, i)
     accepted = [t for t in DENSE_TILES + (16, 18) if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
@@ -673,7 +602,7 @@ def test_conv_shape_on_its_default_tile_and_on_every_tile_that_accepts_it(engine
             got, want, ran = _run_layer(eng, sd, i, batch)
             assert not torch.isnan(got).any(), (name, tile)
             err, scale = (got - want).abs().max().item(), want.abs().max().item()
-            bound = LAYER_TOL * math.sqrt(max(kdim, 4608) / 4608) * max(scale, 1.0)
+            bound = layer_bound(d, scale, k=kdim)
             print("%s %s %d->%d k%d s%d h%d res %d groups %d tile %d%s batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
                   % (arch, name, d.cin, d.cout, d.ksize, d.stride, d.hin, d.residual, eng.groups[i], tile, " (default)" if tile == default else "", batch, err, scale, bound, ran))
             assert err <= bound, "%s tile %d: max err %.3e (scale %.2f, bound %.3e)" % (name, tile, err, scale, bound)
@@ -686,98 +615,25 @@ def test_conv_shape_on_its_default_tile_and_on_every_tile_that_accepts_it(engine
 # ------------------------------------------------------------------------------------------------
 # 5. end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 @pytest.mark.parametrize("arch", ARCHS)
 def test_regnet_y_end_to_end(engines, sds, golden_dir, arch):
     """800MF / 1.6GF / 3.2GF: 4 felzenszwalb + 2 grid rows; 8GF: 3 felzenszwalb rows.  Scores by the MobileNetV2 rule (d = max |fp32 CPU loop -
     fp64|: bound 2e-5 when 4 d < 2e-5, else 4 d rounded up to one digit, never above 1e-4), all logits through the logits lens (4 d_L), every
     argmax equal."""
-    eng, sd = engines[arch], sds[arch]
-    lens = LogitsLens(arch)
-    rows = []
-    for kind, (img, seg, onoff, label, s64, logits64) in ref.e2e_rows(golden_dir, arch).items():
-        x = scorer.to_tensor_normalize(img)
-        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
-        top2 = np.sort(logits64, axis=1)[:, -2:]
-        gap = top2[:, 1] - top2[:, 0]
-        peaks = F.softmax(torch.from_numpy(logits64), 1).max(1)[0].numpy()
-        assert gap.min() >= 1e-3 and peaks.min() >= 0.05 and peaks.max() <= 0.95      # every row: tests/test_regnety_cpu.py holds the weights to it
-        err_cpu = float(np.abs(ref_score.astype(np.float64) - s64).max())
-        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        lens.add(kind, logits, ref_logits, logits64)
-        err_engine = float(np.abs(score.astype(np.float64) - s64).max())
-        err_both = float(np.abs(score.astype(np.float64) - ref_score.astype(np.float64)).max())
-        print("%s %s: %d masks, label %d, scores %.4f..%.4f" % (arch, kind, len(s64), label, ref_score.min(), ref_score.max()))
-        print("%s %s: max|d| engine vs fp64 %.3e, fp32 CPU loop vs fp64 (the yardstick) %.3e, engine vs fp32 CPU loop %.3e, smallest fp64 logit gap %.4f"
-              % (arch, kind, err_engine, err_cpu, err_both, gap.min()))
-        rows.append((kind, err_engine, err_cpu, err_both, pred, ref_pred, logits64.argmax(1)))
-        p_label, _ = eng.predict(img)
-        assert p_label == label
-    d = max(r[2] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
-    print("%s: yardstick distance %.3e over %d rows -> end-to-end bound %.1e" % (arch, d, sum(len(r[4]) for r in rows), bound))
-    for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
-        assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
-        assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
-    lens.check()
+    rows = [(kind,) + row for kind, row in ref.e2e_rows(golden_dir, arch).items()]
+    check_end_to_end(engines[arch], arch, Reference(ref, sds[arch], arch), rows,
+                     "%(arch)s: yardstick distance %(d).3e over %(n)d rows -> end-to-end bound %(bound).1e", segments=False, peaks=True)
 
 
 @pytest.mark.parametrize("arch", ("regnet_y_800mf", "regnet_y_8gf"))
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engines, golden_dir, arch):
-    eng = engines[arch]
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(3, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12))):       # 13 rows: two forwards of an 8-slot engine
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engines[arch], *ref.e2e_inputs(golden_dir, "felz"), (3, ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12)))))
 
 
 def test_api_on_a_regnet_y_engine(engines, sds, golden_dir):
     arch = "regnet_y_800mf"
-    eng, sd = engines[arch], sds[arch]
-    sd32 = ref.cast(sd, torch.float32)
-
-    def score_one(masked_chw, label):
-        with torch.no_grad():
-            logits = ref.forward(sd32, torch.from_numpy(masked_chw[None]), arch)
-        return F.softmax(logits, 1).numpy()[0][label]
-
-    img, seg = ref.e2e_inputs(golden_dir, "grid")
-    x = scorer.to_tensor_normalize(img)
-    with torch.no_grad():
-        label = int(ref.forward(sd32, x[None], arch).argmax(1)[0])
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(4, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND and (pred == ref_pred).all()
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want = score_one(scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
-    table_s, _table_p = api.SaliencySession(eng, x, label, segments=seg).table()
-    assert len(table_s) == S + 1
-    for f in range(0, S + 1, 49):
-        want = score_one(scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(table_s[f]) - float(want)) <= SCORE_BOUND
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=20, rng=random.Random(3))      # the loader holds one image: index 1
-    assert many == {i: api.validate(list(loader), eng, None, i, num_mask_samples=20, rng=random.Random(3)) for i in (1,)}
+    check_api(engines[arch], Reference(ref, sds[arch], arch), *ref.e2e_inputs(golden_dir, "grid"),
+              rows=4, same_pred=True, heatmaps=0, predict=False, table_step=49)
 
 
 @pytest.mark.parametrize("arch", ("regnet_y_800mf", "regnet_y_8gf"))
@@ -819,12 +675,12 @@ def test_regnet_y_error_paths(dev, sds):
         labels = torch.zeros(2, dtype=torch.int32, device=dev)
         score = torch.zeros(2, dtype=torch.float32, device=dev)
         pred = torch.zeros(2, dtype=torch.int32, device=dev)
-        assert lib.mpx_forward(h, _p(labels), _p(score), _p(pred), None, 2, eng._stream()) == -2 and b"weights not loaded" in lib.mpx_last_error(h)
+        assert lib.mpx_forward(h, ptr(labels), ptr(score), ptr(pred), None, 2, eng._stream()) == -2 and b"weights not loaded" in lib.mpx_last_error(h)
         eng.load_state_dict(sd, only=se_names[:-1])
-        assert lib.mpx_weights_complete(h) == 0 and lib.mpx_forward(h, _p(labels), _p(score), _p(pred), None, 2, eng._stream()) == -2
+        assert lib.mpx_weights_complete(h) == 0 and lib.mpx_forward(h, ptr(labels), ptr(score), ptr(pred), None, 2, eng._stream()) == -2
         eng.load_state_dict(sd, only=se_names[-1:])
         assert lib.mpx_weights_complete(h) == 1
-        assert lib.mpx_forward(h, _p(labels), _p(score), _p(pred), None, 2, eng._stream()) == 0
+        assert lib.mpx_forward(h, ptr(labels), ptr(score), ptr(pred), None, 2, eng._stream()) == 0
         torch.cuda.synchronize()
         assert torch.isfinite(score).all() and (score > 0).all()
         bad = dict(sd)

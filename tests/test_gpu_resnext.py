@@ -6,7 +6,6 @@ descriptors, tiles and refusals, and both networks end to end on the rows tests/
 The grouped launch does not cap its grid (ceil(M / 16) workgroups in x, a quarter of the channel blocks in y), so there is no capped-grid
 case to run."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -15,7 +14,9 @@ import torch.nn.functional as F
 
 import gconv_draws as gd
 import resnext_ref as ref
+from gpu_common import dev, Fenced, GENERIC, layer_bound, layer_index, merge, ptr, round_up_one_digit, SCORE_BOUND, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
 from logits_lens import LogitsLens
+from net_harness import stage_stem_input
 from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from oracle import scorer
@@ -23,32 +24,8 @@ from oracle import scorer
 pytestmark = pytest.mark.gpu
 
 ARCHS = ("resnext50_32x4d", "resnext101_32x8d")
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
 DENSE_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
 EPS = 1e-5
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev(mpx_lib):
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -60,45 +37,12 @@ def engines(dev):
         e.close()
 
 
-def _index(eng, name):
-    return [d.name.decode() for d in eng.layers].index(name)
-
-
-class Fenced:
-    """rows x width elements between two fences of FENCE_ROWS x width, everything prefilled with the sentinel."""
-
-    def __init__(self, rows, width, dev):
-        self.fence, self.rows, self.width = gd.FENCE_ROWS * width, rows, width
-        self.bits = torch.full((2 * self.fence + rows * width,), gd.SENTINEL_BITS, dtype=torch.int16, device=dev)
-        self.values = self.bits.view(torch.float16)
-
-    @property
-    def payload(self):
-        return self.values[self.fence:self.fence + self.rows * self.width].view(self.rows, self.width)
-
-    @property
-    def payload_bits(self):
-        return self.bits[self.fence:self.fence + self.rows * self.width].view(self.rows, self.width)
-
-    def problems(self):
-        out = []
-        front, back = self.bits[:self.fence] != gd.SENTINEL_BITS, self.bits[self.fence + self.rows * self.width:] != gd.SENTINEL_BITS
-        if front.any():
-            out.append("front fence: %d elements overwritten" % int(front.sum()))
-        if back.any():
-            out.append("back fence: %d elements overwritten, the first at %d behind the payload" % (int(back.sum()), int(back.nonzero().min())))
-        left = self.payload_bits == gd.SENTINEL_BITS
-        if left.any():
-            out.append("payload: %d elements never written, the first in pixel row %d" % (int(left.sum()), int(left.nonzero()[0, 0])))
-        return out
-
-
 def _launch_grouped(eng, d, x_hi, x_lo, batch):
     """mpx_conv_bn_act of grouped layer d over `batch` images -> fenced (hi, lo); the grouped kernel and nothing else must have run."""
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     rows = batch * d.hout * d.hout
     hi, lo = Fenced(rows, d.width, eng.device), Fenced(rows, d.width, eng.device)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(x_hi), _p(x_lo), None, None, _p(hi.payload), _p(lo.payload), None, batch, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(x_hi), ptr(x_lo), None, None, ptr(hi.payload), ptr(lo.payload), None, batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_bn_act(%s, batch %d)" % (d.name, batch))
     mask = eng._lib.mpx_last_conv_kernels(eng._h)
     torch.cuda.synchronize()
@@ -121,7 +65,7 @@ def test_grouped_layer_behind_fences_inside_the_per_element_bound(engines, d, ba
     same maps with twice the cg.  On the 7 x 7 maps a row is shorter than the MFMA's 16 pixels (a wave's pixels run on into the next rows
     and images); the stride-2 layers read odd windows (the last row's and column's windows hang over the map by the padding alone)."""
     eng = engines[d.arch]
-    e = eng.layers[_index(eng, d.name)]
+    e = eng.layers[layer_index(eng, d.name)]
     assert (e.cin, e.cout, e.ksize, e.stride, e.pad, e.hin, e.hout, e.relu, e.residual) == (d.width, d.width, 3, d.stride, 1, d.hin, d.hout, 1, 0)
     sd = synth.make_state_dict(d.arch)
     x = gd.draws(d, batch, device=eng.device)
@@ -254,25 +198,20 @@ def _run_dense(eng, sd, i, batch):
     if d.residual:
         rh, rl = split(torch.randn(batch, d.hout, d.hout, d.cout, generator=g, device=dev))
     if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
+        stage_stem_input(eng, xh, xl, batch)
         in_h = in_l = None
     else:
         in_h, in_l = xh, xl
     if last:
         out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
+        rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), None, None, None, None, ptr(out), batch, eng._stream())
         _lib.check(eng._h, rc, "mpx_conv_bn_act")
         torch.cuda.synchronize()
         got = out.double().view(batch, 1, 1, d.cout)
     else:
         oh = torch.full((batch + 1, d.hout, d.hout, d.cout), float("nan"), dtype=torch.float16, device=dev)
         ol = torch.full_like(oh, float("nan"))
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(rh), _p(rl), _p(oh), _p(ol), None, batch, eng._stream())
+        rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), ptr(rh), ptr(rl), ptr(oh), ptr(ol), None, batch, eng._stream())
         _lib.check(eng._h, rc, "mpx_conv_bn_act")
         torch.cuda.synchronize()
         assert torch.isnan(oh[batch]).all() and torch.isnan(ol[batch]).all(), "%s wrote past its last pixel" % d.name.decode()
@@ -288,7 +227,7 @@ def _check_dense(eng, sd, i, batch):
     got, want, ran = _run_dense(eng, sd, i, batch)
     assert not torch.isnan(got).any(), d.name
     err, scale = (got - want).abs().max().item(), want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d.cin * d.ksize * d.ksize, 4608) / 4608) * max(scale, 1.0)
+    bound = layer_bound(d, scale, k=d.cin * d.ksize * d.ksize)
     print("%s %s %d->%d k%d s%d h%d res %d default tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
           % (eng.arch, d.name.decode(), d.cin, d.cout, d.ksize, d.stride, d.hin, d.residual, tile, batch, err, scale, bound, ran))
     assert err <= bound, "%s batch %d: max err %.3e (scale %.2f, bound %.3e)" % (d.name.decode(), batch, err, scale, bound)
@@ -316,7 +255,7 @@ def test_every_distinct_dense_shape_on_its_default_tile(engines):
 
 
 def _run_dual(eng, sd, stage, batch):
-    i, j = _index(eng, "layer%d.0.conv3" % stage), _index(eng, "layer%d.0.downsample.0" % stage)
+    i, j = layer_index(eng, "layer%d.0.conv3" % stage), layer_index(eng, "layer%d.0.downsample.0" % stage)
     d3, dd = eng.layers[i], eng.layers[j]
     dev = eng.device
     g = torch.Generator(device=dev).manual_seed(77 * stage + batch)
@@ -324,7 +263,7 @@ def _run_dual(eng, sd, stage, batch):
     x = split(torch.randn(batch, dd.hin, dd.hin, dd.cin, generator=g, device=dev).clamp_min(0) * 1.5)
     oh = torch.full((batch + 1, d3.hout, d3.hout, d3.cout), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    rc = eng._lib.mpx_conv_dual_bn_act(eng._h, i, _p(t2[0]), _p(t2[1]), _p(x[0]), _p(x[1]), _p(oh), _p(ol), batch, eng._stream())
+    rc = eng._lib.mpx_conv_dual_bn_act(eng._h, i, ptr(t2[0]), ptr(t2[1]), ptr(x[0]), ptr(x[1]), ptr(oh), ptr(ol), batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_dual_bn_act")
     ran = eng._lib.mpx_last_conv_kernels(eng._h)
     torch.cuda.synchronize()
@@ -339,7 +278,7 @@ def _run_dual(eng, sd, stage, batch):
     got = merge(oh[:batch], ol[:batch]).double()
     assert not torch.isnan(got).any()
     err, scale = (got - want).abs().max().item(), want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d3.cin + dd.cin, 4608) / 4608) * max(scale, 1.0)
+    bound = layer_bound(d3, scale, k=d3.cin + dd.cin)
     print("%s layer%d.0 conv3 + downsample (k1, k2) = (%d, %d) batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
           % (eng.arch, stage, d3.cin, dd.cin, batch, err, scale, bound, ran))
     assert err <= bound
@@ -398,7 +337,7 @@ def test_the_persistent_kernels_themselves_run_the_shapes_new_to_them(engines):
             assert ran & (1 << own), "%s %s at batch %d ran kernels %#x, not tile %d's" % (arch, d.name.decode(), batch, ran, own)
             ran_by_tile.setdefault(own, []).append((d.cin, d.cout, d.hin))
         for stage in (1, 2, 3, 4):
-            d3 = eng.layers[_index(eng, "layer%d.0.conv3" % stage)]
+            d3 = eng.layers[layer_index(eng, "layer%d.0.conv3" % stage)]
             _k1, _k2, ran = _run_dual(eng, sd, stage, _round_batch(eng, d3.hout, d3.cout, 256))
             assert ran == 1 << 13, "%s layer%d.0 ran kernels %#x, not the persistent dual kernel" % (arch, stage, ran)
     print("persistent kernels on shapes of their own: %s" % ran_by_tile)
@@ -427,7 +366,7 @@ def test_the_square_conv3_layers_of_32x8d_on_tile_9_with_the_split_launch(engine
     eng, sd = engines[ARCHS[1]], synth.make_state_dict(ARCHS[1])
     shapes = []
     for stage in (1, 2, 3, 4):
-        i = _index(eng, "layer%d.1.conv3" % stage)
+        i = layer_index(eng, "layer%d.1.conv3" % stage)
         d = eng.layers[i]
         assert d.residual == 1 and d.cin == d.cout and eng._lib.mpx_get_conv_tile(eng._h, i) == 9
         batch = _split_batch(eng, d.hout, d.cout)
@@ -480,7 +419,7 @@ def test_descriptors_groups_tiles_and_tails(engines, arch):
     assert abs(eng.flops_per_forward - 2.0 * ref.macs(arch)) <= 1e-9 * eng.flops_per_forward
     assert eng.has_stem_table and eng.stem == "table"
     # the public packer sees the descriptor alone and stays the dense packer: it refuses a grouped layer's descriptor
-    d = eng.layers[_index(eng, "layer1.0.conv2")]
+    d = eng.layers[layer_index(eng, "layer1.0.conv2")]
     w = np.zeros((d.cout, d.cin // 32, 3, 3), dtype=np.float32)
     v = np.ones(d.cout, dtype=np.float32)
     hi = np.zeros(d.cout_pad * d.k_packed, dtype=np.uint16)
@@ -500,10 +439,10 @@ def test_groups_is_one_on_every_layer_of_another_engine(dev):
 def test_a_grouped_layer_refuses_a_residual_operand_and_wrong_weight_shapes(engines):
     eng = engines[ARCHS[0]]
     d = gd.layer(ARCHS[0], "layer4.1.conv2")
-    i = _index(eng, d.name)
+    i = layer_index(eng, d.name)
     x_hi, x_lo, _x = gd.draws(d, 1, device=eng.device)
     out = torch.zeros(49, d.width, dtype=torch.float16, device=eng.device)
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(x_hi), _p(x_lo), _p(out), _p(out), _p(out), _p(out.clone()), None, 1, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(x_hi), ptr(x_lo), ptr(out), ptr(out), ptr(out), ptr(out.clone()), None, 1, eng._stream())
     assert rc == -1 and b"residual" in eng._lib.mpx_last_error(eng._h)
     sd = dict(synth.make_state_dict(ARCHS[0]))
     sd[d.name + ".weight"] = torch.zeros(d.width, d.width, 3, 3)           # the dense shape
@@ -533,11 +472,6 @@ def test_default_max_batch_and_bytes_per_slot(dev):
 # ------------------------------------------------------------------------------------------------
 # 7. end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 @pytest.mark.parametrize("arch", ARCHS)
 def test_resnext_end_to_end(engines, golden_dir, arch):
     """resnext50_32x4d: 8 felzenszwalb + 4 grid rows through BOTH stagings (K0 + the MFMA stem, and the stem table); resnext101_32x8d: 4
@@ -568,7 +502,7 @@ def test_resnext_end_to_end(engines, golden_dir, arch):
         p_label, _ = eng.predict(img)
         assert p_label == label
     d = max(r[3] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
+    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(round_up_one_digit(4 * d), SCORE_TOL)
     print("%s: yardstick distance %.3e over %d rows -> end-to-end bound %.1e" % (arch, d, sum(len(r[5]) for r in rows), bound))
     for kind, stem, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
         assert err_engine <= bound and err_both <= bound, (kind, stem, err_engine, err_both, bound)

@@ -2,12 +2,12 @@
 the weight formula (masks.rise_weights) BIT FOR BIT on the staged hi / lo planes, binary weights against mpx_mask_apply_normalize bit for bit,
 the saliency entries against an fp32 emulation of their written order (bit for bit) and the fp64 sum (derived bound, rise_ref), the whole path
 against the CPU forward, and the refusals.  resnet18 with max_batch = 8 unless another engine is named."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_common import dev, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError, rank_segments
 from oracle import scorer
@@ -18,16 +18,6 @@ pytestmark = pytest.mark.gpu
 IMG, PAD = 224, 230
 SENTINEL = 0x5A3C           # fp16 bits of 199.5: neither 0 nor anything a normalised pixel times a weight splits into at every element
 SCORE_TOL = 1e-4            # the project's tolerance of a score against the CPU forward
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

@@ -9,13 +9,13 @@
 There are no tolerances here beyond the project's SCORE_TOL and the two bounds derived below (head_row_sum_bound, the all-classes sum).
 Measured on one MI355X: every bit comparison exact; max |row sum - 1| 9.4e-8 against the bound 1.37e-6; the scores at most 6.6e-7 from the
 CPU forward; the all-classes sum at most 0.07 of its bound; the 69 tests take 4 s."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_common import dev, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from oracle import scorer
@@ -33,18 +33,8 @@ MPX_E_ARG, MPX_E_STATE = -1, -2
 M_MAX, K_MAX = 65, 2 * T + 1
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def bits(a):
     return np.ascontiguousarray(a).view(np.int32)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

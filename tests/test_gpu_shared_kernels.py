@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 import shared_kernel_draws as draws
+from gpu_common import dev, merge, ptr as _p, split  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from oracle import scorer
@@ -25,20 +26,6 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64
 SENTINEL = -1234567
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
 
 
 def guarded(n, dtype, dev):
@@ -54,12 +41,6 @@ def bands_untouched(buf, n):
     if buf.dtype == torch.int32:
         return bool((front == SENTINEL).all() and (back == SENTINEL).all())
     return bool(torch.isnan(front).all() and torch.isnan(back).all())
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 def _smallnet_sd(arch, golden_dir):

@@ -18,54 +18,22 @@ Bounds.
   MI355X: d = 5.7e-07 (shufflenet_v2_x1_0), 6.1e-07 (shufflenet_v2_x0_5); 4 d < 2e-05, so the bound is 2e-05 for both.  The same argmax on EVERY row (tests/test_shufflenet_cpu.py
   asserts a top-two fp64 margin >= 1e-3 on exactly these rows).  The test prints every figure before it asserts."""
 import ctypes as C
-import math
-import random
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import shufflenet_ref as ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
-from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, rank_segments
-from logits_lens import LogitsLens
+from gpu_common import accepted_tiles, dev, FALLBACK, GENERIC, merge, pitch_of, ptr, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import assert_layer_close, check_api, check_end_to_end, check_position_independence, conv_tile, e2e_rows, Reference, stage_stem_input
+from network_interpretation_imagenet_amd import _lib, synth
+from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-GENERIC = {0, 1, 2, 4, 7}
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 EPS = 1e-5
 X10, X05 = "shufflenet_v2_x1_0", "shufflenet_v2_x0_5"
-
-
-def _p(t, offset=0):
-    return C.c_void_p(t.data_ptr() + 2 * offset) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def pitch_of(c):
-    return -(-c // 32) * 32
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")
@@ -139,8 +107,8 @@ def _shuffle_case(eng, dev, bf, hp, batch, hw, mode, seed):
     guard = 64
     yh = torch.full((n_out + guard,), nan, dtype=torch.float16, device=dev)
     yl = torch.full_like(yh, nan)
-    rc = eng._lib.mpx_shuffle2_concat(eng._h, _p(a_ptr[0], a_ptr[2]), _p(a_ptr[1], a_ptr[2]), a_pitch, _p(b_ptr[0], b_ptr[2]), _p(b_ptr[1], b_ptr[2]),
-                                      b_pitch, _p(yh), _p(yl), batch, hw, bf, hp, eng._stream())
+    rc = eng._lib.mpx_shuffle2_concat(eng._h, ptr(a_ptr[0], a_ptr[2]), ptr(a_ptr[1], a_ptr[2]), a_pitch, ptr(b_ptr[0], b_ptr[2]), ptr(b_ptr[1], b_ptr[2]),
+                                      b_pitch, ptr(yh), ptr(yl), batch, hw, bf, hp, eng._stream())
     _lib.check(eng._h, rc, "mpx_shuffle2_concat")
     torch.cuda.synchronize()
     assert torch.isnan(yh[n_out:]).all() and torch.isnan(yl[n_out:]).all()          # the sentinel behind y is intact
@@ -215,7 +183,7 @@ def _dw_check(eng, xh, xl, wt, sc, sh, phys, pitch, hin, stride, what, images=No
     n_out = batch * ho * ho * pitch
     oh = torch.full((n_out + guard,), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    rc = eng._lib.mpx_dwconv3x3_bn(eng._h, _p(xh), _p(xl), _p(wt), _p(sc), _p(sh), _p(oh), _p(ol), batch, hin, pitch, stride, eng._stream())
+    rc = eng._lib.mpx_dwconv3x3_bn(eng._h, ptr(xh), ptr(xl), ptr(wt), ptr(sc), ptr(sh), ptr(oh), ptr(ol), batch, hin, pitch, stride, eng._stream())
     _lib.check(eng._h, rc, "mpx_dwconv3x3_bn")
     torch.cuda.synchronize()
     assert torch.isnan(oh[n_out:]).all() and torch.isnan(ol[n_out:]).all()              # the neighbours behind the planes are untouched
@@ -390,8 +358,7 @@ def test_topology_and_defaults(mpx_lib, dev, sds, arch):
                 else:
                     assert (ypitch, yoff) == (shp, 0)
             if (pitch, off) != (d.cin, 0) or ypitch != d.cout:              # slices and padded layers: the generic tiles only
-                accepted = {t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0}
-                eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+                accepted = set(accepted_tiles(eng, i))
                 assert accepted == GENERIC, (name, accepted)
             assert eng._lib.mpx_get_conv_tile(eng._h, i) in GENERIC | {10, 13, 9}
         assert (in_slices, out_slices, whole_maps) == (13, 6, 5)
@@ -477,12 +444,7 @@ def _run_layer(eng, sd, i, batch, seed):
     x = torch.randn(batch, d.hin, d.hin, d.cin, generator=g).clamp_min(-0.5) * 1.5
     if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
         xh, xl = split(x.to(dev))
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
+        stage_stem_input(eng, xh, xl, batch)
         in_h = in_l = None
         (ypitch, yoff, stored) = _layout(eng, i)[1]
     else:
@@ -494,13 +456,13 @@ def _run_layer(eng, sd, i, batch, seed):
         xh, xl = in_h[..., phys.to(dev)], in_l[..., phys.to(dev)]
     if last:
         out = torch.full((batch, d.cout), nan, dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
+        rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), None, None, None, None, ptr(out), batch, eng._stream())
         _lib.check(eng._h, rc, "mpx_conv_bn_act")
         got = out.double().view(batch, 1, 1, d.cout)
     else:
         oh = torch.full((batch, d.hout, d.hout, ypitch), nan, dtype=torch.float16, device=dev)
         ol = torch.full_like(oh, nan)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, _p(oh), _p(ol), None, batch, eng._stream())
+        rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), None, None, ptr(oh), ptr(ol), None, batch, eng._stream())
         _lib.check(eng._h, rc, "mpx_conv_bn_act")
         torch.cuda.synchronize()
         for t in (oh, ol):
@@ -514,23 +476,12 @@ def _run_layer(eng, sd, i, batch, seed):
 
 
 def _check(eng, sd, i, batch, tile=-1):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
+    with conv_tile(eng, i, tile):
         got, want = _run_layer(eng, sd, i, batch, seed=1000 * i + batch)
         ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
     d = eng.layers[i]
-    name = d.name.decode()
-    assert not torch.isnan(got).any(), (name, tile)
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d.k_packed, 4608) / 4608) * max(scale, 1.0)
-    print("%s %d->%d k%d h%d K %d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-          % (name, d.cin, d.cout, d.ksize, d.hin, d.k_packed, tile, batch, err, scale, bound, ran))
-    assert err <= bound, "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran
+    assert not torch.isnan(got).any(), (d.name, tile)
+    return assert_layer_close(d, got, want, tile, batch, ran, "%d->%d k%d h%d K %d " % (d.cin, d.cout, d.ksize, d.hin, d.k_packed))
 
 
 @pytest.mark.parametrize("arch", ref.ARCHS)
@@ -548,8 +499,7 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engines, sds, ar
         if key in seen:
             continue
         seen.add(key)
-        accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+        accepted = accepted_tiles(eng, i)
         default = eng._lib.mpx_get_conv_tile(eng._h, i)
         assert default in accepted and GENERIC <= set(accepted), (d.name, accepted)
         in_slices += off > 0
@@ -570,110 +520,23 @@ def test_every_distinct_conv_shape_on_every_accepted_tile(small_engines, sds, ar
 # ------------------------------------------------------------------------------------------------
 # end to end
 # ------------------------------------------------------------------------------------------------
-def _round_up_one_digit(v):
-    e = math.floor(math.log10(v))
-    return math.ceil(v / 10 ** e - 1e-9) * 10 ** e
-
-
 @pytest.mark.parametrize("arch", ref.E2E_ARCHS)
 def test_end_to_end(engines, sds, golden_dir, arch):
     """Logits lens (tests/logits_lens.py): all 1000 logits of every row against fp64, bound 4 d_L with d_L = the fp32 CPU loop's distance.  Measured on one MI355X: shufflenet_v2_x1_0 d_L 6.14e-06, engine 1.01e-05 (1.65); shufflenet_v2_x0_5 d_L 5.61e-06, engine 9.00e-06 (1.60)."""
-    lens = LogitsLens(arch)
-    eng, sd = engines[arch], sds[arch]
-    rows = []
-    for kind, m, seed in ref.E2E_CASES:
-        img, seg = ref.e2e_inputs(golden_dir, kind)
-        x = scorer.to_tensor_normalize(img)
-        label, prob = ref.predict(sd, arch, x)
-        assert 0.05 <= prob.max() <= 0.95
-        S = len(np.unique(seg))
-        onoff = synth.random_onoff(m, S, seed=seed)
-        _o, score, pred, logits = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        ref_score, ref_pred, ref_logits = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label, return_logits=True)
-        s64, logits64 = ref.score_masks_fp64(sd, arch, x, seg, onoff, label)
-        lens.add(kind, logits, ref_logits, logits64)
-        top2 = np.sort(logits64, axis=1)[:, -2:]
-        gap = top2[:, 1] - top2[:, 0]
-        err_engine = float(np.abs(score.astype(np.float64) - s64).max())
-        err_cpu = float(np.abs(ref_score.astype(np.float64) - s64).max())
-        err_both = float(np.abs(score.astype(np.float64) - ref_score.astype(np.float64)).max())
-        print("%s %s: %d masks, S %d, label %d, scores %.4f..%.4f" % (arch, kind, m, S, label, ref_score.min(), ref_score.max()))
-        print("%s %s: max|d| engine vs fp64 %.3e, fp32 CPU loop vs fp64 (the yardstick) %.3e, engine vs fp32 CPU loop %.3e, smallest fp64 logit gap %.4f"
-              % (arch, kind, err_engine, err_cpu, err_both, gap.min()))
-        assert gap.min() >= 1e-3
-        rows.append((kind, err_engine, err_cpu, err_both, pred, ref_pred, logits64.argmax(1)))
-        p_label, _ = eng.predict(img)
-        assert p_label == label
-    d = max(r[2] for r in rows)
-    bound = SCORE_BOUND if 4 * d < SCORE_BOUND else min(_round_up_one_digit(4 * d), SCORE_TOL)
-    print("%s: yardstick distance %.3e over the 28 rows -> end-to-end bound %.1e" % (arch, d, bound))
-    for kind, err_engine, _err_cpu, err_both, pred, ref_pred, arg64 in rows:
-        assert err_engine <= bound and err_both <= bound, (kind, err_engine, err_both, bound)
-        assert (pred == arg64).all() and (pred == ref_pred).all()          # every row
-    lens.check()
+    r = Reference(ref, sds[arch], arch)
+    check_end_to_end(engines[arch], arch, r, e2e_rows(r, ref.E2E_CASES, golden_dir),
+                     "%(arch)s: yardstick distance %(d).3e over the 28 rows -> end-to-end bound %(bound).1e")
 
 
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engines, golden_dir):
-    eng = engines[X10]
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(8, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699))):
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engines[X10], *ref.e2e_inputs(golden_dir, "felz"), (8, ((1, 0, (0,)), (37, 41, (0, 5, 36)), (700, 44, (3, 511, 512, 699)))))
 
 
 # ------------------------------------------------------------------------------------------------
 # API, profile and errors
 # ------------------------------------------------------------------------------------------------
-def _score_one(sd32, arch, masked_chw, label):
-    with torch.no_grad():
-        logits = ref.forward(sd32, arch, torch.from_numpy(masked_chw[None]))
-    return F.softmax(logits, 1).numpy()[0][label], int(logits.argmax(1)[0])
-
-
 def test_api_on_a_shufflenet_engine(engines, sds, golden_dir):
-    arch = X10
-    eng, sd = engines[arch], sds[arch]
-    sd32 = ref.cast(sd, torch.float32)
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    x = scorer.to_tensor_normalize(img)
-    label, _ = ref.predict(sd, arch, x)
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(12, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, arch, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    rank_map = rank_segments(seg)[0]
-    heat, n_ok = shard.heatmap_sharded(eng, img, rank_map, onoff, label)
-    want_heat = sum((onoff[i][rank_map] for i in range(12) if pred[i] == label), np.zeros((224, 224)))
-    assert n_ok == int((pred == label).sum()) and np.array_equal(heat.cpu().numpy().astype(np.float64), want_heat.astype(np.float64))
-    p_label, p_prob = eng.predict(img)
-    assert p_label == label and abs(float(p_prob.sum()) - 1.0) < 1e-5
-    # the reference-named entry points
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want, _ = _score_one(sd32, arch, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
-    table_s, _table_p = api.SaliencySession(eng, x, label, segments=seg).table()
-    assert len(table_s) == S + 1
-    for f in range(0, S + 1, 23):
-        want, _want_p = _score_one(sd32, arch, scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(table_s[f]) - float(want)) <= SCORE_BOUND
-    many = api.validate_many(list(loader), eng, None, [1], num_mask_samples=20, rng=random.Random(3))
-    one = api.validate(list(loader), eng, None, 1, num_mask_samples=20, rng=random.Random(3))
-    assert many == {1: one}
+    check_api(engines[X10], Reference(ref, sds[X10], X10), *ref.e2e_inputs(golden_dir, "felz"), heatmaps=1, table_step=23)
 
 
 def test_profile_lists_the_depthwise_and_shuffle_launches(engines, dev):
@@ -700,10 +563,10 @@ def test_error_paths(small_engines, mpx_lib, dev, sds):
     eng = small_engines[X10]
     z = torch.zeros(8192, dtype=torch.float16, device=dev)
     f = torch.zeros(2048, dtype=torch.float32, device=dev)
-    a, b = _p(z), _p(f)
+    a, b = ptr(z), ptr(f)
     odd = C.c_void_p(z.data_ptr() + 2)
     sh = eng._lib.mpx_shuffle2_concat
-    assert sh(eng._h, a, a, 64, a, a, 64, _p(z, 4096), _p(z, 4096), 1, 2, 58, 64, None) == 0
+    assert sh(eng._h, a, a, 64, a, a, 64, ptr(z, 4096), ptr(z, 4096), 1, 2, 58, 64, None) == 0
     torch.cuda.synchronize()
     assert sh(eng._h, None, a, 64, a, a, 64, a, a, 1, 2, 58, 64, None) == -1            # null planes
     assert sh(eng._h, a, a, 64, a, a, 64, a, None, 1, 2, 58, 64, None) == -1
@@ -719,7 +582,7 @@ def test_error_paths(small_engines, mpx_lib, dev, sds):
     assert sh(eng._h, odd, a, 64, a, a, 64, a, a, 1, 2, 58, 64, None) == -1             # misaligned planes
     assert sh(eng._h, a, a, 64, a, a, 64, a, odd, 1, 2, 58, 64, None) == -1
     dw = eng._lib.mpx_dwconv3x3_bn
-    assert dw(eng._h, a, a, b, b, b, _p(z, 4096), _p(z, 4096), 1, 4, 8, 1, None) == 0
+    assert dw(eng._h, a, a, b, b, b, ptr(z, 4096), ptr(z, 4096), 1, 4, 8, 1, None) == 0
     torch.cuda.synchronize()
     assert dw(eng._h, None, a, b, b, b, a, a, 1, 4, 8, 1, None) == -1                   # null planes
     assert dw(eng._h, a, a, None, b, b, a, a, 1, 4, 8, 1, None) == -1                   # null weights
@@ -741,10 +604,10 @@ def test_error_paths(small_engines, mpx_lib, dev, sds):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(zi), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(zi), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     buf = torch.zeros(64, dtype=torch.float16, device=dev)
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(buf), _p(buf), 1, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(buf), ptr(buf), 1, None) == -2
     for bad in (9000, 9001, 9011, 9999):
         h = C.c_void_p()
         assert mpx_lib.mpx_create(bad, 2, 0, C.byref(h)) == -1 and not h.value
@@ -770,7 +633,7 @@ def test_error_paths(small_engines, mpx_lib, dev, sds):
         labels = torch.zeros(1, dtype=torch.int32, device=dev)
         score = torch.zeros(1, device=dev)
         pred = torch.zeros(1, dtype=torch.int32, device=dev)
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == -2
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == -2
         with pytest.raises((KeyError, ValueError)):
             fresh.load_state_dict(sds[X10])
         fresh.load_state_dict(sds[X05], only=[d.name.decode() for d in fresh.dwconvs])

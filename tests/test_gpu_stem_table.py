@@ -2,7 +2,6 @@
 replaces -- K0 + the MFMA stem conv + max pool of the engine, and the oracle's normalise -> mask -> conv1 -> bn1 -> relu -> maxpool
 (generate_gp_training_data_imagenet.py:598-599,234-246 through torchvision's ResNet.forward) in fp64 -- on grid, felzenszwalb,
 single-segment and pathological (pixel-noise) label maps, and end to end against the conv-stem engine and the CPU loop."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -10,15 +9,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_common import ptr as _p
 from network_interpretation_imagenet_amd import synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 @pytest.fixture(scope="module")

@@ -15,6 +15,8 @@ import torch
 import torch.nn.functional as F
 
 import vgg_ref
+from gpu_common import accepted_tiles, dev, FALLBACK, LAYER_TOL, merge, ptr, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import check_conv_layer
 from network_interpretation_imagenet_amd import _lib, api, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from logits_lens import LogitsLens
@@ -22,34 +24,7 @@ from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
-SCORE_TOL = 1e-4
 SCORE_TOL_TIGHT = 2e-5
-LAYER_TOL = 4e-6            # relative to max(|want|, 1): the tolerance of test_gpu_parity's per-layer sweeps (K <= 4608) ...
-LAYER_TOL_K = 4608          # ... grown with sqrt(K / 4608) beyond: fp32 accumulation error grows as sqrt(K), and classifier.0 has K = 25088
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14)
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
 _ENGINES = {}
 
 
@@ -88,55 +63,9 @@ def _ref_layer(sd, d, x_nchw64):
     return F.relu(y) if d.relu else y
 
 
-def _run_layer(eng, i, batch, seed):
-    """One mpx_conv_bn_act of layer i on random post-ReLU-like inputs; -> (got, want) as [B][ho][ho][cout] f64 on the device."""
-    d = eng.layers[i]
-    dev = eng.device
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(batch, d.hin, d.hin, d.cin, generator=g).clamp_min(-0.5) * 1.5).to(dev)
-    xh, xl = split(x)
-    if i == 0:      # the first layer reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
-        in_h = in_l = None
-    else:
-        in_h, in_l = xh, xl
-    if d.hout == 1 and i == len(eng.layers) - 1:
-        out = torch.full((batch, d.cout), float("nan"), dtype=torch.float32, device=dev)
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, None, None, _p(out), batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = out.double().view(batch, 1, 1, d.cout)
-    else:
-        oh = torch.full((batch, d.hout, d.hout, d.cout), float("nan"), dtype=torch.float16, device=dev)
-        ol = torch.full_like(oh, float("nan"))
-        rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), None, None, _p(oh), _p(ol), None, batch, eng._stream())
-        _lib.check(eng._h, rc, "mpx_conv_bn_act")
-        got = merge(oh, ol).double()
-    torch.cuda.synchronize()
-    want = _ref_layer(synth.make_state_dict(eng.arch), d, merge(xh, xl).double().permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
-    return got, want
-
-
 def _check(eng, i, batch, tile=-1):
-    rc = eng._lib.mpx_set_conv_tile(eng._h, i, tile)
-    assert rc == 0, eng._lib.mpx_last_error(eng._h)
-    try:
-        got, want = _run_layer(eng, i, batch, seed=1000 * i + batch)
-        ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
-    name = eng.layers[i].name.decode()
-    assert not torch.isnan(got).any(), name
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    d = eng.layers[i]
-    tol = LAYER_TOL * max(1.0, (d.cin * d.ksize * d.ksize / LAYER_TOL_K) ** 0.5)
-    assert err <= tol * max(scale, 1.0), "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran
+    sd = synth.make_state_dict(eng.arch)
+    return check_conv_layer(eng, i, batch, lambda d, x64, _r64: _ref_layer(sd, d, x64), tile, fields=None)[0]
 
 
 VGG16_CONVS = ["features.%d" % i for i in (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)] + ["classifier.0", "classifier.3", "classifier.6"]
@@ -178,11 +107,7 @@ def test_vgg_every_layer_default_tile(engines, arch, name):
 def test_vgg16_every_accepted_tile(engines, name):
     eng = _engine(engines, "vgg16")
     i = [d.name.decode() for d in eng.layers].index(name)
-    accepted = []
-    for t in ALL_TILES:
-        if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0:
-            accepted.append(t)
-    eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+    accepted = accepted_tiles(eng, i)
     assert {0, 1, 2, 4, 7} <= set(accepted)
     for t in accepted:
         ran = _check(eng, i, 3, tile=t)
@@ -218,13 +143,13 @@ def test_maxpool2x2s2_bit_exact(engines, dev, hin, c, batch):
     xh, xl = split(x.to(dev))
     oh = torch.full((batch, hin // 2, hin // 2, c), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    rc = eng._lib.mpx_maxpool2x2s2(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hin, c, eng._stream())
+    rc = eng._lib.mpx_maxpool2x2s2(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hin, c, eng._stream())
     _lib.check(eng._h, rc, "mpx_maxpool2x2s2")
     torch.cuda.synchronize()
     want = F.max_pool2d(merge(xh, xl).permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)
     assert torch.equal(merge(oh, ol), want)
-    assert eng._lib.mpx_maxpool2x2s2(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hin + 1, c, None) == -1
-    assert eng._lib.mpx_maxpool2x2s2(eng._h, _p(xh), _p(xl), _p(oh), _p(ol), batch, hin, c - 4, None) == -1
+    assert eng._lib.mpx_maxpool2x2s2(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hin + 1, c, None) == -1
+    assert eng._lib.mpx_maxpool2x2s2(eng._h, ptr(xh), ptr(xl), ptr(oh), ptr(ol), batch, hin, c - 4, None) == -1
 
 
 # ------------------------------------------------------------------------------------------------
@@ -243,7 +168,7 @@ def test_first_layer_from_stage_masks(engines, dev, golden_dir, seg_kind, m):
     d = eng.layers[0]
     oh = torch.full((m, 224, 224, 64), float("nan"), dtype=torch.float16, device=dev)
     ol = torch.full_like(oh, float("nan"))
-    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, 0, None, None, None, None, _p(oh), _p(ol), None, m, eng._stream()), "conv")
+    _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, 0, None, None, None, None, ptr(oh), ptr(ol), None, m, eng._stream()), "conv")
     torch.cuda.synchronize()
     staged = merge(*split(xf)).double()                 # what the staging holds: the masked normalised image rounded to hi + lo
     want = _ref_layer(synth.make_state_dict("vgg16_bn"), d, staged).permute(0, 2, 3, 1)
@@ -352,8 +277,8 @@ def test_vgg_error_paths(engines, mpx_lib, dev):
     im = torch.zeros(224, 224, 3, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(z), _p(z), 1, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(z), ptr(z), 1, None) == -2
     hi, lo = C.c_void_p(1), C.c_void_p(1)
     assert eng._lib.mpx_stem_planes(eng._h, C.byref(hi), C.byref(lo)) == 0 and not hi.value and not lo.value
     h = C.c_void_p()

@@ -11,7 +11,6 @@ rows: DESIGN.md 22's bound (tests/cnext_draws.py), and the bits of mpx_layernorm
 printed next to the yardstick (fp32 CPU loop against fp64), every argmax equal, all logits within 4 d_L (tests/logits_lens.py).
 Measured on one MI355X: DESIGN.md 23 has the figures; the tests print them on every run."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -21,53 +20,16 @@ import torch.nn.functional as F
 import attn_draws as draws
 import cnext_draws
 import vit_ref as ref
-from network_interpretation_imagenet_amd import _lib, api, shard, synth
+from gpu_common import accepted_tiles, bits, dev, dev_view, FALLBACK, FencedPair, GENERIC, LAYER_TOL, merge, ptr, SCORE_BOUND, SCORE_TOL, split  # noqa: F401  (dev is a fixture)
+from net_harness import assert_layer_close, check_api, check_position_independence, conv_tile, Reference, stage_stem_input
+from network_interpretation_imagenet_amd import _lib, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine
 from logits_lens import LogitsLens
 from oracle import scorer
 
 pytestmark = pytest.mark.gpu
 
-SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
-SCORE_BOUND = 2e-5          # ... and its end-to-end bound
-LAYER_TOL = 4e-6            # relative to max(|want|, 1), times sqrt(max(K, 4608) / 4608)
-ALL_TILES = (0, 1, 2, 4, 6, 7, 9, 10, 12, 13, 14, 16)
-GENERIC = {0, 1, 2, 4, 7}
-FALLBACK = {9: 2, 10: 7, 12: 6, 13: 2, 14: 7}        # the small-tile kernel a persistent / 256x256 launch may hand work to
 EPS = 1e-6
-FENCE = 256                 # sentinel rows in front of and behind every output plane
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def split(x):
-    hi = x.to(torch.float16)
-    lo = (x - hi.float()).to(torch.float16)
-    return hi.contiguous(), lo.contiguous()
-
-
-def merge(hi, lo):
-    return hi.float() + lo.float()
-
-
-def bits(t):
-    return t.view(torch.int16)
-
-
-def dev_view(ptr, n, dev):
-    class _V:
-        __cuda_array_interface__ = {"data": (ptr.value, False), "shape": (n,), "typestr": "<f4", "version": 2}
-    return torch.as_tensor(_V(), device=dev).clone().cpu()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "gpu tests need an MI355X"
-    return torch.device("cuda", 0)
-
-
 @pytest.fixture(scope="module")
 def sds():
     return {a: synth.make_state_dict(a) for a in ref.ARCHS}
@@ -84,27 +46,6 @@ def engines(mpx_lib, dev, sds):
 @pytest.fixture(scope="module")
 def b16(engines):
     return engines["vit_b_16"]
-
-
-class Fenced:
-    """A pair of output planes of `rows` x `c` elements with FENCE sentinel rows in front of and behind each."""
-
-    def __init__(self, rows, c, dev):
-        self.rows, self.c = rows, c
-        self.hi = torch.full(((rows + 2 * FENCE) * c,), float("nan"), dtype=torch.float16, device=dev)
-        self.lo = torch.full_like(self.hi, float("nan"))
-
-    def ptrs(self):
-        off = FENCE * self.c * 2
-        return C.c_void_p(self.hi.data_ptr() + off), C.c_void_p(self.lo.data_ptr() + off)
-
-    def result(self):
-        torch.cuda.synchronize()
-        a, b = FENCE * self.c, (FENCE + self.rows) * self.c
-        for t in (self.hi, self.lo):
-            assert torch.isnan(t[:a]).all() and torch.isnan(t[b:]).all(), "a sentinel row was written"
-        assert not torch.isnan(self.hi[a:b]).any() and not torch.isnan(self.lo[a:b]).any()
-        return self.hi[a:b].clone(), self.lo[a:b].clone()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -189,9 +130,9 @@ def _attn_run(eng, x, heads, dev, max_blocks=0):
     b, t, _ = x.shape
     d = heads * 64
     xh, xl = split(torch.from_numpy(x).to(dev))
-    out = Fenced(b * t, d, dev)
+    out = FencedPair(b * t, d, dev)
     oh, ol = out.ptrs()
-    rc = eng._lib.mpx_attention(eng._h, _p(xh), _p(xl), oh, ol, b, t, heads, max_blocks, eng._stream())
+    rc = eng._lib.mpx_attention(eng._h, ptr(xh), ptr(xl), oh, ol, b, t, heads, max_blocks, eng._stream())
     _lib.check(eng._h, rc, "mpx_attention")
     yh, yl = out.result()
     return yh.view(b, t, d).cpu(), yl.view(b, t, d).cpu()
@@ -271,7 +212,7 @@ def test_a_row_of_equal_logits_returns_the_mean_of_v(b16, dev, t):
 def test_attention_refusals(b16, engines, dev):
     eng = b16
     z = torch.zeros(1 << 16, dtype=torch.float16, device=dev)
-    a = _p(z)
+    a = ptr(z)
     call = eng._lib.mpx_attention
     assert call(eng._h, a, a, a, a, 1, 4, 1, 0, None) == 0
     torch.cuda.synchronize()
@@ -286,8 +227,8 @@ def test_attention_refusals(b16, engines, dev):
     r = MaskedForwardEngine("resnet18", max_batch=2, device=0)
     try:
         f = torch.zeros(4096, dtype=torch.float32, device=dev)
-        assert r._lib.mpx_tokens_assemble(r._h, a, a, _p(f), _p(f), a, a, 1, 4, 64, 0, None) == -2 and b"ViT" in r._lib.mpx_last_error(r._h)
-        assert r._lib.mpx_load_tokens(r._h, _p(f.cpu()), _p(f.cpu())) == -2
+        assert r._lib.mpx_tokens_assemble(r._h, a, a, ptr(f), ptr(f), a, a, 1, 4, 64, 0, None) == -2 and b"ViT" in r._lib.mpx_last_error(r._h)
+        assert r._lib.mpx_load_tokens(r._h, ptr(f.cpu()), ptr(f.cpu())) == -2
     finally:
         r.close()
 
@@ -298,10 +239,10 @@ def test_attention_refusals(b16, engines, dev):
 def _tok_run(eng, x, cls, pos, dev, max_blocks=0):
     b, t, d = x.shape[0], pos.shape[0], pos.shape[1]
     xh, xl = split(torch.from_numpy(np.ascontiguousarray(x)).to(dev)) if t > 1 else (torch.zeros(8, dtype=torch.float16, device=dev),) * 2
-    out = Fenced(b * t, d, dev)
+    out = FencedPair(b * t, d, dev)
     oh, ol = out.ptrs()
     c, p = torch.from_numpy(cls).to(dev), torch.from_numpy(pos).to(dev)
-    rc = eng._lib.mpx_tokens_assemble(eng._h, _p(xh), _p(xl), _p(c), _p(p), oh, ol, b, t, d, max_blocks, eng._stream())
+    rc = eng._lib.mpx_tokens_assemble(eng._h, ptr(xh), ptr(xl), ptr(c), ptr(p), oh, ol, b, t, d, max_blocks, eng._stream())
     _lib.check(eng._h, rc, "mpx_tokens_assemble")
     yh, yl = out.result()
     return yh.view(b, t, d).cpu(), yl.view(b, t, d).cpu()
@@ -328,7 +269,7 @@ def test_tokens_assemble_refusals(b16, dev):
     eng = b16
     z = torch.zeros(4096, dtype=torch.float16, device=dev)
     f = torch.zeros(4096, dtype=torch.float32, device=dev)
-    a, q = _p(z), _p(f)
+    a, q = ptr(z), ptr(f)
     call = eng._lib.mpx_tokens_assemble
     assert call(eng._h, a, a, q, q, a, a, 1, 4, 64, 0, None) == 0
     torch.cuda.synchronize()
@@ -349,10 +290,10 @@ def test_layernorm_rows_against_fp64_and_layernorm_c(b16, dev, rows, stride, c):
     g, b = gamma.to(dev), beta.to(dev)
 
     def run(n, max_blocks=0, at=0):
-        out = Fenced(n, c, dev)
+        out = FencedPair(n, c, dev)
         oh, ol = out.ptrs()
         ih, il = C.c_void_p(xh.data_ptr() + at * stride * c * 2), C.c_void_p(xl.data_ptr() + at * stride * c * 2)
-        rc = eng._lib.mpx_layernorm_rows(eng._h, ih, il, _p(g), _p(b), EPS, oh, ol, n, stride, c, max_blocks, eng._stream())
+        rc = eng._lib.mpx_layernorm_rows(eng._h, ih, il, ptr(g), ptr(b), EPS, oh, ol, n, stride, c, max_blocks, eng._stream())
         _lib.check(eng._h, rc, "mpx_layernorm_rows")
         yh, yl = out.result()
         return yh.view(n, c), yl.view(n, c)
@@ -367,9 +308,9 @@ def test_layernorm_rows_against_fp64_and_layernorm_c(b16, dev, rows, stride, c):
     assert worst <= 1.0
     # mpx_layernorm_c on the gathered rows: the same bits
     ph, pl = split(picked.contiguous().to(dev))
-    out = Fenced(rows, c, dev)
+    out = FencedPair(rows, c, dev)
     oh, ol = out.ptrs()
-    _lib.check(eng._h, eng._lib.mpx_layernorm_c(eng._h, _p(ph), _p(pl), _p(g), _p(b), EPS, oh, ol, rows, c, 0, eng._stream()), "mpx_layernorm_c")
+    _lib.check(eng._h, eng._lib.mpx_layernorm_c(eng._h, ptr(ph), ptr(pl), ptr(g), ptr(b), EPS, oh, ol, rows, c, 0, eng._stream()), "mpx_layernorm_c")
     wh, wl = out.result()
     assert torch.equal(bits(wh.view(rows, c)), bits(yh)) and torch.equal(bits(wl.view(rows, c)), bits(yl))
     # the last row alone, and a grid of one workgroup
@@ -378,11 +319,11 @@ def test_layernorm_rows_against_fp64_and_layernorm_c(b16, dev, rows, stride, c):
     ch, cl = run(rows, max_blocks=1)
     assert torch.equal(bits(ch), bits(yh)) and torch.equal(bits(cl), bits(yl))
     call = eng._lib.mpx_layernorm_rows
-    oh, ol = Fenced(rows, c, dev).ptrs()
-    assert call(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, rows, 0, c, 0, None) == -1
-    assert call(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, 0, stride, c, 0, None) == -1
-    assert call(eng._h, _p(xh), _p(xl), _p(g), _p(b), EPS, oh, ol, rows, stride, c + 4, 0, None) == -1
-    assert call(eng._h, _p(xh), _p(xl), None, _p(b), EPS, oh, ol, rows, stride, c, 0, None) == -1
+    oh, ol = FencedPair(rows, c, dev).ptrs()
+    assert call(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, rows, 0, c, 0, None) == -1
+    assert call(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, 0, stride, c, 0, None) == -1
+    assert call(eng._h, ptr(xh), ptr(xl), ptr(g), ptr(b), EPS, oh, ol, rows, stride, c + 4, 0, None) == -1
+    assert call(eng._h, ptr(xh), ptr(xl), None, ptr(b), EPS, oh, ol, rows, stride, c, 0, None) == -1
 
 
 # ------------------------------------------------------------------------------------------------
@@ -407,32 +348,24 @@ def _run_layer(eng, i, batch, seed):
     if i == 0:      # the stem reads the engine's padded NHWC4 staging: write the interior, zero border and 4th channel
         x = torch.randn(batch, 224, 224, 3, generator=g) * 1.5
         xh, xl = split(x.to(dev))
-        ih, il = eng.input_planes(batch)
-        ih.zero_()
-        il.zero_()
-        ih[:, 3:227, 3:227, :3] = xh
-        il[:, 3:227, 3:227, :3] = xl
-        eng.mark_input_staged(0, batch)
+        stage_stem_input(eng, xh, xl, batch)
         in_h = in_l = None
     else:
         x = torch.randn(rows, d.cin, generator=g) * 1.5
         xh, xl = split(x.to(dev))
         in_h, in_l = xh, xl
-    fo = Fenced(rows, d.cout, dev)
+    fo = FencedPair(rows, d.cout, dev)
     oh, ol = fo.ptrs()
-    rc = eng._lib.mpx_conv_bn_act(eng._h, i, _p(in_h), _p(in_l), _p(rh), _p(rl), oh, ol, None, batch, eng._stream())
+    rc = eng._lib.mpx_conv_bn_act(eng._h, i, ptr(in_h), ptr(in_l), ptr(rh), ptr(rl), oh, ol, None, batch, eng._stream())
     _lib.check(eng._h, rc, "mpx_conv_bn_act")
     yh, yl = fo.result()
     return merge(yh, yl).cpu().double().view(rows, d.cout), merge(xh, xl).cpu().double(), (merge(rh, rl).cpu().double() if d.residual else None)
 
 
 def _check(eng, sd, i, batch, tile):
-    assert eng._lib.mpx_set_conv_tile(eng._h, i, tile) == 0, eng._lib.mpx_last_error(eng._h)
-    try:
+    with conv_tile(eng, i, tile):
         got, x64, r64 = _run_layer(eng, i, batch, seed=1000 * i + batch)
         ran = eng._lib.mpx_last_conv_kernels(eng._h)
-    finally:
-        eng._lib.mpx_set_conv_tile(eng._h, i, -1)
     d = eng.layers[i]
     name = d.name.decode()
     w, bias = _sd_tensors(sd, name)
@@ -444,13 +377,8 @@ def _check(eng, sd, i, batch, tile):
         want = F.gelu(want)
     if r64 is not None:
         want = want + r64
-    err = (got - want).abs().max().item()
-    scale = want.abs().max().item()
-    bound = LAYER_TOL * math.sqrt(max(d.k_packed, 4608) / 4608) * max(scale, 1.0)
-    print("%s %d->%d k%d rows/image %d K %d res %d act %d tile %d batch %d: max err %.3e (scale %.2f, bound %.3e), kernels 0x%x"
-          % (name, d.cin, d.cout, d.ksize, eng.conv_rows[i] or d.hout * d.hout, d.k_packed, d.residual, eng.epilogue_acts[i], tile, batch, err, scale, bound, ran))
-    assert err <= bound, "%s tile %d batch %d: max err %.3e (scale %.2f)" % (name, tile, batch, err, scale)
-    return ran, want
+    fields = "%d->%d k%d rows/image %d K %d res %d act %d " % (d.cin, d.cout, d.ksize, eng.conv_rows[i] or d.hout * d.hout, d.k_packed, d.residual, eng.epilogue_acts[i])
+    return assert_layer_close(d, got, want, tile, batch, ran, fields), want
 
 
 @pytest.mark.parametrize("arch", ref.ARCHS)
@@ -458,8 +386,7 @@ def test_patchify_stem_on_every_accepted_tile(engines, sds, arch):
     """conv_proj, 16 x 16 stride 16 (k_per_tap 64: two K steps per kernel row) and 32 x 32 stride 32 (k_per_tap 128: four), reading the padded
     NHWC4 staging 3 pixels into its border, batches 1 and 3."""
     eng, sd = engines[arch], sds[arch]
-    accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, 0, t) == 0]
-    eng._lib.mpx_set_conv_tile(eng._h, 0, -1)
+    accepted = accepted_tiles(eng, 0)
     assert set(accepted) == GENERIC and eng._lib.mpx_get_conv_tile(eng._h, 0) == 2
     for t in accepted:
         for batch in (1, 3):
@@ -473,8 +400,7 @@ def test_token_layers_on_every_accepted_tile(engines, sds, arch, layer):
     5 on B x T rows (T = 197: prime, no square map; 50), B = 1 and 3, on every tile each accepts."""
     eng, sd = engines[arch], sds[arch]
     i = [d.name.decode() for d in eng.layers].index("encoder_layer_5." + layer)
-    accepted = [t for t in ALL_TILES if eng._lib.mpx_set_conv_tile(eng._h, i, t) == 0]
-    eng._lib.mpx_set_conv_tile(eng._h, i, -1)
+    accepted = accepted_tiles(eng, i)
     assert eng._lib.mpx_get_conv_tile(eng._h, i) in accepted
     want_set = GENERIC if layer == "mlp.0" else (GENERIC | {9, 10, 13} if layer.endswith("in_proj") else GENERIC | {9, 10})
     assert set(accepted) == want_set, (layer, accepted)
@@ -497,7 +423,7 @@ def test_logit_layer_on_every_accepted_tile(b16, sds, dev):
             x = torch.randn(3, 768, generator=torch.Generator().manual_seed(t)) * 1.5
             xh, xl = split(x.to(dev))
             out = torch.full((3, 1000), float("nan"), dtype=torch.float32, device=dev)
-            _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, i, _p(xh), _p(xl), None, None, None, None, _p(out), 3, eng._stream()), "mpx_conv_bn_act")
+            _lib.check(eng._h, eng._lib.mpx_conv_bn_act(eng._h, i, ptr(xh), ptr(xl), None, None, None, None, ptr(out), 3, eng._stream()), "mpx_conv_bn_act")
             torch.cuda.synchronize()
         finally:
             eng._lib.mpx_set_conv_tile(eng._h, i, -1)
@@ -539,49 +465,12 @@ def test_vit_end_to_end(engines, sds, golden_dir, arch):
 
 @pytest.mark.parametrize("arch", ref.ARCHS)
 def test_a_mask_row_scores_the_same_bits_wherever_it_sits(engines, golden_dir, arch):
-    eng = engines[arch]
-    img, seg = ref.e2e_inputs(golden_dir, "felz")
-    S = len(np.unique(seg))
-    rows = synth.random_onoff(3, S, seed=31)
-    label = 3
-    _o, base_s, base_p, base_l = eng.score_masks(img, seg, rows, label, return_logits=True)
-    for m, seed, at in ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12))):       # 13 rows: two forwards of an 8-slot engine
-        onoff = synth.random_onoff(m, S, seed=seed)
-        for j, pos in enumerate(at):
-            onoff[pos] = rows[j]
-        _o, s, p, l = eng.score_masks(img, seg, onoff, label, return_logits=True)
-        for j, pos in enumerate(at):
-            assert np.array_equal(s[pos], base_s[j]) and p[pos] == base_p[j] and np.array_equal(l[pos], base_l[j]), (m, pos)
+    check_position_independence(engines[arch], *ref.e2e_inputs(golden_dir, "felz"), (3, ((1, 0, (0,)), (8, 41, (0, 5, 7)), (13, 44, (3, 8, 12)))))
 
 
 def test_api_on_a_vit_engine(engines, sds, golden_dir):
-    arch = "vit_b_32"
-    eng, sd = engines[arch], sds[arch]
-    sd32 = ref.cast(sd, torch.float32)
-
-    def score_one(masked_chw, label):
-        with torch.no_grad():
-            logits = ref.forward(sd32, torch.from_numpy(masked_chw[None]))
-        return F.softmax(logits, 1).numpy()[0][label]
-
-    img, seg = ref.e2e_inputs(golden_dir, "grid")
-    x = scorer.to_tensor_normalize(img)
-    with torch.no_grad():
-        label = int(ref.forward(sd32, x[None]).argmax(1)[0])
-    S = len(np.unique(seg))
-    assert eng.stem == "conv" and eng.stem_for_rows(4096) == "conv" and shard.job_stem(eng, 4096) == "conv"
-    onoff = synth.random_onoff(4, S, seed=5)
-    _o, score, pred = api.score_masks(eng, img, seg, onoff, label)
-    ref_score, ref_pred = ref.score_masks_reference_loop(sd, x, seg, onoff, label)
-    assert np.abs(score.astype(np.float64) - ref_score).max() <= SCORE_BOUND and (pred == ref_pred).all()
-    s_sh, p_sh = shard.score_masks_sharded(eng, img, seg, onoff, label)
-    assert np.array_equal(s_sh, score) and np.array_equal(p_sh, pred)
-    api.configure(eval_img_index=1, segmenter=lambda _img_show: seg, mask_dir=None, seed=None)
-    loader = [(x[None], torch.tensor([label]))]
-    for f in (0, 9):
-        got = api.sample_loss([f], loader, eng, None)
-        want = score_one(scorer.apply_mask(x, scorer.window_mask_u8(seg, f)), label)
-        assert abs(float(got) - float(want)) <= SCORE_BOUND
+    check_api(engines["vit_b_32"], Reference(ref, sds["vit_b_32"]), *ref.e2e_inputs(golden_dir, "grid"),
+              rows=4, same_pred=True, heatmaps=0, predict=False, table_step=None, validate=None)
 
 
 def test_profile_lists_the_attention_launches(b16, dev):
@@ -610,10 +499,10 @@ def test_vit_error_paths(b16, mpx_lib, dev, sds):
     on = torch.ones(1, 1, dtype=torch.uint8, device=dev)
     mean = (C.c_float * 3)(*scorer.MEAN)
     std = (C.c_float * 3)(*scorer.STD)
-    assert eng._lib.mpx_stem_table_build(eng._h, _p(im), None, _p(z), 1, mean, std, None) == -2
-    assert eng._lib.mpx_stem_table_apply(eng._h, _p(on), 1, 1, 0, None) == -2
+    assert eng._lib.mpx_stem_table_build(eng._h, ptr(im), None, ptr(z), 1, mean, std, None) == -2
+    assert eng._lib.mpx_stem_table_apply(eng._h, ptr(on), 1, 1, 0, None) == -2
     buf = torch.zeros(64, dtype=torch.float16, device=dev)
-    assert eng._lib.mpx_stem_conv_maxpool(eng._h, _p(buf), _p(buf), 1, None) == -2
+    assert eng._lib.mpx_stem_conv_maxpool(eng._h, ptr(buf), ptr(buf), 1, None) == -2
     ad = _lib.AttnDesc()
     assert eng._lib.mpx_attn_info(eng._h, 12, C.byref(ad)) == -1 and eng._lib.mpx_attn_info(eng._h, -1, C.byref(ad)) == -1
     fresh = MaskedForwardEngine("vit_b_32", max_batch=2, device=0)
@@ -629,11 +518,11 @@ def test_vit_error_paths(b16, mpx_lib, dev, sds):
         labels = torch.zeros(1, dtype=torch.int32, device=dev)
         score = torch.zeros(1, device=dev)
         pred = torch.zeros(1, dtype=torch.int32, device=dev)
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == -2
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == -2
         assert fresh._lib.mpx_load_tokens(fresh._h, None, C.c_void_p(sd["encoder.pos_embedding"].data_ptr())) == -1
         assert fresh._lib.mpx_load_tokens(fresh._h, C.c_void_p(sd["class_token"].data_ptr()), C.c_void_p(sd["encoder.pos_embedding"].data_ptr())) == 0
         assert fresh._lib.mpx_weights_complete(fresh._h) == 1
-        assert fresh._lib.mpx_forward(fresh._h, _p(labels), _p(score), _p(pred), None, 1, None) == 0
+        assert fresh._lib.mpx_forward(fresh._h, ptr(labels), ptr(score), ptr(pred), None, 1, None) == 0
         torch.cuda.synchronize()
         with pytest.raises((KeyError, ValueError)):     # the other ViT's state_dict: conv_proj.weight has another shape
             fresh.load_state_dict(sds["vit_b_16"])

@@ -925,3 +925,16 @@ def test_validate_many_groups_by_staging_and_emits_in_loader_order():
         assert {i: many[i] for i in idx if i != 4} == {i: want[i] for i in idx if i != 4}
     finally:
         api.configure(eval_img_index=1, num_mask_samples=100, segmenter=None, mask_dir=None, seed=None)
+
+
+def test_all_tiles_of_the_tests_are_the_product_tile_table():
+    """gpu_common.ALL_TILES, which the "every tile a layer accepts" tests walk, holds exactly the ids of the rows of kTiles in
+    csrc/mpx_api.hip (named ids resolved from their constexpr lines): a tile added to the product cannot stay out of those tests."""
+    import gpu_common
+    with open(os.path.join(ROOT, "network_interpretation_imagenet_amd", "csrc", "mpx_api.hip")) as fh:
+        src = fh.read()
+    named = {name: int(v) for name, v in re.findall(r"^constexpr int (k\w+Tile) = (\d+);", src, re.M)}
+    table = re.search(r"^const TileRow kTiles\[\] = \{\n(.*?)^\};", src, re.M | re.S).group(1)
+    ids = re.findall(r"^    \{(\w+), launch_", table, re.M)
+    assert {"kGconvTile", "kGconvwTile"} <= set(ids) <= set(named) | {i for i in ids if i.isdigit()}
+    assert tuple(int(i) if i.isdigit() else named[i] for i in ids) == gpu_common.ALL_TILES

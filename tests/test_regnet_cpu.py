@@ -21,6 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import netref
 import regnet_ref as ref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
@@ -29,24 +30,20 @@ ARCHS = ref.ARCHS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,))]
-
-
 def _expected_keys(arch):
     """models.<arch>().state_dict() without num_batches_tracked: key -> shape, written out from the table."""
     _id, widths, depths, gw, groups, _p, _m, _n = ref.TABLE[arch]
-    out = [("stem.0.weight", (32, 3, 3, 3))] + _bn_keys("stem.1", 32)
+    out = [("stem.0.weight", (32, 3, 3, 3))] + netref.bn_keys("stem.1", 32, tracked=False)
     cin = 32
     for s in range(4):
         w = widths[s]
         for j in range(depths[s]):
             p = "trunk_output.block%d.block%d-%d." % (s + 1, s + 1, j)
             if j == 0:
-                out += [(p + "proj.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "proj.1", w)
-            out += [(p + "f.a.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "f.a.1", w)
-            out += [(p + "f.b.0.weight", (w, w // groups[s], 3, 3))] + _bn_keys(p + "f.b.1", w)
-            out += [(p + "f.c.0.weight", (w, w, 1, 1))] + _bn_keys(p + "f.c.1", w)
+                out += [(p + "proj.0.weight", (w, cin, 1, 1))] + netref.bn_keys(p + "proj.1", w, tracked=False)
+            out += [(p + "f.a.0.weight", (w, cin, 1, 1))] + netref.bn_keys(p + "f.a.1", w, tracked=False)
+            out += [(p + "f.b.0.weight", (w, w // groups[s], 3, 3))] + netref.bn_keys(p + "f.b.1", w, tracked=False)
+            out += [(p + "f.c.0.weight", (w, w, 1, 1))] + netref.bn_keys(p + "f.c.1", w, tracked=False)
             cin = w
     return out + [("fc.weight", (1000, cin)), ("fc.bias", (1000,))]
 

@@ -23,6 +23,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import netref
 import regnet_ref as xref
 import regnety_draws as yd
 import regnety_ref as ref
@@ -42,14 +43,10 @@ ISSUE_TABLE = {
 }
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,))]
-
-
 def _expected_keys(arch):
     """models.<arch>().state_dict() without num_batches_tracked: key -> shape, written out from the table."""
     _id, widths, depths, _gw, groups, _p, _n, _k = ref.TABLE[arch]
-    out = [("stem.0.weight", (32, 3, 3, 3))] + _bn_keys("stem.1", 32)
+    out = [("stem.0.weight", (32, 3, 3, 3))] + netref.bn_keys("stem.1", 32, tracked=False)
     cin = 32
     for s in range(4):
         w = widths[s]
@@ -57,11 +54,11 @@ def _expected_keys(arch):
             p = "trunk_output.block%d.block%d-%d." % (s + 1, s + 1, j)
             q = cin // 4
             if j == 0:
-                out += [(p + "proj.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "proj.1", w)
-            out += [(p + "f.a.0.weight", (w, cin, 1, 1))] + _bn_keys(p + "f.a.1", w)
-            out += [(p + "f.b.0.weight", (w, w // groups[s], 3, 3))] + _bn_keys(p + "f.b.1", w)
+                out += [(p + "proj.0.weight", (w, cin, 1, 1))] + netref.bn_keys(p + "proj.1", w, tracked=False)
+            out += [(p + "f.a.0.weight", (w, cin, 1, 1))] + netref.bn_keys(p + "f.a.1", w, tracked=False)
+            out += [(p + "f.b.0.weight", (w, w // groups[s], 3, 3))] + netref.bn_keys(p + "f.b.1", w, tracked=False)
             out += [(p + "f.se.fc1.weight", (q, w, 1, 1)), (p + "f.se.fc1.bias", (q,)), (p + "f.se.fc2.weight", (w, q, 1, 1)), (p + "f.se.fc2.bias", (w,))]
-            out += [(p + "f.c.0.weight", (w, w, 1, 1))] + _bn_keys(p + "f.c.1", w)
+            out += [(p + "f.c.0.weight", (w, w, 1, 1))] + netref.bn_keys(p + "f.c.1", w, tracked=False)
             cin = w
     return out + [("fc.weight", (1000, cin)), ("fc.bias", (1000,))]
 

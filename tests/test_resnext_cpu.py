@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import netref
 import resnext_ref as ref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
@@ -22,23 +23,19 @@ TABLE = {"resnext50_32x4d": ((3, 4, 6, 3), (128, 256, 512, 1024), (256, 512, 102
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,))]
-
-
 def _expected_keys(arch):
     """models.<arch>().state_dict() without num_batches_tracked: key -> shape, written out from the table."""
     depths, widths, outs, cgs = TABLE[arch]
-    out = [("conv1.weight", (64, 3, 7, 7))] + _bn_keys("bn1", 64)
+    out = [("conv1.weight", (64, 3, 7, 7))] + netref.bn_keys("bn1", 64, tracked=False)
     cin = 64
     for s in range(4):
         for b in range(depths[s]):
             p = "layer%d.%d." % (s + 1, b)
-            out += [(p + "conv1.weight", (widths[s], cin, 1, 1))] + _bn_keys(p + "bn1", widths[s])
-            out += [(p + "conv2.weight", (widths[s], cgs[s], 3, 3))] + _bn_keys(p + "bn2", widths[s])
-            out += [(p + "conv3.weight", (outs[s], widths[s], 1, 1))] + _bn_keys(p + "bn3", outs[s])
+            out += [(p + "conv1.weight", (widths[s], cin, 1, 1))] + netref.bn_keys(p + "bn1", widths[s], tracked=False)
+            out += [(p + "conv2.weight", (widths[s], cgs[s], 3, 3))] + netref.bn_keys(p + "bn2", widths[s], tracked=False)
+            out += [(p + "conv3.weight", (outs[s], widths[s], 1, 1))] + netref.bn_keys(p + "bn3", outs[s], tracked=False)
             if b == 0:
-                out += [(p + "downsample.0.weight", (outs[s], cin, 1, 1))] + _bn_keys(p + "downsample.1", outs[s])
+                out += [(p + "downsample.0.weight", (outs[s], cin, 1, 1))] + netref.bn_keys(p + "downsample.1", outs[s], tracked=False)
             cin = outs[s]
     return out + [("fc.weight", (1000, 2048)), ("fc.bias", (1000,))]
 

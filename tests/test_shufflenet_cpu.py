@@ -4,7 +4,6 @@ view / transpose shuffle, the fp64 / fp32 CPU restatement (tests/shufflenet_ref.
 the synthetic networks on exactly the rows the GPU test scores, and the C-ABI surface."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import netref
 import shufflenet_ref as ref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
@@ -39,15 +39,10 @@ def test_the_four_names_are_served_with_ids_of_their_own():
         engine.MaskedForwardEngine("shufflenet_v2_x3_0")
 
 
-def _bn_keys(prefix, c):
-    return [(prefix + ".weight", (c,)), (prefix + ".bias", (c,)), (prefix + ".running_mean", (c,)), (prefix + ".running_var", (c,)),
-            (prefix + ".num_batches_tracked", ())]
-
-
 def _expected_keys(arch):
     """models.<arch>().state_dict(): key -> shape, in module order, written out from the width table."""
     w = WIDTHS[arch]
-    out = [("conv1.0.weight", (w[0], 3, 3, 3))] + _bn_keys("conv1.1", w[0])
+    out = [("conv1.0.weight", (w[0], 3, 3, 3))] + netref.bn_keys("conv1.1", w[0])
     inp = w[0]
     for s, reps in enumerate((4, 8, 4)):
         oup = w[s + 1]
@@ -55,13 +50,13 @@ def _expected_keys(arch):
         for b in range(reps):
             p = "stage%d.%d." % (s + 2, b)
             if b == 0:
-                out += [(p + "branch1.0.weight", (inp, 1, 3, 3))] + _bn_keys(p + "branch1.1", inp)
-                out += [(p + "branch1.2.weight", (bf, inp, 1, 1))] + _bn_keys(p + "branch1.3", bf)
-            out += [(p + "branch2.0.weight", (bf, inp if b == 0 else bf, 1, 1))] + _bn_keys(p + "branch2.1", bf)
-            out += [(p + "branch2.3.weight", (bf, 1, 3, 3))] + _bn_keys(p + "branch2.4", bf)
-            out += [(p + "branch2.5.weight", (bf, bf, 1, 1))] + _bn_keys(p + "branch2.6", bf)
+                out += [(p + "branch1.0.weight", (inp, 1, 3, 3))] + netref.bn_keys(p + "branch1.1", inp)
+                out += [(p + "branch1.2.weight", (bf, inp, 1, 1))] + netref.bn_keys(p + "branch1.3", bf)
+            out += [(p + "branch2.0.weight", (bf, inp if b == 0 else bf, 1, 1))] + netref.bn_keys(p + "branch2.1", bf)
+            out += [(p + "branch2.3.weight", (bf, 1, 3, 3))] + netref.bn_keys(p + "branch2.4", bf)
+            out += [(p + "branch2.5.weight", (bf, bf, 1, 1))] + netref.bn_keys(p + "branch2.6", bf)
         inp = oup
-    out += [("conv5.0.weight", (w[4], w[3], 1, 1))] + _bn_keys("conv5.1", w[4])
+    out += [("conv5.0.weight", (w[4], w[3], 1, 1))] + netref.bn_keys("conv5.1", w[4])
     return out + [("fc.weight", (1000, w[4])), ("fc.bias", (1000,))]
 
 
@@ -260,13 +255,7 @@ def test_synthetic_statistics_on_the_rows_the_gpu_test_scores(arch, golden_dir):
 # the C-ABI surface
 # ------------------------------------------------------------------------------------------------
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_SHUFFLENET 9000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_SHUFFLENET 9000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     i = C.c_int()
     assert mpx_lib.mpx_shuffle2_concat(None, None, None, 64, None, None, 64, None, None, 1, 7, 58, 64, None) == -1

@@ -3,7 +3,6 @@ the fp64 / fp32 CPU restatement (tests/squeezenet_ref.py) against an independent
 giving the same maps, the arch ids, the C-ABI surface, and the statistics of the synthetic network on exactly the rows the GPU test scores."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import netref
 import squeezenet_ref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
@@ -97,13 +97,7 @@ def test_unknown_squeezenet_id_is_refused(mpx_lib, arch_id):
 
 
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_SQUEEZENET 7000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_SQUEEZENET 7000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     a, b = C.c_int(), C.c_int()
     assert mpx_lib.mpx_conv_out_slice(None, 0, C.byref(a), C.byref(b)) == -1

@@ -14,7 +14,6 @@ falling to 0.16 (uniform: 0.02), unmasked peak 0.34 / 0.88, rows' peaks 0.12 .. 
 zero class token: the rows are seeds 8 / 1 (tests/vit_ref.E2E_CASES)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import netref
 import vit_ref as ref
 from network_interpretation_imagenet_amd import _lib, engine, synth
 from oracle import scorer
@@ -106,13 +106,7 @@ def test_descriptor_names_map_back_to_torchvisions():
 
 
 def test_new_c_abi_symbols_are_in_the_header_the_binding_and_the_library(mpx_lib):
-    with open(os.path.join(ROOT, "include", "mpx.h")) as fh:
-        header = fh.read()
-    assert "#define MPX_ARCH_VIT 13000" in header
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(mpx_lib, name) is not None
+    netref.assert_c_abi_symbols(mpx_lib, "MPX_ARCH_VIT 13000", NEW_SYMBOLS)
     # every entry refuses a null engine before it touches a device
     ad, p, a = _lib.AttnDesc(), C.c_void_p(), C.c_int()
     assert mpx_lib.mpx_attention(None, None, None, None, None, 1, 197, 12, 0, None) == -1

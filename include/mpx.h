@@ -638,6 +638,31 @@ int mpx_softmask_saliency_classes(mpx_engine* h, const float* weights, const flo
 int mpx_rise_saliency_classes(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* scores, int score_pitch, int M,
                               int K, int s, float* sal, void* stream);
 
+/* ---- a linear surrogate over on/off superpixel rows: the fp64 moment sums of LIME and KernelSHAP, and the paint per superpixel ---------
+ * extends: mpx_heatmap_accumulate (one count per superpixel of the rows predicted right) to the two sums a weighted least-squares fit of
+ *          score ~ c0 + sum_j c_j * z_j  over random on/off rows needs (Ribeiro et al., "LIME", KDD 2016; Lundberg & Lee, "KernelSHAP",
+ *          NeurIPS 2017), for K classes of the same forwards (csrc/mpx_surrogate.h).  There is no reference line.
+ * mpx_surrogate_accumulate: onoff DEV u8[M][S] (any non-zero byte = on), weight DEV f32[M], scores DEV f32[M][score_pitch] with
+ *   score_pitch >= K (what mpx_softmax_gather_classes writes), A DEV f64[S+1][S+1], B DEV f64[S+1][K], both dense and row-major.
+ *   With z~_m = (1, onoff[m][0] != 0, .., onoff[m][S-1] != 0), for m = 0 .. M - 1 in this order, from the values already in A and B:
+ *     A[i][j] <- fl64(A[i][j] + (double)weight[m])                                          where z~_mi and z~_mj are both on
+ *     B[i][k] <- fl64(B[i][k] + (double)weight[m] * (double)scores[m * score_pitch + k])    where z~_mi is on
+ *   and an element whose condition is off is not touched.  The product of two fp32 numbers is exact in fp64, so every step has ONE
+ *   rounding, and an FMA and a multiply-add give the same bits.  Both triangles of A are written.  The weight and the scores of a row reach
+ *   only the elements whose condition that row turns on: a NaN on an off row reaches nothing, a NaN score of class k on an on row reaches
+ *   column k of the rows of its on superpixels (and row 0).  One thread owns a row and a tile of columns and walks the masks in order (no
+ *   atomics, no reduction tree): the bits depend neither on the launch geometry nor on how the rows are cut into consecutive calls.
+ *   Nothing is read in scores[..][K, score_pitch), nothing is written outside A and B.  1 <= S <= 1024.
+ * mpx_segment_paint: seg DEV i32[H][H] (H = the engine's image_size), value DEV f32[K][value_pitch] with value_pitch >= S,
+ *   out DEV f32[K][H][H]:
+ *     out[k][p] = value[k * value_pitch + seg[p]],   +0.0f where seg[p] lies outside [0, S)
+ * Both serve every engine, the small networks included (neither depends on the network).  MPX_E_ARG, with nothing launched, for a NULL
+ * pointer, M < 0, K < 1, S outside [1, 1024], score_pitch < K or value_pitch < S.  M == 0 succeeds and writes nothing.  No allocation, no
+ * host synchronisation. */
+int mpx_surrogate_accumulate(mpx_engine* h, const uint8_t* onoff, const float* weight, const float* scores, int score_pitch, int M, int S,
+                             int K, double* A, double* B, void* stream);
+int mpx_segment_paint(mpx_engine* h, const int32_t* seg, const float* value, int value_pitch, int S, int K, float* out, void* stream);
+
 /* ---- a second pixel source for the staging: rows selected on a per-pixel rank, and the blurred image ------------------------------
  * extends: mpx_mask_apply_normalize and the soft-mask entries, whose removed pixel is always zero, to a FILL IMAGE: row m takes the pixels
  *          of rank below thresh[m] from one source and the others from the other.  There is no reference line: these are the rows of the

@@ -191,11 +191,15 @@ SIGNATURES = {
     # a second pixel source (csrc/mpx_rankmask.h): rows selected between the image and a fill image on a per-pixel rank; RISE's blur
     "mpx_rank_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _fp, _fp, _i, _vp, _vp]),
     "mpx_blur_fill": (_i, [_vp, _vp, _vp, _fp, _i, _fp, _fp, _vp, _vp]),
+    # a linear surrogate over on/off rows (csrc/mpx_surrogate.h): the fp64 moment sums of LIME / KernelSHAP, the paint per superpixel
+    "mpx_surrogate_accumulate": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mpx_segment_paint": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 SOFTMASK_TILE = 32      # csrc/mpx_softmask.h SM_MT: the masks one block of the apply kernels loops over
 RANKMASK_TILE = 32      # csrc/mpx_rankmask.h RM_MT: the rows one block of rank_apply_kernel loops over
 SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
+SURROGATE_S_MAX = 1024     # csrc/mpx_surrogate.h SUR_S_MAX: the most superpixels mpx_surrogate_accumulate / mpx_segment_paint take
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes
 
 _lib = None

@@ -542,6 +542,40 @@ def rise_saliency_classes(model, image_u8, classes=None, top=None, n_masks=4000,
     return model.rise_saliency_classes(image_u8, classes=classes, top=top, n_masks=n_masks, s=s, p1=p1, seed=seed, out=out)
 
 
+def _surrogate_inputs(image_u8, label, classes, top, segments):
+    """(classes, top, segments) of a superpixel explainer's call: label is shorthand for classes=[label]; segments=None runs the configured
+    segmenter (felzenszwalb by default) on the picture, as the other entries do."""
+    if label is not None:
+        if classes is not None or top is not None:
+            raise ValueError("give label, classes or top, not several")
+        classes = [_as_int(label)]
+    if segments is None:
+        img = np.asarray(image_u8)
+        if img.dtype != np.uint8 or img.shape != (IMG, IMG, 3):
+            raise ValueError("segments=None needs the picture as uint8[224,224,3] to segment, got %s%s" % (img.dtype, img.shape))
+        segments = (_CONFIG["segmenter"] or default_segmenter)(img)
+    return classes, top, segments
+
+
+def lime_saliency(model, image_u8, label=None, classes=None, top=None, segments=None, n_samples=1000, kernel_width=0.25, lam=1.0, seed=0,
+                  out=None):
+    """LIME on superpixels (Ribeiro et al., KDD 2016, lime_image's sampling and kernel): -> (classes i32[K], intercept f64[K],
+    coef f64[K,S], sal f32[K,224,224]) -- a weighted ridge regression of the class scores on n_samples random on/off rows, the rows scored
+    at full batch and their moment sums accumulated on the device in fp64 (engine.MaskedForwardEngine.lime).  label: one class; classes: a
+    sequence; top=k: the k largest logits of the unmasked image; none of them: all 1000.  coef[k][j] belongs to the j-th label of
+    np.unique(segments); sal[k] paints it onto the pixels and feeds deletion_insertion as a RISE map does (out= keeps it on the device)."""
+    classes, top, segments = _surrogate_inputs(image_u8, label, classes, top, segments)
+    return model.lime(image_u8, segments, classes=classes, top=top, n_samples=n_samples, kernel_width=kernel_width, lam=lam, seed=seed, out=out)
+
+
+def kernel_shap_saliency(model, image_u8, label=None, classes=None, top=None, segments=None, n_samples=2048, seed=0, out=None):
+    """KernelSHAP on superpixels (Lundberg & Lee, NeurIPS 2017; paired sampling from the Shapley kernel): -> (classes i32[K], base f64[K],
+    phi f64[K,S], sal f32[K,224,224]) with base + sum(phi) = the unmasked score of every class (engine.MaskedForwardEngine.kernel_shap).
+    n_samples: even and at least S.  The other arguments as lime_saliency."""
+    classes, top, segments = _surrogate_inputs(image_u8, label, classes, top, segments)
+    return model.kernel_shap(image_u8, segments, classes=classes, top=top, n_samples=n_samples, seed=seed, out=out)
+
+
 def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
     """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
     salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on

@@ -22,6 +22,7 @@
 #include "mpx_softmask.h"
 #include "mpx_saliency_classes.h"
 #include "mpx_rankmask.h"
+#include "mpx_surrogate.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2089,6 +2090,49 @@ int mpx_softmask_saliency_classes(mpx_engine* h, const float* weights, const flo
 int mpx_rise_saliency_classes(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* scores, int score_pitch, int M, int K,
                               int s, float* sal, void* stream) {
     return soft_saliency_classes<RiseWeights>(h, "rise_saliency_classes", cells, shift, scores, score_pitch, M, K, s, sal, stream);
+}
+
+// ---- a linear surrogate over on/off superpixel rows (mpx_surrogate.h): the fp64 moment sums of LIME / KernelSHAP, the paint per superpixel ----
+// Neither entry asks what network the engine runs: both serve every engine, the small networks included.  Booked with the head (kind 3) in
+// a profile, ProfTag() as every stand-alone entry.
+int mpx_surrogate_accumulate(mpx_engine* h, const uint8_t* onoff, const float* weight, const float* scores, int score_pitch, int M, int S,
+                             int K, double* A, double* B, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!onoff || !weight || !scores || !A || !B) return fail(h, MPX_E_ARG, "surrogate_accumulate: null pointer");
+    if (M < 0 || K < 1 || K > 65535 * SUR_KT) return fail(h, MPX_E_ARG, "surrogate_accumulate: M=%d K=%d", M, K);
+    if (S < 1 || S > SUR_S_MAX) return fail(h, MPX_E_ARG, "surrogate_accumulate: S=%d outside [1, %d]", S, SUR_S_MAX);
+    if (score_pitch < K) return fail(h, MPX_E_ARG, "surrogate_accumulate: score_pitch=%d < K=%d", score_pitch, K);
+    if (M == 0) return 0;
+    SurParams p;
+    std::memset(&p, 0, sizeof p);
+    p.onoff = onoff; p.weight = weight; p.scores = scores;
+    p.score_pitch = score_pitch; p.M = M; p.S = S; p.K = K;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 3, -1);
+    const int rows = (S + 1 + SUR_THREADS - 1) / SUR_THREADS;
+    p.out = A;
+    hipLaunchKernelGGL(surrogate_accumulate_kernel<true>, dim3(rows, (S + 1 + SUR_KT - 1) / SUR_KT), dim3(SUR_THREADS), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    p.out = B;
+    hipLaunchKernelGGL(surrogate_accumulate_kernel<false>, dim3(rows, (K + SUR_KT - 1) / SUR_KT), dim3(SUR_THREADS), 0, st, p);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_segment_paint(mpx_engine* h, const int32_t* seg, const float* value, int value_pitch, int S, int K, float* out, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!seg || !value || !out) return fail(h, MPX_E_ARG, "segment_paint: null pointer");
+    if (K < 1 || K > 65535) return fail(h, MPX_E_ARG, "segment_paint: K=%d", K);
+    if (S < 1 || S > SUR_S_MAX) return fail(h, MPX_E_ARG, "segment_paint: S=%d outside [1, %d]", S, SUR_S_MAX);
+    if (value_pitch < S) return fail(h, MPX_E_ARG, "segment_paint: value_pitch=%d < S=%d", value_pitch, S);
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 3, -1);
+    const int npix = h->img * h->img;
+    hipLaunchKernelGGL(segment_paint_kernel, dim3((npix + 255) / 256, K), dim3(256), 0, st, seg, value, value_pitch, S, npix, out);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
 }
 
 // ---- a second pixel source (mpx_rankmask.h): rows that select between the image and a fill image on a per-pixel rank, and RISE's blur ----

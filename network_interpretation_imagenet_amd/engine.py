@@ -1149,6 +1149,171 @@ class MaskedForwardEngine:
         cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
         return cls, (sal.cpu().numpy() if out is None else sal)
 
+    # ---- a linear surrogate over on/off superpixel rows (csrc/mpx_surrogate.h): LIME and KernelSHAP ----
+    def surrogate_accumulate(self, onoff, weight, scores, A, B):
+        """mpx_surrogate_accumulate: the fp64 moment sums of a weighted linear fit over on/off rows, in place, on the device.  With
+        z~_m = (1, onoff[m] != 0), for m ascending: A[i][j] <- A[i][j] + weight[m] where z~_mi and z~_mj are on, B[i][k] <- B[i][k] +
+        weight[m] * scores[m][k] where z~_mi is on; one fp64 rounding per step, masks.surrogate_sums bit for bit, however the rows are cut
+        into calls.  onoff: device u8[M,S]; weight: device f32[M]; scores: device f32[M,K] (class_scores' output, rows >= K floats
+        apart); A: device f64[S+1,S+1]; B: device f64[S+1,K].  Every engine takes it, the small networks included."""
+        if onoff.device != self.device or onoff.dtype != torch.uint8 or onoff.dim() != 2 or not onoff.is_contiguous():
+            raise ValueError("onoff must be a contiguous uint8[M,S] tensor on %s" % self.device)
+        m, s = int(onoff.shape[0]), int(onoff.shape[1])
+        if not 1 <= s <= _lib.SURROGATE_S_MAX:
+            raise ValueError("S=%d outside [1, %d]" % (s, _lib.SURROGATE_S_MAX))
+        if weight.device != self.device or weight.dtype != torch.float32 or tuple(weight.shape) != (m,) or not weight.is_contiguous():
+            raise ValueError("weight must be a contiguous float32[%d] tensor on %s" % (m, self.device))
+        if scores.dim() != 2 or B.dim() != 2:
+            raise ValueError("scores must be float32[M,K] and B float64[S+1,K]")
+        k = int(B.shape[1])
+        if k < 1:
+            raise ValueError("K >= 1, got B%s" % (tuple(B.shape),))
+        pitch = self._class_score_rows(scores, m, k)
+        for name, t, shape in (("A", A, (s + 1, s + 1)), ("B", B, (s + 1, k))):
+            if t.device != self.device or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float64[%d,%d] tensor on %s" % (name, shape[0], shape[1], self.device))
+        _lib.check(self._h, self._lib.mpx_surrogate_accumulate(self._h, _ptr(onoff), _ptr(weight), _ptr(scores), pitch, m, s, k, _ptr(A),
+                                                               _ptr(B), self._stream()), "mpx_surrogate_accumulate")
+        return A, B
+
+    def segment_paint(self, seg, value, out=None):
+        """mpx_segment_paint: out[k][p] = value[k][seg[p]] on the device, +0.0 where seg[p] lies outside [0, S) (masks.segment_paint).
+        seg: device i32[H,H] ranks, H = image_size; value: device f32[K,S] with unit column stride and rows >= S floats apart;
+        out: None or a contiguous device f32[K,H,H], which is overwritten.  -> out."""
+        h = self.image_size
+        if seg.device != self.device or seg.dtype != torch.int32 or tuple(seg.shape) != (h, h) or not seg.is_contiguous():
+            raise ValueError("seg must be a contiguous int32[%d,%d] tensor on %s" % (h, h, self.device))
+        if value.dim() != 2 or value.shape[0] < 1:
+            raise ValueError("value must be float32[K,S] with K >= 1")
+        k, s = int(value.shape[0]), int(value.shape[1])
+        if not 1 <= s <= _lib.SURROGATE_S_MAX:
+            raise ValueError("S=%d outside [1, %d]" % (s, _lib.SURROGATE_S_MAX))
+        pitch = self._class_score_rows(value, k, s, "value")
+        if out is None:
+            out = torch.empty(k, h, h, dtype=torch.float32, device=self.device)
+        if out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (k, h, h) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32[%d,%d,%d] tensor on %s" % (k, h, h, self.device))
+        _lib.check(self._h, self._lib.mpx_segment_paint(self._h, _ptr(seg), _ptr(value), pitch, s, k, _ptr(out), self._stream()),
+                   "mpx_segment_paint")
+        return out
+
+    def _onoff_job(self, image, segments, onoff, stem):
+        """What score_masks checks and uploads for ONE image's on/off rows -> (stage(s0, b), seg_d, onoff_d, M, S).  The staging rule is
+        score_masks': the job's whole row count decides between table and conv (_staging); on the table path the table is built once."""
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        seg_rank, s = rank_segments(segments)
+        onoff = np.ascontiguousarray(onoff)
+        if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] != s:
+            raise ValueError("onoff must be uint8[M,%d] (S = number of distinct segment labels), got %s%s" % (s, onoff.dtype, onoff.shape))
+        m = int(onoff.shape[0])
+        table = self._staging(stem, m) == "table"
+        img_d = self._image_to_device(image)
+        seg_d = torch.from_numpy(seg_rank).to(self.device)
+        onoff_d = torch.from_numpy(onoff).to(self.device)
+
+        def stage(s0, b):
+            if table:
+                if s0 == 0:
+                    self.build_stem_table(img_d, seg_d, s)
+                self.apply_stem_table(onoff_d[s0:s0 + b], 0)
+            else:
+                self.stage_masks(img_d, seg_d, onoff_d[s0:s0 + b], 0)
+
+        return stage, seg_d, onoff_d, m, s
+
+    def score_masks_classes(self, image, segments, onoff, classes, stem=None):
+        """score_masks for several classes of the same forwards: -> (scores f32[M,K], pred i32[M]); column i is
+        score_masks(image, segments, onoff, classes[i], stem=stem)'s scores bit for bit.  classes: a sequence of class indices, or None for
+        all; stem as score_masks'."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        stage, _seg_d, _onoff_d, m, _s = self._onoff_job(image, segments, onoff, stem)
+        cls_d, k = self._classes_to_device(cls)
+        scores, pred = self._score_classes_staged(m, stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def _top_or_given(self, image, cls, top):
+        """The classes of a many-class job as i32[K] or None (all): `top` = that many of the largest logits of the unmasked forward."""
+        if top is None:
+            return cls
+        logits = self.score_masks(image, np.zeros((IMG, IMG), dtype=np.int32), np.ones((1, 1), dtype=np.uint8), 0, return_logits=True)[3]
+        return masks.top_classes(logits[0], top)
+
+    def _surrogate_job(self, image, segments, onoff, weight, cls, keep_rows, out):
+        """The device half of lime / kernel_shap: chunks of max_batch rows run stage -> forward -> class_scores -> surrogate_accumulate on
+        the stream with no host round trip in between, then ONE download of A, B and the class scores of the first keep_rows rows (fp32
+        widened to fp64, which is exact).  `out` (None or the caller's device maps) is checked before anything runs.
+        -> (A f64[S+1,S+1], B f64[S+1,K], rows f64[keep_rows,K], seg_d, S, K)."""
+        stage, seg_d, onoff_d, m, s = self._onoff_job(image, segments, onoff, None)
+        if not 1 <= s <= _lib.SURROGATE_S_MAX:
+            raise ValueError("S=%d superpixels outside [1, %d]" % (s, _lib.SURROGATE_S_MAX))
+        cls_d, k = self._classes_to_device(cls)
+        if out is not None:
+            self._sal_maps(out, k)
+        n = s + 1
+        buf = torch.zeros(n * n + n * k + keep_rows * k, dtype=torch.float64, device=self.device)
+        a_d, b_d = buf[:n * n].view(n, n), buf[n * n:n * n + n * k].view(n, k)
+        w_d = torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float32)).to(self.device)
+
+        def after(s0, b, scores):
+            self.surrogate_accumulate(onoff_d[s0:s0 + b], w_d[s0:s0 + b], scores, a_d, b_d)
+
+        scores, _pred = self._score_classes_staged(m, stage, cls_d, k, after=after)
+        if keep_rows:
+            buf[n * n + n * k:].view(keep_rows, k).copy_(scores[:keep_rows])
+        host = buf.cpu().numpy()
+        return (host[:n * n].reshape(n, n), host[n * n:n * n + n * k].reshape(n, k), host[n * n + n * k:].reshape(keep_rows, k),
+                seg_d, s, k)
+
+    def _paint_values(self, seg_d, values, out):
+        """values f64[K,S] rounded to fp32, uploaded and painted -> host f32[K,224,224], or the device tensor `out` overwritten."""
+        v_d = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32)).to(self.device)
+        sal = self.segment_paint(seg_d, v_d, out=out)
+        return sal.cpu().numpy() if out is None else sal
+
+    def lime(self, image, segments, classes=None, top=None, n_samples=1000, kernel_width=0.25, lam=1.0, seed=0, out=None):
+        """LIME on superpixels (Ribeiro et al., KDD 2016, in the lime_image form): a weighted ridge regression of K class scores on
+        n_samples random on/off rows -- onoff = masks.lime_onoff(n_samples, S, seed), weight = masks.lime_weights(onoff, kernel_width).
+        -> (classes i32[K], intercept f64[K], coef f64[K,S], sal f32[K,224,224]); coef[k][j] is the weight of the j-th superpixel in
+        np.unique(segments) order, sal[k] paints the coefficients (rounded to fp32) onto the pixels.  classes / top as
+        rise_saliency_classes.  The rows run at full batch (the stem table from stem_table_min_rows rows on) and their moment sums are
+        accumulated on the device in fp64, in row order; the (S + 1)^2 solve is masks.lime_solve on the host, so the result is exactly
+        lime_solve(surrogate_sums(score_masks_classes(...))).  out: None -> a host map; a contiguous device f32[K,224,224] is overwritten
+        with the maps and returned in their place (nothing is downloaded)."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        if int(n_samples) < 1 or not float(lam) >= 0.0 or not float(kernel_width) > 0.0:
+            raise ValueError("n_samples >= 1, lam >= 0 and kernel_width > 0, got %r, %r, %r" % (n_samples, lam, kernel_width))
+        s = rank_segments(segments)[1]
+        cls = self._top_or_given(image, cls, top)
+        onoff = masks.lime_onoff(n_samples, s, seed)
+        A, B, _rows, seg_d, s, k = self._surrogate_job(image, segments, onoff, masks.lime_weights(onoff, kernel_width), cls, 0, out)
+        intercept, coef = masks.lime_solve(A, B, lam)
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        return cls, intercept, coef, self._paint_values(seg_d, coef, out)
+
+    def kernel_shap(self, image, segments, classes=None, top=None, n_samples=2048, seed=0, out=None):
+        """KernelSHAP on superpixels (Lundberg & Lee, NeurIPS 2017): the Shapley-kernel fit of K class scores on the rows [all off, all on]
+        + masks.shap_onoff(n_samples, S, seed) with weights [0, 0, 1, ..] (a zero weight adds +0.0: the first two rows only bring f0 and
+        f1), under phi_0 = f0 and sum(phi) = f1 - f0 (masks.shap_solve).  -> (classes i32[K], base f64[K] = f0, phi f64[K,S],
+        sal f32[K,224,224]), phi indexed and painted as lime's coef.  ValueError for n_samples odd or below S, and for S < 2.  The device
+        path, classes / top and out are lime's."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        s = rank_segments(segments)[1]
+        if s < 2 or int(n_samples) % 2 or int(n_samples) < s:
+            raise ValueError("S >= 2 and an even n_samples >= S, got S=%d n_samples=%r" % (s, n_samples))
+        cls = self._top_or_given(image, cls, top)
+        onoff = np.concatenate([np.zeros((1, s), np.uint8), np.ones((1, s), np.uint8), masks.shap_onoff(n_samples, s, seed)])
+        weight = np.ones(onoff.shape[0], dtype=np.float32)
+        weight[:2] = 0.0
+        A, B, rows, seg_d, s, k = self._surrogate_job(image, segments, onoff, weight, cls, 2, out)
+        phi = masks.shap_solve(A, B, rows[0], rows[1])
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        return cls, rows[0].copy(), phi, self._paint_values(seg_d, phi, out)
+
     # ---- a second pixel source (csrc/mpx_rankmask.h): rows selected on a per-pixel rank, the blurred image, the causal metrics ----
     def _chw_to_device(self, t, name):
         """A host or device f32[3,224,224] as a contiguous device tensor."""

@@ -9,6 +9,10 @@ rise_weights, the numpy fp32 restatement of the weights csrc/mpx_softmask.h synt
 
 The deletion / insertion curves that score a saliency map (saliency_rank, curve_thresholds, rank_masks_apply, gaussian_taps, blur_fill,
 curve_auc) restate csrc/mpx_rankmask.h the same way.
+
+Back on the superpixel side, the linear surrogates LIME and KernelSHAP: their samplers and weights (lime_onoff, lime_weights, shap_onoff,
+shapley_kernel_onoff), surrogate_sums, the fp64 restatement of csrc/mpx_surrogate.h's moment sums, the two host solves (lime_solve,
+shap_solve) and segment_paint.
 """
 import random
 
@@ -198,6 +202,180 @@ def top_classes(logits, k):
     if not 0 < k <= logits.size:
         raise ValueError("top=%r outside [1, %d]" % (k, logits.size))
     return np.argsort(-logits, kind="stable")[:k].astype(np.int32)
+
+
+# ---- a linear surrogate over on/off superpixel rows: LIME (Ribeiro et al., KDD 2016) and KernelSHAP (Lundberg & Lee, NeurIPS 2017) ----
+# Both fit  score ~ c0 + sum_j c_j * z_j  to random coalitions z in {0, 1}^S.  The samplers, the weights, the numpy fp64 restatement of the
+# moment sums csrc/mpx_surrogate.h accumulates (the device is held to it bit for bit) and the two fp64 solves, which stay on the host.
+SURROGATE_S_MAX = 1024              # csrc/mpx_surrogate.h SUR_S_MAX
+SHAPLEY_ENUM_S_MAX = 12             # shapley_kernel_onoff enumerates 2^S - 2 rows
+
+
+def _check_onoff(onoff):
+    onoff = np.asarray(onoff)
+    if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] < 1:
+        raise ValueError("onoff must be uint8[M,S] with S >= 1, got %s%s" % (onoff.dtype, onoff.shape))
+    return onoff
+
+
+def lime_onoff(M, S, seed=0):
+    """u8[M,S]: lime_image's rows -- every superpixel on with probability 1/2 (its randint(0, 2)), row 0 all on (its data[0, :] = 1),
+    from ONE np.random.default_rng(seed)."""
+    M, S = int(M), int(S)
+    if M < 1 or S < 1:
+        raise ValueError("M >= 1 and S >= 1, got M=%r S=%r" % (M, S))
+    out = np.random.default_rng(seed).integers(0, 2, size=(M, S), dtype=np.uint8)
+    out[0] = 1
+    return out
+
+
+def lime_weights(onoff, kernel_width=0.25):
+    """f32[M]: LIME's kernel sqrt(exp(-d^2 / kernel_width^2)) of the cosine distance d = 1 - sqrt(k / S) of a row with k superpixels on to
+    the all-on row (d = 1 for k = 0), computed in fp64 and rounded once.  1 for an all-on row, exp(-8) for an all-off row at 0.25."""
+    onoff = _check_onoff(onoff)
+    if not float(kernel_width) > 0.0:
+        raise ValueError("kernel_width > 0, got %r" % (kernel_width,))
+    k = np.count_nonzero(onoff, axis=1).astype(np.float64)
+    d = 1.0 - np.sqrt(k / float(onoff.shape[1]))
+    return np.sqrt(np.exp(-(d * d) / float(kernel_width) ** 2)).astype(np.float32)
+
+
+def shap_size_pmf(S):
+    """f64[S-1]: the Shapley kernel's mass on the coalition sizes 1 .. S-1, p(k) proportional to (S - 1) / (k * (S - k))."""
+    S = int(S)
+    if S < 2:
+        raise ValueError("S >= 2, got %r" % (S,))
+    k = np.arange(1, S, dtype=np.float64)
+    p = (S - 1) / (k * (S - k))
+    return p / p.sum()
+
+
+def shap_onoff(M, S, seed=0):
+    """u8[M,S]: KernelSHAP's paired sampling from ONE np.random.default_rng(seed) -- M / 2 sizes drawn from shap_size_pmf(S), then per pair
+    row 2t = the first k of a random permutation switched on and row 2t + 1 = its complement.  Rows drawn from the kernel carry weight 1."""
+    M, S = int(M), int(S)
+    if M < 0 or M % 2 or S < 2:
+        raise ValueError("M even and >= 0, S >= 2, got M=%r S=%r" % (M, S))
+    rng = np.random.default_rng(seed)
+    sizes = rng.choice(np.arange(1, S), size=M // 2, p=shap_size_pmf(S))
+    out = np.zeros((M, S), dtype=np.uint8)
+    for t, k in enumerate(sizes):
+        out[2 * t, rng.permutation(S)[:int(k)]] = 1
+        out[2 * t + 1] = 1 - out[2 * t]
+    return out
+
+
+def shapley_kernel_onoff(S):
+    """(onoff u8[2^S - 2, S], weight f32[2^S - 2]): every coalition but the empty and the full one, row r - 1 = the bits of r (bit j =
+    superpixel j), with the Shapley kernel (S - 1) / (C(S, k) * k * (S - k)).  2 <= S <= 12.  shap_solve on these rows gives the exact
+    Shapley values."""
+    from math import comb
+    S = int(S)
+    if not 2 <= S <= SHAPLEY_ENUM_S_MAX:
+        raise ValueError("S=%r outside [2, %d]" % (S, SHAPLEY_ENUM_S_MAX))
+    r = np.arange(1, 2 ** S - 1, dtype=np.int64)
+    onoff = ((r[:, None] >> np.arange(S)[None, :]) & 1).astype(np.uint8)
+    k = onoff.sum(axis=1).astype(np.int64)
+    binom = np.array([comb(S, int(v)) for v in k], dtype=np.float64)
+    return onoff, ((S - 1) / (binom * k * (S - k))).astype(np.float32)
+
+
+def surrogate_sums(A0, B0, onoff, weight, scores):
+    """(A f64[S+1,S+1], B f64[S+1,K]): the moment sums of csrc/mpx_surrogate.h in numpy fp64, the restatement the device is held to bit
+    for bit.  With z~_m = (1, onoff[m] != 0), for m ascending from A0 and B0:  A[i][j] <- A[i][j] + w_m where z~_mi and z~_mj are on,
+    B[i][k] <- B[i][k] + w_m * scores[m][k] where z~_mi is on (the product of two fp32 numbers is exact in fp64: one rounding per step);
+    an element whose condition is off is not touched.  onoff u8[M,S], weight f32[M], scores f32[M,K]."""
+    onoff = _check_onoff(onoff)
+    m_all, s = onoff.shape
+    A = np.array(A0, dtype=np.float64, copy=True)
+    B = np.array(B0, dtype=np.float64, copy=True)
+    weight, scores = np.asarray(weight), np.asarray(scores)
+    if weight.dtype != np.float32 or scores.dtype != np.float32:
+        raise ValueError("weight and scores must be float32, got %s and %s" % (weight.dtype, scores.dtype))
+    if (A.shape != (s + 1, s + 1) or B.ndim != 2 or B.shape[0] != s + 1 or weight.shape != (m_all,)
+            or scores.shape != (m_all, B.shape[1])):
+        raise ValueError("A [S+1,S+1], B [S+1,K], onoff [M,S], weight [M], scores [M,K]; got %s, %s, %s, %s, %s"
+                         % (A.shape, B.shape, onoff.shape, weight.shape, scores.shape))
+    z = np.concatenate([np.ones((m_all, 1), dtype=bool), onoff != 0], axis=1)
+    w, sc = weight.astype(np.float64), scores.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for m in range(m_all):
+            A = np.where(z[m][:, None] & z[m][None, :], A + w[m], A)
+            B = np.where(z[m][:, None], B + (w[m] * sc[m])[None, :], B)
+    return A, B
+
+
+def _solve_sym(G, b, what):
+    """solve(G, b) in fp64 for a symmetric G; ValueError where G holds a non-finite value or is singular by numpy.linalg.matrix_rank's
+    rule, smallest |eigenvalue| <= largest * n * eps (a symmetric matrix's singular values are its |eigenvalues|; eigvalsh reads one
+    triangle and costs 5 ms at S = 330 where the SVD behind matrix_rank costs 13)."""
+    if not (np.isfinite(G).all() and np.isfinite(b).all()):
+        raise ValueError("%s: the system holds a NaN or an infinity" % what)
+    ev = np.abs(np.linalg.eigvalsh(G))
+    if ev.min() <= ev.max() * G.shape[0] * np.finfo(np.float64).eps:
+        raise ValueError("%s: the system is singular (too few rows, or dependent columns without a penalty)" % what)
+    try:
+        return np.linalg.solve(G, b)
+    except np.linalg.LinAlgError as e:
+        raise ValueError("%s: %s" % (what, e))
+
+
+def _check_moments(A, B):
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 2 or B.ndim != 2 or B.shape[0] != A.shape[0]:
+        raise ValueError("A must be [S+1,S+1] and B [S+1,K], got %s and %s" % (A.shape, B.shape))
+    return A, B
+
+
+def lime_solve(A, B, lam=1.0):
+    """(intercept f64[K], coef f64[K,S]): the weighted ridge regression of LIME from its moment sums -- (A + lam * diag(0, 1, .., 1)) beta
+    = B in fp64, the intercept not penalised (sklearn.linear_model.Ridge(alpha=lam, fit_intercept=True, sample_weight=w) on the rows).
+    ValueError on a singular system."""
+    A, B = _check_moments(A, B)
+    if not float(lam) >= 0.0:
+        raise ValueError("lam >= 0, got %r" % (lam,))
+    pen = np.full(A.shape[0], float(lam))
+    pen[0] = 0.0
+    beta = _solve_sym(A + np.diag(pen), B, "lime_solve")
+    return beta[0].copy(), np.ascontiguousarray(beta[1:].T)
+
+
+def shap_solve(A, B, f0, f1):
+    """phi f64[K,S]: KernelSHAP's constrained fit from the moment sums of rows weighted by the Shapley kernel.  phi_0 = f0 (the score of
+    the all-off row) and sum_j phi_j = f1 - f0 (f1 the all-on row's) are imposed by eliminating the last superpixel L, as shap's
+    KernelExplainer does: with A's and B's indices shifted by one for the intercept,
+      G[j][l] = A[j][l] - A[j][L] - A[L][l] + A[L][L],   b[j] = (B[j] - B[L]) - f0 * (A[0][j] - A[0][L]) - (f1 - f0) * (A[j][L] - A[L][L])
+    for j, l < L; phi = solve(G, b), phi_L = (f1 - f0) - sum(phi).  f0, f1: f64[K].  ValueError on a singular system or S < 2."""
+    A, B = _check_moments(A, B)
+    n, K = A.shape[0], B.shape[1]
+    s = n - 1
+    if s < 2:
+        raise ValueError("S >= 2, got %d" % s)
+    f0 = np.asarray(f0, dtype=np.float64).reshape(-1)
+    f1 = np.asarray(f1, dtype=np.float64).reshape(-1)
+    if f0.shape != (K,) or f1.shape != (K,):
+        raise ValueError("f0 and f1 must be [K=%d], got %s and %s" % (K, f0.shape, f1.shape))
+    L = s                                   # the last superpixel's index in A and B
+    delta = f1 - f0
+    G = A[1:L, 1:L] - A[1:L, L:L + 1] - A[L:L + 1, 1:L] + A[L, L]
+    b = ((B[1:L] - B[L:L + 1]) - f0[None, :] * (A[0, 1:L] - A[0, L])[:, None]
+         - delta[None, :] * (A[1:L, L] - A[L, L])[:, None])
+    phi = np.empty((K, s), dtype=np.float64)
+    phi[:, :s - 1] = _solve_sym(G, b, "shap_solve").T
+    phi[:, s - 1] = delta - phi[:, :s - 1].sum(axis=1)
+    return phi
+
+
+def segment_paint(seg, value):
+    """f32[K,H,W]: out[k][p] = value[k][seg[p]], +0.0 where seg[p] lies outside [0, S) -- what mpx_segment_paint writes.  seg: an integer
+    [H,W] map of ranks; value: f32[K,S]."""
+    seg, value = np.asarray(seg), np.asarray(value)
+    if seg.ndim != 2 or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError("seg must be an integer [H,W] map, got %s%s" % (seg.dtype, seg.shape))
+    if value.dtype != np.float32 or value.ndim != 2 or value.shape[1] < 1:
+        raise ValueError("value must be float32[K,S], got %s%s" % (value.dtype, value.shape))
+    inside = (seg >= 0) & (seg < value.shape[1])
+    return np.where(inside[None], value[:, np.where(inside, seg, 0)], np.float32(0.0)).astype(np.float32)
 
 
 # ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------

@@ -196,8 +196,8 @@ SIGNATURES = {
     "mpx_segment_paint": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
-SOFTMASK_TILE = 32      # csrc/mpx_softmask.h SM_MT: the masks one block of the apply kernels loops over
-RANKMASK_TILE = 32      # csrc/mpx_rankmask.h RM_MT: the rows one block of rank_apply_kernel loops over
+SOFTMASK_TILE = 32      # csrc/mpx_stage.h STAGE_MT: the rows one block of every apply kernel loops over ...
+RANKMASK_TILE = SOFTMASK_TILE   # ... under the name the rank-mask tests know it by
 SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
 SURROGATE_S_MAX = 1024     # csrc/mpx_surrogate.h SUR_S_MAX: the most superpixels mpx_surrogate_accumulate / mpx_segment_paint take
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes

@@ -1909,103 +1909,105 @@ int mpx_norm_params(const mpx_engine* h, int k, const float** scale, const float
     return 0;
 }
 
+// ---- input staging: what the entries that read an image and the entries that fill input slots share ----
+extern "C++" {
+// The image source of a staging entry into p: exactly one of u8 / f32, mean / std required for u8 and 0 / 1 where absent.
+template <class P>
+static int image_source(mpx_engine* h, const char* what, P& p, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float mean[3],
+                        const float std[3]) {
+    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "%s: exactly one of img_u8_hwc / img_f32_chw must be given", what);
+    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "%s: mean/std required for u8 input", what);
+    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw;
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean ? mean[c] : 0.f;
+        p.std[c] = std ? std[c] : 1.f;
+    }
+    return 0;
+}
+
+// The tail of an apply entry: M rows of p into the input slots [p.slot0, p.slot0 + M), one block per 256 pixels and STAGE_MT rows.
+template <class P>
+static int launch_stage(mpx_engine* h, void (*kernel)(P), int M, size_t lds, void* stream, P& p) {
+    p.out_hi = h->in_hi; p.out_lo = h->in_lo;
+    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(h, st, 1, -1);
+    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + STAGE_MT - 1) / STAGE_MT);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, p);
+    MPX_HIP(h, hipGetLastError());
+    std::fill(h->slot_src.begin() + p.slot0, h->slot_src.begin() + p.slot0 + M, (uint8_t)1);
+    return 0;
+}
+
+// The weight source of a soft_* entry into p: RISE's cells, shifts and grid geometry, or the explicit weight maps.
+template <class WS>
+static void soft_source(SoftParams& p, const void* mask, const void* mask2, int s) {
+    if (WS::kLds) {
+        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
+        p.s = s;
+        p.cell = (MPX_IMG + s - 1) / s;
+        p.U2 = 2 * (s + 1) * p.cell;
+        p.f_U2 = (float)p.U2;
+        p.inv_U2 = 1.0f / p.f_U2;
+    } else {
+        p.weights = (const float*)mask;
+    }
+}
+}  // extern "C++"
+
+// K0: on/off rows over a label map, the soft apply kernel with the on/off weight source (mpx_softmask.h)
 int mpx_mask_apply_normalize(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* seg,
                              const uint8_t* onoff, int M, int S, const float mean[3], const float std[3], int slot0,
                              float* out_f32_nchw, void* stream) {
     if (!h) return MPX_E_ARG;
-    if (h->small) return fail(h, MPX_E_STATE, "mask_apply_normalize: this engine runs one of the small networks; use mpx_mask_apply_minmax");
-    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
-        return fail(h, MPX_E_ARG, "mask_apply_normalize: exactly one of img_u8_hwc / img_f32_chw must be given");
-    if (!seg || !onoff || M <= 0 || S <= 0) return fail(h, MPX_E_ARG, "mask_apply_normalize: null input or empty M/S");
-    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "mask_apply_normalize: mean/std required for u8 input");
-    if (slot0 < 0 || slot0 + M > h->max_batch) return fail(h, MPX_E_STATE, "mask_apply_normalize: slots [%d,%d) exceed max_batch %d", slot0, slot0 + M, h->max_batch);
-    const size_t lds = round_up((size_t)K0_MT * S, 16);
-    if (lds > 64 * 1024) return fail(h, MPX_E_ARG, "mask_apply_normalize: S=%d too large (max %d)", S, 64 * 1024 / K0_MT);
-    MaskParams p;
+    if (h->small) return fail(h, MPX_E_STATE, "mask_apply_normalize: this engine runs one of the small networks; use mpx_mask_apply_minmax");       // wording 1 of 3
+    SoftParams p;
     std::memset(&p, 0, sizeof p);
-    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw; p.seg = seg; p.onoff = onoff;
-    p.out_hi = h->in_hi; p.out_lo = h->in_lo; p.out_f32 = out_f32_nchw;
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean ? mean[c] : 0.f;
-        p.std[c] = std ? std[c] : 1.f;
-    }
+    if (const int rc = image_source(h, "mask_apply_normalize", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
+    if (!seg || !onoff || M <= 0 || S <= 0) return fail(h, MPX_E_ARG, "mask_apply_normalize: null input or empty M/S");    // M == 0 is refused here; the soft and rank entries return 0
+    // a slot overflow is MPX_E_STATE here and MPX_E_ARG in the soft and rank entries; slot0 + M is not widened here
+    if (slot0 < 0 || slot0 + M > h->max_batch) return fail(h, MPX_E_STATE, "mask_apply_normalize: slots [%d,%d) exceed max_batch %d", slot0, slot0 + M, h->max_batch);
+    const size_t lds = OnoffWeights::lds_bytes(S);
+    if (lds > 64 * 1024) return fail(h, MPX_E_ARG, "mask_apply_normalize: S=%d too large (max %d)", S, 64 * 1024 / STAGE_MT);
+    p.seg = seg; p.onoff = onoff; p.out_f32 = out_f32_nchw;
     p.M = M; p.S = S; p.slot0 = slot0;
-    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 1, -1);
-    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + K0_MT - 1) / K0_MT);
-    hipLaunchKernelGGL(mask_apply_normalize_kernel, grid, dim3(256), lds, st, p);
-    MPX_HIP(h, hipGetLastError());
-    std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
-    return 0;
+    return launch_stage(h, softmask_apply_kernel<OnoffWeights>, M, lds, stream, p);
 }
 
 // ---- real-valued masks (mpx_softmask.h): explicit weights or RISE's grids, applied like K0 and summed with the scores ----
 extern "C++" {
-static void soft_rise_geometry(SoftParams& p, int s) {
-    p.s = s;
-    p.cell = (MPX_IMG + s - 1) / s;
-    p.U2 = 2 * (s + 1) * p.cell;
-    p.f_U2 = (float)p.U2;
-    p.inv_U2 = 1.0f / p.f_U2;
-}
-
 template <class WS>
 static int soft_apply(mpx_engine* h, const char* what, const uint8_t* img_u8_hwc, const float* img_f32_chw, const void* mask, const void* mask2,
                       int M, int s, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
     if (!h) return MPX_E_ARG;
-    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's", what);
+    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's", what);      // wording 2 of 3
     if (WS::kLds && (s < SM_S_MIN || s > SM_S_MAX)) return fail(h, MPX_E_ARG, "%s: s=%d outside [%d, %d]", what, s, SM_S_MIN, SM_S_MAX);
-    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "%s: exactly one of img_u8_hwc / img_f32_chw must be given", what);
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, what, p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
     if (!mask || (WS::kLds && !mask2)) return fail(h, MPX_E_ARG, "%s: null mask pointer", what);
-    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "%s: mean/std required for u8 input", what);
     if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
         return fail(h, MPX_E_ARG, "%s: slots [%d,%lld) outside [0, max_batch=%d)", what, slot0, (long long)slot0 + M, h->max_batch);
     if (M == 0) return 0;
-    SoftParams p;
-    std::memset(&p, 0, sizeof p);
-    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw;
-    if (WS::kLds) {
-        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
-        soft_rise_geometry(p, s);
-    } else {
-        p.weights = (const float*)mask;
-    }
-    p.out_hi = h->in_hi; p.out_lo = h->in_lo; p.out_f32 = out_f32_nchw;
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean ? mean[c] : 0.f;
-        p.std[c] = std ? std[c] : 1.f;
-    }
+    soft_source<WS>(p, mask, mask2, s);
+    p.out_f32 = out_f32_nchw;
     p.M = M; p.slot0 = slot0;
-    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 1, -1);
-    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + SM_MT - 1) / SM_MT);
-    hipLaunchKernelGGL(softmask_apply_kernel<WS>, grid, dim3(256), WS::lds_bytes(s), st, p);
-    MPX_HIP(h, hipGetLastError());
-    std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
-    return 0;
+    return launch_stage(h, softmask_apply_kernel<WS>, M, WS::lds_bytes(s), stream, p);
 }
 
 template <class WS>
 static int soft_saliency(mpx_engine* h, const char* what, const void* mask, const void* mask2, const float* weight, int M, int s, float* sal,
                          void* stream) {
     if (!h) return MPX_E_ARG;
-    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks (no 224 x 224 input)", what);
+    if (h->small) return fail(h, MPX_E_STATE, "%s: this engine runs one of the small networks (no 224 x 224 input)", what);       // wording 3 of 3
     if (WS::kLds && (s < SM_S_MIN || s > SM_S_MAX)) return fail(h, MPX_E_ARG, "%s: s=%d outside [%d, %d]", what, s, SM_S_MIN, SM_S_MAX);
     if (!mask || (WS::kLds && !mask2) || !weight || !sal) return fail(h, MPX_E_ARG, "%s: null pointer", what);
     if (M < 0) return fail(h, MPX_E_ARG, "%s: M=%d", what, M);
     if (M == 0) return 0;
     SoftParams p;
     std::memset(&p, 0, sizeof p);
-    if (WS::kLds) {
-        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
-        soft_rise_geometry(p, s);
-    } else {
-        p.weights = (const float*)mask;
-    }
+    soft_source<WS>(p, mask, mask2, s);
     p.score = weight; p.sal = sal; p.M = M;
     p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
     MPX_SET_DEVICE(h);
@@ -2065,12 +2067,7 @@ static int soft_saliency_classes(mpx_engine* h, const char* what, const void* ma
     if (score_pitch < K) return fail(h, MPX_E_ARG, "%s: score_pitch=%d < K=%d", what, score_pitch, K);
     SoftParams p;
     std::memset(&p, 0, sizeof p);
-    if (WS::kLds) {
-        p.cells = (const uint8_t*)mask; p.shift = (const int32_t*)mask2;
-        soft_rise_geometry(p, s);
-    } else {
-        p.weights = (const float*)mask;
-    }
+    soft_source<WS>(p, mask, mask2, s);
     p.score = scores; p.sal = sal; p.M = M;
     p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
     MPX_SET_DEVICE(h);
@@ -2141,51 +2138,31 @@ int mpx_rank_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f3
                    void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->small) return fail(h, MPX_E_STATE, "rank_apply: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's");
-    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "rank_apply: exactly one of img_u8_hwc / img_f32_chw must be given");
+    RankParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, "rank_apply", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
     if (!rank || !thresh) return fail(h, MPX_E_ARG, "rank_apply: null rank or thresh pointer");
-    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "rank_apply: mean/std required for u8 input");
     if (keep_top != 0 && keep_top != 1) return fail(h, MPX_E_ARG, "rank_apply: keep_top=%d is neither 0 nor 1", keep_top);
     if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
         return fail(h, MPX_E_ARG, "rank_apply: slots [%d,%lld) outside [0, max_batch=%d)", slot0, (long long)slot0 + M, h->max_batch);
     if (M == 0) return 0;
-    RankParams p;
-    std::memset(&p, 0, sizeof p);
-    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw;
-    p.rank = rank; p.thresh = thresh; p.fill = fill_f32_chw;
-    p.out_hi = h->in_hi; p.out_lo = h->in_lo; p.out_f32 = out_f32_nchw;
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean ? mean[c] : 0.f;
-        p.std[c] = std ? std[c] : 1.f;
-    }
+    p.rank = rank; p.thresh = thresh; p.fill = fill_f32_chw; p.out_f32 = out_f32_nchw;
     p.M = M; p.slot0 = slot0; p.keep_top = keep_top;
-    p.size = MPX_IMG; p.pad_size = MPX_IMG_PAD; p.border = 3;
-    MPX_SET_DEVICE(h);
-    hipStream_t st = as_stream(stream);
-    ProfScope ps(h, st, 1, -1);
-    dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, (M + RM_MT - 1) / RM_MT);
-    hipLaunchKernelGGL(rank_apply_kernel, grid, dim3(256), 0, st, p);
-    MPX_HIP(h, hipGetLastError());
-    std::fill(h->slot_src.begin() + slot0, h->slot_src.begin() + slot0 + M, (uint8_t)1);
-    return 0;
+    return launch_stage(h, rank_apply_kernel, M, 0, stream, p);
 }
 
 int mpx_blur_fill(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* taps, int klen, const float mean[3],
                   const float std[3], float* out_f32_chw, void* stream) {
     if (!h) return MPX_E_ARG;
     if (h->small) return fail(h, MPX_E_STATE, "blur_fill: this engine runs one of the small networks (no 224 x 224 input)");
-    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr)) return fail(h, MPX_E_ARG, "blur_fill: exactly one of img_u8_hwc / img_f32_chw must be given");
-    if (!taps || !out_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: null taps or out pointer");
-    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "blur_fill: mean/std required for u8 input");
-    if (klen < 1 || klen > BF_KMAX || (klen & 1) == 0) return fail(h, MPX_E_ARG, "blur_fill: klen=%d is not an odd number in [1, %d]", klen, BF_KMAX);
-    if (out_f32_chw == img_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: out_f32_chw must not be the image (every block reads its neighbours' pixels)");
     BlurParams p;
     std::memset(&p, 0, sizeof p);
-    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw; p.out = out_f32_chw;
+    if (const int rc = image_source(h, "blur_fill", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
+    if (!taps || !out_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: null taps or out pointer");
+    if (klen < 1 || klen > BF_KMAX || (klen & 1) == 0) return fail(h, MPX_E_ARG, "blur_fill: klen=%d is not an odd number in [1, %d]", klen, BF_KMAX);
+    if (out_f32_chw == img_f32_chw) return fail(h, MPX_E_ARG, "blur_fill: out_f32_chw must not be the image (every block reads its neighbours' pixels)");
+    p.out = out_f32_chw;
     for (int k = 0; k < klen; ++k) p.taps[k] = taps[k];
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean ? mean[c] : 0.f;
-        p.std[c] = std ? std[c] : 1.f;
-    }
     p.klen = klen; p.size = MPX_IMG;
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);
@@ -2200,10 +2177,10 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
     if (!h) return MPX_E_ARG;
     if (h->densenet) return fail(h, MPX_E_STATE, "stem_table_build: a DenseNet engine keeps no stem table; it stages through mpx_mask_apply_normalize");
     if (!h->stem_w32) return fail(h, MPX_E_STATE, "stem_table_build: this architecture has no 7x7 stem with a max pool%s", !h->small ? " (VGG, AlexNet, MobileNetV2, SqueezeNet, GoogLeNet, ShuffleNetV2, EfficientNet-B0, ConvNeXt, ViT, RegNetX and RegNetY stage through mpx_mask_apply_normalize)" : "");
-    if ((img_u8_hwc == nullptr) == (img_f32_chw == nullptr))
-        return fail(h, MPX_E_ARG, "stem_table_build: exactly one of img_u8_hwc / img_f32_chw must be given");
+    StemTabParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, "stem_table_build", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
     if (!seg || S <= 0 || S > 4096) return fail(h, MPX_E_ARG, "stem_table_build: null label map or S outside [1, 4096]");
-    if (img_u8_hwc && (!mean || !std)) return fail(h, MPX_E_ARG, "stem_table_build: mean/std required for u8 input");
     if (!h->stem_w_loaded) return fail(h, MPX_E_STATE, "stem_table_build: layer 0 (%s) has no weights", h->convs[0].d.name);
     MPX_SET_DEVICE(h);
     if (!h->tab_arena) {            // first table of this engine: its 160 MB are allocated now, once (the only allocation behind the boundary after mpx_create)
@@ -2219,13 +2196,7 @@ int mpx_stem_table_build(mpx_engine* h, const uint8_t* img_u8_hwc, const float* 
         h->tab_vec = (float*)take(h->tab_sizes[2]);
         h->tab_bits = (unsigned*)take(h->tab_sizes[3]);
     }
-    StemTabParams p;
-    std::memset(&p, 0, sizeof p);
-    p.img_u8 = img_u8_hwc; p.img_f32 = img_f32_chw; p.seg = seg; p.S = S;
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean ? mean[c] : 0.f;
-        p.std[c] = std ? std[c] : 1.f;
-    }
+    p.seg = seg; p.S = S;
     p.w = h->stem_w32; p.cnt = h->tab_cnt; p.off = h->tab_off; p.lab = h->tab_lab; p.vec = h->tab_vec;
     MPX_SET_DEVICE(h);
     hipStream_t st = as_stream(stream);

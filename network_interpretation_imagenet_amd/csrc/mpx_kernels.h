@@ -6,88 +6,13 @@
 // issued on the fp16 MFMA pipe as three products  W_hi*X_lo + W_lo*X_hi + W_hi*X_hi  with
 // fp32 accumulation (v_mfma_f32_16x16x32_f16), which reproduces fp32 convolution to ~1e-7
 // relative (oracle/precision_study.py) at 1/3 of the fp16 MFMA rate = 5.3x the f32 MFMA rate.
+//
+// Here: the pools, the head and the small networks' kernels.  K0 (mask-apply + normalise) is softmask_apply_kernel<OnoffWeights> in
+// mpx_softmask.h; the pixel and the slot store every staging kernel shares are in mpx_stage.h.
 #pragma once
 #include "mpx_conv.h"
 
 namespace mpx {
-
-// ------------------------------------------------------------------------------------------
-// K0: mask-apply + normalise.  One thread = one pixel; a block stages the on/off rows of MT masks
-// in LDS ([MT][S] bytes) and loops over them, so the image and the label map are read once per
-// MT masks and every store is a coalesced 512-B (planes) / 256-B (f32) wave row.
-// ------------------------------------------------------------------------------------------
-constexpr int K0_MT = 32;
-
-struct MaskParams {
-    const uint8_t* img_u8;   // [H][W][3] or null
-    const float* img_f32;    // [3][H][W] or null
-    const int32_t* seg;      // [H][W]
-    const uint8_t* onoff;    // [M][S]
-    half_t* out_hi;          // engine staging, slot 0 (padded NHWC4)
-    half_t* out_lo;
-    float* out_f32;          // [M][3][H][W] or null
-    float mean[3], std[3];
-    int M, S, slot0;
-    int size, pad_size, border;   // 224, 230, 3
-};
-
-__global__ __launch_bounds__(256) void mask_apply_normalize_kernel(const MaskParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint8_t* s_onoff = (uint8_t*)smem;
-    const int tid = threadIdx.x;
-    const int m_base = blockIdx.y * K0_MT;
-    const int mt = min(K0_MT, p.M - m_base);
-    {   // stage mt*S bytes (4-byte words when aligned, bytes otherwise)
-        const uint8_t* src = p.onoff + (size_t)m_base * p.S;
-        const int nbytes = mt * p.S;
-        for (int i = tid; i < nbytes; i += 256) s_onoff[i] = src[i];
-    }
-    __syncthreads();
-    const int hw = p.size * p.size;
-    const int pix = blockIdx.x * 256 + tid;
-    if (pix >= hw) return;
-    const int y = pix / p.size, x = pix - y * p.size;
-    int s = p.seg[pix];
-    const bool s_ok = (unsigned)s < (unsigned)p.S;
-    if (!s_ok) s = 0;
-    float v[3];
-    if (p.img_u8) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            // ToTensor: u8 -> f32, .div(255); Normalize: .sub_(mean).div_(std); each op rounds in fp32
-            const float t = __fdiv_rn((float)p.img_u8[(size_t)pix * 3 + c], 255.0f);
-            v[c] = __fdiv_rn(__fsub_rn(t, p.mean[c]), p.std[c]);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = p.img_f32[(size_t)c * hw + pix];
-    }
-    const size_t plane = (size_t)p.pad_size * p.pad_size * 4;
-    const size_t pad_off = ((size_t)(y + p.border) * p.pad_size + (x + p.border)) * 4;
-    for (int mi = 0; mi < mt; ++mi) {
-        const float keep = (s_ok && s_onoff[mi * p.S + s]) ? 1.0f : 0.0f;
-        const int m = m_base + mi;
-        float o[3];
-        h4 oh, ol;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            o[c] = fp32_value(v[c] * keep);     // x * mask, as numpy does it (-x*0 = -0.0), also in the planes: hi -0.0, lo +0.0 (fp32_value)
-            half_t hi, lo;
-            split_f32(o[c], hi, lo);
-            oh[c] = hi;
-            ol[c] = lo;
-        }
-        oh[3] = (half_t)0.f;
-        ol[3] = (half_t)0.f;
-        const size_t so = (size_t)(p.slot0 + m) * plane + pad_off;
-        *(h4*)(p.out_hi + so) = oh;       // plain stores: the stem reads these planes next, out of L2 / Infinity Cache
-        *(h4*)(p.out_lo + so) = ol;
-        if (p.out_f32) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p.out_f32[((size_t)m * 3 + c) * hw + pix] = o[c];
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // K3: maxpool 3x3 stride 2 pad 1 on split planes (one thread = 8 channels of one output pixel)

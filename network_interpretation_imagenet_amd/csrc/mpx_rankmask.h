@@ -1,7 +1,9 @@
 // mpx_rankmask.h -- a second pixel source for the input staging: select between the image and a fill image on a per-pixel rank, and the
 // blurred image RISE's insertion curve starts from.
 //
-// Every other staging entry writes the normalised pixel or that pixel times a weight: a removed pixel is zero.  The causal metrics of a
+// Holds rank_apply_kernel and blur_fill_kernel; the normalised pixel and the slot layout are mpx_stage.h's, as in every staging kernel.
+//
+// Every other staging entry writes the normalised pixel times a weight (mpx_softmask.h): a removed pixel is zero.  The causal metrics of a
 // saliency map (Petsiuk, Das, Saenko, "RISE: Randomized Input Sampling for Explanation of Black-box Models", BMVC 2018, section 4.1) need
 // more: DELETION replaces the most salient pixels, `step` more per row, by a substrate; INSERTION starts from a substrate (the blurred image)
 // and reveals them.  Row m of either curve is the image with the pixels of rank below thresh[m] taken from one source and the rest from
@@ -16,7 +18,7 @@
 //   hi, lo = split_f32(o_c); channel 3 = +0.0; the 3-pixel border is not touched; out_f32[m][c][p] = o_c when given.
 // No multiply touches a kept pixel (V * 1.0f == V, so it equals K0's kept pixel bit for bit).  V, F and the two splits of each are computed
 // ONCE per pixel, outside the row loop; the loop body is a compare, a select and two 8-byte h4 stores in K0's coalesced wave rows.  rank[p]
-// and the image are read once per tile of RM_MT rows.
+// and the image are read once per tile of STAGE_MT rows.
 //
 // blur_fill_kernel: the separable correlation of the normalised image with klen taps and zero padding (RISE applies
 // Conv2d(3, 3, klen, padding = klen / 2) with a Gaussian to the normalised tensor).  With r = klen / 2, klen odd in [1, 31]:
@@ -31,11 +33,10 @@
 //
 // Both: #pragma clang fp contract(off), 64-bit offsets, no atomics, no scratch.
 #pragma once
-#include "mpx_conv.h"
+#include "mpx_stage.h"
 
 namespace mpx {
 
-constexpr int RM_MT = 32;           // rows per block tile of rank_apply_kernel (as SM_MT: the image is read once per 32 rows)
 constexpr int BF_TW = 32;           // blur: output tile width
 constexpr int BF_TH = 16;           // blur: output tile height
 constexpr int BF_KMAX = 31;         // blur: most taps
@@ -64,17 +65,11 @@ struct BlurParams {
     int klen, size;
 };
 
-// K0's normalisation of one u8 channel.  ToTensor: u8 -> f32, .div(255); Normalize: .sub_(mean).div_(std); each op rounds in fp32
-__device__ __forceinline__ float normalize_u8(uint8_t b, float mean, float std) {
-    const float t = __fdiv_rn((float)b, 255.0f);
-    return __fdiv_rn(__fsub_rn(t, mean), std);
-}
-
 __global__ __launch_bounds__(256) void rank_apply_kernel(const RankParams p) {
 #pragma clang fp contract(off)
     const int tid = threadIdx.x;
-    const int m_base = blockIdx.y * RM_MT;
-    const int mt = min(RM_MT, p.M - m_base);
+    const int m_base = blockIdx.y * STAGE_MT;
+    const int mt = min(STAGE_MT, p.M - m_base);
     const int hw = p.size * p.size;
     const int pix = blockIdx.x * 256 + tid;
     if (pix >= hw) return;
@@ -102,8 +97,10 @@ __global__ __launch_bounds__(256) void rank_apply_kernel(const RankParams p) {
     }
     a_hi[3] = a_lo[3] = b_hi[3] = b_lo[3] = (half_t)0.f;
     const int rk = p.rank[pix];
+    // The loop keeps its own spelling of the slot store (mpx_stage.h's layout): through store_staged_pixel the four rank rows of
+    // tools/causal_bench.py measured 0.15 to 0.27 % slower than the parent's kernel, with this text the instructions are the parent's
     const size_t plane = (size_t)p.pad_size * p.pad_size * 4;
-    const size_t pad_off = ((size_t)(y + p.border) * p.pad_size + (x + p.border)) * 4;
+    const size_t pad_off = staged_pixel_offset(p, y, x);
     for (int mi = 0; mi < mt; ++mi) {
         const int m = m_base + mi;
         const bool top = rk < p.thresh[m];

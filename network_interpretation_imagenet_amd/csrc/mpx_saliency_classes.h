@@ -102,14 +102,15 @@ __global__ __launch_bounds__(SC_THREADS) void saliency_classes_kernel(const Soft
     float acc[SC_KT];
 #pragma unroll
     for (int j = 0; j < SC_KT; ++j) acc[j] = (active && j < kt) ? sal[(size_t)j * hw] : 0.0f;
-    for (int m_base = 0; m_base < p.M; m_base += SM_MT) {
-        const int mt = min(SM_MT, p.M - m_base);
+    const typename WS::Pixel px = WS::pixel(p, cp);
+    for (int m_base = 0; m_base < p.M; m_base += STAGE_MT) {
+        const int mt = min(STAGE_MT, p.M - m_base);
         if (WS::kLds) {
             WS::stage(p, smem, m_base, mt, tid, SC_THREADS);
             __syncthreads();
         }
         for (int mi = 0; mi < mt; ++mi) {
-            const float w = WS::weight(p, smem, m_base + mi, mi, cp, y, x, hw);
+            const float w = WS::weight(p, smem, px, m_base + mi, mi, cp, y, x, hw);
             const float* srow = p.score + (size_t)(m_base + mi) * score_pitch + k0;
             if (kt == SC_KT) spend_weight<true>(acc, srow, w, kt);
             else spend_weight<false>(acc, srow, w, kt);

@@ -1,11 +1,14 @@
-// mpx_softmask.h -- real-valued per-pixel masks: K0 with a weight in place of `keep`, and the score-weighted sum of the masks.
+// mpx_softmask.h -- the staging kernel of every mask that is a weight per pixel (K0 among them), and the score-weighted sum of the masks.
 //
-// K0 (mpx_kernels.h) takes one kind of mask: the binary union of the superpixels of a label map.  The two kernel bodies here take a
-// weight w_m(p) per mask m and pixel p from one of two sources:
+// softmask_apply_kernel<WS> and softmask_saliency_kernel<WS> take a weight w_m(p) per mask m and pixel p from a weight source WS:
+//   OnoffWeights     w_m(p) = onoff[m][seg[p]] ? 1 : 0: K0, the binary union of the superpixels of a label map (mpx_mask_apply_normalize).
+//                    The tile's STAGE_MT x S on/off bytes are staged in LDS; seg[p] is read once per pixel; a label outside [0, S) weighs 0;
 //   ExplicitWeights  w_m(p) = weights[m][p], DEV f32[M][224][224], read coalesced;
 //   RiseWeights      w_m(p) synthesised from the s x s bits and the shift of mask m: the masks of RISE (Petsiuk, Das, Saenko, "RISE:
 //                    Randomized Input Sampling for Explanation of Black-box Models", BMVC 2018) -- a random s x s grid, upsampled
 //                    bilinearly to U x U with half-pixel centres, cropped to 224 x 224 at a random shift (dy, dx).
+// A source is: kLds, lds_bytes(n), stage() (the tile's rows into LDS), Pixel + pixel() (what it keeps per pixel across the rows of a tile;
+// empty for the explicit and the RISE source) and weight().
 //
 // The RISE weight, stated exactly (cell = ceil(224 / s), U = (s + 1) * cell, 2 <= s <= 32, 0 <= dy, dx < cell; g = the grid as 0.0f / 1.0f):
 //   Y  = y + dy
@@ -23,20 +26,19 @@
 // An all-ones grid gives exactly 1.0 (fl(fl(1 - f) + f) = 1 for every fp32 f in [0, 1)), an all-zeros grid exactly 0.0, everything else
 // lies in [0, 1].
 //
-// Apply:    o = fl(v * w) per channel (ONE fp32 multiply, no FMA with the split behind it), then hi = f16(o), lo = f16(fl(o - f32(hi))) as
-//           split_f32 does.  For w in {0, 1} that is K0's `v * keep`: the f32 output and the planes equal mpx_mask_apply_normalize's bit for
-//           bit, the -0.0 of a removed negative pixel included (hi -0.0, lo +0.0).  Both kernels pin the product in an fp32 register
-//           (fp32_value, mpx_conv.h) before the split: hipcc otherwise folds f16(a * b) into v_fma_mixlo_f16, which rounds the exact product
-//           to fp16 once and turns a -0.0 product into +0.0.
+// Apply:    o = fl(v * w) per channel (ONE fp32 multiply, no FMA with the split behind it), then split_f32: hi = f16(o), lo = f16(fl(o -
+//           f32(hi))).  For w in {0, 1} that is `x * mask` as numpy does it, the -0.0 of a removed negative pixel included (hi -0.0, lo
+//           +0.0), whichever source the weight comes from.  The product is pinned in an fp32 register (fp32_value, mpx_conv.h) before the
+//           split: hipcc otherwise folds f16(a * b) into v_fma_mixlo_f16, which rounds the exact product to fp16 once and turns a -0.0
+//           product into +0.0.
 // Saliency: sal[p] <- fl(sal[p] + fl(weight[m] * w_m(p))) for m = 0, 1, .., M - 1 in this order: a multiply and an add, each rounded, NOT an
 //           FMA.  One thread owns a pixel and walks the masks in order -- no atomics, no reduction tree --, so a pixel's bits depend neither on
 //           the grid nor on how the rows are cut into consecutive calls.
 #pragma once
-#include "mpx_conv.h"
+#include "mpx_stage.h"
 
 namespace mpx {
 
-constexpr int SM_MT = 32;           // masks per block tile: what a block stages of the RISE cells (<= 1 KB per mask) and shifts in LDS
 constexpr int SM_S_MIN = 2;
 constexpr int SM_S_MAX = 32;
 constexpr int SM_SAL_THREADS = 64;  // saliency: one wave per block, 784 blocks over the 256 CUs
@@ -44,6 +46,8 @@ constexpr int SM_SAL_THREADS = 64;  // saliency: one wave per block, 784 blocks 
 struct SoftParams {
     const uint8_t* img_u8;   // [H][W][3] or null                          (apply)
     const float* img_f32;    // [3][H][W] or null                          (apply)
+    const int32_t* seg;      // [H][W]                                     (on/off source)
+    const uint8_t* onoff;    // [M][S], non-zero = keep                    (on/off source)
     const float* weights;    // [M][H][W]                                  (explicit source)
     const uint8_t* cells;    // [M][s][s], non-zero = keep                 (RISE source)
     const int32_t* shift;    // [M][2] = (dy, dx)                          (RISE source)
@@ -53,7 +57,7 @@ struct SoftParams {
     half_t* out_lo;
     float* out_f32;          // [M][3][H][W] or null                       (apply)
     float mean[3], std[3];
-    int M, slot0;
+    int M, S, slot0;
     int s, cell, U2;         // RISE: grid size, ceil(224 / s), 2U = 2 * (s + 1) * cell
     float f_U2, inv_U2;      // float(2U) (exact) and 1 / float(2U) (a first guess of the quotient only)
     int size, pad_size, border;   // 224, 230, 3
@@ -74,32 +78,56 @@ __device__ __forceinline__ void rise_axis(int Y, const SoftParams& p, int& i0, i
     f = __fdiv_rn((float)r, p.f_U2);
 }
 
+struct NoPixelState {};
+
+struct OnoffWeights {
+    static constexpr bool kLds = true;
+    struct Pixel { int s; bool ok; };
+    static size_t lds_bytes(int S) { return ((size_t)STAGE_MT * S + 15) & ~(size_t)15; }      // u8[STAGE_MT][S]
+    __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int nthreads) {
+        const uint8_t* src = p.onoff + (size_t)m_base * p.S;
+        for (int i = tid; i < mt * p.S; i += nthreads) smem[i] = src[i];
+    }
+    __device__ static __forceinline__ Pixel pixel(const SoftParams& p, int pix) {
+        const int s = p.seg[pix];
+        const bool ok = (unsigned)s < (unsigned)p.S;
+        return {ok ? s : 0, ok};
+    }
+    __device__ static __forceinline__ float weight(const SoftParams& p, const char* smem, Pixel px, int, int mi, int, int, int, int) {
+        return (px.ok && smem[mi * p.S + px.s]) ? 1.0f : 0.0f;
+    }
+};
+
 struct ExplicitWeights {
     static constexpr bool kLds = false;
+    typedef NoPixelState Pixel;
     static size_t lds_bytes(int) { return 0; }
     __device__ static __forceinline__ void stage(const SoftParams&, char*, int, int, int, int) {}
-    __device__ static __forceinline__ float weight(const SoftParams& p, const char*, int m, int, int pix, int, int, int hw) {
+    __device__ static __forceinline__ Pixel pixel(const SoftParams&, int) { return {}; }
+    __device__ static __forceinline__ float weight(const SoftParams& p, const char*, Pixel, int m, int, int pix, int, int, int hw) {
         return p.weights[(size_t)m * hw + pix];
     }
 };
 
 struct RiseWeights {
     static constexpr bool kLds = true;
-    // LDS: i32[SM_MT][2] shifts, then u8[SM_MT][s * s] cells
-    static size_t lds_bytes(int s) { return (size_t)SM_MT * 8 + (((size_t)SM_MT * s * s + 15) & ~(size_t)15); }
+    typedef NoPixelState Pixel;
+    // LDS: i32[STAGE_MT][2] shifts, then u8[STAGE_MT][s * s] cells
+    static size_t lds_bytes(int s) { return (size_t)STAGE_MT * 8 + (((size_t)STAGE_MT * s * s + 15) & ~(size_t)15); }
     __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int nthreads) {
         int* s_shift = (int*)smem;
-        uint8_t* s_cells = (uint8_t*)smem + SM_MT * 8;
+        uint8_t* s_cells = (uint8_t*)smem + STAGE_MT * 8;
         const int ss = p.s * p.s;
         const uint8_t* src = p.cells + (size_t)m_base * ss;
         for (int i = tid; i < mt * ss; i += nthreads) s_cells[i] = src[i];
         // a shift outside [0, cell) is outside the contract; clamped here so that no coordinate leaves the grid whatever the caller passes
         for (int i = tid; i < mt * 2; i += nthreads) s_shift[i] = min(max(p.shift[(size_t)m_base * 2 + i], 0), p.cell - 1);
     }
-    __device__ static __forceinline__ float weight(const SoftParams& p, const char* smem, int, int mi, int, int y, int x, int) {
+    __device__ static __forceinline__ Pixel pixel(const SoftParams&, int) { return {}; }
+    __device__ static __forceinline__ float weight(const SoftParams& p, const char* smem, Pixel, int, int mi, int, int y, int x, int) {
 #pragma clang fp contract(off)
         const int* s_shift = (const int*)smem;
-        const uint8_t* g = (const uint8_t*)smem + SM_MT * 8 + mi * p.s * p.s;
+        const uint8_t* g = (const uint8_t*)smem + STAGE_MT * 8 + mi * p.s * p.s;
         int i0, i1, j0, j1;
         float fy, fx;
         rise_axis(y + s_shift[mi * 2], p, i0, i1, fy);
@@ -113,16 +141,16 @@ struct RiseWeights {
     }
 };
 
-// Apply: K0 with `keep` replaced by w.  One thread = one pixel; a block loops over a tile of SM_MT masks (the RISE source stages their cells
-// and shifts in LDS first), so the image is read once per SM_MT masks and every store is the coalesced wave row K0 writes.  No atomics, no
-// scratch, 64-bit offsets.
+// Apply.  One thread = one pixel; a block loops over a tile of STAGE_MT masks (a source with kLds stages what it needs of them in LDS
+// first), so the image -- and the on/off source's label map -- is read once per STAGE_MT masks and every store is a coalesced 512-B
+// (planes) / 256-B (f32) wave row.  No atomics, no scratch, 64-bit offsets.
 template <class WS>
 __global__ __launch_bounds__(256) void softmask_apply_kernel(const SoftParams p) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-    const int m_base = blockIdx.y * SM_MT;
-    const int mt = min(SM_MT, p.M - m_base);
+    const int m_base = blockIdx.y * STAGE_MT;
+    const int mt = min(STAGE_MT, p.M - m_base);
     if (WS::kLds) {
         WS::stage(p, smem, m_base, mt, tid, 256);
         __syncthreads();
@@ -131,41 +159,21 @@ __global__ __launch_bounds__(256) void softmask_apply_kernel(const SoftParams p)
     const int pix = blockIdx.x * 256 + tid;
     if (pix >= hw) return;
     const int y = pix / p.size, x = pix - y * p.size;
+    const typename WS::Pixel px = WS::pixel(p, pix);
     float v[3];
-    if (p.img_u8) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            // K0's op sequence.  ToTensor: u8 -> f32, .div(255); Normalize: .sub_(mean).div_(std); each op rounds in fp32
-            const float t = __fdiv_rn((float)p.img_u8[(size_t)pix * 3 + c], 255.0f);
-            v[c] = __fdiv_rn(__fsub_rn(t, p.mean[c]), p.std[c]);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = p.img_f32[(size_t)c * hw + pix];
-    }
-    const size_t plane = (size_t)p.pad_size * p.pad_size * 4;
-    const size_t pad_off = ((size_t)(y + p.border) * p.pad_size + (x + p.border)) * 4;
+    load_normalized_pixel(p.img_u8, p.img_f32, p.mean, p.std, pix, hw, v);
+    const size_t pad_off = staged_pixel_offset(p, y, x);
     for (int mi = 0; mi < mt; ++mi) {
         const int m = m_base + mi;
-        const float w = WS::weight(p, smem, m, mi, pix, y, x, hw);
+        const float w = WS::weight(p, smem, px, m, mi, pix, y, x, hw);
         float o[3];
-        h4 oh, ol;
+        half_t hi[3], lo[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            o[c] = fp32_value(v[c] * w);            // one rounded multiply; split_f32's two lines follow here, where contraction is off, so
-            const half_t hi = (half_t)o[c];         // that hi and o - hi are taken from the ROUNDED product and never fused with it
-            oh[c] = hi;
-            ol[c] = (half_t)(o[c] - (float)hi);
+            o[c] = fp32_value(v[c] * w);            // one rounded multiply, pinned: hi and o - hi are taken from the ROUNDED product
+            split_f32(o[c], hi[c], lo[c]);
         }
-        oh[3] = (half_t)0.f;
-        ol[3] = (half_t)0.f;
-        const size_t so = (size_t)(p.slot0 + m) * plane + pad_off;
-        *(h4*)(p.out_hi + so) = oh;
-        *(h4*)(p.out_lo + so) = ol;
-        if (p.out_f32) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) p.out_f32[((size_t)m * 3 + c) * hw + pix] = o[c];
-        }
+        store_staged_pixel(p, m, pad_off, pix, hw, staged_h4(hi), staged_h4(lo), o);
     }
 }
 
@@ -181,15 +189,16 @@ __global__ __launch_bounds__(SM_SAL_THREADS) void softmask_saliency_kernel(const
     const bool active = pix < hw;       // no early return: every thread of the block meets the barriers below
     const int cp = active ? pix : 0;
     const int y = cp / p.size, x = cp - y * p.size;
+    const typename WS::Pixel px = WS::pixel(p, cp);
     float acc = active ? p.sal[cp] : 0.0f;
-    for (int m_base = 0; m_base < p.M; m_base += SM_MT) {
-        const int mt = min(SM_MT, p.M - m_base);
+    for (int m_base = 0; m_base < p.M; m_base += STAGE_MT) {
+        const int mt = min(STAGE_MT, p.M - m_base);
         if (WS::kLds) {
             WS::stage(p, smem, m_base, mt, tid, SM_SAL_THREADS);
             __syncthreads();
         }
         for (int mi = 0; mi < mt; ++mi) {
-            const float w = WS::weight(p, smem, m_base + mi, mi, cp, y, x, hw);
+            const float w = WS::weight(p, smem, px, m_base + mi, mi, cp, y, x, hw);
             const float t = p.score[m_base + mi] * w;       // rounded product ...
             acc = acc + t;                                  // ... rounded sum: not an FMA
         }

@@ -19,7 +19,7 @@
 // lab[e] = superpixel rank of entry e, vec[e][64] = its 64 output channels (pre-BatchNorm).  Labels outside [0, S) and taps in the zero
 // padding contribute nothing (K0 treats an out-of-range label as "removed" too).  Capacity is the worst case, 49 entries per pixel.
 #pragma once
-#include "mpx_conv.h"
+#include "mpx_stage.h"
 
 namespace mpx {
 
@@ -105,18 +105,7 @@ __global__ __launch_bounds__(256) void stemtab_fill_kernel(const StemTabParams p
     int pix = 0;
     const int l = lane < ST_TAPS ? st_tap_label(p, oy, ox, lane, &pix) : -1;
     float x[3] = {0.f, 0.f, 0.f};
-    if (l >= 0) {
-        if (p.img_u8) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {       // K0's arithmetic (ToTensor .div(255), Normalize .sub_(mean).div_(std), each rounded in fp32)
-                const float t = __fdiv_rn((float)p.img_u8[(size_t)pix * 3 + c], 255.0f);
-                x[c] = __fdiv_rn(__fsub_rn(t, p.mean[c]), p.std[c]);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x[c] = p.img_f32[(size_t)c * ST_IN * ST_IN + pix];
-        }
-    }
+    if (l >= 0) load_normalized_pixel(p.img_u8, p.img_f32, p.mean, p.std, pix, ST_IN * ST_IN, x);       // the pixel every staging kernel sees
     s_lab[wave][lane] = l;
 #pragma unroll
     for (int c = 0; c < 3; ++c) s_x[wave][c][lane] = x[c];

@@ -135,6 +135,41 @@ def rank_segments(segments):
     return inv.reshape(IMG, IMG).astype(np.int32), int(len(uniq))
 
 
+class _Packer:
+    """The rows of consecutive jobs packed into forwards of up to max_batch slots (a job's rows may straddle two forwards); row g of the
+    call reads label_rows[g] and writes score_out[g] / pred_out[g].  Allocates nothing, synchronises nothing."""
+
+    def __init__(self, eng, label_rows, score_out, pred_out):
+        self.eng, self.label_rows, self.score_out, self.pred_out = eng, label_rows, score_out, pred_out
+        self.done, self.used, self.kind = 0, 0, None    # rows handed to a forward; slots staged for the next one; how those were staged
+
+    def flush(self):
+        at = slice(self.done, self.done + self.used)
+        self.eng.forward(self.used, self.label_rows[at], score_out=self.score_out[at], pred_out=self.pred_out[at])
+        self.done += self.used
+        self.used = 0
+
+    def add(self, rows, stage_fn):
+        """stage_fn(r, take, slot0) stages rows [r, r + take) of a job into slots [slot0, slot0 + take); a full forward runs at once."""
+        r = 0
+        while r < rows:
+            take = min(rows - r, self.eng.max_batch - self.used)
+            stage_fn(r, take, self.used)
+            self.used += take
+            r += take
+            if self.used == self.eng.max_batch:
+                self.flush()
+
+    def kind_changes(self, kind):       # a forward takes its slots from one kind of staging: a pending one of another kind runs now
+        if self.used and kind != self.kind:
+            self.flush()
+        self.kind = kind
+
+    def finish(self):
+        if self.used:
+            self.flush()
+
+
 class MaskedForwardEngine:
     """One engine per process per GPU (one RCCL rank).  `arch` is the reference's `-a/--arch`."""
 
@@ -439,6 +474,18 @@ class MaskedForwardEngine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _image_ptrs(self, image):
+        """(u8 pointer, f32 pointer) of a device image, one of them None: raw u8[224,224,3] or normalised f32[3,224,224]."""
+        if image.dtype == torch.uint8 and tuple(image.shape) == (IMG, IMG, 3):
+            return _ptr(image), None
+        if image.dtype == torch.float32 and tuple(image.shape) == (3, IMG, IMG):
+            return None, _ptr(image)
+        raise ValueError("image must be uint8[224,224,3] or float32[3,224,224], got %s%s" % (image.dtype, tuple(image.shape)))
+
+    def _require_imagenet(self):
+        if self.small:
+            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+
     def stage_masks(self, image, seg, onoff, slot0=0, out_f32=None):
         """K0.  image: device u8[224,224,3] (raw) or f32[3,224,224] (normalised); seg: device
         i32[224,224] ranks; onoff: device u8[M,S].  Fills input slots [slot0, slot0+M)."""
@@ -450,13 +497,7 @@ class MaskedForwardEngine:
         if onoff.dtype != torch.uint8 or onoff.dim() != 2:
             raise ValueError("onoff must be uint8[M,S]")
         m, s = onoff.shape
-        if image.dtype == torch.uint8 and tuple(image.shape) == (IMG, IMG, 3):
-            u8, f32 = _ptr(image), None
-        elif image.dtype == torch.float32 and tuple(image.shape) == (3, IMG, IMG):
-            u8, f32 = None, _ptr(image)
-        else:
-            raise ValueError("image must be uint8[224,224,3] or float32[3,224,224], got %s%s"
-                             % (image.dtype, tuple(image.shape)))
+        u8, f32 = self._image_ptrs(image)
         if out_f32 is not None and (out_f32.dtype != torch.float32 or tuple(out_f32.shape) != (m, 3, IMG, IMG)
                                     or not out_f32.is_contiguous()):
             raise ValueError("out_f32 must be contiguous float32[M,3,224,224]")
@@ -472,12 +513,7 @@ class MaskedForwardEngine:
                 raise ValueError("%s must be a contiguous tensor on %s" % (name, self.device))
         if seg.dtype != torch.int32 or tuple(seg.shape) != (IMG, IMG):
             raise ValueError("seg must be int32[%d,%d]" % (IMG, IMG))
-        if image.dtype == torch.uint8 and tuple(image.shape) == (IMG, IMG, 3):
-            u8, f32 = _ptr(image), None
-        elif image.dtype == torch.float32 and tuple(image.shape) == (3, IMG, IMG):
-            u8, f32 = None, _ptr(image)
-        else:
-            raise ValueError("image must be uint8[224,224,3] or float32[3,224,224], got %s%s" % (image.dtype, tuple(image.shape)))
+        u8, f32 = self._image_ptrs(image)
         _lib.check(self._h, self._lib.mpx_stem_table_build(self._h, u8, f32, _ptr(seg), int(num_segments), self._mean, self._std,
                                                            self._stream()), "mpx_stem_table_build")
 
@@ -521,14 +557,15 @@ class MaskedForwardEngine:
             raise ValueError("input_planes: n must be in [1, max_batch=%d]" % self.max_batch)
         hi, lo = C.c_void_p(), C.c_void_p()
         _lib.check(self._h, self._lib.mpx_input_planes(self._h, C.byref(hi), C.byref(lo)), "mpx_input_planes")
-        shape = self.input_plane_shape(n)
+        return self._plane_views(hi.value, lo.value, self.input_plane_shape(n))
 
+    def _plane_views(self, ptr_hi, ptr_lo, shape):
+        """Zero-copy fp16 tensors of that shape over two engine-owned device planes."""
         class _View:
             def __init__(self, ptr):
                 self.__cuda_array_interface__ = {"data": (ptr, False), "shape": shape, "typestr": "<f2", "version": 2}
 
-        return (torch.as_tensor(_View(hi.value), device=self.device),
-                torch.as_tensor(_View(lo.value), device=self.device))
+        return torch.as_tensor(_View(ptr_hi), device=self.device), torch.as_tensor(_View(ptr_lo), device=self.device)
 
     def mark_input_staged(self, slot0, m):
         """mpx_mark_input_staged: slots [slot0, slot0+m) of the input planes were written by hand -- the next forward runs the stem on them."""
@@ -541,13 +578,7 @@ class MaskedForwardEngine:
             raise ValueError("stem_planes: an ImageNet ResNet engine and n in [1, max_batch=%d]" % self.max_batch)
         hi, lo = C.c_void_p(), C.c_void_p()
         _lib.check(self._h, self._lib.mpx_stem_planes(self._h, C.byref(hi), C.byref(lo)), "mpx_stem_planes")
-        shape = (n, 56, 56, 64)
-
-        class _View:
-            def __init__(self, ptr):
-                self.__cuda_array_interface__ = {"data": (ptr, False), "shape": shape, "typestr": "<f2", "version": 2}
-
-        return (torch.as_tensor(_View(hi.value), device=self.device), torch.as_tensor(_View(lo.value), device=self.device))
+        return self._plane_views(hi.value, lo.value, (n, 56, 56, 64))
 
     # ---- the batched surface ----
     def _image_to_device(self, image):
@@ -563,6 +594,14 @@ class MaskedForwardEngine:
         else:
             raise ValueError("image must be uint8 HWC or float32 CHW, got %s" % t.dtype)
         return t.contiguous().to(self.device)
+
+    @staticmethod
+    def _host_onoff(onoff, s, name="onoff"):
+        """Host on/off rows as a contiguous uint8[M, S] array; S = the number of labels of the job's label map."""
+        onoff = np.ascontiguousarray(onoff)
+        if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] != s:
+            raise ValueError("%s must be uint8[M,%d] (S = number of distinct segment labels), got %s%s" % (name, s, onoff.dtype, onoff.shape))
+        return onoff
 
     def score_masks_removed(self, image_chw, segments, removed, label, return_logits=False, return_inputs=False):
         """The small networks' scorer: (image f32[C,H,W] as the loader yields it, segments int[H,W],
@@ -623,13 +662,9 @@ class MaskedForwardEngine:
         (bayesian_active_learning_imagenet.py:187-198); pred[m] == label is the generators' binary
         label (generate_gp_training_data_imagenet.py:248,257).  stem: None = staged by this call's row count (stem_for_rows(M)); "table" /
         "conv" = the caller's choice -- a caller that scores PART of an image's rows passes stem_for_rows(all of them)."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         seg_rank, s = rank_segments(segments)
-        onoff = np.ascontiguousarray(onoff)
-        if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] != s:
-            raise ValueError("onoff must be uint8[M,%d] (S = number of distinct segment labels), got %s%s"
-                             % (s, onoff.dtype, onoff.shape))
+        onoff = self._host_onoff(onoff, s)
         if not 0 <= int(label) < NUM_CLASSES:
             raise ValueError("label %r outside [0,1000)" % (label,))
         m = onoff.shape[0]
@@ -637,30 +672,10 @@ class MaskedForwardEngine:
             # one upload, forwards of max_batch slots back to back, ONE download at the end (no per-chunk synchronisation)
             score, pred = self.score_images([image], [seg_rank], [onoff], [label], stem=stem)[0]
             return onoff, score, pred
-        score = np.empty(m, dtype=np.float32)
-        pred = np.empty(m, dtype=np.int32)
-        logits = np.empty((m, NUM_CLASSES), dtype=np.float32)
-        if m == 0:
-            return onoff, score, pred, logits
-        img_d = self._image_to_device(image)
-        seg_d = torch.from_numpy(seg_rank).to(self.device)
-        onoff_d = torch.from_numpy(onoff).to(self.device)
-        table = self._staging(stem, m) == "table"
-        for s0 in range(0, m, self.max_batch):
-            b = min(self.max_batch, m - s0)
-            labels = torch.full((b,), int(label), dtype=torch.int32, device=self.device)
-            if table:
-                if s0 == 0:
-                    self.build_stem_table(img_d, seg_d, s)
-                self.apply_stem_table(onoff_d[s0:s0 + b], 0)
-            else:
-                self.stage_masks(img_d, seg_d, onoff_d[s0:s0 + b], 0)
-            out = self.forward(b, labels, want_logits=return_logits)
-            score[s0:s0 + b] = out[0].cpu().numpy()
-            pred[s0:s0 + b] = out[1].cpu().numpy()
-            if return_logits:
-                logits[s0:s0 + b] = out[2].cpu().numpy()
-        return (onoff, score, pred, logits) if return_logits else (onoff, score, pred)
+        if m == 0:          # nothing is uploaded and `stem` is not looked at
+            return onoff, np.empty(0, dtype=np.float32), np.empty(0, dtype=np.int32), np.empty((0, NUM_CLASSES), dtype=np.float32)
+        stage = self._onoff_job(image, seg_rank, onoff, stem)[0]
+        return (onoff,) + self._score_staged(m, stage, label, True)
 
     def score_packed(self, images, segs, onoffs, label_rows, score_out, pred_out, stem=None):
         """Device-resident packed scoring: the mask rows of SEVERAL images share forward batches of up to max_batch slots
@@ -685,49 +700,29 @@ class MaskedForwardEngine:
             if t.dtype != dt or t.device != self.device or t.numel() != total or not t.is_contiguous():
                 raise ValueError("%s must be contiguous %s[%d] on %s" % (name, dt, total, self.device))
         label_rows, score_out, pred_out = label_rows.view(-1), score_out.view(-1), pred_out.view(-1)
-        done = 0            # rows already handed to a forward
-        used = 0            # slots staged for the next forward
-        used_kind = None    # how those slots were staged
         if stem is not None:
             self._staging(stem, 0)
-
-        def flush():
-            nonlocal done, used
-            self.forward(used, label_rows[done:done + used], score_out=score_out[done:done + used], pred_out=pred_out[done:done + used])
-            done += used
-            used = 0
-
+        pack = _Packer(self, label_rows, score_out, pred_out)
         for i in range(n):
-            m, r = int(onoffs[i].shape[0]), 0
+            m, image, onoff = int(onoffs[i].shape[0]), images[i], onoffs[i]
             if not m:
                 continue
             seg = segs if shared else segs[i]
             kind = self.stem_for_rows(m) if stem is None else stem
-            if used and kind != used_kind:
-                flush()                 # one forward, one kind of staging
-            used_kind = kind
+            pack.kind_changes(kind)     # one forward, one kind of staging
             if kind == "table":
-                self.build_stem_table(images[i], seg, int(onoffs[i].shape[1]))      # once per image; its rows follow in one or two forwards
-            while r < m:
-                take = min(m - r, self.max_batch - used)
-                if kind == "table":
-                    self.apply_stem_table(onoffs[i][r:r + take], used)
-                else:
-                    self.stage_masks(images[i], seg, onoffs[i][r:r + take], used)
-                used += take
-                r += take
-                if used == self.max_batch:
-                    flush()
-        if used:
-            flush()
+                self.build_stem_table(image, seg, int(onoff.shape[1]))      # once per image; its rows follow in one or two forwards
+                pack.add(m, lambda r, take, slot0: self.apply_stem_table(onoff[r:r + take], slot0))
+            else:
+                pack.add(m, lambda r, take, slot0: self.stage_masks(image, seg, onoff[r:r + take], slot0))
+        pack.finish()
 
     def score_images(self, images, segments, onoffs, labels, stem=None):
         """Host convenience over score_packed: [(image, segments, onoff u8[M_i,S_i], label)] for several images ->
         [(score f32[M_i], pred i32[M_i])], with ONE upload of the inputs and ONE download of all scores.  `segments` are
         arbitrary integer label maps (ranked here as score_masks does); `stem` as in score_packed: None stages every image by its own row
         count, so an image gets the same bits here as when it is scored alone, whatever it is packed with."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         n = len(images)
         if not (len(segments) == len(onoffs) == len(labels) == n):
             raise ValueError("images, segments, onoffs and labels must have the same length")
@@ -735,9 +730,7 @@ class MaskedForwardEngine:
         img_d, seg_d, onoff_d, lab, sizes = [], [], [], [], []
         for i in range(n):
             seg_rank, s = rank_segments(segments[i])
-            o = np.ascontiguousarray(onoffs[i])
-            if o.dtype != np.uint8 or o.ndim != 2 or o.shape[1] != s:
-                raise ValueError("onoffs[%d] must be uint8[M,%d] (S = number of distinct segment labels), got %s%s" % (i, s, o.dtype, o.shape))
+            o = self._host_onoff(onoffs[i], s, "onoffs[%d]" % i)
             if not 0 <= int(labels[i]) < NUM_CLASSES:
                 raise ValueError("label %r outside [0,1000)" % (labels[i],))
             sizes.append(o.shape[0])
@@ -808,9 +801,7 @@ class MaskedForwardEngine:
         if buf.dtype != torch.float32 or buf.device != self.device or buf.numel() != IMG * IMG + 1 or not buf.is_contiguous():
             raise ValueError("buf must be a contiguous float32[%d] tensor on %s" % (IMG * IMG + 1, self.device))
         seg_rank, s = rank_segments(seg_rank)               # a rank map passes through on the histogram's fast path
-        onoff = np.ascontiguousarray(onoff)
-        if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] != s:
-            raise ValueError("onoff must be uint8[M,%d] (S = number of distinct segment labels), got %s%s" % (s, onoff.dtype, onoff.shape))
+        onoff = self._host_onoff(onoff, s)
         if not 0 <= int(label) < NUM_CLASSES:
             raise ValueError("label %r outside [0,1000)" % (label,))
         m = int(onoff.shape[0])
@@ -843,12 +834,7 @@ class MaskedForwardEngine:
         """(u8 pointer, f32 pointer) of a device image for the soft-mask apply entries, with stage_masks' checks."""
         if image.device != self.device or not image.is_contiguous():
             raise ValueError("image must be a contiguous tensor on %s" % self.device)
-        if image.dtype == torch.uint8 and tuple(image.shape) == (IMG, IMG, 3):
-            ptrs = _ptr(image), None
-        elif image.dtype == torch.float32 and tuple(image.shape) == (3, IMG, IMG):
-            ptrs = None, _ptr(image)
-        else:
-            raise ValueError("image must be uint8[224,224,3] or float32[3,224,224], got %s%s" % (image.dtype, tuple(image.shape)))
+        ptrs = self._image_ptrs(image)
         if out_f32 is not None and (out_f32.dtype != torch.float32 or tuple(out_f32.shape) != (m, 3, IMG, IMG)
                                     or out_f32.device != self.device or not out_f32.is_contiguous()):
             raise ValueError("out_f32 must be contiguous float32[M,3,224,224] on %s" % self.device)
@@ -898,6 +884,18 @@ class MaskedForwardEngine:
         if sal.device != self.device or sal.dtype != torch.float32 or tuple(sal.shape) != (IMG, IMG) or not sal.is_contiguous():
             raise ValueError("sal must be a contiguous float32[224,224] tensor on %s" % self.device)
 
+    def _sal_out(self, out, k=None):
+        """The zeroed device map(s) a saliency driver sums into: the caller's `out` (checked, f32[224,224] or f32[k,224,224]) or new ones."""
+        shape = (IMG, IMG) if k is None else (k, IMG, IMG)
+        sal = torch.zeros(shape, dtype=torch.float32, device=self.device) if out is None else out
+        self._sal_map(sal) if k is None else self._sal_maps(sal, k)
+        return sal.zero_() if out is not None else sal
+
+    @staticmethod
+    def _sal_return(sal, out):
+        """A host array, or the caller's device tensor in its place (nothing is downloaded)."""
+        return sal.cpu().numpy() if out is None else sal
+
     def soft_saliency_accumulate(self, weights, weight, sal):
         """mpx_softmask_saliency: sal[p] <- sal[p] + weight[m] * weights[m][p] for m ascending, in place, on the device (a rounded multiply and
         a rounded add per step; one thread per pixel, so the bits do not depend on how the rows are cut into calls).  weights: device
@@ -920,8 +918,7 @@ class MaskedForwardEngine:
         """Forwards of up to max_batch slots over m rows that stage(s0, b) writes into slots [0, b), always through the input staging (the
         conv path: a real-valued mask has no stem table).  Scores and predictions stay on the device until ONE download at the end;
         after(s0, b, score_chunk), if given, runs behind each forward.  -> (score f32[m], pred i32[m][, logits f32[m,1000]]) host arrays."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         if not 0 <= int(label) < NUM_CLASSES:
             raise ValueError("label %r outside [0,1000)" % (label,))
         score = torch.empty(m, dtype=torch.float32, device=self.device)
@@ -978,10 +975,7 @@ class MaskedForwardEngine:
         if not 0.0 < float(p1) <= 1.0 or int(n_masks) <= 0:
             raise ValueError("n_masks > 0 and p1 in (0, 1], got n_masks=%r p1=%r" % (n_masks, p1))
         cells, shifts = masks.rise_masks(n_masks, s, p1, seed)
-        sal = torch.zeros(IMG, IMG, dtype=torch.float32, device=self.device) if out is None else out
-        self._sal_map(sal)
-        if out is not None:
-            sal.zero_()
+        sal = self._sal_out(out)
         img_d = self._image_to_device(image)
         cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
 
@@ -992,8 +986,7 @@ class MaskedForwardEngine:
             self.rise_saliency_accumulate(cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, score, sal)
 
         self._score_staged(int(n_masks), stage, label, False, after=after)
-        sal.div_(float(n_masks) * float(p1))
-        return sal.cpu().numpy() if out is None else sal
+        return self._sal_return(sal.div_(float(n_masks) * float(p1)), out)
 
     # ---- many classes from the same forwards (csrc/mpx_saliency_classes.h): K gathers per row of logits, the class-tiled sums ----
     def _classes_to_device(self, classes):
@@ -1066,9 +1059,9 @@ class MaskedForwardEngine:
     def _score_classes_staged(self, m, stage, cls_d, k, after=None):
         """_score_staged's loop with the logits kept: chunks of up to max_batch rows run stage(s0, b) -> forward(want_logits=True) ->
         class_scores on the stream; after(s0, b, scores_chunk), if given, runs behind each chunk.  -> (scores f32[m, k], pred i32[m]) on
-        the device."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        the device.  The two loops differ in the step behind stage(): the head's gather of one label there, class_scores of the kept logits
+        here; score_masks_removed's loop differs in kind (another apply entry, a download of out_f32 per chunk)."""
+        self._require_imagenet()
         scores = torch.empty(m, k, dtype=torch.float32, device=self.device)
         pred = torch.empty(m, dtype=torch.int32, device=self.device)
         labels = torch.zeros(min(m, self.max_batch), dtype=torch.int32, device=self.device)    # the head's own gather is not used
@@ -1124,17 +1117,11 @@ class MaskedForwardEngine:
         cls, top = masks.class_selection(classes, top, NUM_CLASSES)
         if not 0.0 < float(p1) <= 1.0 or int(n_masks) <= 0:
             raise ValueError("n_masks > 0 and p1 in (0, 1], got n_masks=%r p1=%r" % (n_masks, p1))
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
-        if top is not None:
-            logits = self.score_masks(image, np.zeros((IMG, IMG), dtype=np.int32), np.ones((1, 1), dtype=np.uint8), 0, return_logits=True)[3]
-            cls = masks.top_classes(logits[0], top)
+        self._require_imagenet()
+        cls = self._top_or_given(image, cls, top)
         cells, shifts = masks.rise_masks(n_masks, s, p1, seed)
         cls_d, k = self._classes_to_device(cls)
-        sal = torch.zeros(k, IMG, IMG, dtype=torch.float32, device=self.device) if out is None else out
-        self._sal_maps(sal, k)
-        if out is not None:
-            sal.zero_()
+        sal = self._sal_out(out, k)
         img_d = self._image_to_device(image)
         cells_d, shifts_d = torch.from_numpy(cells).to(self.device), torch.from_numpy(shifts).to(self.device)
 
@@ -1145,9 +1132,8 @@ class MaskedForwardEngine:
             self.rise_saliency_accumulate_classes(cells_d[s0:s0 + b], shifts_d[s0:s0 + b], s, scores, sal)
 
         self._score_classes_staged(int(n_masks), stage, cls_d, k, after=after)
-        sal.div_(float(n_masks) * float(p1))
         cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
-        return cls, (sal.cpu().numpy() if out is None else sal)
+        return cls, self._sal_return(sal.div_(float(n_masks) * float(p1)), out)
 
     # ---- a linear surrogate over on/off superpixel rows (csrc/mpx_surrogate.h): LIME and KernelSHAP ----
     def surrogate_accumulate(self, onoff, weight, scores, A, B):
@@ -1200,12 +1186,9 @@ class MaskedForwardEngine:
     def _onoff_job(self, image, segments, onoff, stem):
         """What score_masks checks and uploads for ONE image's on/off rows -> (stage(s0, b), seg_d, onoff_d, M, S).  The staging rule is
         score_masks': the job's whole row count decides between table and conv (_staging); on the table path the table is built once."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         seg_rank, s = rank_segments(segments)
-        onoff = np.ascontiguousarray(onoff)
-        if onoff.dtype != np.uint8 or onoff.ndim != 2 or onoff.shape[1] != s:
-            raise ValueError("onoff must be uint8[M,%d] (S = number of distinct segment labels), got %s%s" % (s, onoff.dtype, onoff.shape))
+        onoff = self._host_onoff(onoff, s)
         m = int(onoff.shape[0])
         table = self._staging(stem, m) == "table"
         img_d = self._image_to_device(image)
@@ -1268,8 +1251,7 @@ class MaskedForwardEngine:
     def _paint_values(self, seg_d, values, out):
         """values f64[K,S] rounded to fp32, uploaded and painted -> host f32[K,224,224], or the device tensor `out` overwritten."""
         v_d = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32)).to(self.device)
-        sal = self.segment_paint(seg_d, v_d, out=out)
-        return sal.cpu().numpy() if out is None else sal
+        return self._sal_return(self.segment_paint(seg_d, v_d, out=out), out)
 
     def lime(self, image, segments, classes=None, top=None, n_samples=1000, kernel_width=0.25, lam=1.0, seed=0, out=None):
         """LIME on superpixels (Ribeiro et al., KDD 2016, in the lime_image form): a weighted ridge regression of K class scores on
@@ -1281,8 +1263,7 @@ class MaskedForwardEngine:
         lime_solve(surrogate_sums(score_masks_classes(...))).  out: None -> a host map; a contiguous device f32[K,224,224] is overwritten
         with the maps and returned in their place (nothing is downloaded)."""
         cls, top = masks.class_selection(classes, top, NUM_CLASSES)
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         if int(n_samples) < 1 or not float(lam) >= 0.0 or not float(kernel_width) > 0.0:
             raise ValueError("n_samples >= 1, lam >= 0 and kernel_width > 0, got %r, %r, %r" % (n_samples, lam, kernel_width))
         s = rank_segments(segments)[1]
@@ -1300,8 +1281,7 @@ class MaskedForwardEngine:
         sal f32[K,224,224]), phi indexed and painted as lime's coef.  ValueError for n_samples odd or below S, and for S < 2.  The device
         path, classes / top and out are lime's."""
         cls, top = masks.class_selection(classes, top, NUM_CLASSES)
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         s = rank_segments(segments)[1]
         if s < 2 or int(n_samples) % 2 or int(n_samples) < s:
             raise ValueError("S >= 2 and an even n_samples >= S, got S=%d n_samples=%r" % (s, n_samples))
@@ -1367,8 +1347,7 @@ class MaskedForwardEngine:
             raise ValueError("rank must be int32[224,224], got %s%s" % (rank.dtype, rank.shape))
         if thresh.dtype != np.int32 or thresh.ndim != 1:
             raise ValueError("thresh must be int32[M], got %s%s" % (thresh.dtype, thresh.shape))
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         img_d = self._image_to_device(image)
         fill_d = None if fill is None else self._chw_to_device(fill, "fill")
         rank_d, thresh_d = torch.from_numpy(rank).to(self.device), torch.from_numpy(thresh).to(self.device)
@@ -1411,8 +1390,7 @@ class MaskedForwardEngine:
         masks.saliency_rank's.  The 2 T rows of consecutive images -- an image's deletion rows, then its insertion rows -- are packed into
         forwards of up to max_batch slots, one mpx_rank_apply per (image, curve, row range); all scores stay on the device until ONE
         download.  A row's bits depend neither on its slot nor on its neighbours: an image scores the same alone and packed."""
-        if self.small:
-            raise ValueError("%s scores with score_masks_removed (the small networks' mask convention)" % self.arch)
+        self._require_imagenet()
         n = len(images)
         if not (len(saliencies) == len(labels) == n):
             raise ValueError("images, saliencies and labels must have the same length")
@@ -1436,14 +1414,7 @@ class MaskedForwardEngine:
         label_rows = torch.from_numpy(np.repeat(np.asarray([int(v) for v in labels], dtype=np.int32), 2 * t_rows)).to(self.device)
         score = torch.empty(total, dtype=torch.float32, device=self.device)
         pred = torch.empty(total, dtype=torch.int32, device=self.device)
-        done = used = 0         # rows already handed to a forward; slots staged for the next one
-
-        def flush():
-            nonlocal done, used
-            self.forward(used, label_rows[done:done + used], score_out=score[done:done + used], pred_out=pred[done:done + used])
-            done += used
-            used = 0
-
+        pack = _Packer(self, label_rows, score, pred)
         for i in range(n):
             img_d = self._image_to_device(images[i])
             sal = saliencies[i]
@@ -1453,16 +1424,8 @@ class MaskedForwardEngine:
                 rank_d = torch.from_numpy(masks.saliency_rank(np.asarray(sal))).to(self.device)
             for keep_top, fill in ((False, self._curve_fill(fills[0][i], img_d, taps, "del_fill")),
                                    (True, self._curve_fill(fills[1][i], img_d, taps, "ins_fill"))):
-                r = 0
-                while r < t_rows:
-                    take = min(t_rows - r, self.max_batch - used)
-                    self.stage_rank_masks(img_d, rank_d, thresh_d[r:r + take], fill, keep_top, used)
-                    used += take
-                    r += take
-                    if used == self.max_batch:
-                        flush()
-        if used:
-            flush()
+                pack.add(t_rows, lambda r, take, slot0: self.stage_rank_masks(img_d, rank_d, thresh_d[r:r + take], fill, keep_top, slot0))
+        pack.finish()
         score, pred = score.cpu().numpy().reshape(n, 2, t_rows), pred.cpu().numpy().reshape(n, 2, t_rows)
         return [{"thresholds": thresh.copy(),
                  "del_scores": score[i, 0].copy(), "ins_scores": score[i, 1].copy(),

@@ -1,11 +1,14 @@
 """Constants and small helpers of the GPU tests (test infrastructure only): pointers and split-fp16 planes, the project's tolerances, the
-product's tile ids, the per-layer bound, the fenced output buffer and the `dev` fixture.  A test file imports what it uses by name, the
+product's tile ids, the per-layer bound, the fenced output buffer, the sentinel-filled input staging with its bit-for-bit check and the `dev` fixture.  A test file imports what it uses by name, the
 fixture included (`from gpu_common import dev  # noqa: F401`)."""
 import ctypes as C
 import math
 
+import numpy as np
 import pytest
 import torch
+
+import rise_ref
 
 SCORE_TOL = 1e-4            # the project's tolerance on a score: the ceiling of the end-to-end bound
 SCORE_BOUND = 2e-5          # ... and its end-to-end bound
@@ -120,6 +123,58 @@ class FencedPair:
             assert plane.problems() == [], "%s plane: %s" % (which, "; ".join(plane.problems()))
             assert not torch.isnan(plane.payload).any(), which
         return self.hi.payload.reshape(-1).clone(), self.lo.payload.reshape(-1).clone()
+
+
+PLANE_IMG = 224
+PLANE_SENTINEL = 0x5A3C     # fp16 bits of 199.5: neither 0 nor anything a normalised pixel times a weight splits into at every element
+
+
+class Planes:
+    """The engine's input staging filled with a sentinel for the length of a `with` block, and put back afterwards (the 3-pixel border is
+    zero for the life of an engine and the stem conv reads it)."""
+
+    def __init__(self, e):
+        self.e = e
+        self.hi, self.lo = (t.view(torch.int16) for t in e.input_planes())
+
+    def __enter__(self):
+        self.saved = self.hi.clone(), self.lo.clone()
+        self.hi.fill_(PLANE_SENTINEL)
+        self.lo.fill_(PLANE_SENTINEL)
+        return self
+
+    def __exit__(self, *exc):
+        self.hi.copy_(self.saved[0])
+        self.lo.copy_(self.saved[1])
+        torch.cuda.synchronize()
+
+    def read(self):
+        torch.cuda.synchronize()
+        return self.hi.cpu().numpy(), self.lo.cpu().numpy()
+
+    def intact(self):
+        hi, lo = self.read()
+        return bool((hi == PLANE_SENTINEL).all() and (lo == PLANE_SENTINEL).all())
+
+
+def check_planes(planes, x, w, slot0, out=None):
+    """Slots [slot0, slot0 + M) hold split(fl(x * w[m])) bit for bit in channels 0..2 and +0.0 in channel 3; their 3-pixel border and every
+    other slot still hold the sentinel; out (f32[M,3,224,224]) holds fl(x * w[m]) bit for bit."""
+    hi, lo = planes.read()
+    m = len(w)
+    want = x.numpy()[None] * w[:, None]                             # [M,3,224,224] fp32: one rounded multiply
+    assert want.dtype == np.float32
+    whi, wlo = rise_ref.split16(want.transpose(0, 2, 3, 1))         # NHWC
+    for name, got, exp in (("hi", hi, whi), ("lo", lo, wlo)):
+        inner = got[slot0:slot0 + m, 3:3 + PLANE_IMG, 3:3 + PLANE_IMG]
+        assert (inner[..., :3] == exp).all(), "%s plane differs from split(v * w) at %d elements" % (name, int((inner[..., :3] != exp).sum()))
+        assert (inner[..., 3] == 0).all(), "%s: channel 3 is not +0.0" % name
+        border = got[slot0:slot0 + m].copy()
+        border[:, 3:3 + PLANE_IMG, 3:3 + PLANE_IMG] = PLANE_SENTINEL
+        assert (border == PLANE_SENTINEL).all(), "%s: the 3-pixel border was written" % name
+        assert (got[:slot0] == PLANE_SENTINEL).all() and (got[slot0 + m:] == PLANE_SENTINEL).all(), "%s: a slot outside [slot0, slot0 + M) was written" % name
+    if out is not None:
+        assert (out.cpu().numpy().view(np.int32) == want.view(np.int32)).all(), "out_f32_nchw differs from v * w"
 
 
 @pytest.fixture(scope="module")

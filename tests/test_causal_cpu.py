@@ -24,7 +24,8 @@ def test_entries_exported_and_bound(mpx_lib):
         assert re.search(r"^int %s\(mpx_engine\* h," % name, header, re.M), name
     assert len(_lib.SIGNATURES["mpx_rank_apply"][1]) == 13 and len(_lib.SIGNATURES["mpx_blur_fill"][1]) == 9
     kernel = open(os.path.join(ROOT, "network_interpretation_imagenet_amd", "csrc", "mpx_rankmask.h")).read()
-    assert int(re.search(r"constexpr int RM_MT = (\d+);", kernel).group(1)) == _lib.RANKMASK_TILE
+    stage = open(os.path.join(ROOT, "network_interpretation_imagenet_amd", "csrc", "mpx_stage.h")).read()
+    assert "STAGE_MT" in kernel and int(re.search(r"constexpr int STAGE_MT = (\d+);", stage).group(1)) == _lib.RANKMASK_TILE == _lib.SOFTMASK_TILE
     assert int(re.search(r"constexpr int BF_KMAX = (\d+);", kernel).group(1)) == _lib.BLUR_KLEN_MAX == masks.BLUR_KLEN_MAX
 
 

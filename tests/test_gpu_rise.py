@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_common import dev, ptr as _p  # noqa: F401  (dev is a fixture)
+from gpu_common import PLANE_SENTINEL as SENTINEL, Planes, check_planes, dev, ptr as _p  # noqa: F401  (dev is a fixture)
 from network_interpretation_imagenet_amd import _lib, masks, synth
 from network_interpretation_imagenet_amd.engine import MaskedForwardEngine, MpxError, rank_segments
 from oracle import scorer
@@ -16,7 +16,6 @@ import rise_ref
 pytestmark = pytest.mark.gpu
 
 IMG, PAD = 224, 230
-SENTINEL = 0x5A3C           # fp16 bits of 199.5: neither 0 nor anything a normalised pixel times a weight splits into at every element
 SCORE_TOL = 1e-4            # the project's tolerance of a score against the CPU forward
 
 
@@ -45,54 +44,6 @@ def picture():
     """(u8 HWC image, its normalised f32 CHW tensor): noise, so that negative normalised pixels are everywhere."""
     img = synth.make_images(2, kind="noise")[1]
     return img, scorer.to_tensor_normalize(img)
-
-
-class Planes:
-    """The engine's input staging filled with a sentinel for the length of a `with` block, and put back afterwards (the 3-pixel border is
-    zero for the life of an engine and the stem conv reads it)."""
-
-    def __init__(self, e):
-        self.e = e
-        self.hi, self.lo = (t.view(torch.int16) for t in e.input_planes())
-
-    def __enter__(self):
-        self.saved = self.hi.clone(), self.lo.clone()
-        self.hi.fill_(SENTINEL)
-        self.lo.fill_(SENTINEL)
-        return self
-
-    def __exit__(self, *exc):
-        self.hi.copy_(self.saved[0])
-        self.lo.copy_(self.saved[1])
-        torch.cuda.synchronize()
-
-    def read(self):
-        torch.cuda.synchronize()
-        return self.hi.cpu().numpy(), self.lo.cpu().numpy()
-
-    def intact(self):
-        hi, lo = self.read()
-        return bool((hi == SENTINEL).all() and (lo == SENTINEL).all())
-
-
-def check_planes(planes, x, w, slot0, out=None):
-    """Slots [slot0, slot0 + M) hold split(fl(x * w[m])) bit for bit in channels 0..2 and +0.0 in channel 3; their 3-pixel border and every
-    other slot still hold the sentinel; out (f32[M,3,224,224]) holds fl(x * w[m]) bit for bit."""
-    hi, lo = planes.read()
-    m = len(w)
-    want = x.numpy()[None] * w[:, None]                             # [M,3,224,224] fp32: one rounded multiply
-    assert want.dtype == np.float32
-    whi, wlo = rise_ref.split16(want.transpose(0, 2, 3, 1))         # NHWC
-    for name, got, exp in (("hi", hi, whi), ("lo", lo, wlo)):
-        inner = got[slot0:slot0 + m, 3:3 + IMG, 3:3 + IMG]
-        assert (inner[..., :3] == exp).all(), "%s plane differs from split(v * w) at %d elements" % (name, int((inner[..., :3] != exp).sum()))
-        assert (inner[..., 3] == 0).all(), "%s: channel 3 is not +0.0" % name
-        border = got[slot0:slot0 + m].copy()
-        border[:, 3:3 + IMG, 3:3 + IMG] = SENTINEL
-        assert (border == SENTINEL).all(), "%s: the 3-pixel border was written" % name
-        assert (got[:slot0] == SENTINEL).all() and (got[slot0 + m:] == SENTINEL).all(), "%s: a slot outside [slot0, slot0 + M) was written" % name
-    if out is not None:
-        assert (out.cpu().numpy().view(np.int32) == want.view(np.int32)).all(), "out_f32_nchw differs from v * w"
 
 
 def _image(picture, kind, dev):
@@ -182,6 +133,38 @@ def test_binary_weights_give_k0_planes(binary_staged):
     at = neg_zero.transpose(0, 2, 3, 1)
     inner_hi, inner_lo = hi[1:7, 3:227, 3:227, :3], lo[1:7, 3:227, 3:227, :3]
     assert (inner_hi[at] == np.int16(-2 ** 15)).all() and (inner_lo[at] == 0).all()          # hi -0.0, lo +0.0 in every channel
+
+
+def _label_map(which):
+    """(label map i32[224,224], S): the 14 x 14 grid (S = 196), or five bands (S = 5: a tile of 33 rows is 165 on/off bytes, no multiple of
+    4) in which two blocks of pixels carry the labels -1 and 5 -- outside [0, S), where the weight is 0 whatever the rows say."""
+    if which == "grid":
+        return synth.grid_segments().astype(np.int32), 196
+    seg = np.ascontiguousarray(np.broadcast_to((np.arange(IMG, dtype=np.int32) * 5 // IMG)[:, None], (IMG, IMG)))
+    seg[10:30, 40:90] = -1
+    seg[100:141, 7:19] = 5
+    return seg, 5
+
+
+@pytest.mark.parametrize("kind", ["u8", "f32"])
+@pytest.mark.parametrize("which", ["grid", "five"])
+@pytest.mark.parametrize("m,slot0", [(1, 3), (_lib.SOFTMASK_TILE + 1, 5)])
+def test_k0_planes_bit_exact(eng, eng40, dev, picture, m, slot0, which, kind):
+    """mpx_mask_apply_normalize held to check_planes with w = onoff[:, seg] from numpy: interior bits (hi -0.0 / lo +0.0 where a negative
+    pixel is removed), channel 3, the untouched border and other slots, and out_f32 bit for bit -- one row, and one row more than a block's
+    tile, behind slot0 > 0."""
+    e = eng if m == 1 else eng40
+    seg, s = _label_map(which)
+    onoff = synth.random_onoff(m, s, seed=50 + m)
+    inside = (seg >= 0) & (seg < s)
+    w = np.ascontiguousarray(np.where(inside[None], onoff[:, np.where(inside, seg, 0)], 0), dtype=np.float32)
+    assert w.shape == (m, IMG, IMG) and ((picture[1].numpy() < 0) & (w[0][None] == 0)).any()
+    if which == "five":
+        assert (seg == -1).any() and (seg == s).any()           # without the guard label 5 reads the next row's first byte, label -1 the row before
+    out = torch.full((m, 3, IMG, IMG), float("nan"), dtype=torch.float32, device=dev)
+    with Planes(e) as planes:
+        e.stage_masks(_image(picture, kind, dev), torch.from_numpy(seg).to(dev), torch.from_numpy(onoff).to(dev), slot0, out)
+        check_planes(planes, picture[1], w, slot0, out)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -703,6 +703,7 @@ class _StagingProbe(MaskedForwardEngine):
         self.max_batch, self.device = max_batch, torch.device("cpu")
         self.slots = [None] * max_batch
         self.forwards = []          # [(batch, set of kinds)]
+        self.rows = []              # per forward: [(image id, row)] slot by slot
         self.builds = []
         self._cur = None
 
@@ -721,9 +722,15 @@ class _StagingProbe(MaskedForwardEngine):
         for j in range(onoff.shape[0]):
             self.slots[slot0 + j] = (int(image[0, 0, 0]), int(onoff[j, 0]) + 256 * int(onoff[j, 1]), "conv")
 
+    def stage_rank_masks(self, image, rank, thresh, fill=None, keep_top=False, slot0=0, out_f32=None):
+        """Row j of a curve remembers (image id, 500 * insertion + the index of its threshold in self.thresholds, "conv")."""
+        for j in range(thresh.shape[0]):
+            self.slots[slot0 + j] = (int(image[0, 0, 0]), 500 * bool(keep_top) + self.thresholds.index(int(thresh[j])), "conv")
+
     def forward(self, batch, labels, want_logits=False, score_out=None, pred_out=None):
         kinds = {self.slots[j][2] for j in range(batch)}
         self.forwards.append((batch, kinds))
+        self.rows.append([self.slots[j][:2] for j in range(batch)])
         for j in range(batch):
             img, row, kind = self.slots[j]
             score_out[j] = img * 1000 + row
@@ -786,6 +793,29 @@ def test_staging_is_decided_per_image_however_rows_are_packed():
     assert [(b, sorted(k)) for b, k in eng3.forwards] == [(512, ["conv"]), (148, ["conv"])] and eng3.builds == []
     with pytest.raises(ValueError):
         eng3.score_packed([t(a) for a in im], t(sg[0]), [t(o) for o in oo], rows, score, pred, stem="tabel")
+
+
+@pytest.mark.parametrize("n,step,max_batch", [(1, 12544, 8), (3, 12544, 8), (2, 5000, 7), (2, 12544, 40)])
+def test_curves_pack_rows_of_consecutive_images_into_full_forwards(n, step, max_batch):
+    """deletion_insertion_many's packing, over recorded kernel calls: the 2 T rows of image i -- its deletion rows, then its insertion rows --
+    follow image i - 1's without a gap, so row g of the call sits in slot g % max_batch of forward g // max_batch; no forward exceeds
+    max_batch, there are ceil(2 T n / max_batch) of them, and every score comes back in its image's curve.  Both fills None: no library call."""
+    eng = _StagingProbe(max_batch=max_batch)
+    eng.thresholds = masks.curve_thresholds(step).tolist()
+    t_rows = len(eng.thresholds)
+    assert t_rows == -(-224 * 224 // step) + 1 and t_rows < 500
+    images = _probe_job([1] * n)[0]
+    sal = [np.random.default_rng(i).random((224, 224), dtype=np.float32) for i in range(n)]
+    out = eng.deletion_insertion_many(images, sal, [i + 5 for i in range(n)], step=step, del_fill=None, ins_fill=None)
+    flat = [(i, 500 * curve + r) for i in range(n) for curve in (0, 1) for r in range(t_rows)]
+    want = [flat[at:at + max_batch] for at in range(0, len(flat), max_batch)]
+    assert eng.rows == want
+    assert len(eng.rows) == -(-2 * t_rows * n // max_batch) and all(b <= max_batch for b, _k in eng.forwards)
+    for i, res in enumerate(out):
+        assert res["thresholds"].tolist() == eng.thresholds
+        assert np.array_equal(res["del_scores"], i * 1000 + np.arange(t_rows, dtype=np.float32))
+        assert np.array_equal(res["ins_scores"], i * 1000 + 500 + np.arange(t_rows, dtype=np.float32))
+        assert (res["del_pred"] == 1).all() and (res["ins_pred"] == 1).all()
 
 
 def test_session_fixes_one_staging_for_everything_it_scores():

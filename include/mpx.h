@@ -600,6 +600,33 @@ int mpx_softmask_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* im
 int mpx_rise_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const uint8_t* cells, const int32_t* shift,
                    int M, int s, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream);
 
+/* ---- the rows of a Sobol total-order design over a grid of cells, synthesised in the apply kernel ---------------------------------
+ * extends: mpx_softmask_apply / mpx_rise_apply (a weight per pixel, the removed pixel always zero) to the perturbations of Fel, Cadene,
+ *          Chalvidal, Cord, Vigouroux, Serre, "Look at the Variance! Efficient Black-box Explanations with Sobol-based Sensitivity
+ *          Analysis" (NeurIPS 2021): the image is cut into d x d piecewise constant cells, every cell gets a weight in [0, 1] from a
+ *          quasi-Monte-Carlo design, and a cell's total-order index is estimated from N * (d * d + 1) scores (Jansen's estimator).  There
+ *          is no reference line.  The design is two matrices, and every row's 224 x 224 weights are gathered from them in the kernel
+ *          (csrc/mpx_softmask.h, DesignWeights) instead of being uploaded.
+ * A, B: DEV f32[N][D], D = d * d, 2 <= d <= 32 (MPX_SOBOL_GRID_MIN / _MAX), N >= 2.  The design has R = N * (D + 1) rows; row r is
+ *     r <  N:  the cells are A[r]
+ *     r >= N:  q = r - N, j = q / D, i = q - j * D: the cells are A[j] with cell i taken from B[j]        (j-major; B is no row of its own)
+ * and the weight of pixel (y, x) under row r is the value of its cell c = ((y * d) / 224) * d + (x * d) / 224 (integer divisions): a pure
+ * gather, no arithmetic.  The call stages rows [row0, row0 + M) into slots [slot0, slot0 + M).
+ * img_u8_hwc / img_f32_chw, mean, std, slot0, out_f32_nchw: as mpx_softmask_apply.  fill_f32_chw: NULL, or DEV f32[3][224][224] in
+ * normalised space (what mpx_blur_fill writes).  Per channel, with v the normalised pixel, w the weight and F the fill pixel:
+ *     without a fill:  o = fl(v * w)                                    mpx_softmask_apply's planes for the same weights, bit for bit
+ *     with a fill:     o = fl(fl(v * w) + fl(F * fl(1 - w)))            four fp32 operations, each rounded on its own, no FMA
+ * then the hi / lo split, channel 3 = +0.0, the 3-pixel border untouched, out_f32_nchw[m][c][p] = o when given.
+ * Values of A / B outside [0, 1] are outside the contract; nothing is clamped (the Python layer refuses them before upload).
+ * Marks slots [slot0, slot0 + M) input-staged.  MPX_E_STATE on the small networks.  MPX_E_ARG, with nothing written, for d outside
+ * [2, 32], N < 2, N * (D + 1) not representable in int, M < 0, row0 < 0, row0 + M > N * (D + 1), slot0 + M > max_batch, a NULL A or B,
+ * both or neither image pointer.  M == 0 succeeds and writes nothing.  No allocation, no host synchronisation. */
+#define MPX_SOBOL_GRID_MIN 2
+#define MPX_SOBOL_GRID_MAX 32
+int mpx_sobol_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* A, const float* B, int N, int d,
+                    int row0, int M, const float* fill_f32_chw, const float mean[3], const float std[3], int slot0, float* out_f32_nchw,
+                    void* stream);
+
 /* ---- the score-weighted sum of real-valued masks (RISE's saliency map, before its normalisation) -------------------------------
  * extends: mpx_heatmap_accumulate (counts of binary masks) to  sal[p] <- sal[p] + weight[m] * w_m(p)  for m = 0 .. M - 1 in this order,
  *          accumulated in place in fp32 from the value already in sal (RISE's Monte Carlo estimate: the masks weighted by the class score).

@@ -194,12 +194,15 @@ SIGNATURES = {
     # a linear surrogate over on/off rows (csrc/mpx_surrogate.h): the fp64 moment sums of LIME / KernelSHAP, the paint per superpixel
     "mpx_surrogate_accumulate": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mpx_segment_paint": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    # the rows of a Sobol total-order design over a d x d grid, gathered from the two design matrices in the apply kernel; the fill blend
+    "mpx_sobol_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _fp, _fp, _i, _vp, _vp]),
 }
 
 SOFTMASK_TILE = 32      # csrc/mpx_stage.h STAGE_MT: the rows one block of every apply kernel loops over ...
 RANKMASK_TILE = SOFTMASK_TILE   # ... under the name the rank-mask tests know it by
 SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
 SURROGATE_S_MAX = 1024     # csrc/mpx_surrogate.h SUR_S_MAX: the most superpixels mpx_surrogate_accumulate / mpx_segment_paint take
+SOBOL_GRID_MIN, SOBOL_GRID_MAX = 2, 32  # include/mpx.h MPX_SOBOL_GRID_MIN / _MAX (csrc/mpx_softmask.h SOBOL_GRID_*): the grids mpx_sobol_apply takes
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes
 
 _lib = None

@@ -576,6 +576,20 @@ def kernel_shap_saliency(model, image_u8, label=None, classes=None, top=None, se
     return model.kernel_shap(image_u8, segments, classes=classes, top=top, n_samples=n_samples, seed=seed, out=out)
 
 
+def sobol_saliency(model, image_u8, label=None, classes=None, top=None, grid=8, n_design=32, seed=0, fill=None, out=None):
+    """Sobol total-order indices over a grid x grid grid of cells (Fel et al., NeurIPS 2021): -> (classes i32[K], st f64[K,grid,grid],
+    sal f32[K,224,224]) -- the share of each class score's variance that involves a cell, interactions between cells included, from
+    n_design * (grid^2 + 1) forwards whose real-valued masks are gathered from the quasi-Monte-Carlo design in the apply kernel
+    (engine.MaskedForwardEngine.sobol_attribution).  label / classes / top as lime_saliency.  fill: None pulls a cell towards zero, "blur"
+    towards the blurred image, an f32[3,224,224] towards that image.  sal[k] paints st[k] onto the pixels and feeds deletion_insertion as a
+    RISE map does (out= keeps it on the device)."""
+    if label is not None:
+        if classes is not None or top is not None:
+            raise ValueError("give label, classes or top, not several")
+        classes = [_as_int(label)]
+    return model.sobol_attribution(image_u8, classes=classes, top=top, grid=grid, n_design=n_design, seed=seed, fill=fill, out=out)
+
+
 def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
     """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
     salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on

@@ -25,6 +25,7 @@
 #include "mpx_surrogate.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <initializer_list>
@@ -2028,6 +2029,33 @@ int mpx_softmask_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* im
 int mpx_rise_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const uint8_t* cells, const int32_t* shift, int M, int s,
                    const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
     return soft_apply<RiseWeights>(h, "rise_apply", img_u8_hwc, img_f32_chw, cells, shift, M, s, mean, std, slot0, out_f32_nchw, stream);
+}
+
+static_assert(SOBOL_GRID_MAX * SOBOL_GRID_MAX <= SUR_S_MAX, "mpx_segment_paint paints the d * d cells of the largest grid");
+// the rows [row0, row0 + M) of a Sobol total-order design, their weights gathered from A and B in the kernel (DesignWeights); with a fill
+// image the blend variant of the apply kernel
+int mpx_sobol_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* A, const float* B, int N, int d, int row0,
+                    int M, const float* fill_f32_chw, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "sobol_apply: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's");
+    if (d < SOBOL_GRID_MIN || d > SOBOL_GRID_MAX) return fail(h, MPX_E_ARG, "sobol_apply: d=%d outside [%d, %d]", d, SOBOL_GRID_MIN, SOBOL_GRID_MAX);
+    const long long rows = (long long)N * (d * d + 1);
+    if (N < 2 || rows > INT_MAX) return fail(h, MPX_E_ARG, "sobol_apply: N=%d designs of %d cells: N >= 2 and N * (d * d + 1) rows within int", N, d * d);
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, "sobol_apply", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
+    if (!A || !B) return fail(h, MPX_E_ARG, "sobol_apply: null design pointer");
+    if (M < 0 || row0 < 0 || (long long)row0 + M > rows)
+        return fail(h, MPX_E_ARG, "sobol_apply: rows [%d,%lld) outside the design's [0, %lld)", row0, (long long)row0 + M, rows);
+    if (slot0 < 0 || (long long)slot0 + M > h->max_batch)
+        return fail(h, MPX_E_ARG, "sobol_apply: slots [%d,%lld) outside [0, max_batch=%d)", slot0, (long long)slot0 + M, h->max_batch);
+    if (M == 0) return 0;
+    p.A = A; p.B = B; p.fill = fill_f32_chw;
+    p.N = N; p.d = d; p.row0 = row0;
+    p.out_f32 = out_f32_nchw;
+    p.M = M; p.slot0 = slot0;
+    if (fill_f32_chw) return launch_stage(h, softmask_apply_kernel<DesignWeights, true>, M, DesignWeights::lds_bytes(d), stream, p);
+    return launch_stage(h, softmask_apply_kernel<DesignWeights>, M, DesignWeights::lds_bytes(d), stream, p);
 }
 
 int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weight, int M, float* sal, void* stream) {

@@ -7,7 +7,18 @@
 //   RiseWeights      w_m(p) synthesised from the s x s bits and the shift of mask m: the masks of RISE (Petsiuk, Das, Saenko, "RISE:
 //                    Randomized Input Sampling for Explanation of Black-box Models", BMVC 2018) -- a random s x s grid, upsampled
 //                    bilinearly to U x U with half-pixel centres, cropped to 224 x 224 at a random shift (dy, dx).
-// A source is: kLds, lds_bytes(n), stage() (the tile's rows into LDS), Pixel + pixel() (what it keeps per pixel across the rows of a tile;
+//   DesignWeights    w_r(p) gathered from the two design matrices A, B (DEV f32[N][D], D = d * d) of a Sobol total-order design over a d x d
+//                    grid of piecewise constant cells (Fel, Cadene, Chalvidal, Cord, Vigouroux, Serre, "Look at the Variance! Efficient
+//                    Black-box Explanations with Sobol-based Sensitivity Analysis", NeurIPS 2021), at the global row r = row0 + m:
+//                      c(p) = ((y * d) / 224) * d + (x * d) / 224                      integer divisions; once per pixel (Pixel)
+//                      r <  N:  w = A[r][c]
+//                      r >= N:  q = r - N, j = q / D, i = q - j * D;  w = (i == c) ? B[j][c] : A[j][c]
+//                    a pure gather, no arithmetic on w.  The tile's 32 (row base, i) pairs are worked out once per block in stage() -- one
+//                    integer division per tile row, none per (pixel, row) -- and kept in 256 B of LDS; A and B are read from global memory
+//                    (2 N D floats: the L1 / L2 hold them) when the row base changes and kept in the pixel's state: the D consecutive rows
+//                    of one j differ in the one replaced cell only, so a row is an LDS read and a select.
+// A source is: kLds, kPinPixel (the apply kernel pins the loaded pixel in registers in front of its row loop), lds_bytes(n), stage() (the
+// tile's rows into LDS), Pixel + pixel() (what it keeps per pixel across the rows of a tile;
 // empty for the explicit and the RISE source) and weight().
 //
 // The RISE weight, stated exactly (cell = ceil(224 / s), U = (s + 1) * cell, 2 <= s <= 32, 0 <= dy, dx < cell; g = the grid as 0.0f / 1.0f):
@@ -27,7 +38,8 @@
 // lies in [0, 1].
 //
 // Apply:    o = fl(v * w) per channel (ONE fp32 multiply, no FMA with the split behind it), then split_f32: hi = f16(o), lo = f16(fl(o -
-//           f32(hi))).  For w in {0, 1} that is `x * mask` as numpy does it, the -0.0 of a removed negative pixel included (hi -0.0, lo
+//           f32(hi))).  With a fill image F (kFill, the design source only): o = fl(fl(v * w) + fl(F * fl(1 - w))), four fp32 operations each
+//           rounded on its own, so that a cell is pulled towards F and not towards zero; w = 1 gives v + F * 0, w = 0 gives v * 0 + F.  For w in {0, 1} that is `x * mask` as numpy does it, the -0.0 of a removed negative pixel included (hi -0.0, lo
 //           +0.0), whichever source the weight comes from.  The product is pinned in an fp32 register (fp32_value, mpx_conv.h) before the
 //           split: hipcc otherwise folds f16(a * b) into v_fma_mixlo_f16, which rounds the exact product to fp16 once and turns a -0.0
 //           product into +0.0.
@@ -42,15 +54,29 @@ namespace mpx {
 constexpr int SM_S_MIN = 2;
 constexpr int SM_S_MAX = 32;
 constexpr int SM_SAL_THREADS = 64;  // saliency: one wave per block, 784 blocks over the 256 CUs
+constexpr int SOBOL_GRID_MIN = 2;
+constexpr int SOBOL_GRID_MAX = 32;  // D = 1024 cells: mpx_segment_paint's limit (SUR_S_MAX), which paints the indices
 
+// A launch has ONE weight source, so the design source's fields lie over the other sources' five pointers: the struct keeps its 168 bytes
+// and every field its offset, and with them every kernel that takes (SoftParams, ...) its kernel-argument loads.
 struct SoftParams {
     const uint8_t* img_u8;   // [H][W][3] or null                          (apply)
     const float* img_f32;    // [3][H][W] or null                          (apply)
-    const int32_t* seg;      // [H][W]                                     (on/off source)
-    const uint8_t* onoff;    // [M][S], non-zero = keep                    (on/off source)
-    const float* weights;    // [M][H][W]                                  (explicit source)
-    const uint8_t* cells;    // [M][s][s], non-zero = keep                 (RISE source)
-    const int32_t* shift;    // [M][2] = (dy, dx)                          (RISE source)
+    union {
+        struct {
+            const int32_t* seg;      // [H][W]                             (on/off source)
+            const uint8_t* onoff;    // [M][S], non-zero = keep            (on/off source)
+            const float* weights;    // [M][H][W]                          (explicit source)
+            const uint8_t* cells;    // [M][s][s], non-zero = keep         (RISE source)
+            const int32_t* shift;    // [M][2] = (dy, dx)                  (RISE source)
+        };
+        struct {
+            const float* A;          // [N][d * d]                         (design source)
+            const float* B;          // [N][d * d]
+            const float* fill;       // [3][H][W] or null                  (design source, kFill)
+            int N, d, row0;          // designs, grid size, the design row of mask 0
+        };
+    };
     const float* score;      // [M]: the weight of mask m in the sum       (saliency)
     float* sal;              // [H][W], accumulated in place               (saliency)
     half_t* out_hi;          // engine staging, slot 0 (padded NHWC4)      (apply)
@@ -62,6 +88,8 @@ struct SoftParams {
     float f_U2, inv_U2;      // float(2U) (exact) and 1 / float(2U) (a first guess of the quotient only)
     int size, pad_size, border;   // 224, 230, 3
 };
+
+static_assert(sizeof(SoftParams) == 168, "the design source's fields fit over the other sources' pointers");
 
 // One axis of the RISE upsampling at the shifted coordinate Y: i0, i1 and the fraction, from integers.  The quotient t / 2U is guessed in
 // fp32 (t < 2U * s < 2^24 is exact as a float, the guess is off by at most one) and fixed up against the integer remainder, so i0 and r ARE
@@ -82,6 +110,7 @@ struct NoPixelState {};
 
 struct OnoffWeights {
     static constexpr bool kLds = true;
+    static constexpr bool kPinPixel = false;
     struct Pixel { int s; bool ok; };
     static size_t lds_bytes(int S) { return ((size_t)STAGE_MT * S + 15) & ~(size_t)15; }      // u8[STAGE_MT][S]
     __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int nthreads) {
@@ -100,6 +129,7 @@ struct OnoffWeights {
 
 struct ExplicitWeights {
     static constexpr bool kLds = false;
+    static constexpr bool kPinPixel = false;
     typedef NoPixelState Pixel;
     static size_t lds_bytes(int) { return 0; }
     __device__ static __forceinline__ void stage(const SoftParams&, char*, int, int, int, int) {}
@@ -111,6 +141,7 @@ struct ExplicitWeights {
 
 struct RiseWeights {
     static constexpr bool kLds = true;
+    static constexpr bool kPinPixel = false;
     typedef NoPixelState Pixel;
     // LDS: i32[STAGE_MT][2] shifts, then u8[STAGE_MT][s * s] cells
     static size_t lds_bytes(int s) { return (size_t)STAGE_MT * 8 + (((size_t)STAGE_MT * s * s + 15) & ~(size_t)15); }
@@ -141,10 +172,50 @@ struct RiseWeights {
     }
 };
 
+struct DesignWeights {
+    static constexpr bool kLds = true;
+    // Most rows of a tile take their weight from registers: with the pixel (and the fill) pinned in front of the row loop, such a row waits
+    // for no load, and so not for the stores of the rows before it either (one counter covers both).
+    static constexpr bool kPinPixel = true;
+    struct Pixel { int c, base; float a, b; };      // the pixel's cell, and A[j][c] / B[j][c] of the j (row base) they were last read for
+    static size_t lds_bytes(int) { return (size_t)STAGE_MT * 8; }                             // i32[STAGE_MT][2] = (row base, i or -1)
+    __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int) {
+        if (tid < mt) {
+            const int D = p.d * p.d;
+            const int r = p.row0 + m_base + tid;
+            int jr = r, i = -1;                 // r < N: row r of A, no cell replaced
+            if (r >= p.N) {
+                const int q = r - p.N;
+                jr = q / D;
+                i = q - jr * D;
+            }
+            ((int*)smem)[tid * 2] = jr * D;     // < N * D, which the entry holds below 2^31
+            ((int*)smem)[tid * 2 + 1] = i;
+        }
+    }
+    __device__ static __forceinline__ Pixel pixel(const SoftParams& p, int pix) {
+        const int y = pix / p.size, x = pix - y * p.size;
+        return {((y * p.d) / p.size) * p.d + (x * p.d) / p.size, -1, 0.f, 0.f};
+    }
+    // The D rows of one j read the same two floats: they are loaded when the row base changes (every row below N, every D-th row above)
+    // and kept in the pixel's state, so that a row costs one LDS read and a select.
+    __device__ static __forceinline__ float weight(const SoftParams& p, const char* smem, Pixel& px, int, int mi, int, int, int, int) {
+        const int base = ((const int*)smem)[mi * 2], i = ((const int*)smem)[mi * 2 + 1];
+        if (base != px.base) {
+            px.base = base;
+            const float a = p.A[(size_t)base + px.c], b = p.B[(size_t)base + px.c];
+            px.a = fp32_value(a);       // used HERE: the wait for the two loads stays inside this branch, and the rows that take the values
+            px.b = fp32_value(b);       // from the registers do not wait for the stores of the row before them
+        }
+        return i == px.c ? px.b : px.a;
+    }
+};
+
 // Apply.  One thread = one pixel; a block loops over a tile of STAGE_MT masks (a source with kLds stages what it needs of them in LDS
 // first), so the image -- and the on/off source's label map -- is read once per STAGE_MT masks and every store is a coalesced 512-B
 // (planes) / 256-B (f32) wave row.  No atomics, no scratch, 64-bit offsets.
-template <class WS>
+// kFill: the fill blend o = fl(fl(v * w) + fl(F * fl(1 - w))) with F = p.fill, read once per pixel; without it the arithmetic is o = fl(v * w).
+template <class WS, bool kFill = false>
 __global__ __launch_bounds__(256) void softmask_apply_kernel(const SoftParams p) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -159,9 +230,21 @@ __global__ __launch_bounds__(256) void softmask_apply_kernel(const SoftParams p)
     const int pix = blockIdx.x * 256 + tid;
     if (pix >= hw) return;
     const int y = pix / p.size, x = pix - y * p.size;
-    const typename WS::Pixel px = WS::pixel(p, pix);
+    typename WS::Pixel px = WS::pixel(p, pix);      // not const: the design source keeps what it last read in it
     float v[3];
     load_normalized_pixel(p.img_u8, p.img_f32, p.mean, p.std, pix, hw, v);
+    float f[3] = {0.f, 0.f, 0.f};
+    if (kFill) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = p.fill[(size_t)c * hw + pix];
+    }
+    if (WS::kPinPixel) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v[c] = fp32_value(v[c]);
+            if (kFill) f[c] = fp32_value(f[c]);
+        }
+    }
     const size_t pad_off = staged_pixel_offset(p, y, x);
     for (int mi = 0; mi < mt; ++mi) {
         const int m = m_base + mi;
@@ -170,7 +253,13 @@ __global__ __launch_bounds__(256) void softmask_apply_kernel(const SoftParams p)
         half_t hi[3], lo[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            o[c] = fp32_value(v[c] * w);            // one rounded multiply, pinned: hi and o - hi are taken from the ROUNDED product
+            if (kFill) {
+                const float omw = 1.0f - w;
+                const float a = v[c] * w, b = f[c] * omw;       // contraction is off: two rounded products ...
+                o[c] = fp32_value(a + b);                       // ... and one rounded sum, pinned
+            } else {
+                o[c] = fp32_value(v[c] * w);        // one rounded multiply, pinned: hi and o - hi are taken from the ROUNDED product
+            }
             split_f32(o[c], hi[c], lo[c]);
         }
         store_staged_pixel(p, m, pad_off, pix, hw, staged_h4(hi), staged_h4(lo), o);

@@ -1436,6 +1436,97 @@ class MaskedForwardEngine:
         """deletion_insertion_many for one image: its deletion rows and its insertion rows go through the forward together."""
         return self.deletion_insertion_many([image], [saliency], [label], step=step, del_fill=del_fill, ins_fill=ins_fill, taps=taps)[0]
 
+    # ---- Sobol total-order indices over a grid of cells (csrc/mpx_softmask.h DesignWeights): the design's rows gathered in the apply kernel ----
+    def stage_sobol(self, image, A_d, B_d, grid, row0, m, slot0=0, out_f32=None, fill=None):
+        """mpx_sobol_apply: rows [row0, row0 + m) of the total-order design (A_d, B_d: device f32[N, grid * grid]) into input slots
+        [slot0, slot0 + m); the weights are masks.sobol_weights(A, B, grid, row0, m) bit for bit, gathered from the two matrices in the
+        kernel.  fill: None (normalised image * w) or a device f32[3,224,224] F (fl(fl(v * w) + fl(F * fl(1 - w))): a cell is pulled
+        towards F).  Values outside [0, 1] are the caller's contract (masks.check_sobol verifies host arrays before they are uploaded)."""
+        d = int(grid)
+        if not _lib.SOBOL_GRID_MIN <= d <= _lib.SOBOL_GRID_MAX:
+            raise ValueError("grid=%r outside [%d, %d]" % (grid, _lib.SOBOL_GRID_MIN, _lib.SOBOL_GRID_MAX))
+        for name, t in (("A_d", A_d), ("B_d", B_d)):
+            if (t.device != self.device or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d * d or t.shape[0] != A_d.shape[0]
+                    or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32[N,%d] tensor on %s" % (name, d * d, self.device))
+        if fill is not None and (fill.device != self.device or fill.dtype != torch.float32 or tuple(fill.shape) != (3, IMG, IMG)
+                                 or not fill.is_contiguous()):
+            raise ValueError("fill must be a contiguous float32[3,224,224] tensor on %s" % self.device)
+        m = int(m)
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_sobol_apply(self._h, u8, f32, _ptr(A_d), _ptr(B_d), int(A_d.shape[0]), d, int(row0), m, _ptr(fill),
+                                                      self._mean, self._std, int(slot0), _ptr(out_f32), self._stream()), "mpx_sobol_apply")
+
+    @staticmethod
+    def _sobol_fill_arg(fill):
+        """A driver's `fill`, checked on the host: None, "blur" or an f32[3,224,224] (host or device)."""
+        if fill is None or (isinstance(fill, str) and fill == "blur"):
+            return
+        t = None if isinstance(fill, str) else torch.as_tensor(fill)
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != (3, IMG, IMG):
+            raise ValueError('fill must be None, "blur" or a float32[3,224,224] image, got %r'
+                             % (fill if t is None else (t.dtype, tuple(t.shape)),))
+
+    def _sobol_job(self, image, A, B, grid, fill, taps=None):
+        """What the Sobol drivers check and upload -> (stage(s0, b), rows R, img_d): the design goes up once (2 N D floats), every chunk of
+        rows is gathered from it by mpx_sobol_apply.  Everything is checked before anything touches the device."""
+        self._require_imagenet()
+        A, B = masks.check_sobol(A, B, grid)
+        self._sobol_fill_arg(fill)
+        if taps is not None:
+            taps = masks._check_taps(taps)
+        img_d = self._image_to_device(image)
+        fill_d = self._curve_fill(fill, img_d, taps, "fill")
+        a_d, b_d = torch.from_numpy(A).to(self.device), torch.from_numpy(B).to(self.device)
+
+        def stage(s0, b):
+            self.stage_sobol(img_d, a_d, b_d, grid, s0, b, 0, fill=fill_d)
+
+        return stage, masks.sobol_rows(A.shape[0], grid), img_d
+
+    def score_sobol(self, image, A, B, grid, label, fill=None, return_logits=False):
+        """(image, A f32[N,D], B f32[N,D], grid, label) -> (score f32[R], pred i32[R][, logits f32[R,1000]]), R = N * (D + 1): the scores of
+        the design's rows (masks.sobol_row_cells), whose weights masks.sobol_weights(A, B, grid, 0, R) are gathered in the apply kernel --
+        score_soft_masks of those weights bit for bit, with 2 N D floats uploaded instead of 200 KB per row.  fill: None, "blur" or an
+        f32[3,224,224] (stage_sobol)."""
+        if not 0 <= int(label) < NUM_CLASSES:
+            raise ValueError("label %r outside [0,1000)" % (label,))
+        stage, rows, _img_d = self._sobol_job(image, A, B, grid, fill)
+        return self._score_staged(rows, stage, label, return_logits)
+
+    def score_sobol_classes(self, image, A, B, grid, classes, fill=None):
+        """score_sobol for several classes of the same forwards: -> (scores f32[R,K], pred i32[R]); column i is
+        score_sobol(image, A, B, grid, classes[i], fill)'s scores bit for bit.  classes: a sequence of class indices, or None for all."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        stage, rows, _img_d = self._sobol_job(image, A, B, grid, fill)
+        cls_d, k = self._classes_to_device(cls)
+        scores, pred = self._score_classes_staged(rows, stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def sobol_attribution(self, image, classes=None, top=None, grid=8, n_design=32, seed=0, fill=None, taps=None, out=None):
+        """Sobol total-order indices of the cells of a grid x grid grid (Fel, Cadene, Chalvidal, Cord, Vigouroux, Serre, NeurIPS 2021): the
+        share of each class score's variance that involves a cell, interactions included, from the R = n_design * (grid^2 + 1) rows of
+        A, B = masks.sobol_design(n_design, grid, seed).  -> (classes i32[K], st f64[K,grid,grid], sal f32[K,224,224]);
+        st = masks.sobol_total_order(score_sobol_classes(...), n_design) exactly, sal[k] paints st[k] (rounded to fp32) onto the cells.
+        The design is uploaded once; chunks of max_batch rows run apply -> forward -> class_scores on the stream, the scores come down in
+        ONE download and the estimator runs on the host in fp64.  fill: None (a cell is pulled towards zero), "blur" (towards
+        blur_fill(image, taps), the paper's second perturbation) or an f32[3,224,224].  classes / top / out as rise_saliency_classes."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        A, B = masks.sobol_design(n_design, grid, seed)
+        d = int(grid)
+        self._sobol_fill_arg(fill)
+        self._require_imagenet()
+        cls = self._top_or_given(image, cls, top)
+        stage, rows, _img_d = self._sobol_job(image, A, B, d, fill, taps)
+        cls_d, k = self._classes_to_device(cls)
+        if out is not None:
+            self._sal_maps(out, k)
+        scores, _pred = self._score_classes_staged(rows, stage, cls_d, k)
+        st = masks.sobol_total_order(scores.cpu().numpy(), n_design)
+        seg_d = torch.from_numpy(masks.sobol_cell_map(d)).to(self.device)
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        return cls, st.reshape(k, d, d), self._paint_values(seg_d, st, out)
+
     # ---- kernel variants (tuning / tests) ----
     def set_conv_tile(self, layer, tile):
         """Select the conv kernel variant of one layer (index or torchvision name); tile < 0 = default."""

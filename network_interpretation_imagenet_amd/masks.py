@@ -378,6 +378,126 @@ def segment_paint(seg, value):
     return np.where(inside[None], value[:, np.where(inside, seg, 0)], np.float32(0.0)).astype(np.float32)
 
 
+# ---- Sobol total-order indices over a grid of cells (Fel, Cadene, Chalvidal, Cord, Vigouroux, Serre, NeurIPS 2021) --------------------
+# The design, its rows as csrc/mpx_softmask.h (DesignWeights) gathers them -- the device is held to sobol_weights bit for bit -- and
+# Jansen's total-order estimator, which stays on the host in fp64.
+SOBOL_GRID_MIN, SOBOL_GRID_MAX = 2, 32      # include/mpx.h MPX_SOBOL_GRID_MIN / _MAX: D = d * d <= 1024 cells, segment_paint's limit
+
+
+def _sobol_sizes(n_design, grid):
+    """(N, d, D) of a design, checked: N >= 2 designs over a d x d grid, 2 <= d <= 32."""
+    for name, v in (("n_design", n_design), ("grid", grid)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    n, d = int(n_design), int(grid)
+    if not SOBOL_GRID_MIN <= d <= SOBOL_GRID_MAX:
+        raise ValueError("grid=%r outside [%d, %d]" % (grid, SOBOL_GRID_MIN, SOBOL_GRID_MAX))
+    if n < 2:
+        raise ValueError("n_design=%r: the variance of the score needs at least 2 designs" % (n_design,))
+    if n * (d * d + 1) > 2 ** 31 - 1:
+        raise ValueError("n_design=%r over %d cells: more rows than an int holds" % (n_design, d * d))
+    return n, d, d * d
+
+
+def sobol_rows(n_design, grid):
+    """R = N * (D + 1): the rows (forwards) of a total-order design of N designs over a grid x grid grid, D = grid * grid."""
+    n, _d, D = _sobol_sizes(n_design, grid)
+    return n * (D + 1)
+
+
+def sobol_design(n_design, grid, seed=0):
+    """(A, B), each f32[N, D] in [0, 1): the first N points of ONE scrambled Sobol sequence of dimension 2 D
+    (torch.quasirandom.SobolEngine(2 * D, scramble=True, seed=seed).draw(N)); columns [:D] are A, columns [D:] are B.  Any N >= 2 is taken;
+    a power of two keeps the sequence balanced.  The rows scored are A[j] and, for every cell i, A[j] with cell i taken from B[j]
+    (sobol_row_cells): B itself is never a row.  Jansen's total-order estimator (sobol_total_order) does not read f(B), so the N forwards a
+    Saltelli layout spends on it are not run."""
+    import torch
+    n, _d, D = _sobol_sizes(n_design, grid)
+    pts = torch.quasirandom.SobolEngine(dimension=2 * D, scramble=True, seed=int(seed)).draw(n).numpy().astype(np.float32, copy=False)
+    return np.ascontiguousarray(pts[:, :D]), np.ascontiguousarray(pts[:, D:])
+
+
+def check_sobol(A, B, grid):
+    """What mpx_sobol_apply leaves to the caller: A, B float32[N, grid * grid], finite, within [0, 1], N >= 2, 2 <= grid <= 32.
+    -> (A, B) as contiguous arrays; ValueError otherwise."""
+    A, B = np.asarray(A), np.asarray(B)
+    for name, t in (("A", A), ("B", B)):
+        if t.dtype != np.float32 or t.ndim != 2:
+            raise ValueError("%s must be float32[N, grid * grid], got %s%s" % (name, t.dtype, t.shape))
+    _n, d, D = _sobol_sizes(A.shape[0], grid)
+    if A.shape[1] != D or B.shape != A.shape:
+        raise ValueError("A and B must both be float32[N, %d] for grid=%d, got %s and %s" % (D, d, A.shape, B.shape))
+    for name, t in (("A", A), ("B", B)):
+        if not np.isfinite(t).all() or t.min() < 0.0 or t.max() > 1.0:
+            raise ValueError("%s must be finite and within [0, 1]" % name)
+    return np.ascontiguousarray(A), np.ascontiguousarray(B)
+
+
+def sobol_cell_map(grid):
+    """i32[224,224]: the cell of every pixel, c = ((y * d) // 224) * d + (x * d) // 224 -- piecewise constant cells, as in the paper.  Where
+    d does not divide 224 the cells differ by one pixel (d = 3: 75, 75 and 74 pixels along each axis)."""
+    _n, d, _D = _sobol_sizes(2, grid)
+    a = (np.arange(RISE_IMG, dtype=np.int32) * d) // RISE_IMG
+    return np.ascontiguousarray(a[:, None] * d + a[None, :], dtype=np.int32)
+
+
+def sobol_row_cells(A, B, row0, m):
+    """f32[m, D]: the cells of rows [row0, row0 + m) of the design.  Row r < N is A[r]; row r >= N, with q = r - N, j = q // D and
+    i = q - j * D, is A[j] with cell i taken from B[j] (j-major: the D rows of one A[j] are adjacent)."""
+    A, B = np.asarray(A), np.asarray(B)
+    n, D = A.shape
+    row0, m = int(row0), int(m)
+    if m < 0 or row0 < 0 or row0 + m > n * (D + 1):
+        raise ValueError("rows [%d, %d) outside the design's [0, %d)" % (row0, row0 + m, n * (D + 1)))
+    r = np.arange(row0, row0 + m)
+    q = np.maximum(r - n, 0)
+    j = np.where(r < n, r, q // D)
+    out = A[j].astype(np.float32)           # a copy: fancy indexing
+    sub = np.nonzero(r >= n)[0]
+    i = (q - (q // D) * D)[sub]
+    out[sub, i] = B[j[sub], i]
+    return out
+
+
+def sobol_weights(A, B, grid, row0, m):
+    """f32[m,224,224]: the weight of every pixel under rows [row0, row0 + m), sobol_row_cells(...)[:, sobol_cell_map(grid)] -- a pure gather,
+    the numpy restatement of what mpx_sobol_apply's kernel reads."""
+    A, B = check_sobol(A, B, grid)
+    return np.ascontiguousarray(sobol_row_cells(A, B, row0, m)[:, sobol_cell_map(grid)])
+
+
+def sobol_total_order(scores, n_design):
+    """f64[K, D]: Jansen's total-order indices of D cells from the scores of a design's R = N * (D + 1) rows (f32[R, K], widened to fp64;
+    f32[R] is one class).  With fA = scores[:N] and fC[j][i] = scores[N + j * D + i]:
+        V[k]     = sum_j (fA[j][k] - mean_j fA[.][k])^2 / (N - 1)
+        ST[k][i] = sum_j (fA[j][k] - fC[j][i][k])^2 / (2 N V[k]),     ST[k][.] = 0 where V[k] == 0
+    Every sum runs over j in ascending order, so a class's indices do not depend on which other classes share the call."""
+    s = np.asarray(scores)
+    if s.ndim == 1:
+        s = s[:, None]
+    n = int(n_design)
+    if s.ndim != 2 or n < 2 or s.shape[0] % n or s.shape[0] // n < 2 or s.shape[1] < 1:
+        raise ValueError("scores must be [N * (D + 1), K] with N = n_design >= 2 and D >= 1, got %s for n_design=%r" % (s.shape, n_design))
+    s = s.astype(np.float64)
+    D, K = s.shape[0] // n - 1, s.shape[1]
+    fA, fC = s[:n], s[n:].reshape(n, D, K)
+    total = np.zeros(K)
+    for j in range(n):
+        total = total + fA[j]
+    mean = total / n
+    var, num = np.zeros(K), np.zeros((D, K))
+    for j in range(n):
+        dev = fA[j] - mean
+        var = var + dev * dev
+        diff = fA[j][None, :] - fC[j]
+        num = num + diff * diff
+    var = var / (n - 1)
+    st = np.zeros((K, D))
+    live = var != 0.0
+    st[live] = (num[:, live] / (2.0 * n * var[live])).T
+    return st
+
+
 # ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------
 # The numpy restatements csrc/mpx_rankmask.h is held to bit for bit: a rank per pixel, a threshold per row, a fill image.
 BLUR_KLEN_MAX = 31                  # csrc/mpx_rankmask.h BF_KMAX

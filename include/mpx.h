@@ -627,6 +627,40 @@ int mpx_sobol_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f
                     int row0, int M, const float* fill_f32_chw, const float mean[3], const float std[3], int slot0, float* out_f32_nchw,
                     void* stream);
 
+/* ---- occlusion sensitivity: one sliding box per row, synthesised in the apply kernel; the overlap mean of the score drops ------------
+ * extends: mpx_softmask_apply (a 200 KB weight map per row) to the oldest perturbation method -- Zeiler, Fergus, "Visualizing and
+ *          Understanding Convolutional Networks" (ECCV 2014), Captum's Occlusion, MATLAB's occlusionSensitivity: a box slides over the
+ *          image, the score with the box covered is compared with the score of the whole image, and every pixel gets the mean drop over
+ *          the boxes that cover it.  There is no reference line.  A box is 16 bytes (csrc/mpx_softmask.h BoxWeights, csrc/mpx_occlusion.h).
+ * mpx_box_apply: boxes DEV i32[M][4] = (y0, x0, y1, x1), half-open: pixel (y, x) is covered iff y0 <= y < y1 && x0 <= x < x1.  The contract
+ *   is 0 <= y0 <= y1 <= 224 and 0 <= x0 <= x1 <= 224; an EMPTY box is legal and stages the unoccluded image.  The kernel compares against
+ *   the four values and never indexes by them: a box outside the contract is memory-safe.  The weight is w = covered ? 0.0f : 1.0f and,
+ *   per channel, with v the normalised pixel and F the fill pixel (fill_f32_chw: NULL, or DEV f32[3][224][224] in normalised space):
+ *     without a fill:  o = fl(v * w)                              a covered negative pixel is -0.0, as in mpx_mask_apply_normalize
+ *     with a fill:     o = fl(fl(v * w) + fl(F * fl(1 - w)))      mpx_sobol_apply's blend; as VALUES a select between v and F
+ *   then the hi / lo split, channel 3 = +0.0, the 3-pixel border untouched, out_f32_nchw[m][c][p] = o when given: mpx_softmask_apply's
+ *   planes for the same weights, bit for bit.  No fill is zero in normalised space, the ImageNet mean colour: Zeiler and Fergus's grey
+ *   square.  img_u8_hwc / img_f32_chw, mean, std, slot0, out_f32_nchw: as mpx_softmask_apply.  Marks slots [slot0, slot0 + M)
+ *   input-staged.  MPX_E_STATE on the small networks.  MPX_E_ARG, with nothing written, for a NULL boxes, both or neither image pointer,
+ *   M < 0, slot0 < 0 or slot0 + M > max_batch (checked in 64 bits).  M == 0 succeeds and writes nothing.
+ * mpx_box_saliency_classes: boxes as above; scores DEV f32[M][score_pitch], score_pitch >= K; base DEV f32[K], the scores of the
+ *   unoccluded image (it may point into scores: both are only read); sum DEV f32[K][224][224] and cnt DEV i32[224][224], both accumulated
+ *   in place from what they hold.  For m = 0 .. M - 1 in this order, for every pixel p that box m covers:
+ *     sum[k][p] <- fl(sum[k][p] + fl(base[k] - scores[m * score_pitch + k]))        for every class k
+ *     cnt[p]    <- cnt[p] + 1
+ *   ONE rounded fp32 subtraction and ONE rounded fp32 addition; a box that does not cover p leaves sum[.][p] and cnt[p] unchanged.  One
+ *   thread owns a pixel and a tile of classes and walks the boxes in order (no atomics, no reduction tree): the bits depend neither on the
+ *   launch geometry nor on how the rows are cut into consecutive calls.  Nothing is read beyond scores[..][K) or base[K).
+ * mpx_box_saliency_mean: out[k][p] = cnt[p] > 0 ? sum[k][p] / float(cnt[p]) : 0.0f, one correctly rounded fp32 division; out DEV
+ *   f32[K][224][224] may be sum.
+ * Both: MPX_E_STATE on the small networks; MPX_E_ARG, with nothing launched, for a NULL pointer, M < 0, K <= 0, score_pitch < K.
+ * M == 0 succeeds and writes nothing.  No allocation, no host synchronisation. */
+int mpx_box_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* boxes, int M,
+                  const float* fill_f32_chw, const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream);
+int mpx_box_saliency_classes(mpx_engine* h, const int32_t* boxes, const float* scores, int score_pitch, const float* base, int M, int K,
+                             float* sum, int32_t* cnt, void* stream);
+int mpx_box_saliency_mean(mpx_engine* h, const float* sum, const int32_t* cnt, int K, float* out, void* stream);
+
 /* ---- the score-weighted sum of real-valued masks (RISE's saliency map, before its normalisation) -------------------------------
  * extends: mpx_heatmap_accumulate (counts of binary masks) to  sal[p] <- sal[p] + weight[m] * w_m(p)  for m = 0 .. M - 1 in this order,
  *          accumulated in place in fp32 from the value already in sal (RISE's Monte Carlo estimate: the masks weighted by the class score).

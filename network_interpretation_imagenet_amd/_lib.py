@@ -196,6 +196,10 @@ SIGNATURES = {
     "mpx_segment_paint": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     # the rows of a Sobol total-order design over a d x d grid, gathered from the two design matrices in the apply kernel; the fill blend
     "mpx_sobol_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _fp, _fp, _i, _vp, _vp]),
+    # occlusion sensitivity: one sliding box per row synthesised in the apply kernel; the overlap mean of the score drops (csrc/mpx_occlusion.h)
+    "mpx_box_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _fp, _fp, _i, _vp, _vp]),
+    "mpx_box_saliency_classes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "mpx_box_saliency_mean": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 SOFTMASK_TILE = 32      # csrc/mpx_stage.h STAGE_MT: the rows one block of every apply kernel loops over ...
@@ -203,6 +207,7 @@ RANKMASK_TILE = SOFTMASK_TILE   # ... under the name the rank-mask tests know it
 SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
 SURROGATE_S_MAX = 1024     # csrc/mpx_surrogate.h SUR_S_MAX: the most superpixels mpx_surrogate_accumulate / mpx_segment_paint take
 SOBOL_GRID_MIN, SOBOL_GRID_MAX = 2, 32  # include/mpx.h MPX_SOBOL_GRID_MIN / _MAX (csrc/mpx_softmask.h SOBOL_GRID_*): the grids mpx_sobol_apply takes
+OCCLUSION_BOX_TILE = 256    # csrc/mpx_occlusion.h OCC_BT: the boxes box_saliency_classes_kernel stages in LDS at a time
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes
 
 _lib = None

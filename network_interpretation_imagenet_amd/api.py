@@ -590,6 +590,21 @@ def sobol_saliency(model, image_u8, label=None, classes=None, top=None, grid=8, 
     return model.sobol_attribution(image_u8, classes=classes, top=top, grid=grid, n_design=n_design, seed=seed, fill=fill, out=out)
 
 
+def occlusion_saliency(model, image_u8, label=None, classes=None, top=None, window=32, stride=16, fill=None, out=None):
+    """Occlusion sensitivity (Zeiler & Fergus, ECCV 2014; Captum's Occlusion): -> (classes i32[K], base f32[K], scores f32[R,K],
+    sal f32[K,224,224]) -- a window x window box slides over the image by `stride`, and sal[k][p] is the mean, over the boxes that cover
+    pixel p, of base[k] - scores[r][k]: how much class k's score drops when p is hidden (engine.MaskedForwardEngine.occlusion; the boxes
+    are synthesised in the apply kernel, the overlap mean runs on the device).  label / classes / top as lime_saliency.  window, stride:
+    ints, (h, w) pairs, or window a list of (window, stride) scales.  fill: None covers the box with the mean colour, "blur" with the
+    blurred image, an f32[3,224,224] with that image.  sal[k] feeds deletion_insertion as a RISE map does (out= keeps it, base and scores on
+    the device)."""
+    if label is not None:
+        if classes is not None or top is not None:
+            raise ValueError("give label, classes or top, not several")
+        classes = [_as_int(label)]
+    return model.occlusion(image_u8, classes=classes, top=top, window=window, stride=stride, fill=fill, out=out)
+
+
 def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
     """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
     salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on

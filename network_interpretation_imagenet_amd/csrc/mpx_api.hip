@@ -21,6 +21,7 @@
 #include "mpx_attn.h"
 #include "mpx_softmask.h"
 #include "mpx_saliency_classes.h"
+#include "mpx_occlusion.h"
 #include "mpx_rankmask.h"
 #include "mpx_surrogate.h"
 
@@ -2058,6 +2059,25 @@ int mpx_sobol_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f
     return launch_stage(h, softmask_apply_kernel<DesignWeights>, M, DesignWeights::lds_bytes(d), stream, p);
 }
 
+// one sliding box per row, the weight 0 inside and 1 outside synthesised in the kernel (BoxWeights); with a fill image the blend variant
+int mpx_box_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const int32_t* boxes, int M, const float* fill_f32_chw,
+                  const float mean[3], const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "box_apply: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's");
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, "box_apply", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
+    if (!boxes) return fail(h, MPX_E_ARG, "box_apply: null box pointer");
+    if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
+        return fail(h, MPX_E_ARG, "box_apply: slots [%d,%lld) outside [0, max_batch=%d)", slot0, (long long)slot0 + M, h->max_batch);
+    if (M == 0) return 0;
+    p.boxes = boxes; p.fill = fill_f32_chw;
+    p.out_f32 = out_f32_nchw;
+    p.M = M; p.slot0 = slot0;
+    if (fill_f32_chw) return launch_stage(h, softmask_apply_kernel<BoxWeights, true>, M, BoxWeights::lds_bytes(0), stream, p);
+    return launch_stage(h, softmask_apply_kernel<BoxWeights>, M, BoxWeights::lds_bytes(0), stream, p);
+}
+
 int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weight, int M, float* sal, void* stream) {
     return soft_saliency<ExplicitWeights>(h, "softmask_saliency", weights, nullptr, weight, M, 0, sal, stream);
 }
@@ -2115,6 +2135,36 @@ int mpx_softmask_saliency_classes(mpx_engine* h, const float* weights, const flo
 int mpx_rise_saliency_classes(mpx_engine* h, const uint8_t* cells, const int32_t* shift, const float* scores, int score_pitch, int M, int K,
                               int s, float* sal, void* stream) {
     return soft_saliency_classes<RiseWeights>(h, "rise_saliency_classes", cells, shift, scores, score_pitch, M, K, s, sal, stream);
+}
+
+// ---- occlusion sensitivity (mpx_occlusion.h): the mean score drop over the boxes that cover a pixel, summed and divided on the device ----
+int mpx_box_saliency_classes(mpx_engine* h, const int32_t* boxes, const float* scores, int score_pitch, const float* base, int M, int K,
+                             float* sum, int32_t* cnt, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "box_saliency_classes: this engine runs one of the small networks (no 224 x 224 input)");
+    if (!boxes || !scores || !base || !sum || !cnt) return fail(h, MPX_E_ARG, "box_saliency_classes: null pointer");
+    if (M < 0 || K <= 0 || K > 65535 * SC_KT) return fail(h, MPX_E_ARG, "box_saliency_classes: M=%d K=%d", M, K);
+    if (score_pitch < K) return fail(h, MPX_E_ARG, "box_saliency_classes: score_pitch=%d < K=%d", score_pitch, K);
+    if (M == 0) return 0;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((MPX_IMG * MPX_IMG + OCC_THREADS - 1) / OCC_THREADS, (K + SC_KT - 1) / SC_KT);
+    hipLaunchKernelGGL(box_saliency_classes_kernel, grid, dim3(OCC_THREADS), 0, st, boxes, scores, score_pitch, base, M, K, sum, cnt, MPX_IMG);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_box_saliency_mean(mpx_engine* h, const float* sum, const int32_t* cnt, int K, float* out, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "box_saliency_mean: this engine runs one of the small networks (no 224 x 224 input)");
+    if (!sum || !cnt || !out) return fail(h, MPX_E_ARG, "box_saliency_mean: null pointer");
+    if (K <= 0) return fail(h, MPX_E_ARG, "box_saliency_mean: K=%d", K);
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, std::min(K, 1024));
+    hipLaunchKernelGGL(box_saliency_mean_kernel, grid, dim3(256), 0, st, sum, cnt, K, out, MPX_IMG * MPX_IMG);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
 }
 
 // ---- a linear surrogate over on/off superpixel rows (mpx_surrogate.h): the fp64 moment sums of LIME / KernelSHAP, the paint per superpixel ----

@@ -17,6 +17,12 @@
 //                    integer division per tile row, none per (pixel, row) -- and kept in 256 B of LDS; A and B are read from global memory
 //                    (2 N D floats: the L1 / L2 hold them) when the row base changes and kept in the pixel's state: the D consecutive rows
 //                    of one j differ in the one replaced cell only, so a row is an LDS read and a select.
+//   BoxWeights       w_m(p) = 0 inside the box of row m, 1 outside: the sliding window of occlusion sensitivity (Zeiler, Fergus, "Visualizing
+//                    and Understanding Convolutional Networks", ECCV 2014).  boxes[m] = (y0, x0, y1, x1), DEV i32[M][4], half-open: pixel
+//                    (y, x) is covered iff y0 <= y < y1 && x0 <= x < x1; an empty box (y0 == y1 or x0 == x1) covers nothing.  The tile's
+//                    boxes are 512 B of LDS (every lane reads the same 16 bytes: a broadcast); the kernel COMPARES against the four values
+//                    and never indexes by them, so a box outside [0, 224] is memory-safe whatever the caller passes.  With a fill image
+//                    (kFill) the blend below is, as values, a select between the pixel and the fill pixel.
 // A source is: kLds, kPinPixel (the apply kernel pins the loaded pixel in registers in front of its row loop), lds_bytes(n), stage() (the
 // tile's rows into LDS), Pixel + pixel() (what it keeps per pixel across the rows of a tile;
 // empty for the explicit and the RISE source) and weight().
@@ -38,7 +44,7 @@
 // lies in [0, 1].
 //
 // Apply:    o = fl(v * w) per channel (ONE fp32 multiply, no FMA with the split behind it), then split_f32: hi = f16(o), lo = f16(fl(o -
-//           f32(hi))).  With a fill image F (kFill, the design source only): o = fl(fl(v * w) + fl(F * fl(1 - w))), four fp32 operations each
+//           f32(hi))).  With a fill image F (kFill, the design and the box source): o = fl(fl(v * w) + fl(F * fl(1 - w))), four fp32 operations each
 //           rounded on its own, so that a cell is pulled towards F and not towards zero; w = 1 gives v + F * 0, w = 0 gives v * 0 + F.  For w in {0, 1} that is `x * mask` as numpy does it, the -0.0 of a removed negative pixel included (hi -0.0, lo
 //           +0.0), whichever source the weight comes from.  The product is pinned in an fp32 register (fp32_value, mpx_conv.h) before the
 //           split: hipcc otherwise folds f16(a * b) into v_fma_mixlo_f16, which rounds the exact product to fp16 once and turns a -0.0
@@ -75,6 +81,9 @@ struct SoftParams {
             const float* B;          // [N][d * d]
             const float* fill;       // [3][H][W] or null                  (design source, kFill)
             int N, d, row0;          // designs, grid size, the design row of mask 0
+        };
+        struct {
+            const int32_t* boxes;    // [M][4] = (y0, x0, y1, x1), half-open   (box source; its fill image is the design source's slot)
         };
     };
     const float* score;      // [M]: the weight of mask m in the sum       (saliency)
@@ -208,6 +217,24 @@ struct DesignWeights {
             px.b = fp32_value(b);       // from the registers do not wait for the stores of the row before them
         }
         return i == px.c ? px.b : px.a;
+    }
+};
+
+struct BoxWeights {
+    static constexpr bool kLds = true;
+    // The weight is an LDS read and four compares: with the pixel (and the fill) pinned in front of the row loop no row waits for a load,
+    // and so not for the stores of the rows before it (DesignWeights says why).
+    static constexpr bool kPinPixel = true;
+    typedef NoPixelState Pixel;
+    static size_t lds_bytes(int) { return (size_t)STAGE_MT * 16; }                            // i32[STAGE_MT][4]
+    __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int) {
+        if (tid < mt * 4) ((int*)smem)[tid] = p.boxes[(size_t)m_base * 4 + tid];
+    }
+    __device__ static __forceinline__ Pixel pixel(const SoftParams&, int) { return {}; }
+    __device__ static __forceinline__ float weight(const SoftParams&, const char* smem, Pixel, int, int mi, int, int y, int x, int) {
+        const int4 b = ((const int4*)smem)[mi];     // (y0, x0, y1, x1): compared against, never an index
+        const bool covered = (y >= b.x) & (y < b.z) & (x >= b.y) & (x < b.w);       // & not &&: one 16-byte read, four compares, no branch
+        return covered ? 0.0f : 1.0f;
     }
 };
 

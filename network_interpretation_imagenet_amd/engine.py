@@ -1527,6 +1527,130 @@ class MaskedForwardEngine:
         cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
         return cls, st.reshape(k, d, d), self._paint_values(seg_d, st, out)
 
+    # ---- occlusion sensitivity (csrc/mpx_softmask.h BoxWeights, csrc/mpx_occlusion.h): sliding boxes synthesised in the apply kernel ----
+    def _boxes_d(self, boxes_d):
+        if (boxes_d.device != self.device or boxes_d.dtype != torch.int32 or boxes_d.dim() != 2 or boxes_d.shape[1] != 4
+                or not boxes_d.is_contiguous()):
+            raise ValueError("boxes_d must be a contiguous int32[M,4] tensor on %s" % self.device)
+        return int(boxes_d.shape[0])
+
+    def stage_boxes(self, image, boxes_d, slot0=0, out_f32=None, fill=None):
+        """mpx_box_apply: row m is the image with the box boxes_d[m] = (y0, x0, y1, x1) (device i32[M,4], half-open) covered, into input
+        slots [slot0, slot0 + M); the weights are masks.box_weights(boxes) bit for bit, four compares per pixel in the kernel.  fill:
+        None (a covered pixel is normalised image * 0.0: the mean colour) or a device f32[3,224,224] F (a covered pixel is F's).  The
+        contract 0 <= y0 <= y1 <= 224, 0 <= x0 <= x1 <= 224 is the caller's (masks.check_boxes verifies host arrays before they are
+        uploaded); the kernel never indexes by a box, so one outside it is memory-safe."""
+        m = self._boxes_d(boxes_d)
+        if fill is not None and (fill.device != self.device or fill.dtype != torch.float32 or tuple(fill.shape) != (3, IMG, IMG)
+                                 or not fill.is_contiguous()):
+            raise ValueError("fill must be a contiguous float32[3,224,224] tensor on %s" % self.device)
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_box_apply(self._h, u8, f32, _ptr(boxes_d), m, _ptr(fill), self._mean, self._std, int(slot0),
+                                                    _ptr(out_f32), self._stream()), "mpx_box_apply")
+
+    def _box_job(self, image, boxes, fill, taps=None):
+        """What the box drivers check and upload -> (stage(s0, b), rows M, boxes_d): the boxes go up once (16 bytes a row), every chunk
+        of rows is synthesised from them by mpx_box_apply.  Everything is checked before anything touches the device."""
+        self._require_imagenet()
+        boxes = masks.check_boxes(boxes)
+        self._sobol_fill_arg(fill)
+        if taps is not None:
+            taps = masks._check_taps(taps)
+        img_d = self._image_to_device(image)
+        fill_d = self._curve_fill(fill, img_d, taps, "fill")
+        boxes_d = torch.from_numpy(boxes).to(self.device)
+
+        def stage(s0, b):
+            self.stage_boxes(img_d, boxes_d[s0:s0 + b], 0, fill=fill_d)
+
+        return stage, int(boxes.shape[0]), boxes_d
+
+    def score_boxes(self, image, boxes, label, fill=None, return_logits=False):
+        """(image, boxes i32[M,4], label) -> (score f32[M], pred i32[M][, logits f32[M,1000]]): the scores of the image with one box
+        covered per row -- score_soft_masks(image, masks.box_weights(boxes), label) bit for bit, with 16 bytes uploaded per row instead of
+        200 KB.  fill: None, "blur" or an f32[3,224,224] (stage_boxes)."""
+        if not 0 <= int(label) < NUM_CLASSES:
+            raise ValueError("label %r outside [0,1000)" % (label,))
+        stage, rows, _boxes_d = self._box_job(image, boxes, fill)
+        return self._score_staged(rows, stage, label, return_logits)
+
+    def score_boxes_classes(self, image, boxes, classes, fill=None):
+        """score_boxes for several classes of the same forwards: -> (scores f32[M,K], pred i32[M]); column i is
+        score_boxes(image, boxes, classes[i], fill)'s scores bit for bit.  classes: a sequence of class indices, or None for all."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        stage, rows, _boxes_d = self._box_job(image, boxes, fill)
+        cls_d, k = self._classes_to_device(cls)
+        scores, pred = self._score_classes_staged(rows, stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def _occlusion_maps(self, sum, cnt):
+        if sum.dim() != 3:
+            raise ValueError("sum must be float32[K,224,224]")
+        k = int(sum.shape[0])
+        self._sal_maps(sum, k)
+        if cnt.device != self.device or cnt.dtype != torch.int32 or tuple(cnt.shape) != (IMG, IMG) or not cnt.is_contiguous():
+            raise ValueError("cnt must be a contiguous int32[224,224] tensor on %s" % self.device)
+        return k
+
+    def occlusion_accumulate(self, boxes_d, scores, base, sum, cnt):
+        """mpx_box_saliency_classes: for m ascending, on the pixels box m covers, sum[k][p] <- sum[k][p] + (base[k] - scores[m][k]) (a
+        rounded subtraction and a rounded addition) and cnt[p] <- cnt[p] + 1, in place, on the device -- masks.occlusion_sums bit for bit,
+        however the rows are cut into calls.  boxes_d: device i32[M,4]; scores: device f32[M,K] (class_scores' output, rows >= K floats
+        apart); base: device f32[K], the scores of the whole image (it may be a row of the tensor scores is a view of); sum: device
+        f32[K,224,224]; cnt: device i32[224,224]."""
+        m = self._boxes_d(boxes_d)
+        k = self._occlusion_maps(sum, cnt)
+        if scores.dim() != 2:
+            raise ValueError("scores must be float32[M,K]")
+        pitch = self._class_score_rows(scores, m, k)
+        if base.device != self.device or base.dtype != torch.float32 or tuple(base.shape) != (k,) or not base.is_contiguous():
+            raise ValueError("base must be a contiguous float32[%d] tensor on %s" % (k, self.device))
+        if m == 0:              # an empty tensor has no pointer to hand over, and there is nothing to add
+            return sum, cnt
+        _lib.check(self._h, self._lib.mpx_box_saliency_classes(self._h, _ptr(boxes_d), _ptr(scores), pitch, _ptr(base), m, k, _ptr(sum),
+                                                               _ptr(cnt), self._stream()), "mpx_box_saliency_classes")
+        return sum, cnt
+
+    def occlusion_mean(self, sum, cnt, out=None):
+        """mpx_box_saliency_mean: out[k][p] = sum[k][p] / float(cnt[p]) where cnt[p] > 0 (one rounded division), 0.0 elsewhere --
+        masks.occlusion_mean bit for bit.  out: None (a new device f32[K,224,224]) or a contiguous device f32[K,224,224]; it may be sum."""
+        k = self._occlusion_maps(sum, cnt)
+        if out is None:
+            out = torch.empty(k, IMG, IMG, dtype=torch.float32, device=self.device)
+        self._sal_maps(out, k)
+        _lib.check(self._h, self._lib.mpx_box_saliency_mean(self._h, _ptr(sum), _ptr(cnt), k, _ptr(out), self._stream()),
+                   "mpx_box_saliency_mean")
+        return out
+
+    def occlusion(self, image, classes=None, top=None, window=32, stride=16, fill=None, taps=None, out=None):
+        """Occlusion sensitivity (Zeiler, Fergus, ECCV 2014): a window x window box slides over the image by `stride`
+        (masks.occlusion_boxes; ints, (h, w) pairs, or a list of (window, stride) scales), and every pixel gets the mean, over the R boxes
+        that cover it, of the drop of the class score from the whole image to the image with the box covered.
+        -> (classes i32[K], base f32[K], scores f32[R,K], sal f32[K,224,224]): base the whole image's scores, scores[r] the scores under
+        box r, sal = masks.occlusion_mean(*masks.occlusion_sums(0, 0, boxes, scores, base)) bit for bit.  The job is the empty box, then
+        the R boxes: its row 0 is base.  The boxes are uploaded once; chunks of max_batch rows run apply -> forward -> class_scores on the
+        stream, then one mpx_box_saliency_classes over rows 1 .. R and one mpx_box_saliency_mean, with no download before the end.
+        fill: None (the box is the mean colour), "blur" (blur_fill(image, taps)) or an f32[3,224,224].  classes / top as
+        rise_saliency_classes.  out: None -> host arrays; a contiguous device f32[K,224,224] is overwritten with the maps and returned in
+        their place, and base and scores are returned as device tensors (nothing is downloaded)."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        boxes = np.concatenate([np.zeros((1, 4), dtype=np.int32), masks.occlusion_boxes(window, stride)])
+        self._sobol_fill_arg(fill)
+        self._require_imagenet()
+        cls = self._top_or_given(image, cls, top)
+        stage, rows, boxes_d = self._box_job(image, boxes, fill, taps)
+        cls_d, k = self._classes_to_device(cls)
+        sal = self._sal_out(out, k)
+        cnt = torch.zeros(IMG, IMG, dtype=torch.int32, device=self.device)
+        scores, _pred = self._score_classes_staged(rows, stage, cls_d, k)
+        self.occlusion_accumulate(boxes_d[1:], scores[1:], scores[0], sal, cnt)
+        self.occlusion_mean(sal, cnt, out=sal)
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        if out is not None:
+            return cls, scores[0], scores[1:], sal
+        host = scores.cpu().numpy()
+        return cls, host[0], host[1:], sal.cpu().numpy()
+
     # ---- kernel variants (tuning / tests) ----
     def set_conv_tile(self, layer, tile):
         """Select the conv kernel variant of one layer (index or torchvision name); tile < 0 = default."""

@@ -498,6 +498,96 @@ def sobol_total_order(scores, n_design):
     return st
 
 
+# ---- occlusion sensitivity: a sliding box (Zeiler, Fergus, ECCV 2014; Captum's Occlusion; MATLAB's occlusionSensitivity) ----------------
+# The boxes, their weights as csrc/mpx_softmask.h (BoxWeights) synthesises them, and the overlap mean of the score drops as
+# csrc/mpx_occlusion.h accumulates it -- the device is held to box_weights, occlusion_sums and occlusion_mean bit for bit.  (The window_*
+# names at the top of this module are superpixel index windows of the Bayesian-optimisation loop: another thing.)
+def _occlusion_axes(value, name):
+    """An int, or an (h, w) pair of ints -> (h, w)."""
+    pair = tuple(value) if isinstance(value, (tuple, list, np.ndarray)) else (value, value)
+    if len(pair) != 2 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in pair):
+        raise ValueError("%s must be an int or an (h, w) pair of ints, got %r" % (name, value))
+    return int(pair[0]), int(pair[1])
+
+
+def _occlusion_starts(win, stride):
+    """The starts of a window of `win` pixels sliding by `stride` over 224: n = ceil((224 - win) / stride) + 1 of them, the i-th at
+    min(i * stride, 224 - win) -- the last box is clipped back inside the image, not hung over its edge, so every pixel is covered."""
+    if not 1 <= win <= RISE_IMG:
+        raise ValueError("window %r outside [1, %d]" % (win, RISE_IMG))
+    if stride < 1:
+        raise ValueError("stride %r < 1" % (stride,))
+    n = -(-(RISE_IMG - win) // stride) + 1
+    return [min(i * stride, RISE_IMG - win) for i in range(n)]
+
+
+def occlusion_boxes(window=32, stride=16):
+    """i32[R,4]: the boxes (y0, x0, y1, x1), half-open, of a window sliding over the 224 x 224 image in row-major order.  window, stride:
+    ints or (h, w) pairs; per axis there are ceil((224 - win) / stride) + 1 starts, the last clipped back to 224 - win, so that every pixel
+    is covered by at least one box.  window may also be a LIST of (window, stride) pairs: the boxes of those scales, concatenated (stride is
+    not read then).  ValueError for a window outside [1, 224] or a stride < 1."""
+    if isinstance(window, list):
+        if not window:
+            raise ValueError("an empty list of (window, stride) scales")
+        for scale in window:
+            if not isinstance(scale, (tuple, list)) or len(scale) != 2:
+                raise ValueError("a list of scales holds (window, stride) pairs, got %r" % (scale,))
+        return np.ascontiguousarray(np.concatenate([occlusion_boxes(tuple(w) if isinstance(w, list) else w, s) for w, s in window]))
+    wh, ww = _occlusion_axes(window, "window")
+    sh, sw = _occlusion_axes(stride, "stride")
+    ys, xs = _occlusion_starts(wh, sh), _occlusion_starts(ww, sw)
+    return np.array([(y, x, y + wh, x + ww) for y in ys for x in xs], dtype=np.int32).reshape(-1, 4)
+
+
+def check_boxes(boxes):
+    """What mpx_box_apply leaves to the caller: boxes integer [M,4] = (y0, x0, y1, x1) with 0 <= y0 <= y1 <= 224 and 0 <= x0 <= x1 <= 224
+    (an empty box is legal: it covers nothing).  -> a contiguous i32[M,4]; ValueError otherwise."""
+    b = np.asarray(boxes)
+    if b.ndim != 2 or b.shape[1] != 4 or b.dtype.kind not in "iu":
+        raise ValueError("boxes must be integer [M,4] = (y0, x0, y1, x1), got %s%s" % (b.dtype, b.shape))
+    if b.size and not ((0 <= b[:, :2]).all() and (b[:, :2] <= b[:, 2:]).all() and (b[:, 2:] <= RISE_IMG).all()):
+        raise ValueError("boxes must satisfy 0 <= y0 <= y1 <= %d and 0 <= x0 <= x1 <= %d" % (RISE_IMG, RISE_IMG))
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
+def box_weights(boxes):
+    """f32[M,224,224]: 0.0 inside box m, 1.0 outside -- literal slicing, the numpy restatement of what mpx_box_apply's kernel compares."""
+    b = check_boxes(boxes)
+    w = np.ones((b.shape[0], RISE_IMG, RISE_IMG), dtype=np.float32)
+    for m, (y0, x0, y1, x1) in enumerate(b):
+        w[m, y0:y1, x0:x1] = 0.0
+    return w
+
+
+def occlusion_sums(sum0, cnt0, boxes, scores, base):
+    """(sum f32[K,224,224], cnt i32[224,224]): the restatement csrc/mpx_occlusion.h is held to bit for bit.  From sum0 / cnt0, for m
+    ascending, on the pixels box m covers: sum[k] <- fl(sum[k] + fl(base[k] - scores[m][k])) -- one rounded subtraction, one rounded
+    addition -- and cnt <- cnt + 1; every other pixel keeps its bits.  scores f32[M,K], base f32[K]."""
+    acc = np.array(sum0, dtype=np.float32, copy=True)
+    cnt = np.array(cnt0, dtype=np.int32, copy=True)
+    b = check_boxes(boxes)
+    scores, base = np.asarray(scores, dtype=np.float32), np.asarray(base, dtype=np.float32)
+    if (acc.ndim != 3 or acc.shape[1:] != (RISE_IMG, RISE_IMG) or cnt.shape != (RISE_IMG, RISE_IMG)
+            or scores.shape != (b.shape[0], acc.shape[0]) or base.shape != (acc.shape[0],)):
+        raise ValueError("sum0 [K,224,224], cnt0 [224,224], boxes [M,4], scores [M,K], base [K]; got %s, %s, %s, %s, %s"
+                         % (acc.shape, cnt.shape, b.shape, scores.shape, base.shape))
+    for m, (y0, x0, y1, x1) in enumerate(b):
+        drop = base - scores[m]                     # fp32: one rounding
+        acc[:, y0:y1, x0:x1] = acc[:, y0:y1, x0:x1] + drop[:, None, None]
+        cnt[y0:y1, x0:x1] += 1
+    return acc, cnt
+
+
+def occlusion_mean(sum, cnt):
+    """f32[K,224,224]: sum[k][p] / float32(cnt[p]) where cnt[p] > 0 (one correctly rounded fp32 division), 0.0 where no box covered p."""
+    sum, cnt = np.asarray(sum, dtype=np.float32), np.asarray(cnt)
+    if sum.ndim != 3 or cnt.shape != sum.shape[1:] or cnt.dtype.kind not in "iu":
+        raise ValueError("sum [K,H,W] and integer cnt [H,W]; got %s and %s%s" % (sum.shape, cnt.dtype, cnt.shape))
+    out = np.zeros_like(sum)
+    np.divide(sum, cnt.astype(np.float32)[None], out=out, where=(cnt > 0)[None])
+    return out
+
+
 # ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------
 # The numpy restatements csrc/mpx_rankmask.h is held to bit for bit: a rank per pixel, a threshold per row, a fill image.
 BLUR_KLEN_MAX = 31                  # csrc/mpx_rankmask.h BF_KMAX

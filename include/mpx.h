@@ -661,6 +661,54 @@ int mpx_box_saliency_classes(mpx_engine* h, const int32_t* boxes, const float* s
                              float* sum, int32_t* cnt, void* stream);
 int mpx_box_saliency_mean(mpx_engine* h, const float* sum, const int32_t* cnt, int K, float* out, void* stream);
 
+/* ---- Score-CAM: the network's own activation maps as masks, upsampled in the apply kernel ------------------------------------------------
+ * extends: mpx_softmask_apply (a 200 KB weight map per row) to the family of forward-only attributions whose masks come from inside the
+ *          network -- Wang et al., "Score-CAM: Score-Weighted Visual Explanations for Convolutional Neural Networks" (CVPR-W 2020),
+ *          ScoreCAM in pytorch-grad-cam: every channel of the last feature map is upsampled to the image, normalised to [0, 1] and scored
+ *          as a mask; the class activation map is the sum of the channels weighted by their scores.  There is no reference line.  A row is
+ *          g x g floats (csrc/mpx_softmask.h MapWeights, csrc/mpx_cam.h).
+ * up(G)(y, x), G f32[g][g], 2 <= g <= 16 (MPX_CAM_GRID_MIN / _MAX): bilinear, half-pixel centres, g -> 224, one axis from integers
+ *     t = max((2y + 1) * g - 224, 0);  i0 = t / 448;  r = t - 448 * i0;  f = fl(float(r) / 448.0f);  i1 = min(i0 + 1, g - 1)
+ *     top = fl(fl(fl(1 - fx) * G[i0][j0]) + fl(fx * G[i0][j1])),  bot likewise on row i1,  up = fl(fl(fl(1 - fy) * top) + fl(fy * bot))
+ *   every product and sum rounded on its own, no FMA: torch.nn.functional.interpolate(G, size=(224, 224), mode="bilinear",
+ *   align_corners=False) up to rounding.  An all-ones grid gives exactly 1.0, an all-zeros grid exactly 0.0.
+ * mpx_pool_input: a getter.  Where the global average pool of the op list the last mpx_forward ran (before any: the plain list) reads its
+ *   input: DEV fp16 planes [max_batch][side * side][pitch], of which the first `channels` of every pitch are logical (channels = the input
+ *   width of the logit layer behind the pool; the class count where the pool itself writes the logits), and what the pool applies to a
+ *   value as it loads it: load = 0 nothing, 1 fminf(x, 6), 2 silu(x).  The planes hold the last forward's batch until the next forward.
+ *   MPX_E_STATE, with a text that names the architecture, where the network has no such pool (the VGGs, AlexNet, ViT, the small networks).
+ * mpx_planes_to_chw: out_f32 DEV f32[channels][side][side], out[c][cell] = LOAD(fl(f32(hi) + f32(lo))) of slot `slot` of explicit planes
+ *   [.][side * side][pitch] (as mpx_global_avgpool takes them).  Pad channels [channels, pitch) are not read.  MPX_E_ARG for a NULL
+ *   pointer, side outside [1, 224], channels < 0 or > pitch, load outside [0, 2], slot outside [0, max_batch).  channels == 0 succeeds and
+ *   writes nothing.
+ * mpx_cam_cells: act DEV f32[C][g][g] -> per channel c
+ *     lo[c], hi[c] = min / max over all 224 x 224 pixels of up(act_c)           (the published code normalises the UPSAMPLED map)
+ *     valid[c]     = (max cell > min cell) && (hi[c] > lo[c])                   u8, 1 / 0
+ *     cells[c]     = fl(fl(act_c - lo[c]) / fl(hi[c] - lo[c]))                  one correctly rounded division; all +0.0 where !valid[c]
+ *   cells DEV f32[C][g][g] lie slightly outside [0, 1] (an interior extreme is reached by no pixel centre).  min and max are exact.
+ * mpx_cam_apply: cells DEV f32[M][g][g]; the weight of row m at pixel p is w = min(max(up(cells_m)(p), 0), 1) (as selects: a zero weight is
+ *   +0.0), then mpx_softmask_apply's o = fl(v * w), the hi / lo split, channel 3 = +0.0, the 3-pixel border untouched,
+ *   out_f32_nchw[m][c][p] = o when given: mpx_softmask_apply's planes for the same weights, bit for bit.  img_u8_hwc / img_f32_chw, mean,
+ *   std, slot0, out_f32_nchw: as mpx_softmask_apply.  Marks slots [slot0, slot0 + M) input-staged.
+ * mpx_cam_combine: act DEV f32[R][g][g] (the RAW activations of the scored rows), scores DEV f32[R][score_pitch], score_pitch >= K:
+ *     low[k][cell] = +0.0, then for r = 0 .. R - 1 in this order  low[k][cell] <- fl(low[k][cell] + fl(scores[r * score_pitch + k] * act[r][cell]))
+ *     sal[k][p]    = v > 0 ? v : +0.0  with  v = up(low[k])(p)
+ *   low DEV f32[K][g][g] (the class activation map at layer resolution), sal DEV f32[K][224][224]; both are overwritten.  One thread owns a
+ *   (class, cell) and walks the rows in order: no atomics, no reduction tree.  R == 0 writes zero maps (act and scores may be NULL then).
+ * mpx_cam_cells / _apply / _combine: MPX_E_STATE on the small networks.  MPX_E_ARG, with nothing written or launched, for g outside
+ * [2, 16], a NULL pointer, both or neither image pointer, M / R / C < 0, K <= 0, score_pitch < K, slot0 < 0 or slot0 + M > max_batch
+ * (checked in 64 bits).  M == 0 / C == 0 succeed and write nothing.  No allocation, no host synchronisation. */
+#define MPX_CAM_GRID_MIN 2
+#define MPX_CAM_GRID_MAX 16
+int mpx_pool_input(mpx_engine* h, void** hi, void** lo, int* side, int* channels, int* pitch, int* load);
+int mpx_planes_to_chw(mpx_engine* h, const void* in_hi, const void* in_lo, int slot, int side, int channels, int pitch, int load,
+                      float* out_f32, void* stream);
+int mpx_cam_cells(mpx_engine* h, const float* act, int C, int g, float* cells, float* lo, float* hi, uint8_t* valid, void* stream);
+int mpx_cam_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* cells, int M, int g, const float mean[3],
+                  const float std[3], int slot0, float* out_f32_nchw, void* stream);
+int mpx_cam_combine(mpx_engine* h, const float* act, const float* scores, int score_pitch, int R, int g, int K, float* low, float* sal,
+                    void* stream);
+
 /* ---- the score-weighted sum of real-valued masks (RISE's saliency map, before its normalisation) -------------------------------
  * extends: mpx_heatmap_accumulate (counts of binary masks) to  sal[p] <- sal[p] + weight[m] * w_m(p)  for m = 0 .. M - 1 in this order,
  *          accumulated in place in fp32 from the value already in sal (RISE's Monte Carlo estimate: the masks weighted by the class score).

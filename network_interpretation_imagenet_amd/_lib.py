@@ -200,12 +200,19 @@ SIGNATURES = {
     "mpx_box_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _fp, _fp, _i, _vp, _vp]),
     "mpx_box_saliency_classes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "mpx_box_saliency_mean": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    # Score-CAM: the tap of the pool's input, the normalised cells, the maps upsampled in the apply kernel, the weighted sum (csrc/mpx_cam.h)
+    "mpx_pool_input": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "mpx_planes_to_chw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mpx_cam_cells": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mpx_cam_apply": (_i, [_vp, _vp, _vp, _vp, _i, _i, _fp, _fp, _i, _vp, _vp]),
+    "mpx_cam_combine": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 SOFTMASK_TILE = 32      # csrc/mpx_stage.h STAGE_MT: the rows one block of every apply kernel loops over ...
 RANKMASK_TILE = SOFTMASK_TILE   # ... under the name the rank-mask tests know it by
 SALIENCY_CLASS_TILE = 32    # csrc/mpx_saliency_classes.h SC_KT: the classes one thread of saliency_classes_kernel accumulates
 SURROGATE_S_MAX = 1024     # csrc/mpx_surrogate.h SUR_S_MAX: the most superpixels mpx_surrogate_accumulate / mpx_segment_paint take
+CAM_GRID_MIN, CAM_GRID_MAX = 2, 16     # include/mpx.h MPX_CAM_GRID_MIN / _MAX (csrc/mpx_softmask.h CAM_G_*): the map sides mpx_cam_apply / _cells / _combine take
 SOBOL_GRID_MIN, SOBOL_GRID_MAX = 2, 32  # include/mpx.h MPX_SOBOL_GRID_MIN / _MAX (csrc/mpx_softmask.h SOBOL_GRID_*): the grids mpx_sobol_apply takes
 OCCLUSION_BOX_TILE = 256    # csrc/mpx_occlusion.h OCC_BT: the boxes box_saliency_classes_kernel stages in LDS at a time
 BLUR_KLEN_MAX = 31      # csrc/mpx_rankmask.h BF_KMAX: the most taps mpx_blur_fill takes

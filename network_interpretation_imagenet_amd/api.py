@@ -605,6 +605,21 @@ def occlusion_saliency(model, image_u8, label=None, classes=None, top=None, wind
     return model.occlusion(image_u8, classes=classes, top=top, window=window, stride=stride, fill=fill, out=out)
 
 
+def score_cam_saliency(model, image_u8, label=None, classes=None, top=None, activations=None, out=None):
+    """Score-CAM (Wang et al., CVPR-W 2020; pytorch-grad-cam's ScoreCAM): -> (classes i32[K], channels i32[R], scores f32[R,K],
+    low f32[K,g,g], sal f32[K,224,224]) -- every channel of the map the network's global pool reads becomes a mask (upsampled to the image
+    in the apply kernel, normalised to [0, 1]), scores[r][k] is class k's softmax probability under channel channels[r]'s mask, low[k] the
+    score-weighted sum of the raw channels at layer resolution and sal[k] = relu(up(low[k])) (engine.MaskedForwardEngine.score_cam; the
+    final min-max is the caller's).  label / classes / top as lime_saliency.  activations: None (the tap of the pool's input) or an
+    f32[C,g,g] of another layer, e.g. from a torch hook, 2 <= g <= 16 -- required on a network without a global pool.  sal[k] feeds
+    deletion_insertion as a RISE map does (out= keeps it, scores and low on the device)."""
+    if label is not None:
+        if classes is not None or top is not None:
+            raise ValueError("give label, classes or top, not several")
+        classes = [_as_int(label)]
+    return model.score_cam(image_u8, classes=classes, top=top, activations=activations, out=out)
+
+
 def deletion_insertion(model, image, saliency, label, step=224 * 8, del_fill=None, ins_fill="blur", taps=None):
     """How good is a saliency map?  RISE's causal metrics (Petsiuk, Das, Saenko, BMVC 2018, section 4.1): the class score while the most
     salient pixels are removed `step` at a time (deletion: a sharp drop, a LOW area under the curve, is good) and while they are revealed on

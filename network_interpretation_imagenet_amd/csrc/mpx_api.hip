@@ -22,6 +22,7 @@
 #include "mpx_softmask.h"
 #include "mpx_saliency_classes.h"
 #include "mpx_occlusion.h"
+#include "mpx_cam.h"
 #include "mpx_rankmask.h"
 #include "mpx_surrogate.h"
 
@@ -263,6 +264,7 @@ struct mpx_engine {
     std::vector<PointTail> ptails;
     int ops_pt_x = 0, ops_pt0_x = 0;
     bool fuse_pt = true;            // mpx_forward uses ops_pt / ops_pt0 (mpx_set_fusion bit 2; needs bit 0)
+    const std::vector<Op>* fwd_ops = nullptr;   // the op list the last mpx_forward ran (mpx_pool_input: where that forward's pool read)
     char* arena = nullptr;
     size_t arena_bytes = 0;
     char* tab_arena = nullptr;      // the stem table of one image (CSR, heavy-pixel list, bit planes): allocated by the FIRST mpx_stem_table_build
@@ -2078,6 +2080,25 @@ int mpx_box_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32
     return launch_stage(h, softmask_apply_kernel<BoxWeights>, M, BoxWeights::lds_bytes(0), stream, p);
 }
 
+// one activation map of g x g cells per row, upsampled to 224 x 224 and clamped to [0, 1] in the kernel (MapWeights)
+int mpx_cam_apply(mpx_engine* h, const uint8_t* img_u8_hwc, const float* img_f32_chw, const float* cells, int M, int g, const float mean[3],
+                  const float std[3], int slot0, float* out_f32_nchw, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "cam_apply: this engine runs one of the small networks, whose mask convention is mpx_mask_apply_minmax's");
+    SoftParams p;
+    std::memset(&p, 0, sizeof p);
+    if (const int rc = image_source(h, "cam_apply", p, img_u8_hwc, img_f32_chw, mean, std)) return rc;
+    if (!cells) return fail(h, MPX_E_ARG, "cam_apply: null cells pointer");
+    if (g < CAM_G_MIN || g > CAM_G_MAX) return fail(h, MPX_E_ARG, "cam_apply: g=%d outside [%d, %d]", g, CAM_G_MIN, CAM_G_MAX);
+    if (M < 0 || slot0 < 0 || (long long)slot0 + M > h->max_batch)
+        return fail(h, MPX_E_ARG, "cam_apply: slots [%d,%lld) outside [0, max_batch=%d)", slot0, (long long)slot0 + M, h->max_batch);
+    if (M == 0) return 0;
+    p.maps = cells; p.g = g;
+    p.out_f32 = out_f32_nchw;
+    p.M = M; p.slot0 = slot0;
+    return launch_stage(h, softmask_apply_kernel<MapWeights>, M, MapWeights::lds_bytes(g), stream, p);
+}
+
 int mpx_softmask_saliency(mpx_engine* h, const float* weights, const float* weight, int M, float* sal, void* stream) {
     return soft_saliency<ExplicitWeights>(h, "softmask_saliency", weights, nullptr, weight, M, 0, sal, stream);
 }
@@ -2163,6 +2184,96 @@ int mpx_box_saliency_mean(mpx_engine* h, const float* sum, const int32_t* cnt, i
     hipStream_t st = as_stream(stream);
     const dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, std::min(K, 1024));
     hipLaunchKernelGGL(box_saliency_mean_kernel, grid, dim3(256), 0, st, sum, cnt, K, out, MPX_IMG * MPX_IMG);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// ---- Score-CAM (mpx_cam.h): the tap of the pool's input, the normalised cells of every channel, the score-weighted sum and its upsampling ----
+int mpx_pool_input(mpx_engine* h, void** hi, void** lo, int* side, int* channels, int* pitch, int* load) {
+    if (!h) return MPX_E_ARG;
+    if (!hi || !lo || !side || !channels || !pitch || !load) return fail(h, MPX_E_ARG, "pool_input: null pointer");
+    if (h->small) return fail(h, MPX_E_STATE, "pool_input: arch %d is one of the small networks, whose maps no 224 x 224 mask is made from", h->arch);
+    // the list the last forward ran (the four lists of an engine put the pool's input into buffers of their own); before any, the plain one
+    const std::vector<Op>& ops = h->fwd_ops ? *h->fwd_ops : h->ops;
+    for (const Op& o : ops) {
+        int ld = -1;
+        switch (o.kind) {
+            case OP_AVGPOOL: case OP_AVGPOOLLN: case OP_AVGLOGITS: ld = 0; break;
+            case OP_AVGPOOL6: ld = 1; break;
+            case OP_AVGPOOLSILU: ld = 2; break;
+            default: break;
+        }
+        if (ld < 0) continue;
+        int c = h->ncls;                // OP_AVGLOGITS: the pooled map holds the classes
+        if (o.kind != OP_AVGLOGITS) {
+            c = 0;
+            for (const ConvLayer& L : h->convs)
+                if (L.is_fc) c = L.d.cin;
+        }
+        if (o.in < 0 || c <= 0 || c > o.c) return fail(h, MPX_E_INTERNAL, "pool_input: the pool of arch %d reads buffer %d with %d channels at pitch %d", h->arch, o.in, c, o.c);
+        *hi = h->act_hi[o.in];
+        *lo = h->act_lo[o.in];
+        *side = o.hin; *channels = c; *pitch = o.c; *load = ld;
+        return 0;
+    }
+    const char* family = h->vit ? "ViT" : (h->arch >= MPX_ARCH_ALEXNET && h->arch < MPX_ARCH_ALEXNET + 100) ? "AlexNet"
+                         : (h->arch > MPX_ARCH_VGG && h->arch < MPX_ARCH_VGG_BN + 100) ? "VGG" : "this network";
+    return fail(h, MPX_E_STATE, "pool_input: arch %d (%s) has no global average pool in front of its logits; the VGGs, AlexNet, ViT and the small networks have none",
+                h->arch, family);
+}
+
+int mpx_planes_to_chw(mpx_engine* h, const void* in_hi, const void* in_lo, int slot, int side, int channels, int pitch, int load, float* out_f32,
+                      void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (!in_hi || !in_lo || !out_f32) return fail(h, MPX_E_ARG, "planes_to_chw: null pointer");
+    if (side <= 0 || side > MPX_IMG || channels < 0 || pitch <= 0 || channels > pitch || load < 0 || load > 2)
+        return fail(h, MPX_E_ARG, "planes_to_chw: side=%d channels=%d pitch=%d load=%d (0 < side <= %d, 0 <= channels <= pitch, load 0 plain / 1 clamp6 / 2 silu)",
+                    side, channels, pitch, load, MPX_IMG);
+    if (slot < 0 || (long long)slot >= h->max_batch) return fail(h, MPX_E_ARG, "planes_to_chw: slot %d outside [0, max_batch=%d)", slot, h->max_batch);
+    if (channels == 0) return 0;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    const int hw = side * side;
+    const size_t off = (size_t)slot * hw * pitch;
+    const half_t* a = (const half_t*)in_hi + off;
+    const half_t* b = (const half_t*)in_lo + off;
+    const dim3 grid((channels + CAM_T - 1) / CAM_T, (hw + CAM_T - 1) / CAM_T);
+    if (load == 0) hipLaunchKernelGGL(planes_to_chw_kernel<POOL_PLAIN>, grid, dim3(256), 0, st, a, b, hw, channels, pitch, out_f32);
+    else if (load == 1) hipLaunchKernelGGL(planes_to_chw_kernel<POOL_CLAMP6>, grid, dim3(256), 0, st, a, b, hw, channels, pitch, out_f32);
+    else hipLaunchKernelGGL(planes_to_chw_kernel<POOL_SILU>, grid, dim3(256), 0, st, a, b, hw, channels, pitch, out_f32);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_cam_cells(mpx_engine* h, const float* act, int C, int g, float* cells, float* lo, float* hi, uint8_t* valid, void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "cam_cells: this engine runs one of the small networks (no 224 x 224 input)");
+    if (!act || !cells || !lo || !hi || !valid) return fail(h, MPX_E_ARG, "cam_cells: null pointer");
+    if (g < CAM_G_MIN || g > CAM_G_MAX) return fail(h, MPX_E_ARG, "cam_cells: g=%d outside [%d, %d]", g, CAM_G_MIN, CAM_G_MAX);
+    if (C < 0) return fail(h, MPX_E_ARG, "cam_cells: C=%d", C);
+    if (C == 0) return 0;
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(cam_cells_kernel, dim3(C), dim3(256), 0, st, act, g, cells, lo, hi, valid);
+    MPX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int mpx_cam_combine(mpx_engine* h, const float* act, const float* scores, int score_pitch, int R, int g, int K, float* low, float* sal,
+                    void* stream) {
+    if (!h) return MPX_E_ARG;
+    if (h->small) return fail(h, MPX_E_STATE, "cam_combine: this engine runs one of the small networks (no 224 x 224 input)");
+    if (!low || !sal || ((!act || !scores) && R != 0)) return fail(h, MPX_E_ARG, "cam_combine: null pointer");     // R == 0 reads neither act nor scores
+    if (g < CAM_G_MIN || g > CAM_G_MAX) return fail(h, MPX_E_ARG, "cam_combine: g=%d outside [%d, %d]", g, CAM_G_MIN, CAM_G_MAX);
+    if (R < 0 || K <= 0 || K > 0x7fffffff / (CAM_G_MAX * CAM_G_MAX)) return fail(h, MPX_E_ARG, "cam_combine: R=%d K=%d", R, K);
+    if (score_pitch < K) return fail(h, MPX_E_ARG, "cam_combine: score_pitch=%d < K=%d", score_pitch, K);
+    MPX_SET_DEVICE(h);
+    hipStream_t st = as_stream(stream);
+    const int gg = g * g;
+    hipLaunchKernelGGL(cam_low_kernel, dim3((K * gg + 255) / 256), dim3(256), 0, st, act, scores, score_pitch, R, gg, K, low);
+    MPX_HIP(h, hipGetLastError());
+    const dim3 grid((MPX_IMG * MPX_IMG + 255) / 256, std::min(K, 1024));
+    hipLaunchKernelGGL(cam_sal_kernel, grid, dim3(256), 0, st, (const float*)low, g, K, sal);
     MPX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -2988,6 +3099,7 @@ int mpx_forward(mpx_engine* h, const int32_t* label, float* score, int32_t* pred
     // layer2's pointwise tails likewise (bit 2); a tile override on one of a pair's two layers sends THAT pair through its two layers
     const bool use_pt = h->fuse_pt && h->fuse_ds && !h->ptails.empty();
     const std::vector<Op>& ops = use_pt ? (use_bt ? h->ops_pt : h->ops_pt0) : (use_bt ? h->ops_bt : h->ops);
+    h->fwd_ops = &ops;
     for (size_t oi = 0; oi < ops.size(); ++oi) {
         const Op& o = ops[oi];
         if (stem_done && ((o.kind == OP_CONV && o.conv == 0) || (o.kind == OP_MAXPOOL && o.out == BUF_STEM))) continue;

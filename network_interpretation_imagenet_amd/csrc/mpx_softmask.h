@@ -23,6 +23,13 @@
 //                    boxes are 512 B of LDS (every lane reads the same 16 bytes: a broadcast); the kernel COMPARES against the four values
 //                    and never indexes by them, so a box outside [0, 224] is memory-safe whatever the caller passes.  With a fill image
 //                    (kFill) the blend below is, as values, a select between the pixel and the fill pixel.
+//   MapWeights       w_m(p) = min(max(up(maps[m])(p), 0), 1): the activation maps of Score-CAM (Wang et al., CVPR-W 2020; mpx_cam.h) as
+//                    masks.  maps DEV f32[M][g][g], 2 <= g <= 16 (the normalised cells mpx_cam_cells writes); up() is the RISE upsampling
+//                    below with no shift and U = 224 (cam_axis, cam_up; mpx_cam.h states it).  There is no shift, so the geometry -- i0 * g,
+//                    i1 * g, j0, j1, fy, fx -- is the same for every row and is worked out ONCE per pixel and tile (Pixel), which RISE's
+//                    source cannot do; a row is four LDS reads, nine rounded operations and the clamp.  The tile's 32 x g * g floats
+//                    are staged in LDS (32 KB at g = 16).  The unclamped value leaves [0, 1] by rounding only; the clamp is two selects
+//                    (v > 0 ? v : +0.0, then w < 1 ? w : 1), so that a zero weight is +0.0.
 // A source is: kLds, kPinPixel (the apply kernel pins the loaded pixel in registers in front of its row loop), lds_bytes(n), stage() (the
 // tile's rows into LDS), Pixel + pixel() (what it keeps per pixel across the rows of a tile;
 // empty for the explicit and the RISE source) and weight().
@@ -62,6 +69,9 @@ constexpr int SM_S_MAX = 32;
 constexpr int SM_SAL_THREADS = 64;  // saliency: one wave per block, 784 blocks over the 256 CUs
 constexpr int SOBOL_GRID_MIN = 2;
 constexpr int SOBOL_GRID_MAX = 32;  // D = 1024 cells: mpx_segment_paint's limit (SUR_S_MAX), which paints the indices
+constexpr int CAM_G_MIN = 2;
+constexpr int CAM_G_MAX = 16;       // include/mpx.h MPX_CAM_GRID_MAX: 32 rows x 16 x 16 floats = 32 KB of LDS per apply tile
+constexpr int CAM_IMG = 224;        // the side an activation map is upsampled to
 
 // A launch has ONE weight source, so the design source's fields lie over the other sources' five pointers: the struct keeps its 168 bytes
 // and every field its offset, and with them every kernel that takes (SoftParams, ...) its kernel-argument loads.
@@ -84,6 +94,10 @@ struct SoftParams {
         };
         struct {
             const int32_t* boxes;    // [M][4] = (y0, x0, y1, x1), half-open   (box source; its fill image is the design source's slot)
+        };
+        struct {
+            const float* maps;       // [M][g][g]                          (map source)
+            int g;                   // the maps' side
         };
     };
     const float* score;      // [M]: the weight of mask m in the sum       (saliency)
@@ -113,6 +127,26 @@ __device__ __forceinline__ void rise_axis(int Y, const SoftParams& p, int& i0, i
     i0 = min(q, p.s - 1);           // q <= s - 1 for every shift inside the contract; the clamp keeps a shift outside it inside the grid
     i1 = min(i0 + 1, p.s - 1);
     f = __fdiv_rn((float)r, p.f_U2);
+}
+
+// One axis of the map upsampling g -> 224 at pixel coordinate y (no shift, U = 224): i0, i1 and the fraction, from integers; the one
+// rounding is the division r / 448.
+__device__ __forceinline__ void cam_axis(int y, int g, int& i0, int& i1, float& f) {
+    const int t = max((2 * y + 1) * g - CAM_IMG, 0);
+    i0 = min(t / (2 * CAM_IMG), g - 1);     // t / 448 <= g - 1 inside [0, 224); the clamp keeps a coordinate outside it inside the grid
+    const int r = t - i0 * (2 * CAM_IMG);
+    i1 = min(i0 + 1, g - 1);
+    f = __fdiv_rn((float)r, (float)(2 * CAM_IMG));
+}
+
+// up(G) at one pixel, a0 = i0 * g, a1 = i1 * g: nine operations, each rounded on its own.
+__device__ __forceinline__ float cam_up(const float* G, int a0, int a1, int j0, int j1, float fy, float fx) {
+#pragma clang fp contract(off)
+    const float g00 = G[a0 + j0], g01 = G[a0 + j1], g10 = G[a1 + j0], g11 = G[a1 + j1];
+    const float omx = 1.0f - fx, omy = 1.0f - fy;
+    const float top = omx * g00 + fx * g01;     // contraction is off: two rounded products, one rounded sum
+    const float bot = omx * g10 + fx * g11;
+    return omy * top + fy * bot;
 }
 
 struct NoPixelState {};
@@ -235,6 +269,34 @@ struct BoxWeights {
         const int4 b = ((const int4*)smem)[mi];     // (y0, x0, y1, x1): compared against, never an index
         const bool covered = (y >= b.x) & (y < b.z) & (x >= b.y) & (x < b.w);       // & not &&: one 16-byte read, four compares, no branch
         return covered ? 0.0f : 1.0f;
+    }
+};
+
+struct MapWeights {
+    static constexpr bool kLds = true;
+    // The weight comes from LDS and registers: with the pixel pinned in front of the row loop no row waits for a load, and so not for the
+    // stores of the rows before it (DesignWeights says why).
+    static constexpr bool kPinPixel = true;
+    struct Pixel { int a0, a1, j0, j1; float fy, fx; };      // i0 * g, i1 * g, j0, j1 and the fractions: the same for every row
+    static size_t lds_bytes(int g) { return (size_t)STAGE_MT * g * g * 4; }                   // f32[STAGE_MT][g * g]
+    __device__ static __forceinline__ void stage(const SoftParams& p, char* smem, int m_base, int mt, int tid, int nthreads) {
+        const int gg = p.g * p.g;
+        const float* src = p.maps + (size_t)m_base * gg;
+        for (int i = tid; i < mt * gg; i += nthreads) ((float*)smem)[i] = src[i];
+    }
+    __device__ static __forceinline__ Pixel pixel(const SoftParams& p, int pix) {
+        const int y = pix / p.size, x = pix - y * p.size;
+        Pixel px;
+        int i0, i1;
+        cam_axis(y, p.g, i0, i1, px.fy);
+        cam_axis(x, p.g, px.j0, px.j1, px.fx);
+        px.a0 = i0 * p.g; px.a1 = i1 * p.g;
+        return px;
+    }
+    __device__ static __forceinline__ float weight(const SoftParams& p, const char* smem, const Pixel& px, int, int mi, int, int, int, int) {
+        const float v = cam_up((const float*)smem + mi * p.g * p.g, px.a0, px.a1, px.j0, px.j1, px.fy, px.fx);
+        const float w = v > 0.0f ? v : 0.0f;
+        return w < 1.0f ? w : 1.0f;
     }
 };
 

@@ -312,6 +312,7 @@ class MaskedForwardEngine:
         if not self.has_stem_table and stem == "table":
             raise ValueError("%s has no 7x7 stem: stem='table' is the ImageNet ResNets' path" % arch)
         self.stem = (stem or "table") if self.has_stem_table else "conv"
+        self._last_batch = 0    # the slots the last forward ran (pool_input taps no other)
 
     @property
     def has_stem_table(self):
@@ -540,6 +541,7 @@ class MaskedForwardEngine:
         logits = torch.empty(batch, self.logit_pitch, dtype=torch.float32, device=self.device) if want_logits else None
         _lib.check(self._h, self._lib.mpx_forward(self._h, _ptr(labels), _ptr(score), _ptr(pred), _ptr(logits),
                                                   int(batch), self._stream()), "mpx_forward")
+        self._last_batch = int(batch)
         return (score, pred, logits[:, :self.num_classes]) if want_logits else (score, pred)
 
     def input_plane_shape(self, n):
@@ -1650,6 +1652,154 @@ class MaskedForwardEngine:
             return cls, scores[0], scores[1:], sal
         host = scores.cpu().numpy()
         return cls, host[0], host[1:], sal.cpu().numpy()
+
+    # ---- Score-CAM (csrc/mpx_softmask.h MapWeights, csrc/mpx_cam.h): the network's own activation maps as masks ----
+    def pool_input(self, slot=0):
+        """mpx_pool_input + mpx_planes_to_chw: device f32[C,g,g], the map the global average pool read for row `slot` of the LAST forward,
+        as the pool saw it (its ReLU6 / SiLU on load applied), logical channels only -- Score-CAM's and CAM's default target layer (ResNet's
+        layer4, MobileNetV2's features.18, SqueezeNet's classifier map of 1000 channels ...).  ValueError for a slot the last forward did
+        not run; MpxError (MPX_E_STATE) on a network without such a pool (the VGGs, AlexNet, ViT, the small networks)."""
+        hi, lo = C.c_void_p(), C.c_void_p()
+        side, ch, pitch, load = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._h, self._lib.mpx_pool_input(self._h, C.byref(hi), C.byref(lo), C.byref(side), C.byref(ch), C.byref(pitch),
+                                                     C.byref(load)), "mpx_pool_input")
+        if isinstance(slot, bool) or int(slot) != slot or not 0 <= int(slot) < self._last_batch:
+            raise ValueError("pool_input: slot %r outside the last forward's [0, %d)" % (slot, self._last_batch))
+        out = torch.empty(ch.value, side.value, side.value, dtype=torch.float32, device=self.device)
+        _lib.check(self._h, self._lib.mpx_planes_to_chw(self._h, hi, lo, int(slot), side.value, ch.value, pitch.value, load.value, _ptr(out),
+                                                        self._stream()), "mpx_planes_to_chw")
+        return out
+
+    def _cam_maps(self, t, name):
+        """A contiguous device f32[N,g,g] with 2 <= g <= 16 -> (N, g)."""
+        if (t.device != self.device or t.dtype != torch.float32 or t.dim() != 3 or t.shape[1] != t.shape[2] or not t.is_contiguous()
+                or not masks.CAM_GRID_MIN <= int(t.shape[1]) <= masks.CAM_GRID_MAX):
+            raise ValueError("%s must be a contiguous float32[N,g,g] tensor on %s with g in [%d, %d]"
+                             % (name, self.device, masks.CAM_GRID_MIN, masks.CAM_GRID_MAX))
+        return int(t.shape[0]), int(t.shape[1])
+
+    def cam_cells(self, act_d):
+        """mpx_cam_cells: act_d device f32[C,g,g] -> (cells f32[C,g,g], lo f32[C], hi f32[C], valid u8[C]) on the device --
+        masks.cam_cells bit for bit: every channel normalised by the extremes of its UPSAMPLED map; a flat channel is invalid, cells +0.0."""
+        c, g = self._cam_maps(act_d, "act_d")
+        cells = torch.empty_like(act_d)
+        lo = torch.empty(c, dtype=torch.float32, device=self.device)
+        hi = torch.empty(c, dtype=torch.float32, device=self.device)
+        valid = torch.empty(c, dtype=torch.uint8, device=self.device)
+        if c:
+            _lib.check(self._h, self._lib.mpx_cam_cells(self._h, _ptr(act_d), c, g, _ptr(cells), _ptr(lo), _ptr(hi), _ptr(valid),
+                                                        self._stream()), "mpx_cam_cells")
+        return cells, lo, hi, valid
+
+    def stage_cam(self, image, cells_d, slot0=0, out_f32=None):
+        """mpx_cam_apply: row m is the image times min(max(up(cells_d[m]), 0), 1) (cells_d device f32[M,g,g], upsampled to 224 x 224 in
+        the kernel), into input slots [slot0, slot0 + M); the weights are masks.cam_weights(cells) bit for bit."""
+        m, g = self._cam_maps(cells_d, "cells_d")
+        u8, f32 = self._soft_args(image, out_f32, m)
+        _lib.check(self._h, self._lib.mpx_cam_apply(self._h, u8, f32, _ptr(cells_d), m, g, self._mean, self._std, int(slot0), _ptr(out_f32),
+                                                    self._stream()), "mpx_cam_apply")
+
+    def _cam_job(self, image, cells):
+        """What the row scorers check and upload -> (stage(s0, b), rows M): the cells go up once (g * g floats a row)."""
+        self._require_imagenet()
+        cells = np.ascontiguousarray(cells)
+        if (cells.dtype != np.float32 or cells.ndim != 3 or cells.shape[1] != cells.shape[2]
+                or not masks.CAM_GRID_MIN <= cells.shape[1] <= masks.CAM_GRID_MAX or not np.isfinite(cells).all()):
+            raise ValueError("cells must be finite float32[M,g,g] with g in [%d, %d], got %s%s"
+                             % (masks.CAM_GRID_MIN, masks.CAM_GRID_MAX, cells.dtype, cells.shape))
+        img_d = self._image_to_device(image)
+        cells_d = torch.from_numpy(cells).to(self.device)
+
+        def stage(s0, b):
+            self.stage_cam(img_d, cells_d[s0:s0 + b], 0)
+
+        return stage, int(cells.shape[0])
+
+    def score_cam_rows(self, image, cells, label, return_logits=False):
+        """(image, cells f32[M,g,g], label) -> (score f32[M], pred i32[M][, logits f32[M,1000]]): the scores of the image under the
+        upsampled maps -- score_soft_masks(image, masks.cam_weights(cells), label) bit for bit, with g * g floats uploaded per row instead
+        of 200 KB."""
+        if not 0 <= int(label) < NUM_CLASSES:
+            raise ValueError("label %r outside [0,1000)" % (label,))
+        stage, rows = self._cam_job(image, cells)
+        return self._score_staged(rows, stage, label, return_logits)
+
+    def score_cam_rows_classes(self, image, cells, classes):
+        """score_cam_rows for several classes of the same forwards: -> (scores f32[M,K], pred i32[M]); column i is
+        score_cam_rows(image, cells, classes[i])'s scores bit for bit.  classes: a sequence of class indices, or None for all."""
+        cls = masks.class_selection(classes, None, NUM_CLASSES)[0]
+        stage, rows = self._cam_job(image, cells)
+        cls_d, k = self._classes_to_device(cls)
+        scores, pred = self._score_classes_staged(rows, stage, cls_d, k)
+        return scores.cpu().numpy(), pred.cpu().numpy()
+
+    def cam_combine(self, act_d, scores, low=None, out=None):
+        """mpx_cam_combine: (low f32[K,g,g], sal f32[K,224,224]) on the device -- masks.cam_combine bit for bit: low[k] = the sum over the
+        rows r, in order, of scores[r][k] * act_d[r] (a rounded product and a rounded sum per step, the RAW activations), sal[k] =
+        relu(up(low[k])).  act_d: device f32[R,g,g]; scores: device f32[R,K] (class_scores' output, rows >= K floats apart); low / out:
+        None or contiguous device f32[K,g,g] / f32[K,224,224], overwritten.  R = 0 gives zero maps."""
+        r, g = self._cam_maps(act_d, "act_d")
+        if scores.dim() != 2 or scores.shape[1] < 1:
+            raise ValueError("scores must be float32[R,K] with K >= 1")
+        k = int(scores.shape[1])
+        pitch = self._class_score_rows(scores, r, k)
+        if low is None:
+            low = torch.empty(k, g, g, dtype=torch.float32, device=self.device)
+        if low.device != self.device or low.dtype != torch.float32 or tuple(low.shape) != (k, g, g) or not low.is_contiguous():
+            raise ValueError("low must be a contiguous float32[%d,%d,%d] tensor on %s" % (k, g, g, self.device))
+        if out is None:
+            out = torch.empty(k, IMG, IMG, dtype=torch.float32, device=self.device)
+        self._sal_maps(out, k)
+        _lib.check(self._h, self._lib.mpx_cam_combine(self._h, _ptr(act_d) if r else None, _ptr(scores) if r else None, pitch, r, g, k,
+                                                      _ptr(low), _ptr(out), self._stream()), "mpx_cam_combine")
+        return low, out
+
+    def score_cam(self, image, classes=None, top=None, activations=None, out=None):
+        """Score-CAM (Wang et al., CVPR-W 2020): every channel of the map the global pool reads is upsampled to the image, normalised to
+        [0, 1] and scored as a mask; the class activation map is the channels' sum weighted by those scores.
+        -> (classes i32[K], channels i32[R], scores f32[R,K], low f32[K,g,g], sal f32[K,224,224]): channels the R channels that are not
+        flat (a flat one is skipped, as published), scores[r][k] the softmax probability of class k under channel channels[r]'s mask,
+        (low, sal) = masks.cam_combine(act[channels], scores) bit for bit -- low the map at layer resolution, sal = relu(up(low)) before
+        the caller's min-max.  ONE unmasked forward (staged through the box entry with the empty box) gives the logits behind top= and the
+        tap pool_input(0); activations= (f32[C,g,g], e.g. from a torch hook) replaces the tap -- the only way on a network without a
+        global pool.  valid comes down (C bytes), the valid channels are compacted with a torch index, chunks of max_batch rows run apply ->
+        forward -> class_scores on the stream, then one mpx_cam_combine; one download at the end.  classes / top as rise_saliency_classes.
+        out: None -> host arrays; a contiguous device f32[K,224,224] is overwritten with the maps and returned in their place, and
+        scores and low are returned as device tensors (nothing further is downloaded)."""
+        cls, top = masks.class_selection(classes, top, NUM_CLASSES)
+        self._require_imagenet()
+        if activations is not None:
+            activations = masks.check_activations(activations)
+        img_d = self._image_to_device(image)
+        if top is not None or activations is None:
+            labels = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.stage_boxes(img_d, torch.zeros(1, 4, dtype=torch.int32, device=self.device), 0)
+            logits = self.forward(1, labels, want_logits=True)[2]
+            if activations is None:
+                act_d = self.pool_input(0)
+            if top is not None:
+                cls = masks.top_classes(logits[0].cpu().numpy(), top)
+        if activations is not None:
+            act_d = torch.from_numpy(activations).to(self.device)
+        cls_d, k = self._classes_to_device(cls)
+        if out is not None:
+            self._sal_maps(out, k)
+        cells_d, _lo, _hi, valid = self.cam_cells(act_d)
+        keep = torch.nonzero(valid.cpu()).reshape(-1)                  # C bytes come down; the compaction is a torch index
+        keep_d = keep.to(self.device)
+        cells_d, act_d = cells_d[keep_d].contiguous(), act_d[keep_d].contiguous()
+        rows = int(keep.numel())
+
+        def stage(s0, b):
+            self.stage_cam(img_d, cells_d[s0:s0 + b], 0)
+
+        scores, _pred = self._score_classes_staged(rows, stage, cls_d, k)
+        low, sal = self.cam_combine(act_d, scores, out=out)
+        cls = np.arange(NUM_CLASSES, dtype=np.int32) if cls is None else cls
+        channels = keep.numpy().astype(np.int32)
+        if out is not None:
+            return cls, channels, scores, low, sal
+        return cls, channels, scores.cpu().numpy(), low.cpu().numpy(), sal.cpu().numpy()
 
     # ---- kernel variants (tuning / tests) ----
     def set_conv_tile(self, layer, tile):

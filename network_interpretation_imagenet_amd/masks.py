@@ -588,6 +588,101 @@ def occlusion_mean(sum, cnt):
     return out
 
 
+# ---- Score-CAM: the network's own activation maps as masks (Wang et al., CVPR-W 2020; ScoreCAM in pytorch-grad-cam) ---------------------
+# The numpy fp32 restatements csrc/mpx_cam.h and csrc/mpx_softmask.h (MapWeights) are held to bit for bit: the upsampling g -> 224, the
+# normalised cells of every channel, the weight of a row, the score-weighted sum at layer resolution and its upsampling.
+CAM_GRID_MIN, CAM_GRID_MAX = 2, 16  # include/mpx.h MPX_CAM_GRID_MIN / _MAX
+
+
+def _cam_grid(g):
+    if isinstance(g, (bool, np.bool_)) or int(g) != g or not CAM_GRID_MIN <= int(g) <= CAM_GRID_MAX:
+        raise ValueError("g=%r outside [%d, %d]" % (g, CAM_GRID_MIN, CAM_GRID_MAX))
+    return int(g)
+
+
+def cam_axis(g):
+    """(i0 i64[224], i1 i64[224], f f32[224]): one axis of the bilinear upsampling g -> 224 with half-pixel centres, from integers --
+    t = max((2y + 1) g - 224, 0), i0 = t // 448, r = t - 448 i0, f = fl(float(r) / 448.0f) (ONE fp32 division), i1 = min(i0 + 1, g - 1):
+    RISE's axis (_rise_axis) with no shift and U = 224."""
+    g = _cam_grid(g)
+    i0, i1, f = _rise_axis(np.arange(RISE_IMG, dtype=np.int64), g, RISE_IMG)
+    return i0, i1, f
+
+
+def cam_upsample(G):
+    """f32[..., 224, 224] = up(G) of G f32[..., g, g]: top = fl(fl(fl(1 - fx) G[i0][j0]) + fl(fx G[i0][j1])), bot the same on row i1,
+    up = fl(fl(fl(1 - fy) top) + fl(fy bot)) -- every product and sum rounded on its own, products before their sum, no FMA;
+    torch.nn.functional.interpolate(G, size=(224, 224), mode="bilinear", align_corners=False) up to rounding."""
+    G = np.asarray(G, dtype=np.float32)
+    if G.ndim < 2 or G.shape[-1] != G.shape[-2]:
+        raise ValueError("G must be [..., g, g], got %s" % (G.shape,))
+    i0, i1, f = cam_axis(G.shape[-1])
+    one = np.float32(1.0)
+    fy, fx = f[:, None], f[None, :]
+    omy, omx = one - fy, one - fx
+    r0, r1 = G[..., i0, :], G[..., i1, :]                   # [..., 224, g]
+    top = omx * r0[..., i0] + fx * r0[..., i1]
+    bot = omx * r1[..., i0] + fx * r1[..., i1]
+    return omy * top + fy * bot
+
+
+def check_activations(act):
+    """What the Score-CAM driver refuses before anything is uploaded: act f32[C, g, g], finite, 2 <= g <= 16, C >= 1.  -> contiguous."""
+    a = np.asarray(act)
+    if a.dtype != np.float32 or a.ndim != 3 or a.shape[1] != a.shape[2] or a.shape[0] < 1:
+        raise ValueError("activations must be float32[C,g,g] with C >= 1, got %s%s" % (a.dtype, a.shape))
+    _cam_grid(a.shape[1])
+    if not np.isfinite(a).all():
+        raise ValueError("activations must be finite")
+    return np.ascontiguousarray(a)
+
+
+def cam_cells(act):
+    """(cells f32[C,g,g], lo f32[C], hi f32[C], valid u8[C]) of act f32[C,g,g]: lo_c / hi_c = min / max over the 224 x 224 values of
+    cam_upsample(act_c) (the published code normalises the UPSAMPLED map; its extremes are not the cells'), valid_c = (max cell > min cell)
+    and (hi_c > lo_c), cells_c = fl(fl(act_c - lo_c) / fl(hi_c - lo_c)) where valid and +0.0 elsewhere.  The cells lie slightly outside
+    [0, 1] where an interior extreme is reached by no pixel centre."""
+    act = check_activations(act)
+    c = act.shape[0]
+    lo, hi = np.empty(c, dtype=np.float32), np.empty(c, dtype=np.float32)
+    for a in range(0, c, 64):           # in blocks: cam_upsample holds a few [C,224,224] temporaries
+        up = cam_upsample(act[a:a + 64]).reshape(-1, RISE_IMG * RISE_IMG)
+        lo[a:a + 64], hi[a:a + 64] = up.min(axis=1), up.max(axis=1)
+    flat = act.reshape(c, -1)
+    valid = (flat.max(axis=1) > flat.min(axis=1)) & (hi > lo)
+    cells = np.zeros_like(act)
+    num = act[valid] - lo[valid][:, None, None]
+    cells[valid] = num / (hi[valid] - lo[valid])[:, None, None]
+    return cells, lo, hi, valid.astype(np.uint8)
+
+
+def cam_weights(cells):
+    """f32[M,224,224]: w = min(max(cam_upsample(cells_m), 0), 1), as two selects (v > 0 ? v : +0.0, then w < 1 ? w : 1) -- what
+    mpx_cam_apply's kernel multiplies the image by.  The unclamped value leaves [0, 1] by rounding only."""
+    v = cam_upsample(cells)
+    w = np.where(v > 0, v, np.float32(0.0))
+    return np.where(w < 1, w, np.float32(1.0)).astype(np.float32)
+
+
+def cam_combine(act, scores, low0=None):
+    """(low f32[K,g,g], sal f32[K,224,224]): low[k] starts at +0.0 (or low0: the sum of the rows before these) and takes
+    low[k] <- fl(low[k] + fl(scores[r][k] * act_r)) for r ascending -- a rounded product and a rounded sum, no FMA, the RAW activations as
+    published --, sal[k] = v > 0 ? v : +0.0 with v = cam_upsample(low[k]).  act f32[R,g,g], scores f32[R,K]; R = 0 gives zero maps."""
+    act, scores = np.asarray(act, dtype=np.float32), np.asarray(scores, dtype=np.float32)
+    if act.ndim != 3 or act.shape[1] != act.shape[2] or scores.ndim != 2 or scores.shape[0] != act.shape[0] or scores.shape[1] < 1:
+        raise ValueError("act [R,g,g] and scores [R,K] with K >= 1; got %s and %s" % (act.shape, scores.shape))
+    g = _cam_grid(act.shape[1])
+    k = scores.shape[1]
+    low = np.zeros((k, g, g), dtype=np.float32) if low0 is None else np.array(low0, dtype=np.float32, copy=True)
+    if low.shape != (k, g, g):
+        raise ValueError("low0 must be [%d,%d,%d], got %s" % (k, g, g, low.shape))
+    for r in range(act.shape[0]):
+        prod = scores[r][:, None, None] * act[r][None]
+        low = low + prod
+    v = cam_upsample(low)
+    return low, np.where(v > 0, v, np.float32(0.0)).astype(np.float32)
+
+
 # ---- deletion / insertion curves of a saliency map (Petsiuk, Das, Saenko, BMVC 2018, section 4.1) ---------------------------------
 # The numpy restatements csrc/mpx_rankmask.h is held to bit for bit: a rank per pixel, a threshold per row, a fill image.
 BLUR_KLEN_MAX = 31                  # csrc/mpx_rankmask.h BF_KMAX
